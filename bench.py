@@ -1,8 +1,18 @@
 """Benchmark of the hot path: fp64 CG on the 3-D Poisson CSR matrix.
 
     python bench.py --gpus 1 --steps 100 --warmup 10
+    python bench.py --gpus 1 --steps 100 --warmup 10 --full
+    python bench.py --gpus 1 --steps 100 --warmup 10 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.
+Everything else it can measure -- the CPU baseline and its parity checks, the
+AUTO plan's run (`roofline.specialised`) and the sub-records (symmetric
+storage, LX / row-block / 216^3 / 27-point / ragged / mixed-precision) --
+runs only with --full.  --dump-outputs DIR writes what the timed steps
+computed (x at a fixed seeded sample of rows, the residual history) as .npy
+files, so that two builds can be compared output for output.
 
 One "step" = one CG iteration of spmv::cg (spmv/cg.cpp:55-86): halo update of
 p, SpMV (local + remote block) with the fused p.Ap, x/r update with the fused
@@ -14,8 +24,8 @@ generated on the device, inputs resident in HBM before the timed region.
 Prints ONE JSON line on rank 0.  `value` = CG iterations per second of the
 whole job; `roofline` describes the dominant kernel (the local-block CSR
 SpMV), timed live with HIP events on its own stream inside the timed region;
-`cpu_baseline` is the oracle's OpenMP SpMV + CG (= the reference's CPU path,
-restated) on the host cores this job may use, rank 0 at N = 1 only.
+`cpu_baseline` (--full) is the oracle's OpenMP SpMV + CG (= the reference's
+CPU path, restated) on the host cores this job may use, rank 0 at N = 1 only.
 
 What the headline times (round 6).  `value`, `ms_per_step` and `roofline`
 belong to the CSR-ORDER plan: the matrix as a general CSR matrix, the
@@ -27,7 +37,7 @@ algorithmic bytes B_csr (12 B per entry, row pointer, x, y) / the kernel's
 average launch time measured live / 8 TB/s; `bytes_per_launch` = B_csr; and
 (B_csr + 9 N 8) / ms_per_step stays below the peak.  What the AUTO plan does
 with THIS matrix -- it finds the lattice and that every diagonal is constant,
-and streams no matrix at all -- is faster and is reported beside it as
+and streams no matrix at all -- is faster and is reported beside it (--full) as
 `roofline.specialised` (`--specialised` makes it the main line, as in rounds
 1-5): there `frac_physical` prices the bytes that kernel's own format moves and
 `frac_csr_equivalent` prices B_csr over its time -- a speed-up statement that
@@ -69,7 +79,7 @@ def parse():
                          "treats that as an abbreviation of its options)")
     ap.add_argument("--symmetric", action="store_true",
                     help="symmetric-CSR storage (BASELINE configs[3]) as the "
-                         "main line (the default line carries it as a "
+                         "main line (the --full line carries it as a "
                          "sub-record)")
     ap.add_argument("--peer-reduce", action="store_true",
                     help="N > 1: the two scalar reductions of a CG iteration by the "
@@ -83,9 +93,22 @@ def parse():
                     help="halo model; onesided_put_active: peer stores into "
                          "IPC-mapped windows instead of RCCL send/recv "
                          "(DESIGN.md section 6; never yet run over xGMI)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the CPU "
+                         "baseline and its parity checks, the AUTO plan's run "
+                         "(roofline.specialised), the symmetric / LX / 216^3 / "
+                         "ragged / mixed-precision sub-records.  Off: set-up, "
+                         "warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed as "
+                         "DIR/<name>.npy (float64): x_sample (the solution at a "
+                         "fixed seeded sample of at most 2^21 global rows, all "
+                         "rows if there are fewer), x_sample_index (those rows) "
+                         "and residual_history (||r_k||, k = 0..K)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: no CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="main line only: no symmetric / LX / 216^3 sub-records")
+                    help="with --full: no symmetric / LX / 216^3 sub-records")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "gloo"],
                     help="gloo: REHEARSAL ONLY -- halo and reductions staged "
                          "through the host so that several ranks can share one "
@@ -880,6 +903,42 @@ def emit(out, args):
     print(text, flush=True)
 
 
+# ---------------------------------------------------------------------------
+# --dump-outputs: what the timed CG returned, comparable between two builds
+# ---------------------------------------------------------------------------
+DUMP_SAMPLE = 1 << 21  # rows of x written (16 MiB of values, 16 MiB of indices)
+DUMP_SEED = 512
+
+
+def dump_outputs(path, exec_, d_x, M, N, offset, hist, world, rank, dist):
+    """x after the last timed step at a fixed seeded sample of global rows (the
+    same rows for every rank count), and the residual history, as
+    path/<name>.npy in float64 (rank 0 writes)"""
+    import numpy as np
+    if N <= DUMP_SAMPLE:
+        idx = np.arange(N, dtype=np.int64)
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        idx = np.sort(rng.choice(N, DUMP_SAMPLE, replace=False))
+    exec_.synchronize()
+    x = exec_.copy_to_host(d_x, M)
+    lo, hi = np.searchsorted(idx, [offset, offset + M])
+    mine = x[idx[lo:hi] - offset]
+    del x
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, (offset, mine))
+        mine = np.concatenate([v for _, v in sorted(parts, key=lambda p: p[0])])
+    if rank != 0:
+        return
+    assert len(mine) == len(idx), (len(mine), len(idx))
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("x_sample", mine), ("x_sample_index", idx),
+                    ("residual_history", hist)):
+        np.save(os.path.join(path, name + ".npy"),
+                np.ascontiguousarray(a, dtype=np.float64))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks as
     CHILD processes through torch.distributed.run and wait.  This parent has
@@ -925,7 +984,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     # before torch is imported: with OMP_PROC_BIND set, the first OpenMP runtime
     # that starts pins this thread to one core and the mask would read "1 core"
-    host_cores = usable_cores()
+    host_cores = usable_cores() if args.full else None
 
     import numpy as np
     import torch
@@ -1083,6 +1142,9 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     assert k == args.steps, (k, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, exec_, d_x, M, N, l2g.global_offset(),
+                     hist, world, rank, dist)
 
     # algorithmic bytes of the dominant kernel on THIS rank (DESIGN.md,
     # SURVEY 8d), and the bytes its form really loads and stores
@@ -1239,7 +1301,7 @@ def main():
     exec_.free(d_b), exec_.free(d_x)
 
     if rank == 0:
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             self_comm = comm
             # Time to solution by the reference demo's protocol
             # (demos/cg.cpp:64-72: max_its = 100, rtol = 1e-10, wall clock
@@ -1577,7 +1639,7 @@ def main():
                 # mixed-precision CG against pure fp64, to 1e-10
                 out["mixed_precision_cg"] = mixed_precision_record(
                     exec_, self_comm, host, _lib, args.mixed_grid)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, n, N, host_cores)
             if not args.no_extras:
                 out["cpu_baseline"]["parity_checks"] = oracle_parity_checks(

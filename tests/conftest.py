@@ -6,8 +6,10 @@ import pytest
 # Tests that run several ranks as THREADS of this process give every rank its
 # own streams; the HIP runtime multiplexes a process's streams onto a few
 # hardware queues (four by default), where a kernel that polls for a neighbour
-# can sit in front of the neighbour's kernel.  More queues, before HIP starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
+# can sit in front of the neighbour's kernel.  More queues, before HIP starts,
+# also where the environment pins fewer (a launcher may pass HIP's own four).
+if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 24:
+    os.environ["GPU_MAX_HW_QUEUES"] = "24"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

@@ -95,7 +95,7 @@ def test_bench_single_gpu_line(tmp_path):
     line, d = _run(["--grid", "64", "--steps", "20", "--warmup", "3",
                     "--cpu-n", "32", "--cpu-iters", "3", "--mixed-grid",
                     "48", "--stencil27-grid", "40", "--unstructured-rows",
-                    "200000", "--fem-rows", "200000"], tmp_path)
+                    "200000", "--fem-rows", "200000", "--full"], tmp_path)
     _check(line, d, 1, 20, 3)
     # the compact line: what the driver keeps
     lc, lr = line["cpu_baseline"], line["roofline"]
@@ -226,6 +226,53 @@ def test_bench_single_gpu_line(tmp_path):
     assert mp["x_rel_diff"] < 1e-7
 
 
+def _dumped(path):
+    """the .npy files --dump-outputs wrote -> {name: array}"""
+    import numpy as np
+    names = sorted(p.name for p in path.iterdir())
+    assert names == ["residual_history.npy", "x_sample.npy",
+                     "x_sample_index.npy"], names
+    out = {n[:-4]: np.load(path / n) for n in names}
+    assert all(a.dtype == np.float64 for a in out.values())
+    return out
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the run times the headline and measures nothing beside
+    it; --dump-outputs writes what the timed CG computed (every row of x at
+    this size, the residual history): the same bits from run to run, and the
+    oracle's CG of the same K iterations from x = 0."""
+    import numpy as np
+    import oracle
+    from spmv_amd import poisson
+    n, steps = 64, 12
+    runs = []
+    for rep in ("a", "b"):
+        (tmp_path / rep).mkdir()
+        line, d = _run(["--grid", str(n), "--steps", str(steps), "--warmup", "2",
+                        "--dump-outputs", str(tmp_path / rep / "out")],
+                       tmp_path / rep)
+        _check(line, d, 1, steps, 2)
+        assert line["roofline"]["kernel"] == "csr_lxw_kernel<double>"
+        for k in ("cpu_baseline", "symmetric", "time_to_solution",
+                  "specialised_cg", "north_star_spmv", "mixed_precision_cg"):
+            assert k not in line and k not in d, k
+        assert "specialised" not in d["roofline"] and "ragged" not in d["roofline"]
+        runs.append(_dumped(tmp_path / rep / "out"))
+    a, b = runs
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    N = n ** 3
+    assert np.array_equal(a["x_sample_index"], np.arange(N, dtype=np.float64))
+    assert len(a["residual_history"]) == steps + 1
+    rp, ci, va = poisson.poisson3d_csr(n)
+    x_ref, k_ref, hist_ref = oracle.cg(rp, ci.astype(np.int32), va,
+                                       oracle.gaussian_x_fast(N), steps, 0.0)
+    assert k_ref == steps
+    assert np.allclose(a["residual_history"], hist_ref, rtol=1e-8, atol=0)
+    assert np.linalg.norm(a["x_sample"] - x_ref) <= 1e-9 * np.linalg.norm(x_ref)
+
+
 def test_bench_without_the_symmetry_check(tmp_path):
     """--no-bake: the line of a lattice matrix whose values stay in CSR order
     (the CSR-order lattice kernel; DESIGN.md section 7, 'reading the headline')."""
@@ -258,10 +305,10 @@ def _torchrun(nproc):
             str(nproc), "--master-addr", "127.0.0.1", "--master-port", str(port)]
 
 
-def _k10_one_rank(grid, steps, tmp_path):
+def _k10_one_rank(grid, steps, tmp_path, dump=()):
     (tmp_path / "one").mkdir(exist_ok=True)
     line, _ = _run(["--grid", str(grid), "--steps", str(steps), "--warmup", "2",
-                    "--no-cpu-baseline", "--no-extras"], tmp_path / "one")
+                    "--no-cpu-baseline", "--no-extras", *dump], tmp_path / "one")
     return line["cg_rel_residual"]["k10"]
 
 
@@ -273,7 +320,8 @@ def test_bench_two_rank_rehearsal_self_launched(tmp_path, monkeypatch):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         monkeypatch.delenv(k, raising=False)
     line, d = _run(["--gpus", "2", "--steps", "10", "--warmup", "2", "--grid", "64",
-                    "--transport", "gloo"], tmp_path)
+                    "--transport", "gloo", "--dump-outputs",
+                    str(tmp_path / "out2")], tmp_path)
     _check(line, d, 2, 10, 2)
     assert "child processes" in line["launcher"]
     assert "REHEARSAL" in line["data"] and "cpu_baseline" not in line
@@ -284,8 +332,17 @@ def test_bench_two_rank_rehearsal_self_launched(tmp_path, monkeypatch):
     assert sum(r[2] for r in line["ranks"]) == 64 ** 3
     assert [r["ghosts"] for r in d["ranks"]] == [64 * 64, 64 * 64]
     # the distributed run reproduces the one-rank residual after 10 iterations
-    k10 = _k10_one_rank(64, 10, tmp_path)
+    k10 = _k10_one_rank(64, 10, tmp_path,
+                        dump=("--dump-outputs", str(tmp_path / "out1")))
     assert abs(line["cg_rel_residual"]["k10"] - k10) <= 1e-10 * k10
+    # ... and its x, gathered from both ranks in row order
+    import numpy as np
+    two, one = _dumped(tmp_path / "out2"), _dumped(tmp_path / "out1")
+    assert np.array_equal(two["x_sample_index"], one["x_sample_index"])
+    assert np.allclose(two["residual_history"], one["residual_history"],
+                       rtol=1e-10, atol=0)
+    assert np.linalg.norm(two["x_sample"] - one["x_sample"]) \
+        <= 1e-9 * np.linalg.norm(one["x_sample"])
 
 
 def test_bench_self_launch_reports_a_failing_rank(tmp_path, monkeypatch):

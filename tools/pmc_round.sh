@@ -40,7 +40,7 @@ if [ -n "$ONLY" ]; then echo "pmc round $R done (only: $ONLY)"; exit 0; fi
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/rp_$R
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$R -o bench -- \
-    python3 "$ROOT/bench.py" --no-cpu-baseline > "$ROOT/gpurun_out/${R}_bench_under_rocprof.log" 2>&1
+    python3 "$ROOT/bench.py" --full --no-cpu-baseline > "$OUT/${R}_bench_under_rocprof.log" 2>&1
 cp "$(find /tmp/rp_$R -name '*kernel_stats.csv' | head -1)" \
    "$ROOT/gpurun_out/${R}_rocprof_bench_n512_kernel_stats.csv"
 echo "pmc round $R done"
