@@ -413,6 +413,63 @@ int spmv_hip_csr_spmv_f32(spmv_hip_ctx* ctx, const spmv_hip_csr_plan* plan,
                           const float* diagonal, float alpha, const float* in,
                           float beta, float* out, void* stream);
 
+/* ---- transposed product (Matrix::transpmult, spmv/Matrix.h:78-81) ----------
+ * For a GENERAL plan and a column range [col_begin, col_end) of its block:
+ *   out[j - col_begin] = alpha * s_j + beta * out[j - col_begin]
+ * where s_j starts at +0.0 and adds v * in[i] left to right over the stored
+ * entries (i, j, v) of column j in ascending i, then ascending position in row
+ * i (duplicates keep their CSR order): the row-order CSR sum of the transpose
+ * built by a STABLE sort of the entries by column, mul and add rounded
+ * separately.  `in` holds num_rows entries, `out` col_end - col_begin; as in
+ * the forward product beta == 0 makes `out` write-only (an empty column gives
+ * alpha * 0.0, -0.0 for alpha < 0).
+ *   plan_build_transpose  builds the transposed map on the device (t_ptr:
+ *                         col_end - col_begin + 1 ints, t_row / t_pos: one int
+ *                         per entry) and the form of the product; `values` are
+ *                         the caller's values, value_bytes = 8 (fp64) or 4
+ *                         (fp32).  SPMV_HIP_EINVAL when an entry's column lies
+ *                         outside [col_begin, col_end), for a symmetric plan and
+ *                         after plan_release_matrix.  A second call replaces
+ *                         the first.
+ *   plan_get "t_form"     0 none;  1 COPY: the values permuted into column
+ *                         order and an inner general plan on the transpose's
+ *                         CSR -- every forward form runs A^T (keys "t.<key>"
+ *                         read the inner plan, e.g. "t.sdia_const");  2 IN
+ *                         PLACE: one lane per output column over (t_ptr, t_row,
+ *                         t_pos) and the caller's values, no value copy (the
+ *                         map itself is 8 B per entry + 4 B per column) -- ctx
+ *                         option "csr_in_place", a launch with a `values`
+ *                         pointer other than the one the build saw, or no
+ *                         memory for the copy;  3 SELF: a square block over
+ *                         [0, n) that is its own transpose bit for bit (with
+ *                         row-block kernels) runs the forward plan, no copy,
+ *                         only t_pos kept.  "t_plan_us" (the build's wall
+ *                         time), "t_kib" (device memory of the map, the copy
+ *                         and the inner plan).
+ *   plan_set "t_in_place" 1 forces the in-place kernel (A/B tests), 0 undoes
+ *                         it; "t.<key>" sets a knob of the inner plan.
+ * spmv_hip_csr_plan_values_changed refreshes the copy and runs the
+ * self-transpose check again (a block that is no longer its own transpose
+ * takes the in-place kernel: nothing is allocated); plan_destroy frees
+ * everything.  The bits do not depend on the form. */
+int spmv_hip_csr_plan_build_transpose(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan,
+                                      const int32_t* rowptr, const int32_t* colind,
+                                      const void* values, int value_bytes,
+                                      int32_t col_begin, int32_t col_end,
+                                      void* stream);
+int spmv_hip_csr_spmvt_f64(spmv_hip_ctx* ctx, const spmv_hip_csr_plan* plan,
+                           int32_t num_rows, int32_t num_cols,
+                           int64_t num_non_zeros, const int32_t* rowptr,
+                           const int32_t* colind, const double* values,
+                           double alpha, const double* in, double beta,
+                           double* out, void* stream);
+int spmv_hip_csr_spmvt_f32(spmv_hip_ctx* ctx, const spmv_hip_csr_plan* plan,
+                           int32_t num_rows, int32_t num_cols,
+                           int64_t num_non_zeros, const int32_t* rowptr,
+                           const int32_t* colind, const float* values,
+                           float alpha, const float* in, float beta, float* out,
+                           void* stream);
+
 /* ---- ghost pack -------------------------------------------------------------
  * DeviceExecutor::gather_ghosts_run (device_executor.h:123-126;
  * reference_executor.cpp:150-164): out[i] = in[indices[i]]. */

@@ -175,6 +175,13 @@ int spmvh_matrix_plan_set(spmvh_matrix* A, int remote, const char* key,
 int spmvh_matrix_update(spmvh_matrix* A, double* x);
 int spmvh_matrix_update_finalise(spmvh_matrix* A, double* x);
 int spmvh_matrix_mult(spmvh_matrix* A, double* x, double* y);
+/* Matrix::transpmult: y = A^T b, b in row space (rows() entries), y in column
+ * space (local_size + num_ghosts entries: this rank's part, then the ghost
+ * columns' contributions that spmvh_l2g_map_reverse_update / the matrix's
+ * col_map()->reverse_update adds to their owners).  enable_transpose builds
+ * the transposed maps now (before release_csr). */
+int spmvh_matrix_transpmult(spmvh_matrix* A, double* b, double* y);
+int spmvh_matrix_enable_transpose(spmvh_matrix* A);
 
 /* ---- fp32 instantiation: Matrix<float> (device_executor.h:88-99 carries float
  * visitors).  Same calls, float data. */
@@ -191,6 +198,7 @@ int spmvh_matrix_f32_info(spmvh_matrix_f32* A, int* rows, int64_t* nnz,
                           int32_t* local_size, int32_t* num_ghosts);
 int spmvh_matrix_f32_update(spmvh_matrix_f32* A, float* x);
 int spmvh_matrix_f32_mult(spmvh_matrix_f32* A, float* x, float* y);
+int spmvh_matrix_f32_transpmult(spmvh_matrix_f32* A, float* b, float* y);
 
 /* Host half of create_matrix only (Matrix<double>::split_rows): no device.
  * sizes[0..7] = local rows, cols, nnz, remote rows, cols, nnz, number of

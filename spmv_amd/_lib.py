@@ -99,6 +99,12 @@ _PROTOS = {
                                  C.c_int),
     "spmv_hip_csr_spmv_f32": ([vp, vp, i32, i32, i64, vp, vp, vp, vp, f32, vp,
                                f32, vp, vp], C.c_int),
+    "spmv_hip_csr_plan_build_transpose": ([vp, vp, vp, vp, vp, C.c_int, i32, i32,
+                                           vp], C.c_int),
+    "spmv_hip_csr_spmvt_f64": ([vp, vp, i32, i32, i64, vp, vp, vp, f64, vp, f64,
+                                vp, vp], C.c_int),
+    "spmv_hip_csr_spmvt_f32": ([vp, vp, i32, i32, i64, vp, vp, vp, f32, vp, f32,
+                                vp, vp], C.c_int),
     "spmv_hip_gather_f64": ([vp, C.c_int, vp, vp, vp, vp], C.c_int),
     "spmv_hip_gather_f32": ([vp, C.c_int, vp, vp, vp, vp], C.c_int),
     "spmv_hip_scatter_add_f64": ([vp, C.c_int, vp, vp, vp, vp], C.c_int),

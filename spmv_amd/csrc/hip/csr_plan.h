@@ -383,6 +383,9 @@ struct spmv_hip_csr_plan {
   int sj_phases = 3;             // measurement only: 1 = long rows, 2 = slices
   int sj_blocks_per_cu = 0;      // 0 = what the LDS footprint allows
   int sj_xcd_group = 8;          // consecutive blocks per XCD (0 = off)
+  // the transposed product of a general block (spmv_csrt.hip:
+  // spmv_hip_csr_plan_build_transpose), null until built
+  struct SpmvTranspose* tr = nullptr;
   int32_t* row_list = nullptr; // ROWLIST: device list of non-empty rows
   int32_t num_listed = 0;
   int nt_store = 0; // non-temporal y stores
@@ -513,6 +516,20 @@ int spmv_run_symmetric_f32(const spmv_hip_csr_plan* pl, hipStream_t st,
 int spmv_symt_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
                     const int32_t* colind);
 void spmv_symt_free(spmv_hip_csr_plan* pl);
+// the transposed map of a block's entries, all of whose columns must lie in
+// [c0, c1) (`lower`: and below the diagonal): a stable sort by column, ties in
+// CSR order.  *t_ptr: c1 - c0 + 1 ints, *t_pos / *t_row: one per entry.
+// *refused = 1 (nothing allocated) when an entry breaks the rule; otherwise a
+// HIP error code, with nothing allocated unless it is hipSuccess.
+int spmv_tmap_build(spmv_hip_ctx* ctx, int32_t num_rows, int64_t nnz,
+                    const int32_t* rowptr, const int32_t* colind, int32_t c0,
+                    int32_t c1, bool lower, int32_t** t_ptr, int32_t** t_pos,
+                    int32_t** t_row, int* refused, hipStream_t st);
+// spmv_csrt.hip: the plan API's side of the transposed product
+void spmv_tr_free(spmv_hip_csr_plan* pl);
+int spmv_tr_values_changed(spmv_hip_ctx* ctx, spmv_hip_csr_plan* pl, hipStream_t st);
+int spmv_tr_get(const spmv_hip_csr_plan* pl, const char* key, int* value);
+int spmv_tr_set(spmv_hip_csr_plan* pl, const char* key, int value);
 // spmv_csr_forms.hip: (re)build the plane-walk table for planes `d2` rows apart, a
 // grid of `grid` workgroups and `segments` runs along the plane axis (0 =
 // choose); leaves zw_table null when the lattice is too small for it to pay

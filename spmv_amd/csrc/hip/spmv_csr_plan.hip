@@ -255,6 +255,8 @@ int spmv_hip_csr_plan_create(spmv_hip_ctx* ctx, int32_t num_rows,
 
 int spmv_hip_csr_plan_destroy(spmv_hip_csr_plan* plan)
 {
+  if (plan && plan->tr)
+    spmv_tr_free(plan);
   if (plan && plan->sjt) {
     (void)hipSetDevice(plan->ctx->device);
     spmv_sjds_free(plan->sjt);
@@ -529,6 +531,9 @@ int spmv_hip_csr_plan_values_changed(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan,
     if (rc == SPMV_HIP_ENOTSUP)
       rc = SPMV_HIP_OK;
   }
+  // the transposed product (spmv_csrt.hip): its copy, the self-transpose check
+  if (rc == SPMV_HIP_OK && plan->tr)
+    rc = spmv_tr_values_changed(ctx, plan, st);
   SPMV_CHECK_HIP(hipStreamSynchronize(st));
   plan->plan_us = plan_us0; // (the bakes added themselves: not plan creation)
   plan->values_changed_us
@@ -764,7 +769,8 @@ int spmv_hip_csr_plan_set(spmv_hip_csr_plan* plan, const char* key, int value)
       return spmv_zwalk_order_build(plan, plan->zw_d2, spmv_walk_grid(plan), 0,
                                     true);
   } else {
-    return SPMV_HIP_EINVAL;
+    // "t_in_place", "t.<key>": the transposed product (spmv_csrt.hip)
+    return spmv_tr_set(plan, key, value);
   }
   return SPMV_HIP_OK;
 }
@@ -989,8 +995,8 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
     *value = plan->blocks_per_cu;
   else if (!strcmp(key, "nontemporal"))
     *value = plan->nontemporal;
-  else
-    return SPMV_HIP_EINVAL;
+  else // "t_form", "t_plan_us", "t_kib", "t.<key>" (spmv_csrt.hip)
+    return spmv_tr_get(plan, key, value);
   return SPMV_HIP_OK;
 }
 

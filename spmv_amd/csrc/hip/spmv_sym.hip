@@ -397,22 +397,23 @@ __global__ __launch_bounds__(kBlock) void csr_symt_kernel(
 
 __global__ __launch_bounds__(kBlock) void symt_rowidx_kernel(
     int32_t num_rows, const int32_t* __restrict__ rowptr,
-    const int32_t* __restrict__ colind, int32_t* __restrict__ rowidx,
-    int32_t* __restrict__ pos, int32_t* __restrict__ count,
-    int32_t* __restrict__ not_lower)
+    const int32_t* __restrict__ colind, int32_t c0, int32_t c1, int lower,
+    int32_t* __restrict__ rowidx, int32_t* __restrict__ pos,
+    int32_t* __restrict__ count, int32_t* __restrict__ refused)
 {
   // one lane per row: the row index and position of every entry, the column
-  // histogram, and the check that the block is strictly lower triangular
+  // histogram, and the check that every column lies in [c0, c1) (and, lower,
+  // that the block is strictly lower triangular)
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < num_rows;
        i += (int64_t)gridDim.x * blockDim.x) {
     for (int32_t j = rowptr[i]; j < rowptr[i + 1]; ++j) {
       rowidx[j] = (int32_t)i;
       pos[j] = j;
       const int32_t c = colind[j];
-      if (c >= i || c < 0)
-        atomicOr(not_lower, 1);
+      if (c < c0 || c >= c1 || (lower && c >= i))
+        atomicOr(refused, 1);
       else
-        atomicAdd(count + c, 1);
+        atomicAdd(count + (c - c0), 1);
     }
   }
 }
@@ -600,18 +601,40 @@ int spmv_symt_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   const int64_t nnz = pl->nnz;
   if (n == 0 || nnz == 0)
     return SPMV_HIP_OK;
-  hipStream_t st = pl->ctx->stream;
+  int not_lower = 0;
+  const int e = spmv_tmap_build(pl->ctx, n, nnz, rowptr, colind, 0, n, true,
+                                &pl->t_ptr, &pl->t_pos, &pl->t_row, &not_lower,
+                                pl->ctx->stream);
+  if (e != hipSuccess || not_lower) {
+    spmv_symt_free(pl);
+    return (e == hipSuccess || e == hipErrorOutOfMemory) ? SPMV_HIP_OK : e;
+  }
+  pl->sym_det = 1;
+  return SPMV_HIP_OK;
+}
+
+int spmv_tmap_build(spmv_hip_ctx* ctx, int32_t num_rows, int64_t nnz,
+                    const int32_t* rowptr, const int32_t* colind, int32_t c0,
+                    int32_t c1, bool lower, int32_t** t_ptr_out,
+                    int32_t** t_pos_out, int32_t** t_row_out, int* refused,
+                    hipStream_t st)
+{
+  *refused = 0;
+  const int32_t n = num_rows;
+  const int32_t m = c1 - c0; // columns of the map
+  int32_t *t_ptr = nullptr, *t_pos = nullptr, *t_row = nullptr;
   int32_t *rowidx = nullptr, *pos = nullptr, *keys = nullptr, *flag = nullptr;
   void* tmp = nullptr;
   size_t tmp_bytes = 0, scan_bytes = 0;
+  // the sort's keys are the columns themselves: bits up to the range's end
   int end_bit = 1;
-  while (end_bit < 31 && ((int64_t)1 << end_bit) < n)
+  while (end_bit < 31 && ((int64_t)1 << end_bit) < c1)
     ++end_bit;
-  hipError_t e = hipMalloc(&pl->t_ptr, sizeof(int32_t) * ((size_t)n + 1));
+  hipError_t e = hipMalloc(&t_ptr, sizeof(int32_t) * ((size_t)m + 1));
   if (e == hipSuccess)
-    e = hipMalloc(&pl->t_pos, sizeof(int32_t) * (size_t)nnz);
+    e = hipMalloc(&t_pos, sizeof(int32_t) * (size_t)nnz);
   if (e == hipSuccess)
-    e = hipMalloc(&pl->t_row, sizeof(int32_t) * (size_t)nnz);
+    e = hipMalloc(&t_row, sizeof(int32_t) * (size_t)nnz);
   if (e == hipSuccess)
     e = hipMalloc(&rowidx, sizeof(int32_t) * (size_t)nnz);
   if (e == hipSuccess)
@@ -622,40 +645,40 @@ int spmv_symt_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
     e = hipMalloc(&flag, sizeof(int32_t));
   if (e == hipSuccess)
     e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, colind, keys, pos,
-                                           pl->t_pos, nnz, 0, end_bit, st);
+                                           t_pos, nnz, 0, end_bit, st);
   if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, pl->t_ptr,
-                                         pl->t_ptr, n + 1, st);
+    e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, t_ptr, t_ptr, m + 1,
+                                         st);
   if (e == hipSuccess)
     e = hipMalloc(&tmp, (tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes) + 16);
   if (e == hipSuccess)
-    e = hipMemsetAsync(pl->t_ptr, 0, sizeof(int32_t) * ((size_t)n + 1), st);
+    e = hipMemsetAsync(t_ptr, 0, sizeof(int32_t) * ((size_t)m + 1), st);
   if (e == hipSuccess)
     e = hipMemsetAsync(flag, 0, sizeof(int32_t), st);
-  int32_t not_lower = 0;
+  int32_t bad = 0;
   if (e == hipSuccess) {
-    const int grid = spmv_grid_for(pl->ctx, n, kBlock);
+    const int grid = spmv_grid_for(ctx, n, kBlock);
     hipLaunchKernelGGL(symt_rowidx_kernel, dim3(grid), dim3(kBlock), 0, st, n,
-                       rowptr, colind, rowidx, pos, pl->t_ptr, flag);
+                       rowptr, colind, c0, c1, lower ? 1 : 0, rowidx, pos, t_ptr,
+                       flag);
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&not_lower, flag, sizeof(int32_t), hipMemcpyDeviceToHost,
-                       st);
+    e = hipMemcpyAsync(&bad, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess)
     e = hipStreamSynchronize(st);
-  if (e == hipSuccess && !not_lower) {
+  if (e == hipSuccess && !bad) {
     // entries by column, ties in their original (row, position) order: radix
     // sort is stable
     e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, colind, keys, pos,
-                                           pl->t_pos, nnz, 0, end_bit, st);
+                                           t_pos, nnz, 0, end_bit, st);
     if (e == hipSuccess)
-      e = hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, pl->t_ptr,
-                                           pl->t_ptr, n + 1, st);
+      e = hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, t_ptr, t_ptr, m + 1,
+                                           st);
     if (e == hipSuccess) {
-      const int grid = spmv_grid_for(pl->ctx, nnz, kBlock);
+      const int grid = spmv_grid_for(ctx, nnz, kBlock);
       hipLaunchKernelGGL(symt_gather_rows_kernel, dim3(grid), dim3(kBlock), 0,
-                         st, nnz, rowidx, pl->t_pos, pl->t_row);
+                         st, nnz, rowidx, t_pos, t_row);
       e = hipGetLastError();
     }
     if (e == hipSuccess)
@@ -666,11 +689,15 @@ int spmv_symt_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   (void)hipFree(pos);
   (void)hipFree(keys);
   (void)hipFree(flag);
-  if (e != hipSuccess || not_lower) {
-    spmv_symt_free(pl);
-    return (e == hipSuccess || e == hipErrorOutOfMemory) ? SPMV_HIP_OK
-                                                         : static_cast<int>(e);
+  if (e != hipSuccess || bad) {
+    (void)hipFree(t_ptr);
+    (void)hipFree(t_pos);
+    (void)hipFree(t_row);
+    *refused = e == hipSuccess ? 1 : 0;
+    return static_cast<int>(e);
   }
-  pl->sym_det = 1;
+  *t_ptr_out = t_ptr;
+  *t_pos_out = t_pos;
+  *t_row_out = t_row;
   return SPMV_HIP_OK;
 }

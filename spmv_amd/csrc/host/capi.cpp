@@ -572,6 +572,22 @@ int spmvh_matrix_mult(spmvh_matrix* A, double* x, double* y)
   });
 }
 
+int spmvh_matrix_transpmult(spmvh_matrix* A, double* b, double* y)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    A->A->transpmult(b, y);
+  });
+}
+
+int spmvh_matrix_enable_transpose(spmvh_matrix* A)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    A->A->enable_transpose();
+  });
+}
+
 int spmvh_split_create(const int32_t* rowptr, const int32_t* colind,
                        const double* values, int64_t nrows_local,
                        int64_t ncols_local, int64_t global_row_offset,
@@ -656,6 +672,14 @@ int spmvh_matrix_f32_mult(spmvh_matrix_f32* A, float* x, float* y)
   return guarded([&] {
     require(A != nullptr, "NULL argument");
     A->A->mult(x, y);
+  });
+}
+
+int spmvh_matrix_f32_transpmult(spmvh_matrix_f32* A, float* b, float* y)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    A->A->transpmult(b, y);
   });
 }
 

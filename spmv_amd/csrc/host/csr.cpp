@@ -139,6 +139,36 @@ int CSRSpMV<T>::query(const char* key) const
 }
 
 template <typename T>
+void CSRSpMV<T>::build_transpose(const int32_t* rowptr, const int32_t* colind,
+                                 const T* values, int32_t col_begin,
+                                 int32_t col_end, const HipExecutor& exec) const
+{
+  throw_on_error(spmv_hip_csr_plan_build_transpose(exec.context(), plan(), rowptr,
+                                                   colind, values, (int)sizeof(T),
+                                                   col_begin, col_end, nullptr),
+                 "spmv_hip_csr_plan_build_transpose");
+}
+
+template <typename T>
+void CSRSpMV<T>::run_transpose(int32_t num_rows, int32_t num_cols,
+                               int64_t num_non_zeros, const int32_t* rowptr,
+                               const int32_t* colind, const T* values, T alpha,
+                               const T* in, T beta, T* out,
+                               const HipExecutor& exec) const
+{
+  if constexpr (std::is_same<T, double>::value)
+    throw_on_error(spmv_hip_csr_spmvt_f64(exec.context(), plan(), num_rows,
+                                          num_cols, num_non_zeros, rowptr, colind,
+                                          values, alpha, in, beta, out, nullptr),
+                   "spmv_hip_csr_spmvt_f64");
+  else
+    throw_on_error(spmv_hip_csr_spmvt_f32(exec.context(), plan(), num_rows,
+                                          num_cols, num_non_zeros, rowptr, colind,
+                                          values, alpha, in, beta, out, nullptr),
+                   "spmv_hip_csr_spmvt_f32");
+}
+
+template <typename T>
 void CSRSpMV<T>::finalize(const HipExecutor&) const
 {
   spmv_hip_csr_plan_destroy(plan());
@@ -328,6 +358,38 @@ bool CSRMatrix<T>::mult_dot(T alpha, T* in, T beta, T* out,
     _op.run_dot(this->_num_rows, this->_num_cols, this->_num_non_zeros, _rowptr,
                 _colind, _values, alpha, in, beta, out, dot_partials, *hip);
   return true;
+}
+
+template <typename T>
+void CSRMatrix<T>::enable_transpose(int32_t col_begin, int32_t col_end) const
+{
+  if (col_begin == _t_begin && col_end == _t_end)
+    return;
+  if (this->_symmetric)
+    throw std::runtime_error("CSRMatrix::transpmult: symmetric storage is its own "
+                             "transpose (use mult)");
+  auto* hip = dynamic_cast<const HipExecutor*>(this->_exec.get());
+  if (!hip)
+    throw std::runtime_error(
+        "spmv::HostExecutor::transpmult: this build has no CPU compute path; "
+        "create the matrix with a HipExecutor");
+  if (_released)
+    throw std::runtime_error(
+        "CSRMatrix::transpmult: the CSR arrays were released (release_csr) "
+        "before the transposed map was built; call enable_transpose first");
+  _op.build_transpose(_rowptr, _colind, _values, col_begin, col_end, *hip);
+  _t_begin = col_begin;
+  _t_end = col_end;
+}
+
+template <typename T>
+void CSRMatrix<T>::transpmult(T alpha, const T* in, T beta, T* out,
+                              int32_t col_begin, int32_t col_end) const
+{
+  enable_transpose(col_begin, col_end);
+  auto* hip = dynamic_cast<const HipExecutor*>(this->_exec.get());
+  _op.run_transpose(this->_num_rows, this->_num_cols, this->_num_non_zeros,
+                    _rowptr, _colind, _values, alpha, in, beta, out, *hip);
 }
 
 template class CSRSpMV<float>;

@@ -82,6 +82,18 @@ public:
   // what it cost ("lat", "lx", "slat", "sym_det", "plan_us", "plan_kib", ...)
   int query(const char* key) const;
 
+  // The transposed product (spmv_hip_csr_plan_build_transpose /
+  // spmv_hip_csr_spmvt_*), general blocks: build_transpose makes the map of the
+  // columns [col_begin, col_end); run_transpose then computes
+  // out[j - col_begin] = alpha (A^T in)_j + beta out[j - col_begin].
+  void build_transpose(const int32_t* rowptr, const int32_t* colind,
+                       const T* values, int32_t col_begin, int32_t col_end,
+                       const HipExecutor& exec) const;
+  void run_transpose(int32_t num_rows, int32_t num_cols, int64_t num_non_zeros,
+                     const int32_t* rowptr, const int32_t* colind,
+                     const T* values, T alpha, const T* in, T beta, T* out,
+                     const HipExecutor& exec) const;
+
   bool symmetric() const { return _symmetric; }
   spmv_hip_csr_plan* plan() const
   {
@@ -166,6 +178,16 @@ public:
   size_t release_csr() const;
   bool csr_released() const { return _released; }
 
+  // out[j - col_begin] = alpha (A^T in)_j + beta out[j - col_begin] for the
+  // columns j in [col_begin, col_end) (spmv_hip_csr_spmvt_*): `in` holds
+  // rows() entries.  General blocks; the transposed map is built on first use
+  // (and again for another range).  After release_csr() only a map built
+  // before it -- enable_transpose() -- can serve, else this throws.
+  void transpmult(T alpha, const T* in, T beta, T* out, int32_t col_begin,
+                  int32_t col_end) const;
+  // eager build of the map for [col_begin, col_end) (before release_csr)
+  void enable_transpose(int32_t col_begin, int32_t col_end) const;
+
   const int32_t* rowptr() const { return _rowptr; }
   const int32_t* colind() const { return _colind; }
   const T* values() const { return _values; }
@@ -180,6 +202,7 @@ private:
   mutable float* _values32 = nullptr; // enable_mixed()
   mutable bool _mixed_on = false;
   mutable bool _released = false; // _colind / _values freed (release_csr)
+  mutable int32_t _t_begin = -1, _t_end = -1; // range of the transposed map
   CSRSpMV<T> _op;
 };
 

@@ -153,6 +153,46 @@ void Matrix<T>::spmv_sym_overlap(T* x, T* y) const
   _mat_remote->mult(1, x, 1, y);
 }
 
+// ---------------------------------------------------------------------------
+// transposed product (Matrix.h:78-81)
+// ---------------------------------------------------------------------------
+template <typename T>
+void Matrix<T>::enable_transpose() const
+{
+  const int32_t nloc = _col_map->local_size();
+  const int32_t nall = nloc + _col_map->num_ghosts();
+  if (_symmetric) {
+    if (nall > nloc)
+      _mat_remote->enable_transpose(nloc, nall);
+  } else if (_col_map->overlapping()) {
+    _mat_local->enable_transpose(0, nloc);
+    if (nall > nloc)
+      _mat_remote->enable_transpose(nloc, nall);
+  } else {
+    _mat_local->enable_transpose(0, nall);
+  }
+}
+
+template <typename T>
+void Matrix<T>::transpmult(T* b, T* y) const
+{
+  const int32_t nloc = _col_map->local_size();
+  const int32_t nall = nloc + _col_map->num_ghosts();
+  if (_symmetric) {
+    _mat_local->mult(1, b, 0, y); // D + L + L^T: its own transpose
+    if (nall > nloc)
+      _mat_remote->transpmult(1, b, 0, y + nloc, nloc, nall);
+  } else if (_col_map->overlapping()) {
+    // two launches, neither writes the other's range (beta = 1 would turn a
+    // -0.0 into +0.0): the same bits as one block
+    _mat_local->transpmult(1, b, 0, y, 0, nloc);
+    if (nall > nloc)
+      _mat_remote->transpmult(1, b, 0, y + nloc, nloc, nall);
+  } else {
+    _mat_local->transpmult(1, b, 0, y, 0, nall);
+  }
+}
+
 template <typename T>
 bool Matrix<T>::enable_mixed() const
 {

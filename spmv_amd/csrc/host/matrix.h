@@ -68,6 +68,23 @@ public:
   bool enable_mixed() const;
   void use_mixed(bool on) const;
 
+  // y = A^T b (Matrix.h:78-81; the reference throws "not yet implemented",
+  // Matrix.cpp:145-148).  b: rows() entries (row space); y: col_map()->
+  // local_size() + num_ghosts() entries (column space), device pointers.
+  // y[0:local] is this rank's own contribution, y[local:] the ghost columns'
+  // contributions, which belong to other ranks: col_map()->reverse_update(y)
+  // then adds them to their owners (demos/restrictmain.cpp).
+  //   general, one block     A^T over [0, local + ghosts)
+  //   general, two blocks    local block over [0, local), remote block over
+  //                          [local, local + ghosts) -- the same bits
+  //   symmetric              the stored local block (D + L + L^T) is its own
+  //                          transpose: its forward product; the remote block
+  //                          transposed over the ghost range
+  // The transposed maps are built on first use; enable_transpose() builds them
+  // now (needed before release_csr() if transpmult is wanted later).
+  void transpmult(T* b, T* y) const;
+  void enable_transpose() const;
+
   std::shared_ptr<L2GMap> row_map() const { return _row_map; }
   std::shared_ptr<const L2GMap> col_map() const { return _col_map; }
 

@@ -282,6 +282,25 @@ class CsrBlock:
                  _p(self.values), _p(self.diagonal), float(alpha), x_ptr,
                  float(beta), y_ptr, stream)
 
+    def transpose(self, col_begin=0, col_end=None, stream=None):
+        """spmv_hip_csr_plan_build_transpose over the columns [col_begin,
+        col_end) (default: all of them)."""
+        col_end = self.ncols if col_end is None else col_end
+        call("spmv_hip_csr_plan_build_transpose", self.ctx.h, self.plan,
+             _p(self.rowptr), _p(self.colind), _p(self.values),
+             self.dtype.itemsize, int(col_begin), int(col_end), stream)
+
+    def multt(self, alpha, x_ptr, beta, y_ptr, values=None, stream=None):
+        """spmv_hip_csr_spmvt_*: y = alpha A^T x + beta y over the range of
+        transpose(); `values`: another device array of the block's values
+        (the in-place kernel runs on it)."""
+        v = _p(self.values) if values is None else values
+        name = ("spmv_hip_csr_spmvt_f64" if self.dtype == np.float64
+                else "spmv_hip_csr_spmvt_f32")
+        call(name, self.ctx.h, self.plan, self.nrows, self.ncols, self.nnz,
+             _p(self.rowptr), _p(self.colind), v, float(alpha), x_ptr,
+             float(beta), y_ptr, stream)
+
     def free(self):
         if self.plan:
             call("spmv_hip_csr_plan_destroy", self.plan)

@@ -83,6 +83,9 @@ _PROTOS = {
     "spmvh_matrix_update": [vp, vp],
     "spmvh_matrix_update_finalise": [vp, vp],
     "spmvh_matrix_mult": [vp, vp, vp],
+    "spmvh_matrix_transpmult": [vp, vp, vp],
+    "spmvh_matrix_enable_transpose": [vp],
+    "spmvh_matrix_f32_transpmult": [vp, vp, vp],
     "spmvh_split_create": [vp, vp, vp, i64, i64, i64, i64, vp, i64, C.c_int,
                            C.c_int, PTR(vp), PTR(i64)],
     "spmvh_split_get": [vp, C.c_int, vp, vp, vp],
@@ -511,6 +514,15 @@ class Matrix:
     def mult(self, x_ptr, y_ptr):
         call("spmvh_matrix_mult", self.h, x_ptr, y_ptr)
 
+    def transpmult(self, b_ptr, y_ptr):
+        """y = A^T b: b holds rows() entries, y local_size + num_ghosts (the
+        ghost tail goes to its owners with col_map's reverse_update)."""
+        call("spmvh_matrix_transpmult", self.h, b_ptr, y_ptr)
+
+    def enable_transpose(self):
+        """build the transposed maps now (before release_csr)"""
+        call("spmvh_matrix_enable_transpose", self.h)
+
 
 class MatrixF32:
     """spmv::Matrix<float> (fp32 instantiation)"""
@@ -542,6 +554,9 @@ class MatrixF32:
 
     def mult(self, x_ptr, y_ptr):
         call("spmvh_matrix_f32_mult", self.h, x_ptr, y_ptr)
+
+    def transpmult(self, b_ptr, y_ptr):
+        call("spmvh_matrix_f32_transpmult", self.h, b_ptr, y_ptr)
 
     def close(self):
         if self.h:
