@@ -470,6 +470,81 @@ int spmv_hip_csr_spmvt_f32(spmv_hip_ctx* ctx, const spmv_hip_csr_plan* plan,
                            float alpha, const float* in, float beta, float* out,
                            void* stream);
 
+/* ---- multi-vector product (Matrix::mult_block) -------------------------------
+ * Y = alpha A X + beta Y for a block of k >= 1 vectors.  LAYOUT: a block is
+ * INTERLEAVED (row-major) -- element (i, c), 0 <= c < k, lives at X[i * k + c];
+ * `in` holds num_cols * k elements, `out` num_rows * k, both device pointers.
+ * For every column c, Y[:, c] has THE SAME BITS as the single-vector product
+ * spmv_hip_csr_spmv_* on X[:, c] for the same storage (rows summed left to
+ * right, mul and add rounded separately; beta == 0: `out` is write-only).
+ * k == 1 is the existing product.
+ *   plan_get "mv_form"   the last launch: 0 none yet;  1 NATIVE: one pass over
+ *                        the caller's CSR arrays for all k vectors (general
+ *                        plans, fp64 vectors, fp64 or fp32 values, k = 2, 4, 8,
+ *                        `in` and `out` 16-byte aligned);  2 PER COLUMN: X is
+ *                        de-interleaved into plan-owned scratch, the plan's
+ *                        single-vector launch runs once per column in whatever
+ *                        form the plan took, Y is interleaved back -- symmetric
+ *                        storage, any other k, a plan after
+ *                        plan_release_matrix, the fp32 library type.  k == 1
+ *                        reports 2 as well: one column, the single-vector
+ *                        launch on `in` / `out` themselves, no scratch.
+ *   plan_get "mv_kib"    the scratch held: (num_cols + num_rows) * k elements,
+ *                        each column rounded up to 4 elements; allocated on
+ *                        first use, grown on demand, never shrunk, freed with
+ *                        the plan (512^3 rows, k = 8: about 17 GB).  When
+ *                        it cannot be allocated the call returns the HIP error
+ *                        code and launches nothing.
+ *   plan_set "mv_native" 0 forces the per-column form (A/B tests), 1 (the
+ *                        default) undoes it.
+ * The calls record the form in the plan, so the plan is not const here, and
+ * two of them on one plan must not run concurrently.  SPMV_HIP_EINVAL, before
+ * anything is launched: NULL handles, k < 1, shapes other than the plan's, `in`
+ * and `out` overlapping.  `diagonal` as in spmv_hip_csr_spmv_* (NULL for the
+ * mixed product, which takes general plans only). */
+int spmv_hip_csr_spmm_f64(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan,
+                          int32_t num_rows, int32_t num_cols,
+                          int64_t num_non_zeros, const int32_t* rowptr,
+                          const int32_t* colind, const double* values,
+                          const double* diagonal, double alpha, const double* in,
+                          double beta, double* out, int k, void* stream);
+int spmv_hip_csr_spmm_f32f64(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan,
+                             int32_t num_rows, int32_t num_cols,
+                             int64_t num_non_zeros, const int32_t* rowptr,
+                             const int32_t* colind, const float* values,
+                             const double* diagonal, double alpha,
+                             const double* in, double beta, double* out, int k,
+                             void* stream);
+int spmv_hip_csr_spmm_f32(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan,
+                          int32_t num_rows, int32_t num_cols,
+                          int64_t num_non_zeros, const int32_t* rowptr,
+                          const int32_t* colind, const float* values,
+                          const float* diagonal, float alpha, const float* in,
+                          float beta, float* out, int k, void* stream);
+/* Tiled transposes between the interleaved layout (n x k) and k contiguous
+ * columns, column c at columns[c * ld ... + n), ld >= n:
+ *   interleave    out[i * k + c] = columns[c * ld + i]
+ *   deinterleave  columns[c * ld + i] = in[i * k + c]
+ * Source and destination must not overlap. */
+int spmv_hip_interleave_f64(spmv_hip_ctx* ctx, int64_t n, int k,
+                            const double* columns, int64_t ld, double* out,
+                            void* stream);
+int spmv_hip_interleave_f32(spmv_hip_ctx* ctx, int64_t n, int k,
+                            const float* columns, int64_t ld, float* out,
+                            void* stream);
+int spmv_hip_deinterleave_f64(spmv_hip_ctx* ctx, int64_t n, int k, const double* in,
+                              int64_t ld, double* columns, void* stream);
+int spmv_hip_deinterleave_f32(spmv_hip_ctx* ctx, int64_t n, int k, const float* in,
+                              int64_t ld, float* columns, void* stream);
+/* Ghost pack of an interleaved block, the multi-vector form of spmv_hip_gather_*:
+ * out[g * k + c] = in[indices[g] * k + c]. */
+int spmv_hip_gather_block_f64(spmv_hip_ctx* ctx, int num_indices,
+                              const int32_t* indices, int k, const double* in,
+                              double* out, void* stream);
+int spmv_hip_gather_block_f32(spmv_hip_ctx* ctx, int num_indices,
+                              const int32_t* indices, int k, const float* in,
+                              float* out, void* stream);
+
 /* ---- ghost pack -------------------------------------------------------------
  * DeviceExecutor::gather_ghosts_run (device_executor.h:123-126;
  * reference_executor.cpp:150-164): out[i] = in[indices[i]]. */

@@ -182,6 +182,15 @@ int spmvh_matrix_mult(spmvh_matrix* A, double* x, double* y);
  * the transposed maps now (before release_csr). */
 int spmvh_matrix_transpmult(spmvh_matrix* A, double* b, double* y);
 int spmvh_matrix_enable_transpose(spmvh_matrix* A);
+/* Matrix::mult_block: Y = A X for a block of k >= 1 INTERLEAVED vectors --
+ * element (i, c) at X[i * k + c]; X holds (local_size + num_ghosts) * k
+ * entries, Y rows() * k.  Column c of Y has the bits of spmvh_matrix_mult on
+ * column c of X.  update_block / update_finalise_block are
+ * col_map()->update_block(X, k) / update_finalise_block(X, k): the halo of
+ * all k vectors in one exchange. */
+int spmvh_matrix_mult_block(spmvh_matrix* A, double* X, double* Y, int k);
+int spmvh_matrix_update_block(spmvh_matrix* A, double* X, int k);
+int spmvh_matrix_update_finalise_block(spmvh_matrix* A, double* X, int k);
 
 /* ---- fp32 instantiation: Matrix<float> (device_executor.h:88-99 carries float
  * visitors).  Same calls, float data. */
@@ -199,6 +208,9 @@ int spmvh_matrix_f32_info(spmvh_matrix_f32* A, int* rows, int64_t* nnz,
 int spmvh_matrix_f32_update(spmvh_matrix_f32* A, float* x);
 int spmvh_matrix_f32_mult(spmvh_matrix_f32* A, float* x, float* y);
 int spmvh_matrix_f32_transpmult(spmvh_matrix_f32* A, float* b, float* y);
+int spmvh_matrix_f32_mult_block(spmvh_matrix_f32* A, float* X, float* Y, int k);
+int spmvh_matrix_f32_update_block(spmvh_matrix_f32* A, float* X, int k);
+int spmvh_matrix_f32_update_finalise_block(spmvh_matrix_f32* A, float* X, int k);
 
 /* Host half of create_matrix only (Matrix<double>::split_rows): no device.
  * sizes[0..7] = local rows, cols, nnz, remote rows, cols, nnz, number of
@@ -255,6 +267,10 @@ int spmvh_l2g_map_plan(spmvh_l2g* map, int32_t* neighbours, int32_t* send_count,
                        int32_t* recv_count, int32_t* send_offset,
                        int32_t* recv_offset, int32_t* indexbuf);
 int spmvh_l2g_map_update(spmvh_l2g* map, double* x);
+/* L2GMap::update_block / update_finalise_block on a block of k interleaved
+ * fp64 vectors ((local_size + num_ghosts) * k entries) */
+int spmvh_l2gmap_update_block(spmvh_l2g* map, double* X, int k);
+int spmvh_l2gmap_update_finalise_block(spmvh_l2g* map, double* X, int k);
 /* L2GMap::reverse_update(vec) (L2GMap.h:103): ghost tail -> owners, added */
 int spmvh_l2g_map_reverse_update(spmvh_l2g* map, double* x);
 int spmvh_l2g_map_reverse_update_f32(spmvh_l2g* map, float* x);

@@ -105,6 +105,18 @@ _PROTOS = {
                                 vp, vp], C.c_int),
     "spmv_hip_csr_spmvt_f32": ([vp, vp, i32, i32, i64, vp, vp, vp, f32, vp, f32,
                                 vp, vp], C.c_int),
+    "spmv_hip_csr_spmm_f64": ([vp, vp, i32, i32, i64, vp, vp, vp, vp, f64, vp,
+                               f64, vp, C.c_int, vp], C.c_int),
+    "spmv_hip_csr_spmm_f32f64": ([vp, vp, i32, i32, i64, vp, vp, vp, vp, f64, vp,
+                                  f64, vp, C.c_int, vp], C.c_int),
+    "spmv_hip_csr_spmm_f32": ([vp, vp, i32, i32, i64, vp, vp, vp, vp, f32, vp,
+                               f32, vp, C.c_int, vp], C.c_int),
+    "spmv_hip_interleave_f64": ([vp, i64, C.c_int, vp, i64, vp, vp], C.c_int),
+    "spmv_hip_interleave_f32": ([vp, i64, C.c_int, vp, i64, vp, vp], C.c_int),
+    "spmv_hip_deinterleave_f64": ([vp, i64, C.c_int, vp, i64, vp, vp], C.c_int),
+    "spmv_hip_deinterleave_f32": ([vp, i64, C.c_int, vp, i64, vp, vp], C.c_int),
+    "spmv_hip_gather_block_f64": ([vp, C.c_int, vp, C.c_int, vp, vp, vp], C.c_int),
+    "spmv_hip_gather_block_f32": ([vp, C.c_int, vp, C.c_int, vp, vp, vp], C.c_int),
     "spmv_hip_gather_f64": ([vp, C.c_int, vp, vp, vp, vp], C.c_int),
     "spmv_hip_gather_f32": ([vp, C.c_int, vp, vp, vp, vp], C.c_int),
     "spmv_hip_scatter_add_f64": ([vp, C.c_int, vp, vp, vp, vp], C.c_int),

@@ -8,6 +8,7 @@
 //   spmv_symlat.hip  the same idea for the symmetric storage
 //   spmv_symdia.hip  ... with the values re-laid out by offset (baked copy)
 //   spmv_sjds.hip    sliced jagged form: ragged / long rows, x staged in LDS
+//   spmv_mv.hip      multi-vector product (k interleaved vectors), block pack
 #pragma once
 
 #include "common.h"
@@ -386,6 +387,14 @@ struct spmv_hip_csr_plan {
   // the transposed product of a general block (spmv_csrt.hip:
   // spmv_hip_csr_plan_build_transpose), null until built
   struct SpmvTranspose* tr = nullptr;
+  // the multi-vector product (spmv_mv.hip): scratch of the per-column
+  // fallback (allocated on first use, grown on demand), the form of the last
+  // launch (0 none yet, 1 native kernel, 2 per-column fallback) and the knob
+  // that forces the fallback (plan_set "mv_native" 0)
+  void* mv_scratch = nullptr;
+  size_t mv_bytes = 0;
+  int mv_form = 0;
+  int mv_native = 1;
   int32_t* row_list = nullptr; // ROWLIST: device list of non-empty rows
   int32_t num_listed = 0;
   int nt_store = 0; // non-temporal y stores
@@ -489,6 +498,9 @@ struct XwProbe {
 // --- cross-file entry points (one definition each) -------------------------
 // spmv_csr.hip
 int spmv_rowblock_grid(const spmv_hip_csr_plan* pl); // grid of the row-block kernels
+// may a released plan launch with these operands (of elem_bytes each)?
+bool spmv_released_launch_ok(const spmv_hip_csr_plan* pl, const void* values,
+                             const void* in, const void* diagonal, int elem_bytes);
 // spmv_csr_forms.hip: plan-time builders of the general plans
 int spmv_build_row_list(spmv_hip_csr_plan* pl, const int32_t* rowptr);
 void spmv_free_lx(spmv_hip_csr_plan* pl);
@@ -530,6 +542,8 @@ void spmv_tr_free(spmv_hip_csr_plan* pl);
 int spmv_tr_values_changed(spmv_hip_ctx* ctx, spmv_hip_csr_plan* pl, hipStream_t st);
 int spmv_tr_get(const spmv_hip_csr_plan* pl, const char* key, int* value);
 int spmv_tr_set(spmv_hip_csr_plan* pl, const char* key, int value);
+// spmv_mv.hip: the multi-vector product's scratch
+void spmv_mv_free(spmv_hip_csr_plan* pl);
 // spmv_csr_forms.hip: (re)build the plane-walk table for planes `d2` rows apart, a
 // grid of `grid` workgroups and `segments` runs along the plane axis (0 =
 // choose); leaves zw_table null when the lattice is too small for it to pay

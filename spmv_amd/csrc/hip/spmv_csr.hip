@@ -898,6 +898,20 @@ bool released_launch_ok(const spmv_hip_csr_plan* pl, const T* values,
 
 int spmv_rowblock_grid(const spmv_hip_csr_plan* pl) { return rowblock_grid(pl); }
 
+// the operand check of a launch on a released plan, for callers in other files
+// (the multi-vector fallback validates before it launches anything)
+bool spmv_released_launch_ok(const spmv_hip_csr_plan* pl, const void* values,
+                             const void* in, const void* diagonal, int elem_bytes)
+{
+  if (elem_bytes == 8)
+    return released_launch_ok(pl, static_cast<const double*>(values),
+                              static_cast<const double*>(in),
+                              static_cast<const double*>(diagonal));
+  return released_launch_ok(pl, static_cast<const float*>(values),
+                            static_cast<const float*>(in),
+                            static_cast<const float*>(diagonal));
+}
+
 extern "C" {
 
 int spmv_hip_csr_spmv_f64(spmv_hip_ctx* ctx, const spmv_hip_csr_plan* plan,

@@ -257,6 +257,8 @@ int spmv_hip_csr_plan_destroy(spmv_hip_csr_plan* plan)
 {
   if (plan && plan->tr)
     spmv_tr_free(plan);
+  if (plan)
+    spmv_mv_free(plan);
   if (plan && plan->sjt) {
     (void)hipSetDevice(plan->ctx->device);
     spmv_sjds_free(plan->sjt);
@@ -634,6 +636,10 @@ int spmv_hip_csr_plan_set(spmv_hip_csr_plan* plan, const char* key, int value)
     plan->lx_chunks = value;
   } else if (!strcmp(key, "nt_store")) {
     plan->nt_store = value != 0;
+  } else if (!strcmp(key, "mv_native")) {
+    // 0: the multi-vector product always takes the per-column fallback
+    SPMV_REQUIRE(value == 0 || value == 1);
+    plan->mv_native = value;
   } else if (!strcmp(key, "slat")) {
     // 1 needs the symmetric lattice form built at plan creation
     SPMV_REQUIRE(value == 0 || plan->slat_mask);
@@ -875,6 +881,12 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
     *value = plan->plan_mem_us;
   else if (!strcmp(key, "values_changed_us"))
     *value = plan->values_changed_us;
+  else if (!strcmp(key, "mv_form")) // the multi-vector product (spmv_mv.hip)
+    *value = plan->mv_form;
+  else if (!strcmp(key, "mv_native"))
+    *value = plan->mv_native;
+  else if (!strcmp(key, "mv_kib"))
+    *value = (int)((plan->mv_bytes + 1023) / 1024);
   else if (!strcmp(key, "plan_kib")) {
     // device memory the plan owns beyond the caller's CSR arrays
     const int64_t n = plan->num_rows, nnz = plan->nnz;

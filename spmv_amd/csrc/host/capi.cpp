@@ -580,6 +580,30 @@ int spmvh_matrix_transpmult(spmvh_matrix* A, double* b, double* y)
   });
 }
 
+int spmvh_matrix_mult_block(spmvh_matrix* A, double* X, double* Y, int k)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    A->A->mult_block(X, Y, k);
+  });
+}
+
+int spmvh_matrix_update_block(spmvh_matrix* A, double* X, int k)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    A->A->col_map()->update_block(X, k);
+  });
+}
+
+int spmvh_matrix_update_finalise_block(spmvh_matrix* A, double* X, int k)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    A->A->col_map()->update_finalise_block(X, k);
+  });
+}
+
 int spmvh_matrix_enable_transpose(spmvh_matrix* A)
 {
   return guarded([&] {
@@ -680,6 +704,30 @@ int spmvh_matrix_f32_transpmult(spmvh_matrix_f32* A, float* b, float* y)
   return guarded([&] {
     require(A != nullptr, "NULL argument");
     A->A->transpmult(b, y);
+  });
+}
+
+int spmvh_matrix_f32_mult_block(spmvh_matrix_f32* A, float* X, float* Y, int k)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    A->A->mult_block(X, Y, k);
+  });
+}
+
+int spmvh_matrix_f32_update_block(spmvh_matrix_f32* A, float* X, int k)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    A->A->col_map()->update_block(X, k);
+  });
+}
+
+int spmvh_matrix_f32_update_finalise_block(spmvh_matrix_f32* A, float* X, int k)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    A->A->col_map()->update_finalise_block(X, k);
   });
 }
 
@@ -864,6 +912,22 @@ int spmvh_l2g_map_update(spmvh_l2g* map, double* x)
   return guarded([&] {
     require(map != nullptr, "NULL argument");
     map->map->update(x);
+  });
+}
+
+int spmvh_l2gmap_update_block(spmvh_l2g* map, double* X, int k)
+{
+  return guarded([&] {
+    require(map != nullptr, "NULL argument");
+    map->map->update_block(X, k);
+  });
+}
+
+int spmvh_l2gmap_update_finalise_block(spmvh_l2g* map, double* X, int k)
+{
+  return guarded([&] {
+    require(map != nullptr, "NULL argument");
+    map->map->update_finalise_block(X, k);
   });
 }
 

@@ -277,6 +277,28 @@ void RcclComm::neighbor_exchange(size_t elem_bytes,
   const int n = static_cast<int>(neighbours.size());
   std::vector<int32_t> nb(neighbours.begin(), neighbours.end());
   int rc;
+  if (elem_bytes > sizeof(double) && elem_bytes % sizeof(float) == 0) {
+    // a block of k vectors per element (L2GMap::update_block): the same
+    // exchange in units of 8 (or 4) bytes, counts and offsets scaled
+    const size_t unit
+        = elem_bytes % sizeof(double) == 0 ? sizeof(double) : sizeof(float);
+    const int64_t f = static_cast<int64_t>(elem_bytes / unit);
+    std::vector<int32_t> sc(n), so(n), rcn(n), ro(n);
+    for (int i = 0; i < n; ++i) {
+      const int64_t v[4] = {send_counts[i] * f, send_offsets[i] * f,
+                            recv_counts[i] * f, recv_offsets[i] * f};
+      for (int64_t x : v)
+        if (x > INT32_MAX)
+          throw std::runtime_error("RcclComm: block exchange exceeds 2^31 units");
+      sc[i] = static_cast<int32_t>(v[0]);
+      so[i] = static_cast<int32_t>(v[1]);
+      rcn[i] = static_cast<int32_t>(v[2]);
+      ro[i] = static_cast<int32_t>(v[3]);
+    }
+    neighbor_exchange(unit, neighbours, send_buf, sc, so, recv_base, rcn, ro,
+                      stream);
+    return;
+  }
   if (elem_bytes == sizeof(double))
     rc = spmv_hip_comm_neighbor_exchange_f64(
         _comm, n, nb.data(), static_cast<const double*>(send_buf),

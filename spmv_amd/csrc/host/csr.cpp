@@ -169,6 +169,38 @@ void CSRSpMV<T>::run_transpose(int32_t num_rows, int32_t num_cols,
 }
 
 template <typename T>
+void CSRSpMV<T>::run_block(int32_t num_rows, int32_t num_cols,
+                           int64_t num_non_zeros, const int32_t* rowptr,
+                           const int32_t* colind, const T* values,
+                           const float* values32, const T* diagonal, T alpha,
+                           const T* in, T beta, T* out, int k,
+                           const HipExecutor& exec) const
+{
+  if constexpr (std::is_same<T, double>::value) {
+    if (values32)
+      throw_on_error(spmv_hip_csr_spmm_f32f64(exec.context(), plan(), num_rows,
+                                              num_cols, num_non_zeros, rowptr,
+                                              colind, values32, nullptr, alpha,
+                                              in, beta, out, k, nullptr),
+                     "spmv_hip_csr_spmm_f32f64");
+    else
+      throw_on_error(spmv_hip_csr_spmm_f64(exec.context(), plan(), num_rows,
+                                           num_cols, num_non_zeros, rowptr,
+                                           colind, values, diagonal, alpha, in,
+                                           beta, out, k, nullptr),
+                     "spmv_hip_csr_spmm_f64");
+  } else {
+    if (values32)
+      throw std::runtime_error("CSRSpMV<float>::run_block: no mixed product");
+    throw_on_error(spmv_hip_csr_spmm_f32(exec.context(), plan(), num_rows,
+                                         num_cols, num_non_zeros, rowptr, colind,
+                                         values, diagonal, alpha, in, beta, out,
+                                         k, nullptr),
+                   "spmv_hip_csr_spmm_f32");
+  }
+}
+
+template <typename T>
 void CSRSpMV<T>::finalize(const HipExecutor&) const
 {
   spmv_hip_csr_plan_destroy(plan());
@@ -330,6 +362,25 @@ void CSRMatrix<T>::mult(T alpha, T* in, T beta, T* out) const
   }
   if (this->_num_non_zeros > 0 || this->_diagonal != nullptr) // :85
     this->_exec->spmv_run(_op, *this, alpha, in, beta, out);
+}
+
+template <typename T>
+void CSRMatrix<T>::mult_block(T alpha, const T* in, T beta, T* out, int k) const
+{
+  if (k < 1)
+    throw std::runtime_error("CSRMatrix::mult_block: k must be at least 1");
+  auto* hip = dynamic_cast<const HipExecutor*>(this->_exec.get());
+  if (!hip)
+    throw std::runtime_error(
+        "spmv::HostExecutor::mult_block: this build has no CPU compute path; "
+        "create the matrix with a HipExecutor");
+  // (an empty block without a diagonal launches nothing, as in mult(): :85)
+  if (this->_num_non_zeros == 0 && this->_diagonal == nullptr)
+    return;
+  const bool mixed = _mixed_on && this->_num_non_zeros > 0;
+  _op.run_block(this->_num_rows, this->_num_cols, this->_num_non_zeros, _rowptr,
+                _colind, _values, mixed ? _values32 : nullptr, this->_diagonal,
+                alpha, in, beta, out, k, *hip);
 }
 
 template <typename T>

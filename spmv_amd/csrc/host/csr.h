@@ -94,6 +94,15 @@ public:
                      const T* values, T alpha, const T* in, T beta, T* out,
                      const HipExecutor& exec) const;
 
+  // The multi-vector product (spmv_hip_csr_spmm_*): `in` / `out` are blocks of
+  // k INTERLEAVED vectors (element (i, c) at [i * k + c]); column c of `out`
+  // has the bits of run() on column c of `in`.  values32 != nullptr: the
+  // mixed-precision product on that fp32 copy of the values (fp64 blocks).
+  void run_block(int32_t num_rows, int32_t num_cols, int64_t num_non_zeros,
+                 const int32_t* rowptr, const int32_t* colind, const T* values,
+                 const float* values32, const T* diagonal, T alpha, const T* in,
+                 T beta, T* out, int k, const HipExecutor& exec) const;
+
   bool symmetric() const { return _symmetric; }
   spmv_hip_csr_plan* plan() const
   {
@@ -187,6 +196,11 @@ public:
                   int32_t col_end) const;
   // eager build of the map for [col_begin, col_end) (before release_csr)
   void enable_transpose(int32_t col_begin, int32_t col_end) const;
+
+  // out = alpha*A*in + beta*out for blocks of k interleaved vectors (element
+  // (i, c) at [i * k + c]; `in` cols() x k, `out` rows() x k): column by column
+  // the bits of mult().  Honours use_mixed() as mult() does.
+  void mult_block(T alpha, const T* in, T beta, T* out, int k) const;
 
   const int32_t* rowptr() const { return _rowptr; }
   const int32_t* colind() const { return _colind; }

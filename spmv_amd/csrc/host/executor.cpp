@@ -351,6 +351,22 @@ void HipExecutor::gather_ghosts_run(int num_indices, const int32_t* indices,
                  "spmv_hip_gather_f64");
 }
 
+void HipExecutor::gather_ghosts_block_run(int num_indices, const int32_t* indices,
+                                          int k, const float* in, float* out) const
+{
+  throw_on_error(spmv_hip_gather_block_f32(_ctx, num_indices, indices, k, in, out,
+                                           nullptr),
+                 "spmv_hip_gather_block_f32");
+}
+void HipExecutor::gather_ghosts_block_run(int num_indices, const int32_t* indices,
+                                          int k, const double* in,
+                                          double* out) const
+{
+  throw_on_error(spmv_hip_gather_block_f64(_ctx, num_indices, indices, k, in, out,
+                                           nullptr),
+                 "spmv_hip_gather_block_f64");
+}
+
 void HipExecutor::scatter_add_run(int num_indices, const int32_t* indices,
                                   const float* in, float* out) const
 {

@@ -217,6 +217,12 @@ public:
   void stream_wait_event(void* stream, void* event) const;
   void synchronize_stream(void* stream) const;
   void synchronize_event(void* event) const;
+  // ghost pack of a block of k interleaved vectors (spmv_hip_gather_block_*):
+  // out[g * k + c] = in[indices[g] * k + c]
+  void gather_ghosts_block_run(int num_indices, const int32_t* indices, int k,
+                               const float* in, float* out) const;
+  void gather_ghosts_block_run(int num_indices, const int32_t* indices, int k,
+                               const double* in, double* out) const;
   // owner-side accumulate of L2GMap::reverse_update (distinct indices)
   void scatter_add_run(int num_indices, const int32_t* indices, const float* in,
                        float* out) const;

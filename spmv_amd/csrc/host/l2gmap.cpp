@@ -293,7 +293,7 @@ bool L2GMap::overlapping() const // :975-981
 }
 
 template <typename T>
-void L2GMap::start_exchange(T* vec) const
+void L2GMap::start_exchange(T* vec, int k) const
 {
   if (!_hip)
     throw std::runtime_error(
@@ -305,8 +305,12 @@ void L2GMap::start_exchange(T* vec) const
 
   const void* send_base = vec;
   if (!_direct_send) {
-    const size_t need = sizeof(T) * static_cast<size_t>(_num_indices > 0 ? _num_indices : 1);
+    const size_t need = sizeof(T) * static_cast<size_t>(k)
+                        * static_cast<size_t>(_num_indices > 0 ? _num_indices : 1);
     if (_send_buf == nullptr || _send_buf_bytes < need) { // :607-614
+      // (a regrown buffer: the exchange before this one may still read the old)
+      if (_send_buf != nullptr)
+        _hip->synchronize_stream(_comm_stream);
       _exec->free(_send_buf);
       _send_buf = _exec->alloc<char>(need);
       _send_buf_bytes = need;
@@ -314,8 +318,12 @@ void L2GMap::start_exchange(T* vec) const
     // pack on the comm stream through the executor interface (:618)
     _hip->set_stream(_comm_stream);
     try {
-      _exec->gather_ghosts_run(_num_indices, _indexbuf, vec,
-                               static_cast<T*>(_send_buf));
+      if (k == 1)
+        _exec->gather_ghosts_run(_num_indices, _indexbuf, vec,
+                                 static_cast<T*>(_send_buf));
+      else
+        _hip->gather_ghosts_block_run(_num_indices, _indexbuf, k, vec,
+                                      static_cast<T*>(_send_buf));
     } catch (...) {
       _hip->set_stream(compute);
       throw;
@@ -326,13 +334,16 @@ void L2GMap::start_exchange(T* vec) const
   // receive straight into the ghost tail (:624-628), send packed or direct
   // data (:630-634); one grouped call, ordered on the comm stream; the
   // argument lists were built with the plan
-  if (_put) // one-sided models: peer stores, one launch
+  // (a block of k > 1 vectors: always two-sided -- the peer windows hold one
+  // 8-byte element per ghost)
+  if (_put && k == 1) // one-sided models: peer stores, one launch
     throw_on_error(spmv_hip_put_exchange(_hip->context(), _put, sizeof(T),
                                          send_base, vec + local_size(),
                                          _comm_stream),
                    "spmv_hip_put_exchange");
   else
-    _comm->neighbor_exchange(sizeof(T), _neighbours, send_base, _x_send_count,
+    _comm->neighbor_exchange(sizeof(T) * static_cast<size_t>(k), _neighbours,
+                             send_base, _x_send_count,
                              _x_send_offset, vec, _x_recv_count, _x_recv_offset,
                              _comm_stream);
   _hip->record_event(_ev_done, _comm_stream);
@@ -354,6 +365,26 @@ void L2GMap::update_finalise(T*) const // :899-905
   if (_neighbours.empty() || !overlapping())
     return;
   _hip->stream_wait_event(_hip->get_stream(), _ev_done); // no host wait
+}
+
+template <typename T>
+void L2GMap::update_block(T* vec, int k) const
+{
+  if (k < 1)
+    throw std::runtime_error("L2GMap::update_block: k must be at least 1");
+  if (_neighbours.empty())
+    return;
+  start_exchange(vec, k);
+  if (!overlapping())
+    _hip->stream_wait_event(_hip->get_stream(), _ev_done);
+}
+
+template <typename T>
+void L2GMap::update_finalise_block(T* vec, int k) const
+{
+  if (k < 1)
+    throw std::runtime_error("L2GMap::update_finalise_block: k must be at least 1");
+  update_finalise(vec); // (the event does not depend on the element size)
 }
 
 // Ghost tail -> owners, accumulating (L2GMap.cpp:907-959).  The transfer is the
@@ -400,6 +431,10 @@ template void L2GMap::update<float>(float*) const;
 template void L2GMap::update<double>(double*) const;
 template void L2GMap::update_finalise<float>(float*) const;
 template void L2GMap::update_finalise<double>(double*) const;
+template void L2GMap::update_block<float>(float*, int) const;
+template void L2GMap::update_block<double>(double*, int) const;
+template void L2GMap::update_finalise_block<float>(float*, int) const;
+template void L2GMap::update_finalise_block<double>(double*, int) const;
 template void L2GMap::reverse_update<float>(float*) const;
 template void L2GMap::reverse_update<double>(double*) const;
 

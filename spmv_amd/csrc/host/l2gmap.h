@@ -60,6 +60,17 @@ public:
   void update(T* vec_data) const;
   template <typename T>
   void update_finalise(T* vec_data) const;
+  // The same for a block of k INTERLEAVED vectors (element (i, c) at
+  // vec[i * k + c], (local_size() + num_ghosts()) * k elements): the plan,
+  // streams and events of update() with elements of k * sizeof(T) bytes.  A
+  // contiguous halo is sent straight from the block, any other is packed by
+  // the block gather kernel.  k == 1 is update().  On a one-sided map
+  // (onesided()) a block with k > 1 goes through the two-sided
+  // neighbor_exchange: the peer windows are sized for 8-byte elements.
+  template <typename T>
+  void update_block(T* vec_data, int k) const;
+  template <typename T>
+  void update_finalise_block(T* vec_data, int k) const;
   // Reverse halo (L2GMap.cpp:907-959): every ghost-tail value is sent to its
   // owner and ADDED to the owner's entry; the ghost tail itself is unchanged.
   // Stream-ordered on the executor's stream; the host does not wait.
@@ -122,7 +133,7 @@ private:
   void* _ev_done = nullptr;  // exchange finished on the comm stream
 
   template <typename T>
-  void start_exchange(T* vec_data) const;
+  void start_exchange(T* vec_data, int k = 1) const;
 };
 
 } // namespace spmv

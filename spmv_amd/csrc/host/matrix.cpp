@@ -153,6 +153,22 @@ void Matrix<T>::spmv_sym_overlap(T* x, T* y) const
   _mat_remote->mult(1, x, 1, y);
 }
 
+// The four variants of mult() for a block of k interleaved vectors.
+template <typename T>
+void Matrix<T>::mult_block(T* X, T* Y, int k) const
+{
+  if (k < 1)
+    throw std::runtime_error("Matrix::mult_block: k must be at least 1");
+  const bool overlap = _col_map->overlapping();
+  _mat_local->mult_block(1, X, 0, Y, k); // (overlap: while the halo is in flight)
+  if (overlap)
+    _col_map->update_finalise_block(X, k);
+  if (_symmetric)
+    _mat_remote->mult_block(1, X, 1, Y, k);
+  else if (overlap)
+    _mat_remote->mult_block(1, X, _mat_local->non_zeros() > 0 ? T(1) : T(0), Y, k);
+}
+
 // ---------------------------------------------------------------------------
 // transposed product (Matrix.h:78-81)
 // ---------------------------------------------------------------------------

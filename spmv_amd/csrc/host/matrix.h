@@ -51,6 +51,11 @@ public:
   // y = A x ; x must hold local_size + num_ghosts entries and col_map()->
   // update(x) must have been called (Matrix.cpp:131-141).  Device pointers.
   void mult(T* x, T* y) const;
+  // Y = A X for a block of k INTERLEAVED vectors: element (i, c) of X lives at
+  // X[i * k + c]; X holds (local_size + num_ghosts) * k entries, refreshed by
+  // col_map()->update_block(X, k), Y rows() * k.  Column c of Y has the bits
+  // of mult() on column c of X.  The same four variants as mult().
+  void mult_block(T* X, T* Y, int k) const;
   // mult + the dot product x.y fused into the SpMV kernels where possible.
   // Emits partial sums into dot_local / dot_remote (each
   // spmv_hip_dot_partials_len() device doubles; their total is x[0:rows].y).

@@ -301,6 +301,24 @@ class CsrBlock:
              _p(self.rowptr), _p(self.colind), v, float(alpha), x_ptr,
              float(beta), y_ptr, stream)
 
+    def multm(self, alpha, x_ptr, beta, y_ptr, k, values=None, mixed=False,
+              stream=None):
+        """spmv_hip_csr_spmm_*: Y = alpha A X + beta Y for k INTERLEAVED vectors
+        (element (i, c) at X[i * k + c]; X: ncols * k, Y: nrows * k).  `values`:
+        another device array of the block's values; mixed=True: `values` is an
+        fp32 copy under fp64 vectors (fp64 general blocks)."""
+        v = _p(self.values) if values is None else values
+        if mixed:
+            assert self.dtype == np.float64 and values is not None
+            name, diag = "spmv_hip_csr_spmm_f32f64", None
+        else:
+            name = ("spmv_hip_csr_spmm_f64" if self.dtype == np.float64
+                    else "spmv_hip_csr_spmm_f32")
+            diag = _p(self.diagonal)
+        call(name, self.ctx.h, self.plan, self.nrows, self.ncols, self.nnz,
+             _p(self.rowptr), _p(self.colind), v, diag, float(alpha), x_ptr,
+             float(beta), y_ptr, int(k), stream)
+
     def free(self):
         if self.plan:
             call("spmv_hip_csr_plan_destroy", self.plan)
@@ -312,6 +330,32 @@ class CsrBlock:
 
 def _p(buf):
     return None if buf is None else buf.ptr
+
+
+def _suffix(dtype):
+    return "f64" if np.dtype(dtype) == np.float64 else "f32"
+
+
+def interleave(ctx, n, k, cols_ptr, out_ptr, ld=None, dtype=np.float64,
+               stream=None):
+    """k columns (column c at cols + c * ld, ld >= n) -> the interleaved n x k
+    block: out[i * k + c] = cols[c * ld + i]"""
+    call("spmv_hip_interleave_" + _suffix(dtype), ctx.h, int(n), int(k),
+         cols_ptr, int(n if ld is None else ld), out_ptr, stream)
+
+
+def deinterleave(ctx, n, k, in_ptr, cols_ptr, ld=None, dtype=np.float64,
+                 stream=None):
+    """the interleaved n x k block -> k columns: cols[c * ld + i] = in[i * k + c]"""
+    call("spmv_hip_deinterleave_" + _suffix(dtype), ctx.h, int(n), int(k), in_ptr,
+         int(n if ld is None else ld), cols_ptr, stream)
+
+
+def gather_block(ctx, num_indices, indices_ptr, k, in_ptr, out_ptr,
+                 dtype=np.float64, stream=None):
+    """out[g * k + c] = in[indices[g] * k + c]"""
+    call("spmv_hip_gather_block_" + _suffix(dtype), ctx.h, int(num_indices),
+         indices_ptr, int(k), in_ptr, out_ptr, stream)
 
 
 def poisson3d_block(ctx, n, row_begin, row_end, part, with_diagonal=False,

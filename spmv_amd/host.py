@@ -86,6 +86,14 @@ _PROTOS = {
     "spmvh_matrix_transpmult": [vp, vp, vp],
     "spmvh_matrix_enable_transpose": [vp],
     "spmvh_matrix_f32_transpmult": [vp, vp, vp],
+    "spmvh_matrix_mult_block": [vp, vp, vp, C.c_int],
+    "spmvh_matrix_update_block": [vp, vp, C.c_int],
+    "spmvh_matrix_update_finalise_block": [vp, vp, C.c_int],
+    "spmvh_matrix_f32_mult_block": [vp, vp, vp, C.c_int],
+    "spmvh_matrix_f32_update_block": [vp, vp, C.c_int],
+    "spmvh_matrix_f32_update_finalise_block": [vp, vp, C.c_int],
+    "spmvh_l2gmap_update_block": [vp, vp, C.c_int],
+    "spmvh_l2gmap_update_finalise_block": [vp, vp, C.c_int],
     "spmvh_split_create": [vp, vp, vp, i64, i64, i64, i64, vp, i64, C.c_int,
                            C.c_int, PTR(vp), PTR(i64)],
     "spmvh_split_get": [vp, C.c_int, vp, vp, vp],
@@ -318,6 +326,13 @@ class L2GMap:
     def update(self, x_ptr):
         call("spmvh_l2g_map_update", self.h, x_ptr)
 
+    def update_block(self, x_ptr, k):
+        """update() of a block of k interleaved fp64 vectors"""
+        call("spmvh_l2gmap_update_block", self.h, x_ptr, int(k))
+
+    def update_finalise_block(self, x_ptr, k):
+        call("spmvh_l2gmap_update_finalise_block", self.h, x_ptr, int(k))
+
     def reverse_update(self, x_ptr, f32=False):
         call("spmvh_l2g_map_reverse_update_f32" if f32
              else "spmvh_l2g_map_reverse_update", self.h, x_ptr)
@@ -382,6 +397,14 @@ class ColMapView:
 
     def update_finalise(self, x_ptr):
         call("spmvh_matrix_update_finalise", self.A.h, x_ptr)
+
+    def update_block(self, x_ptr, k):
+        """update() of a block of k interleaved vectors: element (i, c) at
+        X[i * k + c], (local_size + num_ghosts) * k entries"""
+        call("spmvh_matrix_update_block", self.A.h, x_ptr, int(k))
+
+    def update_finalise_block(self, x_ptr, k):
+        call("spmvh_matrix_update_finalise_block", self.A.h, x_ptr, int(k))
 
 
 class Matrix:
@@ -514,6 +537,12 @@ class Matrix:
     def mult(self, x_ptr, y_ptr):
         call("spmvh_matrix_mult", self.h, x_ptr, y_ptr)
 
+    def mult_block(self, x_ptr, y_ptr, k):
+        """Y = A X for k interleaved vectors (element (i, c) at X[i * k + c]): X
+        holds (local_size + num_ghosts) * k entries, Y rows * k; column by
+        column the bits of mult()."""
+        call("spmvh_matrix_mult_block", self.h, x_ptr, y_ptr, int(k))
+
     def transpmult(self, b_ptr, y_ptr):
         """y = A^T b: b holds rows() entries, y local_size + num_ghosts (the
         ghost tail goes to its owners with col_map's reverse_update)."""
@@ -557,6 +586,15 @@ class MatrixF32:
 
     def transpmult(self, b_ptr, y_ptr):
         call("spmvh_matrix_f32_transpmult", self.h, b_ptr, y_ptr)
+
+    def mult_block(self, x_ptr, y_ptr, k):
+        call("spmvh_matrix_f32_mult_block", self.h, x_ptr, y_ptr, int(k))
+
+    def update_block(self, x_ptr, k):
+        call("spmvh_matrix_f32_update_block", self.h, x_ptr, int(k))
+
+    def update_finalise_block(self, x_ptr, k):
+        call("spmvh_matrix_f32_update_finalise_block", self.h, x_ptr, int(k))
 
     def close(self):
         if self.h:
