@@ -105,7 +105,11 @@ int spmv_hip_ctx_get_option(const spmv_hip_ctx* ctx, const char* key, int64_t* v
  *   switches the form off.
  *   "lx_max_x_bytes": ... and only for matrices whose input vector
  *   (num_cols * 8 bytes) is at most this large.  Default 128 MiB (the form
- *   pays while x stays in the Infinity Cache). */
+ *   pays while x stays in the Infinity Cache).
+ *   "lx_codes" (0 / 1, default 1): ... with a second index array of 4-bit
+ *   codes (0.5 B per entry) for the row blocks whose offsets are the row's
+ *   lane plus one of at most 16 distances; the LDS-DMA kernel streams it in
+ *   place of the 16-bit offsets (plan keys "lx4", "lx4_blocks", "lx4_all"). */
 
 /* ---- streams / events ---------------------------------------------------
  * CudaExecutor::set/reset/get_cuda_stream (cuda/cuda_executor.h:72-76). */
@@ -337,6 +341,11 @@ int spmv_hip_zwalk_table(int32_t num_rows, int64_t plane_rows, int grid,
  *                  diagonals on a 3-D lattice: lattice lines per lane (1, 2,
  *                  4), its own plane-walk table, workgroups per CU
  *   "lxw" "lxw_blocks_per_cu"            LX form: the LDS-DMA kernel on/off
+ *   "lx4" "lx4_lut"                      ... streaming 4-bit codes in place of
+ *                  the 16-bit offsets for the row blocks that have them (1 needs
+ *                  the codes: context option "lx_codes", default 1, at plan
+ *                  creation; same launch grid, same bits); lx4_lut: the
+ *                  dictionary look-up, 1 = LDS table, 2 = select tree
  *   "xw" "xw_probe"                      the same kernel on the caller's CSR
  *                  arrays (plans with XW records): on/off -- 1 asks for it by
  *                  name and ends the probe --; xw_probe 1 = let the next four
@@ -361,7 +370,9 @@ int spmv_hip_csr_plan_set(spmv_hip_csr_plan* plan, const char* key, int value);
  * "zwalk_grid", "lat_chain", "sdia_chain", "sdia_nt", "sdia_offsets" (lower
  * offsets of the baked copy), "sdia_general" (baked from a general matrix: 1 = symmetric, half stored; 2 =
  * full form), "sdia_mixed" (fp32 copy), "sdia_const" (constant diagonals: no
- * values kept), "sdia_tile" (lines per lane in use), "sdia_tile_walk"; "lxw";
+ * values kept), "sdia_tile" (lines per lane in use), "sdia_tile_walk"; "lxw",
+ * "lxw_grid" (its fp64 launch grid), "lx4" (4-bit codes in use), "lx4_blocks"
+ * (row blocks that have codes), "lx4_all" (every staged block has), "lx4_lut";
  * "xw", "xw_staged" (row blocks with staged windows), "xw_pick" (1 = the XW
  * kernel runs, 0 = the plan's probe found the gather kernel faster, -1 = the
  * probe's four launches are not all complete), "xw_probe_xw_us",

@@ -29,6 +29,10 @@ struct spmv_hip_ctx {
   // x windows by LDS-DMA one row block ahead; "lx_dma", 0 = the register-staged
   // kernel's layout)
   int lx_dma = 1;
+  // ... with 4-bit codes beside the 16-bit offsets for the row blocks that have
+  // at most 16 distinct (offset - row lane) ("lx_codes"; 0.5 B per entry of
+  // plan memory, streamed by the DMA kernel in place of the offsets)
+  int lx_codes = 1;
   // the host mirror's CSRMatrix frees its device copies of colind / values
   // once a plan holds the matrix in its own format ("release_csr";
   // spmv_hip_csr_plan_owns_matrix); read by the mirror, nothing here acts on it

@@ -152,13 +152,28 @@ constexpr int kLxGap = 16;   // columns closer than this share a window
 //   [3] number of staged pieces (low byte) | (staged position of column
 //       rb * kRows + 1) << 8 when the block's own columns [rb * kRows, + rows)
 //       lie inside one staged window, 0 there otherwise: the fused dot's x_i
+//       ; bit kLxwCodedBit: the block's offsets also exist as 4-bit codes
 //   [kLxwPieces0 + p]  first column of piece p (kLxwPiece elements each)
+//   [kLxwDict0 + k]    coded blocks: dictionary entries 2k (low half) and
+//                      2k + 1 (high half), signed 16 bit each -- an entry of
+//                      row lane t with code c is staged at t + dict[c]
 constexpr int kLxwPiece = 128;     // staged elements per piece
 constexpr int kLxwMaxPieces = 16;  // 2048 staged elements (16 KiB fp64)
 constexpr int kLxwPieces0 = 4;
 constexpr int kLxwNpMask = 0xff;   // word [3]: pieces
 constexpr int kLxwOwnShift = 8;    // ... own position + 1
-constexpr int kLxwRec = 20;        // ints per record (4 + 16)
+constexpr int kLxwOwnMask = 0xfffff;
+constexpr int kLxwCodedBit = 30;   // ... 4-bit codes + dictionary present
+constexpr int kLxwDict0 = kLxwPieces0 + kLxwMaxPieces; // 20
+constexpr int kLxwDictSize = 16;   // distinct (offset - row lane) per coded block
+constexpr int kLxwRec = 28;        // ints per record (4 + 16 + 8)
+// bytes of the 4-bit code array of `nnz` entries (two entries per byte, entry
+// j in nibble j & 1 of byte j / 2): padded so that the 16-byte chunks around
+// any span of entries lie inside it
+__host__ __device__ constexpr int64_t lx_code_bytes(int64_t nnz)
+{
+  return (((nnz + 1) >> 1) + 16 + 15) & ~(int64_t)15;
+}
 constexpr int kLxwAlign = 4;       // window starts: multiples of 4 columns
 // XW: the same kernel on the CALLER's column indices (no 16-bit copy): the
 // record carries, after the LXW words, the windows themselves -- an entry's
@@ -436,6 +451,17 @@ struct spmv_hip_csr_plan {
   int lxw_max_cnt = 0;        // most entries in a staged row block
   int lxw_max_pieces = 0;     // most staged pieces of a row block
   int lxw_blocks_per_cu = 0;  // 0 = what the LDS footprint allows
+  // ... with 4-bit codes in place of the 16-bit offsets (a SECOND index array,
+  // 0.5 B per entry, beside lx_lidx): an offset is the row's lane t plus one of
+  // the few distances d the block's diagonals and windows give; a row block
+  // with at most 16 distinct d carries them as a dictionary in its record and
+  // the DMA kernel streams its codes, any other block its 16-bit offsets.
+  // Built with the DMA records unless the context option "lx_codes" is 0.
+  uint8_t* lx_code = nullptr; // lx_code_bytes(nnz)
+  int lx4 = 0;                // use the codes (plan_set "lx4")
+  int lx4_blocks = 0;         // coded row blocks
+  int lx4_lut = 1;            // dictionary look-up: 1 = LDS table, 2 = select
+                              // tree on uniform registers (plan_set "lx4_lut")
   // XW: the LDS-DMA kernel on the caller's CSR arrays as they are (values,
   // 32-bit column indices), x windows staged: what a plan without lattice / LX
   // / sliced jagged form runs instead of the gather kernel (spmv_lxw.hip)

@@ -237,6 +237,11 @@ int spmv_hip_ctx_set_option(spmv_hip_ctx* ctx, const char* key, int64_t value)
     ctx->lx_dma = (int)value;
     return SPMV_HIP_OK;
   }
+  if (!strcmp(key, "lx_codes")) {
+    SPMV_REQUIRE(value == 0 || value == 1);
+    ctx->lx_codes = (int)value;
+    return SPMV_HIP_OK;
+  }
   if (!strcmp(key, "poisson_stencil")) {
     SPMV_REQUIRE(value == 7 || value == 27);
     ctx->poisson_stencil = (int)value;

@@ -184,6 +184,103 @@ __global__ __launch_bounds__(kBlock) void lx_build_kernel(
   }
 }
 
+// 4-bit codes of the LX form's DMA kernel: one workgroup per row block (lane =
+// row).  An offset is the row's lane t plus a distance d that depends only on
+// the diagonal and the window of the entry; a staged block with at most
+// kLxwDictSize distinct d gets them, ascending, as a dictionary in its record
+// (two signed 16-bit values per word) and one nibble per entry in `code` --
+// the rank of the entry's d.  Any other block is left alone: it keeps reading
+// its 16-bit offsets.  Two blocks may share a 32-bit word of `code` where their
+// spans meet: whole words are stored, the partial ones at both ends are OR-ed
+// into the zeroed array.  stat[0] counts the coded blocks.
+constexpr int kLx4Dmin = -kRows;                      // d = offset - t > -kRows
+constexpr int kLx4Words = (kLxwMaxPieces * kLxwPiece + kRows + 31) / 32; // 72
+__global__ __launch_bounds__(kBlock) void lx4_encode_kernel(
+    int32_t num_rows, const int32_t* __restrict__ rowptr,
+    const uint16_t* __restrict__ lidx, int32_t* __restrict__ wrec,
+    uint32_t* __restrict__ code, int num_row_blocks, int32_t* __restrict__ stat)
+{
+  constexpr int CAP = kBlock * 16; // most entries of a staged block
+  __shared__ uint32_t s_bits[kLx4Words]; // bit (d - kLx4Dmin): d occurs
+  __shared__ int32_t s_rank[kLx4Words + 1]; // set bits below word w
+  __shared__ int32_t s_dict[kLxwDictSize];
+  __shared__ uint32_t s_pack[CAP / 8 + 2]; // the block's nibbles, by word of `code`
+  const int t = threadIdx.x;
+  int coded = 0;
+  for (int rb = blockIdx.x; rb < num_row_blocks; rb += gridDim.x) {
+    int32_t* wr = wrec + (int64_t)rb * kLxwRec;
+    const int32_t a = wr[1], cnt = wr[2];
+    const int nwin = wr[0];
+    __syncthreads(); // previous block done with the shared arrays
+    if (nwin < 0 || cnt <= 0 || cnt > CAP)
+      continue; // uniform
+    const int32_t a0 = a & ~7; // first entry of the first word
+    const int nwords = (int)(((int64_t)a + cnt + 7 - a0) >> 3);
+    for (int w = t; w < kLx4Words; w += kBlock)
+      s_bits[w] = 0;
+    for (int w = t; w < nwords; w += kBlock)
+      s_pack[w] = 0;
+    if (t < kLxwDictSize)
+      s_dict[t] = 0;
+    __syncthreads();
+    const int32_t r = rb * kRows + t;
+    int32_t lo = 0, hi = 0;
+    if (r < num_rows) {
+      lo = rowptr[r];
+      hi = rowptr[r + 1];
+    }
+    for (int32_t j = lo; j < hi; ++j) {
+      const int b = (int)lidx[j] - t - kLx4Dmin;
+      atomicOr(&s_bits[b >> 5], 1u << (b & 31));
+    }
+    __syncthreads();
+    if (t == 0) {
+      int n = 0;
+      for (int w = 0; w < kLx4Words; ++w) {
+        s_rank[w] = n;
+        n += __popc(s_bits[w]);
+      }
+      s_rank[kLx4Words] = n;
+    }
+    __syncthreads();
+    if (s_rank[kLx4Words] > kLxwDictSize)
+      continue; // uniform
+    for (int w = t; w < kLx4Words; w += kBlock) {
+      uint32_t m = s_bits[w];
+      int k = s_rank[w];
+      while (m) {
+        const int b = __ffs(m) - 1;
+        m &= m - 1;
+        s_dict[k++] = w * 32 + b + kLx4Dmin;
+      }
+    }
+    for (int32_t j = lo; j < hi; ++j) {
+      const int b = (int)lidx[j] - t - kLx4Dmin;
+      const uint32_t c
+          = (uint32_t)(s_rank[b >> 5] + __popc(s_bits[b >> 5] & ((1u << (b & 31)) - 1u)));
+      const int q = j - a0;
+      atomicOr(&s_pack[q >> 3], c << ((q & 7) * 4));
+    }
+    __syncthreads();
+    for (int w = t; w < nwords; w += kBlock) {
+      const bool whole = (w > 0 || a0 == a) && (int64_t)a0 + 8 * (w + 1) <= (int64_t)a + cnt;
+      uint32_t* dst = code + ((int64_t)a0 >> 3) + w;
+      if (whole)
+        *dst = s_pack[w];
+      else if (s_pack[w])
+        atomicOr(dst, s_pack[w]);
+    }
+    if (t < kLxwDictSize / 2)
+      wr[kLxwDict0 + t] = (s_dict[2 * t] & 0xffff) | (s_dict[2 * t + 1] << 16);
+    if (t == 0) {
+      wr[3] |= 1 << kLxwCodedBit;
+      ++coded;
+    }
+  }
+  if (t == 0 && coded)
+    atomicAdd(&stat[0], coded);
+}
+
 struct NonEmptyRow {
   const int32_t* rowptr;
   __device__ bool operator()(int i) const { return rowptr[i + 1] > rowptr[i]; }
@@ -297,11 +394,55 @@ void spmv_free_lx(spmv_hip_csr_plan* pl)
   (void)hipFree(pl->lx_lidx);
   (void)hipFree(pl->lx_tab);
   (void)hipFree(pl->lxw_rec);
+  (void)hipFree(pl->lx_code);
   pl->lx_lidx = nullptr;
   pl->lx_tab = nullptr;
   pl->lxw_rec = nullptr;
+  pl->lx_code = nullptr;
   pl->lx = pl->lx_staged = pl->lx_blocks = 0;
   pl->lxw = pl->lxw_max_cnt = pl->lxw_max_pieces = 0;
+  pl->lx4 = pl->lx4_blocks = 0;
+}
+
+// The 4-bit codes of the DMA kernel (lx4_encode_kernel), after the records and
+// the 16-bit offsets: 0.5 B per entry.  Out of memory: the plan goes without.
+static int build_lx_codes(spmv_hip_csr_plan* pl, const int32_t* rowptr, int nrb,
+                          hipStream_t st)
+{
+  const size_t bytes = (size_t)lx_code_bytes(pl->nnz);
+  int32_t* d_stat = nullptr;
+  hipError_t e = hipMalloc(&pl->lx_code, bytes);
+  if (e == hipSuccess)
+    e = hipMalloc(&d_stat, sizeof(int32_t));
+  if (e == hipSuccess)
+    e = hipMemsetAsync(pl->lx_code, 0, bytes, st);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(d_stat, 0, sizeof(int32_t), st);
+  int32_t coded = 0;
+  if (e == hipSuccess) {
+    int grid = pl->ctx->num_cus * 8;
+    grid = grid > nrb ? nrb : grid;
+    hipLaunchKernelGGL(lx4_encode_kernel, dim3(grid), dim3(kBlock), 0, st,
+                       pl->num_rows, rowptr, pl->lx_lidx, pl->lxw_rec,
+                       reinterpret_cast<uint32_t*>(pl->lx_code), nrb, d_stat);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(&coded, d_stat, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st);
+  (void)hipFree(d_stat);
+  if (e != hipSuccess || coded == 0) {
+    (void)hipGetLastError();
+    (void)hipFree(pl->lx_code);
+    pl->lx_code = nullptr;
+    pl->lx4 = pl->lx4_blocks = 0;
+    return e == hipSuccess || e == hipErrorOutOfMemory ? SPMV_HIP_OK
+                                                       : static_cast<int>(e);
+  }
+  pl->lx4_blocks = coded;
+  pl->lx4 = 1;
+  return SPMV_HIP_OK;
 }
 
 void spmv_free_xw(spmv_hip_csr_plan* pl)
@@ -563,6 +704,11 @@ int spmv_build_lx(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   }
   pl->lx = 1;
   pl->lxw = pl->lxw_rec != nullptr;
+  if (pl->lxw_rec && pl->ctx->lx_codes) {
+    const int rc = build_lx_codes(pl, rowptr, nrb, st);
+    if (rc != SPMV_HIP_OK)
+      return rc;
+  }
   // XCD grouping with staged x: still +3.5 % while x lives in the Infinity
   // Cache (216^3: 0.170 vs 0.176 ms), but 1.3-1.8 % slower than the plain
   // order once it does not (512^3)

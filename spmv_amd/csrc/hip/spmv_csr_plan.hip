@@ -603,6 +603,16 @@ int spmv_hip_csr_plan_set(spmv_hip_csr_plan* plan, const char* key, int value)
     if (plan->zw_table && plan->lx_lidx && !plan->lat_tab) // another grid
       return spmv_zwalk_order_build(plan, plan->zw_d2, spmv_walk_grid(plan), 0,
                                     true);
+  } else if (!strcmp(key, "lx4")) {
+    // ... streaming 4-bit codes where a row block has them (needs the codes:
+    // ctx "lx_codes"); the launch geometry does not depend on it
+    SPMV_REQUIRE(value == 0 || value == 1);
+    SPMV_REQUIRE(value == 0 || plan->lx_code);
+    plan->lx4 = value;
+  } else if (!strcmp(key, "lx4_lut")) {
+    // the dictionary look-up of a coded block: 1 = LDS table, 2 = select tree
+    SPMV_REQUIRE(value == 1 || value == 2);
+    plan->lx4_lut = value;
   } else if (!strcmp(key, "xw")) {
     // the LDS-DMA kernel on the caller's CSR arrays (needs its records)
     SPMV_REQUIRE(value == 0 || plan->xw_rec);
@@ -898,6 +908,8 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
       b += 2 * (nnz + 8) + 4 * nrb * kLxRec;
     if (plan->lxw_rec)
       b += 4 * nrb * kLxwRec;
+    if (plan->lx_code)
+      b += lx_code_bytes(nnz);
     if (plan->xw_rec)
       b += 4 * nrb * kXwRec;
     if (plan->lat_tab)
@@ -999,6 +1011,16 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
     *value = plan->lx;
   else if (!strcmp(key, "lxw"))
     *value = plan->lxw && plan->lxw_rec ? 1 : 0;
+  else if (!strcmp(key, "lx4"))
+    *value = plan->lx4 && plan->lx_code ? 1 : 0;
+  else if (!strcmp(key, "lx4_blocks"))
+    *value = plan->lx_code ? plan->lx4_blocks : 0;
+  else if (!strcmp(key, "lx4_all"))
+    *value = plan->lx_code && plan->lx4_blocks == plan->lx_staged ? 1 : 0;
+  else if (!strcmp(key, "lx4_lut"))
+    *value = plan->lx4_lut;
+  else if (!strcmp(key, "lxw_grid")) // launch grid of the DMA kernel (fp64)
+    *value = plan->lxw_rec ? spmv_lxw_grid(plan, 8) : 0;
   else if (!strcmp(key, "lx_staged"))
     *value = plan->lx_staged;
   else if (!strcmp(key, "lx_blocks"))

@@ -35,6 +35,7 @@
 //
 // LDS per workgroup (dynamic, sized by the plan): 2 x (values slot + offsets
 // slot + x buffer); 60 KiB for the 7-point matrix => 2 workgroups per CU.
+// (A coded block's codes use a quarter of its offsets slot, see below.)
 //
 // Measured at 512^3 (7-point matrix, lattice analysis off; one process, the
 // kernels alternating): 2.24-2.51 ms against 2.39-2.48 ms for the
@@ -62,6 +63,35 @@
 // instead of one (three value slots, 75 KiB per workgroup, still two per CU:
 // 2.51 against 2.54 ms at 512^3, 3 % slower at 128^3 and 384^3 -- the bytes a
 // workgroup has in flight are not what bounds the kernel either).
+//
+// 4-bit codes (template parameter C4, plan key "lx4"): three quarters of the
+// offsets stream say nothing new -- an offset is the row's lane t plus a
+// distance d that depends only on the entry's diagonal and window, and a
+// 7-point row block has at most seven of them.  The plan (lx4_encode_kernel,
+// spmv_csr_forms.hip) gives every staged block with at most 16 distinct d a
+// dictionary (8 more words of its record: it arrives with the same vector
+// load a step ahead) and one nibble per entry in a SECOND index array, 0.5 B
+// per entry; such a block's issue() sends its codes into the offsets slot
+// instead of its 16-bit offsets, any other block does what it did (the
+// 16-bit array stays: the register-staged kernel and lx4 = 0 read it).  The
+// row sum reads a row's eight nibbles as two aligned dwords and a funnel
+// shift and turns each into t + dict[code]; values, x reads and the order of
+// the adds are untouched.  Slots, LDS size, grid and row-block order do not
+// depend on it, so the fused dot's partials keep their bits.
+// Measured at 512^3 (profiles/lx4_ab.json; one process, the variants
+// alternating, fused dot on, median of 7 x 10 launches): codes off 2.317 ms,
+// dictionary as an LDS table per slot 2.175 ms (-6.1 %), as eight uniform
+// registers and a select tree (7 selects, a shift pair per entry) 2.375 ms
+// -- SLOWER than the offsets: here the arithmetic is no longer free.  The
+// table is the default ("lx4_lut" 2 selects the tree).  Inside CG
+// (rocprofv3 kernel trace of the benchmark) 2.421 -> 2.244 ms; fabric reads
+// (FETCH_SIZE, calibrated on a streaming dot in the same run) 12.56 ->
+// 10.49 GB per launch, more than the 1.41 GB the stream lost: fewer x pieces
+// are evicted from the L2 between their uses.  The step: 252.5 -> 263.2 it/s,
+// five alternating runs each, ranges apart.  The plan pass: 4.6 ms beside
+// lx_build_kernel's 14.2 ms, +0.49 GB of plan memory.  Not tried: sizing the
+// offsets slot for codes only (a third workgroup per CU would change the
+// grid and with it the partials); byte row lengths instead of the row pointer.
 //
 // XW variant (round 5): the same kernel on the CALLER's CSR arrays as they are.
 // The 16-bit offsets are a plan-owned copy of the index stream (2 B per entry
@@ -93,6 +123,7 @@ struct LxwBlock {
   int np;        // staged pieces
   int own;       // staged position of the block's first row's OWN column
                  // (x[rb * kRows] -- the fused dot's x), -1 = not staged
+  int coded;     // its offsets also exist as 4-bit codes + a dictionary
 };
 
 // A block's record travels as ONE vector load (lane l holds word l) issued a
@@ -114,7 +145,7 @@ __device__ __forceinline__ int32_t lxw_fetch(int rb,
 
 __device__ __forceinline__ LxwBlock lxw_decode(int rb, int32_t w)
 {
-  LxwBlock b{-1, -1, 0, 0, 0, -1};
+  LxwBlock b{-1, -1, 0, 0, 0, -1, 0};
   if (rb >= 0) {
     b.rb = rb;
     b.nwin = __builtin_amdgcn_readlane(w, 0);
@@ -122,7 +153,8 @@ __device__ __forceinline__ LxwBlock lxw_decode(int rb, int32_t w)
     b.cnt = __builtin_amdgcn_readlane(w, 2);
     const int32_t w3 = __builtin_amdgcn_readlane(w, 3);
     b.np = w3 & kLxwNpMask;
-    b.own = (w3 >> kLxwOwnShift) - 1;
+    b.own = ((w3 >> kLxwOwnShift) & kLxwOwnMask) - 1;
+    b.coded = (w3 >> kLxwCodedBit) & 1;
   }
   return b;
 }
@@ -171,12 +203,21 @@ __device__ __forceinline__ LxwRegs<T> lxw_loads(const LxwBlock& blk, int t,
 //          it lets the computed alternative overwrite that register.
 //   XW     the index stream is the caller's `colind` (lidx unused), the
 //          record is the XW one (kXwRec ints: windows behind the pieces)
-template <typename TV, typename T, bool DOT, bool NT, bool TAB, bool XW>
+//   C4     != 0: a row block whose record says so streams its 4-bit codes
+//          (`code`, 0.5 B per entry) into the offsets slot instead of the
+//          16-bit offsets; an entry of row lane t with code c is staged at
+//          t + dict[c], the dictionary being 8 words of the record.  The
+//          look-up: 1 = a 32-byte LDS table per slot, written by the lanes
+//          that hold those words; 2 = the words as uniform registers (taken
+//          with v_readlane right after the wait, like the piece list) and a
+//          select tree.  The branch is uniform per row block; 0 compiles to
+//          the kernel without any of it.
+template <typename TV, typename T, bool DOT, bool NT, bool TAB, bool XW, int C4>
 __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
     int32_t num_rows, int32_t num_cols, int64_t nnz,
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
     const TV* __restrict__ values, const uint16_t* __restrict__ lidx,
-    const int32_t* __restrict__ rec, T alpha, const T* __restrict__ in, T beta,
+    const uint8_t* __restrict__ code, const int32_t* __restrict__ rec, T alpha, const T* __restrict__ in, T beta,
     T* __restrict__ out, DotOut dot, RowBlockOrder ord, int vcap, int lcap,
     int xcap)
 {
@@ -194,6 +235,9 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
   T* const s_x = reinterpret_cast<T*>(smem + 2 * (size_t)vcap * sizeof(TV)
                                       + 2 * (size_t)lcap * sizeof(IDX));
   __shared__ double s_red[kBlock / 64];
+  // C4 == 1: the dictionaries of the two slots, two 16-bit entries per word
+  __shared__ int32_t s_dict[C4 == 1 ? 2 * kLxwDictSize / 2 : 1];
+  static_assert(!(XW && C4), "the XW records carry no dictionary");
 
   const int t = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -208,6 +252,18 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
   auto fits = [&](const LxwBlock& b) {
     return b.cnt + (b.a & (V - 1)) <= vcap && b.cnt + (b.a & IA) <= lcap;
   };
+  // does the block stream its 4-bit codes?  (they and the dword behind a
+  // row's last one lie inside the offsets slot: always, by the slot's size --
+  // at least 1 KiB and 2 B per entry --, checked all the same)
+  auto coded = [&](const LxwBlock& b) {
+    if constexpr (C4 != 0)
+      return b.coded != 0
+             && (b.cnt + (b.a & 31) + 7) / 8 * 4 + 8
+                    <= lcap * (int)sizeof(IDX);
+    else
+      return false;
+  };
+  const int64_t code_len = lx_code_bytes(nnz);
   // A wave's share of a block's piece list: pieces wave, wave + 4, ... as
   // UNIFORM values, extracted from the per-lane list right after a wait -- a
   // v_readlane of a loaded register in the middle of the DMA issue would make
@@ -225,9 +281,15 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
     return pc;
   };
   // DMA of one block's streams and windows into slot `sl`
-  auto issue = [&](const LxwBlock& b, const Pieces& pc, int sl) {
+  auto issue = [&](const LxwBlock& b, const Pieces& pc, int32_t w, int sl) {
     if (b.rb < 0 || b.cnt <= 0 || !fits(b))
       return;
+    if constexpr (C4 == 1) {
+      // the slot's dictionary: the lanes of wave 0 that hold its words (the
+      // record has landed; the slot's readers left it before the barrier)
+      if (coded(b) && t >= kLxwDict0 && t < kLxwDict0 + kLxwDictSize / 2)
+        s_dict[sl * (kLxwDictSize / 2) + t - kLxwDict0] = w;
+    }
     const int64_t a = b.a, e = (int64_t)b.a + b.cnt;
     lat_issue_dma<TV, NT>(values, nnz, a & ~(int64_t)(V - 1), e,
                           s_val + (size_t)sl * vcap, t);
@@ -236,6 +298,10 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
     if constexpr (XW)
       lat_issue_dma<int32_t, NT>(colind, nnz, a & ~(int64_t)IA, e,
                                  s_lidx + (size_t)sl * lcap, t);
+    else if (coded(b))
+      lat_issue_dma<uint8_t, NT>(
+          code, code_len, (a >> 1) & ~(int64_t)15, (e + 1) >> 1,
+          reinterpret_cast<uint8_t*>(s_lidx + (size_t)sl * lcap), t);
     else
       lat_issue_dma<uint16_t, NT>(lidx, nnz + 8, a & ~(int64_t)IA, e,
                                   s_lidx + (size_t)sl * lcap, t);
@@ -269,7 +335,7 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
     nxt_w = lxw_fetch<REC>(nxt_rb, rec);
     cur = lxw_decode(rb0, w0);
     cur_w0 = w0;
-    issue(cur, pieces_of(w0), 0);
+    issue(cur, pieces_of(w0), w0, 0);
   }
   int nn_raw = slot_raw(it + 2 * stride);
   LxwRegs<T> gA = lxw_loads<T>(cur, t, num_rows, rowptr, in, beta, out);
@@ -304,6 +370,21 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
     return ws;
   };
   Windows cur_ws = windows_of(cur_w0);
+  // C4 == 2: the current block's dictionary as uniform values
+  struct Dict {
+    int32_t w[kLxwDictSize / 2];
+  };
+  auto dict_of = [&](int32_t w) {
+    Dict dc;
+#pragma unroll
+    for (int k = 0; k < kLxwDictSize / 2; ++k) {
+      dc.w[k] = 0;
+      if constexpr (C4 == 2)
+        dc.w[k] = __builtin_amdgcn_readlane(w, kLxwDict0 + k);
+    }
+    return dc;
+  };
+  Dict cur_dc = dict_of(cur_w0);
 
   auto step = [&](const LxwRegs<T>& g, LxwRegs<T>& gn) {
     // everything this wave has in flight has landed; after the barrier that
@@ -316,7 +397,8 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
     r_late = -1;
     const LxwBlock nxt = lxw_decode(nxt_rb, nxt_w);
     const Windows nxt_ws = windows_of(nxt_w);
-    issue(nxt, pieces_of(nxt_w), slot ^ 1);
+    const Dict nxt_dc = dict_of(nxt_w);
+    issue(nxt, pieces_of(nxt_w), nxt_w, slot ^ 1);
     gn = lxw_loads<T>(nxt, t, num_rows, rowptr, in, beta, out);
     // the block after the next one: its table entry has landed with the wait
     // above; its record is needed a step from now
@@ -341,6 +423,55 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
             if (cur.own >= 0) { // uniform
               x_own = sx[cur.own + t];
               own_staged = true;
+            }
+          }
+          if (coded(cur)) { // uniform
+            // The same walk on the codes: a row's eight nibbles are two
+            // aligned dwords and a funnel shift; a nibble past the row's end
+            // is another row's (its position may lie outside the buffer): it
+            // reads position 0 and is not added.
+            const uint32_t* sc = reinterpret_cast<const uint32_t*>(
+                s_lidx + (size_t)slot * lcap);
+            const int32_t n0 = cur.a & ~31; // the entry of the slot's nibble 0
+            for (; j < hi; j += 8) {
+              const unsigned n = (unsigned)(j - n0);
+              const uint32_t c_lo = sc[n >> 3], c_hi = sc[(n >> 3) + 1];
+              const uint32_t bits
+                  = __builtin_amdgcn_alignbit(c_hi, c_lo, (n & 7) * 4);
+              unsigned l[8];
+              T v[8], xv[8];
+#pragma unroll
+              for (int k = 0; k < 8; ++k) {
+                const int32_t jj = j + k < hi ? j + k : hi - 1;
+                v[k] = (T)sv[jj];
+              }
+#pragma unroll
+              for (int k = 0; k < 8; ++k) {
+                const unsigned c = (bits >> (4 * k)) & 15u;
+                int32_t d;
+                if constexpr (C4 == 1) {
+                  d = reinterpret_cast<const int16_t*>(
+                      s_dict + slot * (kLxwDictSize / 2))[c];
+                } else {
+                  const int32_t p0 = c & 2 ? cur_dc.w[1] : cur_dc.w[0];
+                  const int32_t p1 = c & 2 ? cur_dc.w[3] : cur_dc.w[2];
+                  const int32_t p2 = c & 2 ? cur_dc.w[5] : cur_dc.w[4];
+                  const int32_t p3 = c & 2 ? cur_dc.w[7] : cur_dc.w[6];
+                  const int32_t q0 = c & 4 ? p1 : p0;
+                  const int32_t q1 = c & 4 ? p3 : p2;
+                  const int32_t pr = c & 8 ? q1 : q0;
+                  // low half (even code) or high half, sign-extended
+                  d = (int32_t)((uint32_t)pr << (16 - 16 * (int)(c & 1))) >> 16;
+                }
+                l[k] = j + k < hi ? (unsigned)(t + d) : 0u;
+              }
+#pragma unroll
+              for (int k = 0; k < 8; ++k)
+                xv[k] = sx[l[k]];
+#pragma unroll
+              for (int k = 0; k < 8; ++k)
+                if (j + k < hi)
+                  sum += v[k] * xv[k];
             }
           }
           // eight entries' LDS reads in flight (offsets, then values and x:
@@ -399,6 +530,7 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
     slot ^= 1;
     cur = nxt;
     cur_ws = nxt_ws;
+    cur_dc = nxt_dc;
     nxt_rb = nn_rb;
     nxt_w = nn_w;
     nn_raw = nnn_raw;
@@ -465,11 +597,14 @@ int lxw_grid(const spmv_hip_csr_plan* pl, int elem_bytes, int idx_bytes)
   return grid;
 }
 
-template <typename TV, typename T, bool DOT, bool XW>
-int lxw_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
-               const int32_t* rowptr, const int32_t* colind, const TV* values,
-               T alpha, const T* in, T beta, T* out, DotOut dot)
+template <typename TV, typename T, bool DOT, bool XW, int C4>
+int lxw_launch_c(const spmv_hip_csr_plan* pl, hipStream_t st,
+                 const int32_t* rowptr, const int32_t* colind, const TV* values,
+                 T alpha, const T* in, T beta, T* out, DotOut dot)
 {
+  // (the geometry does not depend on C4: the codes take a quarter of the
+  // offsets slot, and the grid, the row-block order and with them the fused
+  // dot's partials stay what they are without the codes)
   const LxwGeom g = lxw_geom(pl, (int)sizeof(T), XW ? 4 : 2);
   const int nrb = (pl->num_rows + kRows - 1) / kRows;
   const int grid = lxw_grid(pl, (int)sizeof(T), XW ? 4 : 2);
@@ -481,20 +616,38 @@ int lxw_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
   }
   auto kern
       = ord.table
-            ? (pl->nontemporal ? csr_lxw_kernel<TV, T, DOT, true, true, XW>
-                               : csr_lxw_kernel<TV, T, DOT, false, true, XW>)
-            : (pl->nontemporal ? csr_lxw_kernel<TV, T, DOT, true, false, XW>
-                               : csr_lxw_kernel<TV, T, DOT, false, false, XW>);
+            ? (pl->nontemporal ? csr_lxw_kernel<TV, T, DOT, true, true, XW, C4>
+                               : csr_lxw_kernel<TV, T, DOT, false, true, XW, C4>)
+            : (pl->nontemporal ? csr_lxw_kernel<TV, T, DOT, true, false, XW, C4>
+                               : csr_lxw_kernel<TV, T, DOT, false, false, XW, C4>);
   if (g.lds > 48 * 1024) // beyond the default dynamic-LDS limit
     SPMV_CHECK_HIP(hipFuncSetAttribute(
         reinterpret_cast<const void*>(kern),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), g.lds, st, pl->num_rows,
                      pl->num_cols, pl->nnz, rowptr, colind, values,
-                     XW ? nullptr : pl->lx_lidx, XW ? pl->xw_rec : pl->lxw_rec,
-                     alpha, in, beta, out, dot, ord, g.vcap, g.lcap, g.xcap);
+                     XW ? nullptr : pl->lx_lidx, C4 ? pl->lx_code : nullptr,
+                     XW ? pl->xw_rec : pl->lxw_rec, alpha, in, beta, out, dot,
+                     ord, g.vcap, g.lcap, g.xcap);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
+}
+
+template <typename TV, typename T, bool DOT, bool XW>
+int lxw_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
+               const int32_t* rowptr, const int32_t* colind, const TV* values,
+               T alpha, const T* in, T beta, T* out, DotOut dot)
+{
+  if constexpr (!XW) {
+    if (pl->lx4 && pl->lx_code)
+      return pl->lx4_lut == 2
+                 ? lxw_launch_c<TV, T, DOT, XW, 2>(pl, st, rowptr, colind, values,
+                                                   alpha, in, beta, out, dot)
+                 : lxw_launch_c<TV, T, DOT, XW, 1>(pl, st, rowptr, colind, values,
+                                                   alpha, in, beta, out, dot);
+  }
+  return lxw_launch_c<TV, T, DOT, XW, 0>(pl, st, rowptr, colind, values, alpha,
+                                         in, beta, out, dot);
 }
 
 } // namespace
