@@ -653,6 +653,32 @@ int spmv_hip_cg_update_r_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
 int spmv_hip_cg_update_xp_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                                  int64_t n, const double* r, double* x,
                                  double* p, void* stream);
+/* update_xp_cs with the x update deferred by one iteration: p lives in two
+ * buffers that swap, x is read and written every second iteration (9 vector
+ * passes per pair of iterations instead of 10; every element sees the same
+ * operations in the same order, so the bits are those of update_xp_cs).
+ *   update_p2_cs  (iteration k, k odd from a fresh start): [r.r partials] ->
+ *                 rr[k]; stop test; p_out = beta p_in + r.  x is not touched
+ *                 unless iteration k meets the tolerance: then x += alpha_k
+ *                 p_in and nothing is pending.
+ *   update_x2p_cs (iteration k >= 2 after an update_p2_cs of k-1, p_prev its
+ *                 p_in and p_cur its p_out): -> rr[k]; x += alpha_(k-1) p_prev;
+ *                 x += alpha_k p_cur; stop test; p_prev = beta p_cur + r.
+ *   flush_x       after a loop that ended with update_p2_cs of iteration k:
+ *                 x += alpha_k p (its p_in), unless the solve is done or
+ *                 iteration k met the tolerance.
+ * Every vector 16-byte aligned; p_in / p_out (p_prev / p_cur) distinct. */
+int spmv_hip_cg_update_p2_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
+                                 int64_t n, const double* r, double* x,
+                                 const double* p_in, double* p_out,
+                                 void* stream);
+int spmv_hip_cg_update_x2p_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
+                                  int64_t n, const double* r, double* x,
+                                  double* p_prev, const double* p_cur,
+                                  void* stream);
+int spmv_hip_cg_flush_x_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
+                            int64_t n, const double* p, double* x,
+                            void* stream);
 /* CG start (cg.cpp:39-50) in one pass: r = p = b, x = 0, partials of r.r in
  * the workspace (then spmv_hip_cg_reduce_rr(0) installs rr[0]) */
 int spmv_hip_cg_init_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int64_t n,

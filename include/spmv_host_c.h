@@ -303,7 +303,8 @@ int spmvh_petsc_rows_destroy(spmvh_petsc_rows* rows);
 /* Same solve with the optional arguments of the C++ overload: a reusable
  * spmv::CgWorkspace (may be NULL) and per-iteration HIP-event timing of the
  * local-block SpMV kernel (time_spmv bit 0 -> *spmv_ms_total, *spmv_launches;
- * bit 2 switches CgOptions::consumer_reductions off). */
+ * bit 2 switches CgOptions::consumer_reductions off, bit 3 CgOptions::defer_x;
+ * bits 8-15 set CgOptions::poll_every). */
 typedef struct spmvh_cg_workspace spmvh_cg_workspace;
 /* cg with CgOptions::mixed (fp32 copy of the matrix values in the SpMV,
  * residual replacement every `replace_every` iterations, fp64 correction

@@ -9,6 +9,11 @@
 //         plus single-workgroup reducers.  alpha, beta and the stopping test
 //         are evaluated on the device from the scalar history rr[], pAp[];
 //         precedent for device-resident scalars: cuda/cg.cuda.cu:14-38,73-84.
+//         On one rank the x update is deferred by one iteration
+//         (cg_update_p2_cs_kernel / cg_update_x2p_cs_kernel, see there): x is
+//         read and written every second iteration, 9 vector passes per pair
+//         on the x/p side instead of 10, same bits.  The price is a second p
+//         vector in the workspace (8 N bytes: 1.07 GB at 512^3).
 //
 // Built with -ffp-contract=off: axpy/scal round like unfused BLAS-1.
 //
@@ -226,6 +231,70 @@ __device__ __forceinline__ void stream_update_xp(int64_t n2, double alpha,
       pv[u].x += rv[u].x;
       pv[u].y += rv[u].y;
       vstore<NT>(p, i, pv[u]);
+    }
+  }
+}
+
+// p_out = beta p_in + r (cg.cpp:84-85) into the OTHER p buffer; p_in stays
+template <bool NT>
+__device__ __forceinline__ void stream_update_p2(int64_t n2, double beta,
+                                                 const double* r,
+                                                 const double* p_in,
+                                                 double* p_out)
+{
+  SPMV_FOR_UNITS(n2)
+  {
+    f64x2 pv[kU], rv[kU];
+    SPMV_FOR_LANE_ELEMS(i, n2)
+    {
+      pv[u] = vload<NT>(p_in, i);
+      rv[u] = vload<NT>(r, i);
+    }
+    SPMV_FOR_LANE_ELEMS(i, n2)
+    {
+      pv[u].x = beta * pv[u].x;
+      pv[u].y = beta * pv[u].y;
+      pv[u].x += rv[u].x;
+      pv[u].y += rv[u].y;
+      vstore<NT>(p_out, i, pv[u]);
+    }
+  }
+}
+
+// x += alpha0 p0 ; x += alpha1 p1 (cg.cpp:69 of two consecutive iterations,
+// in their order) ; with UPDATE_P also p0 = beta p1 + r (:84-85), in place
+// over the older direction: the lane that writes an element has read it
+template <bool NT, bool UPDATE_P>
+__device__ __forceinline__ void stream_update_x2p(int64_t n2, double alpha0,
+                                                  double alpha1, double beta,
+                                                  const double* r, double* x,
+                                                  double* p0, const double* p1)
+{
+  SPMV_FOR_UNITS(n2)
+  {
+    f64x2 qv[kU], pv[kU], xv[kU], rv[kU];
+    SPMV_FOR_LANE_ELEMS(i, n2)
+    {
+      qv[u] = vload<NT>(p0, i);
+      pv[u] = vload<NT>(p1, i);
+      xv[u] = vload<NT>(x, i);
+      if constexpr (UPDATE_P)
+        rv[u] = vload<NT>(r, i);
+    }
+    SPMV_FOR_LANE_ELEMS(i, n2)
+    {
+      xv[u].x += alpha0 * qv[u].x;
+      xv[u].y += alpha0 * qv[u].y;
+      xv[u].x += alpha1 * pv[u].x;
+      xv[u].y += alpha1 * pv[u].y;
+      vstore<NT>(x, i, xv[u]);
+      if constexpr (UPDATE_P) {
+        pv[u].x = beta * pv[u].x;
+        pv[u].y = beta * pv[u].y;
+        pv[u].x += rv[u].x;
+        pv[u].y += rv[u].y;
+        vstore<NT>(p0, i, pv[u]);
+      }
     }
   }
 }
@@ -547,6 +616,122 @@ __global__ __launch_bounds__(kBlock) void cg_update_xp_cs_kernel(
     x[i] += alpha * p[i];
     p[i] = beta * p[i] + r[i];
   }
+}
+
+// ---- the x update deferred by one iteration (one rank, CgOptions::defer_x) --
+// Nothing inside an iteration reads x, so cg_update_xp_cs_kernel's pass over
+// it is spent twice per pair of iterations for one accumulation each.  With p
+// kept in two buffers that swap, a pair becomes
+//   P   (iteration k):   rr[k]; stop test; p_out = beta p_in + r     3 passes
+//   X2P (iteration k+1): rr[k+1]; x += a_k p_prev; x += a_k+1 p_cur;
+//                        stop test; p_prev = beta p_cur + r          6 passes
+// instead of 2 x 5.  Every multiply and add of an element is the one of
+// cg_update_xp_cs_kernel, in its order, and a_k is recomputed from the history
+// with the same expression: x, p, r and the scalars keep their bits.
+// An iteration that meets the tolerance applies whatever x update is pending
+// and leaves p alone, as before (:80-81); a loop that ends on a P step is
+// closed by cg_flush_x_kernel.
+
+// P step: reduce_partials_kernel (r.r) + stop test + p update, x deferred
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void cg_update_p2_cs_kernel(
+    int64_t n, int k, double* __restrict__ rr, const double* __restrict__ pAp,
+    CgScalars* __restrict__ sc, const double* __restrict__ rr_partials, int len,
+    const double* __restrict__ r, double* __restrict__ x,
+    const double* __restrict__ p_in, double* __restrict__ p_out)
+{
+  __shared__ double s_red[kBlock / 64];
+  __shared__ double s_bcast;
+  if (sc->done)
+    return;
+  const double rr_new
+      = consume_partials(rr_partials, nullptr, len, s_red, &s_bcast);
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    rr[k] = rr_new;
+  const double rnorm0 = sqrt(rr[0]);
+  const double rnorm_old = sqrt(rr[k - 1]);
+  const double rnorm_new = sqrt(rr_new);                                 // :76
+  const double alpha = (rnorm_old * rnorm_old) / pAp[k];                 // :66
+  const double beta = (rnorm_new * rnorm_new) / (rnorm_old * rnorm_old); // :77
+  const bool converged = rnorm_new / rnorm0 < sc->rtol;                  // :80
+  if (converged) { // x takes this iteration's update now, p stays (:80-81)
+    stream_axpy<NT>(n >> 1, alpha, p_in, x);
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+      x[n - 1] += alpha * p_in[n - 1];
+    return;
+  }
+  stream_update_p2<NT>(n >> 1, beta, r, p_in, p_out);
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int64_t i = n - 1;
+    p_out[i] = beta * p_in[i] + r[i];
+  }
+}
+
+// X2P step (k >= 2): the x updates of iterations k-1 and k, then the p update
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void cg_update_x2p_cs_kernel(
+    int64_t n, int k, double* __restrict__ rr, const double* __restrict__ pAp,
+    CgScalars* __restrict__ sc, const double* __restrict__ rr_partials, int len,
+    const double* __restrict__ r, double* __restrict__ x,
+    double* __restrict__ p_prev, const double* __restrict__ p_cur)
+{
+  __shared__ double s_red[kBlock / 64];
+  __shared__ double s_bcast;
+  if (sc->done)
+    return;
+  const double rr_new
+      = consume_partials(rr_partials, nullptr, len, s_red, &s_bcast);
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    rr[k] = rr_new;
+  const double rnorm0 = sqrt(rr[0]);
+  const double rnorm_old2 = sqrt(rr[k - 2]);
+  const double rnorm_old = sqrt(rr[k - 1]);
+  const double rnorm_new = sqrt(rr_new);                                 // :76
+  const double alpha_prev = (rnorm_old2 * rnorm_old2) / pAp[k - 1]; // :66, k-1
+  const double alpha = (rnorm_old * rnorm_old) / pAp[k];                 // :66
+  const double beta = (rnorm_new * rnorm_new) / (rnorm_old * rnorm_old); // :77
+  const bool converged = rnorm_new / rnorm0 < sc->rtol;                  // :80
+  const bool tail = (n & 1) && blockIdx.x == 0 && threadIdx.x == 0;
+  const int64_t i = n - 1;
+  if (converged) { // x takes both updates, p stays (:80-81)
+    stream_update_x2p<NT, false>(n >> 1, alpha_prev, alpha, beta, r, x, p_prev,
+                                 p_cur);
+    if (tail) {
+      x[i] += alpha_prev * p_prev[i];
+      x[i] += alpha * p_cur[i];
+    }
+    return;
+  }
+  stream_update_x2p<NT, true>(n >> 1, alpha_prev, alpha, beta, r, x, p_prev,
+                              p_cur);
+  if (tail) {
+    x[i] += alpha_prev * p_prev[i];
+    x[i] += alpha * p_cur[i];
+    p_prev[i] = beta * p_cur[i] + r[i];
+  }
+}
+
+// After a loop whose last iteration k was a P step: x += a_k p_k, unless the
+// solve has stopped (`done`) or iteration k itself met the tolerance -- then
+// the P step's converged branch has applied it, and `done` is only raised by
+// the next iteration's r kernel, which never ran.
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(
+    int64_t n, int k, const double* __restrict__ rr,
+    const double* __restrict__ pAp, const CgScalars* __restrict__ sc,
+    const double* __restrict__ p, double* __restrict__ x)
+{
+  if (sc->done)
+    return;
+  const double rnorm0 = sqrt(rr[0]);
+  const double rnorm_old = sqrt(rr[k - 1]);
+  const double rnorm_new = sqrt(rr[k]);
+  if (rnorm_new / rnorm0 < sc->rtol) // :80, as cg_update_p2_cs_kernel
+    return;
+  const double alpha = (rnorm_old * rnorm_old) / pAp[k]; // :66
+  stream_axpy<NT>(n >> 1, alpha, p, x);
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+    x[n - 1] += alpha * p[n - 1];
 }
 
 // CG start (cg.cpp:39-50) in one pass over b: r = p = b, x0 = 0 (defined here
@@ -1086,6 +1271,57 @@ int spmv_hip_cg_update_xp_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
   SPMV_LAUNCH_NT(ctx, n, cg_update_xp_cs_kernel, grid, spmv_stream(ctx, stream),
                  n, k, ws->rr, ws->pAp, ws->sc, ws->partials_rr,
                  ctx->dot_blocks, r, x, p);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_cg_update_p2_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
+                                 int64_t n, const double* r, double* x,
+                                 const double* p_in, double* p_out,
+                                 void* stream)
+{
+  SPMV_SET_DEVICE(ctx);
+  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && n >= 0);
+  SPMV_REQUIRE(n == 0 || (r && x && p_in && p_out && p_in != p_out));
+  SPMV_REQUIRE(aligned16(r) && aligned16(x) && aligned16(p_in)
+               && aligned16(p_out));
+  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
+  SPMV_LAUNCH_NT(ctx, n, cg_update_p2_cs_kernel, grid, spmv_stream(ctx, stream),
+                 n, k, ws->rr, ws->pAp, ws->sc, ws->partials_rr,
+                 ctx->dot_blocks, r, x, p_in, p_out);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_cg_update_x2p_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
+                                  int64_t n, const double* r, double* x,
+                                  double* p_prev, const double* p_cur,
+                                  void* stream)
+{
+  SPMV_SET_DEVICE(ctx);
+  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 2 && k <= ws->kmax && n >= 0);
+  SPMV_REQUIRE(n == 0 || (r && x && p_prev && p_cur && p_prev != p_cur));
+  SPMV_REQUIRE(aligned16(r) && aligned16(x) && aligned16(p_prev)
+               && aligned16(p_cur));
+  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
+  SPMV_LAUNCH_NT(ctx, n, cg_update_x2p_cs_kernel, grid,
+                 spmv_stream(ctx, stream), n, k, ws->rr, ws->pAp, ws->sc,
+                 ws->partials_rr, ctx->dot_blocks, r, x, p_prev, p_cur);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_cg_flush_x_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
+                            int64_t n, const double* p, double* x,
+                            void* stream)
+{
+  SPMV_SET_DEVICE(ctx);
+  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && n >= 0);
+  SPMV_REQUIRE(n == 0 || (p && x));
+  SPMV_REQUIRE(aligned16(p) && aligned16(x));
+  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
+  SPMV_LAUNCH_NT(ctx, n, cg_flush_x_kernel, grid, spmv_stream(ctx, stream), n,
+                 k, ws->rr, ws->pAp, ws->sc, p, x);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }

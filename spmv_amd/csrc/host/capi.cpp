@@ -1063,6 +1063,7 @@ int spmvh_cg_mixed(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     CgOptions opt;
     opt.time_spmv = (time_spmv & 1) != 0;
     opt.consumer_reductions = (time_spmv & 4) == 0;
+    opt.defer_x = (time_spmv & 8) == 0;
     opt.mixed = true;
     opt.replace_every = replace_every;
     CgStats st;
@@ -1096,6 +1097,7 @@ int spmvh_cg_ex(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     CgOptions opt;
     opt.time_spmv = (time_spmv & 1) != 0;
     opt.consumer_reductions = (time_spmv & 4) == 0; // bit 2 switches it off
+    opt.defer_x = (time_spmv & 8) == 0;             // bit 3 likewise
     if ((time_spmv >> 8) & 0xff) // bits 8-15: CgOptions::poll_every (0 = default)
       opt.poll_every = (time_spmv >> 8) & 0xff;
     CgStats st;

@@ -45,13 +45,14 @@ void CgWorkspace::release()
     _exec.free(Ap);
     _exec.free(x);
     _exec.free(p);
+    _exec.free(p2);
     _exec.free(dot2);
     spmv_hip_host_free(_exec.context(), flags);
   } catch (...) {
   }
   timing_ev.clear();
   ws = nullptr;
-  r = Ap = x = p = dot2 = nullptr;
+  r = Ap = x = p = p2 = dot2 = nullptr;
   flags = nullptr;
   stream = poll_event = nullptr;
   kmax_cap = -1;
@@ -87,10 +88,18 @@ void CgWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len)
   if (N_padded > n_cap) {
     _exec.free(x);
     _exec.free(p);
+    _exec.free(p2);
+    p2 = nullptr; // ensure_p2() brings it back at the new size
     x = _exec.alloc<double>(N_padded); // cg.cpp:41-42
     p = _exec.alloc<double>(N_padded);
     n_cap = N_padded;
   }
+}
+
+void CgWorkspace::ensure_p2()
+{
+  if (!p2 && n_cap > 0)
+    p2 = _exec.alloc<double>(n_cap);
 }
 
 void CgWorkspace::reserve_timing(int iterations)
@@ -168,10 +177,19 @@ int cg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   const bool mixed = opt.mixed && A.enable_mixed();
   const bool x_aligned = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
   double* const xi = (mixed || !x_aligned) ? w.x : x;
+  // CgOptions::defer_x: p_k lives in buffer (k - 1) & 1, every solve starts
+  // on buffer 0 with no x update pending
+  const bool defer = opt.defer_x && opt.consumer_reductions && comm.size() == 1
+                     && !mixed && x_aligned;
+  if (defer)
+    w.ensure_p2();
+  double* const pbuf[2] = {w.p, defer ? w.p2 : w.p};
   // r = p = b, x0 = 0, partials of r.r: one pass (cg.cpp:41-47; x0 and the
   // ghost tails are defined here instead of relying on fresh pages)
   if (N_padded > M) {
     exec.memset<double>(w.p + M, 0, N_padded - M);
+    if (defer)
+      exec.memset<double>(w.p2 + M, 0, N_padded - M);
     if (mixed)
       exec.memset<double>(w.x + M, 0, N_padded - M);
   }
@@ -211,7 +229,8 @@ int cg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   bool poll_pending = false;
   while (k < kmax && !stopped) { // cg.cpp:55
     ++k;
-    col_l2g->update(w.p); // cg.cpp:59 (starts on the side stream)
+    double* const pk = pbuf[(k - 1) & 1];
+    col_l2g->update(pk); // cg.cpp:59 (starts on the side stream)
     void* ev1 = nullptr;
     if (opt.time_spmv) {
       ev1 = timing_ev[2 * (size_t)(k - 1) + 1];
@@ -256,18 +275,27 @@ int cg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
       ++replacements;
     } else if (consume) {
       // one rank: the update kernels add the partials themselves
-      const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
+      const bool fused = A.mult_dot(pk, w.Ap, partials, w.dot2, ev1);
       if (!fused)
-        throw_on_error(spmv_hip_dot_partial_f64(ctx, M, w.p, w.Ap, partials,
+        throw_on_error(spmv_hip_dot_partial_f64(ctx, M, pk, w.Ap, partials,
                                                 nullptr),
                        "spmv_hip_dot_partial_f64");
       throw_on_error(spmv_hip_cg_update_r_cs_f64(ctx, w.ws, k, M, w.Ap, w.r,
                                                  fused ? w.dot2 : nullptr,
                                                  nullptr),
                      "spmv_hip_cg_update_r_cs_f64");
-      throw_on_error(spmv_hip_cg_update_xp_cs_f64(ctx, w.ws, k, M, w.r, xi,
-                                                  w.p, nullptr),
-                     "spmv_hip_cg_update_xp_cs_f64");
+      if (!defer)
+        throw_on_error(spmv_hip_cg_update_xp_cs_f64(ctx, w.ws, k, M, w.r, xi,
+                                                    w.p, nullptr),
+                       "spmv_hip_cg_update_xp_cs_f64");
+      else if (k & 1) // P step: p_(k+1) into the other buffer, x += a_k p_k waits
+        throw_on_error(spmv_hip_cg_update_p2_cs_f64(ctx, w.ws, k, M, w.r, xi,
+                                                    pbuf[0], pbuf[1], nullptr),
+                       "spmv_hip_cg_update_p2_cs_f64");
+      else // X2P step: both x updates, p_(k+1) over p_(k-1) in buffer 0
+        throw_on_error(spmv_hip_cg_update_x2p_cs_f64(ctx, w.ws, k, M, w.r, xi,
+                                                     pbuf[0], pbuf[1], nullptr),
+                       "spmv_hip_cg_update_x2p_cs_f64");
     } else {
       const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
       if (fused) {
@@ -314,6 +342,13 @@ int cg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
       }
     }
   }
+
+  // The loop ended on a P step: its x update is still pending (the kernel
+  // does nothing if the solve has stopped or iteration k met the tolerance).
+  if (defer && (k & 1))
+    throw_on_error(spmv_hip_cg_flush_x_f64(ctx, w.ws, k, M, pbuf[0], xi,
+                                           nullptr),
+                   "spmv_hip_cg_flush_x_f64");
 
   // final state: {done, kstop} and the squared-residual history
   // (the device history has the WORKSPACE's capacity, which an earlier solve

@@ -30,6 +30,9 @@ public:
   // events for CgOptions::time_spmv of a solve of up to `iterations` steps,
   // created ahead of it (a benchmark keeps them out of its timed region)
   void reserve_timing(int iterations);
+  // the second p buffer of CgOptions::defer_x, allocated by the first solve
+  // that takes that path (after ensure())
+  void ensure_p2();
   void release();
 
   HipExecutor& _exec;
@@ -37,6 +40,7 @@ public:
   int kmax_cap = -1;
   int64_t m_cap = -1, n_cap = -1;
   double *r = nullptr, *Ap = nullptr, *x = nullptr, *p = nullptr;
+  double* p2 = nullptr;     // CgOptions::defer_x: the second p buffer (n_cap)
   double* dot2 = nullptr;   // partials of the remote block's p.Ap share
   int32_t* flags = nullptr; // pinned {done, kstop}
   void* stream = nullptr;   // compute stream of the solve
@@ -53,6 +57,13 @@ struct CgOptions {
   // than one rank (or when switched off) every dot product is finished by a
   // single-workgroup reducer kernel (5 launches per iteration).
   bool consumer_reductions = true;
+  // With consumer_reductions on one rank (fp64, every vector 16-byte aligned):
+  // nothing inside an iteration reads x, so its update is deferred by one
+  // iteration and two of them are applied in one pass, in their order and
+  // with their roundings (same bits).  p alternates between two buffers; the
+  // x/p side of a pair of iterations takes 9 vector passes instead of 10, for
+  // one more work vector (8 bytes per row).  Elsewhere it has no effect.
+  bool defer_x = true;
   // Mixed precision: the SpMV of every iteration streams an
   // fp32 copy of the matrix values (half the matrix bytes; x, p, r and all
   // arithmetic stay fp64).  Every `replace_every` iterations the recurrence

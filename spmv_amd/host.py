@@ -679,7 +679,8 @@ def cg(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, history=True):
 
 
 def cg_mixed(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, replace_every=50,
-             workspace=None, time_spmv=False, consumer_reductions=True):
+             workspace=None, time_spmv=False, consumer_reductions=True,
+             defer_x=True):
     """spmv::cg with CgOptions::mixed -> (k, rnorm_history, stats)"""
     k = C.c_int()
     hist = np.zeros(kmax + 2)
@@ -687,7 +688,8 @@ def cg_mixed(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, replace_every=50,
     call("spmvh_cg_mixed", comm.h, exec_.h, A.h, b_ptr, x_ptr, kmax,
          float(rtol), int(replace_every), C.byref(k), _np_ptr(hist), len(hist),
          workspace.h if workspace else None,
-         int(time_spmv) | (0 if consumer_reductions else 4), st)
+         int(time_spmv) | (0 if consumer_reductions else 4)
+         | (0 if defer_x else 8), st)
     stats = dict(spmv_ms_total=st[0], spmv_launches=int(st[1]),
                  replacements=int(st[2]), true_rel_residual=st[3],
                  continuation_iterations=int(st[4]),
@@ -749,17 +751,18 @@ class CgWorkspace:
 
 def cg_ex(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, workspace=None,
           time_spmv=False, history=False, consumer_reductions=True,
-          poll_every=0):
+          poll_every=0, defer_x=True):
     """cg with the optional arguments: returns (k, history, spmv_ms_total,
     spmv_launches).  poll_every: CgOptions::poll_every (how many iterations the
-    host may run ahead of the device's `done` flag; 0 = the default, 16)."""
+    host may run ahead of the device's `done` flag; 0 = the default, 16).
+    defer_x: CgOptions::defer_x (False = x updated in every iteration)."""
     k, n = C.c_int(), C.c_int()
     ms = f64()
     hist = np.zeros(kmax + 1) if history else None
     call("spmvh_cg_ex", comm.h, exec_.h, A.h, b_ptr, x_ptr, kmax, float(rtol),
          C.byref(k), _np_ptr(hist), workspace.h if workspace else None,
          int(time_spmv) | (0 if consumer_reductions else 4)
-         | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         | (0 if defer_x else 8) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
          C.byref(n))
     return (k.value, hist[:k.value + 1] if history else None, ms.value,
             n.value)
