@@ -46,6 +46,7 @@ enum {
 typedef struct spmv_hip_ctx spmv_hip_ctx;           /* one GPU             */
 typedef struct spmv_hip_csr_plan spmv_hip_csr_plan; /* CSRSpMV::_aux_data  */
 typedef struct spmv_hip_cg_ws spmv_hip_cg_ws;       /* cg() work vectors   */
+typedef struct spmv_hip_cgb_ws spmv_hip_cgb_ws;     /* cg_block() scalars  */
 typedef struct spmv_hip_comm spmv_hip_comm;         /* RCCL communicator   */
 
 int spmv_hip_abi_version(void);
@@ -712,6 +713,75 @@ int spmv_hip_cg_reduce_pAp2(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
 /* r.r partials for k = 0 (cg.cpp:47) */
 int spmv_hip_cg_dot_rr_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int64_t n,
                            const double* r, void* stream);
+
+/* ---- CG for a block of right-hand sides (spmv::cg_block) ------------------------
+ * nrhs independent CG recurrences (cg.cpp:21-98 once per column) in lockstep on
+ * INTERLEAVED blocks, the layout of the multi-vector product: element (i, c)
+ * of a block lives at V[i * nrhs + c], M * nrhs doubles.  1 <= nrhs <=
+ * SPMV_HIP_CGB_MAX_NRHS; anything else is SPMV_HIP_EINVAL.  nrhs = 2, 4, 8 run
+ * streaming kernels on 16-byte elements (every block 16-byte aligned, except B
+ * of init); the other widths run one thread per row with scalar accesses.
+ *
+ * Device state of a workspace:
+ *   rr[k][c]  = ||r_k||^2 of column c (k = 0..kmax), pAp[k][c] = p_k . A p_k:
+ *               the nrhs scalars of one k are contiguous, so one all-reduce of
+ *               nrhs doubles on the slot address serves every column;
+ *   done[c]   = 1 once column c has stopped, kstop[c] = its iteration count:
+ *               sqrt(rr[k][c]) / sqrt(rr[0][c]) < rtol, or rr[0][c] == 0 (then
+ *               kstop = 0 and x = 0);
+ *   all_done  = 1 once every column has stopped.
+ * The iteration in which a column meets the tolerance updates its x and r and
+ * leaves its p (cg.cpp:80-81); from then on no kernel changes its x, r, p and
+ * its scalars are not extended (slots beyond kstop[c] keep the zero of the
+ * reset).  After all_done every cgb_* kernel returns at once, so the host may
+ * enqueue iterations ahead.  The bits of column c depend on the matrix, on
+ * column c of B, on nrhs and on c only. */
+#define SPMV_HIP_CGB_MAX_NRHS 8
+/* int32 words of the state copied by cgb_ws_read_async:
+ * [0] all_done, [1 + c] done[c], [1 + SPMV_HIP_CGB_MAX_NRHS + c] kstop[c] */
+#define SPMV_HIP_CGB_STATE_WORDS (1 + 2 * SPMV_HIP_CGB_MAX_NRHS)
+int spmv_hip_cgb_ws_create(spmv_hip_ctx* ctx, int kmax, int nrhs,
+                           spmv_hip_cgb_ws** ws);
+int spmv_hip_cgb_ws_destroy(spmv_hip_cgb_ws* ws);
+int spmv_hip_cgb_ws_reset(spmv_hip_cgb_ws* ws, double rtol, void* stream);
+/* kmax and nrhs the workspace was created with */
+int spmv_hip_cgb_ws_capacity(const spmv_hip_cgb_ws* ws, int* kmax, int* nrhs);
+/* device addresses of the nrhs scalars of iteration k (for the all-reduce) */
+int spmv_hip_cgb_ws_rr(spmv_hip_cgb_ws* ws, int k, double** slot);
+int spmv_hip_cgb_ws_pAp(spmv_hip_cgb_ws* ws, int k, double** slot);
+/* the partial array, [spmv_hip_dot_partials_len()][nrhs] */
+int spmv_hip_cgb_ws_partials(spmv_hip_cgb_ws* ws, double** partials);
+int spmv_hip_cgb_ws_done_flag(spmv_hip_cgb_ws* ws, const int32_t** all_done);
+/* copies the state words (above) and rr[0..kmax][nrhs] to the host (async on
+ * stream).  host_state_len < SPMV_HIP_CGB_STATE_WORDS or host_rr_len <
+ * (kmax + 1) * nrhs (cgb_ws_capacity) -> SPMV_HIP_EINVAL, nothing is copied.
+ * Either destination may be NULL (then it is skipped, its length ignored). */
+int spmv_hip_cgb_ws_read_async(spmv_hip_cgb_ws* ws, int32_t* host_state,
+                               size_t host_state_len, double* host_rr,
+                               size_t host_rr_len, void* stream);
+/* R = P = B ; X = 0 ; partials of r.r (then cgb_reduce_rr(0) installs rr[0]) */
+int spmv_hip_cgb_init_f64(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int64_t M,
+                          const double* B, double* R, double* P, double* X,
+                          void* stream);
+/* partials of p.Ap per column */
+int spmv_hip_cgb_dot_f64(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int64_t M,
+                         const double* P, const double* AP, void* stream);
+/* partials -> pAp[k] / rr[k] (local part; all-reduce nrhs doubles afterwards).
+ * reduce_pAp(k) first raises done[c] for the columns that stopped in iteration
+ * k - 1 (at k = 1: the columns with rr[0][c] == 0), and all_done. */
+int spmv_hip_cgb_reduce_pAp(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int k,
+                            void* stream);
+int spmv_hip_cgb_reduce_rr(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int k,
+                           void* stream);
+/* update_r : r -= alpha_c Ap ; partials of r.r            (cg.cpp:66,70,73)
+ * update_xp: x += alpha_c p ; stop test ; p = beta_c p + r (cg.cpp:69,77-85)
+ * per column, with the arithmetic of spmv_hip_cg_update_r_f64 / _xp_f64 */
+int spmv_hip_cgb_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int k,
+                              int64_t M, const double* AP, double* R,
+                              void* stream);
+int spmv_hip_cgb_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int k,
+                               int64_t M, const double* R, double* X, double* P,
+                               void* stream);
 
 /* ---- 3-D Poisson generator (not in the reference)
  * 7-point stencil on an n^3 grid, natural ordering, diag 6, off-diag -1.

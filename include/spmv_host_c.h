@@ -327,6 +327,25 @@ int spmvh_cg_ex(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                 double* rnorm_history, spmvh_cg_workspace* ws, int time_spmv,
                 double* spmv_ms_total, int* spmv_launches);
 
+/* spmv::cg_block: A X = B for nrhs right-hand sides, nrhs independent CG
+ * recurrences in lockstep on INTERLEAVED blocks (element (i, c) at
+ * B[i * nrhs + c], X[i * nrhs + c]; device pointers of rows * nrhs doubles,
+ * 1 <= nrhs <= 8, X must not overlap B).  iterations: nrhs entries;
+ * rnorm_history (may be NULL): nrhs * (kmax + 1) entries, ||r_j|| of column c
+ * at [c * (kmax + 1) + j] for j <= iterations[c], -1.0 beyond.  *max_its = the
+ * largest entry of iterations.  ws: a reusable spmv::CgBlockWorkspace (may be
+ * NULL).  flags: bit 0 -> CgOptions::time_spmv (*spmv_ms_total, *spmv_launches,
+ * both may be NULL), bits 8-15 CgOptions::poll_every (0 = default). */
+typedef struct spmvh_cg_block_workspace spmvh_cg_block_workspace;
+int spmvh_cg_block_workspace_create(spmvh_exec* exec,
+                                    spmvh_cg_block_workspace** ws);
+int spmvh_cg_block_workspace_destroy(spmvh_cg_block_workspace* ws);
+int spmvh_cg_block(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                   const double* B, double* X, int nrhs, int kmax, double rtol,
+                   int* max_its, int* iterations, double* rnorm_history,
+                   spmvh_cg_block_workspace* ws, int flags,
+                   double* spmv_ms_total, int* spmv_launches);
+
 #ifdef __cplusplus
 }
 #endif

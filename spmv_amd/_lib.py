@@ -150,6 +150,22 @@ _PROTOS = {
     "spmv_hip_cg_reduce_pAp": ([vp, vp, C.c_int, vp], C.c_int),
     "spmv_hip_cg_reduce_pAp2": ([vp, vp, C.c_int, vp, vp], C.c_int),
     "spmv_hip_cg_dot_rr_f64": ([vp, vp, i64, vp, vp], C.c_int),
+    "spmv_hip_cgb_ws_create": ([vp, C.c_int, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_cgb_ws_destroy": ([vp], C.c_int),
+    "spmv_hip_cgb_ws_reset": ([vp, f64, vp], C.c_int),
+    "spmv_hip_cgb_ws_capacity": ([vp, P(C.c_int), P(C.c_int)], C.c_int),
+    "spmv_hip_cgb_ws_rr": ([vp, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_cgb_ws_pAp": ([vp, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_cgb_ws_partials": ([vp, P(vp)], C.c_int),
+    "spmv_hip_cgb_ws_done_flag": ([vp, P(vp)], C.c_int),
+    "spmv_hip_cgb_ws_read_async": ([vp, vp, sz, vp, sz, vp], C.c_int),
+    "spmv_hip_cgb_init_f64": ([vp, vp, i64, vp, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_cgb_dot_f64": ([vp, vp, i64, vp, vp, vp], C.c_int),
+    "spmv_hip_cgb_reduce_pAp": ([vp, vp, C.c_int, vp], C.c_int),
+    "spmv_hip_cgb_reduce_rr": ([vp, vp, C.c_int, vp], C.c_int),
+    "spmv_hip_cgb_update_r_f64": ([vp, vp, C.c_int, i64, vp, vp, vp], C.c_int),
+    "spmv_hip_cgb_update_xp_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp],
+                                   C.c_int),
     "spmv_hip_poisson3d_count": ([vp, i32, i64, i64, C.c_int, vp, P(i64), vp],
                                  C.c_int),
     "spmv_hip_poisson3d_fill_f64": ([vp, i32, i64, i64, C.c_int, vp, vp, vp,

@@ -44,6 +44,10 @@ struct spmvh_cg_workspace {
   std::shared_ptr<HipExecutor> exec; // keeps the executor alive
   std::unique_ptr<CgWorkspace> ws;
 };
+struct spmvh_cg_block_workspace {
+  std::shared_ptr<HipExecutor> exec; // keeps the executor alive
+  std::unique_ptr<CgBlockWorkspace> ws;
+};
 
 namespace
 {
@@ -1104,6 +1108,51 @@ int spmvh_cg_ex(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     *num_its = cg(*comm->comm, *exec->hip, *A->A, b, x, kmax, rtol,
                   rnorm_history ? &hist : nullptr, &opt, &st,
                   ws ? ws->ws.get() : nullptr);
+    if (rnorm_history)
+      std::copy(hist.begin(), hist.end(), rnorm_history);
+    if (spmv_ms_total)
+      *spmv_ms_total = st.spmv_ms_total;
+    if (spmv_launches)
+      *spmv_launches = st.spmv_launches;
+  });
+}
+
+int spmvh_cg_block_workspace_create(spmvh_exec* exec,
+                                    spmvh_cg_block_workspace** ws)
+{
+  return guarded([&] {
+    require(exec && ws, "NULL argument");
+    auto w = std::make_unique<spmvh_cg_block_workspace>();
+    w->exec = exec->hip;
+    w->ws.reset(new CgBlockWorkspace(*exec->hip));
+    *ws = w.release();
+  });
+}
+
+int spmvh_cg_block_workspace_destroy(spmvh_cg_block_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_cg_block(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                   const double* B, double* X, int nrhs, int kmax, double rtol,
+                   int* max_its, int* iterations, double* rnorm_history,
+                   spmvh_cg_block_workspace* ws, int flags,
+                   double* spmv_ms_total, int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && max_its && iterations, "NULL argument");
+    std::vector<int> its;
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff)
+      opt.poll_every = (flags >> 8) & 0xff;
+    CgStats st;
+    *max_its = cg_block(*comm->comm, *exec->hip, *A->A, B, X, nrhs, kmax, rtol,
+                        &its, rnorm_history ? &hist : nullptr, &opt, &st,
+                        ws ? ws->ws.get() : nullptr);
+    std::copy(its.begin(), its.end(), iterations);
     if (rnorm_history)
       std::copy(hist.begin(), hist.end(), rnorm_history);
     if (spmv_ms_total)

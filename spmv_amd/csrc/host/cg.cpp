@@ -465,4 +465,278 @@ int cg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   return k_final;
 }
 
+// ---------------------------------------------------------------------------
+// cg_block: see cg.h.  Per iteration (compute stream), on any number of ranks:
+//     halo of the block P on the map's side stream
+//     mult_block: local block [wait halo event] remote block
+//     block dot partials of p.Ap ; reducer -> pAp[k][0:nrhs] ; all-reduce
+//     r -= alpha_c Ap with the r.r partials ; reducer -> rr[k][0:nrhs] ; all-reduce
+//     x += alpha_c p ; stop test ; p = beta_c p + r
+// The two all-reduces carry nrhs doubles each (Comm::reduce_sum: the peer
+// windows up to SPMV_HIP_REDUCE_MAX_COUNT doubles, the transport's all-reduce
+// beyond; every rank takes the same branch, nrhs being collective).
+// ---------------------------------------------------------------------------
+CgBlockWorkspace::~CgBlockWorkspace() { release(); }
+
+void CgBlockWorkspace::release()
+{
+  try {
+    if (stream)
+      _exec.synchronize_stream(stream);
+    _exec.destroy_event(poll_event);
+    for (void* e : timing_ev)
+      _exec.destroy_event(e);
+    if (stream)
+      _exec.destroy_stream(stream);
+    spmv_hip_cgb_ws_destroy(ws);
+    _exec.free(r);
+    _exec.free(Ap);
+    _exec.free(x);
+    _exec.free(p);
+    spmv_hip_host_free(_exec.context(), state);
+  } catch (...) {
+  }
+  timing_ev.clear();
+  ws = nullptr;
+  r = Ap = x = p = nullptr;
+  state = nullptr;
+  stream = poll_event = nullptr;
+  kmax_cap = -1;
+  nrhs_cap = 0;
+  m_cap = n_cap = x_cap = -1;
+}
+
+void CgBlockWorkspace::ensure(int64_t m_elems, int64_t n_elems, int kmax,
+                              int nrhs, bool need_x)
+{
+  spmv_hip_ctx* ctx = _exec.context();
+  if (!stream) {
+    stream = _exec.create_stream();
+    poll_event = _exec.create_event();
+    void* mem = nullptr;
+    throw_on_error(spmv_hip_host_alloc(
+                       ctx, SPMV_HIP_CGB_STATE_WORDS * sizeof(int32_t), &mem),
+                   "spmv_hip_host_alloc");
+    state = static_cast<int32_t*>(mem);
+  }
+  if (kmax > kmax_cap || nrhs != nrhs_cap) {
+    // (an earlier solve on this workspace has been synchronised: nothing
+    // still reads the old scalars)
+    spmv_hip_cgb_ws_destroy(ws);
+    ws = nullptr;
+    kmax_cap = -1;
+    nrhs_cap = 0;
+    throw_on_error(spmv_hip_cgb_ws_create(ctx, kmax, nrhs, &ws),
+                   "spmv_hip_cgb_ws_create");
+    kmax_cap = kmax;
+    nrhs_cap = nrhs;
+  }
+  if (m_elems > m_cap) {
+    _exec.free(r);
+    _exec.free(Ap);
+    r = Ap = nullptr;
+    m_cap = -1;
+    r = _exec.alloc<double>(m_elems);
+    Ap = _exec.alloc<double>(m_elems);
+    m_cap = m_elems;
+  }
+  if (need_x && m_elems > x_cap) {
+    _exec.free(x);
+    x = nullptr;
+    x_cap = -1;
+    x = _exec.alloc<double>(m_elems);
+    x_cap = m_elems;
+  }
+  if (n_elems > n_cap) {
+    _exec.free(p);
+    p = nullptr;
+    n_cap = -1;
+    p = _exec.alloc<double>(n_elems);
+    n_cap = n_elems;
+  }
+}
+
+void CgBlockWorkspace::reserve_timing(int iterations)
+{
+  while (timing_ev.size() < 2 * (size_t)(iterations < 0 ? 0 : iterations))
+    timing_ev.push_back(_exec.create_event(true));
+}
+
+int cg_block(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+             const double* B, double* X, int nrhs, int kmax, double rtol,
+             std::vector<int>* iterations, std::vector<double>* rnorm_history,
+             const CgOptions* options, CgStats* stats,
+             CgBlockWorkspace* workspace)
+{
+  std::shared_ptr<const L2GMap> col_l2g = A.col_map();
+  std::shared_ptr<const L2GMap> row_l2g = A.row_map();
+  if (row_l2g->num_ghosts() > 0) // cg.cpp:32-33
+    throw std::runtime_error(
+        "spmv::cg_block - Error: A.row_map() has ghost entries");
+  if (kmax < 0)
+    throw std::runtime_error("spmv::cg_block - Error: kmax < 0");
+  if (nrhs < 1 || nrhs > SPMV_HIP_CGB_MAX_NRHS)
+    throw std::runtime_error("spmv::cg_block - Error: nrhs must be in 1..8");
+  const CgOptions opt = options ? *options : CgOptions();
+  const int poll_every = opt.poll_every < 1 ? 1 : opt.poll_every;
+
+  const int64_t M = row_l2g->local_size();
+  const int64_t N_padded = col_l2g->local_size() + col_l2g->num_ghosts();
+  const int64_t m_elems = M * nrhs, n_elems = N_padded * nrhs;
+  spmv_hip_ctx* ctx = exec.context();
+
+  { // X is the iterate from the first kernel on (cg.h): it cannot share B
+    const uintptr_t xb = reinterpret_cast<uintptr_t>(X),
+                    bb = reinterpret_cast<uintptr_t>(B);
+    const uintptr_t bytes = (uintptr_t)m_elems * sizeof(double);
+    if (M > 0 && xb < bb + bytes && bb < xb + bytes)
+      throw std::runtime_error("cg_block: X overlaps B (X is updated in place)");
+  }
+  CgBlockWorkspace own(exec);
+  CgBlockWorkspace& w = workspace ? *workspace : own;
+  const bool x_aligned = (reinterpret_cast<uintptr_t>(X) & 15u) == 0;
+  w.ensure(m_elems, n_elems, kmax, nrhs, !x_aligned);
+  if (opt.time_spmv)
+    w.reserve_timing(kmax);
+
+  StreamGuard guard{exec, exec.get_stream()};
+  { // order after whatever the caller enqueued (B may still be in flight)
+    void* ev = exec.create_event();
+    exec.record_event(ev, guard.prev);
+    exec.stream_wait_event(w.stream, ev);
+    exec.destroy_event(ev);
+  }
+  exec.set_stream(w.stream); // every launch below goes to this stream
+
+  throw_on_error(spmv_hip_cgb_ws_reset(w.ws, rtol, nullptr),
+                 "spmv_hip_cgb_ws_reset");
+  double* const Xi = x_aligned ? X : w.x;
+  // R = P = B, X0 = 0, partials of r.r: one pass (cg.cpp:41-47); the ghost
+  // tail of P is defined here instead of relying on fresh pages
+  if (n_elems > m_elems)
+    exec.memset<double>(w.p + m_elems, 0, n_elems - m_elems);
+  throw_on_error(spmv_hip_cgb_init_f64(ctx, w.ws, M, B, w.r, w.p, Xi, nullptr),
+                 "spmv_hip_cgb_init_f64");
+  for (int i = 0; i < SPMV_HIP_CGB_STATE_WORDS; ++i)
+    w.state[i] = i > SPMV_HIP_CGB_MAX_NRHS ? -1 : 0;
+
+  auto slot = [&](bool rr, int k) {
+    double* s = nullptr;
+    throw_on_error(rr ? spmv_hip_cgb_ws_rr(w.ws, k, &s)
+                      : spmv_hip_cgb_ws_pAp(w.ws, k, &s),
+                   "spmv_hip_cgb_ws slot");
+    return s;
+  };
+
+  // rnorm0 of every column (cg.cpp:47-50)
+  throw_on_error(spmv_hip_cgb_reduce_rr(ctx, w.ws, 0, nullptr),
+                 "spmv_hip_cgb_reduce_rr");
+  comm.reduce_sum(slot(true, 0), nrhs, w.stream);
+
+  std::vector<void*>& timing_ev = w.timing_ev;
+  int k = 0;
+  bool stopped = false;
+  bool poll_pending = false;
+  while (k < kmax && !stopped) { // cg.cpp:55
+    ++k;
+    col_l2g->update_block(w.p, nrhs); // cg.cpp:59 (starts on the side stream)
+    void* ev1 = nullptr;
+    if (opt.time_spmv) {
+      ev1 = timing_ev[2 * (size_t)(k - 1) + 1];
+      exec.record_event(timing_ev[2 * (size_t)(k - 1)], w.stream);
+    }
+    // cg.cpp:60: not guarded by the state -- what it leaves in the columns
+    // that have stopped is not used
+    A.mult_block(w.p, w.Ap, nrhs, ev1);
+    throw_on_error(spmv_hip_cgb_dot_f64(ctx, w.ws, M, w.p, w.Ap, nullptr),
+                   "spmv_hip_cgb_dot_f64"); // cg.cpp:63
+    throw_on_error(spmv_hip_cgb_reduce_pAp(ctx, w.ws, k, nullptr),
+                   "spmv_hip_cgb_reduce_pAp");
+    comm.reduce_sum(slot(false, k), nrhs, w.stream); // cg.cpp:65
+    throw_on_error(spmv_hip_cgb_update_r_f64(ctx, w.ws, k, M, w.Ap, w.r,
+                                             nullptr),
+                   "spmv_hip_cgb_update_r_f64"); // cg.cpp:66,70,73
+    throw_on_error(spmv_hip_cgb_reduce_rr(ctx, w.ws, k, nullptr),
+                   "spmv_hip_cgb_reduce_rr");
+    comm.reduce_sum(slot(true, k), nrhs, w.stream); // cg.cpp:75
+    throw_on_error(spmv_hip_cgb_update_xp_f64(ctx, w.ws, k, M, w.r, Xi, w.p,
+                                              nullptr),
+                   "spmv_hip_cgb_update_xp_f64"); // cg.cpp:69,77-85
+
+    if (k % poll_every == 0 && k < kmax) {
+      // lagging look at all_done, as cg() looks at its flag
+      if (poll_pending) {
+        exec.synchronize_event(w.poll_event);
+        stopped = w.state[0] != 0;
+      }
+      if (!stopped) {
+        throw_on_error(spmv_hip_cgb_ws_read_async(w.ws, w.state,
+                                                  SPMV_HIP_CGB_STATE_WORDS,
+                                                  nullptr, 0, nullptr),
+                       "spmv_hip_cgb_ws_read_async");
+        exec.record_event(w.poll_event, w.stream);
+        poll_pending = true;
+      }
+    }
+  }
+
+  // final state and the squared-residual history (the device history has the
+  // WORKSPACE's capacity; the C ABI refuses a shorter destination)
+  int cap = 0, cap_nrhs = 0;
+  throw_on_error(spmv_hip_cgb_ws_capacity(w.ws, &cap, &cap_nrhs),
+                 "spmv_hip_cgb_ws_capacity");
+  std::vector<double> rr(((size_t)std::max(kmax, cap) + 1) * (size_t)nrhs, 0.0);
+  throw_on_error(spmv_hip_cgb_ws_read_async(w.ws, w.state,
+                                            SPMV_HIP_CGB_STATE_WORDS, rr.data(),
+                                            rr.size(), nullptr),
+                 "spmv_hip_cgb_ws_read_async");
+  if (Xi != X)
+    exec.copy<double>(X, Xi, m_elems);
+  exec.synchronize_stream(w.stream);
+
+  if (stats) {
+    *stats = CgStats();
+    for (size_t i = 0; opt.time_spmv && i + 1 < 2 * (size_t)k; i += 2) {
+      float ms = 0.f;
+      throw_on_error(spmv_hip_event_elapsed_ms(ctx, timing_ev[i],
+                                               timing_ev[i + 1], &ms),
+                     "spmv_hip_event_elapsed_ms");
+      stats->spmv_ms_total += ms;
+      ++stats->spmv_launches;
+    }
+  }
+
+  if (iterations)
+    iterations->assign(nrhs, 0);
+  if (rnorm_history)
+    rnorm_history->assign((size_t)nrhs * ((size_t)kmax + 1), -1.0);
+  int k_max = 0;
+  for (int c = 0; c < nrhs; ++c) {
+    auto rr_at = [&](int j) { return rr[(size_t)j * nrhs + c]; };
+    int kc = k;
+    if (w.state[1 + c] != 0) {
+      kc = w.state[1 + SPMV_HIP_CGB_MAX_NRHS + c];
+    } else if (rr_at(0) == 0.0) {
+      kc = 0; // (kmax == 0: no reducer ran to say so)
+    } else {
+      // done[c] is raised by the p.Ap reducer of the NEXT iteration; when the
+      // loop ends first, apply the same test (cg.cpp:80) here, as cg() does
+      const double rnorm0 = std::sqrt(rr_at(0));
+      for (int j = 1; j <= k; ++j)
+        if (std::sqrt(rr_at(j)) / rnorm0 < rtol) {
+          kc = j;
+          break;
+        }
+    }
+    k_max = std::max(k_max, kc);
+    if (iterations)
+      (*iterations)[c] = kc;
+    if (rnorm_history)
+      for (int j = 0; j <= kc; ++j)
+        (*rnorm_history)[(size_t)c * ((size_t)kmax + 1) + j]
+            = std::sqrt(rr_at(j));
+  }
+  return k_max;
+}
+
 } // namespace spmv

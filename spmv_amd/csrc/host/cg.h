@@ -10,6 +10,7 @@
 #include "matrix.h"
 
 struct spmv_hip_cg_ws;
+struct spmv_hip_cgb_ws;
 
 namespace spmv
 {
@@ -113,5 +114,75 @@ int cg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
        std::vector<double>* rnorm_history = nullptr,
        const CgOptions* options = nullptr, CgStats* stats = nullptr,
        CgWorkspace* workspace = nullptr);
+
+// Work vectors + device scalars of cg_block(), kept across calls like
+// CgWorkspace; it regrows itself when a call needs more rows, more iterations
+// or another nrhs.
+class CgBlockWorkspace
+{
+public:
+  explicit CgBlockWorkspace(HipExecutor& exec) : _exec(exec) {}
+  ~CgBlockWorkspace();
+  CgBlockWorkspace(const CgBlockWorkspace&) = delete;
+  CgBlockWorkspace& operator=(const CgBlockWorkspace&) = delete;
+
+  // ---- internal to cg_block() ----
+  // m_elems = rows * nrhs, n_elems = (local + ghosts) * nrhs; need_x: the
+  // caller's X is not 16-byte aligned, the iterate lives in `x`
+  void ensure(int64_t m_elems, int64_t n_elems, int kmax, int nrhs,
+              bool need_x);
+  void reserve_timing(int iterations);
+  void release();
+
+  HipExecutor& _exec;
+  spmv_hip_cgb_ws* ws = nullptr;
+  int kmax_cap = -1, nrhs_cap = 0;
+  int64_t m_cap = -1, n_cap = -1, x_cap = -1;
+  double *r = nullptr, *Ap = nullptr; // m_cap
+  double* x = nullptr; // x_cap: the iterate when the caller's X is unaligned
+  double* p = nullptr; // n_cap: padded, the ghost tail is zeroed by every solve
+  int32_t* state = nullptr; // pinned {all_done, done[], kstop[]} (spmv_hip.h)
+  void* stream = nullptr;   // compute stream of the solve
+  void* poll_event = nullptr;
+  std::vector<void*> timing_ev; // CgOptions::time_spmv: 2 events per iteration
+};
+
+// CG for several right-hand sides: solves A X = B for `nrhs` columns with
+// nrhs INDEPENDENT unpreconditioned CG recurrences from X0 = 0 (cg.cpp:21-98
+// once per column) that run in lockstep -- one halo exchange of the block, one
+// Matrix::mult_block and one all-reduce of nrhs doubles per reduction.  This
+// is not block-Krylov CG: no information passes between columns, and the bits
+// of column c (x, residual history, iteration count) depend on A, on column c
+// of B, on nrhs and on c only.
+//
+// Layout of Matrix::mult_block: element (i, c) at B[i * nrhs + c] and
+// X[i * nrhs + c]; both DEVICE pointers of A.row_map()->local_size() * nrhs
+// doubles.  1 <= nrhs <= 8 (std::runtime_error otherwise).  As with cg(), X is
+// the iterate and must not overlap B (std::runtime_error); an X that is not
+// 16-byte aligned goes through the workspace's copy and one copy at the end.
+//
+// Every column has its own alpha, beta and stopping test ||r_k|| / ||r_0|| <
+// rtol.  The iteration in which a column meets the tolerance updates its x
+// and r and leaves its p (cg.cpp:80-81); from then on the column is frozen.
+// The solve ends when every column has stopped or at k == kmax; the value
+// returned is the largest per-column iteration count.
+//
+// Unlike cg(), which runs a system with r_0 . r_0 == 0 to kmax on NaNs, a
+// column with r_0 . r_0 == 0 is declared stopped at k = 0 with x = 0: a
+// caller may pad a block with zero columns.
+//
+// iterations    (optional) nrhs entries: the k of every column.
+// rnorm_history (optional) nrhs * (kmax + 1) entries: ||r_j|| of column c at
+//               [c * (kmax + 1) + j] for j <= iterations[c], -1.0 beyond.
+// options       poll_every and time_spmv apply (time_spmv brackets the
+//               local-block mult_block launch); consumer_reductions, defer_x
+//               and mixed are IGNORED: every dot product is finished by a
+//               reducer kernel, x is updated in every iteration, in fp64.
+int cg_block(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+             const double* B, double* X, int nrhs, int kmax, double rtol,
+             std::vector<int>* iterations = nullptr,
+             std::vector<double>* rnorm_history = nullptr,
+             const CgOptions* options = nullptr, CgStats* stats = nullptr,
+             CgBlockWorkspace* workspace = nullptr);
 
 } // namespace spmv

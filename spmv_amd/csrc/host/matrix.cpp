@@ -155,12 +155,15 @@ void Matrix<T>::spmv_sym_overlap(T* x, T* y) const
 
 // The four variants of mult() for a block of k interleaved vectors.
 template <typename T>
-void Matrix<T>::mult_block(T* X, T* Y, int k) const
+void Matrix<T>::mult_block(T* X, T* Y, int k, void* ev_local_done) const
 {
   if (k < 1)
     throw std::runtime_error("Matrix::mult_block: k must be at least 1");
   const bool overlap = _col_map->overlapping();
   _mat_local->mult_block(1, X, 0, Y, k); // (overlap: while the halo is in flight)
+  if (ev_local_done)
+    if (auto* hip = dynamic_cast<HipExecutor*>(_exec.get()))
+      hip->record_event(ev_local_done, hip->get_stream());
   if (overlap)
     _col_map->update_finalise_block(X, k);
   if (_symmetric)

@@ -55,7 +55,9 @@ public:
   // X[i * k + c]; X holds (local_size + num_ghosts) * k entries, refreshed by
   // col_map()->update_block(X, k), Y rows() * k.  Column c of Y has the bits
   // of mult() on column c of X.  The same four variants as mult().
-  void mult_block(T* X, T* Y, int k) const;
+  // `ev_local_done` (optional, a HipExecutor event) is recorded right after
+  // the local block's launch was enqueued, as in mult_dot.
+  void mult_block(T* X, T* Y, int k, void* ev_local_done = nullptr) const;
   // mult + the dot product x.y fused into the SpMV kernels where possible.
   // Emits partial sums into dot_local / dot_remote (each
   // spmv_hip_dot_partials_len() device doubles; their total is x[0:rows].y).

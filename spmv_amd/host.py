@@ -126,6 +126,10 @@ _PROTOS = {
     "spmvh_cg_workspace_reserve_timing": [vp, C.c_int],
     "spmvh_cg_ex": [vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int), vp, vp,
                     C.c_int, PTR(f64), PTR(C.c_int)],
+    "spmvh_cg_block_workspace_create": [vp, PTR(vp)],
+    "spmvh_cg_block_workspace_destroy": [vp],
+    "spmvh_cg_block": [vp, vp, vp, vp, vp, C.c_int, C.c_int, f64, PTR(C.c_int),
+                       vp, vp, vp, C.c_int, PTR(f64), PTR(C.c_int)],
 }
 for _n, _a in _PROTOS.items():
     _f = getattr(lib, _n)
@@ -766,6 +770,40 @@ def cg_ex(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, workspace=None,
          C.byref(n))
     return (k.value, hist[:k.value + 1] if history else None, ms.value,
             n.value)
+
+
+class CgBlockWorkspace:
+    """spmv::CgBlockWorkspace: work vectors kept across cg_block() calls."""
+
+    def __init__(self, exec_):
+        h = vp()
+        call("spmvh_cg_block_workspace_create", exec_.h, C.byref(h))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            call("spmvh_cg_block_workspace_destroy", self.h)
+            self.h = None
+
+
+def cg_block(comm, exec_, A, b_ptr, x_ptr, nrhs, kmax, rtol, workspace=None,
+             time_spmv=False, poll_every=0):
+    """spmv::cg_block: A X = B for nrhs interleaved right-hand sides (element
+    (i, c) at B[i * nrhs + c]) -> (iterations[nrhs], history[nrhs, kmax + 1],
+    stats).  history[c, j] = ||r_j|| of column c for j <= iterations[c], -1.0
+    beyond.  stats: max_iterations, spmv_ms_total, spmv_launches."""
+    nrhs, kmax = int(nrhs), int(kmax)
+    kmx, n = C.c_int(), C.c_int()
+    ms = f64()
+    its = np.zeros(max(nrhs, 1), np.int32)
+    hist = np.full((max(nrhs, 1), max(kmax, 0) + 1), -1.0)
+    call("spmvh_cg_block", comm.h, exec_.h, A.h, b_ptr, x_ptr, nrhs, kmax,
+         float(rtol), C.byref(kmx), _np_ptr(its), _np_ptr(hist),
+         workspace.h if workspace else None,
+         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         C.byref(n))
+    return its, hist, dict(max_iterations=kmx.value, spmv_ms_total=ms.value,
+                           spmv_launches=n.value)
 
 
 def host_executor_rejects_compute():
