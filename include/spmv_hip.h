@@ -252,7 +252,18 @@ int spmv_hip_csr_plan_destroy(spmv_hip_csr_plan* plan);
  * again, or drops the copy: values = NULL).  A general plan that took neither
  * the lattice nor the LX form (ragged rows, more than 16 entries per row) keeps
  * its copy in the SLICED JAGGED order instead (spmv_sjds.hip): 64-row slices
- * as jagged diagonals + 16-bit column codes into an LDS-staged copy of x. */
+ * as jagged diagonals + 16-bit column codes into an LDS-staged copy of x.
+ * NARROWED VALUES (fp64 only; ctx option "lx_narrow_values", default 1): a
+ * general plan in the LX form with its LDS-DMA records, whose values no form
+ * above took, is still SPMV_HIP_ENOTSUP -- its kernel keeps CSR order -- but
+ * when EVERY value is a normal binary32 number or +-0 held exactly (integers,
+ * dyadic rationals, single-precision data) the plan keeps an fp32 copy (4 B per
+ * entry) and launches with these `values` stream it in place of the 8-byte
+ * values, widening in the row sum: the same products and adds in the same
+ * order, y and the fused dot bit for bit.  One value that is not exact and the
+ * plan streams the caller's fp64 array as before.  plan_get "lx_v32" says
+ * which; plan_set "lx_v32" 0 / 1 switches while a copy exists.  The contract
+ * above holds: rewritten values need plan_values_changed or a new bake. */
 int spmv_hip_csr_plan_bake_values_f64(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan,
                                       const double* values,
                                       const double* diagonal, void* stream);

@@ -33,6 +33,10 @@ struct spmv_hip_ctx {
   // at most 16 distinct (offset - row lane) ("lx_codes"; 0.5 B per entry of
   // plan memory, streamed by the DMA kernel in place of the offsets)
   int lx_codes = 1;
+  // ... and plan_bake_values_f64 keeps an fp32 copy of the values for that
+  // kernel when every value is exact in fp32 ("lx_narrow_values"; 4 B per
+  // entry of plan memory, streamed in place of the 8-byte values)
+  int lx_narrow_values = 1;
   // the host mirror's CSRMatrix frees its device copies of colind / values
   // once a plan holds the matrix in its own format ("release_csr";
   // spmv_hip_csr_plan_owns_matrix); read by the mirror, nothing here acts on it

@@ -174,6 +174,12 @@ __host__ __device__ constexpr int64_t lx_code_bytes(int64_t nnz)
 {
   return (((nnz + 1) >> 1) + 16 + 15) & ~(int64_t)15;
 }
+// floats of the narrowed copy of `nnz` values (lx_val32): whole 16-byte
+// chunks, so that the chunk around the array's last entry lies inside it
+__host__ __device__ constexpr int64_t lx32_len(int64_t nnz)
+{
+  return (nnz + 3) & ~(int64_t)3;
+}
 constexpr int kLxwAlign = 4;       // window starts: multiples of 4 columns
 // XW: the same kernel on the CALLER's column indices (no 16-bit copy): the
 // record carries, after the LXW words, the windows themselves -- an entry's
@@ -462,6 +468,16 @@ struct spmv_hip_csr_plan {
   int lx4_blocks = 0;         // coded row blocks
   int lx4_lut = 1;            // dictionary look-up: 1 = LDS table, 2 = select
                               // tree on uniform registers (plan_set "lx4_lut")
+  // ... and an fp32 copy of the VALUES where every one of them is exactly
+  // representable as a normal binary32 number or +-0 (plan_bake_values_f64,
+  // ctx option "lx_narrow_values"): (double)(float)v has the bits of v, so the
+  // DMA kernel streams 4 instead of 8 bytes per entry and widens in the row
+  // sum -- same products, same adds, same order.  One inexact value and the
+  // plan keeps the fp64 stream.  Slots, grid and row-block order are those of
+  // the fp64 launch (the values slot is half used).
+  float* lx_val32 = nullptr;  // lx32_len(nnz) floats
+  const void* lx32_values0 = nullptr; // the fp64 array the copy was made from
+  int lx_v32 = 0;             // use it (plan_set "lx_v32")
   // XW: the LDS-DMA kernel on the caller's CSR arrays as they are (values,
   // 32-bit column indices), x windows staged: what a plan without lattice / LX
   // / sliced jagged form runs instead of the gather kernel (spmv_lxw.hip)
@@ -532,6 +548,13 @@ int spmv_build_row_list(spmv_hip_csr_plan* pl, const int32_t* rowptr);
 void spmv_free_lx(spmv_hip_csr_plan* pl);
 void spmv_free_xw(spmv_hip_csr_plan* pl);
 int spmv_build_lx(spmv_hip_csr_plan* pl, const int32_t* rowptr, const int32_t* colind);
+// the narrowed (fp32) copy of an LX plan's values: checked, then made or
+// refreshed in place; dropped when `values` is null, the plan is not an fp64
+// LX plan with DMA records, or a value is not exact in fp32.  may_alloc =
+// false: only an existing copy is refreshed.  Out of memory: no copy, no error.
+int spmv_lx32_bake(spmv_hip_csr_plan* pl, const double* values, bool may_alloc,
+                   hipStream_t st);
+void spmv_lx32_free(spmv_hip_csr_plan* pl);
 // the XW records, + the plane-walk order when the matrix sits on a 3-D grid
 int spmv_build_xw_and_walk(spmv_hip_csr_plan* pl, const int32_t* rowptr,
                            const int32_t* colind);
@@ -619,6 +642,11 @@ int spmv_lxw_run_f64(const spmv_hip_csr_plan* pl, hipStream_t st,
                      const int32_t* rowptr, const int32_t* colind,
                      const double* values, double alpha, const double* in,
                      double beta, double* out, DotOut dot);
+// ... on the plan's fp32 copy of fp64 values (lx_val32), fp64 arithmetic
+int spmv_lxw_run_f32f64(const spmv_hip_csr_plan* pl, hipStream_t st,
+                        const int32_t* rowptr, const int32_t* colind,
+                        const float* values, double alpha, const double* in,
+                        double beta, double* out, DotOut dot);
 int spmv_xw_grid(const spmv_hip_csr_plan* pl, int elem_bytes);
 int spmv_xw_run_f64(const spmv_hip_csr_plan* pl, hipStream_t st,
                     const int32_t* rowptr, const int32_t* colind,

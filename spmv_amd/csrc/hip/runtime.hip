@@ -172,6 +172,8 @@ int spmv_hip_ctx_get_option(const spmv_hip_ctx* ctx, const char* key, int64_t* v
     *value = ctx->lx_min_nnz;
   else if (!strcmp(key, "lat_min_nnz"))
     *value = ctx->lat_min_nnz;
+  else if (!strcmp(key, "lx_narrow_values"))
+    *value = ctx->lx_narrow_values;
   else if (!strcmp(key, "sj_min_nnz"))
     *value = ctx->sj_min_nnz;
   else
@@ -240,6 +242,11 @@ int spmv_hip_ctx_set_option(spmv_hip_ctx* ctx, const char* key, int64_t value)
   if (!strcmp(key, "lx_codes")) {
     SPMV_REQUIRE(value == 0 || value == 1);
     ctx->lx_codes = (int)value;
+    return SPMV_HIP_OK;
+  }
+  if (!strcmp(key, "lx_narrow_values")) {
+    SPMV_REQUIRE(value == 0 || value == 1);
+    ctx->lx_narrow_values = (int)value;
     return SPMV_HIP_OK;
   }
   if (!strcmp(key, "poisson_stencil")) {

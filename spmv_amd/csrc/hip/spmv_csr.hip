@@ -652,10 +652,14 @@ int launch_rowblock(const spmv_hip_csr_plan* pl, hipStream_t st,
       return spmv_lat_run_f32(pl, st, rowptr, values, alpha, in, beta, out);
   }
   if (pl->lx && pl->lxw && pl->lxw_rec && al && aligned16(in)) {
-    if constexpr (sizeof(T) == 8)
+    if constexpr (sizeof(T) == 8) {
+      // the baked values are all exact in fp32: the plan's 4-byte copy
+      if (pl->lx_v32 && pl->lx_val32 && values == pl->lx32_values0)
+        return spmv_lxw_run_f32f64(pl, st, rowptr, colind, pl->lx_val32, alpha,
+                                   in, beta, out, DOT ? dot : DotOut());
       return spmv_lxw_run_f64(pl, st, rowptr, colind, values, alpha, in, beta,
                               out, DOT ? dot : DotOut());
-    else
+    } else
       return spmv_lxw_run_f32(pl, st, rowptr, colind, values, alpha, in, beta,
                               out);
   }

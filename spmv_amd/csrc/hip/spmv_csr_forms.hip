@@ -402,6 +402,7 @@ void spmv_free_lx(spmv_hip_csr_plan* pl)
   pl->lx = pl->lx_staged = pl->lx_blocks = 0;
   pl->lxw = pl->lxw_max_cnt = pl->lxw_max_pieces = 0;
   pl->lx4 = pl->lx4_blocks = 0;
+  spmv_lx32_free(pl); // (the narrowed values are the DMA kernel's)
 }
 
 // The 4-bit codes of the DMA kernel (lx4_encode_kernel), after the records and
@@ -443,6 +444,141 @@ static int build_lx_codes(spmv_hip_csr_plan* pl, const int32_t* rowptr, int nrb,
   pl->lx4_blocks = coded;
   pl->lx4 = 1;
   return SPMV_HIP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The narrowed value stream of the DMA kernel (spmv_lxw.hip, TV = float under
+// T = double): a lossless width compression decided per matrix from its values
+// alone.  When every value v is a normal binary32 number or +-0 held exactly,
+// (double)(float)v has the bits of v and the kernel's row sums are the fp64
+// stream's, operation for operation.
+// ---------------------------------------------------------------------------
+namespace
+{
+
+// Does binary32 hold v exactly, as a normal number or +-0?  A value that would
+// be an fp32 subnormal is refused so that the answer does not depend on a
+// denormal mode; NaN, infinities and |v| > FLT_MAX fail the range test.
+__device__ __forceinline__ bool lx32_exact(double v)
+{
+  const double a = fabs(v);
+  if (!(a == 0.0 || (a >= 0x1p-126 && a <= 0x1.fffffep+127)))
+    return false;
+  return __double_as_longlong((double)(float)v) == __double_as_longlong(v);
+}
+
+// ORs 1 into *flag unless every value passes (values 16-byte aligned)
+__global__ __launch_bounds__(kBlock) void lx32_check_kernel(
+    int64_t nnz, const double* __restrict__ values, int32_t* __restrict__ flag)
+{
+  const f64x2* v2 = reinterpret_cast<const f64x2*>(values);
+  const int64_t pairs = nnz >> 1;
+  bool bad = false;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < pairs;
+       i += (int64_t)gridDim.x * kBlock) {
+    const f64x2 v = v2[i];
+    bad |= !lx32_exact(v.x) || !lx32_exact(v.y);
+  }
+  if ((nnz & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+    bad |= !lx32_exact(values[nnz - 1]);
+  if (bad)
+    atomicOr(flag, 1);
+}
+
+// out[0, lx32_len(nnz)) = (float)values, zeros behind the last entry: one
+// 16-byte store per four entries (values and out 16-byte aligned)
+__global__ __launch_bounds__(kBlock) void lx32_convert_kernel(
+    int64_t nnz, const double* __restrict__ values, float* __restrict__ out)
+{
+  const f64x2* v2 = reinterpret_cast<const f64x2*>(values);
+  f32x4* o4 = reinterpret_cast<f32x4*>(out);
+  const int64_t quads = lx32_len(nnz) >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < quads;
+       i += (int64_t)gridDim.x * kBlock) {
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (4 * i + 4 <= nnz) {
+      const f64x2 a = v2[2 * i], b = v2[2 * i + 1];
+      o.x = (float)a.x;
+      o.y = (float)a.y;
+      o.z = (float)b.x;
+      o.w = (float)b.y;
+    } else { // the array's last, partial chunk
+      const int64_t j = 4 * i;
+      o.x = (float)values[j];
+      if (j + 1 < nnz)
+        o.y = (float)values[j + 1];
+      if (j + 2 < nnz)
+        o.z = (float)values[j + 2];
+    }
+    o4[i] = o;
+  }
+}
+
+} // namespace
+
+void spmv_lx32_free(spmv_hip_csr_plan* pl)
+{
+  (void)hipFree(pl->lx_val32);
+  pl->lx_val32 = nullptr;
+  pl->lx32_values0 = nullptr;
+  pl->lx_v32 = 0;
+}
+
+int spmv_lx32_bake(spmv_hip_csr_plan* pl, const double* values, bool may_alloc,
+                   hipStream_t st)
+{
+  if (!values || pl->symmetric || !(pl->lx && pl->lxw && pl->lxw_rec)
+      || !pl->ctx->lx_narrow_values || pl->nnz == 0 || !aligned16(values)) {
+    spmv_lx32_free(pl);
+    return SPMV_HIP_OK;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  const int grid = spmv_grid_for(pl->ctx, (pl->nnz + 3) / 4, kBlock);
+  // the check first: a matrix it refuses costs one pass and no memory
+  int32_t* d_flag = nullptr;
+  int32_t h_flag = 1;
+  hipError_t e = hipMalloc(&d_flag, sizeof(int32_t));
+  if (e == hipSuccess)
+    e = hipMemsetAsync(d_flag, 0, sizeof(int32_t), st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(lx32_check_kernel, dim3(grid), dim3(kBlock), 0, st, pl->nnz,
+                       values, d_flag);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(&h_flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st);
+  (void)hipFree(d_flag);
+  if (e == hipSuccess && !h_flag && !pl->lx_val32 && may_alloc) {
+    e = hipMalloc(&pl->lx_val32, sizeof(float) * (size_t)lx32_len(pl->nnz));
+    if (e != hipSuccess)
+      pl->lx_val32 = nullptr;
+  }
+  if (e == hipSuccess && !h_flag && pl->lx_val32) {
+    hipLaunchKernelGGL(lx32_convert_kernel, dim3(grid), dim3(kBlock), 0, st,
+                       pl->nnz, values, pl->lx_val32);
+    e = hipGetLastError();
+    if (e == hipSuccess)
+      e = hipStreamSynchronize(st);
+    if (e == hipSuccess) {
+      pl->lx32_values0 = values;
+      pl->lx_v32 = 1;
+      pl->plan_us += (int)std::chrono::duration_cast<std::chrono::microseconds>(
+                         std::chrono::steady_clock::now() - t0)
+                         .count();
+      return SPMV_HIP_OK;
+    }
+  }
+  // refused, no memory for the copy, or an error: the fp64 stream
+  spmv_lx32_free(pl);
+  if (e == hipErrorOutOfMemory)
+    (void)hipGetLastError();
+  pl->plan_us += (int)std::chrono::duration_cast<std::chrono::microseconds>(
+                     std::chrono::steady_clock::now() - t0)
+                     .count();
+  return e == hipSuccess || e == hipErrorOutOfMemory ? SPMV_HIP_OK
+                                                     : static_cast<int>(e);
 }
 
 void spmv_free_xw(spmv_hip_csr_plan* pl)

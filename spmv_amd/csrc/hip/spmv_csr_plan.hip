@@ -353,6 +353,13 @@ int spmv_hip_csr_plan_bake_values_f64(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan
     const int rj = sym_sj_bake<double>(ctx, plan, values, diagonal, st);
     rc = values == nullptr ? (rj != SPMV_HIP_OK ? rj : rc) : rj;
   }
+  // an LX plan no other form took the values of: the DMA kernel's fp32 copy,
+  // where every value is exact in fp32 (rebuilt or dropped by every bake; the
+  // return code does not speak of it: plan_get "lx_v32")
+  const int rn = spmv_lx32_bake(plan, rc == SPMV_HIP_ENOTSUP ? values : nullptr,
+                                !plan->no_new_forms, st);
+  if (rn != SPMV_HIP_OK)
+    return rn;
   return rc;
 }
 
@@ -415,6 +422,7 @@ int spmv_hip_csr_plan_bake_values_f32(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan
     const int rj = sym_sj_bake<float>(ctx, plan, values, diagonal, st);
     rc = values == nullptr ? (rj != SPMV_HIP_OK ? rj : rc) : rj;
   }
+  spmv_lx32_free(plan); // (a narrowed copy of fp64 values baked before)
   return rc;
 }
 
@@ -500,6 +508,11 @@ int spmv_hip_csr_plan_values_changed(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan,
              : spmv_sjds_bake_f32(plan->sjt, static_cast<const float*>(v0),
                                   plan->sjv_map, st);
   }
+  // the LX form's narrowed values: checked again, rewritten in place -- or
+  // dropped when a value is no longer exact in fp32 (back to the fp64 stream)
+  if (rc == SPMV_HIP_OK && plan->lx_val32 && plan->lx32_values0)
+    rc = spmv_lx32_bake(plan, static_cast<const double*>(plan->lx32_values0), false,
+                        st);
   // the diagonal forms: the device checks decide the form again (a matrix
   // they no longer hold: ENOTSUP = back to the CSR-order kernels, which is a
   // correct outcome of this call)
@@ -609,6 +622,12 @@ int spmv_hip_csr_plan_set(spmv_hip_csr_plan* plan, const char* key, int value)
     SPMV_REQUIRE(value == 0 || value == 1);
     SPMV_REQUIRE(value == 0 || plan->lx_code);
     plan->lx4 = value;
+  } else if (!strcmp(key, "lx_v32")) {
+    // ... streaming the plan's fp32 copy of the values (needs the copy:
+    // plan_bake_values_f64 on exact values); nor does the geometry depend on it
+    SPMV_REQUIRE(value == 0 || value == 1);
+    SPMV_REQUIRE(value == 0 || plan->lx_val32);
+    plan->lx_v32 = value;
   } else if (!strcmp(key, "lx4_lut")) {
     // the dictionary look-up of a coded block: 1 = LDS table, 2 = select tree
     SPMV_REQUIRE(value == 1 || value == 2);
@@ -910,6 +929,8 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
       b += 4 * nrb * kLxwRec;
     if (plan->lx_code)
       b += lx_code_bytes(nnz);
+    if (plan->lx_val32)
+      b += 4 * lx32_len(nnz);
     if (plan->xw_rec)
       b += 4 * nrb * kXwRec;
     if (plan->lat_tab)
@@ -1019,6 +1040,8 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
     *value = plan->lx_code && plan->lx4_blocks == plan->lx_staged ? 1 : 0;
   else if (!strcmp(key, "lx4_lut"))
     *value = plan->lx4_lut;
+  else if (!strcmp(key, "lx_v32"))
+    *value = plan->lx_v32 && plan->lx_val32 ? 1 : 0;
   else if (!strcmp(key, "lxw_grid")) // launch grid of the DMA kernel (fp64)
     *value = plan->lxw_rec ? spmv_lxw_grid(plan, 8) : 0;
   else if (!strcmp(key, "lx_staged"))

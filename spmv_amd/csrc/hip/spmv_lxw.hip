@@ -192,7 +192,9 @@ __device__ __forceinline__ LxwRegs<T> lxw_loads(const LxwBlock& blk, int t,
   return g;
 }
 
-// TV = type of `values`, T = type of x, y and the arithmetic.
+// TV = type of `values`, T = type of x, y and the arithmetic.  TV = float
+// under T = double is the plan's narrowed copy of values that are exact in
+// fp32 (lx_val32, padded to whole 16-byte chunks): widened in the row sum.
 //   vcap   entries per values slot (slot bytes a multiple of 1 KiB)
 //   lcap   entries per offsets slot
 //   xcap   elements per x buffer (pieces * kLxwPiece)
@@ -264,6 +266,10 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
       return false;
   };
   const int64_t code_len = lx_code_bytes(nnz);
+  // entries of `values` a 16-byte chunk may touch: the caller's array ends
+  // with its last entry, the plan's narrowed copy (TV = float under T =
+  // double) is padded to whole chunks
+  const int64_t val_len = std::is_same<TV, T>::value ? nnz : lx32_len(nnz);
   // A wave's share of a block's piece list: pieces wave, wave + 4, ... as
   // UNIFORM values, extracted from the per-lane list right after a wait -- a
   // v_readlane of a loaded register in the middle of the DMA issue would make
@@ -291,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
         s_dict[sl * (kLxwDictSize / 2) + t - kLxwDict0] = w;
     }
     const int64_t a = b.a, e = (int64_t)b.a + b.cnt;
-    lat_issue_dma<TV, NT>(values, nnz, a & ~(int64_t)(V - 1), e,
+    lat_issue_dma<TV, NT>(values, val_len, a & ~(int64_t)(V - 1), e,
                           s_val + (size_t)sl * vcap, t);
     if (b.nwin < 0)
       return;
@@ -605,7 +611,12 @@ int lxw_launch_c(const spmv_hip_csr_plan* pl, hipStream_t st,
   // (the geometry does not depend on C4: the codes take a quarter of the
   // offsets slot, and the grid, the row-block order and with them the fused
   // dot's partials stay what they are without the codes)
+  // (nor on TV: narrowed values run in the slots of T -- the same bytes per
+  // values slot, so the offsets slot and the x buffer start where they do for
+  // TV = T, and a slot holds sizeof(T) / sizeof(TV) times the entries: a block
+  // that fits the fp64 slot fits, and `a & 3` entries of alignment slack with)
   const LxwGeom g = lxw_geom(pl, (int)sizeof(T), XW ? 4 : 2);
+  const int vcap = g.vcap * (int)(sizeof(T) / sizeof(TV));
   const int nrb = (pl->num_rows + kRows - 1) / kRows;
   const int grid = lxw_grid(pl, (int)sizeof(T), XW ? 4 : 2);
   RowBlockOrder ord = pl->row_block_order(nrb);
@@ -628,7 +639,7 @@ int lxw_launch_c(const spmv_hip_csr_plan* pl, hipStream_t st,
                      pl->num_cols, pl->nnz, rowptr, colind, values,
                      XW ? nullptr : pl->lx_lidx, C4 ? pl->lx_code : nullptr,
                      XW ? pl->xw_rec : pl->lxw_rec, alpha, in, beta, out, dot,
-                     ord, g.vcap, g.lcap, g.xcap);
+                     ord, vcap, g.lcap, g.xcap);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -672,6 +683,19 @@ int spmv_lxw_run_f64(const spmv_hip_csr_plan* pl, hipStream_t st,
                                                    alpha, in, beta, out, dot);
   return lxw_launch<double, double, false, false>(pl, st, rowptr, colind, values,
                                                   alpha, in, beta, out, dot);
+}
+
+// `values`: the plan's narrowed copy (lx_val32) of the fp64 values
+int spmv_lxw_run_f32f64(const spmv_hip_csr_plan* pl, hipStream_t st,
+                        const int32_t* rowptr, const int32_t* colind,
+                        const float* values, double alpha, const double* in,
+                        double beta, double* out, DotOut dot)
+{
+  if (dot.partials)
+    return lxw_launch<float, double, true, false>(pl, st, rowptr, colind, values,
+                                                  alpha, in, beta, out, dot);
+  return lxw_launch<float, double, false, false>(pl, st, rowptr, colind, values,
+                                                 alpha, in, beta, out, dot);
 }
 
 int spmv_lxw_run_f32(const spmv_hip_csr_plan* pl, hipStream_t st,
