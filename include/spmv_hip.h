@@ -47,6 +47,7 @@ typedef struct spmv_hip_ctx spmv_hip_ctx;           /* one GPU             */
 typedef struct spmv_hip_csr_plan spmv_hip_csr_plan; /* CSRSpMV::_aux_data  */
 typedef struct spmv_hip_cg_ws spmv_hip_cg_ws;       /* cg() work vectors   */
 typedef struct spmv_hip_cgb_ws spmv_hip_cgb_ws;     /* cg_block() scalars  */
+typedef struct spmv_hip_pcg_ws spmv_hip_pcg_ws;     /* pcg() scalars       */
 typedef struct spmv_hip_comm spmv_hip_comm;         /* RCCL communicator   */
 
 int spmv_hip_abi_version(void);
@@ -793,6 +794,97 @@ int spmv_hip_cgb_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int k,
 int spmv_hip_cgb_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int k,
                                int64_t M, const double* R, double* X, double* P,
                                void* stream);
+
+/* ---- CG with a diagonal preconditioner (spmv::pcg) -------------------------------
+ * The preconditioner is the vector `dinv` of its inverse; z = dinv * r
+ * (elementwise) is never stored, every kernel that needs it forms it in
+ * registers.  From x0 = 0, with `.` the global dot product:
+ *   r0 = b; p1 = dinv*r0; rz[0] = r0.(dinv*r0); rr[0] = r0.r0
+ *   k = 1..kmax:  alpha = rz[k-1] / pAp[k];  x += alpha p;  r -= alpha Ap;
+ *                 rz[k] = r.(dinv*r); rr[k] = r.r;
+ *                 stop when sqrt(rr[k]) / sqrt(rr[0]) < rtol (x, r updated, p not)
+ *                 beta = rz[k] / rz[k-1];  p = beta p + dinv*r
+ * Products and sums are separate roundings.
+ *
+ * Device state of a workspace:
+ *   {rz[k], rr[k]} (k = 0..kmax) are ADJACENT, a pair of doubles per k: one
+ *   all-reduce of 2 doubles on the pair's address serves both; pAp[k] (k =
+ *   1..kmax); done = 1 once the solve has stopped, kstop = that k: the k whose
+ *   rr[k] met the tolerance, or 0 when rr[0] == 0 (then x = 0: the rule of
+ *   cg_block, not cg()'s run to kmax on NaNs);
+ *   three partial arrays of spmv_hip_dot_partials_len() doubles: p.Ap (filled
+ *   by the SpMV's fused dot or spmv_hip_dot_partial_f64), r.z and r.r.
+ * After `done` every pcg_* kernel returns at once, so the host may enqueue
+ * iterations ahead.  An iteration index outside its range (0..kmax for the
+ * slots and reduce_rz_rr, 1..kmax elsewhere) is SPMV_HIP_EINVAL. */
+int spmv_hip_pcg_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_pcg_ws** ws);
+int spmv_hip_pcg_ws_destroy(spmv_hip_pcg_ws* ws);
+int spmv_hip_pcg_ws_reset(spmv_hip_pcg_ws* ws, double rtol, void* stream);
+/* kmax the workspace was created with: its history holds kmax + 1 pairs */
+int spmv_hip_pcg_ws_capacity(const spmv_hip_pcg_ws* ws, int* kmax);
+/* device addresses of the pair {rz[k], rr[k]} and of pAp[k] (all-reduce) */
+int spmv_hip_pcg_ws_rz_rr(spmv_hip_pcg_ws* ws, int k, double** pair);
+int spmv_hip_pcg_ws_pAp(spmv_hip_pcg_ws* ws, int k, double** slot);
+/* the p.Ap partial array (for Matrix::mult_dot / spmv_hip_dot_partial_f64) */
+int spmv_hip_pcg_ws_partials(spmv_hip_pcg_ws* ws, double** partials);
+int spmv_hip_pcg_ws_done_flag(spmv_hip_pcg_ws* ws, const int32_t** done);
+/* copies {done, kstop} (2 x int32) and the pairs {rz[k], rr[k]}, k = 0..kmax,
+ * to the host (async on stream).  host_rz_rr_len = doubles `host_rz_rr` can
+ * take: fewer than 2 * (kmax + 1) (pcg_ws_capacity) -> SPMV_HIP_EINVAL, nothing
+ * is copied.  Either destination may be NULL (then it is skipped). */
+int spmv_hip_pcg_ws_read_async(spmv_hip_pcg_ws* ws, int32_t* host_done_kstop,
+                               double* host_rz_rr, size_t host_rz_rr_len,
+                               void* stream);
+/* start in one pass: r = b ; x = 0 ; p = dinv*b ; partials of r.z and r.r
+ * (then pcg_reduce_rz_rr(0) installs the pair 0).  b, dinv: any alignment. */
+int spmv_hip_pcg_init_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
+                          const double* b, const double* dinv, double* r,
+                          double* p, double* x, void* stream);
+/* update_r : r -= alpha Ap ; partials of r.(dinv*r) and r.r
+ * update_xp: x += alpha p ; stop test ; p = beta p + dinv*r
+ * Every vector 16-byte aligned. */
+int spmv_hip_pcg_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                              int64_t n, const double* Ap, const double* dinv,
+                              double* r, void* stream);
+int spmv_hip_pcg_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                               int64_t n, const double* r, const double* dinv,
+                               double* x, double* p, void* stream);
+/* single-workgroup reducers (local part; all-reduce the slot afterwards).
+ * reduce_pAp(k) first raises `done` when iteration k - 1 met the tolerance (at
+ * k = 1: when rr[0] == 0); _pAp2 adds a second partial array (the remote
+ * block's share of p.Ap); reduce_rz_rr(k) installs the pair k. */
+int spmv_hip_pcg_reduce_pAp(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                            void* stream);
+int spmv_hip_pcg_reduce_pAp2(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                             const double* partials2, void* stream);
+int spmv_hip_pcg_reduce_rz_rr(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                              void* stream);
+/* consumer-side forms for ONE rank (see spmv_hip_cg_update_r_cs_f64): every
+ * workgroup adds the preceding producer's partials itself, in the reducers'
+ * order (the same bits), workgroup 0 stores pAp[k] / the pair k.
+ *   update_r_cs : reduce_pAp (+ pap_partials2, may be NULL) + update_r
+ *   update_xp_cs: reduce_rz_rr + update_xp */
+int spmv_hip_pcg_update_r_cs_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                                 int64_t n, const double* Ap,
+                                 const double* dinv, double* r,
+                                 const double* pap_partials2, void* stream);
+int spmv_hip_pcg_update_xp_cs_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                                  int64_t n, const double* r,
+                                  const double* dinv, double* x, double* p,
+                                  void* stream);
+/* Setup of the Jacobi preconditioner.
+ * csr_diagonal: d[i] = the sum of the entries of row i whose column is i, left
+ * to right in storage order; 0 when the row has none.  One thread per row.
+ * jacobi_invert: dinv[i] = 1.0 / d[i] for every i; *bad_count (a device
+ * int32, overwritten) = the number of entries that are not finite or not > 0. */
+int spmv_hip_csr_diagonal_f64(spmv_hip_ctx* ctx, int32_t num_rows,
+                              const int32_t* rowptr, const int32_t* colind,
+                              const double* values, double* d, void* stream);
+int spmv_hip_csr_diagonal_f32(spmv_hip_ctx* ctx, int32_t num_rows,
+                              const int32_t* rowptr, const int32_t* colind,
+                              const float* values, float* d, void* stream);
+int spmv_hip_jacobi_invert_f64(spmv_hip_ctx* ctx, int64_t n, const double* d,
+                               double* dinv, int32_t* bad_count, void* stream);
 
 /* ---- 3-D Poisson generator (not in the reference)
  * 7-point stencil on an n^3 grid, natural ordering, diag 6, off-diag -1.

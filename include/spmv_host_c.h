@@ -346,6 +346,34 @@ int spmvh_cg_block(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                    spmvh_cg_block_workspace* ws, int flags,
                    double* spmv_ms_total, int* spmv_launches);
 
+/* Jacobi-preconditioned CG.
+ * spmvh_matrix_diagonal: Matrix::diagonal -- d (device, rows entries) = the
+ * diagonal of this rank's rows; general storage after release_csr is an error
+ * (take the diagonal first), symmetric storage keeps its diagonal.
+ * spmvh_jacobi_inverse: spmv::jacobi_inverse -- dinv = 1 / d on the device (n
+ * doubles each; they may coincide); an entry that is not finite or not > 0 is
+ * an error whose text says "diagonal is not positive".  One host wait.
+ * spmvh_pcg: spmv::pcg -- CG from x0 = 0 with the diagonal preconditioner
+ * whose inverse is dinv (device, rows doubles, positive; where it came from
+ * does not matter).  x must not overlap b or dinv.  rnorm_history (may be
+ * NULL): kmax + 1 entries, ||r_0|| .. ||r_k|| of the unpreconditioned residual.
+ * ws: a reusable spmv::PcgWorkspace (may be NULL).  flags: bit 0 ->
+ * CgOptions::time_spmv (*spmv_ms_total, *spmv_launches, both may be NULL),
+ * bit 2 switches CgOptions::consumer_reductions off, bits 8-15
+ * CgOptions::poll_every (0 = default). */
+typedef struct spmvh_pcg_workspace spmvh_pcg_workspace;
+int spmvh_matrix_diagonal(spmvh_matrix* A, double* d);
+int spmvh_jacobi_inverse(spmvh_exec* exec, const double* d, double* dinv,
+                         int64_t n);
+int spmvh_pcg_workspace_create(spmvh_exec* exec, spmvh_pcg_workspace** ws);
+int spmvh_pcg_workspace_destroy(spmvh_pcg_workspace* ws);
+int spmvh_pcg_workspace_reserve_timing(spmvh_pcg_workspace* ws, int iterations);
+int spmvh_pcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+              const double* b, double* x, const double* dinv, int kmax,
+              double rtol, int* num_its, double* rnorm_history,
+              spmvh_pcg_workspace* ws, int flags, double* spmv_ms_total,
+              int* spmv_launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,30 @@ _PROTOS = {
     "spmv_hip_cgb_update_r_f64": ([vp, vp, C.c_int, i64, vp, vp, vp], C.c_int),
     "spmv_hip_cgb_update_xp_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp],
                                    C.c_int),
+    "spmv_hip_pcg_ws_create": ([vp, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_pcg_ws_destroy": ([vp], C.c_int),
+    "spmv_hip_pcg_ws_reset": ([vp, f64, vp], C.c_int),
+    "spmv_hip_pcg_ws_capacity": ([vp, P(C.c_int)], C.c_int),
+    "spmv_hip_pcg_ws_rz_rr": ([vp, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_pcg_ws_pAp": ([vp, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_pcg_ws_partials": ([vp, P(vp)], C.c_int),
+    "spmv_hip_pcg_ws_done_flag": ([vp, P(vp)], C.c_int),
+    "spmv_hip_pcg_ws_read_async": ([vp, vp, vp, sz, vp], C.c_int),
+    "spmv_hip_pcg_init_f64": ([vp, vp, i64, vp, vp, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_pcg_update_r_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp],
+                                  C.c_int),
+    "spmv_hip_pcg_update_xp_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp, vp],
+                                   C.c_int),
+    "spmv_hip_pcg_reduce_pAp": ([vp, vp, C.c_int, vp], C.c_int),
+    "spmv_hip_pcg_reduce_pAp2": ([vp, vp, C.c_int, vp, vp], C.c_int),
+    "spmv_hip_pcg_reduce_rz_rr": ([vp, vp, C.c_int, vp], C.c_int),
+    "spmv_hip_pcg_update_r_cs_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp, vp],
+                                     C.c_int),
+    "spmv_hip_pcg_update_xp_cs_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp,
+                                       vp], C.c_int),
+    "spmv_hip_csr_diagonal_f64": ([vp, i32, vp, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_csr_diagonal_f32": ([vp, i32, vp, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_jacobi_invert_f64": ([vp, i64, vp, vp, vp, vp], C.c_int),
     "spmv_hip_poisson3d_count": ([vp, i32, i64, i64, C.c_int, vp, P(i64), vp],
                                  C.c_int),
     "spmv_hip_poisson3d_fill_f64": ([vp, i32, i64, i64, C.c_int, vp, vp, vp,

@@ -48,6 +48,10 @@ struct spmvh_cg_block_workspace {
   std::shared_ptr<HipExecutor> exec; // keeps the executor alive
   std::unique_ptr<CgBlockWorkspace> ws;
 };
+struct spmvh_pcg_workspace {
+  std::shared_ptr<HipExecutor> exec; // keeps the executor alive
+  std::unique_ptr<PcgWorkspace> ws;
+};
 
 namespace
 {
@@ -1153,6 +1157,76 @@ int spmvh_cg_block(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                         &its, rnorm_history ? &hist : nullptr, &opt, &st,
                         ws ? ws->ws.get() : nullptr);
     std::copy(its.begin(), its.end(), iterations);
+    if (rnorm_history)
+      std::copy(hist.begin(), hist.end(), rnorm_history);
+    if (spmv_ms_total)
+      *spmv_ms_total = st.spmv_ms_total;
+    if (spmv_launches)
+      *spmv_launches = st.spmv_launches;
+  });
+}
+
+// ---- Jacobi-preconditioned CG -----------------------------------------------------------
+int spmvh_matrix_diagonal(spmvh_matrix* A, double* d)
+{
+  return guarded([&] {
+    require(A != nullptr && d != nullptr, "NULL argument");
+    A->A->diagonal(d);
+  });
+}
+
+int spmvh_jacobi_inverse(spmvh_exec* exec, const double* d, double* dinv,
+                         int64_t n)
+{
+  return guarded([&] {
+    require(exec != nullptr, "NULL argument");
+    require(n >= 0 && (n == 0 || (d && dinv)), "bad argument");
+    jacobi_inverse(*exec->hip, d, dinv, n);
+  });
+}
+
+int spmvh_pcg_workspace_create(spmvh_exec* exec, spmvh_pcg_workspace** ws)
+{
+  return guarded([&] {
+    require(exec && ws, "NULL argument");
+    auto w = std::make_unique<spmvh_pcg_workspace>();
+    w->exec = exec->hip;
+    w->ws.reset(new PcgWorkspace(*exec->hip));
+    *ws = w.release();
+  });
+}
+
+int spmvh_pcg_workspace_destroy(spmvh_pcg_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_pcg_workspace_reserve_timing(spmvh_pcg_workspace* ws, int iterations)
+{
+  return guarded([&] {
+    require(ws, "NULL argument");
+    ws->ws->reserve_timing(iterations);
+  });
+}
+
+int spmvh_pcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+              const double* b, double* x, const double* dinv, int kmax,
+              double rtol, int* num_its, double* rnorm_history,
+              spmvh_pcg_workspace* ws, int flags, double* spmv_ms_total,
+              int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && num_its, "NULL argument");
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    opt.consumer_reductions = (flags & 4) == 0; // bit 2 switches it off
+    if ((flags >> 8) & 0xff) // bits 8-15: CgOptions::poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    CgStats st;
+    *num_its = pcg(*comm->comm, *exec->hip, *A->A, b, x, dinv, kmax, rtol,
+                   rnorm_history ? &hist : nullptr, &opt, &st,
+                   ws ? ws->ws.get() : nullptr);
     if (rnorm_history)
       std::copy(hist.begin(), hist.end(), rnorm_history);
     if (spmv_ms_total)

@@ -739,4 +739,334 @@ int cg_block(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   return k_max;
 }
 
+// ---------------------------------------------------------------------------
+// pcg: see cg.h.  Per iteration (compute stream):
+//     halo start on the map's side stream
+//     SpMV local block (+ fused p.Ap share) [wait halo event] remote block
+//     one rank, consumer_reductions:            otherwise:
+//       update_r_cs   (pAp[k]; r; r.z, r.r)       reduce_pAp(2) ; all-reduce of 1
+//       update_xp_cs  ({rz,rr}[k]; x; p)          update_r
+//                                                 reduce_rz_rr ; all-reduce of 2
+//                                                 update_xp
+// 3 (or 5) launches; beside the SpMV 10 vector passes (update_r: Ap, r, dinv
+// in, r out; update_xp: r, dinv, x, p in, x, p out) where cg() without
+// defer_x streams 8.
+// ---------------------------------------------------------------------------
+PcgWorkspace::~PcgWorkspace() { release(); }
+
+void PcgWorkspace::release()
+{
+  try {
+    if (stream)
+      _exec.synchronize_stream(stream);
+    _exec.destroy_event(poll_event);
+    for (void* e : timing_ev)
+      _exec.destroy_event(e);
+    if (stream)
+      _exec.destroy_stream(stream);
+    spmv_hip_pcg_ws_destroy(ws);
+    _exec.free(r);
+    _exec.free(Ap);
+    _exec.free(x);
+    _exec.free(dinv);
+    _exec.free(p);
+    _exec.free(dot2);
+    spmv_hip_host_free(_exec.context(), flags);
+  } catch (...) {
+  }
+  timing_ev.clear();
+  ws = nullptr;
+  r = Ap = x = dinv = p = dot2 = nullptr;
+  flags = nullptr;
+  stream = poll_event = nullptr;
+  kmax_cap = -1;
+  m_cap = n_cap = x_cap = dinv_cap = -1;
+}
+
+void PcgWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
+                          bool need_x, bool need_dinv)
+{
+  spmv_hip_ctx* ctx = _exec.context();
+  if (!stream) {
+    stream = _exec.create_stream();
+    poll_event = _exec.create_event();
+    void* mem = nullptr;
+    throw_on_error(spmv_hip_host_alloc(ctx, 2 * sizeof(int32_t), &mem),
+                   "spmv_hip_host_alloc");
+    flags = static_cast<int32_t*>(mem);
+    dot2 = _exec.alloc<double>(len);
+  }
+  if (kmax > kmax_cap) {
+    // (an earlier solve on this workspace has been synchronised: nothing
+    // still reads the old scalars)
+    spmv_hip_pcg_ws_destroy(ws);
+    ws = nullptr;
+    kmax_cap = -1;
+    throw_on_error(spmv_hip_pcg_ws_create(ctx, kmax, &ws),
+                   "spmv_hip_pcg_ws_create");
+    kmax_cap = kmax;
+  }
+  if (M > m_cap) {
+    _exec.free(r);
+    _exec.free(Ap);
+    r = Ap = nullptr;
+    m_cap = -1;
+    r = _exec.alloc<double>(M);
+    Ap = _exec.alloc<double>(M);
+    m_cap = M;
+  }
+  if (need_x && M > x_cap) {
+    _exec.free(x);
+    x = nullptr;
+    x_cap = -1;
+    x = _exec.alloc<double>(M);
+    x_cap = M;
+  }
+  if (need_dinv && M > dinv_cap) {
+    _exec.free(dinv);
+    dinv = nullptr;
+    dinv_cap = -1;
+    dinv = _exec.alloc<double>(M);
+    dinv_cap = M;
+  }
+  if (N_padded > n_cap) {
+    _exec.free(p);
+    p = nullptr;
+    n_cap = -1;
+    p = _exec.alloc<double>(N_padded);
+    n_cap = N_padded;
+  }
+}
+
+void PcgWorkspace::reserve_timing(int iterations)
+{
+  while (timing_ev.size() < 2 * (size_t)(iterations < 0 ? 0 : iterations))
+    timing_ev.push_back(_exec.create_event(true));
+}
+
+void jacobi_inverse(HipExecutor& exec, const double* d, double* dinv, int64_t n)
+{
+  if (n < 0)
+    throw std::runtime_error("spmv::jacobi_inverse - Error: n < 0");
+  int32_t* count = exec.alloc<int32_t>(1);
+  int32_t bad = 0;
+  try {
+    throw_on_error(spmv_hip_jacobi_invert_f64(exec.context(), n, d, dinv, count,
+                                              nullptr),
+                   "spmv_hip_jacobi_invert_f64");
+    exec.copy_to<int32_t>(&bad, exec.get_host(), count, 1); // waits
+  } catch (...) {
+    exec.free(count);
+    throw;
+  }
+  exec.free(count);
+  if (bad != 0)
+    throw std::runtime_error(
+        "spmv::jacobi_inverse - Error: the diagonal is not positive ("
+        + std::to_string(bad) + " of " + std::to_string(n)
+        + " entries are not finite or not > 0)");
+}
+
+int pcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+        const double* b, double* x, const double* dinv, int kmax, double rtol,
+        std::vector<double>* rnorm_history, const CgOptions* options,
+        CgStats* stats, PcgWorkspace* workspace)
+{
+  std::shared_ptr<const L2GMap> col_l2g = A.col_map();
+  std::shared_ptr<const L2GMap> row_l2g = A.row_map();
+  if (row_l2g->num_ghosts() > 0)
+    throw std::runtime_error("spmv::pcg - Error: A.row_map() has ghost entries");
+  if (kmax < 0)
+    throw std::runtime_error("spmv::pcg - Error: kmax < 0");
+  const CgOptions opt = options ? *options : CgOptions();
+  const int poll_every = opt.poll_every < 1 ? 1 : opt.poll_every;
+
+  const int64_t M = row_l2g->local_size();
+  const int64_t N_padded = col_l2g->local_size() + col_l2g->num_ghosts();
+  spmv_hip_ctx* ctx = exec.context();
+  int len = 0;
+  throw_on_error(spmv_hip_dot_partials_len(ctx, &len),
+                 "spmv_hip_dot_partials_len");
+
+  { // x is the iterate from the first kernel on: it cannot share b or dinv
+    const uintptr_t xb = reinterpret_cast<uintptr_t>(x);
+    const uintptr_t bytes = (uintptr_t)M * sizeof(double);
+    auto overlaps = [&](const double* v) {
+      const uintptr_t vb = reinterpret_cast<uintptr_t>(v);
+      return M > 0 && xb < vb + bytes && vb < xb + bytes;
+    };
+    if (overlaps(b))
+      throw std::runtime_error("pcg: x overlaps b (x is updated in place)");
+    if (overlaps(dinv))
+      throw std::runtime_error("pcg: x overlaps dinv (x is updated in place)");
+  }
+  PcgWorkspace own(exec);
+  PcgWorkspace& w = workspace ? *workspace : own;
+  const bool x_aligned = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+  const bool dinv_aligned = (reinterpret_cast<uintptr_t>(dinv) & 15u) == 0;
+  w.ensure(M, N_padded, kmax, len, !x_aligned, !dinv_aligned);
+  if (opt.time_spmv)
+    w.reserve_timing(kmax);
+
+  StreamGuard guard{exec, exec.get_stream()};
+  { // order after whatever the caller enqueued (b, dinv may still be in flight)
+    void* ev = exec.create_event();
+    exec.record_event(ev, guard.prev);
+    exec.stream_wait_event(w.stream, ev);
+    exec.destroy_event(ev);
+  }
+  exec.set_stream(w.stream); // every launch below goes to this stream
+
+  throw_on_error(spmv_hip_pcg_ws_reset(w.ws, rtol, nullptr),
+                 "spmv_hip_pcg_ws_reset");
+  double* partials = nullptr;
+  throw_on_error(spmv_hip_pcg_ws_partials(w.ws, &partials),
+                 "spmv_hip_pcg_ws_partials");
+
+  double* const xi = x_aligned ? x : w.x;
+  const double* di = dinv;
+  if (!dinv_aligned) { // the streaming kernels load 16 bytes at a time
+    exec.copy<double>(w.dinv, dinv, M);
+    di = w.dinv;
+  }
+  // the ghost tail of p is defined here instead of relying on fresh pages
+  if (N_padded > M)
+    exec.memset<double>(w.p + M, 0, N_padded - M);
+  exec.memset<double>(w.dot2, 0, len);
+  // r = b, x0 = 0, p = dinv*b, partials of r.z and r.r: one pass
+  throw_on_error(spmv_hip_pcg_init_f64(ctx, w.ws, M, b, di, w.r, w.p, xi,
+                                       nullptr),
+                 "spmv_hip_pcg_init_f64");
+  w.flags[0] = 0;
+  w.flags[1] = -1;
+
+  auto pair_slot = [&](int k) {
+    double* s = nullptr;
+    throw_on_error(spmv_hip_pcg_ws_rz_rr(w.ws, k, &s), "spmv_hip_pcg_ws_rz_rr");
+    return s;
+  };
+  auto pAp_slot = [&](int k) {
+    double* s = nullptr;
+    throw_on_error(spmv_hip_pcg_ws_pAp(w.ws, k, &s), "spmv_hip_pcg_ws_pAp");
+    return s;
+  };
+
+  // {rz0, rr0}: one all-reduce of 2 doubles
+  throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, 0, nullptr),
+                 "spmv_hip_pcg_reduce_rz_rr");
+  comm.reduce_sum(pair_slot(0), 2, w.stream);
+
+  const bool consume = opt.consumer_reductions && comm.size() == 1;
+  std::vector<void*>& timing_ev = w.timing_ev;
+  int k = 0;
+  bool stopped = false;
+  bool poll_pending = false;
+  while (k < kmax && !stopped) {
+    ++k;
+    col_l2g->update(w.p); // starts on the side stream
+    void* ev1 = nullptr;
+    if (opt.time_spmv) {
+      ev1 = timing_ev[2 * (size_t)(k - 1) + 1];
+      exec.record_event(timing_ev[2 * (size_t)(k - 1)], w.stream);
+    }
+    // Ap = A p with the p.Ap partials produced by the SpMV kernels themselves
+    // (local block's share + remote block's share) where they can
+    const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
+    if (!fused)
+      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, w.p, w.Ap, partials,
+                                              nullptr),
+                     "spmv_hip_dot_partial_f64");
+    if (consume) {
+      // one rank: the update kernels add the partials themselves
+      throw_on_error(spmv_hip_pcg_update_r_cs_f64(ctx, w.ws, k, M, w.Ap, di,
+                                                  w.r, fused ? w.dot2 : nullptr,
+                                                  nullptr),
+                     "spmv_hip_pcg_update_r_cs_f64");
+      throw_on_error(spmv_hip_pcg_update_xp_cs_f64(ctx, w.ws, k, M, w.r, di, xi,
+                                                   w.p, nullptr),
+                     "spmv_hip_pcg_update_xp_cs_f64");
+    } else {
+      if (fused)
+        throw_on_error(spmv_hip_pcg_reduce_pAp2(ctx, w.ws, k, w.dot2, nullptr),
+                       "spmv_hip_pcg_reduce_pAp2");
+      else
+        throw_on_error(spmv_hip_pcg_reduce_pAp(ctx, w.ws, k, nullptr),
+                       "spmv_hip_pcg_reduce_pAp");
+      comm.reduce_sum(pAp_slot(k), 1, w.stream);
+      throw_on_error(spmv_hip_pcg_update_r_f64(ctx, w.ws, k, M, w.Ap, di, w.r,
+                                               nullptr),
+                     "spmv_hip_pcg_update_r_f64");
+      throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, k, nullptr),
+                     "spmv_hip_pcg_reduce_rz_rr");
+      comm.reduce_sum(pair_slot(k), 2, w.stream); // rz[k] and rr[k] at once
+      throw_on_error(spmv_hip_pcg_update_xp_f64(ctx, w.ws, k, M, w.r, di, xi,
+                                                w.p, nullptr),
+                     "spmv_hip_pcg_update_xp_f64");
+    }
+
+    if (k % poll_every == 0 && k < kmax) {
+      // lagging look at the flag, as in cg()
+      if (poll_pending) {
+        exec.synchronize_event(w.poll_event);
+        stopped = w.flags[0] != 0;
+      }
+      if (!stopped) {
+        throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, nullptr, 0,
+                                                  nullptr),
+                       "spmv_hip_pcg_ws_read_async");
+        exec.record_event(w.poll_event, w.stream);
+        poll_pending = true;
+      }
+    }
+  }
+
+  // final state: {done, kstop} and the history of pairs (it has the
+  // WORKSPACE's capacity; the C ABI refuses a shorter destination)
+  int cap = 0;
+  throw_on_error(spmv_hip_pcg_ws_capacity(w.ws, &cap),
+                 "spmv_hip_pcg_ws_capacity");
+  std::vector<double> zr(2 * ((size_t)std::max(kmax, cap) + 1), 0.0);
+  throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, zr.data(), zr.size(),
+                                            nullptr),
+                 "spmv_hip_pcg_ws_read_async");
+  if (xi != x)
+    exec.copy<double>(x, xi, M);
+  exec.synchronize_stream(w.stream);
+
+  if (stats) {
+    *stats = CgStats();
+    for (size_t i = 0; opt.time_spmv && i + 1 < 2 * (size_t)k; i += 2) {
+      float ms = 0.f;
+      throw_on_error(spmv_hip_event_elapsed_ms(ctx, timing_ev[i],
+                                               timing_ev[i + 1], &ms),
+                     "spmv_hip_event_elapsed_ms");
+      stats->spmv_ms_total += ms;
+      ++stats->spmv_launches;
+    }
+  }
+
+  auto rr_at = [&](int j) { return zr[2 * (size_t)j + 1]; };
+  int k_final = k;
+  if (w.flags[0] != 0) {
+    k_final = w.flags[1];
+  } else if (rr_at(0) == 0.0) {
+    k_final = 0; // (kmax == 0: no kernel ran to say so)
+  } else {
+    // `done` is raised by the first kernel of the NEXT iteration; when the
+    // loop ends first, apply the same test to the history here, as cg() does
+    const double rnorm0 = std::sqrt(rr_at(0));
+    for (int j = 1; j <= k; ++j)
+      if (std::sqrt(rr_at(j)) / rnorm0 < rtol) {
+        k_final = j;
+        break;
+      }
+  }
+  if (rnorm_history) {
+    rnorm_history->resize(k_final + 1);
+    for (int j = 0; j <= k_final; ++j)
+      (*rnorm_history)[j] = std::sqrt(rr_at(j));
+  }
+  return k_final;
+}
+
 } // namespace spmv

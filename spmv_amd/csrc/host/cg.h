@@ -11,6 +11,7 @@
 
 struct spmv_hip_cg_ws;
 struct spmv_hip_cgb_ws;
+struct spmv_hip_pcg_ws;
 
 namespace spmv
 {
@@ -184,5 +185,86 @@ int cg_block(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
              std::vector<double>* rnorm_history = nullptr,
              const CgOptions* options = nullptr, CgStats* stats = nullptr,
              CgBlockWorkspace* workspace = nullptr);
+
+// Work vectors + device scalars of pcg(), kept across calls like CgWorkspace;
+// it regrows itself when a call needs more rows or more iterations.
+class PcgWorkspace
+{
+public:
+  explicit PcgWorkspace(HipExecutor& exec) : _exec(exec) {}
+  ~PcgWorkspace();
+  PcgWorkspace(const PcgWorkspace&) = delete;
+  PcgWorkspace& operator=(const PcgWorkspace&) = delete;
+
+  // ---- internal to pcg() ----
+  // need_x / need_dinv: the caller's x / dinv is not 16-byte aligned and lives
+  // in the workspace's copy during the solve
+  void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len,
+              bool need_x, bool need_dinv);
+  void reserve_timing(int iterations);
+  void release();
+
+  HipExecutor& _exec;
+  spmv_hip_pcg_ws* ws = nullptr;
+  int kmax_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, x_cap = -1, dinv_cap = -1;
+  double *r = nullptr, *Ap = nullptr; // m_cap
+  double* x = nullptr;      // x_cap: the iterate when the caller's x is unaligned
+  double* dinv = nullptr;   // dinv_cap: the copy of an unaligned dinv
+  double* p = nullptr;      // n_cap: padded, the ghost tail is zeroed by every solve
+  double* dot2 = nullptr;   // partials of the remote block's p.Ap share
+  int32_t* flags = nullptr; // pinned {done, kstop}
+  void* stream = nullptr;   // compute stream of the solve
+  void* poll_event = nullptr;
+  std::vector<void*> timing_ev; // CgOptions::time_spmv: 2 events per iteration
+};
+
+// dinv[i] = 1.0 / d[i] (spmv_hip_jacobi_invert_f64); `d` and `dinv` DEVICE
+// pointers of n doubles (they may be the same vector).  Reads the device's
+// count of entries that are not finite or not > 0 ONCE -- the only host wait of
+// the preconditioner's setup, outside any solve -- and throws
+// std::runtime_error("... diagonal is not positive ...") when it is nonzero
+// (dinv then holds the quotients all the same).
+void jacobi_inverse(HipExecutor& exec, const double* d, double* dinv, int64_t n);
+
+// CG with a diagonal preconditioner from x0 = 0.  `dinv` is any positive
+// DEVICE vector of A.row_map()->local_size() doubles, the inverse of the
+// preconditioner's diagonal: Jacobi's comes from Matrix::diagonal and
+// jacobi_inverse, the solver does not care.  With `.` the global dot product:
+//
+//   r0 = b; p1 = dinv*r0 (elementwise); rz0 = r0.(dinv*r0); rr0 = r0.r0
+//   for k = 1..kmax:
+//     Ap    = A p_k                  (halo update of p first, as in cg())
+//     alpha = rz[k-1] / (p_k . Ap)
+//     x    += alpha * p_k
+//     r    -= alpha * Ap
+//     rz[k] = r.(dinv*r); rr[k] = r.r
+//     if sqrt(rr[k]) / sqrt(rr[0]) < rtol: stop (x and r updated, p not)
+//     beta  = rz[k] / rz[k-1]
+//     p_(k+1) = beta * p_k + dinv*r
+//
+// Products and sums are separate roundings.  z = dinv*r is never stored: the
+// two update kernels recompute it, dinv is read twice per iteration.  The
+// stopping test is cg()'s, on the unpreconditioned 2-norm, so the histories of
+// the two solvers compare; rnorm_history receives ||r_0||, ..., ||r_k||.  A
+// system with r_0 . r_0 == 0 stops at k = 0 with x = 0 (the rule of cg_block,
+// not cg()'s run to kmax on NaNs).  Returns k.
+//
+// As in cg(): scalars stay on the device, reductions are two-stage and
+// deterministic, convergence is decided on the device and the host only looks
+// at a pinned flag every `poll_every` iterations; `x` IS the iterate and must
+// not overlap `b` or `dinv` (std::runtime_error, "overlaps"); an `x` (or a
+// `dinv`) that is not 16-byte aligned goes through the workspace's copy, x
+// with one copy at the end; kmax < 0 throws; the executor's stream is
+// restored on every exit path.
+//
+// options: poll_every, time_spmv and consumer_reductions apply (one rank with
+//          consumer_reductions: 3 launches per iteration, else 5); defer_x and
+//          mixed are IGNORED: x is updated in every iteration, in fp64.
+int pcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+        const double* b, double* x, const double* dinv, int kmax, double rtol,
+        std::vector<double>* rnorm_history = nullptr,
+        const CgOptions* options = nullptr, CgStats* stats = nullptr,
+        PcgWorkspace* workspace = nullptr);
 
 } // namespace spmv

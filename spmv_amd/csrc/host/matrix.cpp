@@ -212,6 +212,50 @@ void Matrix<T>::transpmult(T* b, T* y) const
   }
 }
 
+// ---------------------------------------------------------------------------
+// diagonal (see matrix.h)
+// ---------------------------------------------------------------------------
+template <typename T>
+void Matrix<T>::diagonal(T* d) const
+{
+  if (_row_map->num_ghosts() > 0
+      || _row_map->local_size() != _col_map->local_size()
+      || _row_map->global_offset() != _col_map->global_offset())
+    throw std::runtime_error(
+        "Matrix::diagonal: rows and owned columns are not the same index range "
+        "on this rank");
+  auto* hip = dynamic_cast<HipExecutor*>(_exec.get());
+  if (!hip)
+    throw std::runtime_error(
+        "spmv::HostExecutor::diagonal: this build has no CPU compute path; "
+        "create the matrix with a HipExecutor");
+  const int32_t M = _row_map->local_size();
+  if (M == 0)
+    return;
+  if (_symmetric) {
+    _exec->template copy<T>(d, _mat_local->diagonal(), M);
+    return;
+  }
+  if (_mat_local->non_zeros() == 0) { // an empty block owns no arrays
+    _exec->template memset<T>(d, 0, M);
+    return;
+  }
+  if (_mat_local->csr_released())
+    throw std::runtime_error(
+        "Matrix::diagonal: the CSR arrays of this matrix were released "
+        "(release_csr); take the diagonal before releasing them");
+  if constexpr (std::is_same<T, double>::value)
+    throw_on_error(spmv_hip_csr_diagonal_f64(
+                       hip->context(), M, _mat_local->rowptr(),
+                       _mat_local->colind(), _mat_local->values(), d, nullptr),
+                   "spmv_hip_csr_diagonal_f64");
+  else
+    throw_on_error(spmv_hip_csr_diagonal_f32(
+                       hip->context(), M, _mat_local->rowptr(),
+                       _mat_local->colind(), _mat_local->values(), d, nullptr),
+                   "spmv_hip_csr_diagonal_f32");
+}
+
 template <typename T>
 bool Matrix<T>::enable_mixed() const
 {

@@ -92,6 +92,24 @@ public:
   void transpmult(T* b, T* y) const;
   void enable_transpose() const;
 
+  // d[i] = the diagonal entry of local row i (the reference has no such
+  // query).  `d`: DEVICE pointer of row_map()->local_size() entries, written
+  // on the executor's current stream.
+  //   symmetric   a device copy of the local block's diagonal array
+  //   general     spmv_hip_csr_diagonal_* over the local block: the sum of the
+  //               entries of row i whose column is i, in storage order; 0 when
+  //               the row has none
+  // Rows and owned columns must be the same index range on this rank (no
+  // ghost rows; local size and global offset of row_map and col_map equal),
+  // else std::runtime_error.
+  // After release_csr() (or with the context option "release_csr"):
+  //   general     throws std::runtime_error -- the values it would read were
+  //               given back; a caller who wants both takes the diagonal first
+  //   symmetric   unchanged: release_csr() frees colind and values of the
+  //               strictly lower block only, the diagonal array is its own
+  //               allocation and stays until the matrix is destroyed
+  void diagonal(T* d) const;
+
   std::shared_ptr<L2GMap> row_map() const { return _row_map; }
   std::shared_ptr<const L2GMap> col_map() const { return _col_map; }
 

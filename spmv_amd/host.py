@@ -130,6 +130,13 @@ _PROTOS = {
     "spmvh_cg_block_workspace_destroy": [vp],
     "spmvh_cg_block": [vp, vp, vp, vp, vp, C.c_int, C.c_int, f64, PTR(C.c_int),
                        vp, vp, vp, C.c_int, PTR(f64), PTR(C.c_int)],
+    "spmvh_matrix_diagonal": [vp, vp],
+    "spmvh_jacobi_inverse": [vp, vp, vp, i64],
+    "spmvh_pcg_workspace_create": [vp, PTR(vp)],
+    "spmvh_pcg_workspace_destroy": [vp],
+    "spmvh_pcg_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_pcg": [vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int), vp, vp,
+                  C.c_int, PTR(f64), PTR(C.c_int)],
 }
 for _n, _a in _PROTOS.items():
     _f = getattr(lib, _n)
@@ -556,6 +563,11 @@ class Matrix:
         """build the transposed maps now (before release_csr)"""
         call("spmvh_matrix_enable_transpose", self.h)
 
+    def diagonal(self, d_ptr):
+        """Matrix::diagonal: d (device, rows entries) = the diagonal of this
+        rank's rows.  General storage: before release_csr only."""
+        call("spmvh_matrix_diagonal", self.h, d_ptr)
+
 
 class MatrixF32:
     """spmv::Matrix<float> (fp32 instantiation)"""
@@ -804,6 +816,50 @@ def cg_block(comm, exec_, A, b_ptr, x_ptr, nrhs, kmax, rtol, workspace=None,
          C.byref(n))
     return its, hist, dict(max_iterations=kmx.value, spmv_ms_total=ms.value,
                            spmv_launches=n.value)
+
+
+def jacobi_inverse(exec_, d_ptr, dinv_ptr, n):
+    """spmv::jacobi_inverse: dinv = 1 / d on the device (n doubles each; they
+    may coincide).  Raises SpmvHostError ("diagonal is not positive") when an
+    entry is not finite or not > 0."""
+    call("spmvh_jacobi_inverse", exec_.h, d_ptr, dinv_ptr, int(n))
+
+
+class PcgWorkspace:
+    """spmv::PcgWorkspace: work vectors kept across pcg() calls."""
+
+    def __init__(self, exec_):
+        h = vp()
+        call("spmvh_pcg_workspace_create", exec_.h, C.byref(h))
+        self.h = h
+
+    def reserve_timing(self, iterations):
+        call("spmvh_pcg_workspace_reserve_timing", self.h, int(iterations))
+
+    def close(self):
+        if self.h:
+            call("spmvh_pcg_workspace_destroy", self.h)
+            self.h = None
+
+
+def pcg(comm, exec_, A, b_ptr, x_ptr, dinv_ptr, kmax, rtol, workspace=None,
+        time_spmv=False, consumer_reductions=True, poll_every=0, stats=None):
+    """spmv::pcg: CG from x0 = 0 with the diagonal preconditioner whose inverse
+    is dinv -> (k, rnorm_history).  The history is that of the unpreconditioned
+    residual, ||r_0|| .. ||r_k||, as cg()'s.  stats (optional dict) receives
+    spmv_ms_total and spmv_launches of a time_spmv solve."""
+    kmax = int(kmax)
+    k, n = C.c_int(), C.c_int()
+    ms = f64()
+    hist = np.zeros(max(kmax, 0) + 1)
+    call("spmvh_pcg", comm.h, exec_.h, A.h, b_ptr, x_ptr, dinv_ptr, kmax,
+         float(rtol), C.byref(k), _np_ptr(hist),
+         workspace.h if workspace else None,
+         int(bool(time_spmv)) | (0 if consumer_reductions else 4)
+         | ((int(poll_every) & 0xff) << 8), C.byref(ms), C.byref(n))
+    if stats is not None:
+        stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, hist[:k.value + 1]
 
 
 def host_executor_rejects_compute():
