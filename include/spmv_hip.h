@@ -48,6 +48,7 @@ typedef struct spmv_hip_csr_plan spmv_hip_csr_plan; /* CSRSpMV::_aux_data  */
 typedef struct spmv_hip_cg_ws spmv_hip_cg_ws;       /* cg() work vectors   */
 typedef struct spmv_hip_cgb_ws spmv_hip_cgb_ws;     /* cg_block() scalars  */
 typedef struct spmv_hip_pcg_ws spmv_hip_pcg_ws;     /* pcg() scalars       */
+typedef struct spmv_hip_bicg_ws spmv_hip_bicg_ws;   /* bicgstab() scalars  */
 typedef struct spmv_hip_comm spmv_hip_comm;         /* RCCL communicator   */
 
 int spmv_hip_abi_version(void);
@@ -885,6 +886,117 @@ int spmv_hip_csr_diagonal_f32(spmv_hip_ctx* ctx, int32_t num_rows,
                               const float* values, float* d, void* stream);
 int spmv_hip_jacobi_invert_f64(spmv_hip_ctx* ctx, int64_t n, const double* d,
                                double* dinv, int32_t* bad_count, void* stream);
+
+/* ---- BiCGStab with an optional diagonal right preconditioner (spmv::bicgstab) ---
+ * For nonsymmetric systems.  `dinv` is the inverse of the preconditioner's
+ * diagonal or NULL; ph = dinv*p, sh = dinv*s (elementwise), p and s themselves
+ * without it.  From x0 = 0, with `.` the global dot product:
+ *   r0 = rhat = p1 = b; rho[0] = rr[0] = b.b
+ *   k = 1..kmax:  v = A ph;  rv[k] = rhat.v;  rv[k] == 0 -> breakdown 1
+ *                 alpha = rho[k-1] / rv[k];  s = r - alpha v
+ *                 t = A sh;  ts[k] = t.s;  tt[k] = t.t
+ *                 omega = tt[k] == 0 ? 0 : ts[k] / tt[k]
+ *                 x += alpha ph;  x += omega sh;  r = s - omega t
+ *                 rr[k] = r.r;  rho[k] = rhat.r
+ *                 stop when sqrt(rr[k]) / sqrt(rr[0]) < rtol (x, r updated, p not)
+ *                 omega == 0 or rho[k] == 0 -> breakdown 2 (x, r, rr[k] valid)
+ *                 beta = (rho[k] / rho[k-1]) * (alpha / omega)
+ *                 p = r + beta (p - omega v)
+ * Products and sums are separate roundings.
+ *
+ * Device state of a workspace:
+ *   rv[k]; the pairs {ts[k], tt[k]} and {rr[k], rho[k]} (k = 0..kmax), each
+ *   pair ADJACENT, 16 bytes per k: one all-reduce of 2 doubles on the pair's
+ *   address serves both;
+ *   done = 1 once the solve has stopped, kstop = the iterations completed,
+ *   status = 0 (the tolerance was met, or rr[0] == 0: kstop = 0, x = 0),
+ *   1 (breakdown 1: kstop = k - 1, iteration k wrote nothing) or
+ *   2 (breakdown 2: kstop = k);
+ *   five partial arrays of spmv_hip_dot_partials_len() doubles (rhat.v, t.s,
+ *   t.t, r.r, rhat.r).
+ * `done` is raised by update_s (breakdown 1, rr[0] == 0) and update_p (the
+ * rest); after it every bicg_* kernel returns at once, so the host may enqueue
+ * iterations ahead.  An iteration index outside its range (0..kmax for the
+ * slots and reduce_rr_rho, 1..kmax elsewhere) is SPMV_HIP_EINVAL. */
+int spmv_hip_bicg_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_bicg_ws** ws);
+int spmv_hip_bicg_ws_destroy(spmv_hip_bicg_ws* ws);
+int spmv_hip_bicg_ws_reset(spmv_hip_bicg_ws* ws, double rtol, void* stream);
+/* kmax the workspace was created with: its history holds kmax + 1 pairs */
+int spmv_hip_bicg_ws_capacity(const spmv_hip_bicg_ws* ws, int* kmax);
+/* device addresses of rv[k] and of the two pairs of k (all-reduce) */
+int spmv_hip_bicg_ws_rv(spmv_hip_bicg_ws* ws, int k, double** slot);
+int spmv_hip_bicg_ws_ts_tt(spmv_hip_bicg_ws* ws, int k, double** pair);
+int spmv_hip_bicg_ws_rr_rho(spmv_hip_bicg_ws* ws, int k, double** pair);
+int spmv_hip_bicg_ws_done_flag(spmv_hip_bicg_ws* ws, const int32_t** done);
+/* copies {done, kstop, status} (3 x int32) and the pairs {rr[k], rho[k]}, k =
+ * 0..kmax, to the host (async on stream).  host_rr_rho_len = doubles
+ * `host_rr_rho` can take: fewer than 2 * (kmax + 1) (bicg_ws_capacity) ->
+ * SPMV_HIP_EINVAL, nothing is copied.  Either destination may be NULL. */
+int spmv_hip_bicg_ws_read_async(spmv_hip_bicg_ws* ws,
+                                int32_t* host_done_kstop_status,
+                                double* host_rr_rho, size_t host_rr_rho_len,
+                                void* stream);
+/* start in one pass: r = rhat = p = b ; ph = dinv*b (dinv != NULL) ; x = 0 ;
+ * partials of b.b for both halves of the pair (then bicg_reduce_rr_rho(0)
+ * installs the pair 0).  b, dinv: any alignment. */
+int spmv_hip_bicg_init_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int64_t n,
+                           const double* b, const double* dinv, double* r,
+                           double* rhat, double* p, double* ph, double* x,
+                           void* stream);
+/* the two dot-product passes: partials of rhat.v ; of t.s and t.t */
+int spmv_hip_bicg_dot_rv_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
+                             int64_t n, const double* rhat, const double* v,
+                             void* stream);
+int spmv_hip_bicg_dot_ts_tt_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
+                                int64_t n, const double* t, const double* s,
+                                void* stream);
+/* update_s : s = r - alpha v ; sh = dinv*s           (breakdown 1 -> done)
+ * update_xr: x += alpha ph ; x += omega sh ; r = s - omega t ; partials of
+ *            r.r and rhat.r
+ * update_p : stop test, breakdown 2 (-> done) ; p = r + beta (p - omega v) ;
+ *            ph = dinv*p
+ * Every vector 16-byte aligned.  dinv == NULL (update_s, update_p) and sh ==
+ * NULL (update_xr) select the unpreconditioned kernels: no dinv stream, sh /
+ * ph are neither read nor written, and update_xr's `ph` is p, its sh is s. */
+int spmv_hip_bicg_update_s_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
+                               int64_t n, const double* r, const double* v,
+                               const double* dinv, double* s, double* sh,
+                               void* stream);
+int spmv_hip_bicg_update_xr_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
+                                int64_t n, const double* ph, const double* sh,
+                                const double* s, const double* t,
+                                const double* rhat, double* x, double* r,
+                                void* stream);
+int spmv_hip_bicg_update_p_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
+                               int64_t n, const double* r, const double* v,
+                               const double* dinv, double* p, double* ph,
+                               void* stream);
+/* single-workgroup reducers (local part; all-reduce the slot afterwards) */
+int spmv_hip_bicg_reduce_rv(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
+                            void* stream);
+int spmv_hip_bicg_reduce_ts_tt(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
+                               void* stream);
+int spmv_hip_bicg_reduce_rr_rho(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
+                                void* stream);
+/* consumer-side forms for ONE rank (see spmv_hip_cg_update_r_cs_f64): every
+ * workgroup adds the preceding producer's partials itself, in the reducers'
+ * order (the same bits), workgroup 0 stores rv[k] / the pair k.
+ *   update_s_cs : reduce_rv + update_s
+ *   update_xr_cs: reduce_ts_tt + update_xr
+ *   update_p_cs : reduce_rr_rho + update_p */
+int spmv_hip_bicg_update_s_cs_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws,
+                                  int k, int64_t n, const double* r,
+                                  const double* v, const double* dinv,
+                                  double* s, double* sh, void* stream);
+int spmv_hip_bicg_update_xr_cs_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws,
+                                   int k, int64_t n, const double* ph,
+                                   const double* sh, const double* s,
+                                   const double* t, const double* rhat,
+                                   double* x, double* r, void* stream);
+int spmv_hip_bicg_update_p_cs_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws,
+                                  int k, int64_t n, const double* r,
+                                  const double* v, const double* dinv,
+                                  double* p, double* ph, void* stream);
 
 /* ---- 3-D Poisson generator (not in the reference)
  * 7-point stencil on an n^3 grid, natural ordering, diag 6, off-diag -1.

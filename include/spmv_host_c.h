@@ -374,6 +374,30 @@ int spmvh_pcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
               spmvh_pcg_workspace* ws, int flags, double* spmv_ms_total,
               int* spmv_launches);
 
+/* ---- BiCGStab (spmv::bicgstab, host/cg.h; not in the reference) -------------
+ * spmvh_bicgstab: BiCGStab from x0 = 0 for a matrix that need not be
+ * symmetric.  dinv: NULL, or the inverse diagonal of a right preconditioner
+ * (device, rows doubles, finite and nonzero).  x must not overlap b or dinv.
+ * *num_its = the iterations completed; *status (may be NULL) = 0 (tolerance
+ * met or kmax reached), 1 (rhat.v == 0: the iteration wrote nothing) or 2
+ * (omega == 0 or rho == 0: x, r and the last residual norm are valid).
+ * rnorm_history (may be NULL): kmax + 1 entries, ||r_0|| .. ||r_k||.
+ * ws: a reusable spmv::BicgstabWorkspace (may be NULL).  flags: bit 0 ->
+ * CgOptions::time_spmv (*spmv_ms_total, *spmv_launches, both may be NULL; two
+ * SpMVs per iteration), bit 2 switches CgOptions::consumer_reductions off,
+ * bits 8-15 CgOptions::poll_every (0 = default). */
+typedef struct spmvh_bicgstab_workspace spmvh_bicgstab_workspace;
+int spmvh_bicgstab_workspace_create(spmvh_exec* exec,
+                                    spmvh_bicgstab_workspace** ws);
+int spmvh_bicgstab_workspace_destroy(spmvh_bicgstab_workspace* ws);
+int spmvh_bicgstab_workspace_reserve_timing(spmvh_bicgstab_workspace* ws,
+                                            int iterations);
+int spmvh_bicgstab(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                   const double* b, double* x, const double* dinv, int kmax,
+                   double rtol, int* num_its, int* status,
+                   double* rnorm_history, spmvh_bicgstab_workspace* ws,
+                   int flags, double* spmv_ms_total, int* spmv_launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,34 @@ _PROTOS = {
                                      C.c_int),
     "spmv_hip_pcg_update_xp_cs_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp,
                                        vp], C.c_int),
+    "spmv_hip_bicg_ws_create": ([vp, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_bicg_ws_destroy": ([vp], C.c_int),
+    "spmv_hip_bicg_ws_reset": ([vp, f64, vp], C.c_int),
+    "spmv_hip_bicg_ws_capacity": ([vp, P(C.c_int)], C.c_int),
+    "spmv_hip_bicg_ws_rv": ([vp, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_bicg_ws_ts_tt": ([vp, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_bicg_ws_rr_rho": ([vp, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_bicg_ws_done_flag": ([vp, P(vp)], C.c_int),
+    "spmv_hip_bicg_ws_read_async": ([vp, vp, vp, sz, vp], C.c_int),
+    "spmv_hip_bicg_init_f64": ([vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp],
+                               C.c_int),
+    "spmv_hip_bicg_dot_rv_f64": ([vp, vp, C.c_int, i64, vp, vp, vp], C.c_int),
+    "spmv_hip_bicg_dot_ts_tt_f64": ([vp, vp, C.c_int, i64, vp, vp, vp], C.c_int),
+    "spmv_hip_bicg_update_s_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp, vp,
+                                    vp], C.c_int),
+    "spmv_hip_bicg_update_xr_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp, vp,
+                                     vp, vp, vp], C.c_int),
+    "spmv_hip_bicg_update_p_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp, vp,
+                                    vp], C.c_int),
+    "spmv_hip_bicg_reduce_rv": ([vp, vp, C.c_int, vp], C.c_int),
+    "spmv_hip_bicg_reduce_ts_tt": ([vp, vp, C.c_int, vp], C.c_int),
+    "spmv_hip_bicg_reduce_rr_rho": ([vp, vp, C.c_int, vp], C.c_int),
+    "spmv_hip_bicg_update_s_cs_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp,
+                                       vp, vp], C.c_int),
+    "spmv_hip_bicg_update_xr_cs_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp,
+                                        vp, vp, vp, vp], C.c_int),
+    "spmv_hip_bicg_update_p_cs_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp,
+                                       vp, vp], C.c_int),
     "spmv_hip_csr_diagonal_f64": ([vp, i32, vp, vp, vp, vp, vp], C.c_int),
     "spmv_hip_csr_diagonal_f32": ([vp, i32, vp, vp, vp, vp, vp], C.c_int),
     "spmv_hip_jacobi_invert_f64": ([vp, i64, vp, vp, vp, vp], C.c_int),

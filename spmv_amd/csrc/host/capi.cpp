@@ -52,6 +52,10 @@ struct spmvh_pcg_workspace {
   std::shared_ptr<HipExecutor> exec; // keeps the executor alive
   std::unique_ptr<PcgWorkspace> ws;
 };
+struct spmvh_bicgstab_workspace {
+  std::shared_ptr<HipExecutor> exec; // keeps the executor alive
+  std::unique_ptr<BicgstabWorkspace> ws;
+};
 
 namespace
 {
@@ -1227,6 +1231,63 @@ int spmvh_pcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     *num_its = pcg(*comm->comm, *exec->hip, *A->A, b, x, dinv, kmax, rtol,
                    rnorm_history ? &hist : nullptr, &opt, &st,
                    ws ? ws->ws.get() : nullptr);
+    if (rnorm_history)
+      std::copy(hist.begin(), hist.end(), rnorm_history);
+    if (spmv_ms_total)
+      *spmv_ms_total = st.spmv_ms_total;
+    if (spmv_launches)
+      *spmv_launches = st.spmv_launches;
+  });
+}
+
+// ---- BiCGStab ---------------------------------------------------------------------------
+int spmvh_bicgstab_workspace_create(spmvh_exec* exec,
+                                    spmvh_bicgstab_workspace** ws)
+{
+  return guarded([&] {
+    require(exec && ws, "NULL argument");
+    auto w = std::make_unique<spmvh_bicgstab_workspace>();
+    w->exec = exec->hip;
+    w->ws.reset(new BicgstabWorkspace(*exec->hip));
+    *ws = w.release();
+  });
+}
+
+int spmvh_bicgstab_workspace_destroy(spmvh_bicgstab_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_bicgstab_workspace_reserve_timing(spmvh_bicgstab_workspace* ws,
+                                            int iterations)
+{
+  return guarded([&] {
+    require(ws, "NULL argument");
+    ws->ws->reserve_timing(iterations);
+  });
+}
+
+int spmvh_bicgstab(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                   const double* b, double* x, const double* dinv, int kmax,
+                   double rtol, int* num_its, int* status,
+                   double* rnorm_history, spmvh_bicgstab_workspace* ws,
+                   int flags, double* spmv_ms_total, int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && num_its, "NULL argument");
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    opt.consumer_reductions = (flags & 4) == 0; // bit 2 switches it off
+    if ((flags >> 8) & 0xff) // bits 8-15: CgOptions::poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    CgStats st;
+    int how = 0;
+    *num_its = bicgstab(*comm->comm, *exec->hip, *A->A, b, x, dinv, kmax, rtol,
+                        rnorm_history ? &hist : nullptr, &opt, &st,
+                        ws ? ws->ws.get() : nullptr, &how);
+    if (status)
+      *status = how;
     if (rnorm_history)
       std::copy(hist.begin(), hist.end(), rnorm_history);
     if (spmv_ms_total)

@@ -1069,4 +1069,323 @@ int pcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   return k_final;
 }
 
+// ---------------------------------------------------------------------------
+// bicgstab: see cg.h.  Per iteration (compute stream), PH / SH being ph / sh
+// with a dinv and p / s without:
+//     halo start of PH on the map's side stream ; v = A PH (Matrix::mult)
+//     one rank, consumer_reductions:            otherwise:
+//       dot_rv                                    dot_rv
+//       update_s_cs   (rv[k]; s, sh)              reduce_rv ; all-reduce of 1
+//                                                 update_s
+//     halo start of SH ; t = A SH
+//       dot_ts_tt                                 dot_ts_tt
+//       update_xr_cs  ({ts,tt}[k]; x; r;          reduce_ts_tt ; all-reduce of 2
+//                      r.r, rhat.r)               update_xr
+//       update_p_cs   ({rr,rho}[k]; stop; p, ph)  reduce_rr_rho ; all-reduce of 2
+//                                                 update_p
+// 2 SpMV + 5 (or 8) launches; beside the SpMVs 23 vector passes with a dinv
+// (dot_rv 2, update_s 5, dot_ts_tt 2, update_xr 8, update_p 6) and 18 without
+// (2, 3, 2, 7, 4), where cg() without defer_x streams 8.
+// ---------------------------------------------------------------------------
+BicgstabWorkspace::~BicgstabWorkspace() { release(); }
+
+void BicgstabWorkspace::release()
+{
+  try {
+    if (stream)
+      _exec.synchronize_stream(stream);
+    _exec.destroy_event(poll_event);
+    for (void* e : timing_ev)
+      _exec.destroy_event(e);
+    if (stream)
+      _exec.destroy_stream(stream);
+    spmv_hip_bicg_ws_destroy(ws);
+    for (double* q : {r, rhat, v, t, p, s, ph, sh, x, dinv})
+      _exec.free(q);
+    spmv_hip_host_free(_exec.context(), flags);
+  } catch (...) {
+  }
+  timing_ev.clear();
+  ws = nullptr;
+  r = rhat = v = t = p = s = ph = sh = x = dinv = nullptr;
+  flags = nullptr;
+  stream = poll_event = nullptr;
+  kmax_cap = -1;
+  m_cap = n_cap = h_cap = x_cap = dinv_cap = -1;
+}
+
+void BicgstabWorkspace::ensure(int64_t M, int64_t N_padded, int kmax,
+                               bool need_x, bool need_dinv, bool need_h)
+{
+  spmv_hip_ctx* ctx = _exec.context();
+  if (!stream) {
+    stream = _exec.create_stream();
+    poll_event = _exec.create_event();
+    void* mem = nullptr;
+    throw_on_error(spmv_hip_host_alloc(ctx, 4 * sizeof(int32_t), &mem),
+                   "spmv_hip_host_alloc");
+    flags = static_cast<int32_t*>(mem);
+  }
+  if (kmax > kmax_cap) {
+    // (an earlier solve on this workspace has been synchronised: nothing
+    // still reads the old scalars)
+    spmv_hip_bicg_ws_destroy(ws);
+    ws = nullptr;
+    kmax_cap = -1;
+    throw_on_error(spmv_hip_bicg_ws_create(ctx, kmax, &ws),
+                   "spmv_hip_bicg_ws_create");
+    kmax_cap = kmax;
+  }
+  // frees the vectors of one capacity, then allocates them at the new one;
+  // the capacity is -1 while they are gone
+  auto regrow = [&](int64_t& cap, int64_t want,
+                    std::initializer_list<double**> vecs) {
+    if (want <= cap)
+      return;
+    for (double** q : vecs) {
+      _exec.free(*q);
+      *q = nullptr;
+    }
+    cap = -1;
+    for (double** q : vecs)
+      *q = _exec.alloc<double>(want);
+    cap = want;
+  };
+  regrow(m_cap, M, {&r, &rhat, &v, &t});
+  regrow(n_cap, N_padded, {&p, &s});
+  if (need_h)
+    regrow(h_cap, N_padded, {&ph, &sh});
+  if (need_x)
+    regrow(x_cap, M, {&x});
+  if (need_dinv)
+    regrow(dinv_cap, M, {&dinv});
+}
+
+void BicgstabWorkspace::reserve_timing(int iterations)
+{
+  while (timing_ev.size() < 4 * (size_t)(iterations < 0 ? 0 : iterations))
+    timing_ev.push_back(_exec.create_event(true));
+}
+
+int bicgstab(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+             const double* b, double* x, const double* dinv, int kmax,
+             double rtol, std::vector<double>* rnorm_history,
+             const CgOptions* options, CgStats* stats,
+             BicgstabWorkspace* workspace, int* status)
+{
+  std::shared_ptr<const L2GMap> col_l2g = A.col_map();
+  std::shared_ptr<const L2GMap> row_l2g = A.row_map();
+  if (row_l2g->num_ghosts() > 0)
+    throw std::runtime_error(
+        "spmv::bicgstab - Error: A.row_map() has ghost entries");
+  if (kmax < 0)
+    throw std::runtime_error("spmv::bicgstab - Error: kmax < 0");
+  const CgOptions opt = options ? *options : CgOptions();
+  const int poll_every = opt.poll_every < 1 ? 1 : opt.poll_every;
+
+  const int64_t M = row_l2g->local_size();
+  const int64_t N_padded = col_l2g->local_size() + col_l2g->num_ghosts();
+  spmv_hip_ctx* ctx = exec.context();
+
+  { // x is the iterate from the first kernel on: it cannot share b or dinv
+    const uintptr_t xb = reinterpret_cast<uintptr_t>(x);
+    const uintptr_t bytes = (uintptr_t)M * sizeof(double);
+    auto overlaps = [&](const double* q) {
+      const uintptr_t qb = reinterpret_cast<uintptr_t>(q);
+      return M > 0 && xb < qb + bytes && qb < xb + bytes;
+    };
+    if (overlaps(b))
+      throw std::runtime_error("bicgstab: x overlaps b (x is updated in place)");
+    if (dinv && overlaps(dinv))
+      throw std::runtime_error(
+          "bicgstab: x overlaps dinv (x is updated in place)");
+  }
+  BicgstabWorkspace own(exec);
+  BicgstabWorkspace& w = workspace ? *workspace : own;
+  const bool pre = dinv != nullptr;
+  const bool x_aligned = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+  const bool dinv_aligned = (reinterpret_cast<uintptr_t>(dinv) & 15u) == 0;
+  w.ensure(M, N_padded, kmax, !x_aligned, !dinv_aligned, pre);
+  if (opt.time_spmv)
+    w.reserve_timing(kmax);
+
+  StreamGuard guard{exec, exec.get_stream()};
+  { // order after whatever the caller enqueued (b, dinv may still be in flight)
+    void* ev = exec.create_event();
+    exec.record_event(ev, guard.prev);
+    exec.stream_wait_event(w.stream, ev);
+    exec.destroy_event(ev);
+  }
+  exec.set_stream(w.stream); // every launch below goes to this stream
+
+  throw_on_error(spmv_hip_bicg_ws_reset(w.ws, rtol, nullptr),
+                 "spmv_hip_bicg_ws_reset");
+
+  double* const xi = x_aligned ? x : w.x;
+  const double* di = dinv;
+  if (pre && !dinv_aligned) { // the streaming kernels load 16 bytes at a time
+    exec.copy<double>(w.dinv, dinv, M);
+    di = w.dinv;
+  }
+  // what the two SpMVs read (padded); without a dinv p and s themselves
+  double* const PH = pre ? w.ph : w.p;
+  double* const SH = pre ? w.sh : w.s;
+  // their ghost tails are defined here instead of relying on fresh pages
+  if (N_padded > M) {
+    exec.memset<double>(PH + M, 0, N_padded - M);
+    exec.memset<double>(SH + M, 0, N_padded - M);
+  }
+  // r = rhat = p = b, ph = dinv*b, x0 = 0, partials of b.b: one pass
+  throw_on_error(spmv_hip_bicg_init_f64(ctx, w.ws, M, b, di, w.r, w.rhat, w.p,
+                                        pre ? w.ph : nullptr, xi, nullptr),
+                 "spmv_hip_bicg_init_f64");
+  w.flags[0] = 0;
+  w.flags[1] = -1;
+  w.flags[2] = 0;
+
+  auto slot = [&](int (*get)(spmv_hip_bicg_ws*, int, double**), int k,
+                  const char* what) {
+    double* q = nullptr;
+    throw_on_error(get(w.ws, k, &q), what);
+    return q;
+  };
+
+  // {rr0, rho0}: one all-reduce of 2 doubles
+  throw_on_error(spmv_hip_bicg_reduce_rr_rho(ctx, w.ws, 0, nullptr),
+                 "spmv_hip_bicg_reduce_rr_rho");
+  comm.reduce_sum(slot(spmv_hip_bicg_ws_rr_rho, 0, "spmv_hip_bicg_ws_rr_rho"),
+                  2, w.stream);
+
+  const bool consume = opt.consumer_reductions && comm.size() == 1;
+  std::vector<void*>& timing_ev = w.timing_ev;
+  // y = A q between two events when the SpMVs are timed
+  auto mult = [&](double* q, double* y, size_t ev) {
+    col_l2g->update(q); // starts on the side stream
+    if (opt.time_spmv)
+      exec.record_event(timing_ev[ev], w.stream);
+    A.mult(q, y);
+    if (opt.time_spmv)
+      exec.record_event(timing_ev[ev + 1], w.stream);
+  };
+  int k = 0;
+  bool stopped = false;
+  bool poll_pending = false;
+  while (k < kmax && !stopped) {
+    ++k;
+    mult(PH, w.v, 4 * (size_t)(k - 1));
+    throw_on_error(spmv_hip_bicg_dot_rv_f64(ctx, w.ws, k, M, w.rhat, w.v,
+                                            nullptr),
+                   "spmv_hip_bicg_dot_rv_f64");
+    if (consume) {
+      // one rank: the update kernels add the partials themselves
+      throw_on_error(spmv_hip_bicg_update_s_cs_f64(ctx, w.ws, k, M, w.r, w.v,
+                                                   di, w.s,
+                                                   pre ? w.sh : nullptr,
+                                                   nullptr),
+                     "spmv_hip_bicg_update_s_cs_f64");
+    } else {
+      throw_on_error(spmv_hip_bicg_reduce_rv(ctx, w.ws, k, nullptr),
+                     "spmv_hip_bicg_reduce_rv");
+      comm.reduce_sum(slot(spmv_hip_bicg_ws_rv, k, "spmv_hip_bicg_ws_rv"), 1,
+                      w.stream);
+      throw_on_error(spmv_hip_bicg_update_s_f64(ctx, w.ws, k, M, w.r, w.v, di,
+                                                w.s, pre ? w.sh : nullptr,
+                                                nullptr),
+                     "spmv_hip_bicg_update_s_f64");
+    }
+    mult(SH, w.t, 4 * (size_t)(k - 1) + 2);
+    throw_on_error(spmv_hip_bicg_dot_ts_tt_f64(ctx, w.ws, k, M, w.t, w.s,
+                                               nullptr),
+                   "spmv_hip_bicg_dot_ts_tt_f64");
+    if (consume) {
+      throw_on_error(spmv_hip_bicg_update_xr_cs_f64(ctx, w.ws, k, M, PH,
+                                                    pre ? w.sh : nullptr, w.s,
+                                                    w.t, w.rhat, xi, w.r,
+                                                    nullptr),
+                     "spmv_hip_bicg_update_xr_cs_f64");
+      throw_on_error(spmv_hip_bicg_update_p_cs_f64(ctx, w.ws, k, M, w.r, w.v,
+                                                   di, w.p,
+                                                   pre ? w.ph : nullptr,
+                                                   nullptr),
+                     "spmv_hip_bicg_update_p_cs_f64");
+    } else {
+      throw_on_error(spmv_hip_bicg_reduce_ts_tt(ctx, w.ws, k, nullptr),
+                     "spmv_hip_bicg_reduce_ts_tt");
+      comm.reduce_sum(slot(spmv_hip_bicg_ws_ts_tt, k, "spmv_hip_bicg_ws_ts_tt"),
+                      2, w.stream); // ts[k] and tt[k] at once
+      throw_on_error(spmv_hip_bicg_update_xr_f64(ctx, w.ws, k, M, PH,
+                                                 pre ? w.sh : nullptr, w.s, w.t,
+                                                 w.rhat, xi, w.r, nullptr),
+                     "spmv_hip_bicg_update_xr_f64");
+      throw_on_error(spmv_hip_bicg_reduce_rr_rho(ctx, w.ws, k, nullptr),
+                     "spmv_hip_bicg_reduce_rr_rho");
+      comm.reduce_sum(slot(spmv_hip_bicg_ws_rr_rho, k,
+                           "spmv_hip_bicg_ws_rr_rho"),
+                      2, w.stream); // rr[k] and rho[k] at once
+      throw_on_error(spmv_hip_bicg_update_p_f64(ctx, w.ws, k, M, w.r, w.v, di,
+                                                w.p, pre ? w.ph : nullptr,
+                                                nullptr),
+                     "spmv_hip_bicg_update_p_f64");
+    }
+
+    if (k % poll_every == 0 && k < kmax) {
+      // lagging look at the flag, as in cg()
+      if (poll_pending) {
+        exec.synchronize_event(w.poll_event);
+        stopped = w.flags[0] != 0;
+      }
+      if (!stopped) {
+        throw_on_error(spmv_hip_bicg_ws_read_async(w.ws, w.flags, nullptr, 0,
+                                                   nullptr),
+                       "spmv_hip_bicg_ws_read_async");
+        exec.record_event(w.poll_event, w.stream);
+        poll_pending = true;
+      }
+    }
+  }
+
+  // final state: {done, kstop, status} and the history of pairs (it has the
+  // WORKSPACE's capacity; the C ABI refuses a shorter destination)
+  int cap = 0;
+  throw_on_error(spmv_hip_bicg_ws_capacity(w.ws, &cap),
+                 "spmv_hip_bicg_ws_capacity");
+  std::vector<double> rrho(2 * ((size_t)std::max(kmax, cap) + 1), 0.0);
+  throw_on_error(spmv_hip_bicg_ws_read_async(w.ws, w.flags, rrho.data(),
+                                             rrho.size(), nullptr),
+                 "spmv_hip_bicg_ws_read_async");
+  if (xi != x)
+    exec.copy<double>(x, xi, M);
+  exec.synchronize_stream(w.stream);
+
+  if (stats) {
+    *stats = CgStats();
+    for (size_t i = 0; opt.time_spmv && i + 1 < 4 * (size_t)k; i += 2) {
+      float ms = 0.f;
+      throw_on_error(spmv_hip_event_elapsed_ms(ctx, timing_ev[i],
+                                               timing_ev[i + 1], &ms),
+                     "spmv_hip_event_elapsed_ms");
+      stats->spmv_ms_total += ms;
+      ++stats->spmv_launches;
+    }
+  }
+
+  // The kernel that takes a decision raises `done` itself, so the flag is
+  // exact when the loop ends: not raised means k iterations ran to the end.
+  int k_final = k, st = 0;
+  if (w.flags[0] != 0) {
+    k_final = w.flags[1];
+    st = w.flags[2];
+  } else if (rrho[0] == 0.0) {
+    k_final = 0; // (kmax == 0: no kernel ran to say so)
+  }
+  if (status)
+    *status = st;
+  if (rnorm_history) {
+    rnorm_history->resize(k_final + 1);
+    for (int j = 0; j <= k_final; ++j)
+      (*rnorm_history)[j] = std::sqrt(rrho[2 * (size_t)j]);
+  }
+  return k_final;
+}
+
 } // namespace spmv

@@ -12,6 +12,7 @@
 struct spmv_hip_cg_ws;
 struct spmv_hip_cgb_ws;
 struct spmv_hip_pcg_ws;
+struct spmv_hip_bicg_ws;
 
 namespace spmv
 {
@@ -266,5 +267,94 @@ int pcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
         std::vector<double>* rnorm_history = nullptr,
         const CgOptions* options = nullptr, CgStats* stats = nullptr,
         PcgWorkspace* workspace = nullptr);
+
+// Work vectors + device scalars of bicgstab(), kept across calls like
+// PcgWorkspace; it regrows itself when a call needs more rows or more
+// iterations.
+class BicgstabWorkspace
+{
+public:
+  explicit BicgstabWorkspace(HipExecutor& exec) : _exec(exec) {}
+  ~BicgstabWorkspace();
+  BicgstabWorkspace(const BicgstabWorkspace&) = delete;
+  BicgstabWorkspace& operator=(const BicgstabWorkspace&) = delete;
+
+  // ---- internal to bicgstab() ----
+  // need_x / need_dinv: the caller's x / dinv is not 16-byte aligned and lives
+  // in the workspace's copy during the solve; need_h: a dinv was given, ph and
+  // sh are vectors of their own
+  void ensure(int64_t M, int64_t N_padded, int kmax, bool need_x, bool need_dinv,
+              bool need_h);
+  void reserve_timing(int iterations);
+  void release();
+
+  HipExecutor& _exec;
+  spmv_hip_bicg_ws* ws = nullptr;
+  int kmax_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, h_cap = -1, x_cap = -1, dinv_cap = -1;
+  double *r = nullptr, *rhat = nullptr, *v = nullptr, *t = nullptr; // m_cap
+  // n_cap: padded -- without a dinv p and s are what the SpMVs read; the
+  // ghost tails are zeroed by every solve that reads them
+  double *p = nullptr, *s = nullptr;
+  double *ph = nullptr, *sh = nullptr; // h_cap: padded, dinv*p and dinv*s
+  double* x = nullptr;      // x_cap: the iterate when the caller's x is unaligned
+  double* dinv = nullptr;   // dinv_cap: the copy of an unaligned dinv
+  int32_t* flags = nullptr; // pinned {done, kstop, status}
+  void* stream = nullptr;   // compute stream of the solve
+  void* poll_event = nullptr;
+  std::vector<void*> timing_ev; // CgOptions::time_spmv: 4 events per iteration
+};
+
+// BiCGStab from x0 = 0 for a matrix that need not be symmetric, with an
+// optional diagonal RIGHT preconditioner.  `dinv` is nullptr or any finite
+// nonzero DEVICE vector of A.row_map()->local_size() doubles, the inverse of
+// the preconditioner's diagonal (Jacobi's: Matrix::diagonal + jacobi_inverse).
+// Only Matrix::mult is used: every plan form, both storages and every halo
+// model serve.  With `.` the global dot product:
+//
+//   r0 = b; rhat = b; p1 = b; rho[0] = rr[0] = b.b
+//   for k = 1..kmax:
+//     ph = dinv*p_k (p_k itself if dinv == nullptr); v = A ph; rv = rhat.v
+//     rv == 0: breakdown 1 -- stop, k-1 iterations completed, x untouched by
+//              this iteration
+//     alpha = rho[k-1] / rv; s = r - alpha*v; sh = dinv*s (or s)
+//     t = A sh; ts = t.s; tt = t.t; omega = (tt == 0) ? 0 : ts / tt
+//     x += alpha*ph; x += omega*sh        (two roundings each, in this order)
+//     r = s - omega*t; rr[k] = r.r; rho[k] = rhat.r
+//     if sqrt(rr[k]) / sqrt(rr[0]) < rtol: stop (x and r updated, p not)
+//     omega == 0 or rho[k] == 0: breakdown 2 -- stop after this iteration
+//              (x, r and rr[k] are valid)
+//     beta = (rho[k]/rho[k-1]) * (alpha/omega); p_(k+1) = r + beta*(p_k - omega*v)
+//
+// Products and sums are separate roundings.  There is no half-step exit on s,
+// so an iteration has three reductions: rv, the pair {ts, tt}, the pair
+// {rr, rho}; with several ranks each pair is ONE all-reduce of 2 doubles.  The
+// stopping test is cg()'s; rnorm_history receives ||r_0||, ..., ||r_k||.  A
+// system with r_0 . r_0 == 0 stops at k = 0 with x = 0 (the rule of pcg).
+// Returns k, the number of iterations completed.  `status` (optional) receives
+// 0 (the tolerance was met, or kmax was reached), 1 or 2 (the breakdowns
+// above).  After a breakdown x is the last finite iterate: the quotient that
+// cannot be formed never is, so no NaN of its making reaches x, r or the
+// history.
+//
+// As in pcg(): scalars stay on the device, reductions are two-stage and
+// deterministic, the decision to stop is taken on the device and the host only
+// looks at a pinned flag every `poll_every` iterations; `x` IS the iterate and
+// must not overlap `b` or `dinv` (std::runtime_error, "overlaps"); an `x` (or a
+// `dinv`) that is not 16-byte aligned goes through the workspace's copy, x
+// with one copy at the end; kmax < 0 throws; the executor's stream is
+// restored on every exit path.  The halo update of ph / sh precedes each mult.
+//
+// options: poll_every, time_spmv (BOTH Matrix::mult calls of an iteration are
+//          bracketed: CgStats::spmv_launches is 2 per iteration) and
+//          consumer_reductions apply (one rank with consumer_reductions: 2 SpMV
+//          + 5 launches per iteration, else 2 SpMV + 8 and 3 all-reduces);
+//          defer_x and mixed are IGNORED: x is updated in every iteration, in
+//          fp64.
+int bicgstab(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+             const double* b, double* x, const double* dinv, int kmax,
+             double rtol, std::vector<double>* rnorm_history = nullptr,
+             const CgOptions* options = nullptr, CgStats* stats = nullptr,
+             BicgstabWorkspace* workspace = nullptr, int* status = nullptr);
 
 } // namespace spmv

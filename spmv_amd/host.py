@@ -137,6 +137,11 @@ _PROTOS = {
     "spmvh_pcg_workspace_reserve_timing": [vp, C.c_int],
     "spmvh_pcg": [vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int), vp, vp,
                   C.c_int, PTR(f64), PTR(C.c_int)],
+    "spmvh_bicgstab_workspace_create": [vp, PTR(vp)],
+    "spmvh_bicgstab_workspace_destroy": [vp],
+    "spmvh_bicgstab_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_bicgstab": [vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int),
+                       PTR(C.c_int), vp, vp, C.c_int, PTR(f64), PTR(C.c_int)],
 }
 for _n, _a in _PROTOS.items():
     _f = getattr(lib, _n)
@@ -860,6 +865,46 @@ def pcg(comm, exec_, A, b_ptr, x_ptr, dinv_ptr, kmax, rtol, workspace=None,
     if stats is not None:
         stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
     return k.value, hist[:k.value + 1]
+
+
+class BicgstabWorkspace:
+    """spmv::BicgstabWorkspace: work vectors kept across bicgstab() calls."""
+
+    def __init__(self, exec_):
+        h = vp()
+        call("spmvh_bicgstab_workspace_create", exec_.h, C.byref(h))
+        self.h = h
+
+    def reserve_timing(self, iterations):
+        call("spmvh_bicgstab_workspace_reserve_timing", self.h, int(iterations))
+
+    def close(self):
+        if self.h:
+            call("spmvh_bicgstab_workspace_destroy", self.h)
+            self.h = None
+
+
+def bicgstab(comm, exec_, A, b_ptr, x_ptr, dinv_ptr, kmax, rtol, ws=None,
+             time_spmv=False, consumer_reductions=True, poll_every=0,
+             stats=None):
+    """spmv::bicgstab: BiCGStab from x0 = 0 for a matrix that need not be
+    symmetric -> (k, rnorm_history, status).  dinv_ptr: None, or the inverse
+    diagonal of a right preconditioner (any finite nonzero device vector).
+    status: 0 converged or kmax reached, 1 / 2 the breakdowns (host/cg.h).
+    stats (optional dict) receives spmv_ms_total and spmv_launches of a
+    time_spmv solve (two SpMVs per iteration)."""
+    kmax = int(kmax)
+    k, n, status = C.c_int(), C.c_int(), C.c_int()
+    ms = f64()
+    hist = np.zeros(max(kmax, 0) + 1)
+    call("spmvh_bicgstab", comm.h, exec_.h, A.h, b_ptr, x_ptr, dinv_ptr or None,
+         kmax, float(rtol), C.byref(k), C.byref(status), _np_ptr(hist),
+         ws.h if ws else None,
+         int(bool(time_spmv)) | (0 if consumer_reductions else 4)
+         | ((int(poll_every) & 0xff) << 8), C.byref(ms), C.byref(n))
+    if stats is not None:
+        stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, hist[:k.value + 1], status.value
 
 
 def host_executor_rejects_compute():
