@@ -887,6 +887,55 @@ int spmv_hip_csr_diagonal_f32(spmv_hip_ctx* ctx, int32_t num_rows,
 int spmv_hip_jacobi_invert_f64(spmv_hip_ctx* ctx, int64_t n, const double* d,
                                double* dinv, int32_t* bad_count, void* stream);
 
+/* ---- Chebyshev polynomial preconditioner (spmv::chebyshev_apply, pcg_chebyshev) --
+ * z = q(dinv*A) dinv r: the `degree`-step Chebyshev iteration for A z = r from
+ * z = 0.  a_j, b_j are the host's chebyshev_coefficients (host/cg.h), passed as
+ * kernel arguments; `dinv` is the inverse of a diagonal or NULL (no multiply, no
+ * dinv stream).  Elementwise, every product and sum a rounding of its own:
+ *   step 0       d = b_0 * (dinv*r) ;                  z = d
+ *   step j >= 1  w = A z (the caller's SpMV) ;
+ *                d = a_j*d + b_j*(dinv*(r - w)) ;      z = z + d
+ * The LAST step does not write d.  Every vector 16-byte aligned unless said.
+ *
+ * cheb_apply0: step 0 on a stored r; d == NULL: it is the last step (degree 1).
+ * cheb_step  : step j >= 1 (`last` != 0: the last one).  ws == NULL: the plain
+ *              step of chebyshev_apply.  With the workspace of a pcg_chebyshev
+ *              solve it returns at once after `done`, and the last step leaves
+ *              the partials of r.z (the new z) for pcg_reduce_rz_rr.
+ *
+ * pcg_chebyshev runs on a spmv_hip_pcg_ws and on the reducers of pcg
+ * (pcg_reduce_pAp, _pAp2, pcg_reduce_rz_rr), with z = M(r) STORED:
+ * cheb_init    : r = b ; x = 0 ; partials of r.r ; step 0 (b, dinv: any
+ *                alignment).  d == NULL (degree 1): partials of r.z too.
+ * cheb_update_r: r -= alpha Ap, alpha = rz[k-1] / pAp[k] ; partials of r.r ;
+ *                step 0 on the new r.  d == NULL (degree 1): partials of r.z too.
+ * cheb_update_xp: x += alpha p ; stop test of pcg_update_xp ; p = beta p + z.
+ * k outside 1..kmax is SPMV_HIP_EINVAL.
+ * cheb_scale   : out = dinv * (in / s), in / s when dinv == NULL (any alignment;
+ *                `in` and `out` may be the same vector): setup work of
+ *                lambda_max_estimate. */
+int spmv_hip_cheb_scale_f64(spmv_hip_ctx* ctx, int64_t n, double s,
+                            const double* dinv, const double* in, double* out,
+                            void* stream);
+int spmv_hip_cheb_apply0_f64(spmv_hip_ctx* ctx, int64_t n, double b0,
+                             const double* r, const double* dinv, double* d,
+                             double* z, void* stream);
+int spmv_hip_cheb_step_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
+                           double a, double b, int last, const double* w,
+                           const double* r, const double* dinv, double* d,
+                           double* z, void* stream);
+int spmv_hip_cheb_init_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
+                           double b0, const double* b, const double* dinv,
+                           double* r, double* x, double* d, double* z,
+                           void* stream);
+int spmv_hip_cheb_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                               int64_t n, double b0, const double* Ap,
+                               const double* dinv, double* r, double* d,
+                               double* z, void* stream);
+int spmv_hip_cheb_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                                int64_t n, const double* z, double* x, double* p,
+                                void* stream);
+
 /* ---- BiCGStab with an optional diagonal right preconditioner (spmv::bicgstab) ---
  * For nonsymmetric systems.  `dinv` is the inverse of the preconditioner's
  * diagonal or NULL; ph = dinv*p, sh = dinv*s (elementwise), p and s themselves

@@ -374,6 +374,44 @@ int spmvh_pcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
               spmvh_pcg_workspace* ws, int flags, double* spmv_ms_total,
               int* spmv_launches);
 
+/* ---- Chebyshev polynomial preconditioner (host/cg.h; not in the reference) ---
+ * spmvh_chebyshev_coefficients: spmv::chebyshev_coefficients -- a[], b[] (host,
+ * `degree` doubles each) of the Chebyshev iteration on [lmin, lmax]; an error
+ * whose text says "degree" (outside 1..16) or "bounds" (not finite, or not
+ * 0 < lmin < lmax).  Touches no device.
+ * spmvh_chebyshev_apply: spmv::chebyshev_apply -- z = q(dinv*A) dinv r (device,
+ * rows doubles each, any alignment, not overlapping); dinv may be NULL; ws may
+ * be NULL (then the call waits for its own work vectors).
+ * spmvh_pcg_chebyshev: spmv::pcg_chebyshev -- CG from x0 = 0 with that
+ * preconditioner; arguments as spmvh_pcg plus degree, lmin, lmax; dinv may be
+ * NULL.  flags: bit 0 CgOptions::time_spmv (`degree` intervals per iteration),
+ * bits 8-15 CgOptions::poll_every (0 = default); consumer_reductions does not
+ * apply.  spmvh_chebyshev_workspace_reserve_timing counts SpMVs (iterations *
+ * degree).
+ * spmvh_lambda_max_estimate: spmv::lambda_max_estimate -- `steps` power
+ * iterations on dinv*A from v0 (device, rows doubles, unchanged); dinv may be
+ * NULL; an error whose text says "steps" (< 1) or "v0" (v0.v0 == 0). */
+typedef struct spmvh_chebyshev_workspace spmvh_chebyshev_workspace;
+int spmvh_chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
+                                 double* b);
+int spmvh_chebyshev_workspace_create(spmvh_exec* exec,
+                                     spmvh_chebyshev_workspace** ws);
+int spmvh_chebyshev_workspace_destroy(spmvh_chebyshev_workspace* ws);
+int spmvh_chebyshev_workspace_reserve_timing(spmvh_chebyshev_workspace* ws,
+                                             int spmvs);
+int spmvh_chebyshev_apply(spmvh_exec* exec, spmvh_matrix* A, const double* r,
+                          double* z, const double* dinv, int degree, double lmin,
+                          double lmax, spmvh_chebyshev_workspace* ws);
+int spmvh_pcg_chebyshev(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                        const double* b, double* x, const double* dinv,
+                        int degree, double lmin, double lmax, int kmax,
+                        double rtol, int* num_its, double* rnorm_history,
+                        spmvh_chebyshev_workspace* ws, int flags,
+                        double* spmv_ms_total, int* spmv_launches);
+int spmvh_lambda_max_estimate(spmvh_comm* comm, spmvh_exec* exec,
+                              spmvh_matrix* A, const double* dinv,
+                              const double* v0, int steps, double* lambda);
+
 /* ---- BiCGStab (spmv::bicgstab, host/cg.h; not in the reference) -------------
  * spmvh_bicgstab: BiCGStab from x0 = 0 for a matrix that need not be
  * symmetric.  dinv: NULL, or the inverse diagonal of a right preconditioner

@@ -187,6 +187,16 @@ _PROTOS = {
                                      C.c_int),
     "spmv_hip_pcg_update_xp_cs_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp,
                                        vp], C.c_int),
+    "spmv_hip_cheb_scale_f64": ([vp, i64, f64, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_cheb_apply0_f64": ([vp, i64, f64, vp, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_cheb_step_f64": ([vp, vp, i64, f64, f64, C.c_int, vp, vp, vp, vp,
+                                vp, vp], C.c_int),
+    "spmv_hip_cheb_init_f64": ([vp, vp, i64, f64, vp, vp, vp, vp, vp, vp, vp],
+                               C.c_int),
+    "spmv_hip_cheb_update_r_f64": ([vp, vp, C.c_int, i64, f64, vp, vp, vp, vp,
+                                    vp, vp], C.c_int),
+    "spmv_hip_cheb_update_xp_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp],
+                                    C.c_int),
     "spmv_hip_bicg_ws_create": ([vp, C.c_int, P(vp)], C.c_int),
     "spmv_hip_bicg_ws_destroy": ([vp], C.c_int),
     "spmv_hip_bicg_ws_reset": ([vp, f64, vp], C.c_int),

@@ -31,26 +31,10 @@
 // Also here, as setup work of the Jacobi preconditioner: the diagonal of a CSR
 // block (one thread per row) and the checked inverse of a diagonal.
 #include "common.h"
+#include "pcg_ws.h"
 
 #include <cmath>
 #include <new>
-
-struct PcgScalars {
-  double rtol;
-  int32_t done;
-  int32_t kstop;
-};
-
-struct spmv_hip_pcg_ws {
-  spmv_hip_ctx* ctx = nullptr;
-  int kmax = 0;
-  double* zr = nullptr;          // [kmax + 1][2]: {rz[k], rr[k]}
-  double* pAp = nullptr;         // kmax + 1
-  double* partials = nullptr;    // p.Ap, ctx->dot_blocks
-  double* partials_rz = nullptr; // r.z,  ctx->dot_blocks
-  double* partials_rr = nullptr; // r.r,  ctx->dot_blocks
-  PcgScalars* sc = nullptr;
-};
 
 namespace
 {

@@ -52,6 +52,10 @@ struct spmvh_pcg_workspace {
   std::shared_ptr<HipExecutor> exec; // keeps the executor alive
   std::unique_ptr<PcgWorkspace> ws;
 };
+struct spmvh_chebyshev_workspace {
+  std::shared_ptr<HipExecutor> exec; // keeps the executor alive
+  std::unique_ptr<ChebyshevWorkspace> ws;
+};
 struct spmvh_bicgstab_workspace {
   std::shared_ptr<HipExecutor> exec; // keeps the executor alive
   std::unique_ptr<BicgstabWorkspace> ws;
@@ -1237,6 +1241,89 @@ int spmvh_pcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
       *spmv_ms_total = st.spmv_ms_total;
     if (spmv_launches)
       *spmv_launches = st.spmv_launches;
+  });
+}
+
+// ---- Chebyshev polynomial preconditioner ------------------------------------------------
+int spmvh_chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
+                                 double* b)
+{
+  return guarded([&] { chebyshev_coefficients(degree, lmin, lmax, a, b); });
+}
+
+int spmvh_chebyshev_workspace_create(spmvh_exec* exec,
+                                     spmvh_chebyshev_workspace** ws)
+{
+  return guarded([&] {
+    require(exec && ws, "NULL argument");
+    auto w = std::make_unique<spmvh_chebyshev_workspace>();
+    w->exec = exec->hip;
+    w->ws.reset(new ChebyshevWorkspace(*exec->hip));
+    *ws = w.release();
+  });
+}
+
+int spmvh_chebyshev_workspace_destroy(spmvh_chebyshev_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_chebyshev_workspace_reserve_timing(spmvh_chebyshev_workspace* ws,
+                                             int spmvs)
+{
+  return guarded([&] {
+    require(ws, "NULL argument");
+    ws->ws->reserve_timing(spmvs);
+  });
+}
+
+int spmvh_chebyshev_apply(spmvh_exec* exec, spmvh_matrix* A, const double* r,
+                          double* z, const double* dinv, int degree, double lmin,
+                          double lmax, spmvh_chebyshev_workspace* ws)
+{
+  return guarded([&] {
+    require(exec && A && r && z, "NULL argument");
+    chebyshev_apply(*exec->hip, *A->A, r, z, dinv, degree, lmin, lmax,
+                    ws ? ws->ws.get() : nullptr);
+  });
+}
+
+int spmvh_pcg_chebyshev(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                        const double* b, double* x, const double* dinv,
+                        int degree, double lmin, double lmax, int kmax,
+                        double rtol, int* num_its, double* rnorm_history,
+                        spmvh_chebyshev_workspace* ws, int flags,
+                        double* spmv_ms_total, int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && num_its, "NULL argument");
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff) // bits 8-15: CgOptions::poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    CgStats st;
+    *num_its = pcg_chebyshev(*comm->comm, *exec->hip, *A->A, b, x, dinv, degree,
+                             lmin, lmax, kmax, rtol,
+                             rnorm_history ? &hist : nullptr, &opt, &st,
+                             ws ? ws->ws.get() : nullptr);
+    if (rnorm_history)
+      std::copy(hist.begin(), hist.end(), rnorm_history);
+    if (spmv_ms_total)
+      *spmv_ms_total = st.spmv_ms_total;
+    if (spmv_launches)
+      *spmv_launches = st.spmv_launches;
+  });
+}
+
+int spmvh_lambda_max_estimate(spmvh_comm* comm, spmvh_exec* exec,
+                              spmvh_matrix* A, const double* dinv,
+                              const double* v0, int steps, double* lambda)
+{
+  return guarded([&] {
+    require(comm && exec && A && v0 && lambda, "NULL argument");
+    *lambda = lambda_max_estimate(*comm->comm, *exec->hip, *A->A, dinv, v0,
+                                  steps);
   });
 }
 

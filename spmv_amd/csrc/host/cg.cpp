@@ -20,7 +20,10 @@
 
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 #include <stdexcept>
+#include <string>
+#include <utility>
 
 #include "spmv_hip.h"
 
@@ -1067,6 +1070,532 @@ int pcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
       (*rnorm_history)[j] = std::sqrt(rr_at(j));
   }
   return k_final;
+}
+
+// ---------------------------------------------------------------------------
+// Chebyshev polynomial preconditioner: see cg.h.  pcg_chebyshev per iteration
+// (compute stream), on the scalars and reducers of pcg():
+//     halo start of p ; Ap = A p (+ fused p.Ap share)
+//     reduce_pAp ; all-reduce of 1
+//     cheb_update_r   (r ; partials of r.r ; step 0 of M: d, z)
+//     degree - 1 times:  halo start of z ; w = A z ; cheb_step
+//                        (the last one: partials of r.z, no d)
+//     reduce_rz_rr ; all-reduce of 2
+//     cheb_update_xp  (x ; stop test ; p)
+// degree SpMVs + degree + 1 streaming launches + 2 reducers; beside the SpMVs
+// 7 (degree - 1) + 11 vector passes with a dinv for degree >= 2 (update_r: Ap,
+// r, dinv in, r, d, z out; a step: w, r, dinv, d, z in, d, z out, the last one
+// without d out; update_xp: z, x, p in, x, p out), 10 for degree 1.
+// ---------------------------------------------------------------------------
+void chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
+                            double* b)
+{
+  if (degree < 1 || degree > kChebyshevMaxDegree)
+    throw std::runtime_error(
+        "spmv::chebyshev_coefficients - Error: degree must be 1.."
+        + std::to_string(kChebyshevMaxDegree));
+  if (!std::isfinite(lmin) || !std::isfinite(lmax) || !(lmin > 0.0)
+      || !(lmin < lmax))
+    throw std::runtime_error("spmv::chebyshev_coefficients - Error: bounds must "
+                             "be finite with 0 < lmin < lmax");
+  if (!a || !b)
+    throw std::runtime_error("spmv::chebyshev_coefficients - Error: NULL output");
+  // (volatile: every operation below is one fp64 rounding, whatever the
+  // compiler's contraction setting)
+  volatile double theta = 0.5 * (lmax + lmin);
+  volatile double delta = 0.5 * (lmax - lmin);
+  volatile double sigma = theta / delta;
+  volatile double rho = 1.0 / sigma;
+  a[0] = 0.0;
+  b[0] = 1.0 / theta;
+  for (int j = 1; j < degree; ++j) {
+    volatile double two_sigma = 2.0 * sigma;
+    volatile double den = two_sigma - rho;
+    volatile double rho_new = 1.0 / den;
+    volatile double aj = rho_new * rho;
+    volatile double two_rho = 2.0 * rho_new;
+    a[j] = aj;
+    b[j] = two_rho / delta;
+    rho = rho_new;
+  }
+}
+
+ChebyshevWorkspace::~ChebyshevWorkspace() { release(); }
+
+void ChebyshevWorkspace::release()
+{
+  try {
+    if (stream)
+      _exec.synchronize_stream(stream);
+    _exec.destroy_event(poll_event);
+    for (void* e : timing_ev)
+      _exec.destroy_event(e);
+    if (stream)
+      _exec.destroy_stream(stream);
+    spmv_hip_pcg_ws_destroy(ws);
+    _exec.free(r);
+    _exec.free(Ap);
+    _exec.free(d);
+    _exec.free(w);
+    _exec.free(p);
+    _exec.free(z);
+    _exec.free(x);
+    _exec.free(dinv);
+    _exec.free(dot2);
+    spmv_hip_host_free(_exec.context(), flags);
+  } catch (...) {
+  }
+  timing_ev.clear();
+  ws = nullptr;
+  r = Ap = d = w = p = z = x = dinv = dot2 = nullptr;
+  flags = nullptr;
+  stream = poll_event = nullptr;
+  kmax_cap = -1;
+  m_cap = n_cap = x_cap = dinv_cap = -1;
+}
+
+void ChebyshevWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
+                                bool need_x, bool need_dinv)
+{
+  spmv_hip_ctx* ctx = _exec.context();
+  if (!stream) {
+    stream = _exec.create_stream();
+    poll_event = _exec.create_event();
+    void* mem = nullptr;
+    throw_on_error(spmv_hip_host_alloc(ctx, 2 * sizeof(int32_t), &mem),
+                   "spmv_hip_host_alloc");
+    flags = static_cast<int32_t*>(mem);
+    dot2 = _exec.alloc<double>(len);
+  }
+  if (kmax > kmax_cap) {
+    // (an earlier solve on this workspace has been synchronised: nothing
+    // still reads the old scalars)
+    spmv_hip_pcg_ws_destroy(ws);
+    ws = nullptr;
+    kmax_cap = -1;
+    throw_on_error(spmv_hip_pcg_ws_create(ctx, kmax, &ws),
+                   "spmv_hip_pcg_ws_create");
+    kmax_cap = kmax;
+  }
+  if (M > m_cap) {
+    for (double** v : {&r, &Ap, &d, &w}) {
+      _exec.free(*v);
+      *v = nullptr;
+    }
+    m_cap = -1;
+    for (double** v : {&r, &Ap, &d, &w})
+      *v = _exec.alloc<double>(M);
+    m_cap = M;
+  }
+  if (need_x && M > x_cap) {
+    _exec.free(x);
+    x = nullptr;
+    x_cap = -1;
+    x = _exec.alloc<double>(M);
+    x_cap = M;
+  }
+  if (need_dinv && M > dinv_cap) {
+    _exec.free(dinv);
+    dinv = nullptr;
+    dinv_cap = -1;
+    dinv = _exec.alloc<double>(M);
+    dinv_cap = M;
+  }
+  if (N_padded > n_cap) {
+    for (double** v : {&p, &z}) {
+      _exec.free(*v);
+      *v = nullptr;
+    }
+    n_cap = -1;
+    for (double** v : {&p, &z})
+      *v = _exec.alloc<double>(N_padded);
+    n_cap = N_padded;
+  }
+}
+
+void ChebyshevWorkspace::reserve_timing(int spmvs)
+{
+  while (timing_ev.size() < 2 * (size_t)(spmvs < 0 ? 0 : spmvs))
+    timing_ev.push_back(_exec.create_event(true));
+}
+
+namespace
+{
+bool is_aligned16(const void* q)
+{
+  return (reinterpret_cast<uintptr_t>(q) & 15u) == 0;
+}
+
+bool ranges_overlap(const double* u, const double* v, int64_t M)
+{
+  const uintptr_t ub = reinterpret_cast<uintptr_t>(u);
+  const uintptr_t vb = reinterpret_cast<uintptr_t>(v);
+  const uintptr_t bytes = (uintptr_t)M * sizeof(double);
+  return M > 0 && ub < vb + bytes && vb < ub + bytes;
+}
+} // namespace
+
+void chebyshev_apply(HipExecutor& exec, const Matrix<double>& A,
+                     const double* r, double* z, const double* dinv, int degree,
+                     double lmin, double lmax, ChebyshevWorkspace* workspace)
+{
+  double ca[kChebyshevMaxDegree], cb[kChebyshevMaxDegree];
+  chebyshev_coefficients(degree, lmin, lmax, ca, cb);
+  std::shared_ptr<const L2GMap> col_l2g = A.col_map();
+  std::shared_ptr<const L2GMap> row_l2g = A.row_map();
+  if (row_l2g->num_ghosts() > 0)
+    throw std::runtime_error(
+        "spmv::chebyshev_apply - Error: A.row_map() has ghost entries");
+  const int64_t M = row_l2g->local_size();
+  const int64_t N_padded = col_l2g->local_size() + col_l2g->num_ghosts();
+  if (ranges_overlap(z, r, M))
+    throw std::runtime_error("chebyshev_apply: z overlaps r");
+  if (dinv && ranges_overlap(z, dinv, M))
+    throw std::runtime_error("chebyshev_apply: z overlaps dinv");
+  spmv_hip_ctx* ctx = exec.context();
+  int len = 0;
+  throw_on_error(spmv_hip_dot_partials_len(ctx, &len),
+                 "spmv_hip_dot_partials_len");
+
+  ChebyshevWorkspace own(exec);
+  ChebyshevWorkspace& w = workspace ? *workspace : own;
+  const bool dinv_aligned = is_aligned16(dinv);
+  w.ensure(M, N_padded, 0, len, false, !dinv_aligned);
+
+  // everything on the executor's current stream, nothing waits
+  const double* ri = r;
+  if (!is_aligned16(r)) { // the streaming kernels load 16 bytes at a time
+    exec.copy<double>(w.r, r, M);
+    ri = w.r;
+  }
+  const double* di = dinv;
+  if (dinv && !dinv_aligned) {
+    exec.copy<double>(w.dinv, dinv, M);
+    di = w.dinv;
+  }
+  if (N_padded > M)
+    exec.memset<double>(w.z + M, 0, N_padded - M);
+  throw_on_error(spmv_hip_cheb_apply0_f64(ctx, M, cb[0], ri, di,
+                                          degree > 1 ? w.d : nullptr, w.z,
+                                          nullptr),
+                 "spmv_hip_cheb_apply0_f64");
+  for (int j = 1; j < degree; ++j) {
+    col_l2g->update(w.z);
+    A.mult(w.z, w.w);
+    throw_on_error(spmv_hip_cheb_step_f64(ctx, nullptr, M, ca[j], cb[j],
+                                          j == degree - 1, w.w, ri, di, w.d, w.z,
+                                          nullptr),
+                   "spmv_hip_cheb_step_f64");
+  }
+  exec.copy<double>(z, w.z, M);
+  if (!workspace) // its vectors go away with it
+    exec.synchronize_stream(exec.get_stream());
+}
+
+int pcg_chebyshev(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+                  const double* b, double* x, const double* dinv, int degree,
+                  double lmin, double lmax, int kmax, double rtol,
+                  std::vector<double>* rnorm_history, const CgOptions* options,
+                  CgStats* stats, ChebyshevWorkspace* workspace)
+{
+  double ca[kChebyshevMaxDegree], cb[kChebyshevMaxDegree];
+  chebyshev_coefficients(degree, lmin, lmax, ca, cb);
+  std::shared_ptr<const L2GMap> col_l2g = A.col_map();
+  std::shared_ptr<const L2GMap> row_l2g = A.row_map();
+  if (row_l2g->num_ghosts() > 0)
+    throw std::runtime_error(
+        "spmv::pcg_chebyshev - Error: A.row_map() has ghost entries");
+  if (kmax < 0)
+    throw std::runtime_error("spmv::pcg_chebyshev - Error: kmax < 0");
+  const CgOptions opt = options ? *options : CgOptions();
+  const int poll_every = opt.poll_every < 1 ? 1 : opt.poll_every;
+
+  const int64_t M = row_l2g->local_size();
+  const int64_t N_padded = col_l2g->local_size() + col_l2g->num_ghosts();
+  spmv_hip_ctx* ctx = exec.context();
+  int len = 0;
+  throw_on_error(spmv_hip_dot_partials_len(ctx, &len),
+                 "spmv_hip_dot_partials_len");
+
+  // x is the iterate from the first kernel on: it cannot share b or dinv
+  if (ranges_overlap(x, b, M))
+    throw std::runtime_error(
+        "pcg_chebyshev: x overlaps b (x is updated in place)");
+  if (dinv && ranges_overlap(x, dinv, M))
+    throw std::runtime_error(
+        "pcg_chebyshev: x overlaps dinv (x is updated in place)");
+
+  ChebyshevWorkspace own(exec);
+  ChebyshevWorkspace& w = workspace ? *workspace : own;
+  const bool x_aligned = is_aligned16(x);
+  const bool dinv_aligned = is_aligned16(dinv);
+  w.ensure(M, N_padded, kmax, len, !x_aligned, !dinv_aligned);
+  if (opt.time_spmv)
+    w.reserve_timing(kmax * degree);
+
+  StreamGuard guard{exec, exec.get_stream()};
+  { // order after whatever the caller enqueued (b, dinv may still be in flight)
+    void* ev = exec.create_event();
+    exec.record_event(ev, guard.prev);
+    exec.stream_wait_event(w.stream, ev);
+    exec.destroy_event(ev);
+  }
+  exec.set_stream(w.stream); // every launch below goes to this stream
+
+  throw_on_error(spmv_hip_pcg_ws_reset(w.ws, rtol, nullptr),
+                 "spmv_hip_pcg_ws_reset");
+  double* partials = nullptr;
+  throw_on_error(spmv_hip_pcg_ws_partials(w.ws, &partials),
+                 "spmv_hip_pcg_ws_partials");
+
+  double* const xi = x_aligned ? x : w.x;
+  const double* di = dinv;
+  if (dinv && !dinv_aligned) { // the streaming kernels load 16 bytes at a time
+    exec.copy<double>(w.dinv, dinv, M);
+    di = w.dinv;
+  }
+  // the ghost tails of p and z are defined here instead of relying on fresh
+  // pages
+  if (N_padded > M) {
+    exec.memset<double>(w.p + M, 0, N_padded - M);
+    exec.memset<double>(w.z + M, 0, N_padded - M);
+  }
+  exec.memset<double>(w.dot2, 0, len);
+  double* const dvec = degree > 1 ? w.d : nullptr; // degree 1: no d
+
+  std::vector<void*>& timing_ev = w.timing_ev;
+  size_t ev_next = 0; // two events per timed SpMV
+  // steps 1 .. degree - 1 of z = M(r); the last one leaves the r.z partials
+  auto cheb_steps = [&](bool timed) {
+    for (int j = 1; j < degree; ++j) {
+      col_l2g->update(w.z); // starts on the side stream
+      if (timed)
+        exec.record_event(timing_ev[ev_next], w.stream);
+      A.mult(w.z, w.w);
+      if (timed) {
+        exec.record_event(timing_ev[ev_next + 1], w.stream);
+        ev_next += 2;
+      }
+      throw_on_error(spmv_hip_cheb_step_f64(ctx, w.ws, M, ca[j], cb[j],
+                                            j == degree - 1, w.w, w.r, di, w.d,
+                                            w.z, nullptr),
+                     "spmv_hip_cheb_step_f64");
+    }
+  };
+
+  // r = b, x0 = 0, partials of r.r, step 0 of M: one pass; then the rest of
+  // z0 = M(r0) and p1 = z0
+  throw_on_error(spmv_hip_cheb_init_f64(ctx, w.ws, M, cb[0], b, di, w.r, xi,
+                                        dvec, w.z, nullptr),
+                 "spmv_hip_cheb_init_f64");
+  cheb_steps(false);
+  exec.copy<double>(w.p, w.z, M);
+  w.flags[0] = 0;
+  w.flags[1] = -1;
+
+  auto pair_slot = [&](int k) {
+    double* s = nullptr;
+    throw_on_error(spmv_hip_pcg_ws_rz_rr(w.ws, k, &s), "spmv_hip_pcg_ws_rz_rr");
+    return s;
+  };
+  auto pAp_slot = [&](int k) {
+    double* s = nullptr;
+    throw_on_error(spmv_hip_pcg_ws_pAp(w.ws, k, &s), "spmv_hip_pcg_ws_pAp");
+    return s;
+  };
+
+  // {rz0, rr0}: one all-reduce of 2 doubles
+  throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, 0, nullptr),
+                 "spmv_hip_pcg_reduce_rz_rr");
+  comm.reduce_sum(pair_slot(0), 2, w.stream);
+
+  int k = 0;
+  bool stopped = false;
+  bool poll_pending = false;
+  while (k < kmax && !stopped) {
+    ++k;
+    col_l2g->update(w.p); // starts on the side stream
+    void* ev1 = nullptr;
+    if (opt.time_spmv) {
+      ev1 = timing_ev[ev_next + 1];
+      exec.record_event(timing_ev[ev_next], w.stream);
+      ev_next += 2;
+    }
+    // Ap = A p with the p.Ap partials produced by the SpMV kernels themselves
+    // (local block's share + remote block's share) where they can
+    const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
+    if (!fused) {
+      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, w.p, w.Ap, partials,
+                                              nullptr),
+                     "spmv_hip_dot_partial_f64");
+      throw_on_error(spmv_hip_pcg_reduce_pAp(ctx, w.ws, k, nullptr),
+                     "spmv_hip_pcg_reduce_pAp");
+    } else {
+      throw_on_error(spmv_hip_pcg_reduce_pAp2(ctx, w.ws, k, w.dot2, nullptr),
+                     "spmv_hip_pcg_reduce_pAp2");
+    }
+    comm.reduce_sum(pAp_slot(k), 1, w.stream);
+    throw_on_error(spmv_hip_cheb_update_r_f64(ctx, w.ws, k, M, cb[0], w.Ap, di,
+                                              w.r, dvec, w.z, nullptr),
+                   "spmv_hip_cheb_update_r_f64");
+    cheb_steps(opt.time_spmv);
+    throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, k, nullptr),
+                   "spmv_hip_pcg_reduce_rz_rr");
+    comm.reduce_sum(pair_slot(k), 2, w.stream); // rz[k] and rr[k] at once
+    throw_on_error(spmv_hip_cheb_update_xp_f64(ctx, w.ws, k, M, w.z, xi, w.p,
+                                               nullptr),
+                   "spmv_hip_cheb_update_xp_f64");
+
+    if (k % poll_every == 0 && k < kmax) {
+      // lagging look at the flag, as in cg()
+      if (poll_pending) {
+        exec.synchronize_event(w.poll_event);
+        stopped = w.flags[0] != 0;
+      }
+      if (!stopped) {
+        throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, nullptr, 0,
+                                                  nullptr),
+                       "spmv_hip_pcg_ws_read_async");
+        exec.record_event(w.poll_event, w.stream);
+        poll_pending = true;
+      }
+    }
+  }
+
+  // final state: {done, kstop} and the history of pairs (it has the
+  // WORKSPACE's capacity; the C ABI refuses a shorter destination)
+  int cap = 0;
+  throw_on_error(spmv_hip_pcg_ws_capacity(w.ws, &cap),
+                 "spmv_hip_pcg_ws_capacity");
+  std::vector<double> zr(2 * ((size_t)std::max(kmax, cap) + 1), 0.0);
+  throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, zr.data(), zr.size(),
+                                            nullptr),
+                 "spmv_hip_pcg_ws_read_async");
+  if (xi != x)
+    exec.copy<double>(x, xi, M);
+  exec.synchronize_stream(w.stream);
+
+  if (stats) {
+    *stats = CgStats();
+    for (size_t i = 0; opt.time_spmv && i + 1 < ev_next; i += 2) {
+      float ms = 0.f;
+      throw_on_error(spmv_hip_event_elapsed_ms(ctx, timing_ev[i],
+                                               timing_ev[i + 1], &ms),
+                     "spmv_hip_event_elapsed_ms");
+      stats->spmv_ms_total += ms;
+      ++stats->spmv_launches;
+    }
+  }
+
+  auto rr_at = [&](int j) { return zr[2 * (size_t)j + 1]; };
+  int k_final = k;
+  if (w.flags[0] != 0) {
+    k_final = w.flags[1];
+  } else if (rr_at(0) == 0.0) {
+    k_final = 0; // (kmax == 0: no kernel ran to say so)
+  } else {
+    // `done` is raised by the first reducer of the NEXT iteration; when the
+    // loop ends first, apply the same test to the history here, as pcg() does
+    const double rnorm0 = std::sqrt(rr_at(0));
+    for (int j = 1; j <= k; ++j)
+      if (std::sqrt(rr_at(j)) / rnorm0 < rtol) {
+        k_final = j;
+        break;
+      }
+  }
+  if (rnorm_history) {
+    rnorm_history->resize(k_final + 1);
+    for (int j = 0; j <= k_final; ++j)
+      (*rnorm_history)[j] = std::sqrt(rr_at(j));
+  }
+  return k_final;
+}
+
+double lambda_max_estimate(const Comm& comm, HipExecutor& exec,
+                           const Matrix<double>& A, const double* dinv,
+                           const double* v0, int steps)
+{
+  if (steps < 1)
+    throw std::runtime_error("spmv::lambda_max_estimate - Error: steps < 1");
+  std::shared_ptr<const L2GMap> col_l2g = A.col_map();
+  std::shared_ptr<const L2GMap> row_l2g = A.row_map();
+  if (row_l2g->num_ghosts() > 0)
+    throw std::runtime_error(
+        "spmv::lambda_max_estimate - Error: A.row_map() has ghost entries");
+  const int64_t M = row_l2g->local_size();
+  const int64_t N_padded = col_l2g->local_size() + col_l2g->num_ghosts();
+  spmv_hip_ctx* ctx = exec.context();
+  int len = 0;
+  throw_on_error(spmv_hip_dot_partials_len(ctx, &len),
+                 "spmv_hip_dot_partials_len");
+
+  // q, u: local; v: padded (the SpMV reads it); 3 scalars; one partial array
+  // (everything is allocated before the first reduction)
+  struct Buffers {
+    HipExecutor& exec;
+    double *q = nullptr, *u = nullptr, *v = nullptr, *s = nullptr,
+           *partials = nullptr;
+    ~Buffers()
+    {
+      try {
+        exec.synchronize_stream(exec.get_stream());
+        for (double* ptr : {q, u, v, s, partials})
+          exec.free(ptr);
+      } catch (...) {
+      }
+    }
+  } m{exec};
+  m.q = exec.alloc<double>(M);
+  m.u = exec.alloc<double>(M);
+  m.v = exec.alloc<double>(N_padded);
+  m.s = exec.alloc<double>(3);
+  m.partials = exec.alloc<double>(len);
+  if (N_padded > M)
+    exec.memset<double>(m.v + M, 0, N_padded - M);
+
+  void* st = exec.get_stream();
+  // s[i] = the global dot product of the i-th pair; ONE host wait for all
+  auto dots = [&](std::initializer_list<std::pair<const double*, const double*>>
+                      pairs,
+                  double* out) {
+    int i = 0;
+    for (const auto& pr : pairs) {
+      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, pr.first, pr.second,
+                                              m.partials, nullptr),
+                     "spmv_hip_dot_partial_f64");
+      throw_on_error(spmv_hip_reduce_partials_f64(ctx, m.partials, m.s + i,
+                                                  nullptr),
+                     "spmv_hip_reduce_partials_f64");
+      ++i;
+    }
+    comm.reduce_sum(m.s, pairs.size(), st);
+    exec.copy_to<double>(out, exec.get_host(), m.s, pairs.size()); // waits
+  };
+  auto scale = [&](double s, const double* dv, const double* in, double* out) {
+    throw_on_error(spmv_hip_cheb_scale_f64(ctx, M, s, dv, in, out, nullptr),
+                   "spmv_hip_cheb_scale_f64");
+  };
+
+  double h[3] = {0.0, 0.0, 0.0};
+  dots({{v0, v0}}, h);
+  if (!(h[0] > 0.0) || !std::isfinite(h[0]))
+    throw std::runtime_error(
+        "spmv::lambda_max_estimate - Error: v0 . v0 is not a positive number");
+  scale(std::sqrt(h[0]), nullptr, v0, m.q); // q = v0 / ||v0||
+  double lambda = 0.0;
+  for (int it = 0; it < steps; ++it) {
+    scale(1.0, dinv, m.q, m.v); // v = dinv*q
+    col_l2g->update(m.v);
+    A.mult(m.v, m.u); // u = A v
+    dots({{m.v, m.u}, {m.v, m.q}, {m.u, m.u}}, h);
+    lambda = h[0] / h[1];
+    if (!(h[2] > 0.0) || !std::isfinite(h[2]))
+      throw std::runtime_error(
+          "spmv::lambda_max_estimate - Error: the iteration broke down "
+          "(||A v|| is not a positive number)");
+    scale(std::sqrt(h[2]), nullptr, m.u, m.q); // q = u / ||u||
+  }
+  return lambda;
 }
 
 // ---------------------------------------------------------------------------

@@ -268,6 +268,151 @@ int pcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
         const CgOptions* options = nullptr, CgStats* stats = nullptr,
         PcgWorkspace* workspace = nullptr);
 
+// ---- Chebyshev polynomial preconditioner ------------------------------------
+// The coefficients of the `degree`-step Chebyshev iteration on the interval
+// [lmin, lmax] (host, plain C++, fp64, in exactly this order; the factors 2 and
+// 0.5 are exact):
+//
+//   theta = 0.5*(lmax+lmin); delta = 0.5*(lmax-lmin); sigma = theta/delta
+//   rho_0 = 1/sigma;  a_0 = 0;  b_0 = 1/theta
+//   j = 1..degree-1:  rho_j = 1/(2*sigma - rho_{j-1});  a_j = rho_j*rho_{j-1}
+//                     b_j = 2*rho_j/delta
+//
+// a[] and b[] take `degree` entries each.  1 <= degree <= 16 ("degree"); lmin
+// and lmax finite with 0 < lmin < lmax ("bounds"): std::runtime_error otherwise.
+constexpr int kChebyshevMaxDegree = 16;
+void chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
+                            double* b);
+
+// Work vectors + device scalars of pcg_chebyshev() and chebyshev_apply(), kept
+// across calls like PcgWorkspace; it regrows itself when a call needs more rows
+// or more iterations.  The device scalars and their reducers are pcg()'s.
+class ChebyshevWorkspace
+{
+public:
+  explicit ChebyshevWorkspace(HipExecutor& exec) : _exec(exec) {}
+  ~ChebyshevWorkspace();
+  ChebyshevWorkspace(const ChebyshevWorkspace&) = delete;
+  ChebyshevWorkspace& operator=(const ChebyshevWorkspace&) = delete;
+
+  // ---- internal to pcg_chebyshev() / chebyshev_apply() ----
+  // need_x / need_dinv: the caller's x / dinv is not 16-byte aligned and lives
+  // in the workspace's copy (chebyshev_apply: an unaligned r goes through `r`,
+  // z always through the padded `z`)
+  void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len,
+              bool need_x, bool need_dinv);
+  // events for CgOptions::time_spmv of a solve with up to `spmvs` SpMVs
+  // (iterations * degree), created ahead of it
+  void reserve_timing(int spmvs);
+  void release();
+
+  HipExecutor& _exec;
+  spmv_hip_pcg_ws* ws = nullptr;
+  int kmax_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, x_cap = -1, dinv_cap = -1;
+  double *r = nullptr, *Ap = nullptr, *d = nullptr, *w = nullptr; // m_cap
+  // n_cap: padded, what the SpMVs read; the ghost tails are zeroed by every call
+  double *p = nullptr, *z = nullptr;
+  double* x = nullptr;      // x_cap: the iterate when the caller's x is unaligned
+  double* dinv = nullptr;   // dinv_cap: the copy of an unaligned dinv
+  double* dot2 = nullptr;   // partials of the remote block's p.Ap share
+  int32_t* flags = nullptr; // pinned {done, kstop}
+  void* stream = nullptr;   // compute stream of the solve
+  void* poll_event = nullptr;
+  std::vector<void*> timing_ev; // CgOptions::time_spmv: 2 events per SpMV
+};
+
+// z = q(dinv*A) dinv r: the preconditioner as an operation of its own (it also
+// serves as a smoother), the `degree`-step Chebyshev iteration for A z = r from
+// z = 0 with the coefficients above:
+//
+//   j = 0:   d = b_0 * (dinv*r);                    z = d
+//   j >= 1:  w = A z  (halo update of z, then Matrix::mult)
+//            d = a_j*d + b_j*(dinv*(r - w));        z = z + d
+//
+// Elementwise; every product and sum is a rounding of its own, so the result
+// is the same bits as the restatement on Matrix::mult.  `r`, `z`: DEVICE
+// vectors of A.row_map()->local_size() doubles, any alignment, not overlapping
+// ("overlaps"); `dinv` as in pcg(), or nullptr (no multiply, no dinv stream).
+// Step j >= 1 is one streaming kernel (w, r, dinv, d, z in; d, z out; the last
+// step does not write d).  Only Matrix::mult is used: every plan form, both
+// storages and every halo model serve.  Runs on the executor's current stream;
+// nothing is read back from the device, and with a workspace the host does not
+// wait (without one the call waits before its own work vectors go away).
+void chebyshev_apply(HipExecutor& exec, const Matrix<double>& A,
+                     const double* r, double* z, const double* dinv, int degree,
+                     double lmin, double lmax,
+                     ChebyshevWorkspace* workspace = nullptr);
+
+// CG with the Chebyshev polynomial preconditioner M(r) = chebyshev_apply(r)
+// from x0 = 0: pcg()'s recurrence with a STORED z = M(r).
+//
+//   r0 = b; z0 = M(r0); p1 = z0; rz[0] = r0.z0; rr[0] = r0.r0
+//   for k = 1..kmax:
+//     Ap    = A p_k (fused p.Ap where the SpMV can); alpha = rz[k-1] / (p_k.Ap)
+//     r    -= alpha * Ap; rr[k] = r.r; z = M(r); rz[k] = r.z
+//     x    += alpha * p_k
+//     if sqrt(rr[k]) / sqrt(rr[0]) < rtol: stop (x and r updated, p not)
+//     beta  = rz[k] / rz[k-1]; p_(k+1) = beta * p_k + z
+//
+// The kernel that updates r also leaves the partials of r.r and runs step 0 of
+// M; the last step of M leaves the partials of r.z (degree 1: one kernel does
+// both); one kernel updates x, applies the stop test and updates p.  An
+// iteration is `degree` SpMVs + degree + 1 streaming launches + 2 reducer
+// launches; beside the SpMVs 7*(degree - 1) + 11 vector passes with a dinv
+// (degree 1: 10, no d is written), one per step less without.  With several
+// ranks: one all-reduce of 1 double (p.Ap) and ONE of 2 doubles ({rz[k],
+// rr[k]}, installed together after the last step).
+//
+// dinv: as in pcg(), or nullptr.  degree, lmin, lmax: see
+// chebyshev_coefficients; they are checked before anything touches a device.
+// The bounds are those of the spectrum of dinv*A.  Advised: lmax = 1.1 *
+// lambda_max_estimate(20 steps), lmin = lmax / 30.  Degree 1 is Jacobi-PCG up
+// to the factor b_0.
+//
+// As in pcg(): the stopping test is cg()'s; rnorm_history receives ||r_0||,
+// ..., ||r_k||; a system with r_0 . r_0 == 0 stops at k = 0 with x = 0; scalars
+// stay on the device, the stop is decided on the device and every kernel after
+// `done` returns at once, so x is exactly the iterate of the returned k; the
+// host only polls a pinned flag every `poll_every` iterations; `x` IS the
+// iterate and must not overlap `b` or `dinv` (std::runtime_error, "overlaps");
+// an `x` (or a `dinv`) that is not 16-byte aligned goes through the
+// workspace's copy; kmax < 0 throws ("kmax"); the executor's stream is
+// restored on every exit path.
+//
+// options: poll_every and time_spmv apply (time_spmv brackets ALL `degree`
+//          Matrix::mult calls of an iteration, each between two events:
+//          CgStats::spmv_launches is `degree` per iteration, the local-block
+//          kernel for A p as in pcg()); consumer_reductions,
+//          defer_x and mixed are IGNORED: every dot product is finished by a
+//          reducer kernel, as in cg_block, x is updated in every iteration, in
+//          fp64.
+int pcg_chebyshev(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+                  const double* b, double* x, const double* dinv, int degree,
+                  double lmin, double lmax, int kmax, double rtol,
+                  std::vector<double>* rnorm_history = nullptr,
+                  const CgOptions* options = nullptr, CgStats* stats = nullptr,
+                  ChebyshevWorkspace* workspace = nullptr);
+
+// An estimate of the largest eigenvalue of dinv*A (A itself with dinv ==
+// nullptr): `steps` steps of the power iteration with the generalised Rayleigh
+// quotient.  Setup code; the host waits once per step.
+//
+//   q = v0 / ||v0||
+//   repeat `steps` times:  v = dinv*q;  u = A v;  lambda = (v.u) / (v.q)
+//                          q = u / ||u||
+//
+// Returns the last lambda (the same on every rank).  `v0`: a DEVICE vector of
+// A.row_map()->local_size() doubles (the right-hand side will do), not
+// modified.  The dot products go through the deterministic partial sums of
+// cg() and the communicator's all-reduce.  steps < 1 ("steps") or v0.v0 == 0
+// ("v0") throws std::runtime_error.  The estimate approaches the eigenvalue
+// from below (0.96 to 0.975 of it after 20 steps on the Poisson test matrices),
+// hence the advised lmax = 1.1 * estimate(20 steps), lmin = lmax / 30.
+double lambda_max_estimate(const Comm& comm, HipExecutor& exec,
+                           const Matrix<double>& A, const double* dinv,
+                           const double* v0, int steps);
+
 // Work vectors + device scalars of bicgstab(), kept across calls like
 // PcgWorkspace; it regrows itself when a call needs more rows or more
 // iterations.

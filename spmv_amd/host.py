@@ -137,6 +137,15 @@ _PROTOS = {
     "spmvh_pcg_workspace_reserve_timing": [vp, C.c_int],
     "spmvh_pcg": [vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int), vp, vp,
                   C.c_int, PTR(f64), PTR(C.c_int)],
+    "spmvh_chebyshev_coefficients": [C.c_int, f64, f64, vp, vp],
+    "spmvh_chebyshev_workspace_create": [vp, PTR(vp)],
+    "spmvh_chebyshev_workspace_destroy": [vp],
+    "spmvh_chebyshev_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_chebyshev_apply": [vp, vp, vp, vp, vp, C.c_int, f64, f64, vp],
+    "spmvh_pcg_chebyshev": [vp, vp, vp, vp, vp, vp, C.c_int, f64, f64, C.c_int,
+                            f64, PTR(C.c_int), vp, vp, C.c_int, PTR(f64),
+                            PTR(C.c_int)],
+    "spmvh_lambda_max_estimate": [vp, vp, vp, vp, vp, C.c_int, PTR(f64)],
     "spmvh_bicgstab_workspace_create": [vp, PTR(vp)],
     "spmvh_bicgstab_workspace_destroy": [vp],
     "spmvh_bicgstab_workspace_reserve_timing": [vp, C.c_int],
@@ -865,6 +874,77 @@ def pcg(comm, exec_, A, b_ptr, x_ptr, dinv_ptr, kmax, rtol, workspace=None,
     if stats is not None:
         stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
     return k.value, hist[:k.value + 1]
+
+
+def chebyshev_coefficients(degree, lmin, lmax):
+    """spmv::chebyshev_coefficients -> (a, b), `degree` doubles each.  Raises
+    SpmvHostError ("degree" / "bounds") for a degree outside 1..16 or bounds
+    that are not finite with 0 < lmin < lmax.  Host only."""
+    n = max(int(degree), 1)
+    a, b = np.zeros(n), np.zeros(n)
+    call("spmvh_chebyshev_coefficients", int(degree), float(lmin), float(lmax),
+         _np_ptr(a), _np_ptr(b))
+    return a, b
+
+
+class ChebyshevWorkspace:
+    """spmv::ChebyshevWorkspace: work vectors kept across pcg_chebyshev() and
+    chebyshev_apply() calls."""
+
+    def __init__(self, exec_):
+        h = vp()
+        call("spmvh_chebyshev_workspace_create", exec_.h, C.byref(h))
+        self.h = h
+
+    def reserve_timing(self, spmvs):
+        call("spmvh_chebyshev_workspace_reserve_timing", self.h, int(spmvs))
+
+    def close(self):
+        if self.h:
+            call("spmvh_chebyshev_workspace_destroy", self.h)
+            self.h = None
+
+
+def chebyshev_apply(exec_, A, r_ptr, z_ptr, dinv_ptr, degree, lmin, lmax,
+                    workspace=None):
+    """spmv::chebyshev_apply: z = q(dinv*A) dinv r, the `degree`-step Chebyshev
+    iteration for A z = r from z = 0 on [lmin, lmax].  dinv_ptr may be None."""
+    call("spmvh_chebyshev_apply", exec_.h, A.h, r_ptr, z_ptr, dinv_ptr or None,
+         int(degree), float(lmin), float(lmax),
+         workspace.h if workspace else None)
+
+
+def pcg_chebyshev(comm, exec_, A, b_ptr, x_ptr, dinv_ptr, degree, lmin, lmax,
+                  kmax, rtol, workspace=None, time_spmv=False, poll_every=0,
+                  stats=None):
+    """spmv::pcg_chebyshev: CG from x0 = 0 with the Chebyshev polynomial
+    preconditioner of `degree` in dinv*A on [lmin, lmax] -> (k, rnorm_history),
+    the history that of the unpreconditioned residual.  dinv_ptr may be None.
+    stats (optional dict) receives spmv_ms_total and spmv_launches of a
+    time_spmv solve (`degree` SpMVs per iteration)."""
+    kmax = int(kmax)
+    k, n = C.c_int(), C.c_int()
+    ms = f64()
+    hist = np.zeros(max(kmax, 0) + 1)
+    call("spmvh_pcg_chebyshev", comm.h, exec_.h, A.h, b_ptr, x_ptr,
+         dinv_ptr or None, int(degree), float(lmin), float(lmax), kmax,
+         float(rtol), C.byref(k), _np_ptr(hist),
+         workspace.h if workspace else None,
+         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         C.byref(n))
+    if stats is not None:
+        stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, hist[:k.value + 1]
+
+
+def lambda_max_estimate(comm, exec_, A, dinv_ptr, v0_ptr, steps):
+    """spmv::lambda_max_estimate: `steps` power iterations on dinv*A from v0
+    with the generalised Rayleigh quotient -> the last estimate.  Advised:
+    lmax = 1.1 * estimate(20 steps), lmin = lmax / 30."""
+    lam = f64()
+    call("spmvh_lambda_max_estimate", comm.h, exec_.h, A.h, dinv_ptr or None,
+         v0_ptr, int(steps), C.byref(lam))
+    return lam.value
 
 
 class BicgstabWorkspace:
