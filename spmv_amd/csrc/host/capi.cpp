@@ -40,26 +40,16 @@ struct spmvh_split {
 struct spmvh_petsc_rows {
   PetscRows rows;
 };
-struct spmvh_cg_workspace {
+template <typename W>
+struct WorkspaceHandle {
   std::shared_ptr<HipExecutor> exec; // keeps the executor alive
-  std::unique_ptr<CgWorkspace> ws;
+  std::unique_ptr<W> ws;
 };
-struct spmvh_cg_block_workspace {
-  std::shared_ptr<HipExecutor> exec; // keeps the executor alive
-  std::unique_ptr<CgBlockWorkspace> ws;
-};
-struct spmvh_pcg_workspace {
-  std::shared_ptr<HipExecutor> exec; // keeps the executor alive
-  std::unique_ptr<PcgWorkspace> ws;
-};
-struct spmvh_chebyshev_workspace {
-  std::shared_ptr<HipExecutor> exec; // keeps the executor alive
-  std::unique_ptr<ChebyshevWorkspace> ws;
-};
-struct spmvh_bicgstab_workspace {
-  std::shared_ptr<HipExecutor> exec; // keeps the executor alive
-  std::unique_ptr<BicgstabWorkspace> ws;
-};
+struct spmvh_cg_workspace : WorkspaceHandle<CgWorkspace> {};
+struct spmvh_cg_block_workspace : WorkspaceHandle<CgBlockWorkspace> {};
+struct spmvh_pcg_workspace : WorkspaceHandle<PcgWorkspace> {};
+struct spmvh_chebyshev_workspace : WorkspaceHandle<ChebyshevWorkspace> {};
+struct spmvh_bicgstab_workspace : WorkspaceHandle<BicgstabWorkspace> {};
 
 namespace
 {
@@ -106,6 +96,40 @@ void copy_plan(const L2GMap& m, int32_t* neighbours, int32_t* send_count,
     recv_offset[i] = m.recv_offset()[i];
   }
   std::copy(m.indexbuf().begin(), m.indexbuf().end(), indexbuf);
+}
+
+// spmvh_*_workspace_create / _reserve_timing of the five solver workspaces
+template <typename W, typename H>
+int workspace_create(spmvh_exec* exec, H** ws)
+{
+  return guarded([&] {
+    require(exec && ws, "NULL argument");
+    auto w = std::make_unique<H>();
+    w->exec = exec->hip;
+    w->ws.reset(new W(*exec->hip));
+    *ws = w.release();
+  });
+}
+
+template <typename H>
+int workspace_reserve_timing(H* ws, int count)
+{
+  return guarded([&] {
+    require(ws, "NULL argument");
+    ws->ws->reserve_timing(count);
+  });
+}
+
+// what every solver entry point hands back: the history and CgOptions::time_spmv
+void copy_out(const std::vector<double>& hist, double* rnorm_history,
+              const CgStats& st, double* spmv_ms_total, int* spmv_launches)
+{
+  if (rnorm_history)
+    std::copy(hist.begin(), hist.end(), rnorm_history);
+  if (spmv_ms_total)
+    *spmv_ms_total = st.spmv_ms_total;
+  if (spmv_launches)
+    *spmv_launches = st.spmv_launches;
 }
 } // namespace
 
@@ -1045,13 +1069,7 @@ int spmvh_petsc_rows_destroy(spmvh_petsc_rows* rows)
 
 int spmvh_cg_workspace_create(spmvh_exec* exec, spmvh_cg_workspace** ws)
 {
-  return guarded([&] {
-    require(exec && ws, "NULL argument");
-    auto w = std::make_unique<spmvh_cg_workspace>();
-    w->exec = exec->hip;
-    w->ws.reset(new CgWorkspace(*exec->hip));
-    *ws = w.release();
-  });
+  return workspace_create<CgWorkspace>(exec, ws);
 }
 
 int spmvh_cg_workspace_destroy(spmvh_cg_workspace* ws)
@@ -1061,10 +1079,7 @@ int spmvh_cg_workspace_destroy(spmvh_cg_workspace* ws)
 
 int spmvh_cg_workspace_reserve_timing(spmvh_cg_workspace* ws, int iterations)
 {
-  return guarded([&] {
-    require(ws, "NULL argument");
-    ws->ws->reserve_timing(iterations);
-  });
+  return workspace_reserve_timing(ws, iterations);
 }
 
 int spmvh_cg_mixed(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
@@ -1120,25 +1135,14 @@ int spmvh_cg_ex(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     *num_its = cg(*comm->comm, *exec->hip, *A->A, b, x, kmax, rtol,
                   rnorm_history ? &hist : nullptr, &opt, &st,
                   ws ? ws->ws.get() : nullptr);
-    if (rnorm_history)
-      std::copy(hist.begin(), hist.end(), rnorm_history);
-    if (spmv_ms_total)
-      *spmv_ms_total = st.spmv_ms_total;
-    if (spmv_launches)
-      *spmv_launches = st.spmv_launches;
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
   });
 }
 
 int spmvh_cg_block_workspace_create(spmvh_exec* exec,
                                     spmvh_cg_block_workspace** ws)
 {
-  return guarded([&] {
-    require(exec && ws, "NULL argument");
-    auto w = std::make_unique<spmvh_cg_block_workspace>();
-    w->exec = exec->hip;
-    w->ws.reset(new CgBlockWorkspace(*exec->hip));
-    *ws = w.release();
-  });
+  return workspace_create<CgBlockWorkspace>(exec, ws);
 }
 
 int spmvh_cg_block_workspace_destroy(spmvh_cg_block_workspace* ws)
@@ -1165,12 +1169,7 @@ int spmvh_cg_block(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                         &its, rnorm_history ? &hist : nullptr, &opt, &st,
                         ws ? ws->ws.get() : nullptr);
     std::copy(its.begin(), its.end(), iterations);
-    if (rnorm_history)
-      std::copy(hist.begin(), hist.end(), rnorm_history);
-    if (spmv_ms_total)
-      *spmv_ms_total = st.spmv_ms_total;
-    if (spmv_launches)
-      *spmv_launches = st.spmv_launches;
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
   });
 }
 
@@ -1195,13 +1194,7 @@ int spmvh_jacobi_inverse(spmvh_exec* exec, const double* d, double* dinv,
 
 int spmvh_pcg_workspace_create(spmvh_exec* exec, spmvh_pcg_workspace** ws)
 {
-  return guarded([&] {
-    require(exec && ws, "NULL argument");
-    auto w = std::make_unique<spmvh_pcg_workspace>();
-    w->exec = exec->hip;
-    w->ws.reset(new PcgWorkspace(*exec->hip));
-    *ws = w.release();
-  });
+  return workspace_create<PcgWorkspace>(exec, ws);
 }
 
 int spmvh_pcg_workspace_destroy(spmvh_pcg_workspace* ws)
@@ -1211,10 +1204,7 @@ int spmvh_pcg_workspace_destroy(spmvh_pcg_workspace* ws)
 
 int spmvh_pcg_workspace_reserve_timing(spmvh_pcg_workspace* ws, int iterations)
 {
-  return guarded([&] {
-    require(ws, "NULL argument");
-    ws->ws->reserve_timing(iterations);
-  });
+  return workspace_reserve_timing(ws, iterations);
 }
 
 int spmvh_pcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
@@ -1235,12 +1225,7 @@ int spmvh_pcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     *num_its = pcg(*comm->comm, *exec->hip, *A->A, b, x, dinv, kmax, rtol,
                    rnorm_history ? &hist : nullptr, &opt, &st,
                    ws ? ws->ws.get() : nullptr);
-    if (rnorm_history)
-      std::copy(hist.begin(), hist.end(), rnorm_history);
-    if (spmv_ms_total)
-      *spmv_ms_total = st.spmv_ms_total;
-    if (spmv_launches)
-      *spmv_launches = st.spmv_launches;
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
   });
 }
 
@@ -1254,13 +1239,7 @@ int spmvh_chebyshev_coefficients(int degree, double lmin, double lmax, double* a
 int spmvh_chebyshev_workspace_create(spmvh_exec* exec,
                                      spmvh_chebyshev_workspace** ws)
 {
-  return guarded([&] {
-    require(exec && ws, "NULL argument");
-    auto w = std::make_unique<spmvh_chebyshev_workspace>();
-    w->exec = exec->hip;
-    w->ws.reset(new ChebyshevWorkspace(*exec->hip));
-    *ws = w.release();
-  });
+  return workspace_create<ChebyshevWorkspace>(exec, ws);
 }
 
 int spmvh_chebyshev_workspace_destroy(spmvh_chebyshev_workspace* ws)
@@ -1271,10 +1250,7 @@ int spmvh_chebyshev_workspace_destroy(spmvh_chebyshev_workspace* ws)
 int spmvh_chebyshev_workspace_reserve_timing(spmvh_chebyshev_workspace* ws,
                                              int spmvs)
 {
-  return guarded([&] {
-    require(ws, "NULL argument");
-    ws->ws->reserve_timing(spmvs);
-  });
+  return workspace_reserve_timing(ws, spmvs);
 }
 
 int spmvh_chebyshev_apply(spmvh_exec* exec, spmvh_matrix* A, const double* r,
@@ -1307,12 +1283,7 @@ int spmvh_pcg_chebyshev(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                              lmin, lmax, kmax, rtol,
                              rnorm_history ? &hist : nullptr, &opt, &st,
                              ws ? ws->ws.get() : nullptr);
-    if (rnorm_history)
-      std::copy(hist.begin(), hist.end(), rnorm_history);
-    if (spmv_ms_total)
-      *spmv_ms_total = st.spmv_ms_total;
-    if (spmv_launches)
-      *spmv_launches = st.spmv_launches;
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
   });
 }
 
@@ -1331,13 +1302,7 @@ int spmvh_lambda_max_estimate(spmvh_comm* comm, spmvh_exec* exec,
 int spmvh_bicgstab_workspace_create(spmvh_exec* exec,
                                     spmvh_bicgstab_workspace** ws)
 {
-  return guarded([&] {
-    require(exec && ws, "NULL argument");
-    auto w = std::make_unique<spmvh_bicgstab_workspace>();
-    w->exec = exec->hip;
-    w->ws.reset(new BicgstabWorkspace(*exec->hip));
-    *ws = w.release();
-  });
+  return workspace_create<BicgstabWorkspace>(exec, ws);
 }
 
 int spmvh_bicgstab_workspace_destroy(spmvh_bicgstab_workspace* ws)
@@ -1348,10 +1313,7 @@ int spmvh_bicgstab_workspace_destroy(spmvh_bicgstab_workspace* ws)
 int spmvh_bicgstab_workspace_reserve_timing(spmvh_bicgstab_workspace* ws,
                                             int iterations)
 {
-  return guarded([&] {
-    require(ws, "NULL argument");
-    ws->ws->reserve_timing(iterations);
-  });
+  return workspace_reserve_timing(ws, iterations);
 }
 
 int spmvh_bicgstab(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
@@ -1375,12 +1337,7 @@ int spmvh_bicgstab(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                         ws ? ws->ws.get() : nullptr, &how);
     if (status)
       *status = how;
-    if (rnorm_history)
-      std::copy(hist.begin(), hist.end(), rnorm_history);
-    if (spmv_ms_total)
-      *spmv_ms_total = st.spmv_ms_total;
-    if (spmv_launches)
-      *spmv_launches = st.spmv_launches;
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
   });
 }
 

@@ -2,7 +2,9 @@
 // per-executor overload set of spmv::cg (spmv/cg.h, spmv/cuda/cg_cuda.h:30-32).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <initializer_list>
 #include <vector>
 
 #include "comm.h"
@@ -17,38 +19,67 @@ struct spmv_hip_bicg_ws;
 namespace spmv
 {
 
+// What the workspaces of all solvers share: the solve's stream, the event and
+// the pinned words of the host's lagging look at the device's state, the
+// timing events, and how the work vectors of one capacity are regrown.
+class SolverWorkspace
+{
+public:
+  SolverWorkspace(const SolverWorkspace&) = delete;
+  SolverWorkspace& operator=(const SolverWorkspace&) = delete;
+
+  HipExecutor& _exec;
+  int32_t* flags = nullptr; // pinned: the device's state words, [0] = done
+  void* stream = nullptr;   // compute stream of the solve
+  void* poll_event = nullptr;
+  std::vector<void*> timing_ev; // CgOptions::time_spmv: 2 events per SpMV
+
+protected:
+  explicit SolverWorkspace(HipExecutor& exec) : _exec(exec) {}
+  ~SolverWorkspace() = default;
+  // first use: creates the stream and the poll event, allocates the pinned words
+  void open(int flag_words);
+  // want > cap: frees the vectors of one capacity, then allocates them at the
+  // new one; the capacity is -1 and the pointers are null while they are gone
+  void regrow(int64_t& cap, int64_t want, std::initializer_list<double**> vecs);
+  // timing_ev grows to n events
+  void reserve_events(size_t n);
+  // waits for the stream, then destroys the events and the stream and frees
+  // the pinned words; what a release() calls first
+  void release_common();
+  // frees and nulls every vector (errors are swallowed: a release() never throws)
+  void free_vectors(std::initializer_list<double**> vecs);
+};
+
 // Work vectors + device scalars of one solve (cg.cpp:39-42 allocates and
 // frees them on every call).  Passing the same CgWorkspace to repeated cg()
 // calls keeps the allocations; it regrows itself when a call needs more.
-class CgWorkspace
+class CgWorkspace : public SolverWorkspace
 {
 public:
-  explicit CgWorkspace(HipExecutor& exec) : _exec(exec) {}
+  explicit CgWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
   ~CgWorkspace();
-  CgWorkspace(const CgWorkspace&) = delete;
-  CgWorkspace& operator=(const CgWorkspace&) = delete;
 
   // ---- internal to cg() ----
   void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len);
   // events for CgOptions::time_spmv of a solve of up to `iterations` steps,
   // created ahead of it (a benchmark keeps them out of its timed region)
-  void reserve_timing(int iterations);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(2 * (size_t)std::max(iterations, 0));
+  }
   // the second p buffer of CgOptions::defer_x, allocated by the first solve
   // that takes that path (after ensure())
   void ensure_p2();
   void release();
 
-  HipExecutor& _exec;
   spmv_hip_cg_ws* ws = nullptr;
   int kmax_cap = -1;
   int64_t m_cap = -1, n_cap = -1;
   double *r = nullptr, *Ap = nullptr, *x = nullptr, *p = nullptr;
   double* p2 = nullptr;     // CgOptions::defer_x: the second p buffer (n_cap)
   double* dot2 = nullptr;   // partials of the remote block's p.Ap share
-  int32_t* flags = nullptr; // pinned {done, kstop}
-  void* stream = nullptr;   // compute stream of the solve
-  void* poll_event = nullptr;
-  std::vector<void*> timing_ev; // CgOptions::time_spmv: 2 events per iteration
+  // flags: {done, kstop}; timing_ev: 2 events per iteration
 };
 
 struct CgOptions {
@@ -120,33 +151,31 @@ int cg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
 // Work vectors + device scalars of cg_block(), kept across calls like
 // CgWorkspace; it regrows itself when a call needs more rows, more iterations
 // or another nrhs.
-class CgBlockWorkspace
+class CgBlockWorkspace : public SolverWorkspace
 {
 public:
-  explicit CgBlockWorkspace(HipExecutor& exec) : _exec(exec) {}
+  explicit CgBlockWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
   ~CgBlockWorkspace();
-  CgBlockWorkspace(const CgBlockWorkspace&) = delete;
-  CgBlockWorkspace& operator=(const CgBlockWorkspace&) = delete;
 
   // ---- internal to cg_block() ----
   // m_elems = rows * nrhs, n_elems = (local + ghosts) * nrhs; need_x: the
   // caller's X is not 16-byte aligned, the iterate lives in `x`
   void ensure(int64_t m_elems, int64_t n_elems, int kmax, int nrhs,
               bool need_x);
-  void reserve_timing(int iterations);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(2 * (size_t)std::max(iterations, 0));
+  }
   void release();
 
-  HipExecutor& _exec;
   spmv_hip_cgb_ws* ws = nullptr;
   int kmax_cap = -1, nrhs_cap = 0;
   int64_t m_cap = -1, n_cap = -1, x_cap = -1;
   double *r = nullptr, *Ap = nullptr; // m_cap
   double* x = nullptr; // x_cap: the iterate when the caller's X is unaligned
   double* p = nullptr; // n_cap: padded, the ghost tail is zeroed by every solve
-  int32_t* state = nullptr; // pinned {all_done, done[], kstop[]} (spmv_hip.h)
-  void* stream = nullptr;   // compute stream of the solve
-  void* poll_event = nullptr;
-  std::vector<void*> timing_ev; // CgOptions::time_spmv: 2 events per iteration
+  // flags: {all_done, done[], kstop[]} (spmv_hip.h); timing_ev: 2 events per
+  // iteration
 };
 
 // CG for several right-hand sides: solves A X = B for `nrhs` columns with
@@ -189,23 +218,23 @@ int cg_block(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
 
 // Work vectors + device scalars of pcg(), kept across calls like CgWorkspace;
 // it regrows itself when a call needs more rows or more iterations.
-class PcgWorkspace
+class PcgWorkspace : public SolverWorkspace
 {
 public:
-  explicit PcgWorkspace(HipExecutor& exec) : _exec(exec) {}
+  explicit PcgWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
   ~PcgWorkspace();
-  PcgWorkspace(const PcgWorkspace&) = delete;
-  PcgWorkspace& operator=(const PcgWorkspace&) = delete;
 
   // ---- internal to pcg() ----
   // need_x / need_dinv: the caller's x / dinv is not 16-byte aligned and lives
   // in the workspace's copy during the solve
   void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len,
               bool need_x, bool need_dinv);
-  void reserve_timing(int iterations);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(2 * (size_t)std::max(iterations, 0));
+  }
   void release();
 
-  HipExecutor& _exec;
   spmv_hip_pcg_ws* ws = nullptr;
   int kmax_cap = -1;
   int64_t m_cap = -1, n_cap = -1, x_cap = -1, dinv_cap = -1;
@@ -214,10 +243,7 @@ public:
   double* dinv = nullptr;   // dinv_cap: the copy of an unaligned dinv
   double* p = nullptr;      // n_cap: padded, the ghost tail is zeroed by every solve
   double* dot2 = nullptr;   // partials of the remote block's p.Ap share
-  int32_t* flags = nullptr; // pinned {done, kstop}
-  void* stream = nullptr;   // compute stream of the solve
-  void* poll_event = nullptr;
-  std::vector<void*> timing_ev; // CgOptions::time_spmv: 2 events per iteration
+  // flags: {done, kstop}; timing_ev: 2 events per iteration
 };
 
 // dinv[i] = 1.0 / d[i] (spmv_hip_jacobi_invert_f64); `d` and `dinv` DEVICE
@@ -287,13 +313,11 @@ void chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
 // Work vectors + device scalars of pcg_chebyshev() and chebyshev_apply(), kept
 // across calls like PcgWorkspace; it regrows itself when a call needs more rows
 // or more iterations.  The device scalars and their reducers are pcg()'s.
-class ChebyshevWorkspace
+class ChebyshevWorkspace : public SolverWorkspace
 {
 public:
-  explicit ChebyshevWorkspace(HipExecutor& exec) : _exec(exec) {}
+  explicit ChebyshevWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
   ~ChebyshevWorkspace();
-  ChebyshevWorkspace(const ChebyshevWorkspace&) = delete;
-  ChebyshevWorkspace& operator=(const ChebyshevWorkspace&) = delete;
 
   // ---- internal to pcg_chebyshev() / chebyshev_apply() ----
   // need_x / need_dinv: the caller's x / dinv is not 16-byte aligned and lives
@@ -303,10 +327,12 @@ public:
               bool need_x, bool need_dinv);
   // events for CgOptions::time_spmv of a solve with up to `spmvs` SpMVs
   // (iterations * degree), created ahead of it
-  void reserve_timing(int spmvs);
+  void reserve_timing(int spmvs)
+  {
+    reserve_events(2 * (size_t)std::max(spmvs, 0));
+  }
   void release();
 
-  HipExecutor& _exec;
   spmv_hip_pcg_ws* ws = nullptr;
   int kmax_cap = -1;
   int64_t m_cap = -1, n_cap = -1, x_cap = -1, dinv_cap = -1;
@@ -316,10 +342,7 @@ public:
   double* x = nullptr;      // x_cap: the iterate when the caller's x is unaligned
   double* dinv = nullptr;   // dinv_cap: the copy of an unaligned dinv
   double* dot2 = nullptr;   // partials of the remote block's p.Ap share
-  int32_t* flags = nullptr; // pinned {done, kstop}
-  void* stream = nullptr;   // compute stream of the solve
-  void* poll_event = nullptr;
-  std::vector<void*> timing_ev; // CgOptions::time_spmv: 2 events per SpMV
+  // flags: {done, kstop}; timing_ev: 2 events per SpMV
 };
 
 // z = q(dinv*A) dinv r: the preconditioner as an operation of its own (it also
@@ -416,13 +439,11 @@ double lambda_max_estimate(const Comm& comm, HipExecutor& exec,
 // Work vectors + device scalars of bicgstab(), kept across calls like
 // PcgWorkspace; it regrows itself when a call needs more rows or more
 // iterations.
-class BicgstabWorkspace
+class BicgstabWorkspace : public SolverWorkspace
 {
 public:
-  explicit BicgstabWorkspace(HipExecutor& exec) : _exec(exec) {}
+  explicit BicgstabWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
   ~BicgstabWorkspace();
-  BicgstabWorkspace(const BicgstabWorkspace&) = delete;
-  BicgstabWorkspace& operator=(const BicgstabWorkspace&) = delete;
 
   // ---- internal to bicgstab() ----
   // need_x / need_dinv: the caller's x / dinv is not 16-byte aligned and lives
@@ -430,10 +451,12 @@ public:
   // sh are vectors of their own
   void ensure(int64_t M, int64_t N_padded, int kmax, bool need_x, bool need_dinv,
               bool need_h);
-  void reserve_timing(int iterations);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(4 * (size_t)std::max(iterations, 0));
+  }
   void release();
 
-  HipExecutor& _exec;
   spmv_hip_bicg_ws* ws = nullptr;
   int kmax_cap = -1;
   int64_t m_cap = -1, n_cap = -1, h_cap = -1, x_cap = -1, dinv_cap = -1;
@@ -444,10 +467,7 @@ public:
   double *ph = nullptr, *sh = nullptr; // h_cap: padded, dinv*p and dinv*s
   double* x = nullptr;      // x_cap: the iterate when the caller's x is unaligned
   double* dinv = nullptr;   // dinv_cap: the copy of an unaligned dinv
-  int32_t* flags = nullptr; // pinned {done, kstop, status}
-  void* stream = nullptr;   // compute stream of the solve
-  void* poll_event = nullptr;
-  std::vector<void*> timing_ev; // CgOptions::time_spmv: 4 events per iteration
+  // flags: {done, kstop, status}; timing_ev: 4 events per iteration
 };
 
 // BiCGStab from x0 = 0 for a matrix that need not be symmetric, with an

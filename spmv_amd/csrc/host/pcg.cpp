@@ -1,0 +1,606 @@
+// spmv::pcg and the Chebyshev polynomial preconditioner for HipExecutor: see
+// cg.h.
+#include "cg.h"
+
+#include <initializer_list>
+#include <utility>
+
+#include "solver_common.h"
+
+namespace spmv
+{
+using namespace detail;
+
+// ---------------------------------------------------------------------------
+// pcg: see cg.h.  Per iteration (compute stream):
+//     halo start on the map's side stream
+//     SpMV local block (+ fused p.Ap share) [wait halo event] remote block
+//     one rank, consumer_reductions:            otherwise:
+//       update_r_cs   (pAp[k]; r; r.z, r.r)       reduce_pAp(2) ; all-reduce of 1
+//       update_xp_cs  ({rz,rr}[k]; x; p)          update_r
+//                                                 reduce_rz_rr ; all-reduce of 2
+//                                                 update_xp
+// 3 (or 5) launches; beside the SpMV 10 vector passes (update_r: Ap, r, dinv
+// in, r out; update_xp: r, dinv, x, p in, x, p out) where cg() without
+// defer_x streams 8.
+// ---------------------------------------------------------------------------
+PcgWorkspace::~PcgWorkspace() { release(); }
+
+void PcgWorkspace::release()
+{
+  release_common();
+  spmv_hip_pcg_ws_destroy(ws);
+  ws = nullptr;
+  free_vectors({&r, &Ap, &x, &dinv, &p, &dot2});
+  kmax_cap = -1;
+  m_cap = n_cap = x_cap = dinv_cap = -1;
+}
+
+namespace
+{
+// the device scalars of pcg() and pcg_chebyshev() for up to kmax iterations
+void regrow_scalars(spmv_hip_ctx* ctx, spmv_hip_pcg_ws*& ws, int& kmax_cap,
+                    int kmax)
+{
+  if (kmax <= kmax_cap)
+    return;
+  // (an earlier solve on this workspace has been synchronised: nothing
+  // still reads the old scalars)
+  spmv_hip_pcg_ws_destroy(ws);
+  ws = nullptr;
+  kmax_cap = -1;
+  throw_on_error(spmv_hip_pcg_ws_create(ctx, kmax, &ws),
+                 "spmv_hip_pcg_ws_create");
+  kmax_cap = kmax;
+}
+} // namespace
+
+void PcgWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
+                          bool need_x, bool need_dinv)
+{
+  open(2);
+  if (!dot2)
+    dot2 = _exec.alloc<double>(len);
+  regrow_scalars(_exec.context(), ws, kmax_cap, kmax);
+  regrow(m_cap, M, {&r, &Ap});
+  if (need_x)
+    regrow(x_cap, M, {&x});
+  if (need_dinv)
+    regrow(dinv_cap, M, {&dinv});
+  regrow(n_cap, N_padded, {&p});
+}
+void jacobi_inverse(HipExecutor& exec, const double* d, double* dinv, int64_t n)
+{
+  if (n < 0)
+    throw std::runtime_error("spmv::jacobi_inverse - Error: n < 0");
+  int32_t* count = exec.alloc<int32_t>(1);
+  int32_t bad = 0;
+  try {
+    throw_on_error(spmv_hip_jacobi_invert_f64(exec.context(), n, d, dinv, count,
+                                              nullptr),
+                   "spmv_hip_jacobi_invert_f64");
+    exec.copy_to<int32_t>(&bad, exec.get_host(), count, 1); // waits
+  } catch (...) {
+    exec.free(count);
+    throw;
+  }
+  exec.free(count);
+  if (bad != 0)
+    throw std::runtime_error(
+        "spmv::jacobi_inverse - Error: the diagonal is not positive ("
+        + std::to_string(bad) + " of " + std::to_string(n)
+        + " entries are not finite or not > 0)");
+}
+
+int pcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+        const double* b, double* x, const double* dinv, int kmax, double rtol,
+        std::vector<double>* rnorm_history, const CgOptions* options,
+        CgStats* stats, PcgWorkspace* workspace)
+{
+  const Dims dims = check_problem("pcg", A, kmax);
+  const int64_t M = dims.M, N_padded = dims.N_padded;
+  const std::shared_ptr<const L2GMap>& col_l2g = dims.col_l2g;
+  const CgOptions opt = options ? *options : CgOptions();
+  spmv_hip_ctx* ctx = exec.context();
+  const int len = dot_partials_len(ctx);
+  // x is the iterate from the first kernel on: it cannot share b or dinv
+  if (ranges_overlap(x, b, M))
+    throw std::runtime_error("pcg: x overlaps b (x is updated in place)");
+  if (ranges_overlap(x, dinv, M))
+    throw std::runtime_error("pcg: x overlaps dinv (x is updated in place)");
+
+  PcgWorkspace own(exec);
+  PcgWorkspace& w = workspace ? *workspace : own;
+  const bool x_aligned = is_aligned16(x);
+  const bool dinv_aligned = is_aligned16(dinv);
+  w.ensure(M, N_padded, kmax, len, !x_aligned, !dinv_aligned);
+  if (opt.time_spmv)
+    w.reserve_timing(kmax);
+
+  SolveStream guard(exec, w.stream); // every launch below goes to w.stream
+
+  throw_on_error(spmv_hip_pcg_ws_reset(w.ws, rtol, nullptr),
+                 "spmv_hip_pcg_ws_reset");
+  double* partials = nullptr;
+  throw_on_error(spmv_hip_pcg_ws_partials(w.ws, &partials),
+                 "spmv_hip_pcg_ws_partials");
+
+  double* const xi = x_aligned ? x : w.x;
+  const double* di = dinv;
+  if (!dinv_aligned) { // the streaming kernels load 16 bytes at a time
+    exec.copy<double>(w.dinv, dinv, M);
+    di = w.dinv;
+  }
+  // the ghost tail of p is defined here instead of relying on fresh pages
+  if (N_padded > M)
+    exec.memset<double>(w.p + M, 0, N_padded - M);
+  exec.memset<double>(w.dot2, 0, len);
+  // r = b, x0 = 0, p = dinv*b, partials of r.z and r.r: one pass
+  throw_on_error(spmv_hip_pcg_init_f64(ctx, w.ws, M, b, di, w.r, w.p, xi,
+                                       nullptr),
+                 "spmv_hip_pcg_init_f64");
+  w.flags[0] = 0;
+  w.flags[1] = -1;
+
+  // the state words alone (h == nullptr), or with the history of pairs
+  auto read = [&](double* h, size_t n) {
+    throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, h, n, nullptr),
+                   "spmv_hip_pcg_ws_read_async");
+  };
+
+  // {rz0, rr0}: one all-reduce of 2 doubles
+  throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, 0, nullptr),
+                 "spmv_hip_pcg_reduce_rz_rr");
+  comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, 0,
+                          "spmv_hip_pcg_ws_rz_rr"),
+                  2, w.stream);
+
+  const bool consume = opt.consumer_reductions && comm.size() == 1;
+  std::vector<void*>& timing_ev = w.timing_ev;
+  LaggingPoll poll(exec, w, opt.poll_every, kmax);
+  int k = 0;
+  while (k < kmax && !poll.stopped) {
+    ++k;
+    col_l2g->update(w.p); // starts on the side stream
+    void* ev1 = nullptr;
+    if (opt.time_spmv) {
+      ev1 = timing_ev[2 * (size_t)(k - 1) + 1];
+      exec.record_event(timing_ev[2 * (size_t)(k - 1)], w.stream);
+    }
+    // Ap = A p with the p.Ap partials produced by the SpMV kernels themselves
+    // (local block's share + remote block's share) where they can
+    const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
+    if (!fused)
+      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, w.p, w.Ap, partials,
+                                              nullptr),
+                     "spmv_hip_dot_partial_f64");
+    if (consume) {
+      // one rank: the update kernels add the partials themselves
+      throw_on_error(spmv_hip_pcg_update_r_cs_f64(ctx, w.ws, k, M, w.Ap, di,
+                                                  w.r, fused ? w.dot2 : nullptr,
+                                                  nullptr),
+                     "spmv_hip_pcg_update_r_cs_f64");
+      throw_on_error(spmv_hip_pcg_update_xp_cs_f64(ctx, w.ws, k, M, w.r, di, xi,
+                                                   w.p, nullptr),
+                     "spmv_hip_pcg_update_xp_cs_f64");
+    } else {
+      if (fused)
+        throw_on_error(spmv_hip_pcg_reduce_pAp2(ctx, w.ws, k, w.dot2, nullptr),
+                       "spmv_hip_pcg_reduce_pAp2");
+      else
+        throw_on_error(spmv_hip_pcg_reduce_pAp(ctx, w.ws, k, nullptr),
+                       "spmv_hip_pcg_reduce_pAp");
+      comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_pAp, k,
+                              "spmv_hip_pcg_ws_pAp"),
+                      1, w.stream);
+      throw_on_error(spmv_hip_pcg_update_r_f64(ctx, w.ws, k, M, w.Ap, di, w.r,
+                                               nullptr),
+                     "spmv_hip_pcg_update_r_f64");
+      throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, k, nullptr),
+                     "spmv_hip_pcg_reduce_rz_rr");
+      comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, k,
+                              "spmv_hip_pcg_ws_rz_rr"),
+                      2, w.stream); // rz[k] and rr[k] at once
+      throw_on_error(spmv_hip_pcg_update_xp_f64(ctx, w.ws, k, M, w.r, di, xi,
+                                                w.p, nullptr),
+                     "spmv_hip_pcg_update_xp_f64");
+    }
+
+    poll.step(k, read);
+  }
+
+  // final state: {done, kstop} and the history of pairs {rz[k], rr[k]}
+  const std::vector<double> zr
+      = read_history(spmv_hip_pcg_ws_capacity, w.ws, kmax, 2, read);
+  if (xi != x)
+    exec.copy<double>(x, xi, M);
+  exec.synchronize_stream(w.stream);
+
+  if (stats) {
+    *stats = CgStats();
+    if (opt.time_spmv)
+      sum_spmv_times(ctx, timing_ev, 2 * (size_t)k, *stats);
+  }
+
+  auto rr_at = [&](int j) { return zr[2 * (size_t)j + 1]; };
+  int k_final;
+  if (w.flags[0] != 0)
+    k_final = w.flags[1];
+  else if (rr_at(0) == 0.0)
+    k_final = 0; // (kmax == 0: no kernel ran to say so)
+  else // `done` is raised by the first kernel of the NEXT iteration
+    k_final = first_k_below(rr_at, k, rtol);
+  write_history(rnorm_history, k_final, rr_at);
+  return k_final;
+}
+
+// ---------------------------------------------------------------------------
+// Chebyshev polynomial preconditioner: see cg.h.  pcg_chebyshev per iteration
+// (compute stream), on the scalars and reducers of pcg():
+//     halo start of p ; Ap = A p (+ fused p.Ap share)
+//     reduce_pAp ; all-reduce of 1
+//     cheb_update_r   (r ; partials of r.r ; step 0 of M: d, z)
+//     degree - 1 times:  halo start of z ; w = A z ; cheb_step
+//                        (the last one: partials of r.z, no d)
+//     reduce_rz_rr ; all-reduce of 2
+//     cheb_update_xp  (x ; stop test ; p)
+// degree SpMVs + degree + 1 streaming launches + 2 reducers; beside the SpMVs
+// 7 (degree - 1) + 11 vector passes with a dinv for degree >= 2 (update_r: Ap,
+// r, dinv in, r, d, z out; a step: w, r, dinv, d, z in, d, z out, the last one
+// without d out; update_xp: z, x, p in, x, p out), 10 for degree 1.
+// ---------------------------------------------------------------------------
+void chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
+                            double* b)
+{
+  if (degree < 1 || degree > kChebyshevMaxDegree)
+    throw std::runtime_error(
+        "spmv::chebyshev_coefficients - Error: degree must be 1.."
+        + std::to_string(kChebyshevMaxDegree));
+  if (!std::isfinite(lmin) || !std::isfinite(lmax) || !(lmin > 0.0)
+      || !(lmin < lmax))
+    throw std::runtime_error("spmv::chebyshev_coefficients - Error: bounds must "
+                             "be finite with 0 < lmin < lmax");
+  if (!a || !b)
+    throw std::runtime_error("spmv::chebyshev_coefficients - Error: NULL output");
+  // (volatile: every operation below is one fp64 rounding, whatever the
+  // compiler's contraction setting)
+  volatile double theta = 0.5 * (lmax + lmin);
+  volatile double delta = 0.5 * (lmax - lmin);
+  volatile double sigma = theta / delta;
+  volatile double rho = 1.0 / sigma;
+  a[0] = 0.0;
+  b[0] = 1.0 / theta;
+  for (int j = 1; j < degree; ++j) {
+    volatile double two_sigma = 2.0 * sigma;
+    volatile double den = two_sigma - rho;
+    volatile double rho_new = 1.0 / den;
+    volatile double aj = rho_new * rho;
+    volatile double two_rho = 2.0 * rho_new;
+    a[j] = aj;
+    b[j] = two_rho / delta;
+    rho = rho_new;
+  }
+}
+
+ChebyshevWorkspace::~ChebyshevWorkspace() { release(); }
+
+void ChebyshevWorkspace::release()
+{
+  release_common();
+  spmv_hip_pcg_ws_destroy(ws);
+  ws = nullptr;
+  free_vectors({&r, &Ap, &d, &w, &p, &z, &x, &dinv, &dot2});
+  kmax_cap = -1;
+  m_cap = n_cap = x_cap = dinv_cap = -1;
+}
+
+void ChebyshevWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
+                                bool need_x, bool need_dinv)
+{
+  open(2);
+  if (!dot2)
+    dot2 = _exec.alloc<double>(len);
+  regrow_scalars(_exec.context(), ws, kmax_cap, kmax);
+  regrow(m_cap, M, {&r, &Ap, &d, &w});
+  if (need_x)
+    regrow(x_cap, M, {&x});
+  if (need_dinv)
+    regrow(dinv_cap, M, {&dinv});
+  regrow(n_cap, N_padded, {&p, &z});
+}
+void chebyshev_apply(HipExecutor& exec, const Matrix<double>& A,
+                     const double* r, double* z, const double* dinv, int degree,
+                     double lmin, double lmax, ChebyshevWorkspace* workspace)
+{
+  double ca[kChebyshevMaxDegree], cb[kChebyshevMaxDegree];
+  chebyshev_coefficients(degree, lmin, lmax, ca, cb);
+  const Dims dims = check_problem("chebyshev_apply", A, 0);
+  const int64_t M = dims.M, N_padded = dims.N_padded;
+  const std::shared_ptr<const L2GMap>& col_l2g = dims.col_l2g;
+  if (ranges_overlap(z, r, M))
+    throw std::runtime_error("chebyshev_apply: z overlaps r");
+  if (dinv && ranges_overlap(z, dinv, M))
+    throw std::runtime_error("chebyshev_apply: z overlaps dinv");
+  spmv_hip_ctx* ctx = exec.context();
+  const int len = dot_partials_len(ctx);
+
+  ChebyshevWorkspace own(exec);
+  ChebyshevWorkspace& w = workspace ? *workspace : own;
+  const bool dinv_aligned = is_aligned16(dinv);
+  w.ensure(M, N_padded, 0, len, false, !dinv_aligned);
+
+  // everything on the executor's current stream, nothing waits
+  const double* ri = r;
+  if (!is_aligned16(r)) { // the streaming kernels load 16 bytes at a time
+    exec.copy<double>(w.r, r, M);
+    ri = w.r;
+  }
+  const double* di = dinv;
+  if (dinv && !dinv_aligned) {
+    exec.copy<double>(w.dinv, dinv, M);
+    di = w.dinv;
+  }
+  if (N_padded > M)
+    exec.memset<double>(w.z + M, 0, N_padded - M);
+  throw_on_error(spmv_hip_cheb_apply0_f64(ctx, M, cb[0], ri, di,
+                                          degree > 1 ? w.d : nullptr, w.z,
+                                          nullptr),
+                 "spmv_hip_cheb_apply0_f64");
+  for (int j = 1; j < degree; ++j) {
+    col_l2g->update(w.z);
+    A.mult(w.z, w.w);
+    throw_on_error(spmv_hip_cheb_step_f64(ctx, nullptr, M, ca[j], cb[j],
+                                          j == degree - 1, w.w, ri, di, w.d, w.z,
+                                          nullptr),
+                   "spmv_hip_cheb_step_f64");
+  }
+  exec.copy<double>(z, w.z, M);
+  if (!workspace) // its vectors go away with it
+    exec.synchronize_stream(exec.get_stream());
+}
+
+int pcg_chebyshev(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+                  const double* b, double* x, const double* dinv, int degree,
+                  double lmin, double lmax, int kmax, double rtol,
+                  std::vector<double>* rnorm_history, const CgOptions* options,
+                  CgStats* stats, ChebyshevWorkspace* workspace)
+{
+  double ca[kChebyshevMaxDegree], cb[kChebyshevMaxDegree];
+  chebyshev_coefficients(degree, lmin, lmax, ca, cb);
+  const Dims dims = check_problem("pcg_chebyshev", A, kmax);
+  const int64_t M = dims.M, N_padded = dims.N_padded;
+  const std::shared_ptr<const L2GMap>& col_l2g = dims.col_l2g;
+  const CgOptions opt = options ? *options : CgOptions();
+  spmv_hip_ctx* ctx = exec.context();
+  const int len = dot_partials_len(ctx);
+  // x is the iterate from the first kernel on: it cannot share b or dinv
+  if (ranges_overlap(x, b, M))
+    throw std::runtime_error(
+        "pcg_chebyshev: x overlaps b (x is updated in place)");
+  if (dinv && ranges_overlap(x, dinv, M))
+    throw std::runtime_error(
+        "pcg_chebyshev: x overlaps dinv (x is updated in place)");
+
+  ChebyshevWorkspace own(exec);
+  ChebyshevWorkspace& w = workspace ? *workspace : own;
+  const bool x_aligned = is_aligned16(x);
+  const bool dinv_aligned = is_aligned16(dinv);
+  w.ensure(M, N_padded, kmax, len, !x_aligned, !dinv_aligned);
+  if (opt.time_spmv)
+    w.reserve_timing(kmax * degree);
+
+  SolveStream guard(exec, w.stream); // every launch below goes to w.stream
+
+  throw_on_error(spmv_hip_pcg_ws_reset(w.ws, rtol, nullptr),
+                 "spmv_hip_pcg_ws_reset");
+  double* partials = nullptr;
+  throw_on_error(spmv_hip_pcg_ws_partials(w.ws, &partials),
+                 "spmv_hip_pcg_ws_partials");
+
+  double* const xi = x_aligned ? x : w.x;
+  const double* di = dinv;
+  if (dinv && !dinv_aligned) { // the streaming kernels load 16 bytes at a time
+    exec.copy<double>(w.dinv, dinv, M);
+    di = w.dinv;
+  }
+  // the ghost tails of p and z are defined here instead of relying on fresh
+  // pages
+  if (N_padded > M) {
+    exec.memset<double>(w.p + M, 0, N_padded - M);
+    exec.memset<double>(w.z + M, 0, N_padded - M);
+  }
+  exec.memset<double>(w.dot2, 0, len);
+  double* const dvec = degree > 1 ? w.d : nullptr; // degree 1: no d
+
+  std::vector<void*>& timing_ev = w.timing_ev;
+  size_t ev_next = 0; // two events per timed SpMV
+  // steps 1 .. degree - 1 of z = M(r); the last one leaves the r.z partials
+  auto cheb_steps = [&](bool timed) {
+    for (int j = 1; j < degree; ++j) {
+      col_l2g->update(w.z); // starts on the side stream
+      if (timed)
+        exec.record_event(timing_ev[ev_next], w.stream);
+      A.mult(w.z, w.w);
+      if (timed) {
+        exec.record_event(timing_ev[ev_next + 1], w.stream);
+        ev_next += 2;
+      }
+      throw_on_error(spmv_hip_cheb_step_f64(ctx, w.ws, M, ca[j], cb[j],
+                                            j == degree - 1, w.w, w.r, di, w.d,
+                                            w.z, nullptr),
+                     "spmv_hip_cheb_step_f64");
+    }
+  };
+
+  // r = b, x0 = 0, partials of r.r, step 0 of M: one pass; then the rest of
+  // z0 = M(r0) and p1 = z0
+  throw_on_error(spmv_hip_cheb_init_f64(ctx, w.ws, M, cb[0], b, di, w.r, xi,
+                                        dvec, w.z, nullptr),
+                 "spmv_hip_cheb_init_f64");
+  cheb_steps(false);
+  exec.copy<double>(w.p, w.z, M);
+  w.flags[0] = 0;
+  w.flags[1] = -1;
+
+  // the state words alone (h == nullptr), or with the history of pairs
+  auto read = [&](double* h, size_t n) {
+    throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, h, n, nullptr),
+                   "spmv_hip_pcg_ws_read_async");
+  };
+
+  // {rz0, rr0}: one all-reduce of 2 doubles
+  throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, 0, nullptr),
+                 "spmv_hip_pcg_reduce_rz_rr");
+  comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, 0,
+                          "spmv_hip_pcg_ws_rz_rr"),
+                  2, w.stream);
+
+  LaggingPoll poll(exec, w, opt.poll_every, kmax);
+  int k = 0;
+  while (k < kmax && !poll.stopped) {
+    ++k;
+    col_l2g->update(w.p); // starts on the side stream
+    void* ev1 = nullptr;
+    if (opt.time_spmv) {
+      ev1 = timing_ev[ev_next + 1];
+      exec.record_event(timing_ev[ev_next], w.stream);
+      ev_next += 2;
+    }
+    // Ap = A p with the p.Ap partials produced by the SpMV kernels themselves
+    // (local block's share + remote block's share) where they can
+    const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
+    if (!fused) {
+      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, w.p, w.Ap, partials,
+                                              nullptr),
+                     "spmv_hip_dot_partial_f64");
+      throw_on_error(spmv_hip_pcg_reduce_pAp(ctx, w.ws, k, nullptr),
+                     "spmv_hip_pcg_reduce_pAp");
+    } else {
+      throw_on_error(spmv_hip_pcg_reduce_pAp2(ctx, w.ws, k, w.dot2, nullptr),
+                     "spmv_hip_pcg_reduce_pAp2");
+    }
+    comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_pAp, k, "spmv_hip_pcg_ws_pAp"),
+                    1, w.stream);
+    throw_on_error(spmv_hip_cheb_update_r_f64(ctx, w.ws, k, M, cb[0], w.Ap, di,
+                                              w.r, dvec, w.z, nullptr),
+                   "spmv_hip_cheb_update_r_f64");
+    cheb_steps(opt.time_spmv);
+    throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, k, nullptr),
+                   "spmv_hip_pcg_reduce_rz_rr");
+    comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, k,
+                            "spmv_hip_pcg_ws_rz_rr"),
+                    2, w.stream); // rz[k] and rr[k] at once
+    throw_on_error(spmv_hip_cheb_update_xp_f64(ctx, w.ws, k, M, w.z, xi, w.p,
+                                               nullptr),
+                   "spmv_hip_cheb_update_xp_f64");
+
+    poll.step(k, read);
+  }
+
+  // final state: {done, kstop} and the history of pairs {rz[k], rr[k]}
+  const std::vector<double> zr
+      = read_history(spmv_hip_pcg_ws_capacity, w.ws, kmax, 2, read);
+  if (xi != x)
+    exec.copy<double>(x, xi, M);
+  exec.synchronize_stream(w.stream);
+
+  if (stats) {
+    *stats = CgStats();
+    if (opt.time_spmv)
+      sum_spmv_times(ctx, timing_ev, ev_next, *stats);
+  }
+
+  auto rr_at = [&](int j) { return zr[2 * (size_t)j + 1]; };
+  int k_final;
+  if (w.flags[0] != 0)
+    k_final = w.flags[1];
+  else if (rr_at(0) == 0.0)
+    k_final = 0; // (kmax == 0: no kernel ran to say so)
+  else // `done` is raised by the first reducer of the NEXT iteration
+    k_final = first_k_below(rr_at, k, rtol);
+  write_history(rnorm_history, k_final, rr_at);
+  return k_final;
+}
+
+double lambda_max_estimate(const Comm& comm, HipExecutor& exec,
+                           const Matrix<double>& A, const double* dinv,
+                           const double* v0, int steps)
+{
+  if (steps < 1)
+    throw std::runtime_error("spmv::lambda_max_estimate - Error: steps < 1");
+  const Dims dims = check_problem("lambda_max_estimate", A, 0);
+  const int64_t M = dims.M, N_padded = dims.N_padded;
+  const std::shared_ptr<const L2GMap>& col_l2g = dims.col_l2g;
+  spmv_hip_ctx* ctx = exec.context();
+  const int len = dot_partials_len(ctx);
+
+  // q, u: local; v: padded (the SpMV reads it); 3 scalars; one partial array
+  // (everything is allocated before the first reduction)
+  struct Buffers {
+    HipExecutor& exec;
+    double *q = nullptr, *u = nullptr, *v = nullptr, *s = nullptr,
+           *partials = nullptr;
+    ~Buffers()
+    {
+      try {
+        exec.synchronize_stream(exec.get_stream());
+        for (double* ptr : {q, u, v, s, partials})
+          exec.free(ptr);
+      } catch (...) {
+      }
+    }
+  } m{exec};
+  m.q = exec.alloc<double>(M);
+  m.u = exec.alloc<double>(M);
+  m.v = exec.alloc<double>(N_padded);
+  m.s = exec.alloc<double>(3);
+  m.partials = exec.alloc<double>(len);
+  if (N_padded > M)
+    exec.memset<double>(m.v + M, 0, N_padded - M);
+
+  void* st = exec.get_stream();
+  // s[i] = the global dot product of the i-th pair; ONE host wait for all
+  auto dots = [&](std::initializer_list<std::pair<const double*, const double*>>
+                      pairs,
+                  double* out) {
+    int i = 0;
+    for (const auto& pr : pairs) {
+      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, pr.first, pr.second,
+                                              m.partials, nullptr),
+                     "spmv_hip_dot_partial_f64");
+      throw_on_error(spmv_hip_reduce_partials_f64(ctx, m.partials, m.s + i,
+                                                  nullptr),
+                     "spmv_hip_reduce_partials_f64");
+      ++i;
+    }
+    comm.reduce_sum(m.s, pairs.size(), st);
+    exec.copy_to<double>(out, exec.get_host(), m.s, pairs.size()); // waits
+  };
+  auto scale = [&](double s, const double* dv, const double* in, double* out) {
+    throw_on_error(spmv_hip_cheb_scale_f64(ctx, M, s, dv, in, out, nullptr),
+                   "spmv_hip_cheb_scale_f64");
+  };
+
+  double h[3] = {0.0, 0.0, 0.0};
+  dots({{v0, v0}}, h);
+  if (!(h[0] > 0.0) || !std::isfinite(h[0]))
+    throw std::runtime_error(
+        "spmv::lambda_max_estimate - Error: v0 . v0 is not a positive number");
+  scale(std::sqrt(h[0]), nullptr, v0, m.q); // q = v0 / ||v0||
+  double lambda = 0.0;
+  for (int it = 0; it < steps; ++it) {
+    scale(1.0, dinv, m.q, m.v); // v = dinv*q
+    col_l2g->update(m.v);
+    A.mult(m.v, m.u); // u = A v
+    dots({{m.v, m.u}, {m.v, m.q}, {m.u, m.u}}, h);
+    lambda = h[0] / h[1];
+    if (!(h[2] > 0.0) || !std::isfinite(h[2]))
+      throw std::runtime_error(
+          "spmv::lambda_max_estimate - Error: the iteration broke down "
+          "(||A v|| is not a positive number)");
+    scale(std::sqrt(h[2]), nullptr, m.u, m.q); // q = u / ||u||
+  }
+  return lambda;
+}
+
+} // namespace spmv

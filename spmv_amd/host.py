@@ -762,21 +762,33 @@ def read_petsc_binary_rows(filename, rank, size):
                 values=va, col_ghosts=gh)
 
 
-class CgWorkspace:
-    """spmv::CgWorkspace: work vectors kept across cg() calls."""
+class _Workspace:
+    """A solver's work vectors, kept across calls: the handle behind the
+    spmvh_<_prefix>_workspace_create / _destroy symbols."""
+    _prefix = None
 
     def __init__(self, exec_):
         h = vp()
-        call("spmvh_cg_workspace_create", exec_.h, C.byref(h))
+        call(f"spmvh_{self._prefix}_workspace_create", exec_.h, C.byref(h))
         self.h = h
-
-    def reserve_timing(self, iterations):
-        call("spmvh_cg_workspace_reserve_timing", self.h, int(iterations))
 
     def close(self):
         if self.h:
-            call("spmvh_cg_workspace_destroy", self.h)
+            call(f"spmvh_{self._prefix}_workspace_destroy", self.h)
             self.h = None
+
+
+class _TimedWorkspace(_Workspace):
+    def reserve_timing(self, count):
+        """Creates the events of a time_spmv solve ahead of it: `count`
+        iterations (ChebyshevWorkspace: SpMVs, iterations * degree)."""
+        call(f"spmvh_{self._prefix}_workspace_reserve_timing", self.h,
+             int(count))
+
+
+class CgWorkspace(_TimedWorkspace):
+    """spmv::CgWorkspace: work vectors kept across cg() calls."""
+    _prefix = "cg"
 
 
 def cg_ex(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, workspace=None,
@@ -798,18 +810,9 @@ def cg_ex(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, workspace=None,
             n.value)
 
 
-class CgBlockWorkspace:
+class CgBlockWorkspace(_Workspace):
     """spmv::CgBlockWorkspace: work vectors kept across cg_block() calls."""
-
-    def __init__(self, exec_):
-        h = vp()
-        call("spmvh_cg_block_workspace_create", exec_.h, C.byref(h))
-        self.h = h
-
-    def close(self):
-        if self.h:
-            call("spmvh_cg_block_workspace_destroy", self.h)
-            self.h = None
+    _prefix = "cg_block"
 
 
 def cg_block(comm, exec_, A, b_ptr, x_ptr, nrhs, kmax, rtol, workspace=None,
@@ -839,21 +842,9 @@ def jacobi_inverse(exec_, d_ptr, dinv_ptr, n):
     call("spmvh_jacobi_inverse", exec_.h, d_ptr, dinv_ptr, int(n))
 
 
-class PcgWorkspace:
+class PcgWorkspace(_TimedWorkspace):
     """spmv::PcgWorkspace: work vectors kept across pcg() calls."""
-
-    def __init__(self, exec_):
-        h = vp()
-        call("spmvh_pcg_workspace_create", exec_.h, C.byref(h))
-        self.h = h
-
-    def reserve_timing(self, iterations):
-        call("spmvh_pcg_workspace_reserve_timing", self.h, int(iterations))
-
-    def close(self):
-        if self.h:
-            call("spmvh_pcg_workspace_destroy", self.h)
-            self.h = None
+    _prefix = "pcg"
 
 
 def pcg(comm, exec_, A, b_ptr, x_ptr, dinv_ptr, kmax, rtol, workspace=None,
@@ -887,22 +878,10 @@ def chebyshev_coefficients(degree, lmin, lmax):
     return a, b
 
 
-class ChebyshevWorkspace:
+class ChebyshevWorkspace(_TimedWorkspace):
     """spmv::ChebyshevWorkspace: work vectors kept across pcg_chebyshev() and
     chebyshev_apply() calls."""
-
-    def __init__(self, exec_):
-        h = vp()
-        call("spmvh_chebyshev_workspace_create", exec_.h, C.byref(h))
-        self.h = h
-
-    def reserve_timing(self, spmvs):
-        call("spmvh_chebyshev_workspace_reserve_timing", self.h, int(spmvs))
-
-    def close(self):
-        if self.h:
-            call("spmvh_chebyshev_workspace_destroy", self.h)
-            self.h = None
+    _prefix = "chebyshev"
 
 
 def chebyshev_apply(exec_, A, r_ptr, z_ptr, dinv_ptr, degree, lmin, lmax,
@@ -947,21 +926,9 @@ def lambda_max_estimate(comm, exec_, A, dinv_ptr, v0_ptr, steps):
     return lam.value
 
 
-class BicgstabWorkspace:
+class BicgstabWorkspace(_TimedWorkspace):
     """spmv::BicgstabWorkspace: work vectors kept across bicgstab() calls."""
-
-    def __init__(self, exec_):
-        h = vp()
-        call("spmvh_bicgstab_workspace_create", exec_.h, C.byref(h))
-        self.h = h
-
-    def reserve_timing(self, iterations):
-        call("spmvh_bicgstab_workspace_reserve_timing", self.h, int(iterations))
-
-    def close(self):
-        if self.h:
-            call("spmvh_bicgstab_workspace_destroy", self.h)
-            self.h = None
+    _prefix = "bicgstab"
 
 
 def bicgstab(comm, exec_, A, b_ptr, x_ptr, dinv_ptr, kmax, rtol, ws=None,

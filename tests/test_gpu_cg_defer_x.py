@@ -204,6 +204,27 @@ def test_workspace_grows_between_solves(comm, problems):
     ws.close()
 
 
+def test_workspace_kept_by_a_smaller_solve_and_p2_brought_back(comm, problems,
+                                                               exec_):
+    """One workspace through n = 11, n = 8 (smaller: nothing regrows), n = 11
+    without defer_x, n = 11 with it (the second p buffer after a solve that
+    did not use it).  kmax = 7: the loop ends on a P step and the flush runs.
+    Every solve equals the same solve on a fresh workspace, x and history."""
+    big, small = problems["poisson11"], _Problem(exec_, comm, "poisson8")
+    ws = host.CgWorkspace(exec_)
+    try:
+        for P, defer in ((big, True), (small, True), (big, False), (big, True)):
+            fresh = host.CgWorkspace(exec_)
+            want = _solve(comm, P, 7, 0.0, defer, ws=fresh)
+            fresh.close()
+            got = _solve(comm, P, 7, 0.0, defer, ws=ws)
+            _same(want, got, (P.N, defer))
+            assert got[0] == 7 and len(got[1]) == 8
+    finally:
+        ws.close()
+        small.close()
+
+
 @pytest.mark.parametrize("shape", ["poisson11", "banded4097"])
 def test_fallbacks_keep_the_bits(comm, problems, shape):
     """Where the deferred sequence does not apply the parent's runs, with the

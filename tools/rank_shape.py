@@ -102,7 +102,7 @@ def model(P, n=512, steps=100, plain=True, cm="p2p_nonblocking", symmetric=False
                 "ms_per_iteration": wall / steps * 1e3,
                 "local_spmv_ms": spmv_ms / max(spmv_n, 1),
                 # SpMV local + remote, p.Ap reducer, r update, r.r reducer,
-                # x / p update (host/cg.cpp:271-298); one rank: 3
+                # x / p update (the loop of cg() in host/cg.cpp); one rank: 3
                 "launches_per_iteration": 5 + (1 if blocks["remote"][2] > 0 else 0),
                 "collectives_per_iteration": 3,  # halo exchange + 2 all-reduces
                 "finite": bool(all(h == h for h in hist)),
