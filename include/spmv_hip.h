@@ -401,8 +401,28 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
                           int* value);
 
 /* out = alpha * A * in + beta * out  (CSRSpMV<T>::run, csr_kernels.cpp:20-52),
- * every row summed left to right, mul and add rounded separately: bit-identical
- * to the reference loops on finite data, with ONE defined difference:
+ * every row summed left to right, mul and add rounded separately: the bits of
+ * the reference loops, special values included (tests/test_gpu_special_values.py
+ * holds every plan form to this):
+ *   - only stored entries take part: an absent entry of a form stored by
+ *     offset, a padded slot, a lane past the row's end and a load clamped into
+ *     range contribute nothing -- not 0 * x, which is NaN under an Inf or NaN x;
+ *   - NaN and Inf propagate as in the loop: a stored 0.0 under an Inf x gives
+ *     NaN, a NaN in x reaches every row (and the fused dot) that reads it.
+ *     NaNs are one class: sign and payload of a generated NaN are not defined;
+ *   - the sign of a zero follows the loop (the sum starts at +0.0, symmetric
+ *     storage: at diagonal[i] * in[i]), with the beta == 0 note below;
+ *   - the left-to-right order holds through overflow: a partial sum that
+ *     reaches +-Inf stays there, whatever another order would give;
+ *   - subnormals: fp64 and fp32 products and sums are not flushed (gradual
+ *     underflow, as the reference on x86-64); the mixed f32f64 kernels widen
+ *     fp32-subnormal values exactly.
+ * The order-tolerant kernels -- SPMV_HIP_ALGO_VECTOR and the atomic symmetric
+ * kernels (plan_get "sym_det" == 0 without the lattice form) -- sum in another
+ * order: they promise the rounding bound on rows that are finite in the loop
+ * and a non-finite result on the others, not the bits, the kind of non-finite
+ * value or the sign of a zero.
+ * TWO defined differences to the reference loops:
  *   beta == 0 means `out` is WRITE-ONLY -- the kernels store alpha*sum and never
  *   read out[i] (the reference computes alpha*sum + 0*out[i] on a
  *   buffer cg.cpp:40 never initialises, so a NaN/Inf there would poison it).
@@ -410,6 +430,15 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
  *   "+ 0*out[i]" turns it into +0.0 (for out[i] >= +0) while this library
  *   returns -0.0.  The two compare equal (np.array_equal, ==); only the sign
  *   bit differs, and only for rows whose sum is an exact negative zero.
+ *   SPMV_HIP_ALGO_ROWLIST at beta == 1 (the remote block of a partitioned matrix,
+ *   once per CG iteration) walks the listed rows only: a row WITHOUT entries
+ *   keeps out[i], where the loop computes alpha*0 + out[i].  The two differ only
+ *   where out[i] is an exact -0.0 (the loop gives +0.0 for alpha*0 == +0.0) and
+ *   for a non-finite alpha (the loop gives NaN); they compare equal otherwise.
+ *   plan_set "rowlist_exact" 1 makes the launch go over all rows at beta == 1
+ *   too and removes the difference.  Every other beta, every other kernel and a
+ *   block without any entry (num_non_zeros == 0, spmv and spmm) follow the loop:
+ *   a row without entries gets alpha*0 + beta*out[i], alpha*0 at beta == 0.
  * dot_partials (may be NULL; general fp64 and symmetric fp64): the launch also
  * leaves spmv_hip_dot_partials_len() partial sums of in . (alpha * A * in),
  * the block's share of p.Ap in CG (cg.cpp:63). */

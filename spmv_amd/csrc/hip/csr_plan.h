@@ -241,6 +241,18 @@ __global__ __launch_bounds__(kBlock) void scale_kernel(int64_t n, T beta,
     out[i] = (beta == T(0)) ? T(0) : beta * out[i];
 }
 
+// rows without entries: the loop's alpha*0 + beta*out (`zero` = alpha*0; it
+// differs from beta*out in the sign of a zero, and is NaN for a non-finite
+// alpha); beta == 0: alpha*0 itself, out is not read
+template <typename T>
+__global__ __launch_bounds__(kBlock) void empty_rows_kernel(int64_t n, T zero, T beta,
+                                                            T* __restrict__ out)
+{
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = (beta == T(0)) ? zero : zero + beta * out[i];
+}
+
 // ---------------------------------------------------------------------------
 // Plan = CSRSpMV::_aux_data
 // ---------------------------------------------------------------------------
@@ -417,6 +429,10 @@ struct spmv_hip_csr_plan {
   int mv_form = 0;
   int mv_native = 1;
   int32_t* row_list = nullptr; // ROWLIST: device list of non-empty rows
+  // ROWLIST at beta == 1 leaves the rows without entries alone (a -0.0 there
+  // stays -0.0 where the loop's `+ alpha*0` gives +0.0); 1: the pass over all
+  // rows at beta == 1 too (plan_set "rowlist_exact")
+  int rowlist_exact = 0;
   int32_t num_listed = 0;
   int nt_store = 0; // non-temporal y stores
   int plan_us = 0;  // wall time of plan creation (analysis kernels included)

@@ -441,18 +441,41 @@ __global__ __launch_bounds__(kBlock) void csr_scalar_kernel(
 // ROWLIST kernel: for blocks whose rows are mostly empty (the "remote" block
 // of a row-partitioned matrix, Matrix.cpp:354-355: only boundary rows touch
 // ghost columns).  The plan holds the compacted list of non-empty rows; one
-// lane per listed row, reference order.  `out` has already been scaled by
-// beta for ALL rows (a no-op for the beta == 1 the reference uses here,
-// Matrix.cpp:508,529,551), so out[r] = alpha*sum + out[r] rounds exactly like
-// alpha*sum + beta*out[r].  With DOT the kernel emits the partials of
-// sum_r in[r] * (alpha*sum_r): the block's own share of p.Ap.
+// lane per listed row, reference order.  csr_rowlist_prep_kernel has gone over
+// ALL rows first: a listed row holds beta*out[r], so out[r] = alpha*sum +
+// out[r] rounds exactly like alpha*sum + beta*out[r] (beta == 0, `assign`:
+// alpha*sum itself is stored); a row without entries holds the loop's alpha*0 +
+// beta*out[r] -- alpha*0 itself at beta == 0 -- which differs from beta*out[r]
+// in the sign of a zero.  At beta == 1, what the reference uses here
+// (Matrix.cpp:508,529,551), there is NO such pass: the kernel walks the listed
+// rows only and a row without entries keeps out[r] (a -0.0 there stays -0.0
+// where the loop gives +0.0, spmv_hip.h) -- unless plan_set "rowlist_exact".
+// With DOT the kernel emits the partials of sum_r in[r] * (alpha*sum_r): the
+// block's own share of p.Ap.
 // ---------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kBlock) void csr_rowlist_prep_kernel(
+    int64_t n, const int32_t* __restrict__ rowptr, T zero, T beta,
+    T* __restrict__ out)
+{
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const bool empty = rowptr[i] == rowptr[i + 1];
+    if (beta == T(0))
+      out[i] = empty ? zero : T(0);
+    else if (empty)
+      out[i] = zero + beta * out[i];
+    else if (beta != T(1))
+      out[i] = beta * out[i];
+  }
+}
+
 template <typename TV, typename T, bool DOT>
 __global__ __launch_bounds__(kBlock) void csr_rowlist_kernel(
     int32_t num_listed, const int32_t* __restrict__ rows,
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
     const TV* __restrict__ values, T alpha, const T* __restrict__ in,
-    T* __restrict__ out, DotOut dot)
+    bool assign, T* __restrict__ out, DotOut dot)
 {
   __shared__ double s_red[kBlock / 64];
   double dot_acc = 0.0;
@@ -463,7 +486,7 @@ __global__ __launch_bounds__(kBlock) void csr_rowlist_kernel(
     for (int32_t j = rowptr[i]; j < rowptr[i + 1]; ++j)
       sum += (T)values[j] * in[colind[j]];
     const T c = alpha * sum;
-    out[i] = c + out[i];
+    out[i] = assign ? c : c + out[i];
     if constexpr (DOT)
       dot_acc += (double)in[i] * (double)c;
   }
@@ -791,20 +814,17 @@ int launch_rowlist(const spmv_hip_csr_plan* pl, hipStream_t st,
                    DotOut dot)
 {
   const int n = pl->num_rows;
-  if (beta != T(1)) { // all rows: out = beta*out (0 without reading it)
-    if (beta == T(0)) {
-      SPMV_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(T) * (size_t)n, st));
-    } else {
-      const int grid = spmv_grid_for(pl->ctx, n, kBlock);
-      hipLaunchKernelGGL((scale_kernel<T>), dim3(grid), dim3(kBlock), 0, st,
-                         (int64_t)n, beta, out);
-      SPMV_CHECK_LAUNCH();
-    }
+  if (beta != T(1) || pl->rowlist_exact) {
+    // all rows: beta*out (never read at beta == 0), alpha*0 where a row is empty
+    const int grid = spmv_grid_for(pl->ctx, n, kBlock);
+    hipLaunchKernelGGL((csr_rowlist_prep_kernel<T>), dim3(grid), dim3(kBlock), 0,
+                       st, (int64_t)n, rowptr, alpha * T(0), beta, out);
+    SPMV_CHECK_LAUNCH();
   }
   const int grid = spmv_grid_for(pl->ctx, pl->num_listed, kBlock);
   hipLaunchKernelGGL((csr_rowlist_kernel<TV, T, DOT>), dim3(grid), dim3(kBlock), 0,
                      st, pl->num_listed, pl->row_list, rowptr, colind, values,
-                     alpha, in, out, dot);
+                     alpha, in, beta == T(0), out, dot);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -950,13 +970,13 @@ int spmv_hip_csr_spmv_f64(spmv_hip_ctx* ctx, const spmv_hip_csr_plan* plan,
                                  alpha, in, beta, out, dot);
   }
   if (num_non_zeros == 0) {
-    // empty general block: out = beta*out (csr_kernels.cpp:44-49 with an
-    // empty inner loop); CSRMatrix::mult skips the call entirely
+    // empty general block: out = alpha*0 + beta*out (csr_kernels.cpp:44-49
+    // with an empty inner loop); CSRMatrix::mult skips the call entirely
     // (csr_matrix.cpp:85), the executor keeps the arithmetic definition.
     SPMV_REQUIRE(dot_partials == nullptr);
     const int grid = spmv_grid_for(ctx, num_rows, kBlock);
-    hipLaunchKernelGGL((scale_kernel<double>), dim3(grid), dim3(kBlock), 0, st,
-                       (int64_t)num_rows, beta, out);
+    hipLaunchKernelGGL((empty_rows_kernel<double>), dim3(grid), dim3(kBlock), 0,
+                       st, (int64_t)num_rows, alpha * 0.0, beta, out);
     SPMV_CHECK_LAUNCH();
     return SPMV_HIP_OK;
   }
@@ -992,8 +1012,8 @@ int spmv_hip_csr_spmv_f32f64(spmv_hip_ctx* ctx, const spmv_hip_csr_plan* plan,
   if (num_non_zeros == 0) {
     SPMV_REQUIRE(dot_partials == nullptr);
     const int grid = spmv_grid_for(ctx, num_rows, kBlock);
-    hipLaunchKernelGGL((scale_kernel<double>), dim3(grid), dim3(kBlock), 0, st,
-                       (int64_t)num_rows, beta, out);
+    hipLaunchKernelGGL((empty_rows_kernel<double>), dim3(grid), dim3(kBlock), 0,
+                       st, (int64_t)num_rows, alpha * 0.0, beta, out);
     SPMV_CHECK_LAUNCH();
     return SPMV_HIP_OK;
   }
@@ -1034,8 +1054,8 @@ int spmv_hip_csr_spmv_f32(spmv_hip_ctx* ctx, const spmv_hip_csr_plan* plan,
                                 alpha, in, beta, out);
   if (num_non_zeros == 0) {
     const int grid = spmv_grid_for(ctx, num_rows, kBlock);
-    hipLaunchKernelGGL((scale_kernel<float>), dim3(grid), dim3(kBlock), 0, st,
-                       (int64_t)num_rows, beta, out);
+    hipLaunchKernelGGL((empty_rows_kernel<float>), dim3(grid), dim3(kBlock), 0,
+                       st, (int64_t)num_rows, alpha * 0.0f, beta, out);
     SPMV_CHECK_LAUNCH();
     return SPMV_HIP_OK;
   }

@@ -692,6 +692,9 @@ int spmv_hip_csr_plan_set(spmv_hip_csr_plan* plan, const char* key, int value)
   } else if (!strcmp(key, "sj_long_table")) {
     SPMV_REQUIRE(value == 0 || value == 1);
     plan->sj_long_table = value;
+  } else if (!strcmp(key, "rowlist_exact")) {
+    SPMV_REQUIRE(value == 0 || value == 1);
+    plan->rowlist_exact = value;
   } else if (!strcmp(key, "sj_blocks_per_cu")) {
     SPMV_REQUIRE(value >= 0 && value <= kBlocksPerCU);
     plan->sj_blocks_per_cu = value;
@@ -876,6 +879,8 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
                      && plan->sj_long_panels && plan->sj_lt_tab && plan->sj_long_table
                  ? 1
                  : 0;
+  else if (!strcmp(key, "rowlist_exact"))
+    *value = plan->rowlist_exact;
   else if (!strcmp(key, "sj_long_table_kib"))
     *value = (int)((plan->sj_lt_entries * 4 + (int64_t)plan->sj_lt_nsg * 16) / 1024);
   else if (!strcmp(key, "sj_long_rows"))

@@ -458,11 +458,11 @@ int run_block(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan, int32_t num_rows,
       plan->mv_form = 2;
     return rc;
   }
-  if (nnz == 0 && !plan->symmetric) { // out = beta * out, all k columns
+  if (nnz == 0 && !plan->symmetric) { // out = alpha*0 + beta*out, all k columns
     const int64_t n = (int64_t)num_rows * k;
     const int grid = spmv_grid_for(ctx, n, kBlock);
-    hipLaunchKernelGGL((scale_kernel<T>), dim3(grid), dim3(kBlock), 0, st, n, beta,
-                       out);
+    hipLaunchKernelGGL((empty_rows_kernel<T>), dim3(grid), dim3(kBlock), 0, st, n,
+                       alpha * T(0), beta, out);
     SPMV_CHECK_LAUNCH();
     plan->mv_form = 2;
     return SPMV_HIP_OK;
