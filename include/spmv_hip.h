@@ -965,6 +965,76 @@ int spmv_hip_cheb_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
                                 int64_t n, const double* z, double* x, double* p,
                                 void* stream);
 
+/* ---- Multicolour symmetric Gauss-Seidel (spmv::SgsPreconditioner, pcg_sgs) --------
+ * z = M^-1 r, M = (D + L) D^-1 (D + U) in the colour-major ordering of the rows
+ * of the local diagonal block, fp64, every product and sum a rounding of its own:
+ *   forward,  colours 0 .. C-1:  s = 0; for e in before(i): s = s + a_e * z[col_e]
+ *                                z_i = (r_i - s) * dinv_i
+ *   backward, colours C-2 .. 0:  t = 0; for e in after(i):  t = t + a_e * z[col_e]
+ *                                z_i = z_i - dinv_i * t
+ * before(i) / after(i): the off-diagonal entries of row i whose column wears a
+ * smaller / larger colour, ascending by column.  One launch per colour and
+ * direction (2C - 1); the order between colours is the stream's order alone.
+ *
+ * The plan is an upload of arrays the HOST built (host/sgs_build.h: colouring,
+ * colour-major copy, slices of 64 rows stored column-major, a list of long rows):
+ *   perm[pos]        the row at a colour-major position
+ *   color_start      num_colors + 1 positions; every colour is worn
+ *   dinv             1 / diagonal, by ROW
+ *   per part: color_slice / color_long (num_colors + 1), slice_pos0, slice_ptr
+ *   (slices + 1), len (by position; -1 = a long row), col / val (entry k of lane
+ *   l of slice s at slice_ptr[s] + 64 k + l), long_pos, long_ptr, long_col /
+ *   long_val (contiguous).  Columns are in the caller's numbering.
+ * plan_create checks every index a kernel will use (SPMV_HIP_EINVAL) and copies;
+ * the host arrays may go away afterwards.
+ *
+ * mcgs_apply: r, z device vectors of num_rows doubles, any alignment, not
+ * overlapping.  ws == NULL: the plain application.  With the workspace of a
+ * pcg_sgs solve every launch returns at once after `done`.
+ *
+ * pcg_sgs runs on a spmv_hip_pcg_ws, on the reducers of pcg and on
+ * cheb_update_xp, with z = M^-1 r STORED:
+ * sgs_init    : r = b ; x = 0 ; partials of r.r (b: any alignment)
+ * sgs_update_r: r -= alpha Ap, alpha = rz[k-1] / pAp[k] ; partials of r.r
+ * sgs_dot_rz  : partials of r.z for pcg_reduce_rz_rr
+ * (r, Ap, z 16-byte aligned; k outside 1..kmax is SPMV_HIP_EINVAL). */
+typedef struct spmv_hip_mcgs_plan spmv_hip_mcgs_plan;
+typedef struct spmv_hip_mcgs_part {
+  const int32_t* color_slice;
+  const int32_t* slice_pos0;
+  const int64_t* slice_ptr;
+  const int32_t* len;
+  const int32_t* col;
+  const double* val;
+  const int32_t* color_long;
+  const int32_t* long_pos;
+  const int64_t* long_ptr;
+  const int32_t* long_col;
+  const double* long_val;
+} spmv_hip_mcgs_part;
+typedef struct spmv_hip_mcgs_host {
+  int32_t num_rows;
+  int32_t num_colors;
+  const int32_t* perm;
+  const int32_t* color_start;
+  const double* dinv;
+  spmv_hip_mcgs_part before, after;
+} spmv_hip_mcgs_host;
+int spmv_hip_mcgs_plan_create(spmv_hip_ctx* ctx, const spmv_hip_mcgs_host* in,
+                              spmv_hip_mcgs_plan** plan);
+int spmv_hip_mcgs_plan_destroy(spmv_hip_mcgs_plan* plan);
+int spmv_hip_mcgs_plan_bytes(const spmv_hip_mcgs_plan* plan, int64_t* bytes);
+int spmv_hip_mcgs_apply_f64(spmv_hip_ctx* ctx, const spmv_hip_mcgs_plan* plan,
+                            spmv_hip_pcg_ws* ws, const double* r, double* z,
+                            void* stream);
+int spmv_hip_sgs_init_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
+                          const double* b, double* r, double* x, void* stream);
+int spmv_hip_sgs_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                              int64_t n, const double* Ap, double* r,
+                              void* stream);
+int spmv_hip_sgs_dot_rz_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
+                            const double* r, const double* z, void* stream);
+
 /* ---- BiCGStab with an optional diagonal right preconditioner (spmv::bicgstab) ---
  * For nonsymmetric systems.  `dinv` is the inverse of the preconditioner's
  * diagonal or NULL; ph = dinv*p, sh = dinv*s (elementwise), p and s themselves

@@ -412,6 +412,60 @@ int spmvh_lambda_max_estimate(spmvh_comm* comm, spmvh_exec* exec,
                               spmvh_matrix* A, const double* dinv,
                               const double* v0, int steps, double* lambda);
 
+/* ---- Multicolour symmetric Gauss-Seidel (host/cg.h; not in the reference) -----
+ * Two entries that touch NO device (host/sgs_build.h).  Input: the rows of a
+ * rank as CSR with local column numbers; entries with column >= ncols_local
+ * are ghosts and ignored, column == row is the diagonal; symmetric != 0: only
+ * column < row counts as an off-diagonal entry and the block stands for
+ * B + B^T.  nrows != ncols_local is an error.
+ * spmvh_sgs_color: the greedy colouring over B + B^T -> colors_out (nrows
+ * entries), *ncolors_out.
+ * spmvh_sgs_build_create: the colouring and the colour-major copy; sizes[3] =
+ * {colours, entries of `before`, entries of `after`}.  spmvh_sgs_build_get
+ * copies out (every pointer may be NULL): colors (nrows), perm (nrows),
+ * color_start (colours + 1), d (nrows, the diagonal), and the two parts as CSR
+ * over POSITIONS: ptr (nrows + 1, int64), col, val.
+ *
+ * spmvh_sgs_create: spmv::SgsPreconditioner(exec, A) -- the setup; errors whose
+ * text says "diagonal is not positive", "released" or "same index range".
+ * spmvh_sgs_info: rows, colours, device bytes of the plan (each may be NULL).
+ * spmvh_sgs_colors: the colours, rows entries (host).
+ * spmvh_sgs_apply: spmv::sgs_apply -- z = M^-1 r (device, rows doubles each, any
+ * alignment, not overlapping: "overlaps"), on the executor's current stream.
+ * spmvh_pcg_sgs: spmv::pcg_sgs; arguments as spmvh_pcg with M in place of
+ * dinv.  flags: bit 0 CgOptions::time_spmv (one interval per iteration), bits
+ * 8-15 CgOptions::poll_every (0 = default). */
+typedef struct spmvh_sgs_build spmvh_sgs_build;
+typedef struct spmvh_sgs spmvh_sgs;
+typedef struct spmvh_sgs_workspace spmvh_sgs_workspace;
+int spmvh_sgs_color(const int32_t* rowptr, const int32_t* colind, int64_t nrows,
+                    int64_t ncols_local, int symmetric, int32_t* colors_out,
+                    int* ncolors_out);
+int spmvh_sgs_build_create(const int32_t* rowptr, const int32_t* colind,
+                           const double* values, int64_t nrows,
+                           int64_t ncols_local, int symmetric,
+                           spmvh_sgs_build** build, int64_t* sizes);
+int spmvh_sgs_build_get(spmvh_sgs_build* build, int32_t* colors, int32_t* perm,
+                        int32_t* color_start, double* d, int64_t* before_ptr,
+                        int32_t* before_col, double* before_val,
+                        int64_t* after_ptr, int32_t* after_col,
+                        double* after_val);
+int spmvh_sgs_build_destroy(spmvh_sgs_build* build);
+int spmvh_sgs_create(spmvh_exec* exec, spmvh_matrix* A, spmvh_sgs** M);
+int spmvh_sgs_destroy(spmvh_sgs* M);
+int spmvh_sgs_info(spmvh_sgs* M, int* rows, int* num_colors,
+                   int64_t* plan_bytes);
+int spmvh_sgs_colors(spmvh_sgs* M, int32_t* colors);
+int spmvh_sgs_apply(spmvh_exec* exec, spmvh_sgs* M, const double* r, double* z);
+int spmvh_sgs_workspace_create(spmvh_exec* exec, spmvh_sgs_workspace** ws);
+int spmvh_sgs_workspace_destroy(spmvh_sgs_workspace* ws);
+int spmvh_sgs_workspace_reserve_timing(spmvh_sgs_workspace* ws, int iterations);
+int spmvh_pcg_sgs(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                  spmvh_sgs* M, const double* b, double* x, int kmax,
+                  double rtol, int* num_its, double* rnorm_history,
+                  spmvh_sgs_workspace* ws, int flags, double* spmv_ms_total,
+                  int* spmv_launches);
+
 /* ---- BiCGStab (spmv::bicgstab, host/cg.h; not in the reference) -------------
  * spmvh_bicgstab: BiCGStab from x0 = 0 for a matrix that need not be
  * symmetric.  dinv: NULL, or the inverse diagonal of a right preconditioner

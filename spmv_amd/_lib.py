@@ -197,6 +197,13 @@ _PROTOS = {
                                     vp, vp], C.c_int),
     "spmv_hip_cheb_update_xp_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp],
                                     C.c_int),
+    "spmv_hip_mcgs_plan_create": ([vp, vp, P(vp)], C.c_int),
+    "spmv_hip_mcgs_plan_destroy": ([vp], C.c_int),
+    "spmv_hip_mcgs_plan_bytes": ([vp, P(i64)], C.c_int),
+    "spmv_hip_mcgs_apply_f64": ([vp, vp, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_sgs_init_f64": ([vp, vp, i64, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_sgs_update_r_f64": ([vp, vp, C.c_int, i64, vp, vp, vp], C.c_int),
+    "spmv_hip_sgs_dot_rz_f64": ([vp, vp, i64, vp, vp, vp], C.c_int),
     "spmv_hip_bicg_ws_create": ([vp, C.c_int, P(vp)], C.c_int),
     "spmv_hip_bicg_ws_destroy": ([vp], C.c_int),
     "spmv_hip_bicg_ws_reset": ([vp, f64, vp], C.c_int),

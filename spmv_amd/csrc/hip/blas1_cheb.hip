@@ -26,6 +26,12 @@
 //              beta = rz[k] / rz[k-1] ; stop: sqrt(rr[k]) / sqrt(rr[0]) < rtol
 //   scale      out = dinv * (in / s): setup work of lambda_max_estimate
 //
+// and, for spmv::pcg_sgs, whose preconditioner is not elementwise
+// (spmv_mcgs.hip) and which shares update_xp:
+//   sgs_init      r = b ; x = 0 ; partials of r.r
+//   sgs_update_r  r -= alpha Ap ; partials of r.r
+//   sgs_dot_rz    partials of r.z after the sweeps
+//
 // pcg_chebyshev runs on the device state of spmv::pcg (pcg_ws.h) and on its
 // reducers (blas1_pcg.hip: pcg_reduce_pAp, _pAp2, pcg_reduce_rz_rr), whose
 // scalar layout fits as it is: the partials of r.r come from update_r, those of
@@ -363,6 +369,101 @@ __global__ __launch_bounds__(kBlock) void cheb_scale_kernel(
     out[i] = scaled<PRE>(PRE ? dinv[i] : 0.0, in[i] / s);
 }
 
+// ---- pcg_sgs: the recurrence of pcg_chebyshev around a preconditioner that is
+// ---- not elementwise (spmv_mcgs.hip), so step 0 leaves the kernels above ------
+// r = b ; x = 0 ; partials of r.r  (b needs no alignment)
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void sgs_init_kernel(
+    int64_t n, const double* __restrict__ bvec, double* __restrict__ r,
+    double* __restrict__ x, double* __restrict__ partials_rr, int len)
+{
+  __shared__ double s_red[kBlock / 64];
+  double acc_rr = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const double v = bvec[i];
+    if constexpr (NT) {
+      __builtin_nontemporal_store(v, &r[i]);
+      __builtin_nontemporal_store(0.0, &x[i]);
+    } else {
+      r[i] = v;
+      x[i] = 0.0;
+    }
+    acc_rr += v * v;
+  }
+  store_partials(acc_rr, partials_rr, len, s_red);
+}
+
+// r -= alpha Ap ; partials of r.r
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void sgs_update_r_kernel(
+    int64_t n, int k, const double* __restrict__ zr,
+    const double* __restrict__ pAp, const PcgScalars* __restrict__ sc,
+    const double* __restrict__ Ap, double* __restrict__ r,
+    double* __restrict__ partials_rr, int len)
+{
+  __shared__ double s_red[kBlock / 64];
+  if (sc->done)
+    return;
+  const double nalpha = -(zr[2 * (k - 1)] / pAp[k]);
+  double acc_rr = 0.0;
+  const int64_t n2 = n >> 1;
+  SPMV_FOR_UNITS(n2)
+  {
+    f64x2 av[kU], rv[kU];
+    SPMV_FOR_LANE_ELEMS(i, n2)
+    {
+      av[u] = vload<NT>(Ap, i);
+      rv[u] = vload<NT>(r, i);
+    }
+    SPMV_FOR_LANE_ELEMS(i, n2)
+    {
+      rv[u].x += nalpha * av[u].x;
+      rv[u].y += nalpha * av[u].y;
+      vstore<NT>(r, i, rv[u]);
+      acc_rr += rv[u].x * rv[u].x;
+      acc_rr += rv[u].y * rv[u].y;
+    }
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int64_t i = n - 1;
+    const double rv = r[i] + nalpha * Ap[i];
+    r[i] = rv;
+    acc_rr += rv * rv;
+  }
+  store_partials(acc_rr, partials_rr, len, s_red);
+}
+
+// partials of r.z, z = M(r) as the sweeps left it
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void sgs_dot_rz_kernel(
+    int64_t n, const PcgScalars* __restrict__ sc, const double* __restrict__ r,
+    const double* __restrict__ z, double* __restrict__ partials_rz, int len)
+{
+  __shared__ double s_red[kBlock / 64];
+  if (sc->done)
+    return;
+  double acc_rz = 0.0;
+  const int64_t n2 = n >> 1;
+  SPMV_FOR_UNITS(n2)
+  {
+    f64x2 rv[kU], zv[kU];
+    SPMV_FOR_LANE_ELEMS(i, n2)
+    {
+      rv[u] = vload<NT>(r, i);
+      zv[u] = vload<NT>(z, i);
+    }
+    SPMV_FOR_LANE_ELEMS(i, n2)
+    {
+      acc_rz += rv[u].x * zv[u].x;
+      acc_rz += rv[u].y * zv[u].y;
+    }
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+    acc_rz += r[n - 1] * z[n - 1];
+  store_partials(acc_rz, partials_rz, len, s_red);
+}
+
 bool aligned16(const void* p)
 {
   return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
@@ -532,6 +633,71 @@ int spmv_hip_cheb_scale_f64(spmv_hip_ctx* ctx, int64_t n, double s,
   else
     hipLaunchKernelGGL(cheb_scale_kernel<false>, dim3(grid), dim3(kBlock), 0,
                        st, n, s, dinv, in, out);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_sgs_init_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
+                          const double* b, double* r, double* x, void* stream)
+{
+  SPMV_REQUIRE(ctx && ws && ws->ctx == ctx && n >= 0);
+  SPMV_REQUIRE(n == 0 || (b && r && x));
+  SPMV_SET_DEVICE(ctx);
+  int grid = spmv_grid_for(ctx, n, kBlock);
+  if (grid > ctx->dot_blocks)
+    grid = ctx->dot_blocks;
+  hipStream_t st = spmv_stream(ctx, stream);
+  if (n >= ctx->blas1_nt_min_elems)
+    hipLaunchKernelGGL(sgs_init_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n,
+                       b, r, x, ws->partials_rr, ctx->dot_blocks);
+  else
+    hipLaunchKernelGGL(sgs_init_kernel<false>, dim3(grid), dim3(kBlock), 0, st,
+                       n, b, r, x, ws->partials_rr, ctx->dot_blocks);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_sgs_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
+                              int64_t n, const double* Ap, double* r,
+                              void* stream)
+{
+  SPMV_REQUIRE(ctx && ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (Ap && r)));
+  SPMV_REQUIRE(aligned16(Ap) && aligned16(r));
+  SPMV_SET_DEVICE(ctx);
+  int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
+  if (grid > ctx->dot_blocks)
+    grid = ctx->dot_blocks;
+  hipStream_t st = spmv_stream(ctx, stream);
+  if (n >= ctx->blas1_nt_min_elems)
+    hipLaunchKernelGGL(sgs_update_r_kernel<true>, dim3(grid), dim3(kBlock), 0,
+                       st, n, k, ws->zr, ws->pAp, ws->sc, Ap, r, ws->partials_rr,
+                       ctx->dot_blocks);
+  else
+    hipLaunchKernelGGL(sgs_update_r_kernel<false>, dim3(grid), dim3(kBlock), 0,
+                       st, n, k, ws->zr, ws->pAp, ws->sc, Ap, r, ws->partials_rr,
+                       ctx->dot_blocks);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_sgs_dot_rz_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
+                            const double* r, const double* z, void* stream)
+{
+  SPMV_REQUIRE(ctx && ws && ws->ctx == ctx);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (r && z)));
+  SPMV_REQUIRE(aligned16(r) && aligned16(z));
+  SPMV_SET_DEVICE(ctx);
+  int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
+  if (grid > ctx->dot_blocks)
+    grid = ctx->dot_blocks;
+  hipStream_t st = spmv_stream(ctx, stream);
+  if (n >= ctx->blas1_nt_min_elems)
+    hipLaunchKernelGGL(sgs_dot_rz_kernel<true>, dim3(grid), dim3(kBlock), 0, st,
+                       n, ws->sc, r, z, ws->partials_rz, ctx->dot_blocks);
+  else
+    hipLaunchKernelGGL(sgs_dot_rz_kernel<false>, dim3(grid), dim3(kBlock), 0, st,
+                       n, ws->sc, r, z, ws->partials_rz, ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }

@@ -1,0 +1,319 @@
+// Multicolour symmetric Gauss-Seidel sweeps (gfx950): the application of
+// spmv::SgsPreconditioner, z = M^-1 r with M = (D + L) D^-1 (D + U) in the
+// colour-major ordering of the rows of the local diagonal block.
+//
+//   forward,  colours 0 .. C-1:   s = 0; for e in before(i): s = s + a_e * z[col_e]
+//                                 z_i = (r_i - s) * dinv_i
+//   backward, colours C-2 .. 0:   t = 0; for e in after(i):  t = t + a_e * z[col_e]
+//                                 z_i = z_i - dinv_i * t
+//
+// before(i) / after(i): the off-diagonal entries of row i whose column wears a
+// smaller / larger colour, ascending by column.  One launch per colour and
+// direction, 2C - 1 in all; the order between colours is the stream's order and
+// nothing else -- no kernel here waits on another workgroup.  Inside a launch
+// no row reads what another row of the launch writes: a row of colour c reads
+// z only at columns of other colours.
+//
+// Layout (host/sgs_build.h, SgsSlicedPart): the rows of a colour in slices of
+// 64 consecutive positions, a slice column-major, one lane per row, so a
+// wavefront's loads of values and columns are contiguous.  A row with more than
+// 64 entries in a part takes a wavefront of its own from the long list: 64
+// entries are loaded and multiplied at a time, then added in their order, one
+// lane's product after the other, so the sum has the bits of the sequential
+// loop above.  The long rows of a colour are served by extra wavefronts of the
+// same launch.
+//
+// Built with -ffp-contract=off: every product and sum is a rounding of its own.
+#include "common.h"
+#include "pcg_ws.h"
+
+#include <vector>
+
+#include "plan_malloc.h"
+
+struct McgsPartDev {
+  int32_t* slice_pos0 = nullptr;
+  int64_t* slice_ptr = nullptr;
+  int32_t* len = nullptr;
+  int32_t* col = nullptr;
+  double* val = nullptr;
+  int32_t* long_pos = nullptr;
+  int64_t* long_ptr = nullptr;
+  int32_t* long_col = nullptr;
+  double* long_val = nullptr;
+  std::vector<int32_t> color_slice, color_long; // host: num_colors + 1 each
+};
+
+struct spmv_hip_mcgs_plan {
+  spmv_hip_ctx* ctx = nullptr;
+  int32_t n = 0;
+  int32_t num_colors = 0;
+  int32_t* perm = nullptr;
+  double* dinv = nullptr;
+  std::vector<int32_t> color_start; // host
+  McgsPartDev before, after;
+  int64_t bytes = 0;
+};
+
+namespace
+{
+
+constexpr int kWaves = kBlock / 64;
+
+// One colour, one direction.  Wavefront w of the launch: slice first_slice + w
+// while w < num_slices, then long row first_long + (w - num_slices).
+template <bool FORWARD>
+__global__ __launch_bounds__(kBlock) void mcgs_sweep_kernel(
+    int32_t first_slice, int32_t num_slices, int32_t pos_end,
+    int32_t first_long, int32_t num_long,
+    const int32_t* __restrict__ slice_pos0,
+    const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ len,
+    const int32_t* __restrict__ col, const double* __restrict__ val,
+    const int32_t* __restrict__ long_pos, const int64_t* __restrict__ long_ptr,
+    const int32_t* __restrict__ long_col, const double* __restrict__ long_val,
+    const int32_t* __restrict__ perm, const double* __restrict__ dinv,
+    const double* __restrict__ r, double* z, const PcgScalars* __restrict__ sc)
+{
+  if (sc && sc->done)
+    return;
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (w < num_slices) {
+    const int64_t s = first_slice + w;
+    const int32_t pos = slice_pos0[s] + lane;
+    if (pos >= pos_end)
+      return;
+    const int32_t m = len[pos];
+    if (m < 0) // a long row: another wavefront's
+      return;
+    const int64_t base = slice_ptr[s] + lane;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int32_t k = 0; k < m; ++k) {
+      const int64_t e = base + (int64_t)k * 64;
+      acc = acc + val[e] * z[col[e]];
+    }
+    const int32_t i = perm[pos];
+    if constexpr (FORWARD)
+      z[i] = (r[i] - acc) * dinv[i];
+    else
+      z[i] = z[i] - dinv[i] * acc;
+    return;
+  }
+  const int64_t l = w - num_slices;
+  if (l >= num_long)
+    return;
+  const int32_t pos = long_pos[first_long + l];
+  const int64_t e0 = long_ptr[first_long + l], e1 = long_ptr[first_long + l + 1];
+  double acc = 0.0;
+  for (int64_t e = e0; e < e1; e += 64) {
+    const int64_t mine = e + lane;
+    const double prod = mine < e1 ? long_val[mine] * z[long_col[mine]] : 0.0;
+    const int cnt = e1 - e < 64 ? (int)(e1 - e) : 64;
+    for (int j = 0; j < cnt; ++j) // in the entries' order, every lane the same
+      acc = acc + __shfl(prod, j, 64);
+  }
+  if (lane == 0) {
+    const int32_t i = perm[pos];
+    if constexpr (FORWARD)
+      z[i] = (r[i] - acc) * dinv[i];
+    else
+      z[i] = z[i] - dinv[i] * acc;
+  }
+}
+
+template <typename T>
+int upload(const T* host, size_t count, T** dev, int64_t* bytes)
+{
+  *dev = nullptr;
+  if (count == 0)
+    return SPMV_HIP_OK;
+  SPMV_REQUIRE(host != nullptr);
+  SPMV_CHECK_HIP(hipMalloc(dev, count * sizeof(T)));
+  *bytes += (int64_t)(count * sizeof(T));
+  SPMV_CHECK_HIP(hipMemcpy(*dev, host, count * sizeof(T), hipMemcpyHostToDevice));
+  return SPMV_HIP_OK;
+}
+
+// Everything a kernel will index with is checked here, once, on the host.
+bool part_is_sound(const spmv_hip_mcgs_host& in, const spmv_hip_mcgs_part& p)
+{
+  const int32_t n = in.num_rows, C = in.num_colors;
+  if (!p.color_slice || !p.color_long || !p.slice_ptr || !p.long_ptr)
+    return false;
+  if (p.color_slice[0] != 0 || p.color_long[0] != 0 || p.slice_ptr[0] != 0
+      || p.long_ptr[0] != 0)
+    return false;
+  for (int c = 0; c < C; ++c)
+    if (p.color_slice[c + 1] < p.color_slice[c]
+        || p.color_long[c + 1] < p.color_long[c])
+      return false;
+  const int32_t ns = p.color_slice[C], nl = p.color_long[C];
+  if ((ns > 0 && !p.slice_pos0) || (n > 0 && !p.len) || (nl > 0 && !p.long_pos))
+    return false;
+  for (int c = 0; c < C; ++c) {
+    const int32_t c0 = in.color_start[c], c1 = in.color_start[c + 1];
+    // the slices of a colour tile its positions
+    if ((int64_t)p.color_slice[c + 1] - p.color_slice[c]
+        != ((int64_t)c1 - c0 + 63) / 64)
+      return false;
+    for (int32_t s = p.color_slice[c]; s < p.color_slice[c + 1]; ++s) {
+      if (p.slice_pos0[s] != c0 + 64 * (s - p.color_slice[c]))
+        return false;
+      const int64_t span = p.slice_ptr[s + 1] - p.slice_ptr[s];
+      if (span < 0 || span % 64 != 0)
+        return false;
+      const int32_t p1 = p.slice_pos0[s] + 64 < c1 ? p.slice_pos0[s] + 64 : c1;
+      for (int32_t pos = p.slice_pos0[s]; pos < p1; ++pos)
+        if (p.len[pos] > span / 64)
+          return false;
+    }
+    for (int32_t l = p.color_long[c]; l < p.color_long[c + 1]; ++l)
+      if (p.long_pos[l] < c0 || p.long_pos[l] >= c1 || p.len[p.long_pos[l]] >= 0
+          || p.long_ptr[l + 1] < p.long_ptr[l])
+        return false;
+  }
+  const int64_t ne = p.slice_ptr[ns], nle = p.long_ptr[nl];
+  if ((ne > 0 && (!p.col || !p.val)) || (nle > 0 && (!p.long_col || !p.long_val)))
+    return false;
+  for (int64_t e = 0; e < ne; ++e)
+    if (p.col[e] < 0 || p.col[e] >= n)
+      return false;
+  for (int64_t e = 0; e < nle; ++e)
+    if (p.long_col[e] < 0 || p.long_col[e] >= n)
+      return false;
+  return true;
+}
+
+int upload_part(const spmv_hip_mcgs_host& in, const spmv_hip_mcgs_part& p,
+                McgsPartDev* d, int64_t* bytes)
+{
+  const int32_t C = in.num_colors;
+  const size_t ns = (size_t)p.color_slice[C], nl = (size_t)p.color_long[C];
+  d->color_slice.assign(p.color_slice, p.color_slice + C + 1);
+  d->color_long.assign(p.color_long, p.color_long + C + 1);
+  int rc;
+  if ((rc = upload(p.slice_pos0, ns, &d->slice_pos0, bytes)) != SPMV_HIP_OK
+      || (rc = upload(p.slice_ptr, ns + 1, &d->slice_ptr, bytes)) != SPMV_HIP_OK
+      || (rc = upload(p.len, (size_t)in.num_rows, &d->len, bytes)) != SPMV_HIP_OK
+      || (rc = upload(p.col, (size_t)p.slice_ptr[ns], &d->col, bytes))
+             != SPMV_HIP_OK
+      || (rc = upload(p.val, (size_t)p.slice_ptr[ns], &d->val, bytes))
+             != SPMV_HIP_OK
+      || (rc = upload(p.long_pos, nl, &d->long_pos, bytes)) != SPMV_HIP_OK
+      || (rc = upload(p.long_ptr, nl + 1, &d->long_ptr, bytes)) != SPMV_HIP_OK
+      || (rc = upload(p.long_col, (size_t)p.long_ptr[nl], &d->long_col, bytes))
+             != SPMV_HIP_OK
+      || (rc = upload(p.long_val, (size_t)p.long_ptr[nl], &d->long_val, bytes))
+             != SPMV_HIP_OK)
+    return rc;
+  return SPMV_HIP_OK;
+}
+
+void free_part(McgsPartDev* d)
+{
+  for (void* q : {(void*)d->slice_pos0, (void*)d->slice_ptr, (void*)d->len,
+                  (void*)d->col, (void*)d->val, (void*)d->long_pos,
+                  (void*)d->long_ptr, (void*)d->long_col, (void*)d->long_val})
+    if (q)
+      (void)hipFree(q);
+}
+
+template <bool FORWARD>
+void launch_colour(const spmv_hip_mcgs_plan* plan, const McgsPartDev& p, int c,
+                   const double* r, double* z, const PcgScalars* sc,
+                   hipStream_t st)
+{
+  const int32_t ns = p.color_slice[c + 1] - p.color_slice[c];
+  const int32_t nl = p.color_long[c + 1] - p.color_long[c];
+  const int64_t waves = (int64_t)ns + nl;
+  if (waves == 0)
+    return;
+  const unsigned grid = (unsigned)((waves + kWaves - 1) / kWaves);
+  hipLaunchKernelGGL(mcgs_sweep_kernel<FORWARD>, dim3(grid), dim3(kBlock), 0, st,
+                     p.color_slice[c], ns, plan->color_start[c + 1],
+                     p.color_long[c], nl, p.slice_pos0, p.slice_ptr, p.len,
+                     p.col, p.val, p.long_pos, p.long_ptr, p.long_col,
+                     p.long_val, plan->perm, plan->dinv, r, z, sc);
+}
+
+} // namespace
+
+extern "C" {
+
+int spmv_hip_mcgs_plan_create(spmv_hip_ctx* ctx, const spmv_hip_mcgs_host* in,
+                              spmv_hip_mcgs_plan** plan)
+{
+  SPMV_REQUIRE(ctx && in && plan);
+  *plan = nullptr;
+  const int32_t n = in->num_rows, C = in->num_colors;
+  SPMV_REQUIRE(n >= 0 && C >= 0 && (n == 0) == (C == 0));
+  SPMV_REQUIRE(in->color_start && (n == 0 || (in->perm && in->dinv)));
+  SPMV_REQUIRE(in->color_start[0] == 0 && in->color_start[C] == n);
+  for (int c = 0; c < C; ++c) // every colour is worn
+    SPMV_REQUIRE(in->color_start[c + 1] > in->color_start[c]);
+  for (int32_t pos = 0; pos < n; ++pos)
+    SPMV_REQUIRE(in->perm[pos] >= 0 && in->perm[pos] < n);
+  SPMV_REQUIRE(part_is_sound(*in, in->before) && part_is_sound(*in, in->after));
+  SPMV_SET_DEVICE(ctx);
+  spmv_hip_mcgs_plan* p = new (std::nothrow) spmv_hip_mcgs_plan();
+  if (!p)
+    return SPMV_HIP_EINVAL;
+  p->ctx = ctx;
+  p->n = n;
+  p->num_colors = C;
+  p->color_start.assign(in->color_start, in->color_start + C + 1);
+  int rc;
+  if ((rc = upload(in->perm, (size_t)n, &p->perm, &p->bytes)) != SPMV_HIP_OK
+      || (rc = upload(in->dinv, (size_t)n, &p->dinv, &p->bytes)) != SPMV_HIP_OK
+      || (rc = upload_part(*in, in->before, &p->before, &p->bytes)) != SPMV_HIP_OK
+      || (rc = upload_part(*in, in->after, &p->after, &p->bytes))
+             != SPMV_HIP_OK) {
+    spmv_hip_mcgs_plan_destroy(p);
+    return rc;
+  }
+  *plan = p;
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_mcgs_plan_destroy(spmv_hip_mcgs_plan* plan)
+{
+  if (!plan)
+    return SPMV_HIP_OK;
+  (void)hipSetDevice(plan->ctx->device);
+  free_part(&plan->before);
+  free_part(&plan->after);
+  if (plan->perm)
+    (void)hipFree(plan->perm);
+  if (plan->dinv)
+    (void)hipFree(plan->dinv);
+  delete plan;
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_mcgs_plan_bytes(const spmv_hip_mcgs_plan* plan, int64_t* bytes)
+{
+  SPMV_REQUIRE(plan && bytes);
+  *bytes = plan->bytes;
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_mcgs_apply_f64(spmv_hip_ctx* ctx, const spmv_hip_mcgs_plan* plan,
+                            spmv_hip_pcg_ws* ws, const double* r, double* z,
+                            void* stream)
+{
+  SPMV_REQUIRE(ctx && plan && plan->ctx == ctx && (!ws || ws->ctx == ctx));
+  SPMV_REQUIRE(plan->n == 0 || (r && z));
+  SPMV_SET_DEVICE(ctx);
+  hipStream_t st = spmv_stream(ctx, stream);
+  const PcgScalars* sc = ws ? ws->sc : nullptr;
+  const int C = plan->num_colors;
+  for (int c = 0; c < C; ++c)
+    launch_colour<true>(plan, plan->before, c, r, z, sc, st);
+  for (int c = C - 2; c >= 0; --c)
+    launch_colour<false>(plan, plan->after, c, r, z, sc, st);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
+} // extern "C"

@@ -15,6 +15,7 @@
 #include "l2gmap.h"
 #include "matrix.h"
 #include "read_petsc.h"
+#include "sgs_build.h"
 
 using namespace spmv;
 
@@ -50,6 +51,14 @@ struct spmvh_cg_block_workspace : WorkspaceHandle<CgBlockWorkspace> {};
 struct spmvh_pcg_workspace : WorkspaceHandle<PcgWorkspace> {};
 struct spmvh_chebyshev_workspace : WorkspaceHandle<ChebyshevWorkspace> {};
 struct spmvh_bicgstab_workspace : WorkspaceHandle<BicgstabWorkspace> {};
+struct spmvh_sgs_workspace : WorkspaceHandle<SgsWorkspace> {};
+struct spmvh_sgs_build {
+  SgsHostPlan plan;
+};
+struct spmvh_sgs {
+  std::shared_ptr<HipExecutor> exec; // keeps the executor alive
+  std::unique_ptr<SgsPreconditioner> M;
+};
 
 namespace
 {
@@ -1295,6 +1304,152 @@ int spmvh_lambda_max_estimate(spmvh_comm* comm, spmvh_exec* exec,
     require(comm && exec && A && v0 && lambda, "NULL argument");
     *lambda = lambda_max_estimate(*comm->comm, *exec->hip, *A->A, dinv, v0,
                                   steps);
+  });
+}
+
+// ---- Multicolour symmetric Gauss-Seidel -------------------------------------------------
+int spmvh_sgs_color(const int32_t* rowptr, const int32_t* colind, int64_t nrows,
+                    int64_t ncols_local, int symmetric, int32_t* colors_out,
+                    int* ncolors_out)
+{
+  return guarded([&] {
+    require(nrows == 0 || colors_out, "NULL argument");
+    int nc = 0;
+    const std::vector<int32_t> c
+        = sgs_color(rowptr, colind, nrows, ncols_local, symmetric != 0, &nc);
+    std::copy(c.begin(), c.end(), colors_out);
+    if (ncolors_out)
+      *ncolors_out = nc;
+  });
+}
+
+int spmvh_sgs_build_create(const int32_t* rowptr, const int32_t* colind,
+                           const double* values, int64_t nrows,
+                           int64_t ncols_local, int symmetric,
+                           spmvh_sgs_build** build, int64_t* sizes)
+{
+  return guarded([&] {
+    require(build && sizes, "NULL argument");
+    auto b = std::make_unique<spmvh_sgs_build>();
+    b->plan = sgs_build(rowptr, colind, values, nullptr, nrows, ncols_local,
+                        symmetric != 0);
+    sizes[0] = b->plan.num_colors;
+    sizes[1] = (int64_t)b->plan.before.col.size();
+    sizes[2] = (int64_t)b->plan.after.col.size();
+    *build = b.release();
+  });
+}
+
+int spmvh_sgs_build_get(spmvh_sgs_build* build, int32_t* colors, int32_t* perm,
+                        int32_t* color_start, double* d, int64_t* before_ptr,
+                        int32_t* before_col, double* before_val,
+                        int64_t* after_ptr, int32_t* after_col,
+                        double* after_val)
+{
+  return guarded([&] {
+    require(build != nullptr, "NULL argument");
+    auto out = [](const auto& v, auto* dst) {
+      if (dst)
+        std::copy(v.begin(), v.end(), dst);
+    };
+    const SgsHostPlan& p = build->plan;
+    out(p.colors, colors);
+    out(p.perm, perm);
+    out(p.color_start, color_start);
+    out(p.d, d);
+    out(p.before.ptr, before_ptr);
+    out(p.before.col, before_col);
+    out(p.before.val, before_val);
+    out(p.after.ptr, after_ptr);
+    out(p.after.col, after_col);
+    out(p.after.val, after_val);
+  });
+}
+
+int spmvh_sgs_build_destroy(spmvh_sgs_build* build)
+{
+  return guarded([&] { delete build; });
+}
+
+int spmvh_sgs_create(spmvh_exec* exec, spmvh_matrix* A, spmvh_sgs** M)
+{
+  return guarded([&] {
+    require(exec && A && M, "NULL argument");
+    require(exec->hip != nullptr, "not a HipExecutor");
+    auto m = std::make_unique<spmvh_sgs>();
+    m->exec = exec->hip;
+    m->M.reset(new SgsPreconditioner(*exec->hip, *A->A));
+    *M = m.release();
+  });
+}
+
+int spmvh_sgs_destroy(spmvh_sgs* M)
+{
+  return guarded([&] { delete M; });
+}
+
+int spmvh_sgs_info(spmvh_sgs* M, int* rows, int* num_colors, int64_t* plan_bytes)
+{
+  return guarded([&] {
+    require(M != nullptr, "NULL argument");
+    if (rows)
+      *rows = M->M->rows();
+    if (num_colors)
+      *num_colors = M->M->num_colors();
+    if (plan_bytes)
+      *plan_bytes = M->M->plan_bytes();
+  });
+}
+
+int spmvh_sgs_colors(spmvh_sgs* M, int32_t* colors)
+{
+  return guarded([&] {
+    require(M != nullptr, "NULL argument");
+    M->M->colors(colors);
+  });
+}
+
+int spmvh_sgs_apply(spmvh_exec* exec, spmvh_sgs* M, const double* r, double* z)
+{
+  return guarded([&] {
+    require(exec && M, "NULL argument");
+    sgs_apply(*exec->hip, *M->M, r, z);
+  });
+}
+
+int spmvh_sgs_workspace_create(spmvh_exec* exec, spmvh_sgs_workspace** ws)
+{
+  return workspace_create<SgsWorkspace>(exec, ws);
+}
+
+int spmvh_sgs_workspace_destroy(spmvh_sgs_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_sgs_workspace_reserve_timing(spmvh_sgs_workspace* ws, int iterations)
+{
+  return workspace_reserve_timing(ws, iterations);
+}
+
+int spmvh_pcg_sgs(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                  spmvh_sgs* M, const double* b, double* x, int kmax,
+                  double rtol, int* num_its, double* rnorm_history,
+                  spmvh_sgs_workspace* ws, int flags, double* spmv_ms_total,
+                  int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && M && num_its, "NULL argument");
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff) // bits 8-15: CgOptions::poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    CgStats st;
+    *num_its = pcg_sgs(*comm->comm, *exec->hip, *A->A, *M->M, b, x, kmax, rtol,
+                       rnorm_history ? &hist : nullptr, &opt, &st,
+                       ws ? ws->ws.get() : nullptr);
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
   });
 }
 

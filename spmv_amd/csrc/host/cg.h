@@ -15,6 +15,7 @@ struct spmv_hip_cg_ws;
 struct spmv_hip_cgb_ws;
 struct spmv_hip_pcg_ws;
 struct spmv_hip_bicg_ws;
+struct spmv_hip_mcgs_plan;
 
 namespace spmv
 {
@@ -435,6 +436,137 @@ int pcg_chebyshev(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
 double lambda_max_estimate(const Comm& comm, HipExecutor& exec,
                            const Matrix<double>& A, const double* dinv,
                            const double* v0, int steps);
+
+// ---- Multicolour symmetric Gauss-Seidel preconditioner ------------------------
+// M = (D + L) D^-1 (D + U) on the LOCAL DIAGONAL BLOCK of A -- the rows of this
+// rank and the columns < local_size; ghost columns and the remote block are
+// ignored, so on several ranks the preconditioner is block-Jacobi over the ranks
+// with SGS inside each, and an application needs no halo exchange -- with the
+// rows in colour-major order:
+//
+//   colouring  greedy in natural row order over the pattern of B + B^T, B the
+//              block without its diagonal (symmetric storage: the stored
+//              strictly lower block): colour(i) = the smallest colour not worn
+//              by an already coloured neighbour.  Deterministic; the 7-point
+//              Poisson matrix gets two colours, the parity of x + y + z.
+//   rows       colour-major, natural order within a colour
+//   before(i)  the off-diagonal entries of row i whose column's colour is
+//              smaller than colour(i); after(i): larger.  Each ascending by
+//              column, duplicates of a column in storage order.  Symmetric
+//              storage: a row's entries are its stored lower entries and the
+//              entries of its column in the stored block (a stable transpose).
+//   d_i        what Matrix::diagonal defines; dinv_i = 1.0 / d_i
+//
+//   forward,  colours 0 .. C-1:  s = 0.0; for e in before(i): s = s + a_e * z[col_e]
+//                                z_i = (r_i - s) * dinv_i
+//   backward, colours C-2 .. 0:  t = 0.0; for e in after(i):  t = t + a_e * z[col_e]
+//                                z_i = z_i - dinv_i * t
+//
+// Every product and sum is a rounding of its own.  Inside a colour the rows are
+// independent: one launch per colour and direction (2C - 1 per application),
+// ordered by the stream alone.
+//
+// The constructor is the setup and the one place that waits on the device: it
+// reads the block back, colours and reorders it on the host
+// (host/sgs_build.h) and uploads the plan's own copy (slices of 64 rows stored
+// column-major, one lane per row; rows with more than 64 entries in a part take
+// a wavefront each).  A may release_csr() AFTERWARDS; on a matrix that has
+// released its CSR arrays the constructor throws, for both storages (the lower
+// block's arrays are gone).  Rows and owned columns must be the same index
+// range on the rank, as for Matrix::diagonal (std::runtime_error).  A diagonal
+// entry that is not finite or not > 0 throws with jacobi_inverse's message
+// ("... diagonal is not positive ...").
+class SgsPreconditioner
+{
+public:
+  SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A);
+  ~SgsPreconditioner();
+  SgsPreconditioner(const SgsPreconditioner&) = delete;
+  SgsPreconditioner& operator=(const SgsPreconditioner&) = delete;
+
+  int rows() const { return (int)_colors.size(); }
+  int num_colors() const { return _num_colors; }
+  void colors(int32_t* out) const; // host copy, rows() entries
+  int64_t plan_bytes() const;      // device memory of the plan
+  spmv_hip_mcgs_plan* plan() const { return _plan; }
+
+private:
+  HipExecutor& _exec;
+  spmv_hip_mcgs_plan* _plan = nullptr;
+  int _num_colors = 0;
+  std::vector<int32_t> _colors;
+};
+
+// z = M^-1 r.  `r`, `z`: DEVICE vectors of rows() doubles, any alignment, not
+// overlapping ("overlaps").  Runs on the executor's current stream; the host
+// does not wait.
+void sgs_apply(HipExecutor& exec, const SgsPreconditioner& M, const double* r,
+               double* z);
+
+// Work vectors + device scalars of pcg_sgs(), kept across calls like
+// ChebyshevWorkspace; the device scalars and their reducers are pcg()'s.
+class SgsWorkspace : public SolverWorkspace
+{
+public:
+  explicit SgsWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
+  ~SgsWorkspace();
+
+  // ---- internal to pcg_sgs() ----
+  void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len,
+              bool need_x);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(2 * (size_t)std::max(iterations, 0));
+  }
+  void release();
+
+  spmv_hip_pcg_ws* ws = nullptr;
+  int kmax_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, x_cap = -1;
+  double *r = nullptr, *Ap = nullptr, *z = nullptr; // m_cap
+  double* p = nullptr;    // n_cap: padded, the ghost tail is zeroed by every solve
+  double* x = nullptr;    // x_cap: the iterate when the caller's x is unaligned
+  double* dot2 = nullptr; // partials of the remote block's p.Ap share
+  // flags: {done, kstop}; timing_ev: 2 events per iteration
+};
+
+// CG with the preconditioner M from x0 = 0: pcg_chebyshev()'s recurrence with
+// the stored z = sgs_apply(r).
+//
+//   r0 = b; z0 = M^-1 r0; p1 = z0; rz[0] = r0.z0; rr[0] = r0.r0
+//   for k = 1..kmax:
+//     Ap    = A p_k (fused p.Ap where the SpMV can); alpha = rz[k-1] / (p_k.Ap)
+//     r    -= alpha * Ap; rr[k] = r.r; z = M^-1 r; rz[k] = r.z
+//     x    += alpha * p_k
+//     if sqrt(rr[k]) / sqrt(rr[0]) < rtol: stop (x and r updated, p not)
+//     beta  = rz[k] / rz[k-1]; p_(k+1) = beta * p_k + z
+//
+// An iteration is one SpMV, the 2C - 1 sweeps, 3 streaming launches (r and the
+// partials of r.r; the partials of r.z; x, the stop test and p) and 2 reducer
+// launches; beside the SpMV and the sweeps 3 + 2 + 5 = 10 vector passes.  With
+// several ranks: one all-reduce of 1 double (p.Ap) and ONE of 2 doubles
+// ({rz[k], rr[k]}).  M must have been built from A (or from a matrix with A's
+// rows on this rank): M.rows() != A's rows throws.
+//
+// As in pcg_chebyshev(): the stopping test is cg()'s; rnorm_history receives
+// ||r_0||, ..., ||r_k||; a system with r_0 . r_0 == 0 stops at k = 0 with x = 0;
+// scalars stay on the device, the stop is decided on the device and every
+// kernel after `done` returns at once, so x is exactly the iterate of the
+// returned k; the host only polls a pinned flag every `poll_every` iterations;
+// `x` IS the iterate and must not overlap `b` (std::runtime_error,
+// "overlaps"); an `x` that is not 16-byte aligned goes through the workspace's
+// copy; kmax < 0 throws ("kmax"); the executor's stream is restored on every
+// exit path.
+//
+// options: poll_every and time_spmv apply (time_spmv brackets the ONE
+//          Matrix::mult of an iteration: CgStats::spmv_launches is 1 per
+//          iteration); consumer_reductions, defer_x and mixed are IGNORED, as in
+//          pcg_chebyshev.
+int pcg_sgs(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+            const SgsPreconditioner& M, const double* b, double* x, int kmax,
+            double rtol, std::vector<double>* rnorm_history = nullptr,
+            const CgOptions* options = nullptr, CgStats* stats = nullptr,
+            SgsWorkspace* workspace = nullptr);
 
 // Work vectors + device scalars of bicgstab(), kept across calls like
 // PcgWorkspace; it regrows itself when a call needs more rows or more

@@ -1,10 +1,11 @@
-// spmv::pcg and the Chebyshev polynomial preconditioner for HipExecutor: see
-// cg.h.
+// spmv::pcg, the Chebyshev polynomial preconditioner and the multicolour
+// symmetric Gauss-Seidel preconditioner for HipExecutor: see cg.h.
 #include "cg.h"
 
 #include <initializer_list>
 #include <utility>
 
+#include "sgs_build.h"
 #include "solver_common.h"
 
 namespace spmv
@@ -508,6 +509,301 @@ int pcg_chebyshev(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
     *stats = CgStats();
     if (opt.time_spmv)
       sum_spmv_times(ctx, timing_ev, ev_next, *stats);
+  }
+
+  auto rr_at = [&](int j) { return zr[2 * (size_t)j + 1]; };
+  int k_final;
+  if (w.flags[0] != 0)
+    k_final = w.flags[1];
+  else if (rr_at(0) == 0.0)
+    k_final = 0; // (kmax == 0: no kernel ran to say so)
+  else // `done` is raised by the first reducer of the NEXT iteration
+    k_final = first_k_below(rr_at, k, rtol);
+  write_history(rnorm_history, k_final, rr_at);
+  return k_final;
+}
+
+// ---------------------------------------------------------------------------
+// Multicolour symmetric Gauss-Seidel: see cg.h.  pcg_sgs per iteration (compute
+// stream), on the scalars and reducers of pcg():
+//     halo start of p ; Ap = A p (+ fused p.Ap share)
+//     reduce_pAp ; all-reduce of 1
+//     sgs_update_r    (r ; partials of r.r)
+//     2C - 1 sweeps   (z = M^-1 r, local: no halo)
+//     sgs_dot_rz      (partials of r.z)
+//     reduce_rz_rr ; all-reduce of 2
+//     cheb_update_xp  (x ; stop test ; p)
+// ---------------------------------------------------------------------------
+SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A)
+    : _exec(exec)
+{
+  std::shared_ptr<L2GMap> row_map = A.row_map();
+  std::shared_ptr<const L2GMap> col_map = A.col_map();
+  if (row_map->num_ghosts() > 0
+      || row_map->local_size() != col_map->local_size()
+      || row_map->global_offset() != col_map->global_offset())
+    throw std::runtime_error(
+        "spmv::SgsPreconditioner - Error: rows and owned columns are not the "
+        "same index range on this rank");
+  const auto* blk = dynamic_cast<const CSRMatrix<double>*>(A.local_block());
+  if (!blk)
+    throw std::runtime_error(
+        "spmv::SgsPreconditioner - Error: the matrix has no local block");
+  if (blk->csr_released())
+    throw std::runtime_error(
+        "spmv::SgsPreconditioner - Error: the CSR arrays of this matrix were "
+        "released (release_csr); build the preconditioner before releasing "
+        "them");
+  const int64_t n = row_map->local_size();
+  const int64_t nnz = blk->non_zeros();
+  const bool symmetric = A.symmetric();
+
+  // the block, read back (the copies wait for the device)
+  const DeviceExecutor& host = exec.get_host();
+  std::vector<int32_t> rowptr((size_t)n + 1, 0), colind((size_t)nnz);
+  std::vector<double> values((size_t)nnz), diagonal;
+  if (nnz > 0) { // (an empty block owns no arrays)
+    exec.copy_to<int32_t>(rowptr.data(), host, blk->rowptr(), (size_t)n + 1);
+    exec.copy_to<int32_t>(colind.data(), host, blk->colind(), (size_t)nnz);
+    exec.copy_to<double>(values.data(), host, blk->values(), (size_t)nnz);
+  }
+  if (symmetric && n > 0) {
+    diagonal.resize((size_t)n);
+    exec.copy_to<double>(diagonal.data(), host, blk->diagonal(), (size_t)n);
+  }
+
+  SgsHostPlan hp = sgs_build(rowptr.data(), colind.data(), values.data(),
+                             symmetric ? diagonal.data() : nullptr, n, n,
+                             symmetric);
+  std::vector<int32_t>().swap(colind);
+  std::vector<double>().swap(values);
+
+  // jacobi_inverse's rule and message
+  int64_t bad = 0;
+  std::vector<double> dinv((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const double v = hp.d[(size_t)i];
+    dinv[(size_t)i] = 1.0 / v;
+    if (!(v > 0.0) || !std::isfinite(v))
+      ++bad;
+  }
+  if (bad != 0)
+    throw std::runtime_error(
+        "spmv::SgsPreconditioner - Error: the diagonal is not positive ("
+        + std::to_string(bad) + " of " + std::to_string(n)
+        + " entries are not finite or not > 0)");
+
+  auto part_of = [](const SgsSlicedPart& s) {
+    return spmv_hip_mcgs_part{s.color_slice.data(), s.slice_pos0.data(),
+                              s.slice_ptr.data(),   s.len.data(),
+                              s.col.data(),         s.val.data(),
+                              s.color_long.data(),  s.long_pos.data(),
+                              s.long_ptr.data(),    s.long_col.data(),
+                              s.long_val.data()};
+  };
+  const SgsSlicedPart before = sgs_slice(hp, hp.before);
+  hp.before = SgsCsrPart();
+  const SgsSlicedPart after = sgs_slice(hp, hp.after);
+  hp.after = SgsCsrPart();
+  spmv_hip_mcgs_host in{};
+  in.num_rows = hp.n;
+  in.num_colors = hp.num_colors;
+  in.perm = hp.perm.data();
+  in.color_start = hp.color_start.data();
+  in.dinv = dinv.data();
+  in.before = part_of(before);
+  in.after = part_of(after);
+  throw_on_error(spmv_hip_mcgs_plan_create(exec.context(), &in, &_plan),
+                 "spmv_hip_mcgs_plan_create");
+  _num_colors = hp.num_colors;
+  _colors = std::move(hp.colors);
+}
+
+SgsPreconditioner::~SgsPreconditioner()
+{
+  try {
+    if (_plan) // a sweep may still be in flight
+      _exec.synchronize();
+  } catch (...) {
+  }
+  spmv_hip_mcgs_plan_destroy(_plan);
+}
+
+void SgsPreconditioner::colors(int32_t* out) const
+{
+  if (!out && !_colors.empty())
+    throw std::runtime_error("spmv::SgsPreconditioner::colors - Error: NULL output");
+  std::copy(_colors.begin(), _colors.end(), out);
+}
+
+int64_t SgsPreconditioner::plan_bytes() const
+{
+  int64_t bytes = 0;
+  throw_on_error(spmv_hip_mcgs_plan_bytes(_plan, &bytes),
+                 "spmv_hip_mcgs_plan_bytes");
+  return bytes;
+}
+
+void sgs_apply(HipExecutor& exec, const SgsPreconditioner& M, const double* r,
+               double* z)
+{
+  if (ranges_overlap(z, r, M.rows()))
+    throw std::runtime_error("sgs_apply: z overlaps r");
+  if (M.rows() > 0 && (!r || !z))
+    throw std::runtime_error("sgs_apply: NULL vector");
+  throw_on_error(spmv_hip_mcgs_apply_f64(exec.context(), M.plan(), nullptr, r, z,
+                                         nullptr),
+                 "spmv_hip_mcgs_apply_f64");
+}
+
+SgsWorkspace::~SgsWorkspace() { release(); }
+
+void SgsWorkspace::release()
+{
+  release_common();
+  spmv_hip_pcg_ws_destroy(ws);
+  ws = nullptr;
+  free_vectors({&r, &Ap, &z, &p, &x, &dot2});
+  kmax_cap = -1;
+  m_cap = n_cap = x_cap = -1;
+}
+
+void SgsWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
+                          bool need_x)
+{
+  open(2);
+  if (!dot2)
+    dot2 = _exec.alloc<double>(len);
+  regrow_scalars(_exec.context(), ws, kmax_cap, kmax);
+  regrow(m_cap, M, {&r, &Ap, &z});
+  if (need_x)
+    regrow(x_cap, M, {&x});
+  regrow(n_cap, N_padded, {&p});
+}
+
+int pcg_sgs(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+            const SgsPreconditioner& Mpre, const double* b, double* x, int kmax,
+            double rtol, std::vector<double>* rnorm_history,
+            const CgOptions* options, CgStats* stats, SgsWorkspace* workspace)
+{
+  const Dims dims = check_problem("pcg_sgs", A, kmax);
+  const int64_t M = dims.M, N_padded = dims.N_padded;
+  const std::shared_ptr<const L2GMap>& col_l2g = dims.col_l2g;
+  const CgOptions opt = options ? *options : CgOptions();
+  spmv_hip_ctx* ctx = exec.context();
+  const int len = dot_partials_len(ctx);
+  if (Mpre.rows() != M)
+    throw std::runtime_error(
+        "spmv::pcg_sgs - Error: the preconditioner was built for "
+        + std::to_string(Mpre.rows()) + " rows, the matrix has "
+        + std::to_string(M));
+  // x is the iterate from the first kernel on: it cannot share b
+  if (ranges_overlap(x, b, M))
+    throw std::runtime_error("pcg_sgs: x overlaps b (x is updated in place)");
+
+  SgsWorkspace own(exec);
+  SgsWorkspace& w = workspace ? *workspace : own;
+  const bool x_aligned = is_aligned16(x);
+  w.ensure(M, N_padded, kmax, len, !x_aligned);
+  if (opt.time_spmv)
+    w.reserve_timing(kmax);
+
+  SolveStream guard(exec, w.stream); // every launch below goes to w.stream
+
+  throw_on_error(spmv_hip_pcg_ws_reset(w.ws, rtol, nullptr),
+                 "spmv_hip_pcg_ws_reset");
+  double* partials = nullptr;
+  throw_on_error(spmv_hip_pcg_ws_partials(w.ws, &partials),
+                 "spmv_hip_pcg_ws_partials");
+
+  double* const xi = x_aligned ? x : w.x;
+  // the ghost tail of p is defined here instead of relying on fresh pages
+  if (N_padded > M)
+    exec.memset<double>(w.p + M, 0, N_padded - M);
+  exec.memset<double>(w.dot2, 0, len);
+
+  // z = M^-1 r and the partials of r.z
+  auto precondition = [&] {
+    throw_on_error(spmv_hip_mcgs_apply_f64(ctx, Mpre.plan(), w.ws, w.r, w.z,
+                                           nullptr),
+                   "spmv_hip_mcgs_apply_f64");
+    throw_on_error(spmv_hip_sgs_dot_rz_f64(ctx, w.ws, M, w.r, w.z, nullptr),
+                   "spmv_hip_sgs_dot_rz_f64");
+  };
+
+  // r = b, x0 = 0, partials of r.r: one pass; then z0 = M^-1 r0 and p1 = z0
+  throw_on_error(spmv_hip_sgs_init_f64(ctx, w.ws, M, b, w.r, xi, nullptr),
+                 "spmv_hip_sgs_init_f64");
+  precondition();
+  exec.copy<double>(w.p, w.z, M);
+  w.flags[0] = 0;
+  w.flags[1] = -1;
+
+  // the state words alone (h == nullptr), or with the history of pairs
+  auto read = [&](double* h, size_t n) {
+    throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, h, n, nullptr),
+                   "spmv_hip_pcg_ws_read_async");
+  };
+
+  // {rz0, rr0}: one all-reduce of 2 doubles
+  throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, 0, nullptr),
+                 "spmv_hip_pcg_reduce_rz_rr");
+  comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, 0,
+                          "spmv_hip_pcg_ws_rz_rr"),
+                  2, w.stream);
+
+  std::vector<void*>& timing_ev = w.timing_ev;
+  LaggingPoll poll(exec, w, opt.poll_every, kmax);
+  int k = 0;
+  while (k < kmax && !poll.stopped) {
+    ++k;
+    col_l2g->update(w.p); // starts on the side stream
+    void* ev1 = nullptr;
+    if (opt.time_spmv) {
+      ev1 = timing_ev[2 * (size_t)(k - 1) + 1];
+      exec.record_event(timing_ev[2 * (size_t)(k - 1)], w.stream);
+    }
+    // Ap = A p with the p.Ap partials produced by the SpMV kernels themselves
+    // (local block's share + remote block's share) where they can
+    const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
+    if (!fused) {
+      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, w.p, w.Ap, partials,
+                                              nullptr),
+                     "spmv_hip_dot_partial_f64");
+      throw_on_error(spmv_hip_pcg_reduce_pAp(ctx, w.ws, k, nullptr),
+                     "spmv_hip_pcg_reduce_pAp");
+    } else {
+      throw_on_error(spmv_hip_pcg_reduce_pAp2(ctx, w.ws, k, w.dot2, nullptr),
+                     "spmv_hip_pcg_reduce_pAp2");
+    }
+    comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_pAp, k, "spmv_hip_pcg_ws_pAp"),
+                    1, w.stream);
+    throw_on_error(spmv_hip_sgs_update_r_f64(ctx, w.ws, k, M, w.Ap, w.r, nullptr),
+                   "spmv_hip_sgs_update_r_f64");
+    precondition();
+    throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, k, nullptr),
+                   "spmv_hip_pcg_reduce_rz_rr");
+    comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, k,
+                            "spmv_hip_pcg_ws_rz_rr"),
+                    2, w.stream); // rz[k] and rr[k] at once
+    throw_on_error(spmv_hip_cheb_update_xp_f64(ctx, w.ws, k, M, w.z, xi, w.p,
+                                               nullptr),
+                   "spmv_hip_cheb_update_xp_f64");
+
+    poll.step(k, read);
+  }
+
+  // final state: {done, kstop} and the history of pairs {rz[k], rr[k]}
+  const std::vector<double> zr
+      = read_history(spmv_hip_pcg_ws_capacity, w.ws, kmax, 2, read);
+  if (xi != x)
+    exec.copy<double>(x, xi, M);
+  exec.synchronize_stream(w.stream);
+
+  if (stats) {
+    *stats = CgStats();
+    if (opt.time_spmv)
+      sum_spmv_times(ctx, timing_ev, 2 * (size_t)k, *stats);
   }
 
   auto rr_at = [&](int j) { return zr[2 * (size_t)j + 1]; };

@@ -146,6 +146,20 @@ _PROTOS = {
                             f64, PTR(C.c_int), vp, vp, C.c_int, PTR(f64),
                             PTR(C.c_int)],
     "spmvh_lambda_max_estimate": [vp, vp, vp, vp, vp, C.c_int, PTR(f64)],
+    "spmvh_sgs_color": [vp, vp, i64, i64, C.c_int, vp, PTR(C.c_int)],
+    "spmvh_sgs_build_create": [vp, vp, vp, i64, i64, C.c_int, PTR(vp), vp],
+    "spmvh_sgs_build_get": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "spmvh_sgs_build_destroy": [vp],
+    "spmvh_sgs_create": [vp, vp, PTR(vp)],
+    "spmvh_sgs_destroy": [vp],
+    "spmvh_sgs_info": [vp, PTR(C.c_int), PTR(C.c_int), PTR(i64)],
+    "spmvh_sgs_colors": [vp, vp],
+    "spmvh_sgs_apply": [vp, vp, vp, vp],
+    "spmvh_sgs_workspace_create": [vp, PTR(vp)],
+    "spmvh_sgs_workspace_destroy": [vp],
+    "spmvh_sgs_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_pcg_sgs": [vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int), vp, vp,
+                      C.c_int, PTR(f64), PTR(C.c_int)],
     "spmvh_bicgstab_workspace_create": [vp, PTR(vp)],
     "spmvh_bicgstab_workspace_destroy": [vp],
     "spmvh_bicgstab_workspace_reserve_timing": [vp, C.c_int],
@@ -924,6 +938,116 @@ def lambda_max_estimate(comm, exec_, A, dinv_ptr, v0_ptr, steps):
     call("spmvh_lambda_max_estimate", comm.h, exec_.h, A.h, dinv_ptr or None,
          v0_ptr, int(steps), C.byref(lam))
     return lam.value
+
+
+def sgs_color(rowptr, colind, nrows, ncols_local=None, symmetric=False):
+    """spmv::sgs_color: the greedy colouring of the local diagonal block over
+    the pattern of B + B^T -> (colors[nrows], num_colors).  Host only."""
+    rp = np.ascontiguousarray(rowptr, np.int32)
+    ci = np.ascontiguousarray(colind, np.int32)
+    nrows = int(nrows)
+    colors = np.zeros(max(nrows, 1), np.int32)
+    nc = C.c_int()
+    call("spmvh_sgs_color", _np_ptr(rp), _np_ptr(ci), nrows,
+         nrows if ncols_local is None else int(ncols_local), int(bool(symmetric)),
+         _np_ptr(colors), C.byref(nc))
+    return colors[:nrows], nc.value
+
+
+def sgs_build(rowptr, colind, values, nrows, ncols_local=None, symmetric=False):
+    """spmv::sgs_build: the colouring and the colour-major copy -> dict(colors,
+    num_colors, perm, color_start, d, before=(ptr, col, val), after=(ptr, col,
+    val)); the parts are CSR over positions (row perm[pos]).  Host only."""
+    rp = np.ascontiguousarray(rowptr, np.int32)
+    ci = np.ascontiguousarray(colind, np.int32)
+    va = np.ascontiguousarray(values, np.float64)
+    n = int(nrows)
+    h = vp()
+    sizes = np.zeros(3, np.int64)
+    call("spmvh_sgs_build_create", _np_ptr(rp), _np_ptr(ci), _np_ptr(va), n,
+         n if ncols_local is None else int(ncols_local), int(bool(symmetric)),
+         C.byref(h), _np_ptr(sizes))
+    try:
+        nc, nb, na = (int(v) for v in sizes)
+        colors, perm = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        start, d = np.zeros(nc + 1, np.int32), np.zeros(n)
+        parts = [(np.zeros(n + 1, np.int64), np.zeros(m, np.int32), np.zeros(m))
+                 for m in (nb, na)]
+        call("spmvh_sgs_build_get", h, _np_ptr(colors), _np_ptr(perm),
+             _np_ptr(start), _np_ptr(d), *[_np_ptr(a) for p in parts for a in p])
+    finally:
+        call("spmvh_sgs_build_destroy", h)
+    return dict(colors=colors, num_colors=nc, perm=perm, color_start=start, d=d,
+                before=parts[0], after=parts[1])
+
+
+class SgsPreconditioner:
+    """spmv::SgsPreconditioner: the multicolour symmetric Gauss-Seidel
+    preconditioner of A's local diagonal block.  Owns its copy: A may
+    release_csr() afterwards.  Raises SpmvHostError ("diagonal is not
+    positive", "released", "same index range")."""
+
+    def __init__(self, exec_, A):
+        h = vp()
+        call("spmvh_sgs_create", exec_.h, A.h, C.byref(h))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            call("spmvh_sgs_destroy", self.h)
+            self.h = None
+
+    def _info(self):
+        rows, nc, nbytes = C.c_int(), C.c_int(), i64()
+        call("spmvh_sgs_info", self.h, C.byref(rows), C.byref(nc),
+             C.byref(nbytes))
+        return rows.value, nc.value, nbytes.value
+
+    def rows(self):
+        return self._info()[0]
+
+    def num_colors(self):
+        return self._info()[1]
+
+    def plan_bytes(self):
+        return self._info()[2]
+
+    def colors(self):
+        out = np.zeros(self.rows(), np.int32)
+        call("spmvh_sgs_colors", self.h, _np_ptr(out))
+        return out
+
+
+def sgs_apply(exec_, M, r_ptr, z_ptr):
+    """spmv::sgs_apply: z = M^-1 r on the executor's current stream; the host
+    does not wait."""
+    call("spmvh_sgs_apply", exec_.h, M.h, r_ptr, z_ptr)
+
+
+class SgsWorkspace(_TimedWorkspace):
+    """spmv::SgsWorkspace: work vectors kept across pcg_sgs() calls."""
+    _prefix = "sgs"
+
+
+def pcg_sgs(comm, exec_, A, M, b_ptr, x_ptr, kmax, rtol, workspace=None,
+            time_spmv=False, poll_every=0, stats=None):
+    """spmv::pcg_sgs: CG from x0 = 0 with the multicolour symmetric
+    Gauss-Seidel preconditioner M -> (k, rnorm_history), the history that of
+    the unpreconditioned residual.  stats (optional dict) receives
+    spmv_ms_total and spmv_launches of a time_spmv solve (one SpMV per
+    iteration)."""
+    kmax = int(kmax)
+    k, n = C.c_int(), C.c_int()
+    ms = f64()
+    hist = np.zeros(max(kmax, 0) + 1)
+    call("spmvh_pcg_sgs", comm.h, exec_.h, A.h, M.h, b_ptr, x_ptr, kmax,
+         float(rtol), C.byref(k), _np_ptr(hist),
+         workspace.h if workspace else None,
+         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         C.byref(n))
+    if stats is not None:
+        stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, hist[:k.value + 1]
 
 
 class BicgstabWorkspace(_TimedWorkspace):
