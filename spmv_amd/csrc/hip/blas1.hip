@@ -16,90 +16,15 @@
 //         vector in the workspace (8 N bytes: 1.07 GB at 512^3).
 //
 // Built with -ffp-contract=off: axpy/scal round like unfused BLAS-1.
-//
-// Streaming shape (measured with tools/membench on MI355X, 1-4 GiB vectors):
-// a persistent grid walks UNITS of kU x 4 KiB, every lane keeps kU 16-byte
-// loads per stream in flight, and vectors that cannot stay in the 256 MiB
-// Infinity Cache anyway are read and written non-temporally.  Against plain
-// 16-byte grid-stride loops this gave 4.6-4.9 -> 5.8-5.9 TB/s for the
-// two-read-one-write shape (r -= alpha Ap), 4.7-5.0 -> 5.6-5.7 TB/s for the
-// three-read-two-write shape (x, p update) and 6.3 -> 7.1 TB/s for dots.
+// Streaming shape: see blas1_stream.h.
 #include "common.h"
+#include "blas1_stream.h"
 
 #include <cmath>
 #include <new>
 
 namespace
 {
-
-__device__ __forceinline__ double block_sum(double v, double* s_red)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-    s_red[wave] = v;
-  __syncthreads();
-  double r = 0.0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w)
-      r += s_red[w];
-  }
-  return r; // valid in thread 0
-}
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-constexpr int kU = 4;                           // 16-B loads in flight per stream
-constexpr int64_t kUnit = (int64_t)kU * kBlock; // double2 elements per step
-
-template <bool NT>
-__device__ __forceinline__ f64x2 vload(const double* p, int64_t i2)
-{
-  const f64x2* q = reinterpret_cast<const f64x2*>(p) + i2;
-  return NT ? __builtin_nontemporal_load(q) : *q;
-}
-template <bool NT>
-__device__ __forceinline__ void vstore(double* p, int64_t i2, f64x2 v)
-{
-  f64x2* q = reinterpret_cast<f64x2*>(p) + i2;
-  if (NT)
-    __builtin_nontemporal_store(v, q);
-  else
-    *q = v;
-}
-
-// for (unit of this workgroup) { load phase ; compute + store phase }
-#define SPMV_FOR_UNITS(n2)                                                     \
-  for (int64_t base = (int64_t)blockIdx.x * kUnit; base < (n2);               \
-       base += (int64_t)gridDim.x * kUnit)
-#define SPMV_FOR_LANE_ELEMS(i, n2)                                             \
-  _Pragma("unroll") for (int u = 0; u < kU; ++u)                               \
-    if (const int64_t i = base + u * kBlock + threadIdx.x; i < (n2))
-
-// sum over the double2 elements [0, n2) of x . y : this thread's share
-template <bool NT>
-__device__ __forceinline__ double stream_dot(int64_t n2, const double* x,
-                                             const double* y)
-{
-  double acc = 0.0;
-  SPMV_FOR_UNITS(n2)
-  {
-    f64x2 a[kU], b[kU];
-    SPMV_FOR_LANE_ELEMS(i, n2)
-    {
-      a[u] = vload<NT>(x, i);
-      b[u] = vload<NT>(y, i);
-    }
-    SPMV_FOR_LANE_ELEMS(i, n2)
-    {
-      acc += a[u].x * b[u].x;
-      acc += a[u].y * b[u].y;
-    }
-  }
-  return acc;
-}
 
 // r += nalpha * Ap (cg.cpp:70), returns this thread's share of r.r (:73)
 template <bool NT>
@@ -160,17 +85,31 @@ __device__ __forceinline__ double stream_update_xr(int64_t n2, double alpha,
   return acc;
 }
 
-// p = beta p + r (cg.cpp:84-85)
+// x += alpha p (cg.cpp:69) over all n doubles: what an iteration that meets
+// the tolerance does to x while p stays (:80-81)
 template <bool NT>
-__device__ __forceinline__ void stream_update_p(int64_t n2, double beta,
-                                                const double* r, double* p)
+__device__ __forceinline__ void axpy_all(int64_t n, double alpha,
+                                         const double* p, double* x)
+{
+  stream_axpy<NT>(n >> 1, alpha, p, x);
+  if (odd_tail(n))
+    x[n - 1] += alpha * p[n - 1];
+}
+
+// p_out = beta p_in + r (cg.cpp:84-85): in place (p_out == p_in), or into the
+// OTHER p buffer while p_in stays
+template <bool NT>
+__device__ __forceinline__ void stream_update_p2(int64_t n2, double beta,
+                                                 const double* r,
+                                                 const double* p_in,
+                                                 double* p_out)
 {
   SPMV_FOR_UNITS(n2)
   {
     f64x2 pv[kU], rv[kU];
     SPMV_FOR_LANE_ELEMS(i, n2)
     {
-      pv[u] = vload<NT>(p, i);
+      pv[u] = vload<NT>(p_in, i);
       rv[u] = vload<NT>(r, i);
     }
     SPMV_FOR_LANE_ELEMS(i, n2)
@@ -179,29 +118,7 @@ __device__ __forceinline__ void stream_update_p(int64_t n2, double beta,
       pv[u].y = beta * pv[u].y;
       pv[u].x += rv[u].x;
       pv[u].y += rv[u].y;
-      vstore<NT>(p, i, pv[u]);
-    }
-  }
-}
-
-// x += alpha p (cg.cpp:69)
-template <bool NT>
-__device__ __forceinline__ void stream_axpy(int64_t n2, double alpha,
-                                            const double* p, double* x)
-{
-  SPMV_FOR_UNITS(n2)
-  {
-    f64x2 pv[kU], xv[kU];
-    SPMV_FOR_LANE_ELEMS(i, n2)
-    {
-      pv[u] = vload<NT>(p, i);
-      xv[u] = vload<NT>(x, i);
-    }
-    SPMV_FOR_LANE_ELEMS(i, n2)
-    {
-      xv[u].x += alpha * pv[u].x;
-      xv[u].y += alpha * pv[u].y;
-      vstore<NT>(x, i, xv[u]);
+      vstore<NT>(p_out, i, pv[u]);
     }
   }
 }
@@ -231,32 +148,6 @@ __device__ __forceinline__ void stream_update_xp(int64_t n2, double alpha,
       pv[u].x += rv[u].x;
       pv[u].y += rv[u].y;
       vstore<NT>(p, i, pv[u]);
-    }
-  }
-}
-
-// p_out = beta p_in + r (cg.cpp:84-85) into the OTHER p buffer; p_in stays
-template <bool NT>
-__device__ __forceinline__ void stream_update_p2(int64_t n2, double beta,
-                                                 const double* r,
-                                                 const double* p_in,
-                                                 double* p_out)
-{
-  SPMV_FOR_UNITS(n2)
-  {
-    f64x2 pv[kU], rv[kU];
-    SPMV_FOR_LANE_ELEMS(i, n2)
-    {
-      pv[u] = vload<NT>(p_in, i);
-      rv[u] = vload<NT>(r, i);
-    }
-    SPMV_FOR_LANE_ELEMS(i, n2)
-    {
-      pv[u].x = beta * pv[u].x;
-      pv[u].y = beta * pv[u].y;
-      pv[u].x += rv[u].x;
-      pv[u].y += rv[u].y;
-      vstore<NT>(p_out, i, pv[u]);
     }
   }
 }
@@ -299,13 +190,6 @@ __device__ __forceinline__ void stream_update_x2p(int64_t n2, double alpha0,
   }
 }
 
-__device__ __forceinline__ void clear_partials_tail(double* partials, int len)
-{
-  for (int i = gridDim.x + blockIdx.x * blockDim.x + threadIdx.x; i < len;
-       i += gridDim.x * blockDim.x)
-    partials[i] = 0.0;
-}
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void gather_kernel(
     int n, const int32_t* __restrict__ indices, const T* __restrict__ in,
@@ -335,7 +219,7 @@ __global__ __launch_bounds__(kBlock) void dot_partial_kernel(
 {
   __shared__ double s_red[kBlock / 64];
   double acc = stream_dot<NT>(n >> 1, x, y);
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+  if (odd_tail(n))
     acc += x[n - 1] * y[n - 1];
   spmv_dot_epilogue(dot, acc, s_red);
 }
@@ -348,10 +232,7 @@ __global__ __launch_bounds__(kBlock) void reduce_partials_kernel(
   __shared__ double s_red[kBlock / 64];
   if (done && *done)
     return;
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < len; i += kBlock)
-    acc += partials[i];
-  double s = block_sum(acc, s_red);
+  const double s = sum_partials(partials, nullptr, len, s_red);
   if (threadIdx.x == 0)
     *result = s;
 }
@@ -362,6 +243,47 @@ struct CgScalars {
   int32_t done;
   int32_t kstop;
 };
+
+// What the first kernel of iteration k finds about iteration k - 1: the solve
+// stops there when rr[k-1] met the tolerance (cg.cpp:80-81; k >= 2).  Uniform
+// across the grid: every thread reads the same words.
+__device__ __forceinline__ bool stopped_before(const double* __restrict__ rr,
+                                               int k,
+                                               const CgScalars* __restrict__ sc)
+{
+  if (k >= 2) {
+    const double rnorm0 = sqrt(rr[0]);
+    const double rnorm_prev = sqrt(rr[k - 1]);
+    if (rnorm_prev / rnorm0 < sc->rtol)
+      return true;
+  }
+  return false;
+}
+
+// alpha, beta and the stopping test of iteration k from its scalars
+struct CgStep {
+  double alpha, beta;
+  bool converged;
+};
+__device__ __forceinline__ CgStep cg_step(double rr0, double rr_old,
+                                          double rr_new, double pap, double rtol)
+{
+  const double rnorm0 = sqrt(rr0);
+  const double rnorm_old = sqrt(rr_old);
+  const double rnorm_new = sqrt(rr_new);                           // cg.cpp:76
+  CgStep s;
+  s.alpha = (rnorm_old * rnorm_old) / pap;                         // :66
+  s.beta = (rnorm_new * rnorm_new) / (rnorm_old * rnorm_old);      // :77
+  s.converged = rnorm_new / rnorm0 < rtol;                         // :80
+  return s;
+}
+
+// alpha of iteration k (cg.cpp:50,76 ; :66)
+__device__ __forceinline__ double cg_alpha(double rr_old, double pap)
+{
+  const double rnorm_old = sqrt(rr_old);
+  return (rnorm_old * rnorm_old) / pap;
+}
 
 // x += alpha p ; r += (-alpha) Ap ; partial r.r
 template <bool NT>
@@ -375,21 +297,17 @@ __global__ __launch_bounds__(kBlock) void cg_update_xr_kernel(
   __shared__ double s_red[kBlock / 64];
   if (sc->done)
     return;
-  const double rnorm_old = sqrt(*rr_prev);             // cg.cpp:50,76
-  const double alpha = (rnorm_old * rnorm_old) / *pAp; // cg.cpp:66
+  const double alpha = cg_alpha(*rr_prev, *pAp);
   const double nalpha = -alpha;
   double acc = stream_update_xr<NT>(n >> 1, alpha, nalpha, p, Ap, x, r);
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (odd_tail(n)) {
     const int64_t i = n - 1;
     x[i] += alpha * p[i];
     double rv = r[i] + nalpha * Ap[i];
     r[i] = rv;
     acc += rv * rv;
   }
-  double s = block_sum(acc, s_red);
-  if (threadIdx.x == 0)
-    partials[blockIdx.x] = s;
-  clear_partials_tail(partials, len);
+  spmv_dot_epilogue(DotOut{partials, len}, acc, s_red);
 }
 
 // stopping test on rr[k], then p = beta p + r
@@ -408,8 +326,8 @@ __global__ __launch_bounds__(kBlock) void cg_update_p_kernel(
   const double beta = (rnorm_new * rnorm_new) / (rnorm_old * rnorm_old); // :77
   if (rnorm_new / rnorm0 < sc->rtol)                                // :80
     return; // p is left untouched (:81); cg_reduce_pAp_kernel raises `done`
-  stream_update_p<NT>(n >> 1, beta, r, p);
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  stream_update_p2<NT>(n >> 1, beta, r, p, p);
+  if (odd_tail(n)) {
     const int64_t i = n - 1;
     p[i] = beta * p[i] + r[i];
   }
@@ -421,6 +339,45 @@ __global__ __launch_bounds__(kBlock) void cg_update_p_kernel(
 // Element-wise arithmetic and its order per element are unchanged; only the
 // kernel an update lives in differs (8 instead of 9 vector passes).  x is
 // still updated in the iteration that converges and p is not (cg.cpp:80-81).
+
+// body of update_r / update_r_cs behind their prologues
+template <bool NT>
+__device__ __forceinline__ void update_r_body(int64_t n, double nalpha,
+                                              const double* __restrict__ Ap,
+                                              double* __restrict__ r,
+                                              double* __restrict__ partials,
+                                              int len, double* s_red)
+{
+  double acc = stream_update_r<NT>(n >> 1, nalpha, Ap, r);
+  if (odd_tail(n)) {
+    const int64_t i = n - 1;
+    double rv = r[i] + nalpha * Ap[i];
+    r[i] = rv;
+    acc += rv * rv;
+  }
+  spmv_dot_epilogue(DotOut{partials, len}, acc, s_red);
+}
+
+// body of update_xp / update_xp_cs: rr_new is iteration k's
+template <bool NT>
+__device__ __forceinline__ void update_xp_body(
+    int64_t n, double rr0, double rr_old, double rr_new, double pap,
+    double rtol, const double* __restrict__ r, double* __restrict__ x,
+    double* __restrict__ p)
+{
+  const CgStep s = cg_step(rr0, rr_old, rr_new, pap, rtol);
+  if (s.converged) { // x takes this iteration's update, p stays (:80-81)
+    axpy_all<NT>(n, s.alpha, p, x);
+    return;
+  }
+  stream_update_xp<NT>(n >> 1, s.alpha, s.beta, r, x, p);
+  if (odd_tail(n)) {
+    const int64_t i = n - 1;
+    x[i] += s.alpha * p[i];
+    p[i] = s.beta * p[i] + r[i];
+  }
+}
+
 template <bool NT>
 __global__ __launch_bounds__(kBlock) void cg_update_r_kernel(
     int64_t n, const double* __restrict__ rr_prev,
@@ -431,20 +388,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_r_kernel(
   __shared__ double s_red[kBlock / 64];
   if (sc->done)
     return;
-  const double rnorm_old = sqrt(*rr_prev);
-  const double alpha = (rnorm_old * rnorm_old) / *pAp; // cg.cpp:66
-  const double nalpha = -alpha;
-  double acc = stream_update_r<NT>(n >> 1, nalpha, Ap, r);
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    double rv = r[i] + nalpha * Ap[i];
-    r[i] = rv;
-    acc += rv * rv;
-  }
-  double s = block_sum(acc, s_red);
-  if (threadIdx.x == 0)
-    partials[blockIdx.x] = s;
-  clear_partials_tail(partials, len);
+  update_r_body<NT>(n, -cg_alpha(*rr_prev, *pAp), Ap, r, partials, len, s_red);
 }
 
 template <bool NT>
@@ -457,29 +401,12 @@ __global__ __launch_bounds__(kBlock) void cg_update_xp_kernel(
 {
   if (sc->done)
     return;
-  const double rnorm0 = sqrt(*rr0);
-  const double rnorm_old = sqrt(*rr_prev);
-  const double rnorm_new = sqrt(*rr_new);                                // :76
-  const double alpha = (rnorm_old * rnorm_old) / *pAp;                   // :66
-  const double beta = (rnorm_new * rnorm_new) / (rnorm_old * rnorm_old); // :77
-  const bool converged = rnorm_new / rnorm0 < sc->rtol;                  // :80
-  if (converged) { // x takes this iteration's update, p stays (:80-81)
-    stream_axpy<NT>(n >> 1, alpha, p, x);
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
-      x[n - 1] += alpha * p[n - 1];
-    return;
-  }
-  stream_update_xp<NT>(n >> 1, alpha, beta, r, x, p);
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    x[i] += alpha * p[i];
-    p[i] = beta * p[i] + r[i];
-  }
+  update_xp_body<NT>(n, *rr0, *rr_prev, *rr_new, *pAp, sc->rtol, r, x, p);
 }
 
 // Reduces the p.Ap partials of iteration k.  It is the first single-workgroup
 // kernel after the p-update of iteration k-1, so it also raises `done` when
-// rr[k-1] met the tolerance (cg.cpp:80-81): every later cg_* kernel then
+// rr[k-1] met the tolerance (see stopped_before): every later cg_* kernel then
 // returns at once and x, r, p keep their iteration-(k-1) values.  In-order
 // stream execution makes the flag visible to the following launches.
 __global__ __launch_bounds__(kBlock) void cg_reduce_pAp_kernel(
@@ -491,24 +418,14 @@ __global__ __launch_bounds__(kBlock) void cg_reduce_pAp_kernel(
   __shared__ double s_red[kBlock / 64];
   if (sc->done)
     return;
-  if (k >= 2) {
-    const double rnorm0 = sqrt(rr[0]);
-    const double rnorm_prev = sqrt(rr[k - 1]);
-    if (rnorm_prev / rnorm0 < sc->rtol) { // uniform across the workgroup
-      if (threadIdx.x == 0) {
-        sc->kstop = k - 1;
-        sc->done = 1;
-      }
-      return;
+  if (stopped_before(rr, k, sc)) { // uniform across the workgroup
+    if (threadIdx.x == 0) {
+      sc->kstop = k - 1;
+      sc->done = 1;
     }
+    return;
   }
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < len; i += kBlock)
-    acc += partials[i];
-  if (partials2) // the remote block's share of p.Ap
-    for (int i = threadIdx.x; i < len; i += kBlock)
-      acc += partials2[i];
-  double s = block_sum(acc, s_red);
+  const double s = sum_partials(partials, partials2, len, s_red);
   if (threadIdx.x == 0)
     pAp[k] = s;
 }
@@ -516,27 +433,11 @@ __global__ __launch_bounds__(kBlock) void cg_reduce_pAp_kernel(
 // ---- consumer-side reductions (one rank) -----------------------------------
 // Instead of a single-workgroup reducer launch between producer and consumer,
 // EVERY workgroup of the consuming kernel adds the <= 2048 partials itself, in
-// the reducers' order (same loop, same tree => the same bits), and workgroup 0
-// records the value in the history.  16 KB of L2-resident reads per workgroup
-// against two kernel launches per iteration: what a small problem spends most
-// of its iteration on.  Needs the scalar on this rank only, so it is used when
-// the communicator has one rank.
-__device__ __forceinline__ double consume_partials(
-    const double* __restrict__ partials, const double* __restrict__ partials2,
-    int len, double* s_red, double* s_bcast)
-{
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < len; i += kBlock)
-    acc += partials[i];
-  if (partials2)
-    for (int i = threadIdx.x; i < len; i += kBlock)
-      acc += partials2[i];
-  const double s = block_sum(acc, s_red);
-  if (threadIdx.x == 0)
-    *s_bcast = s;
-  __syncthreads();
-  return *s_bcast;
-}
+// the reducers' order (consume_partials: same loop, same tree => the same
+// bits), and workgroup 0 records the value in the history.  16 KB of
+// L2-resident reads per workgroup against two kernel launches per iteration:
+// what a small problem spends most of its iteration on.  Needs the scalar on
+// this rank only, so it is used when the communicator has one rank.
 
 // cg_reduce_pAp_kernel + cg_update_r_kernel in one launch
 template <bool NT>
@@ -551,36 +452,19 @@ __global__ __launch_bounds__(kBlock) void cg_update_r_cs_kernel(
   __shared__ double s_bcast;
   if (sc->done)
     return;
-  if (k >= 2) { // cg.cpp:80-81 of iteration k-1, as cg_reduce_pAp_kernel
-    const double rnorm0 = sqrt(rr[0]);
-    const double rnorm_prev = sqrt(rr[k - 1]);
-    if (rnorm_prev / rnorm0 < sc->rtol) { // uniform across the grid
-      if (blockIdx.x == 0 && threadIdx.x == 0) {
-        sc->kstop = k - 1;
-        sc->done = 1;
-      }
-      return;
+  if (stopped_before(rr, k, sc)) { // uniform across the grid
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      sc->kstop = k - 1;
+      sc->done = 1;
     }
+    return;
   }
   const double pap
       = consume_partials(pap_partials, pap_partials2, len, s_red, &s_bcast);
   if (blockIdx.x == 0 && threadIdx.x == 0)
     pAp[k] = pap;
-  const double rnorm_old = sqrt(rr[k - 1]);
-  const double alpha = (rnorm_old * rnorm_old) / pap; // cg.cpp:66
-  const double nalpha = -alpha;
-  double acc = stream_update_r<NT>(n >> 1, nalpha, Ap, r);
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    double rv = r[i] + nalpha * Ap[i];
-    r[i] = rv;
-    acc += rv * rv;
-  }
-  __syncthreads(); // s_red is reused
-  double s = block_sum(acc, s_red);
-  if (threadIdx.x == 0)
-    rr_partials[blockIdx.x] = s;
-  clear_partials_tail(rr_partials, len);
+  update_r_body<NT>(n, -cg_alpha(rr[k - 1], pap), Ap, r, rr_partials, len,
+                    s_red);
 }
 
 // reduce_partials_kernel (r.r) + cg_update_xp_kernel in one launch
@@ -598,24 +482,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_xp_cs_kernel(
       = consume_partials(rr_partials, nullptr, len, s_red, &s_bcast);
   if (blockIdx.x == 0 && threadIdx.x == 0)
     rr[k] = rr_new;
-  const double rnorm0 = sqrt(rr[0]);
-  const double rnorm_old = sqrt(rr[k - 1]);
-  const double rnorm_new = sqrt(rr_new);                                 // :76
-  const double alpha = (rnorm_old * rnorm_old) / pAp[k];                 // :66
-  const double beta = (rnorm_new * rnorm_new) / (rnorm_old * rnorm_old); // :77
-  const bool converged = rnorm_new / rnorm0 < sc->rtol;                  // :80
-  if (converged) { // x takes this iteration's update, p stays (:80-81)
-    stream_axpy<NT>(n >> 1, alpha, p, x);
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
-      x[n - 1] += alpha * p[n - 1];
-    return;
-  }
-  stream_update_xp<NT>(n >> 1, alpha, beta, r, x, p);
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    x[i] += alpha * p[i];
-    p[i] = beta * p[i] + r[i];
-  }
+  update_xp_body<NT>(n, rr[0], rr[k - 1], rr_new, pAp[k], sc->rtol, r, x, p);
 }
 
 // ---- the x update deferred by one iteration (one rank, CgOptions::defer_x) --
@@ -648,22 +515,15 @@ __global__ __launch_bounds__(kBlock) void cg_update_p2_cs_kernel(
       = consume_partials(rr_partials, nullptr, len, s_red, &s_bcast);
   if (blockIdx.x == 0 && threadIdx.x == 0)
     rr[k] = rr_new;
-  const double rnorm0 = sqrt(rr[0]);
-  const double rnorm_old = sqrt(rr[k - 1]);
-  const double rnorm_new = sqrt(rr_new);                                 // :76
-  const double alpha = (rnorm_old * rnorm_old) / pAp[k];                 // :66
-  const double beta = (rnorm_new * rnorm_new) / (rnorm_old * rnorm_old); // :77
-  const bool converged = rnorm_new / rnorm0 < sc->rtol;                  // :80
-  if (converged) { // x takes this iteration's update now, p stays (:80-81)
-    stream_axpy<NT>(n >> 1, alpha, p_in, x);
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
-      x[n - 1] += alpha * p_in[n - 1];
+  const CgStep s = cg_step(rr[0], rr[k - 1], rr_new, pAp[k], sc->rtol);
+  if (s.converged) { // x takes this iteration's update now, p stays (:80-81)
+    axpy_all<NT>(n, s.alpha, p_in, x);
     return;
   }
-  stream_update_p2<NT>(n >> 1, beta, r, p_in, p_out);
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  stream_update_p2<NT>(n >> 1, s.beta, r, p_in, p_out);
+  if (odd_tail(n)) {
     const int64_t i = n - 1;
-    p_out[i] = beta * p_in[i] + r[i];
+    p_out[i] = s.beta * p_in[i] + r[i];
   }
 }
 
@@ -683,31 +543,25 @@ __global__ __launch_bounds__(kBlock) void cg_update_x2p_cs_kernel(
       = consume_partials(rr_partials, nullptr, len, s_red, &s_bcast);
   if (blockIdx.x == 0 && threadIdx.x == 0)
     rr[k] = rr_new;
-  const double rnorm0 = sqrt(rr[0]);
-  const double rnorm_old2 = sqrt(rr[k - 2]);
-  const double rnorm_old = sqrt(rr[k - 1]);
-  const double rnorm_new = sqrt(rr_new);                                 // :76
-  const double alpha_prev = (rnorm_old2 * rnorm_old2) / pAp[k - 1]; // :66, k-1
-  const double alpha = (rnorm_old * rnorm_old) / pAp[k];                 // :66
-  const double beta = (rnorm_new * rnorm_new) / (rnorm_old * rnorm_old); // :77
-  const bool converged = rnorm_new / rnorm0 < sc->rtol;                  // :80
-  const bool tail = (n & 1) && blockIdx.x == 0 && threadIdx.x == 0;
+  const double alpha_prev = cg_alpha(rr[k - 2], pAp[k - 1]); // :66, k-1
+  const CgStep s = cg_step(rr[0], rr[k - 1], rr_new, pAp[k], sc->rtol);
+  const bool tail = odd_tail(n);
   const int64_t i = n - 1;
-  if (converged) { // x takes both updates, p stays (:80-81)
-    stream_update_x2p<NT, false>(n >> 1, alpha_prev, alpha, beta, r, x, p_prev,
-                                 p_cur);
+  if (s.converged) { // x takes both updates, p stays (:80-81)
+    stream_update_x2p<NT, false>(n >> 1, alpha_prev, s.alpha, s.beta, r, x,
+                                 p_prev, p_cur);
     if (tail) {
       x[i] += alpha_prev * p_prev[i];
-      x[i] += alpha * p_cur[i];
+      x[i] += s.alpha * p_cur[i];
     }
     return;
   }
-  stream_update_x2p<NT, true>(n >> 1, alpha_prev, alpha, beta, r, x, p_prev,
+  stream_update_x2p<NT, true>(n >> 1, alpha_prev, s.alpha, s.beta, r, x, p_prev,
                               p_cur);
   if (tail) {
     x[i] += alpha_prev * p_prev[i];
-    x[i] += alpha * p_cur[i];
-    p_prev[i] = beta * p_cur[i] + r[i];
+    x[i] += s.alpha * p_cur[i];
+    p_prev[i] = s.beta * p_cur[i] + r[i];
   }
 }
 
@@ -729,9 +583,7 @@ __global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(
   if (rnorm_new / rnorm0 < sc->rtol) // :80, as cg_update_p2_cs_kernel
     return;
   const double alpha = (rnorm_old * rnorm_old) / pAp[k]; // :66
-  stream_axpy<NT>(n >> 1, alpha, p, x);
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
-    x[n - 1] += alpha * p[n - 1];
+  axpy_all<NT>(n, alpha, p, x);
 }
 
 // CG start (cg.cpp:39-50) in one pass over b: r = p = b, x0 = 0 (defined here
@@ -747,21 +599,12 @@ __global__ __launch_bounds__(kBlock) void cg_init_kernel(
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     const double v = b[i];
-    if constexpr (NT) {
-      __builtin_nontemporal_store(v, &r[i]);
-      __builtin_nontemporal_store(v, &p[i]);
-      __builtin_nontemporal_store(0.0, &x[i]);
-    } else {
-      r[i] = v;
-      p[i] = v;
-      x[i] = 0.0;
-    }
+    sstore<NT>(&r[i], v);
+    sstore<NT>(&p[i], v);
+    sstore<NT>(&x[i], 0.0);
     acc += v * v;
   }
-  double s = block_sum(acc, s_red);
-  if (threadIdx.x == 0)
-    partials[blockIdx.x] = s;
-  clear_partials_tail(partials, len);
+  spmv_dot_epilogue(DotOut{partials, len}, acc, s_red);
 }
 
 // ---- mixed-precision CG support -----------------------------
@@ -801,10 +644,7 @@ __global__ __launch_bounds__(kBlock) void cg_residual_kernel(
     r[i] = rv;
     acc += rv * rv;
   }
-  double s = block_sum(acc, s_red);
-  if (threadIdx.x == 0)
-    partials[blockIdx.x] = s;
-  clear_partials_tail(partials, len);
+  spmv_dot_epilogue(DotOut{partials, len}, acc, s_red);
 }
 
 __global__ void cg_reset_kernel(CgScalars* sc, double rtol, double* rr,
@@ -841,9 +681,22 @@ __global__ __launch_bounds__(kBlock) void fill_const_kernel(
     x[k] = value;
 }
 
-bool aligned16(const void* p)
+// the four index kernels' entry points: gather / scatter_add, f64 / f32
+template <typename T>
+int launch_indexed(void (*kernel)(int, const int32_t*, const T*, T*),
+                   spmv_hip_ctx* ctx, int num_indices, const int32_t* indices,
+                   const T* in, T* out, void* stream)
 {
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+  SPMV_SET_DEVICE(ctx);
+  SPMV_REQUIRE(num_indices >= 0);
+  if (num_indices == 0)
+    return SPMV_HIP_OK;
+  SPMV_REQUIRE(indices && in && out);
+  const int grid = spmv_grid_for(ctx, num_indices, kBlock);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0,
+                     spmv_stream(ctx, stream), num_indices, indices, in, out);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
 }
 
 } // namespace
@@ -858,82 +711,38 @@ struct spmv_hip_cg_ws {
   CgScalars* sc = nullptr;
 };
 
-// Vectors of at least ctx->blas1_nt_min_elems doubles stream past the caches
-// (non-temporal loads and stores); shorter ones stay cached between kernels.
-#define SPMV_LAUNCH_NT(ctx, n, kernel, grid, st, ...)                          \
-  do {                                                                         \
-    if ((int64_t)(n) >= (ctx)->blas1_nt_min_elems)                             \
-      hipLaunchKernelGGL(kernel<true>, dim3(grid), dim3(kBlock), 0, st,        \
-                         __VA_ARGS__);                                         \
-    else                                                                       \
-      hipLaunchKernelGGL(kernel<false>, dim3(grid), dim3(kBlock), 0, st,       \
-                         __VA_ARGS__);                                         \
-  } while (0)
-
 extern "C" {
 
 int spmv_hip_gather_f64(spmv_hip_ctx* ctx, int num_indices,
                         const int32_t* indices, const double* in, double* out,
                         void* stream)
 {
-  SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(num_indices >= 0);
-  if (num_indices == 0)
-    return SPMV_HIP_OK;
-  SPMV_REQUIRE(indices && in && out);
-  const int grid = spmv_grid_for(ctx, num_indices, kBlock);
-  hipLaunchKernelGGL((gather_kernel<double>), dim3(grid), dim3(kBlock), 0,
-                     spmv_stream(ctx, stream), num_indices, indices, in, out);
-  SPMV_CHECK_LAUNCH();
-  return SPMV_HIP_OK;
+  return launch_indexed(gather_kernel<double>, ctx, num_indices, indices, in,
+                        out, stream);
 }
 
 int spmv_hip_scatter_add_f64(spmv_hip_ctx* ctx, int num_indices,
                              const int32_t* indices, const double* in,
                              double* out, void* stream)
 {
-  SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(num_indices >= 0);
-  if (num_indices == 0)
-    return SPMV_HIP_OK;
-  SPMV_REQUIRE(indices && in && out);
-  const int grid = spmv_grid_for(ctx, num_indices, kBlock);
-  hipLaunchKernelGGL((scatter_add_kernel<double>), dim3(grid), dim3(kBlock), 0,
-                     spmv_stream(ctx, stream), num_indices, indices, in, out);
-  SPMV_CHECK_LAUNCH();
-  return SPMV_HIP_OK;
+  return launch_indexed(scatter_add_kernel<double>, ctx, num_indices, indices,
+                        in, out, stream);
 }
 
 int spmv_hip_scatter_add_f32(spmv_hip_ctx* ctx, int num_indices,
                              const int32_t* indices, const float* in,
                              float* out, void* stream)
 {
-  SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(num_indices >= 0);
-  if (num_indices == 0)
-    return SPMV_HIP_OK;
-  SPMV_REQUIRE(indices && in && out);
-  const int grid = spmv_grid_for(ctx, num_indices, kBlock);
-  hipLaunchKernelGGL((scatter_add_kernel<float>), dim3(grid), dim3(kBlock), 0,
-                     spmv_stream(ctx, stream), num_indices, indices, in, out);
-  SPMV_CHECK_LAUNCH();
-  return SPMV_HIP_OK;
+  return launch_indexed(scatter_add_kernel<float>, ctx, num_indices, indices,
+                        in, out, stream);
 }
 
 int spmv_hip_gather_f32(spmv_hip_ctx* ctx, int num_indices,
                         const int32_t* indices, const float* in, float* out,
                         void* stream)
 {
-  SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(num_indices >= 0);
-  if (num_indices == 0)
-    return SPMV_HIP_OK;
-  SPMV_REQUIRE(indices && in && out);
-  const int grid = spmv_grid_for(ctx, num_indices, kBlock);
-  hipLaunchKernelGGL((gather_kernel<float>), dim3(grid), dim3(kBlock), 0,
-                     spmv_stream(ctx, stream), num_indices, indices, in, out);
-  SPMV_CHECK_LAUNCH();
-  return SPMV_HIP_OK;
+  return launch_indexed(gather_kernel<float>, ctx, num_indices, indices, in,
+                        out, stream);
 }
 
 int spmv_hip_dot_partials_len(const spmv_hip_ctx* ctx, int* len)
@@ -948,12 +757,12 @@ int spmv_hip_dot_partial_f64(spmv_hip_ctx* ctx, int64_t n, const double* x,
 {
   SPMV_SET_DEVICE(ctx);
   SPMV_REQUIRE(n >= 0 && partials && (n == 0 || (x && y)));
-  SPMV_REQUIRE(aligned16(x) && aligned16(y));
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
+  SPMV_REQUIRE(aligned16(x, y));
   DotOut dot;
   dot.partials = partials;
   dot.len = ctx->dot_blocks;
-  SPMV_LAUNCH_NT(ctx, n, dot_partial_kernel, grid, spmv_stream(ctx, stream), n, x, y, dot);
+  SPMV_LAUNCH_NT(ctx, n, dot_partial_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, x, y, dot);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -967,8 +776,8 @@ int spmv_hip_cg_init_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int64_t n,
   int grid = spmv_grid_for(ctx, n, kBlock);
   if (grid > ctx->dot_blocks)
     grid = ctx->dot_blocks;
-  SPMV_LAUNCH_NT(ctx, n, cg_init_kernel, grid, spmv_stream(ctx, stream), n, b, r,
-                 p, x, ws->partials, ctx->dot_blocks);
+  SPMV_LAUNCH_NT(ctx, n, cg_init_kernel, grid, spmv_stream(ctx, stream), n, b,
+                 r, p, x, ws->partials, ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -1148,7 +957,7 @@ int spmv_hip_cg_reduce_rr(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                           void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 0 && k <= ws->kmax);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 0);
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(kBlock), 0,
                      spmv_stream(ctx, stream), ws->partials, ctx->dot_blocks,
                      ws->rr + k, &ws->sc->done);
@@ -1160,7 +969,7 @@ int spmv_hip_cg_reduce_pAp(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                            void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   hipLaunchKernelGGL(cg_reduce_pAp_kernel, dim3(1), dim3(kBlock), 0,
                      spmv_stream(ctx, stream), ws->partials,
                      (const double*)nullptr, ctx->dot_blocks, k, ws->rr,
@@ -1173,7 +982,8 @@ int spmv_hip_cg_reduce_pAp2(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                             const double* partials2, void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && partials2);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
+  SPMV_REQUIRE(partials2);
   hipLaunchKernelGGL(cg_reduce_pAp_kernel, dim3(1), dim3(kBlock), 0,
                      spmv_stream(ctx, stream), ws->partials, partials2,
                      ctx->dot_blocks, k, ws->rr, ws->pAp, ws->sc);
@@ -1186,13 +996,12 @@ int spmv_hip_cg_update_xr_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                               double* x, double* r, void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && n >= 0);
-  SPMV_REQUIRE(n == 0 || (p && Ap && x && r));
-  SPMV_REQUIRE(aligned16(p) && aligned16(Ap) && aligned16(x) && aligned16(r));
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, cg_update_xr_kernel, grid, spmv_stream(ctx, stream), n, ws->rr + (k - 1),
-                     ws->pAp + k, ws->sc, p, Ap, x, r, ws->partials,
-                     ctx->dot_blocks);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (p && Ap && x && r)));
+  SPMV_REQUIRE(aligned16(p, Ap, x, r));
+  SPMV_LAUNCH_NT(ctx, n, cg_update_xr_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, ws->rr + (k - 1), ws->pAp + k,
+                 ws->sc, p, Ap, x, r, ws->partials, ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -1202,13 +1011,12 @@ int spmv_hip_cg_update_p_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                              void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && n >= 0);
-  SPMV_REQUIRE(n == 0 || (r && p));
-  SPMV_REQUIRE(aligned16(r) && aligned16(p));
-  hipStream_t st = spmv_stream(ctx, stream);
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, cg_update_p_kernel, grid, st, n, k,
-                     ws->rr, ws->rr + (k - 1), ws->rr + k, ws->sc, r, p);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (r && p)));
+  SPMV_REQUIRE(aligned16(r, p));
+  SPMV_LAUNCH_NT(ctx, n, cg_update_p_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, k, ws->rr, ws->rr + (k - 1),
+                 ws->rr + k, ws->sc, r, p);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -1218,12 +1026,12 @@ int spmv_hip_cg_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                              void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && n >= 0);
-  SPMV_REQUIRE(n == 0 || (Ap && r));
-  SPMV_REQUIRE(aligned16(Ap) && aligned16(r));
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, cg_update_r_kernel, grid, spmv_stream(ctx, stream), n, ws->rr + (k - 1), ws->pAp + k,
-                     ws->sc, Ap, r, ws->partials, ctx->dot_blocks);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (Ap && r)));
+  SPMV_REQUIRE(aligned16(Ap, r));
+  SPMV_LAUNCH_NT(ctx, n, cg_update_r_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, ws->rr + (k - 1), ws->pAp + k,
+                 ws->sc, Ap, r, ws->partials, ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -1233,12 +1041,12 @@ int spmv_hip_cg_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                               void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && n >= 0);
-  SPMV_REQUIRE(n == 0 || (r && x && p));
-  SPMV_REQUIRE(aligned16(r) && aligned16(x) && aligned16(p));
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, cg_update_xp_kernel, grid, spmv_stream(ctx, stream), n, k, ws->rr, ws->rr + (k - 1),
-                     ws->rr + k, ws->pAp + k, ws->sc, r, x, p);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (r && x && p)));
+  SPMV_REQUIRE(aligned16(r, x, p));
+  SPMV_LAUNCH_NT(ctx, n, cg_update_xp_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, k, ws->rr, ws->rr + (k - 1),
+                 ws->rr + k, ws->pAp + k, ws->sc, r, x, p);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -1248,13 +1056,13 @@ int spmv_hip_cg_update_r_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                                 const double* pap_partials2, void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && n >= 0);
-  SPMV_REQUIRE(n == 0 || (Ap && r));
-  SPMV_REQUIRE(aligned16(Ap) && aligned16(r));
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, cg_update_r_cs_kernel, grid, spmv_stream(ctx, stream),
-                 n, k, ws->rr, ws->pAp, ws->sc, ws->partials, pap_partials2,
-                 ctx->dot_blocks, Ap, r, ws->partials_rr);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (Ap && r)));
+  SPMV_REQUIRE(aligned16(Ap, r));
+  SPMV_LAUNCH_NT(ctx, n, cg_update_r_cs_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, k, ws->rr, ws->pAp, ws->sc,
+                 ws->partials, pap_partials2, ctx->dot_blocks, Ap, r,
+                 ws->partials_rr);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -1264,13 +1072,12 @@ int spmv_hip_cg_update_xp_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                                  double* p, void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && n >= 0);
-  SPMV_REQUIRE(n == 0 || (r && x && p));
-  SPMV_REQUIRE(aligned16(r) && aligned16(x) && aligned16(p));
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, cg_update_xp_cs_kernel, grid, spmv_stream(ctx, stream),
-                 n, k, ws->rr, ws->pAp, ws->sc, ws->partials_rr,
-                 ctx->dot_blocks, r, x, p);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (r && x && p)));
+  SPMV_REQUIRE(aligned16(r, x, p));
+  SPMV_LAUNCH_NT(ctx, n, cg_update_xp_cs_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, k, ws->rr, ws->pAp, ws->sc,
+                 ws->partials_rr, ctx->dot_blocks, r, x, p);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -1281,14 +1088,13 @@ int spmv_hip_cg_update_p2_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                                  void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && n >= 0);
-  SPMV_REQUIRE(n == 0 || (r && x && p_in && p_out && p_in != p_out));
-  SPMV_REQUIRE(aligned16(r) && aligned16(x) && aligned16(p_in)
-               && aligned16(p_out));
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, cg_update_p2_cs_kernel, grid, spmv_stream(ctx, stream),
-                 n, k, ws->rr, ws->pAp, ws->sc, ws->partials_rr,
-                 ctx->dot_blocks, r, x, p_in, p_out);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (r && x && p_in && p_out && p_in !=
+               p_out)));
+  SPMV_REQUIRE(aligned16(r, x, p_in, p_out));
+  SPMV_LAUNCH_NT(ctx, n, cg_update_p2_cs_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, k, ws->rr, ws->pAp, ws->sc,
+                 ws->partials_rr, ctx->dot_blocks, r, x, p_in, p_out);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -1299,12 +1105,11 @@ int spmv_hip_cg_update_x2p_cs_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                                   void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 2 && k <= ws->kmax && n >= 0);
-  SPMV_REQUIRE(n == 0 || (r && x && p_prev && p_cur && p_prev != p_cur));
-  SPMV_REQUIRE(aligned16(r) && aligned16(x) && aligned16(p_prev)
-               && aligned16(p_cur));
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, cg_update_x2p_cs_kernel, grid,
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 2);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (r && x && p_prev && p_cur && p_prev !=
+               p_cur)));
+  SPMV_REQUIRE(aligned16(r, x, p_prev, p_cur));
+  SPMV_LAUNCH_NT(ctx, n, cg_update_x2p_cs_kernel, stream_grid(ctx, n),
                  spmv_stream(ctx, stream), n, k, ws->rr, ws->pAp, ws->sc,
                  ws->partials_rr, ctx->dot_blocks, r, x, p_prev, p_cur);
   SPMV_CHECK_LAUNCH();
@@ -1316,12 +1121,11 @@ int spmv_hip_cg_flush_x_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int k,
                             void* stream)
 {
   SPMV_SET_DEVICE(ctx);
-  SPMV_REQUIRE(ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && n >= 0);
-  SPMV_REQUIRE(n == 0 || (p && x));
-  SPMV_REQUIRE(aligned16(p) && aligned16(x));
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, cg_flush_x_kernel, grid, spmv_stream(ctx, stream), n,
-                 k, ws->rr, ws->pAp, ws->sc, p, x);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
+  SPMV_REQUIRE(n >= 0 && (n == 0 || (p && x)));
+  SPMV_REQUIRE(aligned16(p, x));
+  SPMV_LAUNCH_NT(ctx, n, cg_flush_x_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, k, ws->rr, ws->pAp, ws->sc, p, x);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }

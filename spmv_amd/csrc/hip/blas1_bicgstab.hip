@@ -34,10 +34,11 @@
 // here returns at once.  A system with rr[0] == 0 stops at k = 0 with x = 0.
 //
 // Built with -ffp-contract=off: every product and sum above is a rounding of
-// its own.  Streaming shape: see blas1.hip (persistent grid, units of kU
-// 16-byte loads per lane and stream, non-temporal from blas1_nt_min_elems
+// its own.  Streaming shape: see blas1_stream.h (persistent grid, units of
+// kU 16-byte loads per lane and stream, non-temporal from blas1_nt_min_elems
 // doubles on).
 #include "common.h"
+#include "blas1_stream.h"
 
 #include <cmath>
 #include <new>
@@ -68,83 +69,6 @@ struct spmv_hip_bicg_ws {
 
 namespace
 {
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-constexpr int kU = 4;                           // 16-B loads in flight per stream
-constexpr int64_t kUnit = (int64_t)kU * kBlock; // double2 elements per step
-
-template <bool NT>
-__device__ __forceinline__ f64x2 vload(const double* p, int64_t i2)
-{
-  const f64x2* q = reinterpret_cast<const f64x2*>(p) + i2;
-  return NT ? __builtin_nontemporal_load(q) : *q;
-}
-template <bool NT>
-__device__ __forceinline__ void vstore(double* p, int64_t i2, f64x2 v)
-{
-  f64x2* q = reinterpret_cast<f64x2*>(p) + i2;
-  if (NT)
-    __builtin_nontemporal_store(v, q);
-  else
-    *q = v;
-}
-
-#define SPMV_FOR_UNITS(n2)                                                     \
-  for (int64_t base = (int64_t)blockIdx.x * kUnit; base < (n2);               \
-       base += (int64_t)gridDim.x * kUnit)
-#define SPMV_FOR_LANE_ELEMS(i, n2)                                             \
-  _Pragma("unroll") for (int u = 0; u < kU; ++u)                               \
-    if (const int64_t i = base + u * kBlock + threadIdx.x; i < (n2))
-
-__device__ __forceinline__ void clear_partials_tail(double* partials, int len)
-{
-  for (int i = gridDim.x + blockIdx.x * blockDim.x + threadIdx.x; i < len;
-       i += gridDim.x * blockDim.x)
-    partials[i] = 0.0;
-}
-
-// The one way a partial array becomes a scalar: the single-workgroup reducers
-// and the consumer-side prologues both go through here, so they agree bit for
-// bit.  Valid in thread 0; callers that reuse s_red synchronise first.
-__device__ __forceinline__ double sum_partials(const double* partials, int len,
-                                               double* s_red)
-{
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < len; i += kBlock)
-    acc += partials[i];
-  return spmv_block_sum(acc, s_red);
-}
-
-// ... and its value in every thread of the workgroup
-__device__ __forceinline__ double consume_partials(const double* partials,
-                                                   int len, double* s_red,
-                                                   double* s_bcast)
-{
-  const double s = sum_partials(partials, len, s_red);
-  if (threadIdx.x == 0)
-    *s_bcast = s;
-  __syncthreads();
-  const double v = *s_bcast;
-  __syncthreads(); // s_red and s_bcast may be written again
-  return v;
-}
-
-// the workgroup's shares of two dot products into their slots
-__device__ __forceinline__ void store_pair_partials(double acc_a, double acc_b,
-                                                    double* partials_a,
-                                                    double* partials_b, int len,
-                                                    double* s_red)
-{
-  const double s_a = spmv_block_sum(acc_a, s_red);
-  __syncthreads(); // s_red is reused
-  const double s_b = spmv_block_sum(acc_b, s_red);
-  if (threadIdx.x == 0) {
-    partials_a[blockIdx.x] = s_a;
-    partials_b[blockIdx.x] = s_b;
-  }
-  clear_partials_tail(partials_a, len);
-  clear_partials_tail(partials_b, len);
-}
 
 // the scalars of an iteration, formed alike wherever they are needed
 __device__ __forceinline__ double omega_of(double ts, double tt)
@@ -209,7 +133,7 @@ __device__ __forceinline__ void update_s_body(int64_t n, int k, double rvk,
       }
     }
   }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (odd_tail(n)) {
     const int64_t i = n - 1;
     const double sv = r[i] - alpha * v[i];
     s[i] = sv;
@@ -262,7 +186,7 @@ __device__ __forceinline__ void update_xr_body(
       acc_rho += qv[u].y * rv.y;
     }
   }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (odd_tail(n)) {
     const int64_t i = n - 1;
     const double sv = s[i];
     const double hv = PRE ? sh[i] : sv;
@@ -325,7 +249,7 @@ __device__ __forceinline__ void update_p_body(
       }
     }
   }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (odd_tail(n)) {
     const int64_t i = n - 1;
     double w = p[i] - omega * v[i];
     w = r[i] + beta * w;
@@ -398,7 +322,7 @@ __global__ __launch_bounds__(kBlock) void bicg_dot_rv_kernel(
       acc += a[u].y * c[u].y;
     }
   }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+  if (odd_tail(n))
     acc += rhat[n - 1] * v[n - 1];
   const double s = spmv_block_sum(acc, s_red);
   if (threadIdx.x == 0)
@@ -433,7 +357,7 @@ __global__ __launch_bounds__(kBlock) void bicg_dot_ts_tt_kernel(
       acc_tt += a[u].y * a[u].y;
     }
   }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (odd_tail(n)) {
     const double tv = t[n - 1];
     acc_ts += tv * s[n - 1];
     acc_tt += tv * tv;
@@ -449,7 +373,7 @@ __global__ __launch_bounds__(kBlock) void bicg_reduce1_kernel(
   __shared__ double s_red[kBlock / 64];
   if (sc->done)
     return;
-  const double s = sum_partials(partials, len, s_red);
+  const double s = sum_partials(partials, nullptr, len, s_red);
   if (threadIdx.x == 0)
     slot[0] = s;
 }
@@ -462,9 +386,9 @@ __global__ __launch_bounds__(kBlock) void bicg_reduce2_kernel(
   __shared__ double s_red[kBlock / 64];
   if (sc->done)
     return;
-  const double a = sum_partials(partials_a, len, s_red);
+  const double a = sum_partials(partials_a, nullptr, len, s_red);
   __syncthreads(); // s_red is reused
-  const double b = sum_partials(partials_b, len, s_red);
+  const double b = sum_partials(partials_b, nullptr, len, s_red);
   if (threadIdx.x == 0) {
     pair[0] = a;
     pair[1] = b;
@@ -528,7 +452,8 @@ __global__ __launch_bounds__(kBlock) void bicg_update_s_cs_kernel(
   __shared__ double s_bcast;
   if (sc->done)
     return;
-  const double rvk = consume_partials(partials_rv, len, s_red, &s_bcast);
+  const double rvk
+      = consume_partials(partials_rv, nullptr, len, s_red, &s_bcast);
   if (blockIdx.x == 0 && threadIdx.x == 0)
     rvh[k] = rvk;
   update_s_body<NT, PRE>(n, k, rvk, rrho, sc, r, v, dinv, s, sh);
@@ -549,8 +474,10 @@ __global__ __launch_bounds__(kBlock) void bicg_update_xr_cs_kernel(
   __shared__ double s_bcast;
   if (sc->done)
     return;
-  const double ts = consume_partials(partials_ts, len, s_red, &s_bcast);
-  const double tt = consume_partials(partials_tt, len, s_red, &s_bcast);
+  const double ts
+      = consume_partials(partials_ts, nullptr, len, s_red, &s_bcast);
+  const double tt
+      = consume_partials(partials_tt, nullptr, len, s_red, &s_bcast);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     tstt[2 * k] = ts;
     tstt[2 * k + 1] = tt;
@@ -573,8 +500,10 @@ __global__ __launch_bounds__(kBlock) void bicg_update_p_cs_kernel(
   __shared__ double s_bcast;
   if (sc->done)
     return;
-  const double rr_k = consume_partials(partials_rr, len, s_red, &s_bcast);
-  const double rho_k = consume_partials(partials_rho, len, s_red, &s_bcast);
+  const double rr_k
+      = consume_partials(partials_rr, nullptr, len, s_red, &s_bcast);
+  const double rho_k
+      = consume_partials(partials_rho, nullptr, len, s_red, &s_bcast);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     rrho[2 * k] = rr_k;
     rrho[2 * k + 1] = rho_k;
@@ -603,14 +532,9 @@ __global__ void bicg_reset_kernel(BicgScalars* sc, double rtol, double* rv,
   }
 }
 
-bool aligned16(const void* p)
-{
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
-
 } // namespace
 
-// NT by the vector length (see blas1.hip), PRE by the caller's dinv
+// NT by the vector length (see blas1_stream.h), PRE by the caller's dinv
 #define SPMV_LAUNCH_NT_PRE(ctx, n, pre, kernel, grid, st, ...)                 \
   do {                                                                         \
     const bool _nt = (int64_t)(n) >= (ctx)->blas1_nt_min_elems;                \
@@ -627,28 +551,6 @@ bool aligned16(const void* p)
       hipLaunchKernelGGL((kernel<false, false>), dim3(grid), dim3(kBlock), 0,  \
                          st, __VA_ARGS__);                                     \
   } while (0)
-
-#define SPMV_LAUNCH_NT(ctx, n, kernel, grid, st, ...)                          \
-  do {                                                                         \
-    if ((int64_t)(n) >= (ctx)->blas1_nt_min_elems)                             \
-      hipLaunchKernelGGL(kernel<true>, dim3(grid), dim3(kBlock), 0, st,        \
-                         __VA_ARGS__);                                         \
-    else                                                                       \
-      hipLaunchKernelGGL(kernel<false>, dim3(grid), dim3(kBlock), 0, st,       \
-                         __VA_ARGS__);                                         \
-  } while (0)
-
-// every kernel of iteration k: the workspace is this context's, k in range
-#define SPMV_BICG_REQUIRE_K(ctx, ws, k, kmin)                                  \
-  SPMV_REQUIRE((ws) && (ws)->ctx == (ctx) && (k) >= (kmin) && (k) <= (ws)->kmax)
-
-// grid of a streaming kernel over n doubles: never more workgroups than a
-// partial array has slots
-static int bicg_stream_grid(const spmv_hip_ctx* ctx, int64_t n)
-{
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  return grid > ctx->dot_blocks ? ctx->dot_blocks : grid;
-}
 
 extern "C" {
 
@@ -794,11 +696,11 @@ int spmv_hip_bicg_dot_rv_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                              void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_REQUIRE(n >= 0 && (n == 0 || (rhat && v)));
-  SPMV_REQUIRE(aligned16(rhat) && aligned16(v));
+  SPMV_REQUIRE(aligned16(rhat, v));
   SPMV_SET_DEVICE(ctx);
-  SPMV_LAUNCH_NT(ctx, n, bicg_dot_rv_kernel, bicg_stream_grid(ctx, n),
+  SPMV_LAUNCH_NT(ctx, n, bicg_dot_rv_kernel, stream_grid_capped(ctx, n),
                  spmv_stream(ctx, stream), n, ws->sc, rhat, v, ws->p_rv,
                  ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
@@ -810,11 +712,11 @@ int spmv_hip_bicg_dot_ts_tt_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                                 void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_REQUIRE(n >= 0 && (n == 0 || (t && s)));
-  SPMV_REQUIRE(aligned16(t) && aligned16(s));
+  SPMV_REQUIRE(aligned16(t, s));
   SPMV_SET_DEVICE(ctx);
-  SPMV_LAUNCH_NT(ctx, n, bicg_dot_ts_tt_kernel, bicg_stream_grid(ctx, n),
+  SPMV_LAUNCH_NT(ctx, n, bicg_dot_ts_tt_kernel, stream_grid_capped(ctx, n),
                  spmv_stream(ctx, stream), n, ws->sc, t, s, ws->p_ts, ws->p_tt,
                  ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
@@ -825,7 +727,7 @@ int spmv_hip_bicg_reduce_rv(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                             void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_SET_DEVICE(ctx);
   hipLaunchKernelGGL(bicg_reduce1_kernel, dim3(1), dim3(kBlock), 0,
                      spmv_stream(ctx, stream), ws->p_rv, ctx->dot_blocks,
@@ -838,7 +740,7 @@ int spmv_hip_bicg_reduce_ts_tt(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                                void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_SET_DEVICE(ctx);
   hipLaunchKernelGGL(bicg_reduce2_kernel, dim3(1), dim3(kBlock), 0,
                      spmv_stream(ctx, stream), ws->p_ts, ws->p_tt,
@@ -851,7 +753,7 @@ int spmv_hip_bicg_reduce_rr_rho(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                                 void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 0);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 0);
   SPMV_SET_DEVICE(ctx);
   hipLaunchKernelGGL(bicg_reduce2_kernel, dim3(1), dim3(kBlock), 0,
                      spmv_stream(ctx, stream), ws->p_rr, ws->p_rho,
@@ -865,8 +767,7 @@ int spmv_hip_bicg_reduce_rr_rho(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
 #define SPMV_BICG_CHECK_S(n, r, v, dinv, s, sh)                                \
   SPMV_REQUIRE((n) >= 0 && ((n) == 0 || ((r) && (v) && (s))));                 \
   SPMV_REQUIRE((n) == 0 || !(dinv) || (sh));                                   \
-  SPMV_REQUIRE(aligned16(r) && aligned16(v) && aligned16(dinv) && aligned16(s) \
-               && (!(dinv) || aligned16(sh)))
+  SPMV_REQUIRE(aligned16(r, v, dinv, s) && (!(dinv) || aligned16(sh)))
 
 int spmv_hip_bicg_update_s_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                                int64_t n, const double* r, const double* v,
@@ -874,11 +775,11 @@ int spmv_hip_bicg_update_s_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                                void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_BICG_CHECK_S(n, r, v, dinv, s, sh);
   SPMV_SET_DEVICE(ctx);
   SPMV_LAUNCH_NT_PRE(ctx, n, dinv != nullptr, bicg_update_s_kernel,
-                     bicg_stream_grid(ctx, n), spmv_stream(ctx, stream), n, k,
+                     stream_grid_capped(ctx, n), spmv_stream(ctx, stream), n, k,
                      ws->rrho, ws->rv, ws->sc, r, v, dinv, s, sh);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
@@ -890,11 +791,11 @@ int spmv_hip_bicg_update_s_cs_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws,
                                   double* s, double* sh, void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_BICG_CHECK_S(n, r, v, dinv, s, sh);
   SPMV_SET_DEVICE(ctx);
   SPMV_LAUNCH_NT_PRE(ctx, n, dinv != nullptr, bicg_update_s_cs_kernel,
-                     bicg_stream_grid(ctx, n), spmv_stream(ctx, stream), n, k,
+                     stream_grid_capped(ctx, n), spmv_stream(ctx, stream), n, k,
                      ws->rrho, ws->rv, ws->sc, ws->p_rv, ctx->dot_blocks, r, v,
                      dinv, s, sh);
   SPMV_CHECK_LAUNCH();
@@ -905,8 +806,7 @@ int spmv_hip_bicg_update_s_cs_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws,
 #define SPMV_BICG_CHECK_XR(n, ph, sh, s, t, rhat, x, r)                        \
   SPMV_REQUIRE((n) >= 0                                                        \
                && ((n) == 0 || ((ph) && (s) && (t) && (rhat) && (x) && (r)))); \
-  SPMV_REQUIRE(aligned16(ph) && aligned16(sh) && aligned16(s) && aligned16(t)  \
-               && aligned16(rhat) && aligned16(x) && aligned16(r))
+  SPMV_REQUIRE(aligned16(ph, sh, s, t, rhat, x, r))
 
 int spmv_hip_bicg_update_xr_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                                 int64_t n, const double* ph, const double* sh,
@@ -915,11 +815,11 @@ int spmv_hip_bicg_update_xr_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                                 void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_BICG_CHECK_XR(n, ph, sh, s, t, rhat, x, r);
   SPMV_SET_DEVICE(ctx);
   SPMV_LAUNCH_NT_PRE(ctx, n, sh != nullptr, bicg_update_xr_kernel,
-                     bicg_stream_grid(ctx, n), spmv_stream(ctx, stream), n, k,
+                     stream_grid_capped(ctx, n), spmv_stream(ctx, stream), n, k,
                      ws->rrho, ws->rv, ws->tstt, ws->sc, ph, sh, s, t, rhat, x,
                      r, ws->p_rr, ws->p_rho, ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
@@ -933,11 +833,11 @@ int spmv_hip_bicg_update_xr_cs_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws,
                                    double* x, double* r, void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_BICG_CHECK_XR(n, ph, sh, s, t, rhat, x, r);
   SPMV_SET_DEVICE(ctx);
   SPMV_LAUNCH_NT_PRE(ctx, n, sh != nullptr, bicg_update_xr_cs_kernel,
-                     bicg_stream_grid(ctx, n), spmv_stream(ctx, stream), n, k,
+                     stream_grid_capped(ctx, n), spmv_stream(ctx, stream), n, k,
                      ws->rrho, ws->rv, ws->tstt, ws->sc, ws->p_ts, ws->p_tt,
                      ctx->dot_blocks, ph, sh, s, t, rhat, x, r, ws->p_rr,
                      ws->p_rho);
@@ -949,8 +849,7 @@ int spmv_hip_bicg_update_xr_cs_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws,
 #define SPMV_BICG_CHECK_P(n, r, v, dinv, p, ph)                                \
   SPMV_REQUIRE((n) >= 0 && ((n) == 0 || ((r) && (v) && (p))));                 \
   SPMV_REQUIRE((n) == 0 || !(dinv) || (ph));                                   \
-  SPMV_REQUIRE(aligned16(r) && aligned16(v) && aligned16(dinv) && aligned16(p) \
-               && (!(dinv) || aligned16(ph)))
+  SPMV_REQUIRE(aligned16(r, v, dinv, p) && (!(dinv) || aligned16(ph)))
 
 int spmv_hip_bicg_update_p_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                                int64_t n, const double* r, const double* v,
@@ -958,11 +857,11 @@ int spmv_hip_bicg_update_p_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws, int k,
                                void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_BICG_CHECK_P(n, r, v, dinv, p, ph);
   SPMV_SET_DEVICE(ctx);
   SPMV_LAUNCH_NT_PRE(ctx, n, dinv != nullptr, bicg_update_p_kernel,
-                     bicg_stream_grid(ctx, n), spmv_stream(ctx, stream), n, k,
+                     stream_grid_capped(ctx, n), spmv_stream(ctx, stream), n, k,
                      ws->rrho, ws->rv, ws->tstt, ws->sc, r, v, dinv, p, ph);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
@@ -974,11 +873,11 @@ int spmv_hip_bicg_update_p_cs_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws,
                                   double* p, double* ph, void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_BICG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_BICG_CHECK_P(n, r, v, dinv, p, ph);
   SPMV_SET_DEVICE(ctx);
   SPMV_LAUNCH_NT_PRE(ctx, n, dinv != nullptr, bicg_update_p_cs_kernel,
-                     bicg_stream_grid(ctx, n), spmv_stream(ctx, stream), n, k,
+                     stream_grid_capped(ctx, n), spmv_stream(ctx, stream), n, k,
                      ws->rrho, ws->rv, ws->tstt, ws->sc, ws->p_rr, ws->p_rho,
                      ctx->dot_blocks, r, v, dinv, p, ph);
   SPMV_CHECK_LAUNCH();

@@ -16,7 +16,7 @@
 // per column, so the bits of column c depend on A, on column c of B, on nrhs
 // and on c -- not on what the other columns hold or on when they stop.
 //
-// nrhs = 2, 4, 8 (template K): the streaming shape of blas1.hip -- a
+// nrhs = 2, 4, 8 (template K): the streaming shape of blas1_stream.h -- a
 // persistent grid walks units of kU x kBlock 16-byte elements.  The unit
 // stride is a multiple of K, so a lane sees the same column pair
 // (2 (tid % (K/2)), +1) in every step and keeps two accumulators and two
@@ -32,6 +32,7 @@
 // Built with -ffp-contract=off like blas1.hip: every element sees the
 // multiplies and adds of the single-vector kernels.
 #include "common.h"
+#include "blas1_stream.h"
 
 #include <climits>
 #include <cmath>
@@ -60,46 +61,6 @@ struct spmv_hip_cgb_ws {
 
 namespace
 {
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-constexpr int kU = 4;                           // 16-B loads in flight per stream
-constexpr int64_t kUnit = (int64_t)kU * kBlock; // double2 elements per step
-
-template <bool NT>
-__device__ __forceinline__ f64x2 vload(const double* p, int64_t i2)
-{
-  const f64x2* q = reinterpret_cast<const f64x2*>(p) + i2;
-  return NT ? __builtin_nontemporal_load(q) : *q;
-}
-template <bool NT>
-__device__ __forceinline__ void vstore(double* p, int64_t i2, f64x2 v)
-{
-  f64x2* q = reinterpret_cast<f64x2*>(p) + i2;
-  if (NT)
-    __builtin_nontemporal_store(v, q);
-  else
-    *q = v;
-}
-template <bool NT>
-__device__ __forceinline__ double sload(const double* p)
-{
-  return NT ? __builtin_nontemporal_load(p) : *p;
-}
-template <bool NT>
-__device__ __forceinline__ void sstore(double* p, double v)
-{
-  if (NT)
-    __builtin_nontemporal_store(v, p);
-  else
-    *p = v;
-}
-
-#define SPMV_FOR_UNITS(n2)                                                     \
-  for (int64_t base = (int64_t)blockIdx.x * kUnit; base < (n2);               \
-       base += (int64_t)gridDim.x * kUnit)
-#define SPMV_FOR_LANE_ELEMS(i, n2)                                             \
-  _Pragma("unroll") for (int u = 0; u < kU; ++u)                               \
-    if (const int64_t i = base + u * kBlock + threadIdx.x; i < (n2))
 
 // what iteration k does to one column (cg.cpp:66,76-80)
 struct ColStep {
@@ -294,24 +255,6 @@ __global__ __launch_bounds__(kBlock) void cgb_update_xp_kernel(
 }
 
 // ---- nrhs at run time (1..8): one thread per row -----------------------------
-__device__ __forceinline__ double block_sum(double v, double* s_red)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-    s_red[wave] = v;
-  __syncthreads();
-  double r = 0.0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w)
-      r += s_red[w];
-  }
-  return r; // valid in thread 0
-}
-
 // one block sum per column, columns in order (nrhs is uniform)
 __device__ __forceinline__ void rows_epilogue(const double (&acc)[SPMV_CGB_MAX],
                                               int nrhs, double* s_red,
@@ -320,7 +263,7 @@ __device__ __forceinline__ void rows_epilogue(const double (&acc)[SPMV_CGB_MAX],
 #pragma unroll
   for (int c = 0; c < SPMV_CGB_MAX; ++c) {
     if (c < nrhs) {
-      const double s = block_sum(acc[c], s_red);
+      const double s = spmv_block_sum(acc[c], s_red);
       if (threadIdx.x == 0)
         partials[(int64_t)blockIdx.x * nrhs + c] = s;
       __syncthreads(); // s_red is reused
@@ -465,7 +408,7 @@ __device__ __forceinline__ double reduce_column(const double* partials, int len,
   double acc = 0.0;
   for (int i = threadIdx.x; i < len; i += kBlock)
     acc += partials[(int64_t)i * nrhs + c];
-  const double s = block_sum(acc, s_red);
+  const double s = spmv_block_sum(acc, s_red);
   __syncthreads(); // s_red is reused by the next column
   return s;        // valid in thread 0
 }
@@ -547,21 +490,11 @@ __global__ void cgb_reset_kernel(CgbState* st, double rtol, double* rr,
   }
 }
 
-bool aligned16(const void* p)
-{
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
-
 bool native_width(int nrhs) { return nrhs == 2 || nrhs == 4 || nrhs == 8; }
 
 bool nrhs_ok(int nrhs) { return nrhs >= 1 && nrhs <= SPMV_CGB_MAX; }
 
-// grid of the streaming kernels over n2 16-byte elements / of the row kernels
-int stream_grid(const spmv_hip_ctx* ctx, int64_t n2)
-{
-  const int g = spmv_grid_for(ctx, n2, (int)kUnit);
-  return g < ctx->dot_blocks ? g : ctx->dot_blocks;
-}
+// grid of the row kernels (the streaming kernels: stream_grid_capped)
 int rows_grid(const spmv_hip_ctx* ctx, int64_t M)
 {
   const int g = spmv_grid_for(ctx, M, kBlock);
@@ -737,14 +670,15 @@ int spmv_hip_cgb_dot_f64(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int64_t M,
   SPMV_REQUIRE(ctx && ws && ws->ctx == ctx && M >= 0);
   SPMV_REQUIRE(M == 0 || (P && AP));
   const int nrhs = ws->nrhs;
-  SPMV_REQUIRE(!native_width(nrhs) || (aligned16(P) && aligned16(AP)));
+  SPMV_REQUIRE(!native_width(nrhs) || aligned16(P, AP));
   SPMV_SET_DEVICE(ctx);
   const bool nt = M * nrhs >= ctx->blas1_nt_min_elems;
   hipStream_t st = spmv_stream(ctx, stream);
   if (native_width(nrhs)) {
     const int64_t n2 = M * nrhs / 2;
-    SPMV_CGB_LAUNCH_WIDTH(nrhs, nt, cgb_dot_kernel, stream_grid(ctx, n2), st, n2,
-                          ws->st, P, AP, ws->partials, ctx->dot_blocks);
+    SPMV_CGB_LAUNCH_WIDTH(nrhs, nt, cgb_dot_kernel,
+                          stream_grid_capped(ctx, M * nrhs), st, n2, ws->st, P,
+                          AP, ws->partials, ctx->dot_blocks);
   } else {
     SPMV_CGB_LAUNCH_NT(nt, cgb_dot_rows_kernel, rows_grid(ctx, M), st, M, nrhs,
                        ws->st, P, AP, ws->partials, ctx->dot_blocks);
@@ -784,15 +718,15 @@ int spmv_hip_cgb_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int k,
   SPMV_REQUIRE(ctx && ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && M >= 0);
   SPMV_REQUIRE(M == 0 || (AP && R));
   const int nrhs = ws->nrhs;
-  SPMV_REQUIRE(!native_width(nrhs) || (aligned16(AP) && aligned16(R)));
+  SPMV_REQUIRE(!native_width(nrhs) || aligned16(AP, R));
   SPMV_SET_DEVICE(ctx);
   const bool nt = M * nrhs >= ctx->blas1_nt_min_elems;
   hipStream_t st = spmv_stream(ctx, stream);
   if (native_width(nrhs)) {
     const int64_t n2 = M * nrhs / 2;
-    SPMV_CGB_LAUNCH_WIDTH(nrhs, nt, cgb_update_r_kernel, stream_grid(ctx, n2),
-                          st, n2, k, ws->rr, ws->pAp, ws->st, AP, R,
-                          ws->partials, ctx->dot_blocks);
+    SPMV_CGB_LAUNCH_WIDTH(nrhs, nt, cgb_update_r_kernel,
+                          stream_grid_capped(ctx, M * nrhs), st, n2, k, ws->rr,
+                          ws->pAp, ws->st, AP, R, ws->partials, ctx->dot_blocks);
   } else {
     SPMV_CGB_LAUNCH_NT(nt, cgb_update_r_rows_kernel, rows_grid(ctx, M), st, M,
                        nrhs, k, ws->rr, ws->pAp, ws->st, AP, R, ws->partials,
@@ -809,15 +743,15 @@ int spmv_hip_cgb_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int k,
   SPMV_REQUIRE(ctx && ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax && M >= 0);
   SPMV_REQUIRE(M == 0 || (R && X && P));
   const int nrhs = ws->nrhs;
-  SPMV_REQUIRE(!native_width(nrhs)
-               || (aligned16(R) && aligned16(X) && aligned16(P)));
+  SPMV_REQUIRE(!native_width(nrhs) || aligned16(R, X, P));
   SPMV_SET_DEVICE(ctx);
   const bool nt = M * nrhs >= ctx->blas1_nt_min_elems;
   hipStream_t st = spmv_stream(ctx, stream);
   if (native_width(nrhs)) {
     const int64_t n2 = M * nrhs / 2;
-    SPMV_CGB_LAUNCH_WIDTH(nrhs, nt, cgb_update_xp_kernel, stream_grid(ctx, n2),
-                          st, n2, k, ws->rr, ws->pAp, ws->st, R, X, P);
+    SPMV_CGB_LAUNCH_WIDTH(nrhs, nt, cgb_update_xp_kernel,
+                          stream_grid_capped(ctx, M * nrhs), st, n2, k, ws->rr,
+                          ws->pAp, ws->st, R, X, P);
   } else {
     SPMV_CGB_LAUNCH_NT(nt, cgb_update_xp_rows_kernel, rows_grid(ctx, M), st, M,
                        nrhs, k, ws->rr, ws->pAp, ws->st, R, X, P);

@@ -39,43 +39,17 @@
 // the pair {rz[k], rr[k]}.  Every dot product is finished by a reducer kernel.
 //
 // Built with -ffp-contract=off: every product and sum is a rounding of its
-// own.  Streaming shape: see blas1.hip (persistent grid, units of kU 16-byte
-// loads per lane and stream, non-temporal from blas1_nt_min_elems doubles on,
-// a scalar tail for an odd n).
+// own.  Streaming shape: see blas1_stream.h (persistent grid, units of kU
+// 16-byte loads per lane and stream, non-temporal from blas1_nt_min_elems
+// doubles on, a scalar tail for an odd n).
 #include "common.h"
+#include "blas1_stream.h"
 #include "pcg_ws.h"
 
 #include <cmath>
 
 namespace
 {
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-constexpr int kU = 4;                           // 16-B loads in flight per stream
-constexpr int64_t kUnit = (int64_t)kU * kBlock; // double2 elements per step
-
-template <bool NT>
-__device__ __forceinline__ f64x2 vload(const double* p, int64_t i2)
-{
-  const f64x2* q = reinterpret_cast<const f64x2*>(p) + i2;
-  return NT ? __builtin_nontemporal_load(q) : *q;
-}
-template <bool NT>
-__device__ __forceinline__ void vstore(double* p, int64_t i2, f64x2 v)
-{
-  f64x2* q = reinterpret_cast<f64x2*>(p) + i2;
-  if (NT)
-    __builtin_nontemporal_store(v, q);
-  else
-    *q = v;
-}
-
-#define SPMV_FOR_UNITS(n2)                                                     \
-  for (int64_t base = (int64_t)blockIdx.x * kUnit; base < (n2);               \
-       base += (int64_t)gridDim.x * kUnit)
-#define SPMV_FOR_LANE_ELEMS(i, n2)                                             \
-  _Pragma("unroll") for (int u = 0; u < kU; ++u)                               \
-    if (const int64_t i = base + u * kBlock + threadIdx.x; i < (n2))
 
 // the workgroup's share of one dot product into its slot (as the producers of
 // blas1_pcg.hip leave theirs: pcg_reduce_rz_rr adds `len` entries)
@@ -86,9 +60,7 @@ __device__ __forceinline__ void store_partials(double acc,
   const double s = spmv_block_sum(acc, s_red);
   if (threadIdx.x == 0)
     partials[blockIdx.x] = s;
-  for (int i = gridDim.x + blockIdx.x * blockDim.x + threadIdx.x; i < len;
-       i += gridDim.x * blockDim.x)
-    partials[i] = 0.0;
+  clear_partials_tail(partials, len);
   __syncthreads(); // s_red may be written again
 }
 
@@ -126,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void cheb_apply0_kernel(
       vstore<NT>(z, i, t);
     }
   }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (odd_tail(n)) {
     const int64_t i = n - 1;
     const double t = b0 * scaled<PRE>(PRE ? dinv[i] : 0.0, r[i]);
     if constexpr (!LAST)
@@ -180,7 +152,7 @@ __global__ __launch_bounds__(kBlock) void cheb_step_kernel(
       }
     }
   }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (odd_tail(n)) {
     const int64_t i = n - 1;
     const double t = b * scaled<PRE>(PRE ? dinv[i] : 0.0, r[i] - w[i]);
     const double e = a * d[i] + t;
@@ -276,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void cheb_update_r_kernel(
       }
     }
   }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (odd_tail(n)) {
     const int64_t i = n - 1;
     const double rv = r[i] + nalpha * Ap[i];
     r[i] = rv;
@@ -307,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void cheb_update_xp_kernel(
   const double alpha = rz_old / pAp[k];
   const double beta = zr[2 * k] / rz_old;
   const bool converged = sqrt(zr[2 * k + 1]) / sqrt(zr[1]) < sc->rtol;
-  const bool tail = (n & 1) && blockIdx.x == 0 && threadIdx.x == 0;
+  const bool tail = odd_tail(n);
   const int64_t n2 = n >> 1;
   if (converged) { // x takes this iteration's update, p stays
     SPMV_FOR_UNITS(n2)
@@ -425,7 +397,7 @@ __global__ __launch_bounds__(kBlock) void sgs_update_r_kernel(
       acc_rr += rv[u].y * rv[u].y;
     }
   }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (odd_tail(n)) {
     const int64_t i = n - 1;
     const double rv = r[i] + nalpha * Ap[i];
     r[i] = rv;
@@ -459,19 +431,15 @@ __global__ __launch_bounds__(kBlock) void sgs_dot_rz_kernel(
       acc_rz += rv[u].y * zv[u].y;
     }
   }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+  if (odd_tail(n))
     acc_rz += r[n - 1] * z[n - 1];
   store_partials(acc_rz, partials_rz, len, s_red);
 }
 
-bool aligned16(const void* p)
-{
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
-
 } // namespace
 
-// kernel<NT, PRE, LAST>: NT by the vector's length (see blas1.hip), PRE by dinv
+// kernel<NT, PRE, LAST>: NT by the vector's length (see blas1_stream.h), PRE
+// by dinv
 #define SPMV_CHEB_LAUNCH3(ctx, n, pre, last, kernel, grid, st, ...)            \
   do {                                                                         \
     const bool _nt = (int64_t)(n) >= (ctx)->blas1_nt_min_elems;                \
@@ -518,9 +486,9 @@ int spmv_hip_cheb_apply0_f64(spmv_hip_ctx* ctx, int64_t n, double b0,
                              double* z, void* stream)
 {
   SPMV_REQUIRE(ctx && n >= 0 && (n == 0 || (r && z)));
-  SPMV_REQUIRE(aligned16(r) && aligned16(dinv) && aligned16(d) && aligned16(z));
+  SPMV_REQUIRE(aligned16(r, dinv, d, z));
   SPMV_SET_DEVICE(ctx);
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
+  const int grid = stream_grid(ctx, n);
   SPMV_CHEB_LAUNCH3(ctx, n, dinv != nullptr, d == nullptr, cheb_apply0_kernel,
                     grid, spmv_stream(ctx, stream), n, b0, r, dinv, d, z);
   SPMV_CHECK_LAUNCH();
@@ -534,12 +502,9 @@ int spmv_hip_cheb_step_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
 {
   SPMV_REQUIRE(ctx && (!ws || ws->ctx == ctx));
   SPMV_REQUIRE(n >= 0 && (n == 0 || (w && r && d && z)));
-  SPMV_REQUIRE(aligned16(w) && aligned16(r) && aligned16(dinv) && aligned16(d)
-               && aligned16(z));
+  SPMV_REQUIRE(aligned16(w, r, dinv, d, z));
   SPMV_SET_DEVICE(ctx);
-  int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  if (grid > ctx->dot_blocks)
-    grid = ctx->dot_blocks;
+  const int grid = stream_grid_capped(ctx, n);
   hipStream_t st = spmv_stream(ctx, stream);
   const PcgScalars* sc = ws ? ws->sc : nullptr;
   double* prz = ws ? ws->partials_rz : nullptr;
@@ -585,12 +550,9 @@ int spmv_hip_cheb_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
 {
   SPMV_REQUIRE(ctx && ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax);
   SPMV_REQUIRE(n >= 0 && (n == 0 || (Ap && r && z)));
-  SPMV_REQUIRE(aligned16(Ap) && aligned16(dinv) && aligned16(r) && aligned16(d)
-               && aligned16(z));
+  SPMV_REQUIRE(aligned16(Ap, dinv, r, d, z));
   SPMV_SET_DEVICE(ctx);
-  int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  if (grid > ctx->dot_blocks)
-    grid = ctx->dot_blocks;
+  const int grid = stream_grid_capped(ctx, n);
   SPMV_CHEB_LAUNCH3(ctx, n, dinv != nullptr, d == nullptr, cheb_update_r_kernel,
                     grid, spmv_stream(ctx, stream), n, k, b0, ws->zr, ws->pAp,
                     ws->sc, Ap, dinv, r, d, z, ws->partials_rz, ws->partials_rr,
@@ -605,16 +567,12 @@ int spmv_hip_cheb_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
 {
   SPMV_REQUIRE(ctx && ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax);
   SPMV_REQUIRE(n >= 0 && (n == 0 || (z && x && p)));
-  SPMV_REQUIRE(aligned16(z) && aligned16(x) && aligned16(p));
+  SPMV_REQUIRE(aligned16(z, x, p));
   SPMV_SET_DEVICE(ctx);
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
+  const int grid = stream_grid(ctx, n);
   hipStream_t st = spmv_stream(ctx, stream);
-  if (n >= ctx->blas1_nt_min_elems)
-    hipLaunchKernelGGL(cheb_update_xp_kernel<true>, dim3(grid), dim3(kBlock), 0,
-                       st, n, k, ws->zr, ws->pAp, ws->sc, z, x, p);
-  else
-    hipLaunchKernelGGL(cheb_update_xp_kernel<false>, dim3(grid), dim3(kBlock), 0,
-                       st, n, k, ws->zr, ws->pAp, ws->sc, z, x, p);
+  SPMV_LAUNCH_NT(ctx, n, cheb_update_xp_kernel, grid, st, n, k, ws->zr, ws->pAp,
+                 ws->sc, z, x, p);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -647,12 +605,8 @@ int spmv_hip_sgs_init_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
   if (grid > ctx->dot_blocks)
     grid = ctx->dot_blocks;
   hipStream_t st = spmv_stream(ctx, stream);
-  if (n >= ctx->blas1_nt_min_elems)
-    hipLaunchKernelGGL(sgs_init_kernel<true>, dim3(grid), dim3(kBlock), 0, st, n,
-                       b, r, x, ws->partials_rr, ctx->dot_blocks);
-  else
-    hipLaunchKernelGGL(sgs_init_kernel<false>, dim3(grid), dim3(kBlock), 0, st,
-                       n, b, r, x, ws->partials_rr, ctx->dot_blocks);
+  SPMV_LAUNCH_NT(ctx, n, sgs_init_kernel, grid, st, n, b, r, x, ws->partials_rr,
+                 ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -663,20 +617,12 @@ int spmv_hip_sgs_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
 {
   SPMV_REQUIRE(ctx && ws && ws->ctx == ctx && k >= 1 && k <= ws->kmax);
   SPMV_REQUIRE(n >= 0 && (n == 0 || (Ap && r)));
-  SPMV_REQUIRE(aligned16(Ap) && aligned16(r));
+  SPMV_REQUIRE(aligned16(Ap, r));
   SPMV_SET_DEVICE(ctx);
-  int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  if (grid > ctx->dot_blocks)
-    grid = ctx->dot_blocks;
+  const int grid = stream_grid_capped(ctx, n);
   hipStream_t st = spmv_stream(ctx, stream);
-  if (n >= ctx->blas1_nt_min_elems)
-    hipLaunchKernelGGL(sgs_update_r_kernel<true>, dim3(grid), dim3(kBlock), 0,
-                       st, n, k, ws->zr, ws->pAp, ws->sc, Ap, r, ws->partials_rr,
-                       ctx->dot_blocks);
-  else
-    hipLaunchKernelGGL(sgs_update_r_kernel<false>, dim3(grid), dim3(kBlock), 0,
-                       st, n, k, ws->zr, ws->pAp, ws->sc, Ap, r, ws->partials_rr,
-                       ctx->dot_blocks);
+  SPMV_LAUNCH_NT(ctx, n, sgs_update_r_kernel, grid, st, n, k, ws->zr, ws->pAp,
+                 ws->sc, Ap, r, ws->partials_rr, ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -686,18 +632,12 @@ int spmv_hip_sgs_dot_rz_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
 {
   SPMV_REQUIRE(ctx && ws && ws->ctx == ctx);
   SPMV_REQUIRE(n >= 0 && (n == 0 || (r && z)));
-  SPMV_REQUIRE(aligned16(r) && aligned16(z));
+  SPMV_REQUIRE(aligned16(r, z));
   SPMV_SET_DEVICE(ctx);
-  int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  if (grid > ctx->dot_blocks)
-    grid = ctx->dot_blocks;
+  const int grid = stream_grid_capped(ctx, n);
   hipStream_t st = spmv_stream(ctx, stream);
-  if (n >= ctx->blas1_nt_min_elems)
-    hipLaunchKernelGGL(sgs_dot_rz_kernel<true>, dim3(grid), dim3(kBlock), 0, st,
-                       n, ws->sc, r, z, ws->partials_rz, ctx->dot_blocks);
-  else
-    hipLaunchKernelGGL(sgs_dot_rz_kernel<false>, dim3(grid), dim3(kBlock), 0, st,
-                       n, ws->sc, r, z, ws->partials_rz, ctx->dot_blocks);
+  SPMV_LAUNCH_NT(ctx, n, sgs_dot_rz_kernel, grid, st, n, ws->sc, r, z,
+                 ws->partials_rz, ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }

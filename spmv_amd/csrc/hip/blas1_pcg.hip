@@ -24,13 +24,14 @@
 // `done` every kernel here returns at once.
 //
 // Built with -ffp-contract=off: dinv*r, beta*p and their sum are three
-// roundings, r*(dinv*r) two.  Streaming shape: see blas1.hip (persistent grid,
-// units of kU 16-byte loads per lane and stream, non-temporal from
+// roundings, r*(dinv*r) two.  Streaming shape: see blas1_stream.h (persistent
+// grid, units of kU 16-byte loads per lane and stream, non-temporal from
 // blas1_nt_min_elems doubles on).
 //
 // Also here, as setup work of the Jacobi preconditioner: the diagonal of a CSR
 // block (one thread per row) and the checked inverse of a diagonal.
 #include "common.h"
+#include "blas1_stream.h"
 #include "pcg_ws.h"
 
 #include <cmath>
@@ -38,87 +39,6 @@
 
 namespace
 {
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-constexpr int kU = 4;                           // 16-B loads in flight per stream
-constexpr int64_t kUnit = (int64_t)kU * kBlock; // double2 elements per step
-
-template <bool NT>
-__device__ __forceinline__ f64x2 vload(const double* p, int64_t i2)
-{
-  const f64x2* q = reinterpret_cast<const f64x2*>(p) + i2;
-  return NT ? __builtin_nontemporal_load(q) : *q;
-}
-template <bool NT>
-__device__ __forceinline__ void vstore(double* p, int64_t i2, f64x2 v)
-{
-  f64x2* q = reinterpret_cast<f64x2*>(p) + i2;
-  if (NT)
-    __builtin_nontemporal_store(v, q);
-  else
-    *q = v;
-}
-
-#define SPMV_FOR_UNITS(n2)                                                     \
-  for (int64_t base = (int64_t)blockIdx.x * kUnit; base < (n2);               \
-       base += (int64_t)gridDim.x * kUnit)
-#define SPMV_FOR_LANE_ELEMS(i, n2)                                             \
-  _Pragma("unroll") for (int u = 0; u < kU; ++u)                               \
-    if (const int64_t i = base + u * kBlock + threadIdx.x; i < (n2))
-
-__device__ __forceinline__ void clear_partials_tail(double* partials, int len)
-{
-  for (int i = gridDim.x + blockIdx.x * blockDim.x + threadIdx.x; i < len;
-       i += gridDim.x * blockDim.x)
-    partials[i] = 0.0;
-}
-
-// The one way a partial array becomes a scalar: the single-workgroup reducers
-// and the consumer-side prologues both go through here, so they agree bit for
-// bit.  Valid in thread 0; ends behind a barrier only for thread 0's reads of
-// s_red -- callers that reuse s_red synchronise first.
-__device__ __forceinline__ double sum_partials(
-    const double* __restrict__ partials, const double* __restrict__ partials2,
-    int len, double* s_red)
-{
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < len; i += kBlock)
-    acc += partials[i];
-  if (partials2) // the remote block's share of p.Ap
-    for (int i = threadIdx.x; i < len; i += kBlock)
-      acc += partials2[i];
-  return spmv_block_sum(acc, s_red);
-}
-
-// ... and its value in every thread of the workgroup
-__device__ __forceinline__ double consume_partials(
-    const double* __restrict__ partials, const double* __restrict__ partials2,
-    int len, double* s_red, double* s_bcast)
-{
-  const double s = sum_partials(partials, partials2, len, s_red);
-  if (threadIdx.x == 0)
-    *s_bcast = s;
-  __syncthreads();
-  const double v = *s_bcast;
-  __syncthreads(); // s_red and s_bcast may be written again
-  return v;
-}
-
-// the workgroup's shares of r.z and r.r into their slots
-__device__ __forceinline__ void store_rz_rr_partials(
-    double acc_rz, double acc_rr, double* __restrict__ partials_rz,
-    double* __restrict__ partials_rr, int len, double* s_red)
-{
-  const double s_rz = spmv_block_sum(acc_rz, s_red);
-  __syncthreads(); // s_red is reused
-  const double s_rr = spmv_block_sum(acc_rr, s_red);
-  if (threadIdx.x == 0) {
-    partials_rz[blockIdx.x] = s_rz;
-    partials_rr[blockIdx.x] = s_rr;
-  }
-  clear_partials_tail(partials_rz, len);
-  clear_partials_tail(partials_rr, len);
-}
 
 // What the first kernel of iteration k finds about iteration k - 1: the solve
 // stops there when rr[k-1] met the tolerance (k >= 2), or at k = 0 when
@@ -158,28 +78,6 @@ __device__ __forceinline__ void stream_update_r(int64_t n2, double nalpha,
       acc_rz += rv[u].y * zy;
       acc_rr += rv[u].x * rv[u].x;
       acc_rr += rv[u].y * rv[u].y;
-    }
-  }
-}
-
-// x += alpha p
-template <bool NT>
-__device__ __forceinline__ void stream_axpy(int64_t n2, double alpha,
-                                            const double* p, double* x)
-{
-  SPMV_FOR_UNITS(n2)
-  {
-    f64x2 pv[kU], xv[kU];
-    SPMV_FOR_LANE_ELEMS(i, n2)
-    {
-      pv[u] = vload<NT>(p, i);
-      xv[u] = vload<NT>(x, i);
-    }
-    SPMV_FOR_LANE_ELEMS(i, n2)
-    {
-      xv[u].x += alpha * pv[u].x;
-      xv[u].y += alpha * pv[u].y;
-      vstore<NT>(x, i, xv[u]);
     }
   }
 }
@@ -240,9 +138,9 @@ __device__ __forceinline__ void update_r_body(
   const double nalpha = -alpha;
   double acc_rz = 0.0, acc_rr = 0.0;
   stream_update_r<NT>(n >> 1, nalpha, Ap, dinv, r, acc_rz, acc_rr);
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+  if (odd_tail(n))
     tail_update_r(n - 1, nalpha, Ap, dinv, r, acc_rz, acc_rr);
-  store_rz_rr_partials(acc_rz, acc_rr, partials_rz, partials_rr, len, s_red);
+  store_pair_partials(acc_rz, acc_rr, partials_rz, partials_rr, len, s_red);
 }
 
 // body of update_xp / update_xp_cs: rz_new, rr_new are iteration k's scalars
@@ -256,7 +154,7 @@ __device__ __forceinline__ void update_xp_body(
   const double alpha = rz_old / pap;
   const double beta = rz_new / rz_old;
   const bool converged = sqrt(rr_new) / sqrt(rr0) < rtol;
-  const bool tail = (n & 1) && blockIdx.x == 0 && threadIdx.x == 0;
+  const bool tail = odd_tail(n);
   const int64_t i = n - 1;
   if (converged) { // x takes this iteration's update, p stays
     stream_axpy<NT>(n >> 1, alpha, p, x);
@@ -298,7 +196,7 @@ __global__ __launch_bounds__(kBlock) void pcg_init_kernel(
     acc_rz += v * z;
     acc_rr += v * v;
   }
-  store_rz_rr_partials(acc_rz, acc_rr, partials_rz, partials_rr, len, s_red);
+  store_pair_partials(acc_rz, acc_rr, partials_rz, partials_rr, len, s_red);
 }
 
 template <bool NT>
@@ -480,27 +378,7 @@ __global__ __launch_bounds__(kBlock) void jacobi_invert_kernel(
     atomicAdd(bad_count, bad);
 }
 
-bool aligned16(const void* p)
-{
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
-
 } // namespace
-
-// see blas1.hip
-#define SPMV_LAUNCH_NT(ctx, n, kernel, grid, st, ...)                          \
-  do {                                                                         \
-    if ((int64_t)(n) >= (ctx)->blas1_nt_min_elems)                             \
-      hipLaunchKernelGGL(kernel<true>, dim3(grid), dim3(kBlock), 0, st,        \
-                         __VA_ARGS__);                                         \
-    else                                                                       \
-      hipLaunchKernelGGL(kernel<false>, dim3(grid), dim3(kBlock), 0, st,       \
-                         __VA_ARGS__);                                         \
-  } while (0)
-
-// every kernel of iteration k: the workspace is this context's, k in range
-#define SPMV_PCG_REQUIRE_K(ctx, ws, k, kmin)                                   \
-  SPMV_REQUIRE((ws) && (ws)->ctx == (ctx) && (k) >= (kmin) && (k) <= (ws)->kmax)
 
 extern "C" {
 
@@ -639,7 +517,7 @@ int spmv_hip_pcg_reduce_pAp(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
                             void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_PCG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_SET_DEVICE(ctx);
   hipLaunchKernelGGL(pcg_reduce_pAp_kernel, dim3(1), dim3(kBlock), 0,
                      spmv_stream(ctx, stream), ws->partials,
@@ -653,7 +531,7 @@ int spmv_hip_pcg_reduce_pAp2(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
                              const double* partials2, void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_PCG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_REQUIRE(partials2);
   SPMV_SET_DEVICE(ctx);
   hipLaunchKernelGGL(pcg_reduce_pAp_kernel, dim3(1), dim3(kBlock), 0,
@@ -667,7 +545,7 @@ int spmv_hip_pcg_reduce_rz_rr(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
                               void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_PCG_REQUIRE_K(ctx, ws, k, 0);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 0);
   SPMV_SET_DEVICE(ctx);
   hipLaunchKernelGGL(pcg_reduce_rz_rr_kernel, dim3(1), dim3(kBlock), 0,
                      spmv_stream(ctx, stream), ws->partials_rz,
@@ -682,14 +560,13 @@ int spmv_hip_pcg_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
                               double* r, void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_PCG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_REQUIRE(n >= 0 && (n == 0 || (Ap && dinv && r)));
-  SPMV_REQUIRE(aligned16(Ap) && aligned16(dinv) && aligned16(r));
+  SPMV_REQUIRE(aligned16(Ap, dinv, r));
   SPMV_SET_DEVICE(ctx);
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, pcg_update_r_kernel, grid, spmv_stream(ctx, stream), n,
-                 k, ws->zr, ws->pAp, ws->sc, Ap, dinv, r, ws->partials_rz,
-                 ws->partials_rr, ctx->dot_blocks);
+  SPMV_LAUNCH_NT(ctx, n, pcg_update_r_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, k, ws->zr, ws->pAp, ws->sc, Ap,
+                 dinv, r, ws->partials_rz, ws->partials_rr, ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -699,13 +576,13 @@ int spmv_hip_pcg_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
                                double* x, double* p, void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_PCG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_REQUIRE(n >= 0 && (n == 0 || (r && dinv && x && p)));
-  SPMV_REQUIRE(aligned16(r) && aligned16(dinv) && aligned16(x) && aligned16(p));
+  SPMV_REQUIRE(aligned16(r, dinv, x, p));
   SPMV_SET_DEVICE(ctx);
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, pcg_update_xp_kernel, grid, spmv_stream(ctx, stream),
-                 n, k, ws->zr, ws->pAp, ws->sc, r, dinv, x, p);
+  SPMV_LAUNCH_NT(ctx, n, pcg_update_xp_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, k, ws->zr, ws->pAp, ws->sc, r,
+                 dinv, x, p);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -716,15 +593,14 @@ int spmv_hip_pcg_update_r_cs_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
                                  const double* pap_partials2, void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_PCG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_REQUIRE(n >= 0 && (n == 0 || (Ap && dinv && r)));
-  SPMV_REQUIRE(aligned16(Ap) && aligned16(dinv) && aligned16(r));
+  SPMV_REQUIRE(aligned16(Ap, dinv, r));
   SPMV_SET_DEVICE(ctx);
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, pcg_update_r_cs_kernel, grid, spmv_stream(ctx, stream),
-                 n, k, ws->zr, ws->pAp, ws->sc, ws->partials, pap_partials2,
-                 ctx->dot_blocks, Ap, dinv, r, ws->partials_rz,
-                 ws->partials_rr);
+  SPMV_LAUNCH_NT(ctx, n, pcg_update_r_cs_kernel, stream_grid(ctx, n),
+                 spmv_stream(ctx, stream), n, k, ws->zr, ws->pAp, ws->sc,
+                 ws->partials, pap_partials2, ctx->dot_blocks, Ap, dinv, r,
+                 ws->partials_rz, ws->partials_rr);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -735,12 +611,11 @@ int spmv_hip_pcg_update_xp_cs_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
                                   void* stream)
 {
   SPMV_REQUIRE(ctx);
-  SPMV_PCG_REQUIRE_K(ctx, ws, k, 1);
+  SPMV_REQUIRE_WS_K(ctx, ws, k, 1);
   SPMV_REQUIRE(n >= 0 && (n == 0 || (r && dinv && x && p)));
-  SPMV_REQUIRE(aligned16(r) && aligned16(dinv) && aligned16(x) && aligned16(p));
+  SPMV_REQUIRE(aligned16(r, dinv, x, p));
   SPMV_SET_DEVICE(ctx);
-  const int grid = spmv_grid_for(ctx, n / 2, (int)kUnit);
-  SPMV_LAUNCH_NT(ctx, n, pcg_update_xp_cs_kernel, grid,
+  SPMV_LAUNCH_NT(ctx, n, pcg_update_xp_cs_kernel, stream_grid(ctx, n),
                  spmv_stream(ctx, stream), n, k, ws->zr, ws->pAp, ws->sc,
                  ws->partials_rz, ws->partials_rr, ctx->dot_blocks, r, dinv, x,
                  p);
