@@ -49,6 +49,7 @@ typedef struct spmv_hip_cg_ws spmv_hip_cg_ws;       /* cg() work vectors   */
 typedef struct spmv_hip_cgb_ws spmv_hip_cgb_ws;     /* cg_block() scalars  */
 typedef struct spmv_hip_pcg_ws spmv_hip_pcg_ws;     /* pcg() scalars       */
 typedef struct spmv_hip_bicg_ws spmv_hip_bicg_ws;   /* bicgstab() scalars  */
+typedef struct spmv_hip_gmres_ws spmv_hip_gmres_ws; /* gmres() scalars     */
 typedef struct spmv_hip_comm spmv_hip_comm;         /* RCCL communicator   */
 
 int spmv_hip_abi_version(void);
@@ -1145,6 +1146,111 @@ int spmv_hip_bicg_update_p_cs_f64(spmv_hip_ctx* ctx, spmv_hip_bicg_ws* ws,
                                   int k, int64_t n, const double* r,
                                   const double* v, const double* dinv,
                                   double* p, double* ph, void* stream);
+
+/* ---- Restarted GMRES with right preconditioning (spmv::gmres) ----------------
+ * For nonsymmetric systems; the recurrence is stated in host/cg.h.  The basis
+ * is `nvec` vectors of n doubles at V, V + stride, ... (stride even, >= n, V
+ * 16-byte aligned); 1 <= nvec <= SPMV_HIP_GMRES_MAX_RESTART.  One inner step
+ * at basis size j + 1, w = A M^-1 v_j:
+ *   multi_dot(j + 1) ; reduce(H, j + 1) ; [all-reduce of j + 1 at array H]
+ *   multi_axpy(first) ; multi_dot(j + 1) ; reduce(C, j + 1) ; [all-reduce at C]
+ *   multi_axpy(second: w -= sum c_i v_i ; h_i += c_i ; partials of w.w)
+ *   [reduce(WW, 1) ; all-reduce of 1 at WW] ; givens(j, reduced)
+ *   scale(w -> v_{j+1})
+ * and per cycle: residual ; [reduce(WW, 1) ; all-reduce] ; start ; scale(r ->
+ * v_0) ; the inner steps ; solve_y ; combine ; M^-1 ; add.
+ *
+ * Device state of a workspace: the arrays named below, `done` (raised by
+ * givens -- tolerance, k == kmax, hn == 0 (status 1), R_jj == 0 (status 2) --
+ * and by start when r.r == 0), kstop, status, k (inner steps completed), jn
+ * (columns kept in the current cycle) and `finished`.  After `done`
+ * multi_dot, reduce, multi_axpy, givens, scale and start return at once;
+ * solve_y, combine and add run until `finished`, which the residual kernel
+ * raises when it finds `done`: the cycle that stopped gets its update exactly
+ * once however many cycles the host has enqueued behind it. */
+#define SPMV_HIP_GMRES_MAX_RESTART 64
+#define SPMV_HIP_GMRES_GROUP 8 /* basis vectors per group of the multi kernels */
+enum {
+  SPMV_HIP_GMRES_H = 0,       /* 64: first-pass, then summed coefficients      */
+  SPMV_HIP_GMRES_C = 1,       /* 64: second-pass coefficients                  */
+  SPMV_HIP_GMRES_WW = 2,      /* 1: w.w / r.r where a reducer put it           */
+  SPMV_HIP_GMRES_CS = 3,      /* 64: rotation cosines                          */
+  SPMV_HIP_GMRES_SN = 4,      /* 64: rotation sines                            */
+  SPMV_HIP_GMRES_G = 5,       /* 65: the rotated right-hand side               */
+  SPMV_HIP_GMRES_Y = 6,       /* 64                                            */
+  SPMV_HIP_GMRES_R = 7,       /* 64 x 64: R_il at [l * 64 + i]                 */
+  SPMV_HIP_GMRES_HIST = 8,    /* kmax + 1: hist[k]                             */
+  SPMV_HIP_GMRES_INV = 9,     /* 1: what scale multiplies by                   */
+  SPMV_HIP_GMRES_PART = 10,   /* 64 x dot_partials_len: [i][workgroup]         */
+  SPMV_HIP_GMRES_PART_WW = 11 /* dot_partials_len: partials of w.w / r.r       */
+};
+int spmv_hip_gmres_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_gmres_ws** ws);
+int spmv_hip_gmres_ws_destroy(spmv_hip_gmres_ws* ws);
+/* kmax <= the capacity, 1 <= restart <= SPMV_HIP_GMRES_MAX_RESTART */
+int spmv_hip_gmres_ws_reset(spmv_hip_gmres_ws* ws, double rtol, int kmax,
+                            int restart, void* stream);
+int spmv_hip_gmres_ws_capacity(const spmv_hip_gmres_ws* ws, int* kmax);
+int spmv_hip_gmres_ws_done_flag(spmv_hip_gmres_ws* ws, const int32_t** done);
+/* ---- TEST HOOKS, not part of the stable surface: spmv_hip_gmres_ws_array,
+ * _ws_set_state and _ws_get_state exist so that a kernel can be launched alone
+ * with chosen scalars (tests/test_gpu_gmres_kernels.py).  gmres() uses only
+ * ws_array for the three all-reduce addresses H, C and WW.  set_state
+ * overwrites done, k, jn and finished: never call it on a workspace of a
+ * running solve. */
+/* device address (and length, optional) of one of the arrays above */
+int spmv_hip_gmres_ws_array(spmv_hip_gmres_ws* ws, int which, double** p,
+                            int64_t* count);
+/* copies {done, kstop, status, k} (4 x int32) and hist[0..kmax] to the host
+ * (async on stream); a host_hist shorter than the capacity + 1 ->
+ * SPMV_HIP_EINVAL, nothing is copied.  Either destination may be NULL. */
+int spmv_hip_gmres_ws_read_async(spmv_hip_gmres_ws* ws,
+                                 int32_t* host_done_kstop_status_k,
+                                 double* host_hist, size_t host_hist_len,
+                                 void* stream);
+/* for driving single kernels: installs k, jn, done (kstop = k) and finished
+ * (waits for the stream); reads {done, kstop, status, k, jn, finished} */
+int spmv_hip_gmres_ws_set_state(spmv_hip_gmres_ws* ws, int k, int jn, int done,
+                                int finished, void* stream);
+int spmv_hip_gmres_ws_get_state(spmv_hip_gmres_ws* ws, int32_t* host_words6,
+                                void* stream);
+/* partials of v_i . w, i = 0..nvec-1, into PART */
+int spmv_hip_gmres_multi_dot_f64(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws,
+                                 int64_t n, const double* V, int64_t stride,
+                                 int nvec, const double* w, void* stream);
+/* which = H or C: rows 0..nvec-1 of PART -> that array; WW (nvec = 1): PART_WW
+ * -> WW.  One launch, one workgroup per row. */
+int spmv_hip_gmres_reduce(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws, int which,
+                          int nvec, void* stream);
+/* w = w - coef_0 v_0 - ... in that order; second == 0: coef = H; otherwise
+ * coef = C, H_i = H_i + C_i and the partials of w.w go to PART_WW */
+int spmv_hip_gmres_multi_axpy_f64(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws,
+                                  int second, int64_t n, const double* V,
+                                  int64_t stride, int nvec, double* w,
+                                  void* stream);
+/* reduced == 0: adds PART_WW itself; otherwise takes WW */
+int spmv_hip_gmres_givens(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws, int j,
+                          int reduced, void* stream);
+int spmv_hip_gmres_start(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws, int first,
+                         int reduced, void* stream);
+/* dst = src * INV (dst may be src) */
+int spmv_hip_gmres_scale_f64(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws, int64_t n,
+                             const double* src, double* dst, void* stream);
+int spmv_hip_gmres_solve_y(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws,
+                           void* stream);
+/* u = Y_0 v_0 ; u = u + Y_i v_i, i = 1..jn-1 (jn == 0: u is not written) */
+int spmv_hip_gmres_combine_f64(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws,
+                               int64_t n, const double* V, int64_t stride,
+                               double* u, void* stream);
+/* x = x + z (jn == 0: nothing) */
+int spmv_hip_gmres_add_f64(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws, int64_t n,
+                           const double* z, double* x, void* stream);
+/* r = b - Ax (Ax == NULL: r = b) ; partials of r.r into PART_WW */
+int spmv_hip_gmres_residual_f64(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws,
+                                int64_t n, const double* b, const double* Ax,
+                                double* r, void* stream);
+/* z = dinv * v (elementwise): the diagonal right preconditioner */
+int spmv_hip_gmres_diag_f64(spmv_hip_ctx* ctx, int64_t n, const double* dinv,
+                            const double* v, double* z, void* stream);
 
 /* ---- 3-D Poisson generator (not in the reference)
  * 7-point stencil on an n^3 grid, natural ordering, diag 6, off-diag -1.

@@ -490,6 +490,33 @@ int spmvh_bicgstab(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                    double* rnorm_history, spmvh_bicgstab_workspace* ws,
                    int flags, double* spmv_ms_total, int* spmv_launches);
 
+/* ---- Restarted GMRES (spmv::gmres, host/cg.h; not in the reference) ---------
+ * spmvh_gmres: GMRES(restart) from x0 = 0 with a right preconditioner for a
+ * matrix that need not be symmetric.  The preconditioner: none (dinv NULL,
+ * cheb_degree 0, sgs NULL), the diagonal dinv, chebyshev_apply (cheb_degree >=
+ * 1, dinv or NULL, lmin, lmax) or sgs_apply (sgs; excludes the others).  1 <=
+ * restart <= 64.  x must not overlap b or dinv.  *num_its = the inner steps
+ * completed; *status (may be NULL) = 0 (tolerance met or kmax reached), 1 (the
+ * lucky breakdown: x solves the system) or 2 (a zero pivot: x is the update of
+ * the columns before it).  rnorm_history (may be NULL): kmax + 1 entries.
+ * ws: a reusable spmv::GmresWorkspace (may be NULL).  flags: bit 0 ->
+ * CgOptions::time_spmv (*spmv_ms_total, *spmv_launches, both may be NULL; one
+ * SpMV per inner step), bits 8-15 CgOptions::poll_every (0 = default).
+ * spmvh_gmres_check_arguments: the argument rules alone (no device). */
+typedef struct spmvh_gmres_workspace spmvh_gmres_workspace;
+int spmvh_gmres_workspace_create(spmvh_exec* exec, spmvh_gmres_workspace** ws);
+int spmvh_gmres_workspace_destroy(spmvh_gmres_workspace* ws);
+int spmvh_gmres_workspace_reserve_timing(spmvh_gmres_workspace* ws,
+                                         int iterations);
+int spmvh_gmres_check_arguments(int restart, int kmax, int cheb_degree,
+                                double lmin, double lmax);
+int spmvh_gmres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                const double* b, double* x, const double* dinv,
+                int cheb_degree, double lmin, double lmax, spmvh_sgs* sgs,
+                int restart, int kmax, double rtol, int* num_its, int* status,
+                double* rnorm_history, spmvh_gmres_workspace* ws, int flags,
+                double* spmv_ms_total, int* spmv_launches);
+
 #ifdef __cplusplus
 }
 #endif

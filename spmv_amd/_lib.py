@@ -232,6 +232,29 @@ _PROTOS = {
                                         vp, vp, vp, vp], C.c_int),
     "spmv_hip_bicg_update_p_cs_f64": ([vp, vp, C.c_int, i64, vp, vp, vp, vp,
                                        vp, vp], C.c_int),
+    "spmv_hip_gmres_ws_create": ([vp, C.c_int, P(vp)], C.c_int),
+    "spmv_hip_gmres_ws_destroy": ([vp], C.c_int),
+    "spmv_hip_gmres_ws_reset": ([vp, f64, C.c_int, C.c_int, vp], C.c_int),
+    "spmv_hip_gmres_ws_capacity": ([vp, P(C.c_int)], C.c_int),
+    "spmv_hip_gmres_ws_done_flag": ([vp, P(vp)], C.c_int),
+    "spmv_hip_gmres_ws_array": ([vp, C.c_int, P(vp), P(i64)], C.c_int),
+    "spmv_hip_gmres_ws_read_async": ([vp, vp, vp, sz, vp], C.c_int),
+    "spmv_hip_gmres_ws_set_state": ([vp, C.c_int, C.c_int, C.c_int, C.c_int, vp],
+                                    C.c_int),
+    "spmv_hip_gmres_ws_get_state": ([vp, vp, vp], C.c_int),
+    "spmv_hip_gmres_multi_dot_f64": ([vp, vp, i64, vp, i64, C.c_int, vp, vp],
+                                     C.c_int),
+    "spmv_hip_gmres_reduce": ([vp, vp, C.c_int, C.c_int, vp], C.c_int),
+    "spmv_hip_gmres_multi_axpy_f64": ([vp, vp, C.c_int, i64, vp, i64, C.c_int, vp,
+                                       vp], C.c_int),
+    "spmv_hip_gmres_givens": ([vp, vp, C.c_int, C.c_int, vp], C.c_int),
+    "spmv_hip_gmres_start": ([vp, vp, C.c_int, C.c_int, vp], C.c_int),
+    "spmv_hip_gmres_scale_f64": ([vp, vp, i64, vp, vp, vp], C.c_int),
+    "spmv_hip_gmres_solve_y": ([vp, vp, vp], C.c_int),
+    "spmv_hip_gmres_combine_f64": ([vp, vp, i64, vp, i64, vp, vp], C.c_int),
+    "spmv_hip_gmres_add_f64": ([vp, vp, i64, vp, vp, vp], C.c_int),
+    "spmv_hip_gmres_residual_f64": ([vp, vp, i64, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_gmres_diag_f64": ([vp, i64, vp, vp, vp, vp], C.c_int),
     "spmv_hip_csr_diagonal_f64": ([vp, i32, vp, vp, vp, vp, vp], C.c_int),
     "spmv_hip_csr_diagonal_f32": ([vp, i32, vp, vp, vp, vp, vp], C.c_int),
     "spmv_hip_jacobi_invert_f64": ([vp, i64, vp, vp, vp, vp], C.c_int),

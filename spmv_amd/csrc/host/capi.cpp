@@ -52,6 +52,7 @@ struct spmvh_pcg_workspace : WorkspaceHandle<PcgWorkspace> {};
 struct spmvh_chebyshev_workspace : WorkspaceHandle<ChebyshevWorkspace> {};
 struct spmvh_bicgstab_workspace : WorkspaceHandle<BicgstabWorkspace> {};
 struct spmvh_sgs_workspace : WorkspaceHandle<SgsWorkspace> {};
+struct spmvh_gmres_workspace : WorkspaceHandle<GmresWorkspace> {};
 struct spmvh_sgs_build {
   SgsHostPlan plan;
 };
@@ -1490,6 +1491,66 @@ int spmvh_bicgstab(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     *num_its = bicgstab(*comm->comm, *exec->hip, *A->A, b, x, dinv, kmax, rtol,
                         rnorm_history ? &hist : nullptr, &opt, &st,
                         ws ? ws->ws.get() : nullptr, &how);
+    if (status)
+      *status = how;
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
+  });
+}
+
+// ---- GMRES ------------------------------------------------------------------------------
+int spmvh_gmres_workspace_create(spmvh_exec* exec, spmvh_gmres_workspace** ws)
+{
+  return workspace_create<GmresWorkspace>(exec, ws);
+}
+
+int spmvh_gmres_workspace_destroy(spmvh_gmres_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_gmres_workspace_reserve_timing(spmvh_gmres_workspace* ws,
+                                         int iterations)
+{
+  return workspace_reserve_timing(ws, iterations);
+}
+
+int spmvh_gmres_check_arguments(int restart, int kmax, int cheb_degree,
+                                double lmin, double lmax)
+{
+  return guarded([&] {
+    GmresPreconditioner pre;
+    pre.cheb_degree = cheb_degree;
+    pre.lmin = lmin;
+    pre.lmax = lmax;
+    gmres_check_arguments(&pre, restart, kmax, 0);
+  });
+}
+
+int spmvh_gmres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                const double* b, double* x, const double* dinv,
+                int cheb_degree, double lmin, double lmax, spmvh_sgs* sgs,
+                int restart, int kmax, double rtol, int* num_its, int* status,
+                double* rnorm_history, spmvh_gmres_workspace* ws, int flags,
+                double* spmv_ms_total, int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && num_its, "NULL argument");
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff) // bits 8-15: CgOptions::poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    GmresPreconditioner pre;
+    pre.dinv = dinv;
+    pre.cheb_degree = cheb_degree;
+    pre.lmin = lmin;
+    pre.lmax = lmax;
+    pre.sgs = sgs ? sgs->M.get() : nullptr;
+    CgStats st;
+    int how = 0;
+    *num_its = gmres(*comm->comm, *exec->hip, *A->A, b, x, &pre, restart, kmax,
+                     rtol, rnorm_history ? &hist : nullptr, &opt, &st,
+                     ws ? ws->ws.get() : nullptr, &how);
     if (status)
       *status = how;
     copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);

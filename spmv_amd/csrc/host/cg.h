@@ -10,11 +10,13 @@
 #include "comm.h"
 #include "executor.h"
 #include "matrix.h"
+#include "solver_args.h"
 
 struct spmv_hip_cg_ws;
 struct spmv_hip_cgb_ws;
 struct spmv_hip_pcg_ws;
 struct spmv_hip_bicg_ws;
+struct spmv_hip_gmres_ws;
 struct spmv_hip_mcgs_plan;
 
 namespace spmv
@@ -307,7 +309,7 @@ int pcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
 //
 // a[] and b[] take `degree` entries each.  1 <= degree <= 16 ("degree"); lmin
 // and lmax finite with 0 < lmin < lmax ("bounds"): std::runtime_error otherwise.
-constexpr int kChebyshevMaxDegree = 16;
+// (kChebyshevMaxDegree = 16: solver_args.h, whose declaration this repeats)
 void chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
                             double* b);
 
@@ -653,5 +655,134 @@ int bicgstab(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
              double rtol, std::vector<double>* rnorm_history = nullptr,
              const CgOptions* options = nullptr, CgStats* stats = nullptr,
              BicgstabWorkspace* workspace = nullptr, int* status = nullptr);
+
+// ---- Restarted GMRES ----------------------------------------------------------
+// (kGmresMaxRestart = 64: solver_args.h)
+
+// The right preconditioner of gmres(): any FIXED linear operator.  All
+// defaults: none.
+struct GmresPreconditioner {
+  // the inverse diagonal of bicgstab()'s dinv (z = dinv*v), or Chebyshev's dinv
+  const double* dinv = nullptr;
+  // >= 1: z = chebyshev_apply(v, dinv (may be nullptr), cheb_degree, lmin, lmax)
+  int cheb_degree = 0;
+  double lmin = 0, lmax = 0;
+  // z = sgs_apply(*sgs, v); excludes the two above ("preconditioner")
+  const SgsPreconditioner* sgs = nullptr;
+};
+
+// Work vectors + device scalars of gmres(), kept across calls like
+// BicgstabWorkspace; it regrows itself when a call needs more rows, a longer
+// restart or more iterations.  Owns the ChebyshevWorkspace of a Chebyshev
+// preconditioner.
+class GmresWorkspace : public SolverWorkspace
+{
+public:
+  explicit GmresWorkspace(HipExecutor& exec);
+  ~GmresWorkspace();
+
+  // ---- internal to gmres() ----
+  // basis_elems = stride * (restart + 1); need_b / need_dinv: the caller's b /
+  // dinv is not 16-byte aligned and lives in the workspace's copy
+  void ensure(int64_t M, int64_t N_padded, int64_t basis_elems, int kmax,
+              bool need_b, bool need_dinv);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(2 * (size_t)std::max(iterations, 0));
+  }
+  void release();
+
+  spmv_hip_gmres_ws* ws = nullptr;
+  ChebyshevWorkspace cheb;
+  int kmax_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, v_cap = -1, b_cap = -1, dinv_cap = -1;
+  double *r = nullptr, *ax = nullptr, *u = nullptr; // m_cap
+  // n_cap: padded -- z = M^-1 v_j is what the SpMV reads with a
+  // preconditioner, x is the iterate (r = b - A x reads it through
+  // Matrix::mult); the ghost tails are zeroed by every solve
+  double *z = nullptr, *x = nullptr;
+  double* V = nullptr;    // v_cap: the basis, restart + 1 padded vectors
+  double* b = nullptr;    // b_cap: the copy of an unaligned b
+  double* dinv = nullptr; // dinv_cap: the copy of an unaligned dinv
+  // flags: {done, kstop, status, k}; timing_ev: 2 events per inner step
+};
+
+// the argument rules of gmres() that need no device (std::runtime_error):
+// kmax < 0 ("kmax"), restart outside 1..kGmresMaxRestart ("restart"), sgs
+// together with dinv or a Chebyshev degree ("preconditioner"),
+// chebyshev_coefficients' rules ("degree", "bounds"), sgs->rows() != rows
+// (gmres_check_rules of solver_args.h on the fields of M)
+void gmres_check_arguments(const GmresPreconditioner* M, int restart, int kmax,
+                           int64_t rows);
+
+// Restarted GMRES(m) from x0 = 0 with a RIGHT preconditioner and twice-iterated
+// classical Gram-Schmidt (CGS2), for a matrix that need not be symmetric.  It
+// has no breakdown except the lucky one, and M^-1 is any fixed linear operator:
+// none, dinv* (elementwise), chebyshev_apply or sgs_apply.  Only Matrix::mult
+// is used: every plan form, both storages and every halo model serve.  With
+// `.` the global dot product, m = restart, every product, sum, difference,
+// quotient and square root one rounding of its own:
+//
+//   x = 0; r = b; rr0 = b.b; hist[0] = sqrt(rr0); k = 0; status = 0
+//   rr0 == 0: return 0                       (the rule of pcg / bicgstab)
+//   cycle:
+//     beta = sqrt(r.r) (first cycle: hist[0]); v_0 = r * (1.0 / beta);
+//     g = (beta, 0, ..)
+//     for j = 0 .. m-1:
+//       w  = A (M^-1 v_j)                    halo update first
+//       h_i = v_i . w, i = 0..j              ONE multi-dot, one all-reduce of j+1
+//       for i = 0..j in order:  w = w - h_i * v_i
+//       c_i = v_i . w, i = 0..j              second pass, one all-reduce of j+1
+//       for i = 0..j in order:  w = w - c_i * v_i ;  h_i = h_i + c_i
+//       hn = sqrt(w.w)                       all-reduce of 1
+//       column = (h_0..h_j, hn); rotations 0..j-1 in order:
+//         t = c_i*col_i + s_i*col_{i+1}; col_{i+1} = -s_i*col_i + c_i*col_{i+1};
+//         col_i = t
+//       new rotation from a = col_j, b = col_{j+1}:
+//         b == 0:     c = 1, s = 0
+//         |b| > |a|:  tau = a/b; s = 1/sqrt(1 + tau*tau); c = s*tau
+//         else:       tau = b/a; c = 1/sqrt(1 + tau*tau); s = c*tau
+//       R_jj = c*a + s*b
+//       R_jj == 0: status = 2; the column is discarded; leave with j columns
+//       g_{j+1} = -s*g_j; g_j = c*g_j; k += 1; hist[k] = |g_{j+1}|
+//       hn == 0: status = 1 (lucky breakdown); leave the loop
+//       hist[k] / hist[0] < rtol or k == kmax: leave the loop
+//       v_{j+1} = w * (1.0 / hn)
+//     with the jn columns kept, i = jn-1 .. 0:
+//       s = g_i; for l = i+1 .. jn-1 in order: s = s - R_il * y_l; y_i = s / R_ii
+//     jn > 0: u = y_0 * v_0; for i = 1..jn-1: u = u + y_i * v_i; x = x + M^-1 u
+//     if the loop was left early: return k
+//     r = b - A x  (the true residual; its norm is NOT written to the history)
+//     r.r == 0: return k
+//
+// rnorm_history receives hist[0..k]: for a right preconditioner hist[k] is the
+// residual norm of x in exact arithmetic, so the histories compare with
+// bicgstab()'s; the stopping test is cg()'s.  Returns k, the inner steps
+// completed; `status` (optional) receives 0, 1 or 2 as above.
+//
+// As in bicgstab(): scalars (the Hessenberg columns, the rotations, g, the
+// history, k) stay on the device, reductions are two-stage and deterministic,
+// the decision to stop is taken on the device and the host only looks at a
+// pinned flag every `poll_every` inner steps.  After the stop the Arnoldi
+// kernels return at once, the cycle that stopped still gets its update of x
+// exactly once, and nothing afterwards changes x, the history or k (the
+// preconditioner and the SpMV may still run on scratch).  The iterate lives in
+// the workspace's padded vector (r = b - A x reads it through Matrix::mult)
+// and `x` takes ONE copy at the end, so an `x` of any alignment serves; a `b`
+// or `dinv` that is not 16-byte aligned goes through the workspace's copy.
+// `x` must not overlap `b` or `dinv` (std::runtime_error, "overlaps"); the
+// argument rules are those of gmres_check_arguments, checked before anything
+// touches a device; the executor's stream is restored on every exit path.
+//
+// options: poll_every and time_spmv apply (time_spmv brackets the Matrix::mult
+//          of every Arnoldi step: CgStats::spmv_launches is 1 per inner step
+//          enqueued; the SpMVs of r = b - A x and of a Chebyshev
+//          preconditioner are not timed); consumer_reductions, defer_x and
+//          mixed are IGNORED.
+int gmres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+          const double* b, double* x, const GmresPreconditioner* M, int restart,
+          int kmax, double rtol, std::vector<double>* rnorm_history = nullptr,
+          const CgOptions* options = nullptr, CgStats* stats = nullptr,
+          GmresWorkspace* workspace = nullptr, int* status = nullptr);
 
 } // namespace spmv

@@ -250,39 +250,7 @@ int pcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
 // r, dinv in, r, d, z out; a step: w, r, dinv, d, z in, d, z out, the last one
 // without d out; update_xp: z, x, p in, x, p out), 10 for degree 1.
 // ---------------------------------------------------------------------------
-void chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
-                            double* b)
-{
-  if (degree < 1 || degree > kChebyshevMaxDegree)
-    throw std::runtime_error(
-        "spmv::chebyshev_coefficients - Error: degree must be 1.."
-        + std::to_string(kChebyshevMaxDegree));
-  if (!std::isfinite(lmin) || !std::isfinite(lmax) || !(lmin > 0.0)
-      || !(lmin < lmax))
-    throw std::runtime_error("spmv::chebyshev_coefficients - Error: bounds must "
-                             "be finite with 0 < lmin < lmax");
-  if (!a || !b)
-    throw std::runtime_error("spmv::chebyshev_coefficients - Error: NULL output");
-  // (volatile: every operation below is one fp64 rounding, whatever the
-  // compiler's contraction setting)
-  volatile double theta = 0.5 * (lmax + lmin);
-  volatile double delta = 0.5 * (lmax - lmin);
-  volatile double sigma = theta / delta;
-  volatile double rho = 1.0 / sigma;
-  a[0] = 0.0;
-  b[0] = 1.0 / theta;
-  for (int j = 1; j < degree; ++j) {
-    volatile double two_sigma = 2.0 * sigma;
-    volatile double den = two_sigma - rho;
-    volatile double rho_new = 1.0 / den;
-    volatile double aj = rho_new * rho;
-    volatile double two_rho = 2.0 * rho_new;
-    a[j] = aj;
-    b[j] = two_rho / delta;
-    rho = rho_new;
-  }
-}
-
+// (chebyshev_coefficients: solver_args.cpp)
 ChebyshevWorkspace::~ChebyshevWorkspace() { release(); }
 
 void ChebyshevWorkspace::release()

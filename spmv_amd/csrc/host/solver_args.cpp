@@ -1,0 +1,87 @@
+// see solver_args.h
+#include "solver_args.h"
+
+#include <cmath>
+#include <limits>
+#include <stdexcept>
+#include <string>
+
+namespace spmv
+{
+
+void chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
+                            double* b)
+{
+  if (degree < 1 || degree > kChebyshevMaxDegree)
+    throw std::runtime_error(
+        "spmv::chebyshev_coefficients - Error: degree must be 1.."
+        + std::to_string(kChebyshevMaxDegree));
+  if (!std::isfinite(lmin) || !std::isfinite(lmax) || !(lmin > 0.0)
+      || !(lmin < lmax))
+    throw std::runtime_error("spmv::chebyshev_coefficients - Error: bounds must "
+                             "be finite with 0 < lmin < lmax");
+  if (!a || !b)
+    throw std::runtime_error("spmv::chebyshev_coefficients - Error: NULL output");
+  // (volatile: every operation below is one fp64 rounding, whatever the
+  // compiler's contraction setting)
+  volatile double theta = 0.5 * (lmax + lmin);
+  volatile double delta = 0.5 * (lmax - lmin);
+  volatile double sigma = theta / delta;
+  volatile double rho = 1.0 / sigma;
+  a[0] = 0.0;
+  b[0] = 1.0 / theta;
+  for (int j = 1; j < degree; ++j) {
+    volatile double two_sigma = 2.0 * sigma;
+    volatile double den = two_sigma - rho;
+    volatile double rho_new = 1.0 / den;
+    volatile double aj = rho_new * rho;
+    volatile double two_rho = 2.0 * rho_new;
+    a[j] = aj;
+    b[j] = two_rho / delta;
+    rho = rho_new;
+  }
+}
+
+void gmres_check_rules(int restart, int kmax, bool has_dinv, int cheb_degree,
+                       double lmin, double lmax, bool has_sgs, int64_t sgs_rows,
+                       int64_t rows)
+{
+  if (kmax < 0)
+    throw std::runtime_error("spmv::gmres - Error: kmax < 0");
+  if (restart < 1 || restart > kGmresMaxRestart)
+    throw std::runtime_error("spmv::gmres - Error: restart must be 1.."
+                             + std::to_string(kGmresMaxRestart));
+  if (has_sgs && (has_dinv || cheb_degree != 0))
+    throw std::runtime_error(
+        "spmv::gmres - Error: one preconditioner at a time (sgs excludes dinv "
+        "and the Chebyshev degree)");
+  if (cheb_degree != 0) {
+    double ca[kChebyshevMaxDegree], cb[kChebyshevMaxDegree];
+    chebyshev_coefficients(cheb_degree, lmin, lmax, ca, cb);
+  }
+  if (has_sgs && sgs_rows != rows)
+    throw std::runtime_error("spmv::gmres - Error: the preconditioner has "
+                             + std::to_string(sgs_rows) + " rows, A has "
+                             + std::to_string(rows));
+}
+
+int64_t gmres_basis_stride(int64_t N_padded)
+{
+  if (N_padded < 0 || N_padded == std::numeric_limits<int64_t>::max())
+    throw std::runtime_error("spmv::gmres - Error: the basis stride overflows");
+  return N_padded + (N_padded & 1);
+}
+
+int64_t gmres_basis_elems(int64_t N_padded, int restart)
+{
+  const int64_t stride = gmres_basis_stride(N_padded);
+  const int64_t count = (int64_t)restart + 1;
+  if (restart < 0
+      || (stride != 0
+          && count > std::numeric_limits<int64_t>::max() / (int64_t)sizeof(double)
+                         / stride))
+    throw std::runtime_error("spmv::gmres - Error: the basis overflows");
+  return stride * count;
+}
+
+} // namespace spmv

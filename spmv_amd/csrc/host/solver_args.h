@@ -1,0 +1,34 @@
+// The solvers' argument rules and sizes that are plain C++ (no device, no other
+// header of the mirror: tools/solver_args_check.cpp compiles solver_args.cpp
+// alone, under the sanitizers).  Declared for users in cg.h.
+#pragma once
+
+#include <cstdint>
+
+namespace spmv
+{
+
+constexpr int kChebyshevMaxDegree = 16;
+constexpr int kGmresMaxRestart = 64;
+
+// see cg.h
+void chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
+                            double* b);
+
+// The argument rules of gmres() (std::runtime_error): kmax < 0 ("kmax"),
+// restart outside 1..kGmresMaxRestart ("restart"), an SGS preconditioner
+// together with a dinv or a Chebyshev degree ("preconditioner"),
+// chebyshev_coefficients' rules when cheb_degree != 0 ("degree", "bounds"),
+// an SGS preconditioner of sgs_rows != rows rows ("rows").
+void gmres_check_rules(int restart, int kmax, bool has_dinv, int cheb_degree,
+                       double lmin, double lmax, bool has_sgs, int64_t sgs_rows,
+                       int64_t rows);
+
+// stride of the basis vectors: N_padded rounded up to an even number, so that
+// every v_j is 16-byte aligned
+int64_t gmres_basis_stride(int64_t N_padded);
+// doubles of the basis: restart + 1 vectors at that stride; throws
+// ("overflows") when the product does not fit int64_t
+int64_t gmres_basis_elems(int64_t N_padded, int restart);
+
+} // namespace spmv

@@ -163,6 +163,13 @@ _PROTOS = {
     "spmvh_bicgstab_workspace_create": [vp, PTR(vp)],
     "spmvh_bicgstab_workspace_destroy": [vp],
     "spmvh_bicgstab_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_gmres_workspace_create": [vp, PTR(vp)],
+    "spmvh_gmres_workspace_destroy": [vp],
+    "spmvh_gmres_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_gmres_check_arguments": [C.c_int, C.c_int, C.c_int, f64, f64],
+    "spmvh_gmres": [vp, vp, vp, vp, vp, vp, C.c_int, f64, f64, vp, C.c_int,
+                    C.c_int, f64, PTR(C.c_int), PTR(C.c_int), vp, vp, C.c_int,
+                    PTR(f64), PTR(C.c_int)],
     "spmvh_bicgstab": [vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int),
                        PTR(C.c_int), vp, vp, C.c_int, PTR(f64), PTR(C.c_int)],
 }
@@ -1073,6 +1080,42 @@ def bicgstab(comm, exec_, A, b_ptr, x_ptr, dinv_ptr, kmax, rtol, ws=None,
          ws.h if ws else None,
          int(bool(time_spmv)) | (0 if consumer_reductions else 4)
          | ((int(poll_every) & 0xff) << 8), C.byref(ms), C.byref(n))
+    if stats is not None:
+        stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, hist[:k.value + 1], status.value
+
+
+class GmresWorkspace(_TimedWorkspace):
+    """spmv::GmresWorkspace: basis, work vectors and device scalars kept across
+    gmres() calls."""
+    _prefix = "gmres"
+
+
+GMRES_MAX_RESTART = 64
+
+
+def gmres(comm, exec_, A, b_ptr, x_ptr, restart, kmax, rtol, dinv_ptr=None,
+          cheb=None, sgs=None, ws=None, time_spmv=False, poll_every=0,
+          stats=None):
+    """spmv::gmres: restarted GMRES from x0 = 0 with a right preconditioner for
+    a matrix that need not be symmetric -> (k, rnorm_history, status).
+    Preconditioner: none; dinv_ptr (the inverse diagonal); cheb = (degree, lmin,
+    lmax) for chebyshev_apply (with dinv_ptr or without); or sgs, an
+    SgsPreconditioner.  status: 0 converged or kmax reached, 1 the lucky
+    breakdown, 2 a zero pivot (host/cg.h).  stats (optional dict) receives
+    spmv_ms_total and spmv_launches of a time_spmv solve (one SpMV per inner
+    step)."""
+    kmax = int(kmax)
+    k, n, status = C.c_int(), C.c_int(), C.c_int()
+    ms = f64()
+    hist = np.zeros(max(kmax, 0) + 1)
+    degree, lmin, lmax = cheb if cheb else (0, 0.0, 0.0)
+    call("spmvh_gmres", comm.h, exec_.h, A.h, b_ptr, x_ptr, dinv_ptr or None,
+         int(degree), float(lmin), float(lmax), sgs.h if sgs else None,
+         int(restart), kmax, float(rtol), C.byref(k), C.byref(status),
+         _np_ptr(hist), ws.h if ws else None,
+         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         C.byref(n))
     if stats is not None:
         stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
     return k.value, hist[:k.value + 1], status.value
