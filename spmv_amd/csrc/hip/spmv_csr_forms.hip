@@ -15,7 +15,7 @@
 #include <utility>
 #include <vector>
 
-#include "plan_malloc.h" // (last: hipMalloc / hipFree below are timed)
+#include "plan_scratch.h"
 
 namespace
 {
@@ -357,32 +357,24 @@ int spmv_build_row_list(spmv_hip_csr_plan* pl, const int32_t* rowptr)
   hipStream_t st = pl->ctx->stream;
   const int n = pl->num_rows;
   const size_t cap = (size_t)(pl->nnz < n ? pl->nnz : n);
-  int32_t* d_count = nullptr;
-  void* tmp = nullptr;
-  size_t tmp_bytes = 0;
-  SPMV_CHECK_HIP(hipMalloc(&pl->row_list, sizeof(int32_t) * (cap ? cap : 1)));
-  hipError_t e = hipMalloc(&d_count, sizeof(int32_t));
+  PlanScratch<int32_t> d_count;
+  PlanScratch<void> tmp;
+  SPMV_CHECK_HIP(spmv_plan_malloc(&pl->row_list, sizeof(int32_t) * (cap ? cap : 1)));
+  hipError_t e = d_count.alloc(1);
   hipcub::CountingInputIterator<int32_t> first(0);
   NonEmptyRow pred{rowptr};
   if (e == hipSuccess)
-    e = hipcub::DeviceSelect::If(nullptr, tmp_bytes, first, pl->row_list,
-                                 d_count, n, pred, st);
-  if (e == hipSuccess)
-    e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16);
-  if (e == hipSuccess)
-    e = hipcub::DeviceSelect::If(tmp, tmp_bytes, first, pl->row_list, d_count,
-                                 n, pred, st);
+    e = plan_cub(tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceSelect::If(t, tb, first, pl->row_list, d_count.get(), n,
+                                      pred, st);
+    });
   int32_t count = 0;
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&count, d_count, sizeof(int32_t), hipMemcpyDeviceToHost,
-                       st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(tmp);
-  (void)hipFree(d_count);
+    e = plan_fetch(&count, d_count.get(), 1, st);
+  tmp.reset();
+  d_count.reset();
   if (e != hipSuccess) {
-    (void)hipFree(pl->row_list);
-    pl->row_list = nullptr;
+    plan_drop(pl->row_list);
     return static_cast<int>(e);
   }
   pl->num_listed = count;
@@ -391,14 +383,10 @@ int spmv_build_row_list(spmv_hip_csr_plan* pl, const int32_t* rowptr)
 
 void spmv_free_lx(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->lx_lidx);
-  (void)hipFree(pl->lx_tab);
-  (void)hipFree(pl->lxw_rec);
-  (void)hipFree(pl->lx_code);
-  pl->lx_lidx = nullptr;
-  pl->lx_tab = nullptr;
-  pl->lxw_rec = nullptr;
-  pl->lx_code = nullptr;
+  plan_drop(pl->lx_lidx);
+  plan_drop(pl->lx_tab);
+  plan_drop(pl->lxw_rec);
+  plan_drop(pl->lx_code);
   pl->lx = pl->lx_staged = pl->lx_blocks = 0;
   pl->lxw = pl->lxw_max_cnt = pl->lxw_max_pieces = 0;
   pl->lx4 = pl->lx4_blocks = 0;
@@ -411,32 +399,29 @@ static int build_lx_codes(spmv_hip_csr_plan* pl, const int32_t* rowptr, int nrb,
                           hipStream_t st)
 {
   const size_t bytes = (size_t)lx_code_bytes(pl->nnz);
-  int32_t* d_stat = nullptr;
-  hipError_t e = hipMalloc(&pl->lx_code, bytes);
+  PlanScratch<int32_t> d_stat;
+  hipError_t e = spmv_plan_malloc(&pl->lx_code, bytes);
   if (e == hipSuccess)
-    e = hipMalloc(&d_stat, sizeof(int32_t));
+    e = d_stat.alloc(1);
   if (e == hipSuccess)
     e = hipMemsetAsync(pl->lx_code, 0, bytes, st);
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_stat, 0, sizeof(int32_t), st);
+    e = hipMemsetAsync(d_stat.get(), 0, sizeof(int32_t), st);
   int32_t coded = 0;
   if (e == hipSuccess) {
     int grid = pl->ctx->num_cus * 8;
     grid = grid > nrb ? nrb : grid;
     hipLaunchKernelGGL(lx4_encode_kernel, dim3(grid), dim3(kBlock), 0, st,
                        pl->num_rows, rowptr, pl->lx_lidx, pl->lxw_rec,
-                       reinterpret_cast<uint32_t*>(pl->lx_code), nrb, d_stat);
+                       reinterpret_cast<uint32_t*>(pl->lx_code), nrb, d_stat.get());
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&coded, d_stat, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_stat);
+    e = plan_fetch(&coded, d_stat.get(), 1, st);
+  d_stat.reset();
   if (e != hipSuccess || coded == 0) {
     (void)hipGetLastError();
-    (void)hipFree(pl->lx_code);
-    pl->lx_code = nullptr;
+    plan_drop(pl->lx_code);
     pl->lx4 = pl->lx4_blocks = 0;
     return e == hipSuccess || e == hipErrorOutOfMemory ? SPMV_HIP_OK
                                                        : static_cast<int>(e);
@@ -518,8 +503,7 @@ __global__ __launch_bounds__(kBlock) void lx32_convert_kernel(
 
 void spmv_lx32_free(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->lx_val32);
-  pl->lx_val32 = nullptr;
+  plan_drop(pl->lx_val32);
   pl->lx32_values0 = nullptr;
   pl->lx_v32 = 0;
 }
@@ -535,23 +519,21 @@ int spmv_lx32_bake(spmv_hip_csr_plan* pl, const double* values, bool may_alloc,
   const auto t0 = std::chrono::steady_clock::now();
   const int grid = spmv_grid_for(pl->ctx, (pl->nnz + 3) / 4, kBlock);
   // the check first: a matrix it refuses costs one pass and no memory
-  int32_t* d_flag = nullptr;
+  PlanScratch<int32_t> d_flag;
   int32_t h_flag = 1;
-  hipError_t e = hipMalloc(&d_flag, sizeof(int32_t));
+  hipError_t e = d_flag.alloc(1);
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_flag, 0, sizeof(int32_t), st);
+    e = hipMemsetAsync(d_flag.get(), 0, sizeof(int32_t), st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(lx32_check_kernel, dim3(grid), dim3(kBlock), 0, st, pl->nnz,
-                       values, d_flag);
+                       values, d_flag.get());
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&h_flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_flag);
+    e = plan_fetch(&h_flag, d_flag.get(), 1, st);
+  d_flag.reset();
   if (e == hipSuccess && !h_flag && !pl->lx_val32 && may_alloc) {
-    e = hipMalloc(&pl->lx_val32, sizeof(float) * (size_t)lx32_len(pl->nnz));
+    e = spmv_plan_malloc(&pl->lx_val32, sizeof(float) * (size_t)lx32_len(pl->nnz));
     if (e != hipSuccess)
       pl->lx_val32 = nullptr;
   }
@@ -583,8 +565,7 @@ int spmv_lx32_bake(spmv_hip_csr_plan* pl, const double* values, bool may_alloc,
 
 void spmv_free_xw(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->xw_rec);
-  pl->xw_rec = nullptr;
+  plan_drop(pl->xw_rec);
   pl->xw = pl->xw_staged = pl->xw_max_cnt = pl->xw_max_pieces = 0;
   xw_probe_free(pl);
 }
@@ -609,27 +590,22 @@ static int max_block_entries(const spmv_hip_csr_plan* pl, const int32_t* rowptr,
                              hipStream_t st, int32_t* out)
 {
   *out = INT32_MAX; // (on any failure: the large instantiation)
-  int32_t* d_max = nullptr;
-  void* tmp = nullptr;
-  size_t tb = 0;
+  PlanScratch<int32_t> d_max;
+  PlanScratch<void> tmp;
   hipcub::CountingInputIterator<int32_t> ids(0);
   hipcub::TransformInputIterator<int32_t, RowBlockEntries,
                                  hipcub::CountingInputIterator<int32_t>>
       cnt(ids, RowBlockEntries{rowptr, pl->num_rows});
-  hipError_t e = hipMalloc(&d_max, sizeof(int32_t));
+  hipError_t e = d_max.alloc(1);
   if (e == hipSuccess)
-    e = hipcub::DeviceReduce::Max(nullptr, tb, cnt, d_max, nrb, st);
-  if (e == hipSuccess)
-    e = hipMalloc(&tmp, tb ? tb : 16);
-  if (e == hipSuccess)
-    e = hipcub::DeviceReduce::Max(tmp, tb, cnt, d_max, nrb, st);
+    e = plan_cub(tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceReduce::Max(t, tb, cnt, d_max.get(), nrb, st);
+    });
   int32_t h = INT32_MAX;
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&h, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(tmp);
-  (void)hipFree(d_max);
+    e = plan_fetch(&h, d_max.get(), 1, st);
+  tmp.reset();
+  d_max.reset();
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return SPMV_HIP_OK; // (not fatal: *out stays at its default)
@@ -649,17 +625,17 @@ int spmv_build_xw(spmv_hip_csr_plan* pl, const int32_t* rowptr, const int32_t* c
   if (nrb == 0 || pl->nnz == 0 || pl->num_cols < kLxwAlign)
     return SPMV_HIP_OK;
   hipStream_t st = pl->ctx->stream;
-  int32_t* d_stat = nullptr;
-  hipError_t e = hipMalloc(&pl->xw_rec, sizeof(int32_t) * (size_t)nrb * kXwRec);
+  PlanScratch<int32_t> d_stat;
+  hipError_t e = spmv_plan_malloc(&pl->xw_rec, sizeof(int32_t) * (size_t)nrb * kXwRec);
   if (e == hipSuccess)
-    e = hipMalloc(&d_stat, 3 * sizeof(int32_t));
+    e = d_stat.alloc(3);
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_stat, 0, 3 * sizeof(int32_t), st);
+    e = hipMemsetAsync(d_stat.get(), 0, 3 * sizeof(int32_t), st);
   if (e == hipSuccess)
     e = hipMemsetAsync(pl->xw_rec, 0, sizeof(int32_t) * (size_t)nrb * kXwRec, st);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    (void)hipFree(d_stat);
+    d_stat.reset();
     spmv_free_xw(pl);
     return e == hipErrorOutOfMemory ? SPMV_HIP_OK : static_cast<int>(e);
   }
@@ -674,19 +650,17 @@ int spmv_build_xw(spmv_hip_csr_plan* pl, const int32_t* rowptr, const int32_t* c
     hipLaunchKernelGGL(lx_build_kernel<8>, dim3(grid), dim3(kBlock), 0, st,
                        pl->num_rows, pl->num_cols, rowptr, colind, nullptr,
                        nullptr, nrb, end_bit, kLxwAlign, kLxwPiece,
-                       kLxwMaxPieces * kLxwPiece, pl->xw_rec, d_stat, 1);
+                       kLxwMaxPieces * kLxwPiece, pl->xw_rec, d_stat.get(), 1);
   else
     hipLaunchKernelGGL(lx_build_kernel<16>, dim3(grid), dim3(kBlock), 0, st,
                        pl->num_rows, pl->num_cols, rowptr, colind, nullptr,
                        nullptr, nrb, end_bit, kLxwAlign, kLxwPiece,
-                       kLxwMaxPieces * kLxwPiece, pl->xw_rec, d_stat, 1);
+                       kLxwMaxPieces * kLxwPiece, pl->xw_rec, d_stat.get(), 1);
   e = hipGetLastError();
   int32_t h_stat[3] = {0, 0, 0};
   if (e == hipSuccess)
-    e = hipMemcpyAsync(h_stat, d_stat, sizeof(h_stat), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_stat);
+    e = plan_fetch(h_stat, d_stat.get(), 3, st);
+  d_stat.reset();
   if (e != hipSuccess) {
     spmv_free_xw(pl);
     return static_cast<int>(e);
@@ -748,9 +722,9 @@ int spmv_build_lx(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   if (nrb == 0 || pl->nnz == 0)
     return SPMV_HIP_OK;
   hipStream_t st = pl->ctx->stream;
-  hipError_t e = hipMalloc(&pl->lx_lidx, sizeof(uint16_t) * (pl->nnz + 8));
+  hipError_t e = spmv_plan_malloc(&pl->lx_lidx, sizeof(uint16_t) * (pl->nnz + 8));
   if (e == hipSuccess)
-    e = hipMalloc(&pl->lx_tab, sizeof(int32_t) * (size_t)nrb * kLxRec);
+    e = spmv_plan_malloc(&pl->lx_tab, sizeof(int32_t) * (size_t)nrb * kLxRec);
   if (e == hipSuccess)
     e = hipMemsetAsync(pl->lx_lidx, 0, sizeof(uint16_t) * (pl->nnz + 8), st);
   if (e == hipSuccess)
@@ -762,15 +736,15 @@ int spmv_build_lx(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   // The LDS-DMA kernel's layout (windows padded to whole DMA pieces) when the
   // context asks for it and the matrix has at least one aligned chunk of x
   const bool dma = pl->ctx->lx_dma && pl->num_cols >= kLxwAlign;
-  int32_t* d_stat = nullptr;
+  PlanScratch<int32_t> d_stat;
   if (dma) {
-    e = hipMalloc(&pl->lxw_rec, sizeof(int32_t) * (size_t)nrb * kLxwRec);
+    e = spmv_plan_malloc(&pl->lxw_rec, sizeof(int32_t) * (size_t)nrb * kLxwRec);
     if (e == hipSuccess)
-      e = hipMalloc(&d_stat, 2 * sizeof(int32_t));
+      e = d_stat.alloc(2);
     if (e == hipSuccess)
-      e = hipMemsetAsync(d_stat, 0, 2 * sizeof(int32_t), st);
+      e = hipMemsetAsync(d_stat.get(), 0, 2 * sizeof(int32_t), st);
     if (e != hipSuccess) {
-      (void)hipFree(d_stat);
+      d_stat.reset();
       spmv_free_lx(pl);
       return e == hipErrorOutOfMemory ? SPMV_HIP_OK : static_cast<int>(e);
     }
@@ -789,42 +763,37 @@ int spmv_build_lx(spmv_hip_csr_plan* pl, const int32_t* rowptr,
     hipLaunchKernelGGL(lx_build_kernel<8>, dim3(grid), dim3(kBlock), 0, st,
                        pl->num_rows, pl->num_cols, rowptr, colind, pl->lx_lidx,
                        pl->lx_tab, nrb, end_bit, align, pad, cap, pl->lxw_rec,
-                       d_stat, 0);
+                       d_stat.get(), 0);
   else
     hipLaunchKernelGGL(lx_build_kernel<16>, dim3(grid), dim3(kBlock), 0, st,
                        pl->num_rows, pl->num_cols, rowptr, colind, pl->lx_lidx,
                        pl->lx_tab, nrb, end_bit, align, pad, cap, pl->lxw_rec,
-                       d_stat, 0);
+                       d_stat.get(), 0);
   e = hipGetLastError();
   int32_t h_stat[2] = {0, 0};
   if (dma && e == hipSuccess)
-    e = hipMemcpyAsync(h_stat, d_stat, sizeof(h_stat), hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(h_stat, d_stat.get(), sizeof(h_stat), hipMemcpyDeviceToHost,
+                       st);
   // how many row blocks are staged?
-  int32_t* d_count = nullptr;
-  void* tmp = nullptr;
-  size_t tmp_bytes = 0;
+  PlanScratch<int32_t> d_count;
+  PlanScratch<void> tmp;
   int32_t staged = 0;
   if (e == hipSuccess)
-    e = hipMalloc(&d_count, sizeof(int32_t));
+    e = d_count.alloc(1);
   // the window count is the first int of every record
   hipcub::CountingInputIterator<int32_t> block_ids(0);
   hipcub::TransformInputIterator<int32_t, IsStagedRecord,
                                  hipcub::CountingInputIterator<int32_t>>
       flags(block_ids, IsStagedRecord{pl->lx_tab});
   if (e == hipSuccess)
-    e = hipcub::DeviceReduce::Sum(nullptr, tmp_bytes, flags, d_count, nrb, st);
+    e = plan_cub(tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceReduce::Sum(t, tb, flags, d_count.get(), nrb, st);
+    });
   if (e == hipSuccess)
-    e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16);
-  if (e == hipSuccess)
-    e = hipcub::DeviceReduce::Sum(tmp, tmp_bytes, flags, d_count, nrb, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(&staged, d_count, sizeof(int32_t), hipMemcpyDeviceToHost,
-                       st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(tmp);
-  (void)hipFree(d_count);
-  (void)hipFree(d_stat);
+    e = plan_fetch(&staged, d_count.get(), 1, st);
+  tmp.reset();
+  d_count.reset();
+  d_stat.reset();
   if (e != hipSuccess) {
     spmv_free_lx(pl);
     return static_cast<int>(e);
@@ -897,8 +866,7 @@ int spmv_walk_grid(const spmv_hip_csr_plan* pl)
 
 void spmv_zwalk_free(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->zw_table);
-  pl->zw_table = nullptr;
+  plan_drop(pl->zw_table);
   pl->zw_slots = pl->zw_grid = pl->zw_segments = 0;
   pl->zwalk = 0; // zw_d2 stays: a knob can rebuild
 }
@@ -984,12 +952,11 @@ int spmv_zwalk_table_device(const spmv_hip_csr_plan* pl, int64_t rows,
   if (!zwalk_table((int32_t)rows, d2, grid, segments, force, &table, segs))
     return SPMV_HIP_OK;
   SPMV_CHECK_HIP(hipSetDevice(pl->ctx->device));
-  SPMV_CHECK_HIP(hipMalloc(d_table, sizeof(int32_t) * table.size()));
+  SPMV_CHECK_HIP(spmv_plan_malloc(d_table, sizeof(int32_t) * table.size()));
   hipError_t e = hipMemcpy(*d_table, table.data(), sizeof(int32_t) * table.size(),
                            hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    (void)hipFree(*d_table);
-    *d_table = nullptr;
+    plan_drop(*d_table);
     return static_cast<int>(e);
   }
   *slots = (int)table.size();
@@ -1010,7 +977,7 @@ int spmv_zwalk_order_build(spmv_hip_csr_plan* pl, int64_t d2, int grid,
   int segs = 0;
   if (!zwalk_table(pl->num_rows, d2, grid, segments, force, &table, &segs))
     return SPMV_HIP_OK;
-  SPMV_CHECK_HIP(hipMalloc(&pl->zw_table, sizeof(int32_t) * table.size()));
+  SPMV_CHECK_HIP(spmv_plan_malloc(&pl->zw_table, sizeof(int32_t) * table.size()));
   hipError_t e = hipMemcpy(pl->zw_table, table.data(),
                            sizeof(int32_t) * table.size(),
                            hipMemcpyHostToDevice);

@@ -15,9 +15,9 @@
 #include <utility>
 #include <vector>
 
-#include "plan_malloc.h" // (last: hipMalloc / hipFree below are timed)
+#include "plan_scratch.h"
 
-thread_local int64_t spmv_plan_mem_ns = 0; // (plan_malloc.h)
+thread_local int64_t spmv_plan_mem_ns = 0; // (plan_scratch.h)
 
 namespace
 {
@@ -264,17 +264,16 @@ int spmv_hip_csr_plan_destroy(spmv_hip_csr_plan* plan)
     spmv_sjds_free(plan->sjt);
     delete plan->sjt;
     plan->sjt = nullptr;
-    (void)hipFree(plan->sjv_ptr);
-    (void)hipFree(plan->sjv_col);
-    (void)hipFree(plan->sjv_map);
-    plan->sjv_ptr = plan->sjv_col = plan->sjv_map = nullptr;
+    plan_drop(plan->sjv_ptr);
+    plan_drop(plan->sjv_col);
+    plan_drop(plan->sjv_map);
   }
   if (plan
       && (plan->row_list || plan->lx_lidx || plan->lat_tab || plan->t_ptr
           || plan->slat_mask || plan->zw_table || plan->wdia_val
           || plan->sdia_val || plan->sj_lenperm || plan->xw_rec)) {
     (void)hipSetDevice(plan->ctx->device);
-    (void)hipFree(plan->row_list);
+    plan_drop(plan->row_list);
     spmv_free_lx(plan);
     spmv_free_xw(plan);
     spmv_lat_free(plan);
@@ -466,11 +465,9 @@ int spmv_hip_csr_plan_release_matrix(spmv_hip_csr_plan* plan, int mask)
     // the row pointer and the diagonal, 1.75 times its own CSR bytes
     SPMV_CHECK_HIP(hipSetDevice(plan->ctx->device));
     SPMV_CHECK_HIP(hipDeviceSynchronize());
-    (void)hipFree(plan->t_pos);
-    (void)hipFree(plan->t_row);
-    plan->t_pos = plan->t_row = nullptr;
-    (void)hipFree(plan->sjv_map);
-    plan->sjv_map = nullptr;
+    plan_drop(plan->t_pos);
+    plan_drop(plan->t_row);
+    plan_drop(plan->sjv_map);
   }
   return SPMV_HIP_OK;
 }

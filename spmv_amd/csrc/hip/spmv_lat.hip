@@ -59,7 +59,7 @@
 
 #include <new>
 
-#include "plan_malloc.h" // (last: hipMalloc / hipFree below are timed)
+#include "plan_scratch.h"
 
 namespace
 {
@@ -550,10 +550,8 @@ int spmv_lat_grid(const spmv_hip_csr_plan* pl)
 
 void spmv_lat_free(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->lat_tab);
-  (void)hipFree(pl->lat_mask);
-  pl->lat_tab = nullptr;
-  pl->lat_mask = nullptr;
+  plan_drop(pl->lat_tab);
+  plan_drop(pl->lat_mask);
   pl->lat = 0;
 }
 
@@ -569,28 +567,26 @@ int spmv_lat_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   if (nrb == 0 || pl->nnz == 0)
     return SPMV_HIP_OK;
   hipStream_t st = pl->ctx->stream;
-  int32_t* d_ok = nullptr;
-  hipError_t e = hipMalloc(&pl->lat_tab, sizeof(int32_t) * (size_t)nrb * kLatRec);
+  PlanScratch<int32_t> d_ok;
+  hipError_t e = spmv_plan_malloc(&pl->lat_tab, sizeof(int32_t) * (size_t)nrb * kLatRec);
   if (e == hipSuccess)
-    e = hipMalloc(&pl->lat_mask, (size_t)pl->num_rows);
+    e = spmv_plan_malloc(&pl->lat_mask, (size_t)pl->num_rows);
   if (e == hipSuccess)
-    e = hipMalloc(&d_ok, sizeof(int32_t));
+    e = d_ok.alloc(1);
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_ok, 0, sizeof(int32_t), st);
+    e = hipMemsetAsync(d_ok.get(), 0, sizeof(int32_t), st);
   int32_t ok = 0;
   if (e == hipSuccess) {
     int grid = pl->ctx->num_cus * 8;
     grid = grid > nrb ? nrb : grid;
     hipLaunchKernelGGL(lat_build_kernel, dim3(grid), dim3(kBlock), 0, st,
                        pl->num_rows, rowptr, colind, pl->lat_tab, pl->lat_mask,
-                       nrb, d_ok);
+                       nrb, d_ok.get());
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&ok, d_ok, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_ok);
+    e = plan_fetch(&ok, d_ok.get(), 1, st);
+  d_ok.reset();
   if (e != hipSuccess) {
     spmv_lat_free(pl);
     return e == hipErrorOutOfMemory ? SPMV_HIP_OK : static_cast<int>(e);

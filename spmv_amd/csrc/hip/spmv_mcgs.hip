@@ -29,7 +29,7 @@
 
 #include <vector>
 
-#include "plan_malloc.h"
+#include "plan_scratch.h"
 
 struct McgsPartDev {
   int32_t* slice_pos0 = nullptr;
@@ -129,7 +129,7 @@ int upload(const T* host, size_t count, T** dev, int64_t* bytes)
   if (count == 0)
     return SPMV_HIP_OK;
   SPMV_REQUIRE(host != nullptr);
-  SPMV_CHECK_HIP(hipMalloc(dev, count * sizeof(T)));
+  SPMV_CHECK_HIP(spmv_plan_malloc(dev, count * sizeof(T)));
   *bytes += (int64_t)(count * sizeof(T));
   SPMV_CHECK_HIP(hipMemcpy(*dev, host, count * sizeof(T), hipMemcpyHostToDevice));
   return SPMV_HIP_OK;
@@ -216,7 +216,7 @@ void free_part(McgsPartDev* d)
                   (void*)d->col, (void*)d->val, (void*)d->long_pos,
                   (void*)d->long_ptr, (void*)d->long_col, (void*)d->long_val})
     if (q)
-      (void)hipFree(q);
+      (void)spmv_plan_free(q);
 }
 
 template <bool FORWARD>
@@ -283,10 +283,8 @@ int spmv_hip_mcgs_plan_destroy(spmv_hip_mcgs_plan* plan)
   (void)hipSetDevice(plan->ctx->device);
   free_part(&plan->before);
   free_part(&plan->after);
-  if (plan->perm)
-    (void)hipFree(plan->perm);
-  if (plan->dinv)
-    (void)hipFree(plan->dinv);
+  plan_drop(plan->perm);
+  plan_drop(plan->dinv);
   delete plan;
   return SPMV_HIP_OK;
 }

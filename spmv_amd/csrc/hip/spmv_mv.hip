@@ -43,7 +43,7 @@
 
 #include <cstring>
 
-#include "plan_malloc.h"
+#include "plan_scratch.h"
 
 namespace
 {
@@ -375,12 +375,11 @@ int mv_scratch(spmv_hip_csr_plan* pl, size_t bytes, hipStream_t st)
     // an earlier launch, on this stream or another, may still read it
     // (this stream's launches; hipFree itself waits for the rest of the device)
     SPMV_CHECK_HIP(hipStreamSynchronize(st));
-    (void)hipFree(pl->mv_scratch);
-    pl->mv_scratch = nullptr;
+    plan_drop(pl->mv_scratch);
     pl->mv_bytes = 0;
   }
   void* p = nullptr;
-  const hipError_t e = hipMalloc(&p, bytes);
+  const hipError_t e = spmv_plan_malloc(&p, bytes);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return static_cast<int>(e);
@@ -545,8 +544,7 @@ void spmv_mv_free(spmv_hip_csr_plan* pl)
   if (!pl->mv_scratch)
     return;
   (void)hipSetDevice(pl->ctx->device);
-  (void)hipFree(pl->mv_scratch);
-  pl->mv_scratch = nullptr;
+  plan_drop(pl->mv_scratch);
   pl->mv_bytes = 0;
 }
 

@@ -9,7 +9,7 @@
 #include <chrono>
 #include <new>
 
-#include "plan_malloc.h" // (last: hipMalloc / hipFree below are timed)
+#include "plan_scratch.h"
 
 namespace
 {
@@ -558,94 +558,72 @@ int spmv_sj_build_long_list(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   hipcub::TransformInputIterator<int, SjLongCount,
                                  hipcub::CountingInputIterator<int32_t>>
       ones(first, SjLongCount{rowptr, thr, pl->nnz});
-  int32_t* d_count = nullptr;
-  void* tmp = nullptr;
-  size_t tb = 0, tb2 = 0;
+  PlanScratch<int32_t> d_count;
+  PlanScratch<void> tmp;
   int32_t count = 0;
-  hipError_t e = hipMalloc(&d_count, sizeof(int32_t));
+  hipError_t e = d_count.alloc(1);
   if (e == hipSuccess)
-    e = hipcub::DeviceReduce::Sum(nullptr, tb, ones, d_count, n, st);
+    e = plan_cub(tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceReduce::Sum(t, tb, ones, d_count.get(), n, st);
+    });
   if (e == hipSuccess)
-    e = hipMalloc(&tmp, tb ? tb : 16);
-  if (e == hipSuccess)
-    e = hipcub::DeviceReduce::Sum(tmp, tb, ones, d_count, n, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(&count, d_count, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(tmp);
-  tmp = nullptr;
+    e = plan_fetch(&count, d_count.get(), 1, st);
+  tmp.reset();
   if (e == hipSuccess && count > 0) {
-    e = hipMalloc(&pl->sj_long_rows, sizeof(int32_t) * (size_t)count);
+    e = spmv_plan_malloc(&pl->sj_long_rows, sizeof(int32_t) * (size_t)count);
     SjIsLong pred{rowptr, thr, pl->nnz};
     if (e == hipSuccess)
-      e = hipcub::DeviceSelect::If(nullptr, tb2, first, pl->sj_long_rows, d_count, n,
-                                   pred, st);
-    if (e == hipSuccess)
-      e = hipMalloc(&tmp, tb2 ? tb2 : 16);
-    if (e == hipSuccess)
-      e = hipcub::DeviceSelect::If(tmp, tb2, first, pl->sj_long_rows, d_count, n,
-                                   pred, st);
+      e = plan_cub(tmp, [&](void* t, size_t& tb) {
+        return hipcub::DeviceSelect::If(t, tb, first, pl->sj_long_rows, d_count.get(),
+                                        n, pred, st);
+      });
     if (e == hipSuccess)
       e = hipStreamSynchronize(st);
     // ... inside runs of 64 the longest first, so that the eight rows a wave
     // takes together end together and still are neighbours
-    uint64_t *d_key = nullptr, *d_key2 = nullptr;
-    int32_t* d_rows2 = nullptr;
-    void* tmp2 = nullptr;
-    size_t tb3 = 0;
+    PlanScratch<uint64_t> d_key, d_key2;
+    PlanScratch<int32_t> d_rows2;
+    PlanScratch<void> tmp2;
     if (e == hipSuccess)
-      e = hipMalloc(&d_key, sizeof(uint64_t) * (size_t)count);
+      e = d_key.alloc((size_t)count);
     if (e == hipSuccess)
-      e = hipMalloc(&d_key2, sizeof(uint64_t) * (size_t)count);
+      e = d_key2.alloc((size_t)count);
     if (e == hipSuccess)
-      e = hipMalloc(&d_rows2, sizeof(int32_t) * (size_t)count);
+      e = d_rows2.alloc((size_t)count);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(sj_long_key_kernel,
                          dim3(spmv_grid_for(pl->ctx, count, kBlock)), dim3(kBlock), 0,
-                         st, count, rowptr, pl->sj_long_rows, d_key);
+                         st, count, rowptr, pl->sj_long_rows, d_key.get());
       e = hipGetLastError();
     }
     if (e == hipSuccess)
-      e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb3, d_key, d_key2,
-                                             pl->sj_long_rows, d_rows2, count, 0, 64,
-                                             st);
+      e = plan_cub(tmp2, [&](void* t, size_t& tb) {
+        return hipcub::DeviceRadixSort::SortPairs(t, tb, d_key.get(), d_key2.get(),
+                                                  pl->sj_long_rows, d_rows2.get(),
+                                                  count, 0, 64, st);
+      });
     if (e == hipSuccess)
-      e = hipMalloc(&tmp2, tb3 ? tb3 : 16);
-    if (e == hipSuccess)
-      e = hipcub::DeviceRadixSort::SortPairs(tmp2, tb3, d_key, d_key2,
-                                             pl->sj_long_rows, d_rows2, count, 0, 64,
-                                             st);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(pl->sj_long_rows, d_rows2, sizeof(int32_t) * (size_t)count,
-                         hipMemcpyDeviceToDevice, st);
+      e = hipMemcpyAsync(pl->sj_long_rows, d_rows2.get(),
+                         sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToDevice, st);
     // ascending columns in every long row?  (d_count is free to be the flag)
     int32_t h_bad = 1;
     if (e == hipSuccess)
-      e = hipMemsetAsync(d_count, 0, sizeof(int32_t), st);
+      e = hipMemsetAsync(d_count.get(), 0, sizeof(int32_t), st);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(sj_long_sorted_kernel,
                          dim3(spmv_grid_for(pl->ctx, count, kBlock / 64)),
                          dim3(kBlock), 0, st, count, rowptr, colind,
-                         pl->sj_long_rows, d_count);
+                         pl->sj_long_rows, d_count.get());
       e = hipGetLastError();
     }
     if (e == hipSuccess)
-      e = hipMemcpyAsync(&h_bad, d_count, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-      e = hipStreamSynchronize(st);
+      e = plan_fetch(&h_bad, d_count.get(), 1, st);
     pl->sj_long_sorted = h_bad ? 0 : 1;
-    (void)hipFree(d_key);
-    (void)hipFree(d_key2);
-    (void)hipFree(d_rows2);
-    (void)hipFree(tmp2);
   }
-  (void)hipFree(tmp);
-  (void)hipFree(d_count);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? SPMV_HIP_ENOMEM : static_cast<int>(e);
-  }
+  tmp.reset(); // (freed before the sticky error is cleared, as ever)
+  d_count.reset();
+  if (e != hipSuccess)
+    return plan_fail(e);
   pl->sj_nlong = count;
   return SPMV_HIP_OK;
 }
@@ -777,16 +755,12 @@ __global__ __launch_bounds__(kBlock) void sj_lt_codes_kernel(
 
 void spmv_sj_lt_free(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->sj_lt_codes);
-  (void)hipFree(pl->sj_lt_coff);
-  pl->sj_lt_codes = nullptr;
-  pl->sj_lt_coff = nullptr;
-  (void)hipFree(pl->sj_lt_cmin);
-  (void)hipFree(pl->sj_lt_np);
-  (void)hipFree(pl->sj_lt_off);
-  (void)hipFree(pl->sj_lt_tab);
-  pl->sj_lt_cmin = pl->sj_lt_np = pl->sj_lt_tab = nullptr;
-  pl->sj_lt_off = nullptr;
+  plan_drop(pl->sj_lt_codes);
+  plan_drop(pl->sj_lt_coff);
+  plan_drop(pl->sj_lt_cmin);
+  plan_drop(pl->sj_lt_np);
+  plan_drop(pl->sj_lt_off);
+  plan_drop(pl->sj_lt_tab);
   pl->sj_lt_entries = 0;
   pl->sj_lt_nsg = 0;
 }
@@ -799,14 +773,13 @@ int spmv_sj_build_long_table(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   if (nlong <= 0 || !pl->sj_long_sorted)
     return SPMV_HIP_OK;
   const int nsg = (nlong + kSjLtRun - 1) / kSjLtRun;
-  void* tmp = nullptr;
-  size_t tb = 0;
+  PlanScratch<void> tmp;
   int64_t total = 0;
-  hipError_t e = hipMalloc(&pl->sj_lt_cmin, sizeof(int32_t) * (size_t)nsg);
+  hipError_t e = spmv_plan_malloc(&pl->sj_lt_cmin, sizeof(int32_t) * (size_t)nsg);
   if (e == hipSuccess)
-    e = hipMalloc(&pl->sj_lt_np, sizeof(int32_t) * (size_t)nsg);
+    e = spmv_plan_malloc(&pl->sj_lt_np, sizeof(int32_t) * (size_t)nsg);
   if (e == hipSuccess)
-    e = hipMalloc(&pl->sj_lt_off, sizeof(int64_t) * (size_t)(nsg + 1));
+    e = spmv_plan_malloc(&pl->sj_lt_off, sizeof(int64_t) * (size_t)(nsg + 1));
   if (e == hipSuccess) {
     hipLaunchKernelGGL(sj_lt_span_kernel, dim3(spmv_grid_for(pl->ctx, nsg, kBlock / 64)),
                        dim3(kBlock), 0, st, nlong, nsg, rowptr, colind,
@@ -814,21 +787,15 @@ int spmv_sj_build_long_table(spmv_hip_csr_plan* pl, const int32_t* rowptr,
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, pl->sj_lt_off, pl->sj_lt_off,
-                                         nsg + 1, st);
+    e = plan_cub(tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceScan::ExclusiveSum(t, tb, pl->sj_lt_off, pl->sj_lt_off,
+                                              nsg + 1, st);
+    });
   if (e == hipSuccess)
-    e = hipMalloc(&tmp, tb ? tb : 16);
+    e = plan_fetch(&total, pl->sj_lt_off + nsg, 1, st);
+  tmp.reset();
   if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, pl->sj_lt_off, pl->sj_lt_off,
-                                         nsg + 1, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(&total, pl->sj_lt_off + nsg, sizeof(int64_t),
-                       hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(tmp);
-  if (e == hipSuccess)
-    e = hipMalloc(&pl->sj_lt_tab, sizeof(int32_t) * (size_t)(total > 0 ? total : 1));
+    e = spmv_plan_malloc(&pl->sj_lt_tab, sizeof(int32_t) * (size_t)(total > 0 ? total : 1));
   if (e == hipSuccess && total > 0) {
     hipLaunchKernelGGL(sj_lt_fill_kernel, dim3(spmv_grid_for(pl->ctx, nsg, 1)),
                        dim3(kBlock), 0, st, nlong, nsg, rowptr, colind,
@@ -841,9 +808,7 @@ int spmv_sj_build_long_table(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   // the rows' columns as 16-bit panel positions (kSjLtCodes)
   int64_t ncodes = 0;
   if (e == hipSuccess && kSjLtCodes) {
-    void* tmp2 = nullptr;
-    size_t tb2 = 0;
-    e = hipMalloc(&pl->sj_lt_coff, sizeof(int64_t) * ((size_t)nlong + 1));
+    e = spmv_plan_malloc(&pl->sj_lt_coff, sizeof(int64_t) * ((size_t)nlong + 1));
     if (e == hipSuccess) {
       hipLaunchKernelGGL(sj_lt_len_kernel, dim3(spmv_grid_for(pl->ctx, nlong + 1, kBlock)),
                          dim3(kBlock), 0, st, nlong, rowptr, pl->sj_long_rows,
@@ -851,23 +816,17 @@ int spmv_sj_build_long_table(spmv_hip_csr_plan* pl, const int32_t* rowptr,
       e = hipGetLastError();
     }
     if (e == hipSuccess)
-      e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, pl->sj_lt_coff, pl->sj_lt_coff,
-                                           nlong + 1, st);
+      e = plan_cub(tmp, [&](void* t, size_t& tb) {
+        return hipcub::DeviceScan::ExclusiveSum(t, tb, pl->sj_lt_coff, pl->sj_lt_coff,
+                                                nlong + 1, st);
+      });
     if (e == hipSuccess)
-      e = hipMalloc(&tmp2, tb2 ? tb2 : 16);
-    if (e == hipSuccess)
-      e = hipcub::DeviceScan::ExclusiveSum(tmp2, tb2, pl->sj_lt_coff, pl->sj_lt_coff,
-                                           nlong + 1, st);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(&ncodes, pl->sj_lt_coff + nlong, sizeof(int64_t),
-                         hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-      e = hipStreamSynchronize(st);
-    (void)hipFree(tmp2);
+      e = plan_fetch(&ncodes, pl->sj_lt_coff + nlong, 1, st);
+    tmp.reset();
     // (loads run up to two trips past a row's end: slack behind the last row)
     const size_t nalloc = (size_t)ncodes + 4 * kSjLtTrip * (kSjLtDepth + 1);
     if (e == hipSuccess)
-      e = hipMalloc(&pl->sj_lt_codes, sizeof(uint16_t) * nalloc);
+      e = spmv_plan_malloc(&pl->sj_lt_codes, sizeof(uint16_t) * nalloc);
     if (e == hipSuccess)
       e = hipMemsetAsync(pl->sj_lt_codes, 0, sizeof(uint16_t) * nalloc, st);
     if (e == hipSuccess) {
@@ -900,8 +859,7 @@ int sj_bake(spmv_hip_csr_plan* pl, const T* values, const int32_t* map, hipStrea
   SPMV_CHECK_HIP(hipSetDevice(pl->ctx->device));
   if (values == nullptr) { // drop the copy
     SPMV_CHECK_HIP(hipDeviceSynchronize());
-    (void)hipFree(pl->sj_val);
-    pl->sj_val = nullptr;
+    plan_drop(pl->sj_val);
     pl->sj_values0 = nullptr;
     pl->sj_elem = 0;
     return SPMV_HIP_OK;
@@ -911,19 +869,17 @@ int sj_bake(spmv_hip_csr_plan* pl, const T* values, const int32_t* map, hipStrea
   const auto t_begin = std::chrono::steady_clock::now();
   if (pl->sj_val && pl->sj_elem != (int)sizeof(T)) {
     SPMV_CHECK_HIP(hipDeviceSynchronize());
-    (void)hipFree(pl->sj_val);
-    pl->sj_val = nullptr;
+    plan_drop(pl->sj_val);
   }
   if (!pl->sj_val) {
     const size_t entries = (size_t)(pl->sj_units + kSjSlack) * pl->sj_unit;
-    hipError_t e = hipMalloc(&pl->sj_val, sizeof(T) * entries);
+    hipError_t e = spmv_plan_malloc(&pl->sj_val, sizeof(T) * entries);
     if (e == hipSuccess) // the slack is read (never used): keep it finite
       e = hipMemsetAsync(static_cast<T*>(pl->sj_val)
                              + (size_t)pl->sj_units * pl->sj_unit,
                          0, sizeof(T) * (size_t)kSjSlack * pl->sj_unit, st);
     if (e != hipSuccess) {
-      (void)hipFree(pl->sj_val);
-      pl->sj_val = nullptr;
+      plan_drop(pl->sj_val);
       (void)hipGetLastError();
       return e == hipErrorOutOfMemory ? SPMV_HIP_ENOTSUP : static_cast<int>(e);
     }
@@ -981,45 +937,32 @@ int spmv_sjds_long_entries(spmv_hip_ctx* ctx, int32_t num_rows, int64_t nnz,
   hipcub::TransformInputIterator<int64_t, SjLongEntries,
                                  hipcub::CountingInputIterator<int32_t>>
       it(first, SjLongEntries{rowptr, thr, nnz});
-  int64_t* d_sum = nullptr;
-  void* tmp = nullptr;
-  size_t tb = 0;
-  hipError_t e = hipMalloc(&d_sum, sizeof(int64_t));
+  PlanScratch<int64_t> d_sum;
+  PlanScratch<void> tmp;
+  hipError_t e = d_sum.alloc(1);
   if (e == hipSuccess)
-    e = hipcub::DeviceReduce::Sum(nullptr, tb, it, d_sum, num_rows, st);
+    e = plan_cub(tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceReduce::Sum(t, tb, it, d_sum.get(), num_rows, st);
+    });
   if (e == hipSuccess)
-    e = hipMalloc(&tmp, tb ? tb : 16);
-  if (e == hipSuccess)
-    e = hipcub::DeviceReduce::Sum(tmp, tb, it, d_sum, num_rows, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(entries, d_sum, sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(tmp);
-  (void)hipFree(d_sum);
+    e = plan_fetch(entries, d_sum.get(), 1, st);
   (void)ctx;
   return e == hipSuccess ? SPMV_HIP_OK : static_cast<int>(e);
 }
 
 void spmv_sjds_free(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->sj_lenperm);
-  (void)hipFree(pl->sj_blk);
-  (void)hipFree(pl->sj_chunks);
-  (void)hipFree(pl->sj_codes);
-  (void)hipFree(pl->sj_val);
-  (void)hipFree(pl->sj_val32);
-  pl->sj_val32 = nullptr;
+  plan_drop(pl->sj_lenperm);
+  plan_drop(pl->sj_blk);
+  plan_drop(pl->sj_chunks);
+  plan_drop(pl->sj_codes);
+  plan_drop(pl->sj_val);
+  plan_drop(pl->sj_val32);
   pl->sj32_values0 = nullptr;
-  (void)hipFree(pl->sj_long_rows);
-  (void)hipFree(pl->sj_ubase);
+  plan_drop(pl->sj_long_rows);
+  plan_drop(pl->sj_ubase);
   spmv_sj_lt_free(pl);
-  pl->sj_ubase = nullptr;
-  pl->sj_long_rows = nullptr;
   pl->sj_nlong = 0;
-  pl->sj_lenperm = pl->sj_blk = pl->sj_chunks = nullptr;
-  pl->sj_codes = nullptr;
-  pl->sj_val = nullptr;
   pl->sj_values0 = nullptr;
   pl->sj = pl->sj_elem = 0;
 }
@@ -1062,23 +1005,15 @@ int spmv_sjds_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   int E = unit_force ? unit_force : (avg >= 4.0 ? 2 : 1);
   const int nblk4 = (n + 255) / 256;
   const int64_t nsl = ((int64_t)n + 63) / 64;
-  int32_t* d_k = nullptr;
-  int32_t* d_far3[3] = {nullptr, nullptr, nullptr}; // per candidate: the fill
-                                                    // pass reads the winner's
-  int64_t* d_stats = nullptr;
-  hipError_t e = hipMalloc(&d_k, sizeof(int32_t) * (size_t)nblk4);
+  PlanScratch<int32_t> d_k;
+  PlanScratch<int32_t> d_far3[3]; // per candidate: the fill pass reads the winner's
+  PlanScratch<int64_t> d_stats;
+  hipError_t e = d_k.alloc((size_t)nblk4);
   for (int ci = 0; ci < 3 && e == hipSuccess; ++ci)
-    e = hipMalloc(&d_far3[ci], sizeof(int32_t) * (size_t)nblk4);
+    e = d_far3[ci].alloc((size_t)nblk4);
   if (e == hipSuccess)
-    e = hipMalloc(&d_stats, sizeof(int64_t) * 4);
-  auto cleanup = [&]() {
-    (void)hipFree(d_k);
-    for (int32_t* p : d_far3)
-      (void)hipFree(p);
-    (void)hipFree(d_stats);
-  };
+    e = d_stats.alloc(4);
   if (e != hipSuccess) {
-    cleanup();
     (void)hipGetLastError();
     return e == hipErrorOutOfMemory ? SPMV_HIP_OK : static_cast<int>(e);
   }
@@ -1093,13 +1028,14 @@ int spmv_sjds_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   double best_cost = 0.0;
   SjStats best_st;
   auto count = [&](int wpb, int ci, SjStats* s) {
-    return wpb == 4 ? sj_count<256>(pl, rowptr, colind, kcap, thr, d_k, d_far3[ci],
-                                    d_stats, s, st)
+    int32_t* far = d_far3[ci].get();
+    return wpb == 4 ? sj_count<256>(pl, rowptr, colind, kcap, thr, d_k.get(), far,
+                                    d_stats.get(), s, st)
            : wpb == 8
-               ? sj_count<512>(pl, rowptr, colind, kcap, thr, d_k, d_far3[ci], d_stats,
-                               s, st)
-               : sj_count<1024>(pl, rowptr, colind, kcap, thr, d_k, d_far3[ci],
-                                d_stats, s, st);
+               ? sj_count<512>(pl, rowptr, colind, kcap, thr, d_k.get(), far,
+                               d_stats.get(), s, st)
+               : sj_count<1024>(pl, rowptr, colind, kcap, thr, d_k.get(), far,
+                                d_stats.get(), s, st);
   };
   // (the largest block first: when it stages every entry -- no far ones -- and
   // leaves the CU its 16 waves, the smaller blocks can only stage more bytes
@@ -1115,10 +1051,8 @@ int spmv_sjds_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
       continue;
     SjStats s;
     const int rc = count(wpb, ci, &s);
-    if (rc != SPMV_HIP_OK) {
-      cleanup();
+    if (rc != SPMV_HIP_OK)
       return rc;
-    }
     const int64_t lds = s.maxk * kSjChunk * 8 + 128;
     const int waves = sj_wgs_per_cu(wpb, lds) * wpb;
     double cost = (s.far > 0 ? 12.0 : 10.0)
@@ -1139,17 +1073,13 @@ int spmv_sjds_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
     best = wpb_force ? wpb_force : (no_long ? 8 : 4);
     best_ci = best == 4 ? 0 : best == 8 ? 1 : 2;
     const int rc = count(best, best_ci, &best_st);
-    if (rc != SPMV_HIP_OK) {
-      cleanup();
+    if (rc != SPMV_HIP_OK)
       return rc;
-    }
   }
-  int32_t* d_far = d_far3[best_ci];
+  int32_t* d_far = d_far3[best_ci].get();
   // nearly all entries far: the form buys nothing
-  if (best_st.far * 10 > pl->nnz * 9 && !wpb_force) {
-    cleanup();
+  if (best_st.far * 10 > pl->nnz * 9 && !wpb_force)
     return SPMV_HIP_OK;
-  }
   tr.mark("count");
   // The SIGMA layout (blocks of 16 slices sorted by length across the block,
   // two slices per wave: sj_sigma_kernel) for blocks of 1024 rows; `nsl` then
@@ -1178,32 +1108,22 @@ int spmv_sjds_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
     hipcub::TransformInputIterator<int32_t, SjShortLen,
                                    hipcub::CountingInputIterator<int32_t>>
         lens(first, SjShortLen{rowptr, thr, pl->nnz});
-    int32_t* d_max = nullptr;
-    void* tmpm = nullptr;
-    size_t tbm = 0;
-    hipError_t em = hipMalloc(&d_max, sizeof(int32_t));
+    PlanScratch<int32_t> d_max;
+    PlanScratch<void> tmpm;
+    hipError_t em = d_max.alloc(1);
     if (em == hipSuccess)
-      em = hipcub::DeviceReduce::Max(nullptr, tbm, lens, d_max, n, st);
+      em = plan_cub(tmpm, [&](void* t, size_t& tb) {
+        return hipcub::DeviceReduce::Max(t, tb, lens, d_max.get(), n, st);
+      });
     if (em == hipSuccess)
-      em = hipMalloc(&tmpm, tbm ? tbm : 16);
-    if (em == hipSuccess)
-      em = hipcub::DeviceReduce::Max(tmpm, tbm, lens, d_max, n, st);
-    if (em == hipSuccess)
-      em = hipMemcpyAsync(&h_max, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (em == hipSuccess)
-      em = hipStreamSynchronize(st);
-    (void)hipFree(tmpm);
-    (void)hipFree(d_max);
+      em = plan_fetch(&h_max, d_max.get(), 1, st);
     if (em != hipSuccess) {
-      cleanup();
       (void)hipGetLastError();
       return em == hipErrorOutOfMemory ? SPMV_HIP_OK : static_cast<int>(em);
     }
   }
-  if (h_max >= (1 << (31 - 6))) { // no word holds it: the form is not taken
-    cleanup();
+  if (h_max >= (1 << (31 - 6))) // no word holds it: the form is not taken
     return SPMV_HIP_OK;
-  }
   tr.mark("max length");
   int sigma = 0;
   if (best == 16 && pl->ctx->sj_sigma && h_max < (1 << (31 - kSjSigBits))) {
@@ -1215,11 +1135,10 @@ int spmv_sjds_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   // first unit of every slice: scan of the slices' unit counts
   uint32_t total_units = 0;
   {
-    void* tmp = nullptr;
-    size_t tb = 0;
-    e = hipMalloc(&pl->sj_ubase, sizeof(uint32_t) * (size_t)(nsl_all + 1));
+    PlanScratch<void> tmp;
+    e = spmv_plan_malloc(&pl->sj_ubase, sizeof(uint32_t) * (size_t)(nsl_all + 1));
     if (e == hipSuccess)
-      e = hipMalloc(&pl->sj_lenperm, sizeof(int32_t) * (size_t)nsl_all * 64);
+      e = spmv_plan_malloc(&pl->sj_lenperm, sizeof(int32_t) * (size_t)nsl_all * 64);
     if (e == hipSuccess) {
       if (sigma)
         hipLaunchKernelGGL(sj_sigma_kernel,
@@ -1233,19 +1152,12 @@ int spmv_sjds_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
       e = hipGetLastError();
     }
     if (e == hipSuccess)
-      e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, pl->sj_ubase, pl->sj_ubase,
-                                           (int)(nsl_all + 1), st);
+      e = plan_cub(tmp, [&](void* t, size_t& tb) {
+        return hipcub::DeviceScan::ExclusiveSum(t, tb, pl->sj_ubase, pl->sj_ubase,
+                                                (int)(nsl_all + 1), st);
+      });
     if (e == hipSuccess)
-      e = hipMalloc(&tmp, tb ? tb : 16);
-    if (e == hipSuccess)
-      e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, pl->sj_ubase, pl->sj_ubase,
-                                           (int)(nsl_all + 1), st);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(&total_units, pl->sj_ubase + nsl_all, sizeof(uint32_t),
-                         hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-      e = hipStreamSynchronize(st);
-    (void)hipFree(tmp);
+      e = plan_fetch(&total_units, pl->sj_ubase + nsl_all, 1, st);
   }
   tr.mark("sigma / units");
   const int R = 64 * best;
@@ -1255,11 +1167,11 @@ int spmv_sjds_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   const size_t code_bytes
       = (size_t)(wide_alloc ? 4 : 2) * ((size_t)total_units + kSjSlack) * E;
   if (e == hipSuccess)
-    e = hipMalloc(&pl->sj_blk, sizeof(int32_t) * 2 * (size_t)nblk);
+    e = spmv_plan_malloc(&pl->sj_blk, sizeof(int32_t) * 2 * (size_t)nblk);
   if (e == hipSuccess)
-    e = hipMalloc(&pl->sj_chunks, sizeof(int32_t) * (size_t)nblk * stride);
+    e = spmv_plan_malloc(&pl->sj_chunks, sizeof(int32_t) * (size_t)nblk * stride);
   if (e == hipSuccess)
-    e = hipMalloc(&pl->sj_codes, code_bytes);
+    e = spmv_plan_malloc(&pl->sj_codes, code_bytes);
   if (e == hipSuccess) // (the slack's codes must be valid LDS indices: 0)
     e = hipMemsetAsync(pl->sj_codes, 0, code_bytes, st);
   tr.mark("alloc codes");
@@ -1282,7 +1194,10 @@ int spmv_sjds_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   if (e == hipSuccess)
     e = hipStreamSynchronize(st);
   tr.mark("fill");
-  cleanup();
+  d_k.reset(); // (before the long rows' list allocates)
+  for (PlanScratch<int32_t>& far : d_far3)
+    far.reset();
+  d_stats.reset();
   if (e != hipSuccess) {
     spmv_sjds_free(pl);
     (void)hipGetLastError();
@@ -1334,9 +1249,8 @@ int spmv_sjds_bake_f32f64(spmv_hip_csr_plan* pl, const float* values32, hipStrea
   if (values32 == nullptr) {
     if (pl->sj_val32) {
       SPMV_CHECK_HIP(hipDeviceSynchronize());
-      (void)hipFree(pl->sj_val32);
+      plan_drop(pl->sj_val32);
     }
-    pl->sj_val32 = nullptr;
     pl->sj32_values0 = nullptr;
     return SPMV_HIP_OK;
   }
@@ -1346,14 +1260,13 @@ int spmv_sjds_bake_f32f64(spmv_hip_csr_plan* pl, const float* values32, hipStrea
   const auto t_begin = std::chrono::steady_clock::now();
   if (!pl->sj_val32) {
     const size_t entries = (size_t)(pl->sj_units + kSjSlack) * pl->sj_unit;
-    hipError_t e = hipMalloc(&pl->sj_val32, sizeof(float) * entries);
+    hipError_t e = spmv_plan_malloc(&pl->sj_val32, sizeof(float) * entries);
     if (e == hipSuccess)
       e = hipMemsetAsync(static_cast<float*>(pl->sj_val32)
                              + (size_t)pl->sj_units * pl->sj_unit,
                          0, sizeof(float) * (size_t)kSjSlack * pl->sj_unit, st);
     if (e != hipSuccess) {
-      (void)hipFree(pl->sj_val32);
-      pl->sj_val32 = nullptr;
+      plan_drop(pl->sj_val32);
       (void)hipGetLastError();
       return e == hipErrorOutOfMemory ? SPMV_HIP_ENOTSUP : static_cast<int>(e);
     }
@@ -1423,7 +1336,7 @@ __global__ __launch_bounds__(kBlock) void sj_sym_merge_kernel(
 } // namespace
 
 // The merged matrix of a symmetric plan with its transposed map: row pointer,
-// columns and value positions, owned by the caller (hipFree).  ENOMEM: no memory.
+// columns and value positions, owned by the caller (spmv_plan_free).  ENOMEM: no memory.
 // long_thr: rows of the stored lower block with more entries keep only their
 // column's entries (INT32_MAX: every row whole); *total: the merged entries.
 int spmv_sjds_sym_merge(const spmv_hip_csr_plan* pl, int long_thr, int32_t** vptr,
@@ -1434,13 +1347,12 @@ int spmv_sjds_sym_merge(const spmv_hip_csr_plan* pl, int long_thr, int32_t** vpt
   if (nnz2 > INT32_MAX)
     return SPMV_HIP_ENOTSUP;
   *vptr = *vcol = *vmap = nullptr;
-  void* tmp = nullptr;
-  size_t tb = 0;
-  hipError_t e = hipMalloc(vptr, sizeof(int32_t) * ((size_t)n + 1));
+  PlanScratch<void> tmp;
+  hipError_t e = spmv_plan_malloc(vptr, sizeof(int32_t) * ((size_t)n + 1));
   if (e == hipSuccess)
-    e = hipMalloc(vcol, sizeof(int32_t) * (size_t)nnz2);
+    e = spmv_plan_malloc(vcol, sizeof(int32_t) * (size_t)nnz2);
   if (e == hipSuccess)
-    e = hipMalloc(vmap, sizeof(int32_t) * (size_t)nnz2);
+    e = spmv_plan_malloc(vmap, sizeof(int32_t) * (size_t)nnz2);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(sj_sym_len_kernel, dim3(spmv_grid_for(pl->ctx, n + 1, kBlock)),
                        dim3(kBlock), 0, st, n, pl->rowptr0, pl->t_ptr, long_thr, pl->nnz,
@@ -1448,11 +1360,9 @@ int spmv_sjds_sym_merge(const spmv_hip_csr_plan* pl, int long_thr, int32_t** vpt
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, *vptr, *vptr, n + 1, st);
-  if (e == hipSuccess)
-    e = hipMalloc(&tmp, tb ? tb : 16);
-  if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, *vptr, *vptr, n + 1, st);
+    e = plan_cub(tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceScan::ExclusiveSum(t, tb, *vptr, *vptr, n + 1, st);
+    });
   if (e == hipSuccess) {
     hipLaunchKernelGGL(sj_sym_merge_kernel,
                        dim3(spmv_grid_for(pl->ctx, n, kBlock / 64)), dim3(kBlock), 0, st,
@@ -1462,18 +1372,14 @@ int spmv_sjds_sym_merge(const spmv_hip_csr_plan* pl, int long_thr, int32_t** vpt
   }
   int32_t h_total = 0;
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&h_total, *vptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
+    e = plan_fetch(&h_total, *vptr + n, 1, st);
   *total = h_total;
-  (void)hipFree(tmp);
+  tmp.reset();
   if (e != hipSuccess) {
-    (void)hipFree(*vptr);
-    (void)hipFree(*vcol);
-    (void)hipFree(*vmap);
-    *vptr = *vcol = *vmap = nullptr;
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? SPMV_HIP_ENOMEM : static_cast<int>(e);
+    plan_drop(*vptr);
+    plan_drop(*vcol);
+    plan_drop(*vmap);
+    return plan_fail(e);
   }
   return SPMV_HIP_OK;
 }
@@ -1507,8 +1413,7 @@ int spmv_sjds_sym_build(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan, hipStream_t 
   // state must not outlive a form that was not built -- ADVICE r05)
   auto drop_long = [&]() {
     spmv_sj_lt_free(plan);
-    (void)hipFree(plan->sj_long_rows);
-    plan->sj_long_rows = nullptr;
+    plan_drop(plan->sj_long_rows);
     plan->sj_nlong = 0;
     plan->sj_long_thr = INT32_MAX;
   };
@@ -1550,8 +1455,7 @@ int spmv_sjds_sym_build(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan, hipStream_t 
   }
   tr.mark("sjds_build");
   // (the columns were for the analysis only: the kernel reads its codes)
-  (void)hipFree(plan->sjv_col);
-  plan->sjv_col = nullptr;
+  plan_drop(plan->sjv_col);
   if (ch)
     ch->colind0 = nullptr;
   if (rb != SPMV_HIP_OK || !ch->sj_lenperm) {
@@ -1559,9 +1463,8 @@ int spmv_sjds_sym_build(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan, hipStream_t 
       spmv_sjds_free(ch);
       delete ch;
     }
-    (void)hipFree(plan->sjv_ptr);
-    (void)hipFree(plan->sjv_map);
-    plan->sjv_ptr = plan->sjv_map = nullptr;
+    plan_drop(plan->sjv_ptr);
+    plan_drop(plan->sjv_map);
     drop_long();
     return rb != SPMV_HIP_OK ? rb : SPMV_HIP_ENOTSUP;
   }

@@ -5,7 +5,7 @@
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 #include <hipcub/hipcub.hpp>
 
-#include "plan_malloc.h" // (last: hipMalloc / hipFree below are timed)
+#include "plan_scratch.h"
 
 namespace
 {
@@ -581,10 +581,9 @@ int spmv_run_symmetric_f32(const spmv_hip_csr_plan* pl, hipStream_t st,
 
 void spmv_symt_free(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->t_ptr);
-  (void)hipFree(pl->t_pos);
-  (void)hipFree(pl->t_row);
-  pl->t_ptr = pl->t_pos = pl->t_row = nullptr;
+  plan_drop(pl->t_ptr);
+  plan_drop(pl->t_pos);
+  plan_drop(pl->t_row);
   pl->sym_det = 0;
 }
 
@@ -622,82 +621,80 @@ int spmv_tmap_build(spmv_hip_ctx* ctx, int32_t num_rows, int64_t nnz,
   *refused = 0;
   const int32_t n = num_rows;
   const int32_t m = c1 - c0; // columns of the map
-  int32_t *t_ptr = nullptr, *t_pos = nullptr, *t_row = nullptr;
-  int32_t *rowidx = nullptr, *pos = nullptr, *keys = nullptr, *flag = nullptr;
-  void* tmp = nullptr;
+  PlanScratch<int32_t> t_ptr, t_pos, t_row; // (the caller's on success)
+  PlanScratch<int32_t> rowidx, pos, keys, flag;
+  PlanScratch<void> tmp; // (one for the sort and the scan: the larger size)
   size_t tmp_bytes = 0, scan_bytes = 0;
   // the sort's keys are the columns themselves: bits up to the range's end
   int end_bit = 1;
   while (end_bit < 31 && ((int64_t)1 << end_bit) < c1)
     ++end_bit;
-  hipError_t e = hipMalloc(&t_ptr, sizeof(int32_t) * ((size_t)m + 1));
+  hipError_t e = t_ptr.alloc((size_t)m + 1);
   if (e == hipSuccess)
-    e = hipMalloc(&t_pos, sizeof(int32_t) * (size_t)nnz);
+    e = t_pos.alloc((size_t)nnz);
   if (e == hipSuccess)
-    e = hipMalloc(&t_row, sizeof(int32_t) * (size_t)nnz);
+    e = t_row.alloc((size_t)nnz);
   if (e == hipSuccess)
-    e = hipMalloc(&rowidx, sizeof(int32_t) * (size_t)nnz);
+    e = rowidx.alloc((size_t)nnz);
   if (e == hipSuccess)
-    e = hipMalloc(&pos, sizeof(int32_t) * (size_t)nnz);
+    e = pos.alloc((size_t)nnz);
   if (e == hipSuccess)
-    e = hipMalloc(&keys, sizeof(int32_t) * (size_t)nnz);
+    e = keys.alloc((size_t)nnz);
   if (e == hipSuccess)
-    e = hipMalloc(&flag, sizeof(int32_t));
+    e = flag.alloc(1);
   if (e == hipSuccess)
-    e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, colind, keys, pos,
-                                           t_pos, nnz, 0, end_bit, st);
+    e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, colind, keys.get(),
+                                           pos.get(), t_pos.get(), nnz, 0, end_bit,
+                                           st);
   if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, t_ptr, t_ptr, m + 1,
-                                         st);
+    e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, t_ptr.get(),
+                                         t_ptr.get(), m + 1, st);
   if (e == hipSuccess)
-    e = hipMalloc(&tmp, (tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes) + 16);
+    e = tmp.alloc((tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes) + 16);
   if (e == hipSuccess)
-    e = hipMemsetAsync(t_ptr, 0, sizeof(int32_t) * ((size_t)m + 1), st);
+    e = hipMemsetAsync(t_ptr.get(), 0, sizeof(int32_t) * ((size_t)m + 1), st);
   if (e == hipSuccess)
-    e = hipMemsetAsync(flag, 0, sizeof(int32_t), st);
+    e = hipMemsetAsync(flag.get(), 0, sizeof(int32_t), st);
   int32_t bad = 0;
   if (e == hipSuccess) {
     const int grid = spmv_grid_for(ctx, n, kBlock);
     hipLaunchKernelGGL(symt_rowidx_kernel, dim3(grid), dim3(kBlock), 0, st, n,
-                       rowptr, colind, c0, c1, lower ? 1 : 0, rowidx, pos, t_ptr,
-                       flag);
+                       rowptr, colind, c0, c1, lower ? 1 : 0, rowidx.get(), pos.get(),
+                       t_ptr.get(), flag.get());
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&bad, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
+    e = plan_fetch(&bad, flag.get(), 1, st);
   if (e == hipSuccess && !bad) {
     // entries by column, ties in their original (row, position) order: radix
     // sort is stable
-    e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, colind, keys, pos,
-                                           t_pos, nnz, 0, end_bit, st);
-    if (e == hipSuccess)
-      e = hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, t_ptr, t_ptr, m + 1,
+    e = hipcub::DeviceRadixSort::SortPairs(tmp.get(), tmp_bytes, colind, keys.get(),
+                                           pos.get(), t_pos.get(), nnz, 0, end_bit,
                                            st);
+    if (e == hipSuccess)
+      e = hipcub::DeviceScan::ExclusiveSum(tmp.get(), scan_bytes, t_ptr.get(),
+                                           t_ptr.get(), m + 1, st);
     if (e == hipSuccess) {
       const int grid = spmv_grid_for(ctx, nnz, kBlock);
       hipLaunchKernelGGL(symt_gather_rows_kernel, dim3(grid), dim3(kBlock), 0,
-                         st, nnz, rowidx, t_pos, t_row);
+                         st, nnz, rowidx.get(), t_pos.get(), t_row.get());
       e = hipGetLastError();
     }
     if (e == hipSuccess)
       e = hipStreamSynchronize(st);
   }
-  (void)hipFree(tmp);
-  (void)hipFree(rowidx);
-  (void)hipFree(pos);
-  (void)hipFree(keys);
-  (void)hipFree(flag);
+  tmp.reset();
+  rowidx.reset();
+  pos.reset();
+  keys.reset();
+  flag.reset();
   if (e != hipSuccess || bad) {
-    (void)hipFree(t_ptr);
-    (void)hipFree(t_pos);
-    (void)hipFree(t_row);
     *refused = e == hipSuccess ? 1 : 0;
     return static_cast<int>(e);
   }
-  *t_ptr_out = t_ptr;
-  *t_pos_out = t_pos;
-  *t_row_out = t_row;
+  // (both callers pass fields they have just dropped: give frees nothing)
+  t_ptr.give(*t_ptr_out);
+  t_pos.give(*t_pos_out);
+  t_row.give(*t_row_out);
   return SPMV_HIP_OK;
 }

@@ -59,7 +59,7 @@
 #include "csr_plan.h"
 #include "lat_dma.h"
 
-#include "plan_malloc.h" // (last: hipMalloc / hipFree below are timed)
+#include "plan_scratch.h"
 
 static void sdia_free_arrays(spmv_hip_csr_plan* pl);
 
@@ -1150,8 +1150,8 @@ int sdia_tile_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
     static int64_t have_rows = 0;
     if (have_rows < pl->num_rows) {
       for (auto& b : bufs) {
-        (void)hipFree(b);
-        SPMV_CHECK_HIP(hipMalloc(&b, sizeof(double) * ((size_t)pl->num_rows + 64)));
+        (void)spmv_plan_free(b);
+        SPMV_CHECK_HIP(spmv_plan_malloc(&b, sizeof(double) * ((size_t)pl->num_rows + 64)));
         SPMV_CHECK_HIP(hipMemset(b, 0, sizeof(double) * ((size_t)pl->num_rows + 64)));
       }
       have_rows = pl->num_rows;
@@ -1328,32 +1328,30 @@ int sdia_restore_walk(spmv_hip_csr_plan* pl)
 // there are more than three (or none)
 int sdia_general_offsets(spmv_hip_csr_plan* pl, hipStream_t st, int* nd, int* U)
 {
-  int32_t* d_w = nullptr; // [0..7] set, [8] fail
+  PlanScratch<int32_t> d_w; // [0..7] set, [8] fail
   int32_t h_w[9];
   for (int s = 0; s < 8; ++s)
     h_w[s] = INT32_MAX;
   h_w[8] = 0;
-  hipError_t e = hipMalloc(&d_w, sizeof(h_w));
+  hipError_t e = d_w.alloc(9);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(d_w, h_w, sizeof(h_w), hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(d_w.get(), h_w, sizeof(h_w), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     if (pl->lat_tab) {
       const int nrb = (pl->num_rows + kRows - 1) / kRows;
       hipLaunchKernelGGL(sdia_offsets_from_lattice_kernel,
                          dim3((nrb + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
-                         nrb, pl->lat_tab, d_w, d_w + 8);
+                         nrb, pl->lat_tab, d_w.get(), d_w.get() + 8);
     } else {
       const int grid = spmv_grid_for(pl->ctx, pl->num_rows, kBlock);
       hipLaunchKernelGGL(sdia_offsets_kernel, dim3(grid), dim3(kBlock), 0, st,
-                         pl->num_rows, pl->rowptr0, pl->colind0, d_w, d_w + 8);
+                         pl->num_rows, pl->rowptr0, pl->colind0, d_w.get(), d_w.get() + 8);
     }
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(h_w, d_w, sizeof(h_w), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_w);
+    e = plan_fetch(h_w, d_w.get(), 9, st);
+  d_w.reset();
   if (e != hipSuccess)
     return static_cast<int>(e);
   *nd = 0;
@@ -1396,51 +1394,48 @@ int sdia_fill(spmv_hip_csr_plan* pl, bool general, const T* values,
   const int64_t len = (((int64_t)n + kRows - 1) / kRows) * kRows + 2 * kRows;
   const int narr = pl->sdia_general == 2 ? 2 * g.nd + 1 : g.nd + 1;
   const size_t bytes = (size_t)narr * len * sizeof(T);
-  void* sval = nullptr;
-  uint8_t* cm = nullptr;
-  int32_t* d_fail = nullptr;
+  PlanScratch<void> sval;
+  PlanScratch<uint8_t> cm;
+  PlanScratch<int32_t> d_fail;
   int32_t h_fail = 0;
-  hipError_t e = hipMalloc(&sval, bytes);
+  hipError_t e = sval.alloc(bytes);
   if (e == hipSuccess)
-    e = hipMalloc(&cm, (size_t)n);
+    e = cm.alloc((size_t)n);
   if (e == hipSuccess)
-    e = hipMalloc(&d_fail, sizeof(int32_t));
+    e = d_fail.alloc(1);
   if (e == hipSuccess)
-    e = hipMemsetAsync(sval, 0, bytes, st);
+    e = hipMemsetAsync(sval.get(), 0, bytes, st);
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_fail, 0, sizeof(int32_t), st);
+    e = hipMemsetAsync(d_fail.get(), 0, sizeof(int32_t), st);
   if (e == hipSuccess) {
     const int grid = spmv_grid_for(pl->ctx, n, kBlock);
     if (general && pl->sdia_general == 2)
       hipLaunchKernelGGL((sdia_bake_general_kernel<T, true, true>), dim3(grid),
                          dim3(kBlock), 0, st, n, g.nd, g.U[0], g.U[1], g.U[2],
                          pl->rowptr0, pl->colind0, values, len,
-                         static_cast<T*>(sval), cm, d_fail, 0);
+                         static_cast<T*>(sval.get()), cm.get(), d_fail.get(), 0);
     else if (general) // (the mirrors were checked by sdia_is_symmetric)
       hipLaunchKernelGGL((sdia_bake_general_kernel<T, false, true>), dim3(grid),
                          dim3(kBlock), 0, st, n, g.nd, g.U[0], g.U[1], g.U[2],
                          pl->rowptr0, pl->colind0, values, len,
-                         static_cast<T*>(sval), cm, d_fail, 0);
+                         static_cast<T*>(sval.get()), cm.get(), d_fail.get(), 0);
     else
       hipLaunchKernelGGL((sdia_bake_kernel<T>), dim3(grid), dim3(kBlock), 0, st,
                          n, g.nd, g.U[0], g.U[1], g.U[2], pl->rowptr0,
                          pl->slat_mask, values, diagonal, len,
-                         static_cast<T*>(sval), cm);
+                         static_cast<T*>(sval.get()), cm.get());
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&h_fail, d_fail, sizeof(int32_t), hipMemcpyDeviceToHost,
-                       st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_fail);
+    e = plan_fetch(&h_fail, d_fail.get(), 1, st);
+  d_fail.reset();
   if (e != hipSuccess || h_fail) { // not symmetric: nothing changes
-    (void)hipFree(sval);
-    (void)hipFree(cm);
+    sval.reset();
+    cm.reset();
     return e != hipSuccess ? static_cast<int>(e) : SPMV_HIP_ENOTSUP;
   }
-  *out_val = sval;
-  *out_cmask = cm;
+  sval.give(*out_val); // (the caller passes null pointers: give frees nothing)
+  cm.give(*out_cmask);
   *out_len = len;
   return SPMV_HIP_OK;
 }
@@ -1451,26 +1446,23 @@ template <typename T>
 int sdia_is_symmetric(spmv_hip_csr_plan* pl, const T* values, hipStream_t st,
                       bool* yes)
 {
-  int32_t* d_fail = nullptr;
+  PlanScratch<int32_t> d_fail;
   int32_t h_fail = 1;
-  hipError_t e = hipMalloc(&d_fail, sizeof(int32_t));
+  hipError_t e = d_fail.alloc(1);
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_fail, 0, sizeof(int32_t), st);
+    e = hipMemsetAsync(d_fail.get(), 0, sizeof(int32_t), st);
   if (e == hipSuccess) {
     const int grid = spmv_grid_for(pl->ctx, pl->num_rows, kBlock);
     hipLaunchKernelGGL((sdia_bake_general_kernel<T, false, false>), dim3(grid),
                        dim3(kBlock), 0, st, pl->num_rows, pl->sdia_nd,
                        pl->sdia_U[0], pl->sdia_U[1], pl->sdia_U[2], pl->rowptr0,
                        pl->colind0, values, (int64_t)0, (T*)nullptr,
-                       (uint8_t*)nullptr, d_fail, 1);
+                       (uint8_t*)nullptr, d_fail.get(), 1);
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&h_fail, d_fail, sizeof(int32_t), hipMemcpyDeviceToHost,
-                       st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_fail);
+    e = plan_fetch(&h_fail, d_fail.get(), 1, st);
+  d_fail.reset();
   *yes = h_fail == 0;
   return e == hipSuccess ? SPMV_HIP_OK : static_cast<int>(e);
 }
@@ -1483,11 +1475,11 @@ int sdia_const_probe(spmv_hip_csr_plan* pl, bool general, const T* values,
                      uint8_t* cmask_out)
 {
   *yes = false;
-  SdiaConstProbe* d_pr = nullptr;
+  PlanScratch<SdiaConstProbe> d_pr;
   SdiaConstProbe h_pr;
-  hipError_t e = hipMalloc(&d_pr, sizeof(SdiaConstProbe));
+  hipError_t e = d_pr.alloc(1);
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_pr, 0, sizeof(SdiaConstProbe), st);
+    e = hipMemsetAsync(d_pr.get(), 0, sizeof(SdiaConstProbe), st);
   if (e == hipSuccess) {
     const int grid = spmv_grid_for(pl->ctx, pl->num_rows, kBlock);
     const int nd = pl->sdia_nd, u0 = pl->sdia_U[0], u1 = pl->sdia_U[1],
@@ -1504,32 +1496,29 @@ int sdia_const_probe(spmv_hip_csr_plan* pl, bool general, const T* values,
                          dim3(kBlock), 0, st, pick_rows, pl->num_rows, nd, u0, u1,
                          u2,
                          pl->rowptr0, pl->colind0, (const uint8_t*)nullptr,
-                         values, diagonal, d_pr, (uint8_t*)nullptr);
+                         values, diagonal, d_pr.get(), (uint8_t*)nullptr);
       hipLaunchKernelGGL((sdia_const_kernel<T, true, true>), dim3(grid),
                          dim3(kBlock), 0, st, pl->num_rows, pl->num_rows, nd, u0,
                          u1, u2,
                          pl->rowptr0, pl->colind0, (const uint8_t*)nullptr,
-                         values, diagonal, d_pr, cmask_out);
+                         values, diagonal, d_pr.get(), cmask_out);
     } else {
       hipLaunchKernelGGL((sdia_const_kernel<T, false, false>), dim3(grid),
                          dim3(kBlock), 0, st, pick_rows, pl->num_rows, nd, u0, u1,
                          u2,
                          pl->rowptr0, pl->colind0, pl->slat_mask, values,
-                         diagonal, d_pr, (uint8_t*)nullptr);
+                         diagonal, d_pr.get(), (uint8_t*)nullptr);
       hipLaunchKernelGGL((sdia_const_kernel<T, false, true>), dim3(grid),
                          dim3(kBlock), 0, st, pl->num_rows, pl->num_rows, nd, u0,
                          u1, u2,
                          pl->rowptr0, pl->colind0, pl->slat_mask, values,
-                         diagonal, d_pr, cmask_out);
+                         diagonal, d_pr.get(), cmask_out);
     }
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&h_pr, d_pr, sizeof(SdiaConstProbe), hipMemcpyDeviceToHost,
-                       st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_pr);
+    e = plan_fetch(&h_pr, d_pr.get(), 1, st);
+  d_pr.reset();
   if (e != hipSuccess)
     return static_cast<int>(e);
   if (h_pr.fail)
@@ -1635,18 +1624,16 @@ int sdia_bake(spmv_hip_csr_plan* pl, const T* values, const T* diagonal,
     bool is_const = false;
     if (pl->ctx->const_diagonals) {
       // (the second pass writes the mask byte on the way: one pass fewer)
-      hipError_t ea = hipMalloc(&cm, (size_t)pl->num_rows);
+      hipError_t ea = spmv_plan_malloc(&cm, (size_t)pl->num_rows);
       if (ea == hipSuccess)
-        ea = hipMalloc(&sval, 64); // the "baked" marker every check looks at
+        ea = spmv_plan_malloc(&sval, 64); // the "baked" marker every check looks at
       rc = ea == hipSuccess ? SPMV_HIP_OK : static_cast<int>(ea);
       if (rc == SPMV_HIP_OK)
         rc = sdia_const_probe<T>(pl, general, values, diagonal, st, &is_const,
                                  pl->sdia_cval, cm);
       if (rc != SPMV_HIP_OK || !is_const) {
-        (void)hipFree(cm);
-        (void)hipFree(sval);
-        cm = nullptr;
-        sval = nullptr;
+        plan_drop(cm);
+        plan_drop(sval);
       }
     }
     if (rc == SPMV_HIP_OK && is_const) {
@@ -1703,10 +1690,8 @@ int sdia_bake(spmv_hip_csr_plan* pl, const T* values, const T* diagonal,
 int sdia_bake_mixed(spmv_hip_csr_plan* pl, const float* values32, hipStream_t st)
 {
   SPMV_CHECK_HIP(hipSetDevice(pl->ctx->device));
-  (void)hipFree(pl->sdia32_val);
-  (void)hipFree(pl->sdia32_cmask);
-  pl->sdia32_val = nullptr;
-  pl->sdia32_cmask = nullptr;
+  plan_drop(pl->sdia32_val);
+  plan_drop(pl->sdia32_cmask);
   pl->sdia32_values0 = nullptr;
   if (values32 == nullptr)
     return SPMV_HIP_OK; // dropped
@@ -1722,7 +1707,7 @@ int sdia_bake_mixed(spmv_hip_csr_plan* pl, const float* values32, hipStream_t st
       return rcc;
     if (!is_const)
       return SPMV_HIP_ENOTSUP;
-    SPMV_CHECK_HIP(hipMalloc(&pl->sdia32_val, 64)); // the "baked" marker
+    SPMV_CHECK_HIP(spmv_plan_malloc(&pl->sdia32_val, 64)); // the "baked" marker
     pl->sdia32_values0 = values32;
     pl->plan_us += (int)std::chrono::duration_cast<std::chrono::microseconds>(
                        std::chrono::steady_clock::now() - t_begin)
@@ -1766,8 +1751,7 @@ int spmv_sdia_tile_build(spmv_hip_csr_plan* pl, int R, int segments, bool force)
   if (pl->sdia_tile_table) {
     SPMV_CHECK_HIP(hipSetDevice(pl->ctx->device));
     SPMV_CHECK_HIP(hipDeviceSynchronize()); // no launch still reads the old one
-    (void)hipFree(pl->sdia_tile_table);
-    pl->sdia_tile_table = nullptr;
+    plan_drop(pl->sdia_tile_table);
   }
   pl->sdia_tile_slots = pl->sdia_tile_grid = pl->sdia_tile_segments = 0;
   pl->sdia_tile = 0;
@@ -1805,21 +1789,16 @@ void spmv_sdia_free(spmv_hip_csr_plan* pl)
 // the baked copies alone; the plane-walk table is the caller's business
 static void sdia_free_arrays(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->sdia_val);
-  (void)hipFree(pl->sdia_cmask);
-  (void)hipFree(pl->sdia32_val);
-  (void)hipFree(pl->sdia32_cmask);
-  pl->sdia32_val = nullptr;
-  pl->sdia32_cmask = nullptr;
+  plan_drop(pl->sdia_val);
+  plan_drop(pl->sdia_cmask);
+  plan_drop(pl->sdia32_val);
+  plan_drop(pl->sdia32_cmask);
   pl->sdia32_values0 = nullptr;
-  pl->sdia_val = nullptr;
-  pl->sdia_cmask = nullptr;
   pl->sdia_values0 = pl->sdia_diag0 = nullptr;
   pl->sdia_len = 0;
   pl->sdia_elem = 0;
   pl->sdia_const = 0;
-  (void)hipFree(pl->sdia_tile_table);
-  pl->sdia_tile_table = nullptr;
+  plan_drop(pl->sdia_tile_table);
   pl->sdia_tile_slots = pl->sdia_tile_grid = pl->sdia_tile_segments = 0;
   pl->sdia_tile = 0;
   pl->sdia = 0;

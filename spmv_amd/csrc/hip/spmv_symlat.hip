@@ -36,7 +36,7 @@
 #include "csr_plan.h"
 #include "lat_dma.h"
 
-#include "plan_malloc.h" // (last: hipMalloc / hipFree below are timed)
+#include "plan_scratch.h"
 
 namespace
 {
@@ -463,8 +463,7 @@ int spmv_slat_grid(const spmv_hip_csr_plan* pl)
 
 void spmv_slat_free(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->slat_mask);
-  pl->slat_mask = nullptr;
+  plan_drop(pl->slat_mask);
   pl->slat = 0;
 }
 
@@ -479,24 +478,22 @@ int spmv_slat_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   if (n == 0 || pl->nnz == 0)
     return SPMV_HIP_OK;
   hipStream_t st = pl->ctx->stream;
-  int32_t* d_w = nullptr; // [0..7] offset set, [8] fail, [9] max bytes
+  PlanScratch<int32_t> d_w; // [0..7] offset set, [8] fail, [9] max bytes
   int32_t h_w[10];
   for (int s = 0; s < 8; ++s)
     h_w[s] = INT32_MAX;
   h_w[8] = h_w[9] = 0;
-  hipError_t e = hipMalloc(&d_w, sizeof(h_w));
+  hipError_t e = d_w.alloc(10);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(d_w, h_w, sizeof(h_w), hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(d_w.get(), h_w, sizeof(h_w), hipMemcpyHostToDevice, st);
   const int grid = spmv_grid_for(pl->ctx, n, kBlock);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(slat_offsets_kernel, dim3(grid), dim3(kBlock), 0, st, n,
-                       rowptr, colind, d_w, d_w + 8);
+                       rowptr, colind, d_w.get(), d_w.get() + 8);
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(h_w, d_w, sizeof(h_w), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
+    e = plan_fetch(h_w, d_w.get(), 10, st);
   int nd = 0;
   int D[8];
   if (e == hipSuccess && !h_w[8]) {
@@ -511,7 +508,6 @@ int spmv_slat_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
       }
   }
   if (e != hipSuccess || h_w[8] || nd == 0 || nd > kSlatMaxOff) {
-    (void)hipFree(d_w);
     return (e == hipSuccess || e == hipErrorOutOfMemory) ? SPMV_HIP_OK
                                                          : static_cast<int>(e);
   }
@@ -538,17 +534,15 @@ int spmv_slat_build(spmv_hip_csr_plan* pl, const int32_t* rowptr,
       }
     }
   }
-  e = hipMalloc(&pl->slat_mask, (size_t)n);
+  e = spmv_plan_malloc(&pl->slat_mask, (size_t)n);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(slat_mask_kernel, dim3(grid), dim3(kBlock), 0, st, n,
-                       rowptr, colind, g, pl->slat_mask, d_w + 8, d_w + 9);
+                       rowptr, colind, g, pl->slat_mask, d_w.get() + 8, d_w.get() + 9);
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(h_w, d_w, sizeof(h_w), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_w);
+    e = plan_fetch(h_w, d_w.get(), 10, st);
+  d_w.reset();
   // two slots of nw windows must leave room for at least one workgroup
   const int64_t lds = (int64_t)2 * g.nw * h_w[9];
   if (e != hipSuccess || h_w[8] || h_w[9] <= 0 || lds > 150 * 1024) {

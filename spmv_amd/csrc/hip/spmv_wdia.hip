@@ -50,7 +50,7 @@
 #include <new>
 #include <type_traits>
 
-#include "plan_malloc.h" // (last: hipMalloc / hipFree below are timed)
+#include "plan_scratch.h"
 
 namespace
 {
@@ -826,11 +826,11 @@ int wdia_const_probe(const spmv_hip_csr_plan* pl, int K, const WdiaOffsets& off,
                      uint32_t* mask_out)
 {
   *yes = false;
-  WdiaConstProbe* d_pr = nullptr;
+  PlanScratch<WdiaConstProbe> d_pr;
   WdiaConstProbe h_pr;
-  hipError_t e = hipMalloc(&d_pr, sizeof(WdiaConstProbe));
+  hipError_t e = d_pr.alloc(1);
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_pr, 0, sizeof(WdiaConstProbe), st);
+    e = hipMemsetAsync(d_pr.get(), 0, sizeof(WdiaConstProbe), st);
   if (e == hipSuccess) {
     const int grid = spmv_grid_for(pl->ctx, pl->num_rows, kBlock);
     // pass 1 looks at the first few planes only (every diagonal of a stencil
@@ -846,18 +846,15 @@ int wdia_const_probe(const spmv_hip_csr_plan* pl, int K, const WdiaOffsets& off,
         = prefix < pl->num_rows ? (int32_t)prefix : pl->num_rows;
     hipLaunchKernelGGL((wdia_const_kernel<T, false>), dim3(grid), dim3(kBlock), 0,
                        st, pick_rows, K, off, pl->rowptr0, pl->colind0, values,
-                       d_pr, (uint32_t*)nullptr);
+                       d_pr.get(), (uint32_t*)nullptr);
     hipLaunchKernelGGL((wdia_const_kernel<T, true>), dim3(grid), dim3(kBlock), 0,
                        st, pl->num_rows, K, off, pl->rowptr0, pl->colind0, values,
-                       d_pr, mask_out);
+                       d_pr.get(), mask_out);
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&h_pr, d_pr, sizeof(WdiaConstProbe), hipMemcpyDeviceToHost,
-                       st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_pr);
+    e = plan_fetch(&h_pr, d_pr.get(), 1, st);
+  d_pr.reset();
   if (e != hipSuccess)
     return static_cast<int>(e);
   if (h_pr.fail)
@@ -957,13 +954,10 @@ __global__ __launch_bounds__(kBlock) void wdia_bake_kernel(
 
 void wdia_free_arrays(spmv_hip_csr_plan* pl)
 {
-  (void)hipFree(pl->wdia32_val);
-  pl->wdia32_val = nullptr;
+  plan_drop(pl->wdia32_val);
   pl->wdia32_values0 = nullptr;
-  (void)hipFree(pl->wdia_val);
-  (void)hipFree(pl->wdia_mask);
-  pl->wdia_val = nullptr;
-  pl->wdia_mask = nullptr;
+  plan_drop(pl->wdia_val);
+  plan_drop(pl->wdia_mask);
   pl->wdia_values0 = nullptr;
   pl->wdia_len = 0;
   pl->wdia_elem = 0;
@@ -971,13 +965,11 @@ void wdia_free_arrays(spmv_hip_csr_plan* pl)
   pl->wdia_narr = 0;
   pl->wdia_const = 0;
   pl->wdia = 0;
-  (void)hipFree(pl->wdia_box_table);
-  pl->wdia_box_table = nullptr;
+  plan_drop(pl->wdia_box_table);
   pl->wdia_box_slots = pl->wdia_box_grid = pl->wdia_box_segments = 0;
   pl->wdia_box = 0;
   pl->wdia_hbox = 0;
-  (void)hipFree(pl->wdia_zw_table);
-  pl->wdia_zw_table = nullptr;
+  plan_drop(pl->wdia_zw_table);
   pl->wdia_zw_slots = pl->wdia_zw_grid = pl->wdia_zw_segments = 0;
   pl->wdia_d2 = 0;
 }
@@ -1027,22 +1019,19 @@ int wdia_bake(spmv_hip_csr_plan* pl, const T* values, hipStream_t st)
   for (int s = 0; s < kWdiaMaxOff; ++s)
     h_set[s] = INT32_MIN;
   h_set[kWdiaMaxOff] = 0; // fail flag
-  int32_t* d_set = nullptr;
-  hipError_t e = hipMalloc(&d_set, sizeof(h_set));
+  PlanScratch<int32_t> d_set;
+  hipError_t e = d_set.alloc(kWdiaMaxOff + 1);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(d_set, h_set, sizeof(h_set), hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(d_set.get(), h_set, sizeof(h_set), hipMemcpyHostToDevice, st);
   const int grid = spmv_grid_for(pl->ctx, n, kBlock);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(wdia_offsets_kernel, dim3(grid), dim3(kBlock), 0, st, n,
-                       pl->rowptr0, pl->colind0, d_set, d_set + kWdiaMaxOff);
+                       pl->rowptr0, pl->colind0, d_set.get(), d_set.get() + kWdiaMaxOff);
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(h_set, d_set, sizeof(h_set), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
+    e = plan_fetch(h_set, d_set.get(), kWdiaMaxOff + 1, st);
   if (e != hipSuccess) {
-    (void)hipFree(d_set);
     return static_cast<int>(e);
   }
   lap("offsets");
@@ -1053,7 +1042,6 @@ int wdia_bake(spmv_hip_csr_plan* pl, const T* values, hipStream_t st)
       off.D[K++] = h_set[s];
   // worth the memory only while the arrays are mostly full
   if (h_set[kWdiaMaxOff] || K == 0 || (double)pl->nnz < 0.5 * (double)K * n) {
-    (void)hipFree(d_set);
     return SPMV_HIP_ENOTSUP;
   }
   for (int a = 1; a < K; ++a) // insertion sort, ascending
@@ -1074,19 +1062,16 @@ int wdia_bake(spmv_hip_csr_plan* pl, const T* values, hipStream_t st)
   }
   // constant diagonals: no arrays at all, whatever the symmetry
   bool is_const = false;
-  uint32_t* msk = nullptr;
-  e = hipMalloc(&msk, sizeof(uint32_t) * (size_t)n);
+  PlanScratch<uint32_t> msk;
+  e = msk.alloc((size_t)n);
   if (e != hipSuccess) {
-    (void)hipFree(d_set);
     return static_cast<int>(e);
   }
   if (pl->ctx->const_diagonals) {
     // (its second pass writes the masks on the way)
     const int rcc = wdia_const_probe<T>(pl, K, off, values, st, &is_const,
-                                        pl->wdia_cval, msk);
+                                        pl->wdia_cval, msk.get());
     if (rcc != SPMV_HIP_OK) {
-      (void)hipFree(d_set);
-      (void)hipFree(msk);
       return rcc;
     }
     if (is_const)
@@ -1105,24 +1090,21 @@ int wdia_bake(spmv_hip_csr_plan* pl, const T* values, hipStream_t st)
   // pass 2: the copy by offset
   const int64_t len = (((int64_t)n + kRows - 1) / kRows) * kRows;
   const size_t bytes = (size_t)narr * len * sizeof(T);
-  void* sval = nullptr;
+  PlanScratch<void> sval;
   int32_t h_fail = 0;
-  e = hipMalloc(&sval, bytes > 0 ? bytes : 64); // (constant: a marker only)
+  e = sval.alloc(bytes > 0 ? bytes : 64); // (constant: a marker only)
   lap("alloc arrays");
   if (e == hipSuccess && !is_const) {
     // (the bake kernel writes every element of the arrays, zeros included)
-    e = hipMemsetAsync(d_set + kWdiaMaxOff, 0, sizeof(int32_t), st);
+    e = hipMemsetAsync(d_set.get() + kWdiaMaxOff, 0, sizeof(int32_t), st);
     if (e == hipSuccess) {
       hipLaunchKernelGGL((wdia_bake_kernel<T>), dim3(grid), dim3(kBlock), 0, st,
                          n, K, narr, off, pl->rowptr0, pl->colind0, values, len,
-                         static_cast<T*>(sval), msk, d_set + kWdiaMaxOff);
+                         static_cast<T*>(sval.get()), msk.get(), d_set.get() + kWdiaMaxOff);
       e = hipGetLastError();
     }
     if (e == hipSuccess)
-      e = hipMemcpyAsync(&h_fail, d_set + kWdiaMaxOff, sizeof(int32_t),
-                         hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-      e = hipStreamSynchronize(st);
+      e = plan_fetch(&h_fail, d_set.get() + kWdiaMaxOff, 1, st);
     lap("bake");
     // HALF form?  The offsets mirror each other (try_half); is the matrix
     // symmetric entry for entry, bit for bit?  One coalesced pass over the
@@ -1138,58 +1120,55 @@ int wdia_bake(spmv_hip_csr_plan* pl, const T* values, hipStream_t st)
             mir.q[k] = q;
       }
       int32_t h_asym = 1;
-      e = hipMemsetAsync(d_set + kWdiaMaxOff, 0, sizeof(int32_t), st);
+      e = hipMemsetAsync(d_set.get() + kWdiaMaxOff, 0, sizeof(int32_t), st);
       if (e == hipSuccess) {
         hipLaunchKernelGGL((wdia_array_symmetry_kernel<T>), dim3(grid), dim3(kBlock),
-                           0, st, n, K, off, mir, len, static_cast<const T*>(sval),
-                           msk, d_set + kWdiaMaxOff);
+                           0, st, n, K, off, mir, len, static_cast<const T*>(sval.get()),
+                           msk.get(), d_set.get() + kWdiaMaxOff);
         e = hipGetLastError();
       }
       if (e == hipSuccess)
-        e = hipMemcpyAsync(&h_asym, d_set + kWdiaMaxOff, sizeof(int32_t),
-                           hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
+        e = plan_fetch(&h_asym, d_set.get() + kWdiaMaxOff, 1, st);
       lap("symmetry check");
       if (e == hipSuccess && !h_asym) {
         int nh = 0;
         while (nh < K && off.D[nh] <= 0)
           ++nh;
-        void* half = nullptr;
+        PlanScratch<void> half;
         const size_t hbytes = (size_t)nh * len * sizeof(T);
-        hipError_t eh = hipMalloc(&half, hbytes);
+        hipError_t eh = half.alloc(hbytes);
         if (eh == hipSuccess)
-          eh = hipMemcpyAsync(half, sval, hbytes, hipMemcpyDeviceToDevice, st);
+          eh = hipMemcpyAsync(half.get(), sval.get(), hbytes, hipMemcpyDeviceToDevice, st);
         if (eh == hipSuccess)
           eh = hipStreamSynchronize(st);
         lap("alloc + copy half");
         if (eh == hipSuccess) {
-          (void)hipFree(sval);
+          sval.reset();
           lap("free full");
-          sval = half;
+          sval = std::move(half);
           narr = nh;
           for (int k = narr; k < K; ++k) {
             off.A[k] = mir.q[k];
             off.S[k] = off.D[k];
           }
         } else { // no room for the compact copy: the full form serves
-          (void)hipFree(half);
+          half.reset();
           (void)hipGetLastError();
         }
       }
     }
   }
-  (void)hipFree(d_set);
+  d_set.reset();
   if (e != hipSuccess || h_fail) {
-    (void)hipFree(sval);
-    (void)hipFree(msk);
+    sval.reset();
+    msk.reset();
     if (e == hipErrorOutOfMemory)
       (void)hipGetLastError(); // the CSR-order kernels keep running
     return (e != hipSuccess && e != hipErrorOutOfMemory) ? static_cast<int>(e)
                                                          : SPMV_HIP_ENOTSUP;
   }
-  pl->wdia_val = sval;
-  pl->wdia_mask = msk;
+  sval.give(pl->wdia_val);
+  msk.give(pl->wdia_mask);
   pl->wdia_len = len;
   pl->wdia_elem = (int)sizeof(T);
   pl->wdia_K = K;
@@ -1265,8 +1244,7 @@ int wdia_bake(spmv_hip_csr_plan* pl, const T* values, hipStream_t st)
 int wdia_bake_mixed(spmv_hip_csr_plan* pl, const float* values32, hipStream_t st)
 {
   SPMV_CHECK_HIP(hipSetDevice(pl->ctx->device));
-  (void)hipFree(pl->wdia32_val);
-  pl->wdia32_val = nullptr;
+  plan_drop(pl->wdia32_val);
   pl->wdia32_values0 = nullptr;
   if (values32 == nullptr)
     return SPMV_HIP_OK; // dropped
@@ -1289,7 +1267,7 @@ int wdia_bake_mixed(spmv_hip_csr_plan* pl, const float* values32, hipStream_t st
       return rcc;
     if (!is_const)
       return SPMV_HIP_ENOTSUP;
-    SPMV_CHECK_HIP(hipMalloc(&pl->wdia32_val, 64)); // the "baked" marker
+    SPMV_CHECK_HIP(spmv_plan_malloc(&pl->wdia32_val, 64)); // the "baked" marker
     pl->wdia32_values0 = values32;
     pl->plan_us += (int)std::chrono::duration_cast<std::chrono::microseconds>(
                        std::chrono::steady_clock::now() - t_begin)
@@ -1299,62 +1277,56 @@ int wdia_bake_mixed(spmv_hip_csr_plan* pl, const float* values32, hipStream_t st
   if (pl->wdia_narr < pl->wdia_K) {
     // the half form needs THESE values symmetric too (nothing says the fp32
     // array is the rounded fp64 one)
-    int32_t* d_asym = nullptr;
+    PlanScratch<int32_t> d_asym;
     int32_t h_asym = 1;
-    hipError_t es = hipMalloc(&d_asym, sizeof(int32_t));
+    hipError_t es = d_asym.alloc(1);
     if (es == hipSuccess)
-      es = hipMemsetAsync(d_asym, 0, sizeof(int32_t), st);
+      es = hipMemsetAsync(d_asym.get(), 0, sizeof(int32_t), st);
     if (es == hipSuccess) {
       hipLaunchKernelGGL((wdia_symmetry_csr_kernel<float>),
                          dim3(spmv_grid_for(pl->ctx, n, kBlock)), dim3(kBlock), 0,
-                         st, n, pl->rowptr0, pl->colind0, values32, d_asym);
+                         st, n, pl->rowptr0, pl->colind0, values32, d_asym.get());
       es = hipGetLastError();
     }
     if (es == hipSuccess)
-      es = hipMemcpyAsync(&h_asym, d_asym, sizeof(int32_t),
-                          hipMemcpyDeviceToHost, st);
-    if (es == hipSuccess)
-      es = hipStreamSynchronize(st);
-    (void)hipFree(d_asym);
+      es = plan_fetch(&h_asym, d_asym.get(), 1, st);
+    d_asym.reset();
     if (es != hipSuccess)
       return static_cast<int>(es);
     if (h_asym)
       return SPMV_HIP_ENOTSUP;
   }
   const size_t bytes = (size_t)pl->wdia_narr * pl->wdia_len * sizeof(float);
-  void* sval = nullptr;
-  uint32_t* msk = nullptr; // rewritten with the same bits: the kernel's output
-  int32_t* d_fail = nullptr;
+  PlanScratch<void> sval;
+  PlanScratch<uint32_t> msk; // rewritten with the same bits: the kernel's output
+  PlanScratch<int32_t> d_fail;
   int32_t h_fail = 0;
-  hipError_t e = hipMalloc(&sval, bytes);
+  hipError_t e = sval.alloc(bytes);
   if (e == hipSuccess)
-    e = hipMalloc(&msk, sizeof(uint32_t) * (size_t)n);
+    e = msk.alloc((size_t)n);
   if (e == hipSuccess)
-    e = hipMalloc(&d_fail, sizeof(int32_t));
+    e = d_fail.alloc(1);
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_fail, 0, sizeof(int32_t), st);
+    e = hipMemsetAsync(d_fail.get(), 0, sizeof(int32_t), st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL((wdia_bake_kernel<float>), dim3(spmv_grid_for(pl->ctx, n, kBlock)),
                        dim3(kBlock), 0, st, n, pl->wdia_K, pl->wdia_narr, off,
                        pl->rowptr0, pl->colind0, values32, pl->wdia_len,
-                       static_cast<float*>(sval), msk, d_fail);
+                       static_cast<float*>(sval.get()), msk.get(), d_fail.get());
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&h_fail, d_fail, sizeof(int32_t), hipMemcpyDeviceToHost,
-                       st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  (void)hipFree(d_fail);
-  (void)hipFree(msk);
+    e = plan_fetch(&h_fail, d_fail.get(), 1, st);
+  d_fail.reset();
+  msk.reset();
   if (e != hipSuccess || h_fail) {
-    (void)hipFree(sval);
+    sval.reset();
     if (e == hipErrorOutOfMemory)
       (void)hipGetLastError();
     return (e != hipSuccess && e != hipErrorOutOfMemory) ? static_cast<int>(e)
                                                          : SPMV_HIP_ENOTSUP;
   }
-  pl->wdia32_val = sval;
+  sval.give(pl->wdia32_val);
   pl->wdia32_values0 = values32;
   pl->plan_us += (int)std::chrono::duration_cast<std::chrono::microseconds>(
                      std::chrono::steady_clock::now() - t_begin)
@@ -1534,8 +1506,7 @@ int spmv_wdia_walk_build(spmv_hip_csr_plan* pl, int segments, bool force)
   if (pl->wdia_zw_table) {
     SPMV_CHECK_HIP(hipSetDevice(pl->ctx->device));
     SPMV_CHECK_HIP(hipDeviceSynchronize()); // no launch still reads the old one
-    (void)hipFree(pl->wdia_zw_table);
-    pl->wdia_zw_table = nullptr;
+    plan_drop(pl->wdia_zw_table);
     pl->wdia_zw_slots = pl->wdia_zw_grid = pl->wdia_zw_segments = 0;
   }
   const int grid = wdia_grid(pl);
@@ -1603,8 +1574,7 @@ int spmv_wdia_box_build(spmv_hip_csr_plan* pl, int R, int segments, bool force)
   if (pl->wdia_box_table) {
     SPMV_CHECK_HIP(hipSetDevice(pl->ctx->device));
     SPMV_CHECK_HIP(hipDeviceSynchronize()); // no launch still reads the old one
-    (void)hipFree(pl->wdia_box_table);
-    pl->wdia_box_table = nullptr;
+    plan_drop(pl->wdia_box_table);
   }
   pl->wdia_box_slots = pl->wdia_box_grid = pl->wdia_box_segments = 0;
   pl->wdia_box = 0;
