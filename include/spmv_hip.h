@@ -1036,6 +1036,65 @@ int spmv_hip_sgs_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
 int spmv_hip_sgs_dot_rz_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
                             const double* r, const double* z, void* stream);
 
+/* ---- Multicolour ILU(0) factored on the device (spmv::Ilu0Preconditioner) ---------
+ * M = (D~ + L~) D~^-1 (D~ + U~) on the local diagonal block in the colour-major
+ * ordering, fp64, every product, difference and quotient a rounding of its own.
+ * before(i) / after(i) as above but ascending by the POSITION of the column;
+ * rows in position order, rows of one colour never read each other:
+ *   w = row i;  for k in before(i), ascending pos(k):
+ *                 m = w[k] * dinv~[k]
+ *                 for (j, u) in after~(k), in its order:
+ *                   if j == i or j in the pattern of row i: w[j] = w[j] - m * u
+ *   l~(i, .) = w on before(i); u~(i, .) = w on after(i); d~_i = w[i];
+ *   dinv~_i = 1.0 / d~_i
+ * Fill outside the pattern is dropped.  The application is mcgs_apply on the
+ * inner plan (ilu0_mcgs_plan), whose values and dinv ilu0_factor writes.
+ *
+ * The plan is an upload of arrays the HOST built (host/ilu0_build.h): `mcgs`, the
+ * sliced layout with the columns in position order (its values and dinv are
+ * placeholders), and per part, in CSR over positions: ptr (num_rows + 1), cpos
+ * (the column's position, strictly ascending in a row, of a smaller / larger
+ * colour), src (index of the entry's value in the matrix's value array, below
+ * num_values) and slot (>= 0: index into the part's sliced val; < 0: index ~slot
+ * into its long_val).  plan_create checks every index a kernel will use
+ * (SPMV_HIP_EINVAL) and copies.
+ *
+ * ilu0_factor: `values` the matrix's value array (num_values doubles), `diagonal`
+ * the diagonal by ROW (num_rows doubles), both on the device; gather, one launch
+ * per colour 1 .. C-1, finish; nothing waits.  It may be called again with other
+ * values (the same pattern).  ilu0_pivots waits for the stream and returns how
+ * many pivots d~ are not finite or zero, and how many are finite and negative.
+ * ilu0_get_factor (waits): l~ and u~ in part-CSR order and d~ by position;
+ * ilu0_get_pattern: the parts' ptr and cpos.  NULL outputs are skipped. */
+typedef struct spmv_hip_ilu0_plan spmv_hip_ilu0_plan;
+typedef struct spmv_hip_ilu0_part {
+  const int64_t* ptr;
+  const int32_t* cpos;
+  const int32_t* src;
+  const int64_t* slot;
+} spmv_hip_ilu0_part;
+typedef struct spmv_hip_ilu0_host {
+  spmv_hip_mcgs_host mcgs;
+  int64_t num_values;
+  spmv_hip_ilu0_part before, after;
+} spmv_hip_ilu0_host;
+int spmv_hip_ilu0_plan_create(spmv_hip_ctx* ctx, const spmv_hip_ilu0_host* in,
+                              spmv_hip_ilu0_plan** plan);
+int spmv_hip_ilu0_plan_destroy(spmv_hip_ilu0_plan* plan);
+int spmv_hip_ilu0_plan_bytes(const spmv_hip_ilu0_plan* plan, int64_t* bytes);
+int spmv_hip_ilu0_mcgs_plan(const spmv_hip_ilu0_plan* plan,
+                            spmv_hip_mcgs_plan** inner);
+int spmv_hip_ilu0_factor(spmv_hip_ctx* ctx, spmv_hip_ilu0_plan* plan,
+                         const double* values, const double* diagonal,
+                         void* stream);
+int spmv_hip_ilu0_pivots(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
+                         int64_t* not_usable, int64_t* negative, void* stream);
+int spmv_hip_ilu0_get_pattern(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
+                              int64_t* before_ptr, int32_t* before_cpos,
+                              int64_t* after_ptr, int32_t* after_cpos);
+int spmv_hip_ilu0_get_factor(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
+                             double* l, double* u, double* d, void* stream);
+
 /* ---- BiCGStab with an optional diagonal right preconditioner (spmv::bicgstab) ---
  * For nonsymmetric systems.  `dinv` is the inverse of the preconditioner's
  * diagonal or NULL; ph = dinv*p, sh = dinv*s (elementwise), p and s themselves

@@ -156,6 +156,17 @@ int spmvh_matrix_symmetric(spmvh_matrix* A, int* symmetric);
 /* local / remote block sizes: out[0..5] = rows, cols, nnz of local then remote
  * (remote all zero when the matrix has a single block) */
 int spmvh_matrix_blocks(spmvh_matrix* A, int64_t out[6]);
+/* DEVICE pointers of the local block's value array (non-zeros of the local
+ * block doubles, in its CSR order; symmetric storage: the strictly lower
+ * entries) and of its diagonal array (symmetric storage; NULL otherwise), for a
+ * caller who rewrites the coefficients in place on a fixed pattern.  Such a
+ * caller then calls spmvh_matrix_plan_values_changed (Matrix::
+ * plan_values_changed: every copy the SpMV plans keep is refreshed; without it
+ * mult may return the OLD matrix's product) and, for an Ilu0Preconditioner,
+ * spmvh_ilu0_refactor.  Both: error after release_csr ("released"). */
+int spmvh_matrix_local_values(spmvh_matrix* A, double** values,
+                              double** diagonal);
+int spmvh_matrix_plan_values_changed(spmvh_matrix* A);
 /* spmv_hip_csr_plan_get / _set on the local (remote = 0) or remote block's
  * plan: which form it took, what it cost, launch-shape knobs */
 int spmvh_matrix_plan_get(spmvh_matrix* A, int remote, const char* key,
@@ -465,6 +476,41 @@ int spmvh_pcg_sgs(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                   double rtol, int* num_its, double* rnorm_history,
                   spmvh_sgs_workspace* ws, int flags, double* spmv_ms_total,
                   int* spmv_launches);
+
+/* ---- Multicolour ILU(0) (spmv::Ilu0Preconditioner, host/cg.h) ----------------
+ * spmvh_ilu0_symbolic_*: host/ilu0_build.h, no device.  Input as
+ * spmvh_sgs_color; sizes[7] = {colours, entries of `before`, of `after`, sliced
+ * and long entries of `before`, sliced and long entries of `after`}.  _get: each
+ * output may be NULL; colors / perm / pos nrows entries, color_start colours + 1;
+ * per part ptr (nrows + 1, by position), cpos, src, slot, and the columns of the
+ * sliced layout (sliced_col, long_col).  A column twice in a row: "duplicate".
+ * spmvh_ilu0_create: spmv::Ilu0Preconditioner(exec, A); the handle is an
+ * spmvh_sgs and serves wherever one does (spmvh_sgs_info / _colors / _apply /
+ * _destroy, spmvh_pcg_sgs, spmvh_gmres).  The calls below need a handle made
+ * here ("not an Ilu0Preconditioner" otherwise).
+ * spmvh_ilu0_refactor: refactor(A) -- device only; errors "pivot", "released".
+ * spmvh_ilu0_info: info[6] = {entries of before, of after, negative pivots,
+ * plan bytes, the constructor's symbolic and numeric wall time in microseconds}.
+ * spmvh_ilu0_pattern / _factor: the host copies of cg.h (outputs may be NULL). */
+typedef struct spmvh_ilu0_symbolic spmvh_ilu0_symbolic;
+int spmvh_ilu0_symbolic_create(const int32_t* rowptr, const int32_t* colind,
+                               int64_t nrows, int64_t ncols_local, int symmetric,
+                               spmvh_ilu0_symbolic** sym, int64_t* sizes);
+int spmvh_ilu0_symbolic_get(spmvh_ilu0_symbolic* sym, int32_t* colors,
+                            int32_t* perm, int32_t* pos, int32_t* color_start,
+                            int64_t* before_ptr, int32_t* before_cpos,
+                            int32_t* before_src, int64_t* before_slot,
+                            int32_t* before_sliced_col, int32_t* before_long_col,
+                            int64_t* after_ptr, int32_t* after_cpos,
+                            int32_t* after_src, int64_t* after_slot,
+                            int32_t* after_sliced_col, int32_t* after_long_col);
+int spmvh_ilu0_symbolic_destroy(spmvh_ilu0_symbolic* sym);
+int spmvh_ilu0_create(spmvh_exec* exec, spmvh_matrix* A, spmvh_sgs** M);
+int spmvh_ilu0_refactor(spmvh_sgs* M, spmvh_matrix* A);
+int spmvh_ilu0_info(spmvh_sgs* M, int64_t* info);
+int spmvh_ilu0_pattern(spmvh_sgs* M, int64_t* before_ptr, int32_t* before_col,
+                       int64_t* after_ptr, int32_t* after_col);
+int spmvh_ilu0_factor(spmvh_sgs* M, double* l, double* u, double* d);
 
 /* ---- BiCGStab (spmv::bicgstab, host/cg.h; not in the reference) -------------
  * spmvh_bicgstab: BiCGStab from x0 = 0 for a matrix that need not be

@@ -201,6 +201,14 @@ _PROTOS = {
     "spmv_hip_mcgs_plan_destroy": ([vp], C.c_int),
     "spmv_hip_mcgs_plan_bytes": ([vp, P(i64)], C.c_int),
     "spmv_hip_mcgs_apply_f64": ([vp, vp, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_ilu0_plan_create": ([vp, vp, P(vp)], C.c_int),
+    "spmv_hip_ilu0_plan_destroy": ([vp], C.c_int),
+    "spmv_hip_ilu0_plan_bytes": ([vp, P(i64)], C.c_int),
+    "spmv_hip_ilu0_mcgs_plan": ([vp, P(vp)], C.c_int),
+    "spmv_hip_ilu0_factor": ([vp, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_ilu0_pivots": ([vp, vp, P(i64), P(i64), vp], C.c_int),
+    "spmv_hip_ilu0_get_pattern": ([vp, vp, vp, vp, vp, vp], C.c_int),
+    "spmv_hip_ilu0_get_factor": ([vp, vp, vp, vp, vp, vp], C.c_int),
     "spmv_hip_sgs_init_f64": ([vp, vp, i64, vp, vp, vp, vp], C.c_int),
     "spmv_hip_sgs_update_r_f64": ([vp, vp, C.c_int, i64, vp, vp, vp], C.c_int),
     "spmv_hip_sgs_dot_rz_f64": ([vp, vp, i64, vp, vp, vp], C.c_int),

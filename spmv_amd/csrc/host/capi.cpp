@@ -15,6 +15,7 @@
 #include "l2gmap.h"
 #include "matrix.h"
 #include "read_petsc.h"
+#include "ilu0_build.h"
 #include "sgs_build.h"
 
 using namespace spmv;
@@ -55,6 +56,9 @@ struct spmvh_sgs_workspace : WorkspaceHandle<SgsWorkspace> {};
 struct spmvh_gmres_workspace : WorkspaceHandle<GmresWorkspace> {};
 struct spmvh_sgs_build {
   SgsHostPlan plan;
+};
+struct spmvh_ilu0_symbolic {
+  Ilu0Symbolic sym;
 };
 struct spmvh_sgs {
   std::shared_ptr<HipExecutor> exec; // keeps the executor alive
@@ -543,6 +547,30 @@ int spmvh_matrix_blocks(spmvh_matrix* A, int64_t out[6])
       out[4] = r->cols();
       out[5] = r->non_zeros();
     }
+  });
+}
+
+int spmvh_matrix_local_values(spmvh_matrix* A, double** values,
+                              double** diagonal)
+{
+  return guarded([&] {
+    require(A && values && diagonal, "NULL argument");
+    const auto* blk = dynamic_cast<const CSRMatrix<double>*>(A->A->local_block());
+    require(blk != nullptr, "the matrix has no local block");
+    if (blk->csr_released())
+      throw std::runtime_error(
+          "spmvh_matrix_local_values - Error: the CSR arrays of this matrix "
+          "were released (release_csr)");
+    *values = const_cast<double*>(blk->values());
+    *diagonal = const_cast<double*>(blk->diagonal());
+  });
+}
+
+int spmvh_matrix_plan_values_changed(spmvh_matrix* A)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    A->A->plan_values_changed();
   });
 }
 
@@ -1416,6 +1444,125 @@ int spmvh_sgs_apply(spmvh_exec* exec, spmvh_sgs* M, const double* r, double* z)
     require(exec && M, "NULL argument");
     sgs_apply(*exec->hip, *M->M, r, z);
   });
+}
+
+// ---- Multicolour ILU(0) --------------------------------------------------------------
+int spmvh_ilu0_symbolic_create(const int32_t* rowptr, const int32_t* colind,
+                               int64_t nrows, int64_t ncols_local, int symmetric,
+                               spmvh_ilu0_symbolic** sym, int64_t* sizes)
+{
+  return guarded([&] {
+    require(sym && sizes, "NULL argument");
+    auto s = std::make_unique<spmvh_ilu0_symbolic>();
+    s->sym = ilu0_symbolic(rowptr, colind, nrows, ncols_local, symmetric != 0);
+    const Ilu0Symbolic& y = s->sym;
+    sizes[0] = y.num_colors;
+    sizes[1] = (int64_t)y.before.cpos.size();
+    sizes[2] = (int64_t)y.after.cpos.size();
+    sizes[3] = (int64_t)y.sliced_before.col.size();
+    sizes[4] = (int64_t)y.sliced_before.long_col.size();
+    sizes[5] = (int64_t)y.sliced_after.col.size();
+    sizes[6] = (int64_t)y.sliced_after.long_col.size();
+    *sym = s.release();
+  });
+}
+
+int spmvh_ilu0_symbolic_get(spmvh_ilu0_symbolic* sym, int32_t* colors,
+                            int32_t* perm, int32_t* pos, int32_t* color_start,
+                            int64_t* before_ptr, int32_t* before_cpos,
+                            int32_t* before_src, int64_t* before_slot,
+                            int32_t* before_sliced_col, int32_t* before_long_col,
+                            int64_t* after_ptr, int32_t* after_cpos,
+                            int32_t* after_src, int64_t* after_slot,
+                            int32_t* after_sliced_col, int32_t* after_long_col)
+{
+  return guarded([&] {
+    require(sym != nullptr, "NULL argument");
+    auto out = [](const auto& v, auto* dst) {
+      if (dst)
+        std::copy(v.begin(), v.end(), dst);
+    };
+    const Ilu0Symbolic& y = sym->sym;
+    out(y.colors, colors);
+    out(y.perm, perm);
+    out(y.pos, pos);
+    out(y.color_start, color_start);
+    out(y.before.ptr, before_ptr);
+    out(y.before.cpos, before_cpos);
+    out(y.before.src, before_src);
+    out(y.before.slot, before_slot);
+    out(y.sliced_before.col, before_sliced_col);
+    out(y.sliced_before.long_col, before_long_col);
+    out(y.after.ptr, after_ptr);
+    out(y.after.cpos, after_cpos);
+    out(y.after.src, after_src);
+    out(y.after.slot, after_slot);
+    out(y.sliced_after.col, after_sliced_col);
+    out(y.sliced_after.long_col, after_long_col);
+  });
+}
+
+int spmvh_ilu0_symbolic_destroy(spmvh_ilu0_symbolic* sym)
+{
+  return guarded([&] { delete sym; });
+}
+
+int spmvh_ilu0_create(spmvh_exec* exec, spmvh_matrix* A, spmvh_sgs** M)
+{
+  return guarded([&] {
+    require(exec && A && M, "NULL argument");
+    require(exec->hip != nullptr, "not a HipExecutor");
+    auto m = std::make_unique<spmvh_sgs>();
+    m->exec = exec->hip;
+    m->M.reset(new Ilu0Preconditioner(*exec->hip, *A->A));
+    *M = m.release();
+  });
+}
+
+namespace
+{
+Ilu0Preconditioner& ilu0_of(spmvh_sgs* M)
+{
+  require(M != nullptr, "NULL argument");
+  auto* ilu = dynamic_cast<Ilu0Preconditioner*>(M->M.get());
+  require(ilu != nullptr, "not an Ilu0Preconditioner");
+  return *ilu;
+}
+} // namespace
+
+int spmvh_ilu0_refactor(spmvh_sgs* M, spmvh_matrix* A)
+{
+  return guarded([&] {
+    require(A != nullptr, "NULL argument");
+    ilu0_of(M).refactor(*A->A);
+  });
+}
+
+int spmvh_ilu0_info(spmvh_sgs* M, int64_t* info)
+{
+  return guarded([&] {
+    require(info != nullptr, "NULL argument");
+    const Ilu0Preconditioner& ilu = ilu0_of(M);
+    info[0] = ilu.before_entries();
+    info[1] = ilu.after_entries();
+    info[2] = ilu.negative_pivots();
+    info[3] = ilu.plan_bytes();
+    info[4] = (int64_t)(ilu.symbolic_ms() * 1000.0);
+    info[5] = (int64_t)(ilu.numeric_ms() * 1000.0);
+  });
+}
+
+int spmvh_ilu0_pattern(spmvh_sgs* M, int64_t* before_ptr, int32_t* before_col,
+                       int64_t* after_ptr, int32_t* after_col)
+{
+  return guarded([&] {
+    ilu0_of(M).pattern(before_ptr, before_col, after_ptr, after_col);
+  });
+}
+
+int spmvh_ilu0_factor(spmvh_sgs* M, double* l, double* u, double* d)
+{
+  return guarded([&] { ilu0_of(M).factor(l, u, d); });
 }
 
 int spmvh_sgs_workspace_create(spmvh_exec* exec, spmvh_sgs_workspace** ws)

@@ -18,6 +18,7 @@ struct spmv_hip_pcg_ws;
 struct spmv_hip_bicg_ws;
 struct spmv_hip_gmres_ws;
 struct spmv_hip_mcgs_plan;
+struct spmv_hip_ilu0_plan;
 
 namespace spmv
 {
@@ -482,28 +483,136 @@ class SgsPreconditioner
 {
 public:
   SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A);
-  ~SgsPreconditioner();
+  virtual ~SgsPreconditioner();
   SgsPreconditioner(const SgsPreconditioner&) = delete;
   SgsPreconditioner& operator=(const SgsPreconditioner&) = delete;
 
   int rows() const { return (int)_colors.size(); }
   int num_colors() const { return _num_colors; }
-  void colors(int32_t* out) const; // host copy, rows() entries
-  int64_t plan_bytes() const;      // device memory of the plan
-  spmv_hip_mcgs_plan* plan() const { return _plan; }
+  void colors(int32_t* out) const;    // host copy, rows() entries
+  virtual int64_t plan_bytes() const; // device memory of the plan
+  // the plan the sweeps run on (a derived class may refuse: check_usable)
+  spmv_hip_mcgs_plan* plan() const
+  {
+    check_usable();
+    return _plan;
+  }
+  // pivots of the factor that are negative: 0 here, Ilu0Preconditioner counts
+  virtual int64_t negative_pivots() const { return 0; }
 
-private:
+protected:
+  // An object whose plan the derived class builds, owns and adopts (adopt());
+  // this class then neither creates nor destroys one.
+  explicit SgsPreconditioner(HipExecutor& exec) : _exec(exec), _owns_plan(false) {}
+  void adopt(spmv_hip_mcgs_plan* plan, int num_colors,
+             std::vector<int32_t> colors);
+  // called by plan(): throws when the plan must not be used now
+  virtual void check_usable() const {}
+
   HipExecutor& _exec;
   spmv_hip_mcgs_plan* _plan = nullptr;
+  bool _owns_plan = true;
   int _num_colors = 0;
   std::vector<int32_t> _colors;
 };
+
+// ---- Multicolour ILU(0), factored on the device ---------------------------------
+// M = (D~ + L~) D~^-1 (D~ + U~) on the local diagonal block (as above: block-
+// Jacobi over the ranks, no halo exchange), the incomplete LU factorisation
+// without fill in the colour-major ordering; for a symmetric matrix the same
+// factor is IC(0) in the form L D L^T.  Colouring, positions and d_i are
+// SgsPreconditioner's; pos(j) is the position of row j.
+//
+//   before(i)  the off-diagonal entries of row i whose column's colour is
+//              smaller than colour(i); after(i): larger.  Each ascending by
+//              pos(column) -- NOT by column: the elimination needs position
+//              order, and the sweeps of this plan add in it.  A column that
+//              occurs twice in one row of the block is refused
+//              (std::runtime_error, "duplicate").
+//   factor     rows in position order (rows of one colour never read each other):
+//                w = copy of row i (before, diagonal, after)
+//                for k in before(i), ascending pos(k):
+//                  m = w[k] * dinv~[k]
+//                  for (j, u) in after~(k), in its order:
+//                    if j == i or j is in the pattern of row i:
+//                      w[j] = w[j] - m * u
+//                l~(i, .) = w on before(i); u~(i, .) = w on after(i)
+//                d~_i = w[i]; dinv~_i = 1.0 / d~_i
+//              Every product, difference and quotient is one rounding; fill
+//              outside the pattern is dropped.
+//   apply      sgs_apply's two sweeps with l~, u~ and dinv~: sgs_apply, pcg_sgs
+//              and GmresPreconditioner::sgs take the object as it is.
+//
+// The constructor reads the block's PATTERN back and does the symbolic work on
+// the host (host/ilu0_build.h); the numbers never leave the device: a gather
+// from the matrix's values, one launch per colour 1 .. C-1 (a wavefront per
+// row), a scatter into the sweep plan (spmv_ilu0.hip).  refactor(A) repeats
+// only that, for a matrix with the SAME pattern and storage whose values have
+// changed (time stepping, Newton; Matrix::plan_values_changed does the same for
+// the SpMV plans' copies): no read-back, no host pass.  The one wait of
+// a factorisation is the read of two counts:
+//   pivots d~ that are not finite or zero: the call throws ("pivot"); after a
+//     failed refactor the object is not usable (plan() throws "pivot") until a
+//     later refactor succeeds;
+//   pivots that are finite and negative: negative_pivots().  pcg_sgs refuses
+//     such a preconditioner ("pivot"): it is not positive definite; gmres takes
+//     it.
+// The constructor and refactor throw on a matrix that has released its CSR
+// arrays ("released"); release_csr() afterwards is fine until the next
+// refactor.  refactor checks rows, storage and the number of stored entries;
+// that the pattern is the same is the caller's promise.
+class Ilu0Preconditioner : public SgsPreconditioner
+{
+public:
+  Ilu0Preconditioner(HipExecutor& exec, const Matrix<double>& A);
+  ~Ilu0Preconditioner() override;
+
+  void refactor(const Matrix<double>& A);
+  int64_t negative_pivots() const override { return _negative; }
+  // the sweep plan, the working copy of the factor, the maps, the diagonal
+  int64_t plan_bytes() const override;
+
+  // host copies (they wait for the device).  The parts are CSR over positions
+  // (row perm[pos], colour-major, natural order within a colour); a NULL
+  // output is skipped.
+  int64_t before_entries() const { return _nbefore; }
+  int64_t after_entries() const { return _nafter; }
+  // ptr: rows() + 1 entries; col: the entries' columns (rows' numbers)
+  void pattern(int64_t* before_ptr, int32_t* before_col, int64_t* after_ptr,
+               int32_t* after_col) const;
+  // l~ and u~ in the order of pattern(), d~ by POSITION
+  void factor(double* l, double* u, double* d) const;
+
+  // wall time of the constructor's two halves, for measurements
+  double symbolic_ms() const { return _symbolic_ms; }
+  double numeric_ms() const { return _numeric_ms; }
+
+protected:
+  // throws ("pivot") while the last factorisation left no usable factor
+  void check_usable() const override;
+
+private:
+  void numeric(const Matrix<double>& A);
+  bool _usable = true;
+
+  spmv_hip_ilu0_plan* _ilu = nullptr;
+  double* _diag = nullptr; // general storage: Matrix::diagonal's output
+  int64_t _nbefore = 0, _nafter = 0, _num_values = 0, _negative = 0;
+  bool _symmetric = false;
+  double _symbolic_ms = 0, _numeric_ms = 0;
+};
+
 
 // z = M^-1 r.  `r`, `z`: DEVICE vectors of rows() doubles, any alignment, not
 // overlapping ("overlaps").  Runs on the executor's current stream; the host
 // does not wait.
 void sgs_apply(HipExecutor& exec, const SgsPreconditioner& M, const double* r,
                double* z);
+inline void ilu0_apply(HipExecutor& exec, const Ilu0Preconditioner& M,
+                       const double* r, double* z)
+{
+  sgs_apply(exec, M, r, z);
+}
 
 // Work vectors + device scalars of pcg_sgs(), kept across calls like
 // ChebyshevWorkspace; the device scalars and their reducers are pcg()'s.
@@ -548,7 +657,10 @@ public:
 // launches; beside the SpMV and the sweeps 3 + 2 + 5 = 10 vector passes.  With
 // several ranks: one all-reduce of 1 double (p.Ap) and ONE of 2 doubles
 // ({rz[k], rr[k]}).  M must have been built from A (or from a matrix with A's
-// rows on this rank): M.rows() != A's rows throws.
+// rows on this rank): M.rows() != A's rows throws.  M may be an
+// Ilu0Preconditioner (IC(0) in the form L D L^T for a symmetric A): the same
+// sweeps on its factor; one with negative_pivots() > 0 is not positive definite
+// and is refused (std::runtime_error, "pivot").
 //
 // As in pcg_chebyshev(): the stopping test is cg()'s; rnorm_history receives
 // ||r_0||, ..., ||r_k||; a system with r_0 . r_0 == 0 stops at k = 0 with x = 0;

@@ -311,6 +311,28 @@ size_t CSRMatrix<T>::release_csr() const
 }
 
 template <typename T>
+void CSRMatrix<T>::values_changed() const
+{
+  if (_released)
+    throw std::runtime_error(
+        "CSRMatrix::values_changed: the CSR arrays were released (release_csr); "
+        "there are no values to rewrite");
+  auto* hip = dynamic_cast<const HipExecutor*>(this->_exec.get());
+  if (!hip || this->_num_non_zeros == 0 || !_op.plan())
+    return;
+  if constexpr (std::is_same<T, double>::value) {
+    if (_values32)
+      throw_on_error(spmv_hip_convert_f64_f32(hip->context(),
+                                              this->_num_non_zeros, _values,
+                                              _values32, nullptr),
+                     "spmv_hip_convert_f64_f32");
+  }
+  throw_on_error(spmv_hip_csr_plan_values_changed(hip->context(), _op.plan(),
+                                                  nullptr),
+                 "spmv_hip_csr_plan_values_changed");
+}
+
+template <typename T>
 void CSRMatrix<T>::enable_mixed() const
 {
   if (_released)

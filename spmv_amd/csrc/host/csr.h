@@ -187,6 +187,16 @@ public:
   size_t release_csr() const;
   bool csr_released() const { return _released; }
 
+  // The caller has REWRITTEN values() (and diagonal()) in place on the device,
+  // on the same sparsity: refreshes every copy made of them -- the plan's baked
+  // forms (spmv_hip_csr_plan_values_changed) and the fp32 copy of
+  // enable_mixed() -- in the order of the executor's current stream; mult()
+  // then returns the new matrix's product.  Throws after release_csr(): the
+  // arrays that would have been rewritten are gone.  A no-op where nothing
+  // keeps a copy: an empty block, a block without a plan, a block on an
+  // executor that is not a HipExecutor.
+  void values_changed() const;
+
   // out[j - col_begin] = alpha (A^T in)_j + beta out[j - col_begin] for the
   // columns j in [col_begin, col_end) (spmv_hip_csr_spmvt_*): `in` holds
   // rows() entries.  General blocks; the transposed map is built on first use

@@ -1,0 +1,220 @@
+// spmv::Ilu0Preconditioner for HipExecutor: see cg.h.  The symbolic half is
+// ilu0_build.h's, on the host; the numeric half is spmv_ilu0.hip's, on the
+// device, on the executor's current stream:
+//     Matrix::diagonal (general storage; symmetric storage has the array)
+//     gather ; C - 1 factor launches ; finish ; scatter
+//     read of the two pivot counts (the one wait)
+#include "cg.h"
+
+#include <chrono>
+#include <string>
+#include <utility>
+
+#include "ilu0_build.h"
+#include "solver_common.h"
+
+namespace spmv
+{
+using namespace detail;
+
+namespace
+{
+
+const CSRMatrix<double>* block_of(const Matrix<double>& A, const char* who)
+{
+  std::shared_ptr<L2GMap> row_map = A.row_map();
+  std::shared_ptr<const L2GMap> col_map = A.col_map();
+  if (row_map->num_ghosts() > 0
+      || row_map->local_size() != col_map->local_size()
+      || row_map->global_offset() != col_map->global_offset())
+    throw std::runtime_error(
+        std::string("spmv::Ilu0Preconditioner") + who
+        + " - Error: rows and owned columns are not the same index range on "
+          "this rank");
+  const auto* blk = dynamic_cast<const CSRMatrix<double>*>(A.local_block());
+  if (!blk)
+    throw std::runtime_error(std::string("spmv::Ilu0Preconditioner") + who
+                             + " - Error: the matrix has no local block");
+  if (blk->csr_released())
+    throw std::runtime_error(
+        std::string("spmv::Ilu0Preconditioner") + who
+        + " - Error: the CSR arrays of this matrix were released "
+          "(release_csr); the factorisation reads its values");
+  return blk;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0)
+{
+  return std::chrono::duration<double, std::milli>(
+             std::chrono::steady_clock::now() - t0)
+      .count();
+}
+
+} // namespace
+
+Ilu0Preconditioner::Ilu0Preconditioner(HipExecutor& exec, const Matrix<double>& A)
+    : SgsPreconditioner(exec)
+{
+  const CSRMatrix<double>* blk = block_of(A, "");
+  const auto t0 = std::chrono::steady_clock::now();
+  const int64_t n = A.row_map()->local_size();
+  const int64_t nnz = blk->non_zeros();
+  _symmetric = A.symmetric();
+  _num_values = nnz;
+
+  // the pattern, read back (the copies wait for the device); no values
+  const DeviceExecutor& host = exec.get_host();
+  std::vector<int32_t> rowptr((size_t)n + 1, 0), colind((size_t)nnz);
+  if (nnz > 0) { // (an empty block owns no arrays)
+    exec.copy_to<int32_t>(rowptr.data(), host, blk->rowptr(), (size_t)n + 1);
+    exec.copy_to<int32_t>(colind.data(), host, blk->colind(), (size_t)nnz);
+  }
+  Ilu0Symbolic sym = ilu0_symbolic(rowptr.data(), colind.data(), n, n, _symmetric);
+  std::vector<int32_t>().swap(colind);
+  _nbefore = (int64_t)sym.before.cpos.size();
+  _nafter = (int64_t)sym.after.cpos.size();
+
+  auto sliced_of = [](const SgsSlicedPart& s) {
+    return spmv_hip_mcgs_part{s.color_slice.data(), s.slice_pos0.data(),
+                              s.slice_ptr.data(),   s.len.data(),
+                              s.col.data(),         s.val.data(),
+                              s.color_long.data(),  s.long_pos.data(),
+                              s.long_ptr.data(),    s.long_col.data(),
+                              s.long_val.data()};
+  };
+  auto part_of = [](const Ilu0Part& p) {
+    return spmv_hip_ilu0_part{p.ptr.data(), p.cpos.data(), p.src.data(),
+                              p.slot.data()};
+  };
+  const std::vector<double> no_dinv((size_t)n, 0.0); // the factorisation's to write
+  spmv_hip_ilu0_host in{};
+  in.mcgs.num_rows = sym.n;
+  in.mcgs.num_colors = sym.num_colors;
+  in.mcgs.perm = sym.perm.data();
+  in.mcgs.color_start = sym.color_start.data();
+  in.mcgs.dinv = no_dinv.data();
+  in.mcgs.before = sliced_of(sym.sliced_before);
+  in.mcgs.after = sliced_of(sym.sliced_after);
+  in.num_values = nnz;
+  in.before = part_of(sym.before);
+  in.after = part_of(sym.after);
+  throw_on_error(spmv_hip_ilu0_plan_create(exec.context(), &in, &_ilu),
+                 "spmv_hip_ilu0_plan_create");
+  spmv_hip_mcgs_plan* inner = nullptr;
+  spmv_hip_ilu0_mcgs_plan(_ilu, &inner);
+  adopt(inner, sym.num_colors, std::move(sym.colors));
+  _symbolic_ms = ms_since(t0);
+
+  const auto t1 = std::chrono::steady_clock::now();
+  try {
+    if (!_symmetric && n > 0)
+      _diag = exec.alloc<double>((size_t)n);
+    numeric(A);
+  } catch (...) {
+    if (_diag)
+      exec.free(_diag);
+    spmv_hip_ilu0_plan_destroy(_ilu);
+    throw;
+  }
+  _numeric_ms = ms_since(t1);
+}
+
+Ilu0Preconditioner::~Ilu0Preconditioner()
+{
+  try {
+    if (_ilu) // a sweep may still be in flight
+      _exec.synchronize();
+  } catch (...) {
+  }
+  _plan = nullptr; // the inner plan goes with its owner
+  spmv_hip_ilu0_plan_destroy(_ilu);
+  try {
+    if (_diag)
+      _exec.free(_diag);
+  } catch (...) {
+  }
+}
+
+void Ilu0Preconditioner::check_usable() const
+{
+  if (!_usable)
+    throw std::runtime_error(
+        "spmv::Ilu0Preconditioner - Error: the last factorisation met a pivot "
+        "that is zero or not finite; refactor before using it");
+}
+
+void Ilu0Preconditioner::numeric(const Matrix<double>& A)
+{
+  const auto* blk = static_cast<const CSRMatrix<double>*>(A.local_block());
+  const double* diagonal = blk->diagonal();
+  if (!_symmetric && rows() > 0) {
+    A.diagonal(_diag);
+    diagonal = _diag;
+  }
+  _usable = false;
+  _negative = 0;
+  spmv_hip_ctx* ctx = _exec.context();
+  throw_on_error(spmv_hip_ilu0_factor(ctx, _ilu, blk->values(), diagonal, nullptr),
+                 "spmv_hip_ilu0_factor");
+  int64_t bad = 0, negative = 0;
+  throw_on_error(spmv_hip_ilu0_pivots(ctx, _ilu, &bad, &negative, nullptr),
+                 "spmv_hip_ilu0_pivots");
+  if (bad != 0)
+    throw std::runtime_error(
+        "spmv::Ilu0Preconditioner - Error: " + std::to_string(bad) + " of "
+        + std::to_string(rows()) + " pivot(s) are zero or not finite");
+  _negative = negative;
+  _usable = true;
+}
+
+void Ilu0Preconditioner::refactor(const Matrix<double>& A)
+{
+  const CSRMatrix<double>* blk = block_of(A, "::refactor");
+  if (A.row_map()->local_size() != rows() || A.symmetric() != _symmetric
+      || blk->non_zeros() != _num_values)
+    throw std::runtime_error(
+        "spmv::Ilu0Preconditioner::refactor - Error: not the pattern this "
+        "object was built for (rows, storage or number of stored entries "
+        "differ)");
+  numeric(A);
+}
+
+int64_t Ilu0Preconditioner::plan_bytes() const
+{
+  int64_t bytes = 0;
+  throw_on_error(spmv_hip_ilu0_plan_bytes(_ilu, &bytes),
+                 "spmv_hip_ilu0_plan_bytes");
+  return bytes + (_diag ? (int64_t)rows() * 8 : 0);
+}
+
+void Ilu0Preconditioner::pattern(int64_t* before_ptr, int32_t* before_col,
+                                 int64_t* after_ptr, int32_t* after_col) const
+{
+  throw_on_error(spmv_hip_ilu0_get_pattern(_exec.context(), _ilu, before_ptr,
+                                           before_col, after_ptr, after_col),
+                 "spmv_hip_ilu0_get_pattern");
+  // positions -> rows: perm, the stable counting sort of the colours
+  const int32_t n = rows();
+  std::vector<int32_t> next((size_t)_num_colors + 1, 0), perm((size_t)n);
+  for (int32_t i = 0; i < n; ++i)
+    ++next[(size_t)_colors[i] + 1];
+  for (int c = 0; c < _num_colors; ++c)
+    next[(size_t)c + 1] += next[c];
+  for (int32_t i = 0; i < n; ++i)
+    perm[(size_t)next[_colors[i]]++] = i;
+  if (before_col)
+    for (int64_t e = 0; e < _nbefore; ++e)
+      before_col[e] = perm[(size_t)before_col[e]];
+  if (after_col)
+    for (int64_t e = 0; e < _nafter; ++e)
+      after_col[e] = perm[(size_t)after_col[e]];
+}
+
+void Ilu0Preconditioner::factor(double* l, double* u, double* d) const
+{
+  throw_on_error(
+      spmv_hip_ilu0_get_factor(_exec.context(), _ilu, l, u, d, nullptr),
+      "spmv_hip_ilu0_get_factor");
+}
+
+} // namespace spmv

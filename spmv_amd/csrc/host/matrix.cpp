@@ -216,6 +216,15 @@ void Matrix<T>::transpmult(T* b, T* y) const
 // diagonal (see matrix.h)
 // ---------------------------------------------------------------------------
 template <typename T>
+void Matrix<T>::plan_values_changed() const
+{
+  if (_mat_local)
+    _mat_local->values_changed();
+  if (_mat_remote)
+    _mat_remote->values_changed();
+}
+
+template <typename T>
 void Matrix<T>::diagonal(T* d) const
 {
   if (_row_map->num_ghosts() > 0

@@ -110,6 +110,14 @@ public:
   //               allocation and stays until the matrix is destroyed
   void diagonal(T* d) const;
 
+  // The caller has rewritten the blocks' device value arrays (and the
+  // diagonal array of symmetric storage) in place, on the same sparsity -- new
+  // coefficients of a time step or a Newton step: CSRMatrix::values_changed on
+  // the local and the remote block, so that mult() and its kin return the new
+  // matrix's product whatever form the plans keep.  Throws after
+  // release_csr().  An Ilu0Preconditioner is refreshed by its refactor().
+  void plan_values_changed() const;
+
   std::shared_ptr<L2GMap> row_map() const { return _row_map; }
   std::shared_ptr<const L2GMap> col_map() const { return _col_map; }
 

@@ -594,7 +594,16 @@ SgsPreconditioner::~SgsPreconditioner()
       _exec.synchronize();
   } catch (...) {
   }
-  spmv_hip_mcgs_plan_destroy(_plan);
+  if (_owns_plan)
+    spmv_hip_mcgs_plan_destroy(_plan);
+}
+
+void SgsPreconditioner::adopt(spmv_hip_mcgs_plan* plan, int num_colors,
+                              std::vector<int32_t> colors)
+{
+  _plan = plan;
+  _num_colors = num_colors;
+  _colors = std::move(colors);
 }
 
 void SgsPreconditioner::colors(int32_t* out) const
@@ -607,7 +616,7 @@ void SgsPreconditioner::colors(int32_t* out) const
 int64_t SgsPreconditioner::plan_bytes() const
 {
   int64_t bytes = 0;
-  throw_on_error(spmv_hip_mcgs_plan_bytes(_plan, &bytes),
+  throw_on_error(spmv_hip_mcgs_plan_bytes(plan(), &bytes),
                  "spmv_hip_mcgs_plan_bytes");
   return bytes;
 }
@@ -665,6 +674,11 @@ int pcg_sgs(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
         "spmv::pcg_sgs - Error: the preconditioner was built for "
         + std::to_string(Mpre.rows()) + " rows, the matrix has "
         + std::to_string(M));
+  if (Mpre.negative_pivots() > 0)
+    throw std::runtime_error(
+        "spmv::pcg_sgs - Error: the preconditioner has "
+        + std::to_string(Mpre.negative_pivots())
+        + " negative pivot(s): it is not positive definite");
   // x is the iterate from the first kernel on: it cannot share b
   if (ranges_overlap(x, b, M))
     throw std::runtime_error("pcg_sgs: x overlaps b (x is updated in place)");

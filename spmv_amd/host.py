@@ -155,6 +155,16 @@ _PROTOS = {
     "spmvh_sgs_info": [vp, PTR(C.c_int), PTR(C.c_int), PTR(i64)],
     "spmvh_sgs_colors": [vp, vp],
     "spmvh_sgs_apply": [vp, vp, vp, vp],
+    "spmvh_matrix_local_values": [vp, PTR(vp), PTR(vp)],
+    "spmvh_matrix_plan_values_changed": [vp],
+    "spmvh_ilu0_symbolic_create": [vp, vp, i64, i64, C.c_int, PTR(vp), vp],
+    "spmvh_ilu0_symbolic_get": [vp] * 17,
+    "spmvh_ilu0_symbolic_destroy": [vp],
+    "spmvh_ilu0_create": [vp, vp, PTR(vp)],
+    "spmvh_ilu0_refactor": [vp, vp],
+    "spmvh_ilu0_info": [vp, vp],
+    "spmvh_ilu0_pattern": [vp, vp, vp, vp, vp],
+    "spmvh_ilu0_factor": [vp, vp, vp, vp],
     "spmvh_sgs_workspace_create": [vp, PTR(vp)],
     "spmvh_sgs_workspace_destroy": [vp],
     "spmvh_sgs_workspace_reserve_timing": [vp, C.c_int],
@@ -558,6 +568,21 @@ class Matrix:
         out = (i64 * 6)()
         call("spmvh_matrix_blocks", self.h, out)
         return dict(local=tuple(out[0:3]), remote=tuple(out[3:6]))
+
+    def local_values(self):
+        """-> (values_ptr, diagonal_ptr): device addresses of the local block's
+        value array (blocks()["local"][2] doubles) and of its diagonal array
+        (symmetric storage; None otherwise), for rewriting the coefficients in
+        place on a fixed pattern; call plan_values_changed() afterwards (and
+        Ilu0Preconditioner.refactor)"""
+        v, d = vp(), vp()
+        call("spmvh_matrix_local_values", self.h, C.byref(v), C.byref(d))
+        return v.value, d.value
+
+    def plan_values_changed(self):
+        """Matrix::plan_values_changed: the arrays of local_values() were
+        rewritten in place; every copy the SpMV plans keep is refreshed"""
+        call("spmvh_matrix_plan_values_changed", self.h)
 
     def col_map(self):
         return ColMapView(self)
@@ -1029,6 +1054,99 @@ def sgs_apply(exec_, M, r_ptr, z_ptr):
     """spmv::sgs_apply: z = M^-1 r on the executor's current stream; the host
     does not wait."""
     call("spmvh_sgs_apply", exec_.h, M.h, r_ptr, z_ptr)
+
+
+def ilu0_symbolic(rowptr, colind, nrows, ncols_local=None, symmetric=False):
+    """spmv::ilu0_symbolic: the colouring, the positions and the two parts in
+    POSITION order -> dict(colors, num_colors, perm, pos, color_start, before,
+    after); a part is dict(ptr, cpos, src, slot, sliced_col, long_col), CSR over
+    positions (host/ilu0_build.h).  Host only.  Raises SpmvHostError
+    ("duplicate")."""
+    rp = np.ascontiguousarray(rowptr, np.int32)
+    ci = np.ascontiguousarray(colind, np.int32)
+    n = int(nrows)
+    h = vp()
+    sizes = np.zeros(7, np.int64)
+    call("spmvh_ilu0_symbolic_create", _np_ptr(rp), _np_ptr(ci), n,
+         n if ncols_local is None else int(ncols_local), int(bool(symmetric)),
+         C.byref(h), _np_ptr(sizes))
+    try:
+        nc = int(sizes[0])
+        colors, perm, pos = (np.zeros(n, np.int32) for _ in range(3))
+        start = np.zeros(nc + 1, np.int32)
+        parts = []
+        for m, ns, nl in ((sizes[1], sizes[3], sizes[4]),
+                          (sizes[2], sizes[5], sizes[6])):
+            parts.append(dict(ptr=np.zeros(n + 1, np.int64),
+                              cpos=np.zeros(int(m), np.int32),
+                              src=np.zeros(int(m), np.int32),
+                              slot=np.zeros(int(m), np.int64),
+                              sliced_col=np.zeros(int(ns), np.int32),
+                              long_col=np.zeros(int(nl), np.int32)))
+        call("spmvh_ilu0_symbolic_get", h, _np_ptr(colors), _np_ptr(perm),
+             _np_ptr(pos), _np_ptr(start),
+             *[_np_ptr(a) for p in parts for a in p.values()])
+    finally:
+        call("spmvh_ilu0_symbolic_destroy", h)
+    return dict(colors=colors, num_colors=nc, perm=perm, pos=pos,
+                color_start=start, before=parts[0], after=parts[1])
+
+
+class Ilu0Preconditioner(SgsPreconditioner):
+    """spmv::Ilu0Preconditioner: multicolour ILU(0) of A's local diagonal block,
+    factored on the device (IC(0) as L D L^T for a symmetric A).  Accepted
+    wherever an SgsPreconditioner is (sgs_apply, pcg_sgs, gmres(sgs=...)).
+    Raises SpmvHostError ("pivot", "duplicate", "released", "same index
+    range")."""
+
+    def __init__(self, exec_, A):
+        h = vp()
+        call("spmvh_ilu0_create", exec_.h, A.h, C.byref(h))
+        self.h = h
+
+    def refactor(self, A):
+        """the numeric factorisation again, on the device alone, for a matrix
+        of the same pattern whose values have changed"""
+        call("spmvh_ilu0_refactor", self.h, A.h)
+
+    def _ilu_info(self):
+        info = np.zeros(6, np.int64)
+        call("spmvh_ilu0_info", self.h, _np_ptr(info))
+        return [int(v) for v in info]
+
+    def negative_pivots(self):
+        return self._ilu_info()[2]
+
+    def plan_bytes(self):
+        return self._ilu_info()[3]
+
+    def setup_ms(self):
+        """-> (host symbolic, device numeric) wall time of the constructor"""
+        info = self._ilu_info()
+        return info[4] / 1000.0, info[5] / 1000.0
+
+    def pattern(self):
+        """-> ((before_ptr, before_col), (after_ptr, after_col)): CSR over
+        colour-major positions, the entries ascending by the position of their
+        column"""
+        n, info = self.rows(), self._ilu_info()
+        out = [(np.zeros(n + 1, np.int64), np.zeros(m, np.int32))
+               for m in info[:2]]
+        call("spmvh_ilu0_pattern", self.h, *[_np_ptr(a) for p in out for a in p])
+        return out[0], out[1]
+
+    def factor(self):
+        """-> (l, u, d): the factor's entries in the order of pattern(), the
+        pivots d by position"""
+        n, info = self.rows(), self._ilu_info()
+        l, u, d = np.zeros(info[0]), np.zeros(info[1]), np.zeros(n)
+        call("spmvh_ilu0_factor", self.h, _np_ptr(l), _np_ptr(u), _np_ptr(d))
+        return l, u, d
+
+
+def ilu0_apply(exec_, M, r_ptr, z_ptr):
+    """spmv::ilu0_apply = sgs_apply on the factor"""
+    sgs_apply(exec_, M, r_ptr, z_ptr)
 
 
 class SgsWorkspace(_TimedWorkspace):
