@@ -220,12 +220,47 @@ int cg_block(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
              const CgOptions* options = nullptr, CgStats* stats = nullptr,
              CgBlockWorkspace* workspace = nullptr);
 
-// Work vectors + device scalars of pcg(), kept across calls like CgWorkspace;
-// it regrows itself when a call needs more rows or more iterations.
-class PcgWorkspace : public SolverWorkspace
+// What the workspaces of pcg(), pcg_chebyshev() and pcg_sgs() share: the device
+// scalars (spmv_hip_pcg_ws) and the vectors every one of them has.  A derived
+// class adds its own vectors and their capacities.
+class PcgFamilyWorkspace : public SolverWorkspace
 {
 public:
-  explicit PcgWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
+  // events for CgOptions::time_spmv of a solve with up to `spmvs` timed SpMVs
+  // (pcg_chebyshev: iterations * degree, else iterations), created ahead of it
+  void reserve_timing(int spmvs)
+  {
+    reserve_events(2 * (size_t)std::max(spmvs, 0));
+  }
+
+  spmv_hip_pcg_ws* ws = nullptr;
+  int kmax_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, x_cap = -1;
+  double *r = nullptr, *Ap = nullptr; // m_cap
+  double* x = nullptr;    // x_cap: the iterate when the caller's x is unaligned
+  double* p = nullptr;    // n_cap: padded, the ghost tail is zeroed by every solve
+  double* dot2 = nullptr; // partials of the remote block's p.Ap share
+  // flags: {done, kstop}; timing_ev: 2 events per timed SpMV
+
+protected:
+  explicit PcgFamilyWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
+  ~PcgFamilyWorkspace() = default;
+  // The head of every ensure(): the stream and flags, dot2, the scalars for
+  // kmax iterations, the vectors of M doubles (`m_vecs`: r, Ap and the class's
+  // own) and, if need_x, x.  The class's ensure() goes on with its dinv copy
+  // and the padded vectors (n_cap); the order of the allocations is kept.
+  void ensure_common(int64_t M, int kmax, int partials_len, bool need_x,
+                     std::initializer_list<double**> m_vecs);
+  // everything above, then the class's own vectors
+  void release_family(std::initializer_list<double**> own_vecs);
+};
+
+// Work vectors + device scalars of pcg(), kept across calls like CgWorkspace;
+// it regrows itself when a call needs more rows or more iterations.
+class PcgWorkspace : public PcgFamilyWorkspace
+{
+public:
+  explicit PcgWorkspace(HipExecutor& exec) : PcgFamilyWorkspace(exec) {}
   ~PcgWorkspace();
 
   // ---- internal to pcg() ----
@@ -233,21 +268,10 @@ public:
   // in the workspace's copy during the solve
   void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len,
               bool need_x, bool need_dinv);
-  void reserve_timing(int iterations)
-  {
-    reserve_events(2 * (size_t)std::max(iterations, 0));
-  }
   void release();
 
-  spmv_hip_pcg_ws* ws = nullptr;
-  int kmax_cap = -1;
-  int64_t m_cap = -1, n_cap = -1, x_cap = -1, dinv_cap = -1;
-  double *r = nullptr, *Ap = nullptr; // m_cap
-  double* x = nullptr;      // x_cap: the iterate when the caller's x is unaligned
-  double* dinv = nullptr;   // dinv_cap: the copy of an unaligned dinv
-  double* p = nullptr;      // n_cap: padded, the ghost tail is zeroed by every solve
-  double* dot2 = nullptr;   // partials of the remote block's p.Ap share
-  // flags: {done, kstop}; timing_ev: 2 events per iteration
+  int64_t dinv_cap = -1;
+  double* dinv = nullptr; // dinv_cap: the copy of an unaligned dinv
 };
 
 // dinv[i] = 1.0 / d[i] (spmv_hip_jacobi_invert_f64); `d` and `dinv` DEVICE
@@ -317,10 +341,10 @@ void chebyshev_coefficients(int degree, double lmin, double lmax, double* a,
 // Work vectors + device scalars of pcg_chebyshev() and chebyshev_apply(), kept
 // across calls like PcgWorkspace; it regrows itself when a call needs more rows
 // or more iterations.  The device scalars and their reducers are pcg()'s.
-class ChebyshevWorkspace : public SolverWorkspace
+class ChebyshevWorkspace : public PcgFamilyWorkspace
 {
 public:
-  explicit ChebyshevWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
+  explicit ChebyshevWorkspace(HipExecutor& exec) : PcgFamilyWorkspace(exec) {}
   ~ChebyshevWorkspace();
 
   // ---- internal to pcg_chebyshev() / chebyshev_apply() ----
@@ -329,24 +353,14 @@ public:
   // z always through the padded `z`)
   void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len,
               bool need_x, bool need_dinv);
-  // events for CgOptions::time_spmv of a solve with up to `spmvs` SpMVs
-  // (iterations * degree), created ahead of it
-  void reserve_timing(int spmvs)
-  {
-    reserve_events(2 * (size_t)std::max(spmvs, 0));
-  }
   void release();
 
-  spmv_hip_pcg_ws* ws = nullptr;
-  int kmax_cap = -1;
-  int64_t m_cap = -1, n_cap = -1, x_cap = -1, dinv_cap = -1;
-  double *r = nullptr, *Ap = nullptr, *d = nullptr, *w = nullptr; // m_cap
-  // n_cap: padded, what the SpMVs read; the ghost tails are zeroed by every call
-  double *p = nullptr, *z = nullptr;
-  double* x = nullptr;      // x_cap: the iterate when the caller's x is unaligned
-  double* dinv = nullptr;   // dinv_cap: the copy of an unaligned dinv
-  double* dot2 = nullptr;   // partials of the remote block's p.Ap share
-  // flags: {done, kstop}; timing_ev: 2 events per SpMV
+  int64_t dinv_cap = -1;
+  double *d = nullptr, *w = nullptr; // m_cap
+  // n_cap: padded like p, what the SpMVs of M read; its ghost tail is zeroed by
+  // every call
+  double* z = nullptr;
+  double* dinv = nullptr; // dinv_cap: the copy of an unaligned dinv
 };
 
 // z = q(dinv*A) dinv r: the preconditioner as an operation of its own (it also
@@ -616,29 +630,18 @@ inline void ilu0_apply(HipExecutor& exec, const Ilu0Preconditioner& M,
 
 // Work vectors + device scalars of pcg_sgs(), kept across calls like
 // ChebyshevWorkspace; the device scalars and their reducers are pcg()'s.
-class SgsWorkspace : public SolverWorkspace
+class SgsWorkspace : public PcgFamilyWorkspace
 {
 public:
-  explicit SgsWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
+  explicit SgsWorkspace(HipExecutor& exec) : PcgFamilyWorkspace(exec) {}
   ~SgsWorkspace();
 
   // ---- internal to pcg_sgs() ----
   void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len,
               bool need_x);
-  void reserve_timing(int iterations)
-  {
-    reserve_events(2 * (size_t)std::max(iterations, 0));
-  }
   void release();
 
-  spmv_hip_pcg_ws* ws = nullptr;
-  int kmax_cap = -1;
-  int64_t m_cap = -1, n_cap = -1, x_cap = -1;
-  double *r = nullptr, *Ap = nullptr, *z = nullptr; // m_cap
-  double* p = nullptr;    // n_cap: padded, the ghost tail is zeroed by every solve
-  double* x = nullptr;    // x_cap: the iterate when the caller's x is unaligned
-  double* dot2 = nullptr; // partials of the remote block's p.Ap share
-  // flags: {done, kstop}; timing_ev: 2 events per iteration
+  double* z = nullptr; // m_cap
 };
 
 // CG with the preconditioner M from x0 = 0: pcg_chebyshev()'s recurrence with

@@ -3,6 +3,7 @@
 #include "cg.h"
 
 #include <initializer_list>
+#include <type_traits>
 #include <utility>
 
 #include "sgs_build.h"
@@ -13,33 +14,44 @@ namespace spmv
 using namespace detail;
 
 // ---------------------------------------------------------------------------
-// pcg: see cg.h.  Per iteration (compute stream):
-//     halo start on the map's side stream
-//     SpMV local block (+ fused p.Ap share) [wait halo event] remote block
-//     one rank, consumer_reductions:            otherwise:
-//       update_r_cs   (pAp[k]; r; r.z, r.r)       reduce_pAp(2) ; all-reduce of 1
-//       update_xp_cs  ({rz,rr}[k]; x; p)          update_r
-//                                                 reduce_rz_rr ; all-reduce of 2
-//                                                 update_xp
-// 3 (or 5) launches; beside the SpMV 10 vector passes (update_r: Ap, r, dinv
-// in, r out; update_xp: r, dinv, x, p in, x, p out) where cg() without
-// defer_x streams 8.
+// pcg, pcg_chebyshev and pcg_sgs (see cg.h) are one frame, pcg_solve(), on one
+// set of device scalars (spmv_hip_pcg_ws) and reducers.  On the compute stream:
+//     prologue: checks, workspace, aligned copies, ghost tails, ws_reset
+//     [init]    r = b, x = 0, z0 = M(r0), p1 = z0, partials of r.z and r.r
+//     reduce_rz_rr(0) ; all-reduce of 2
+//     k = 1..kmax, until the lagging poll sees `done`:
+//       [body]  spmv_and_pAp: halo start of p on the map's side stream ;
+//                 Ap = A p (+ fused p.Ap share, else dot_partial) ;
+//                 reduce_pAp(2) ; all-reduce of 1
+//               [update r, z = M(r), partials of r.z and r.r]
+//               reduce_rz_rr(k) ; all-reduce of 2
+//               [update x ; stop test ; update p]
+//     epilogue: history, copy back of an unaligned x, sync, times, k_final
+// A solver plugs in what stands in brackets:
+//   pcg            init; one rank with consumer_reductions: spmv_and_pAp
+//                  without its reducer, update_r_cs (pAp[k]; r; r.z, r.r),
+//                  update_xp_cs ({rz,rr}[k]; x; p): 3 launches; otherwise
+//                  update_r and update_xp in the two slots: 5 launches.
+//                  z = dinv*r is not stored.  Beside the SpMV 10 vector passes
+//                  (update_r: Ap, r, dinv in, r out; update_xp: r, dinv, x, p
+//                  in, x, p out) where cg() without defer_x streams 8.
+//   pcg_chebyshev  cheb_init / cheb_update_r (r ; partials of r.r ; step 0 of
+//                  M: d, z), then degree - 1 times: halo start of z ; w = A z ;
+//                  cheb_step (the last one: partials of r.z, no d); all
+//                  `degree` SpMVs of an iteration are timed.  degree SpMVs +
+//                  degree + 1 streaming launches + 2 reducers; beside the SpMVs
+//                  7 (degree - 1) + 11 vector passes with a dinv for degree >=
+//                  2 (update_r: Ap, r, dinv in, r, d, z out; a step: w, r,
+//                  dinv, d, z in, d, z out, the last one without d out;
+//                  update_xp: z, x, p in, x, p out), 10 for degree 1.
+//   pcg_sgs        sgs_init / sgs_update_r (r ; partials of r.r), then the 2C -
+//                  1 sweeps of z = M^-1 r (local: no halo) and sgs_dot_rz
+//                  (partials of r.z).
+// The last two keep z and share cheb_update_xp (x ; stop test ; p).
 // ---------------------------------------------------------------------------
-PcgWorkspace::~PcgWorkspace() { release(); }
-
-void PcgWorkspace::release()
-{
-  release_common();
-  spmv_hip_pcg_ws_destroy(ws);
-  ws = nullptr;
-  free_vectors({&r, &Ap, &x, &dinv, &p, &dot2});
-  kmax_cap = -1;
-  m_cap = n_cap = x_cap = dinv_cap = -1;
-}
-
 namespace
 {
-// the device scalars of pcg() and pcg_chebyshev() for up to kmax iterations
+// the device scalars of the family for up to kmax iterations
 void regrow_scalars(spmv_hip_ctx* ctx, spmv_hip_pcg_ws*& ws, int& kmax_cap,
                     int kmax)
 {
@@ -56,20 +68,258 @@ void regrow_scalars(spmv_hip_ctx* ctx, spmv_hip_pcg_ws*& ws, int& kmax_cap,
 }
 } // namespace
 
-void PcgWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
-                          bool need_x, bool need_dinv)
+void PcgFamilyWorkspace::ensure_common(int64_t M, int kmax, int len,
+                                       bool need_x,
+                                       std::initializer_list<double**> m_vecs)
 {
   open(2);
   if (!dot2)
     dot2 = _exec.alloc<double>(len);
   regrow_scalars(_exec.context(), ws, kmax_cap, kmax);
-  regrow(m_cap, M, {&r, &Ap});
+  regrow(m_cap, M, m_vecs);
   if (need_x)
     regrow(x_cap, M, {&x});
+}
+
+void PcgFamilyWorkspace::release_family(
+    std::initializer_list<double**> own_vecs)
+{
+  release_common();
+  spmv_hip_pcg_ws_destroy(ws);
+  ws = nullptr;
+  free_vectors({&r, &Ap, &x, &p, &dot2});
+  free_vectors(own_vecs);
+  kmax_cap = -1;
+  m_cap = n_cap = x_cap = -1;
+}
+
+PcgWorkspace::~PcgWorkspace() { release(); }
+
+void PcgWorkspace::release()
+{
+  release_family({&dinv});
+  dinv_cap = -1;
+}
+
+void PcgWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
+                          bool need_x, bool need_dinv)
+{
+  ensure_common(M, kmax, len, need_x, {&r, &Ap});
   if (need_dinv)
     regrow(dinv_cap, M, {&dinv});
   regrow(n_cap, N_padded, {&p});
 }
+
+ChebyshevWorkspace::~ChebyshevWorkspace() { release(); }
+
+void ChebyshevWorkspace::release()
+{
+  release_family({&d, &w, &z, &dinv});
+  dinv_cap = -1;
+}
+
+void ChebyshevWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
+                                bool need_x, bool need_dinv)
+{
+  ensure_common(M, kmax, len, need_x, {&r, &Ap, &d, &w});
+  if (need_dinv)
+    regrow(dinv_cap, M, {&dinv});
+  regrow(n_cap, N_padded, {&p, &z});
+}
+
+SgsWorkspace::~SgsWorkspace() { release(); }
+
+void SgsWorkspace::release() { release_family({&z}); }
+
+void SgsWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
+                          bool need_x)
+{
+  ensure_common(M, kmax, len, need_x, {&r, &Ap, &z});
+  regrow(n_cap, N_padded, {&p});
+}
+
+namespace
+{
+// What a solve of the family holds between its prologue and its epilogue, and
+// the two steps that every loop body is made of.  W: the solver's workspace.
+template <class W>
+struct PcgSolve {
+  const Comm& comm;
+  HipExecutor& exec;
+  const Matrix<double>& A;
+  const L2GMap& col_l2g;
+  spmv_hip_ctx* const ctx;
+  const CgOptions& opt;
+  W& w;
+  const int64_t M;
+  double* const xi;       // the iterate: the caller's x, or w.x
+  const double* const di; // the caller's dinv, w.dinv, or null
+  double* const partials;
+  size_t ev_next = 0; // two events per timed SpMV
+
+  // Ap = A p with the p.Ap partials produced by the SpMV kernels themselves
+  // (local block's share + remote block's share, the latter in w.dot2) where
+  // they can: returns whether they did.  reduce: pAp[k] is finished by its
+  // reducer and the all-reduce of 1 (a consumer kernel adds the partials
+  // itself).
+  bool spmv_and_pAp(int k, bool reduce)
+  {
+    col_l2g.update(w.p); // starts on the side stream
+    void* ev1 = nullptr;
+    if (opt.time_spmv) {
+      ev1 = w.timing_ev[ev_next + 1];
+      exec.record_event(w.timing_ev[ev_next], w.stream);
+      ev_next += 2;
+    }
+    const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
+    if (!fused)
+      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, w.p, w.Ap, partials,
+                                              nullptr),
+                     "spmv_hip_dot_partial_f64");
+    if (reduce) {
+      if (fused)
+        throw_on_error(spmv_hip_pcg_reduce_pAp2(ctx, w.ws, k, w.dot2, nullptr),
+                       "spmv_hip_pcg_reduce_pAp2");
+      else
+        throw_on_error(spmv_hip_pcg_reduce_pAp(ctx, w.ws, k, nullptr),
+                       "spmv_hip_pcg_reduce_pAp");
+      comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_pAp, k,
+                              "spmv_hip_pcg_ws_pAp"),
+                      1, w.stream);
+    }
+    return fused;
+  }
+
+  // {rz[k], rr[k]} from their partials: one all-reduce of 2 doubles
+  void reduce_rz_rr(int k)
+  {
+    throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, k, nullptr),
+                   "spmv_hip_pcg_reduce_rz_rr");
+    comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, k,
+                            "spmv_hip_pcg_ws_rz_rr"),
+                    2, w.stream);
+  }
+};
+
+// The frame described at the top for spmv::<who>.  dinv may be null where the
+// solver allows it (pcg_sgs has none); more_tails: the padded vectors beside p
+// whose ghost tail is zeroed; init(s) and body(s, k) are the solver's slots,
+// inlined here.  Returns k_final.
+template <class W, class Init, class Body>
+int pcg_solve(const char* who, const Comm& comm, HipExecutor& exec,
+              const Matrix<double>& A, const Dims& dims, const double* b,
+              double* x, const double* dinv, int kmax, double rtol,
+              std::vector<double>* rnorm_history, const CgOptions& opt,
+              CgStats* stats, W* workspace, int spmvs_per_iteration,
+              std::initializer_list<double* W::*> more_tails, Init&& init,
+              Body&& body)
+{
+  constexpr bool has_dinv = !std::is_same<W, SgsWorkspace>::value;
+  const int64_t M = dims.M, N_padded = dims.N_padded;
+  spmv_hip_ctx* ctx = exec.context();
+  const int len = dot_partials_len(ctx);
+  // x is the iterate from the first kernel on: it cannot share b or dinv
+  if (ranges_overlap(x, b, M))
+    throw std::runtime_error(std::string(who)
+                             + ": x overlaps b (x is updated in place)");
+  if (dinv && ranges_overlap(x, dinv, M))
+    throw std::runtime_error(std::string(who)
+                             + ": x overlaps dinv (x is updated in place)");
+
+  W own(exec);
+  W& w = workspace ? *workspace : own;
+  const bool x_aligned = is_aligned16(x);
+  const bool dinv_aligned = is_aligned16(dinv);
+  if constexpr (has_dinv)
+    w.ensure(M, N_padded, kmax, len, !x_aligned, !dinv_aligned);
+  else
+    w.ensure(M, N_padded, kmax, len, !x_aligned);
+  if (opt.time_spmv)
+    w.reserve_timing(kmax * spmvs_per_iteration);
+
+  SolveStream guard(exec, w.stream); // every launch below goes to w.stream
+
+  throw_on_error(spmv_hip_pcg_ws_reset(w.ws, rtol, nullptr),
+                 "spmv_hip_pcg_ws_reset");
+  double* partials = nullptr;
+  throw_on_error(spmv_hip_pcg_ws_partials(w.ws, &partials),
+                 "spmv_hip_pcg_ws_partials");
+
+  const double* di = dinv;
+  if constexpr (has_dinv) {
+    if (dinv && !dinv_aligned) { // the streaming kernels load 16 bytes at a time
+      exec.copy<double>(w.dinv, dinv, M);
+      di = w.dinv;
+    }
+  }
+  // the ghost tails are defined here instead of relying on fresh pages
+  if (N_padded > M) {
+    exec.memset<double>(w.p + M, 0, N_padded - M);
+    for (double* W::*v : more_tails)
+      exec.memset<double>(w.*v + M, 0, N_padded - M);
+  }
+  exec.memset<double>(w.dot2, 0, len);
+
+  PcgSolve<W> s{comm, exec, A, *dims.col_l2g, ctx, opt, w, M,
+                x_aligned ? x : w.x, di, partials};
+  init(s);
+  w.flags[0] = 0;
+  w.flags[1] = -1;
+
+  // the state words alone (h == nullptr), or with the history of pairs
+  auto read = [&](double* h, size_t n) {
+    throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, h, n, nullptr),
+                   "spmv_hip_pcg_ws_read_async");
+  };
+
+  s.reduce_rz_rr(0);
+  LaggingPoll poll(exec, w, opt.poll_every, kmax);
+  int k = 0;
+  while (k < kmax && !poll.stopped) {
+    ++k;
+    body(s, k);
+    poll.step(k, read);
+  }
+
+  // final state: {done, kstop} and the history of pairs {rz[k], rr[k]}
+  const std::vector<double> zr
+      = read_history(spmv_hip_pcg_ws_capacity, w.ws, kmax, 2, read);
+  if (s.xi != x)
+    exec.copy<double>(x, s.xi, M);
+  exec.synchronize_stream(w.stream);
+
+  if (stats) {
+    *stats = CgStats();
+    if (opt.time_spmv)
+      sum_spmv_times(ctx, w.timing_ev, s.ev_next, *stats);
+  }
+
+  auto rr_at = [&](int j) { return zr[2 * (size_t)j + 1]; };
+  int k_final;
+  if (w.flags[0] != 0)
+    k_final = w.flags[1];
+  else if (rr_at(0) == 0.0)
+    k_final = 0; // (kmax == 0: no kernel ran to say so)
+  else // `done` is raised by the first launch of the NEXT iteration
+    k_final = first_k_below(rr_at, k, rtol);
+  write_history(rnorm_history, k_final, rr_at);
+  return k_final;
+}
+
+// An iteration of the two solvers that keep z: update_r() updates r and
+// leaves z = M(r) with the partials of r.z and r.r
+template <class W, class UpdateR>
+void stored_z_iteration(PcgSolve<W>& s, int k, UpdateR&& update_r)
+{
+  s.spmv_and_pAp(k, true);
+  update_r();
+  s.reduce_rz_rr(k); // rz[k] and rr[k] at once
+  throw_on_error(spmv_hip_cheb_update_xp_f64(s.ctx, s.w.ws, k, s.M, s.w.z, s.xi,
+                                             s.w.p, nullptr),
+                 "spmv_hip_cheb_update_xp_f64");
+}
+} // namespace
+
 void jacobi_inverse(HipExecutor& exec, const double* d, double* dinv, int64_t n)
 {
   if (n < 0)
@@ -99,184 +349,43 @@ int pcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
         CgStats* stats, PcgWorkspace* workspace)
 {
   const Dims dims = check_problem("pcg", A, kmax);
-  const int64_t M = dims.M, N_padded = dims.N_padded;
-  const std::shared_ptr<const L2GMap>& col_l2g = dims.col_l2g;
   const CgOptions opt = options ? *options : CgOptions();
-  spmv_hip_ctx* ctx = exec.context();
-  const int len = dot_partials_len(ctx);
-  // x is the iterate from the first kernel on: it cannot share b or dinv
-  if (ranges_overlap(x, b, M))
-    throw std::runtime_error("pcg: x overlaps b (x is updated in place)");
-  if (ranges_overlap(x, dinv, M))
-    throw std::runtime_error("pcg: x overlaps dinv (x is updated in place)");
-
-  PcgWorkspace own(exec);
-  PcgWorkspace& w = workspace ? *workspace : own;
-  const bool x_aligned = is_aligned16(x);
-  const bool dinv_aligned = is_aligned16(dinv);
-  w.ensure(M, N_padded, kmax, len, !x_aligned, !dinv_aligned);
-  if (opt.time_spmv)
-    w.reserve_timing(kmax);
-
-  SolveStream guard(exec, w.stream); // every launch below goes to w.stream
-
-  throw_on_error(spmv_hip_pcg_ws_reset(w.ws, rtol, nullptr),
-                 "spmv_hip_pcg_ws_reset");
-  double* partials = nullptr;
-  throw_on_error(spmv_hip_pcg_ws_partials(w.ws, &partials),
-                 "spmv_hip_pcg_ws_partials");
-
-  double* const xi = x_aligned ? x : w.x;
-  const double* di = dinv;
-  if (!dinv_aligned) { // the streaming kernels load 16 bytes at a time
-    exec.copy<double>(w.dinv, dinv, M);
-    di = w.dinv;
-  }
-  // the ghost tail of p is defined here instead of relying on fresh pages
-  if (N_padded > M)
-    exec.memset<double>(w.p + M, 0, N_padded - M);
-  exec.memset<double>(w.dot2, 0, len);
-  // r = b, x0 = 0, p = dinv*b, partials of r.z and r.r: one pass
-  throw_on_error(spmv_hip_pcg_init_f64(ctx, w.ws, M, b, di, w.r, w.p, xi,
-                                       nullptr),
-                 "spmv_hip_pcg_init_f64");
-  w.flags[0] = 0;
-  w.flags[1] = -1;
-
-  // the state words alone (h == nullptr), or with the history of pairs
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_pcg_ws_read_async");
-  };
-
-  // {rz0, rr0}: one all-reduce of 2 doubles
-  throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, 0, nullptr),
-                 "spmv_hip_pcg_reduce_rz_rr");
-  comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, 0,
-                          "spmv_hip_pcg_ws_rz_rr"),
-                  2, w.stream);
-
+  // one rank: the update kernels add the partials themselves
   const bool consume = opt.consumer_reductions && comm.size() == 1;
-  std::vector<void*>& timing_ev = w.timing_ev;
-  LaggingPoll poll(exec, w, opt.poll_every, kmax);
-  int k = 0;
-  while (k < kmax && !poll.stopped) {
-    ++k;
-    col_l2g->update(w.p); // starts on the side stream
-    void* ev1 = nullptr;
-    if (opt.time_spmv) {
-      ev1 = timing_ev[2 * (size_t)(k - 1) + 1];
-      exec.record_event(timing_ev[2 * (size_t)(k - 1)], w.stream);
-    }
-    // Ap = A p with the p.Ap partials produced by the SpMV kernels themselves
-    // (local block's share + remote block's share) where they can
-    const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
-    if (!fused)
-      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, w.p, w.Ap, partials,
-                                              nullptr),
-                     "spmv_hip_dot_partial_f64");
-    if (consume) {
-      // one rank: the update kernels add the partials themselves
-      throw_on_error(spmv_hip_pcg_update_r_cs_f64(ctx, w.ws, k, M, w.Ap, di,
-                                                  w.r, fused ? w.dot2 : nullptr,
-                                                  nullptr),
-                     "spmv_hip_pcg_update_r_cs_f64");
-      throw_on_error(spmv_hip_pcg_update_xp_cs_f64(ctx, w.ws, k, M, w.r, di, xi,
-                                                   w.p, nullptr),
-                     "spmv_hip_pcg_update_xp_cs_f64");
-    } else {
-      if (fused)
-        throw_on_error(spmv_hip_pcg_reduce_pAp2(ctx, w.ws, k, w.dot2, nullptr),
-                       "spmv_hip_pcg_reduce_pAp2");
-      else
-        throw_on_error(spmv_hip_pcg_reduce_pAp(ctx, w.ws, k, nullptr),
-                       "spmv_hip_pcg_reduce_pAp");
-      comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_pAp, k,
-                              "spmv_hip_pcg_ws_pAp"),
-                      1, w.stream);
-      throw_on_error(spmv_hip_pcg_update_r_f64(ctx, w.ws, k, M, w.Ap, di, w.r,
-                                               nullptr),
-                     "spmv_hip_pcg_update_r_f64");
-      throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, k, nullptr),
-                     "spmv_hip_pcg_reduce_rz_rr");
-      comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, k,
-                              "spmv_hip_pcg_ws_rz_rr"),
-                      2, w.stream); // rz[k] and rr[k] at once
-      throw_on_error(spmv_hip_pcg_update_xp_f64(ctx, w.ws, k, M, w.r, di, xi,
-                                                w.p, nullptr),
-                     "spmv_hip_pcg_update_xp_f64");
-    }
-
-    poll.step(k, read);
-  }
-
-  // final state: {done, kstop} and the history of pairs {rz[k], rr[k]}
-  const std::vector<double> zr
-      = read_history(spmv_hip_pcg_ws_capacity, w.ws, kmax, 2, read);
-  if (xi != x)
-    exec.copy<double>(x, xi, M);
-  exec.synchronize_stream(w.stream);
-
-  if (stats) {
-    *stats = CgStats();
-    if (opt.time_spmv)
-      sum_spmv_times(ctx, timing_ev, 2 * (size_t)k, *stats);
-  }
-
-  auto rr_at = [&](int j) { return zr[2 * (size_t)j + 1]; };
-  int k_final;
-  if (w.flags[0] != 0)
-    k_final = w.flags[1];
-  else if (rr_at(0) == 0.0)
-    k_final = 0; // (kmax == 0: no kernel ran to say so)
-  else // `done` is raised by the first kernel of the NEXT iteration
-    k_final = first_k_below(rr_at, k, rtol);
-  write_history(rnorm_history, k_final, rr_at);
-  return k_final;
+  using Solve = PcgSolve<PcgWorkspace>;
+  return pcg_solve(
+      "pcg", comm, exec, A, dims, b, x, dinv, kmax, rtol, rnorm_history, opt,
+      stats, workspace, 1, {},
+      // r = b, x0 = 0, p = dinv*b, partials of r.z and r.r: one pass
+      [&](Solve& s) {
+        throw_on_error(spmv_hip_pcg_init_f64(s.ctx, s.w.ws, s.M, b, s.di, s.w.r,
+                                             s.w.p, s.xi, nullptr),
+                       "spmv_hip_pcg_init_f64");
+      },
+      [&](Solve& s, int k) {
+        PcgWorkspace& w = s.w;
+        const bool fused = s.spmv_and_pAp(k, !consume);
+        if (consume) {
+          throw_on_error(spmv_hip_pcg_update_r_cs_f64(
+                             s.ctx, w.ws, k, s.M, w.Ap, s.di, w.r,
+                             fused ? w.dot2 : nullptr, nullptr),
+                         "spmv_hip_pcg_update_r_cs_f64");
+          throw_on_error(spmv_hip_pcg_update_xp_cs_f64(s.ctx, w.ws, k, s.M, w.r,
+                                                       s.di, s.xi, w.p, nullptr),
+                         "spmv_hip_pcg_update_xp_cs_f64");
+        } else {
+          throw_on_error(spmv_hip_pcg_update_r_f64(s.ctx, w.ws, k, s.M, w.Ap,
+                                                   s.di, w.r, nullptr),
+                         "spmv_hip_pcg_update_r_f64");
+          s.reduce_rz_rr(k); // rz[k] and rr[k] at once
+          throw_on_error(spmv_hip_pcg_update_xp_f64(s.ctx, w.ws, k, s.M, w.r,
+                                                    s.di, s.xi, w.p, nullptr),
+                         "spmv_hip_pcg_update_xp_f64");
+        }
+      });
 }
 
-// ---------------------------------------------------------------------------
-// Chebyshev polynomial preconditioner: see cg.h.  pcg_chebyshev per iteration
-// (compute stream), on the scalars and reducers of pcg():
-//     halo start of p ; Ap = A p (+ fused p.Ap share)
-//     reduce_pAp ; all-reduce of 1
-//     cheb_update_r   (r ; partials of r.r ; step 0 of M: d, z)
-//     degree - 1 times:  halo start of z ; w = A z ; cheb_step
-//                        (the last one: partials of r.z, no d)
-//     reduce_rz_rr ; all-reduce of 2
-//     cheb_update_xp  (x ; stop test ; p)
-// degree SpMVs + degree + 1 streaming launches + 2 reducers; beside the SpMVs
-// 7 (degree - 1) + 11 vector passes with a dinv for degree >= 2 (update_r: Ap,
-// r, dinv in, r, d, z out; a step: w, r, dinv, d, z in, d, z out, the last one
-// without d out; update_xp: z, x, p in, x, p out), 10 for degree 1.
-// ---------------------------------------------------------------------------
 // (chebyshev_coefficients: solver_args.cpp)
-ChebyshevWorkspace::~ChebyshevWorkspace() { release(); }
-
-void ChebyshevWorkspace::release()
-{
-  release_common();
-  spmv_hip_pcg_ws_destroy(ws);
-  ws = nullptr;
-  free_vectors({&r, &Ap, &d, &w, &p, &z, &x, &dinv, &dot2});
-  kmax_cap = -1;
-  m_cap = n_cap = x_cap = dinv_cap = -1;
-}
-
-void ChebyshevWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
-                                bool need_x, bool need_dinv)
-{
-  open(2);
-  if (!dot2)
-    dot2 = _exec.alloc<double>(len);
-  regrow_scalars(_exec.context(), ws, kmax_cap, kmax);
-  regrow(m_cap, M, {&r, &Ap, &d, &w});
-  if (need_x)
-    regrow(x_cap, M, {&x});
-  if (need_dinv)
-    regrow(dinv_cap, M, {&dinv});
-  regrow(n_cap, N_padded, {&p, &z});
-}
 void chebyshev_apply(HipExecutor& exec, const Matrix<double>& A,
                      const double* r, double* z, const double* dinv, int degree,
                      double lmin, double lmax, ChebyshevWorkspace* workspace)
@@ -337,171 +446,52 @@ int pcg_chebyshev(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   double ca[kChebyshevMaxDegree], cb[kChebyshevMaxDegree];
   chebyshev_coefficients(degree, lmin, lmax, ca, cb);
   const Dims dims = check_problem("pcg_chebyshev", A, kmax);
-  const int64_t M = dims.M, N_padded = dims.N_padded;
-  const std::shared_ptr<const L2GMap>& col_l2g = dims.col_l2g;
   const CgOptions opt = options ? *options : CgOptions();
-  spmv_hip_ctx* ctx = exec.context();
-  const int len = dot_partials_len(ctx);
-  // x is the iterate from the first kernel on: it cannot share b or dinv
-  if (ranges_overlap(x, b, M))
-    throw std::runtime_error(
-        "pcg_chebyshev: x overlaps b (x is updated in place)");
-  if (dinv && ranges_overlap(x, dinv, M))
-    throw std::runtime_error(
-        "pcg_chebyshev: x overlaps dinv (x is updated in place)");
-
-  ChebyshevWorkspace own(exec);
-  ChebyshevWorkspace& w = workspace ? *workspace : own;
-  const bool x_aligned = is_aligned16(x);
-  const bool dinv_aligned = is_aligned16(dinv);
-  w.ensure(M, N_padded, kmax, len, !x_aligned, !dinv_aligned);
-  if (opt.time_spmv)
-    w.reserve_timing(kmax * degree);
-
-  SolveStream guard(exec, w.stream); // every launch below goes to w.stream
-
-  throw_on_error(spmv_hip_pcg_ws_reset(w.ws, rtol, nullptr),
-                 "spmv_hip_pcg_ws_reset");
-  double* partials = nullptr;
-  throw_on_error(spmv_hip_pcg_ws_partials(w.ws, &partials),
-                 "spmv_hip_pcg_ws_partials");
-
-  double* const xi = x_aligned ? x : w.x;
-  const double* di = dinv;
-  if (dinv && !dinv_aligned) { // the streaming kernels load 16 bytes at a time
-    exec.copy<double>(w.dinv, dinv, M);
-    di = w.dinv;
-  }
-  // the ghost tails of p and z are defined here instead of relying on fresh
-  // pages
-  if (N_padded > M) {
-    exec.memset<double>(w.p + M, 0, N_padded - M);
-    exec.memset<double>(w.z + M, 0, N_padded - M);
-  }
-  exec.memset<double>(w.dot2, 0, len);
-  double* const dvec = degree > 1 ? w.d : nullptr; // degree 1: no d
-
-  std::vector<void*>& timing_ev = w.timing_ev;
-  size_t ev_next = 0; // two events per timed SpMV
+  using Solve = PcgSolve<ChebyshevWorkspace>;
   // steps 1 .. degree - 1 of z = M(r); the last one leaves the r.z partials
-  auto cheb_steps = [&](bool timed) {
+  auto cheb_steps = [&](Solve& s, bool timed) {
+    ChebyshevWorkspace& w = s.w;
     for (int j = 1; j < degree; ++j) {
-      col_l2g->update(w.z); // starts on the side stream
+      s.col_l2g.update(w.z); // starts on the side stream
       if (timed)
-        exec.record_event(timing_ev[ev_next], w.stream);
+        exec.record_event(w.timing_ev[s.ev_next], w.stream);
       A.mult(w.z, w.w);
       if (timed) {
-        exec.record_event(timing_ev[ev_next + 1], w.stream);
-        ev_next += 2;
+        exec.record_event(w.timing_ev[s.ev_next + 1], w.stream);
+        s.ev_next += 2;
       }
-      throw_on_error(spmv_hip_cheb_step_f64(ctx, w.ws, M, ca[j], cb[j],
-                                            j == degree - 1, w.w, w.r, di, w.d,
+      throw_on_error(spmv_hip_cheb_step_f64(s.ctx, w.ws, s.M, ca[j], cb[j],
+                                            j == degree - 1, w.w, w.r, s.di, w.d,
                                             w.z, nullptr),
                      "spmv_hip_cheb_step_f64");
     }
   };
-
-  // r = b, x0 = 0, partials of r.r, step 0 of M: one pass; then the rest of
-  // z0 = M(r0) and p1 = z0
-  throw_on_error(spmv_hip_cheb_init_f64(ctx, w.ws, M, cb[0], b, di, w.r, xi,
-                                        dvec, w.z, nullptr),
-                 "spmv_hip_cheb_init_f64");
-  cheb_steps(false);
-  exec.copy<double>(w.p, w.z, M);
-  w.flags[0] = 0;
-  w.flags[1] = -1;
-
-  // the state words alone (h == nullptr), or with the history of pairs
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_pcg_ws_read_async");
-  };
-
-  // {rz0, rr0}: one all-reduce of 2 doubles
-  throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, 0, nullptr),
-                 "spmv_hip_pcg_reduce_rz_rr");
-  comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, 0,
-                          "spmv_hip_pcg_ws_rz_rr"),
-                  2, w.stream);
-
-  LaggingPoll poll(exec, w, opt.poll_every, kmax);
-  int k = 0;
-  while (k < kmax && !poll.stopped) {
-    ++k;
-    col_l2g->update(w.p); // starts on the side stream
-    void* ev1 = nullptr;
-    if (opt.time_spmv) {
-      ev1 = timing_ev[ev_next + 1];
-      exec.record_event(timing_ev[ev_next], w.stream);
-      ev_next += 2;
-    }
-    // Ap = A p with the p.Ap partials produced by the SpMV kernels themselves
-    // (local block's share + remote block's share) where they can
-    const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
-    if (!fused) {
-      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, w.p, w.Ap, partials,
+  // degree 1: no d
+  auto dvec = [&](Solve& s) { return degree > 1 ? s.w.d : nullptr; };
+  return pcg_solve(
+      "pcg_chebyshev", comm, exec, A, dims, b, x, dinv, kmax, rtol,
+      rnorm_history, opt, stats, workspace, degree, {&ChebyshevWorkspace::z},
+      // r = b, x0 = 0, partials of r.r, step 0 of M: one pass; then the rest
+      // of z0 = M(r0) and p1 = z0
+      [&](Solve& s) {
+        throw_on_error(spmv_hip_cheb_init_f64(s.ctx, s.w.ws, s.M, cb[0], b, s.di,
+                                              s.w.r, s.xi, dvec(s), s.w.z,
                                               nullptr),
-                     "spmv_hip_dot_partial_f64");
-      throw_on_error(spmv_hip_pcg_reduce_pAp(ctx, w.ws, k, nullptr),
-                     "spmv_hip_pcg_reduce_pAp");
-    } else {
-      throw_on_error(spmv_hip_pcg_reduce_pAp2(ctx, w.ws, k, w.dot2, nullptr),
-                     "spmv_hip_pcg_reduce_pAp2");
-    }
-    comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_pAp, k, "spmv_hip_pcg_ws_pAp"),
-                    1, w.stream);
-    throw_on_error(spmv_hip_cheb_update_r_f64(ctx, w.ws, k, M, cb[0], w.Ap, di,
-                                              w.r, dvec, w.z, nullptr),
-                   "spmv_hip_cheb_update_r_f64");
-    cheb_steps(opt.time_spmv);
-    throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, k, nullptr),
-                   "spmv_hip_pcg_reduce_rz_rr");
-    comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, k,
-                            "spmv_hip_pcg_ws_rz_rr"),
-                    2, w.stream); // rz[k] and rr[k] at once
-    throw_on_error(spmv_hip_cheb_update_xp_f64(ctx, w.ws, k, M, w.z, xi, w.p,
-                                               nullptr),
-                   "spmv_hip_cheb_update_xp_f64");
-
-    poll.step(k, read);
-  }
-
-  // final state: {done, kstop} and the history of pairs {rz[k], rr[k]}
-  const std::vector<double> zr
-      = read_history(spmv_hip_pcg_ws_capacity, w.ws, kmax, 2, read);
-  if (xi != x)
-    exec.copy<double>(x, xi, M);
-  exec.synchronize_stream(w.stream);
-
-  if (stats) {
-    *stats = CgStats();
-    if (opt.time_spmv)
-      sum_spmv_times(ctx, timing_ev, ev_next, *stats);
-  }
-
-  auto rr_at = [&](int j) { return zr[2 * (size_t)j + 1]; };
-  int k_final;
-  if (w.flags[0] != 0)
-    k_final = w.flags[1];
-  else if (rr_at(0) == 0.0)
-    k_final = 0; // (kmax == 0: no kernel ran to say so)
-  else // `done` is raised by the first reducer of the NEXT iteration
-    k_final = first_k_below(rr_at, k, rtol);
-  write_history(rnorm_history, k_final, rr_at);
-  return k_final;
+                       "spmv_hip_cheb_init_f64");
+        cheb_steps(s, false);
+        exec.copy<double>(s.w.p, s.w.z, s.M);
+      },
+      [&](Solve& s, int k) {
+        stored_z_iteration(s, k, [&] {
+          throw_on_error(spmv_hip_cheb_update_r_f64(s.ctx, s.w.ws, k, s.M, cb[0],
+                                                    s.w.Ap, s.di, s.w.r, dvec(s),
+                                                    s.w.z, nullptr),
+                         "spmv_hip_cheb_update_r_f64");
+          cheb_steps(s, opt.time_spmv);
+        });
+      });
 }
 
-// ---------------------------------------------------------------------------
-// Multicolour symmetric Gauss-Seidel: see cg.h.  pcg_sgs per iteration (compute
-// stream), on the scalars and reducers of pcg():
-//     halo start of p ; Ap = A p (+ fused p.Ap share)
-//     reduce_pAp ; all-reduce of 1
-//     sgs_update_r    (r ; partials of r.r)
-//     2C - 1 sweeps   (z = M^-1 r, local: no halo)
-//     sgs_dot_rz      (partials of r.z)
-//     reduce_rz_rr ; all-reduce of 2
-//     cheb_update_xp  (x ; stop test ; p)
-// ---------------------------------------------------------------------------
 SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A)
     : _exec(exec)
 {
@@ -633,171 +623,52 @@ void sgs_apply(HipExecutor& exec, const SgsPreconditioner& M, const double* r,
                  "spmv_hip_mcgs_apply_f64");
 }
 
-SgsWorkspace::~SgsWorkspace() { release(); }
-
-void SgsWorkspace::release()
-{
-  release_common();
-  spmv_hip_pcg_ws_destroy(ws);
-  ws = nullptr;
-  free_vectors({&r, &Ap, &z, &p, &x, &dot2});
-  kmax_cap = -1;
-  m_cap = n_cap = x_cap = -1;
-}
-
-void SgsWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
-                          bool need_x)
-{
-  open(2);
-  if (!dot2)
-    dot2 = _exec.alloc<double>(len);
-  regrow_scalars(_exec.context(), ws, kmax_cap, kmax);
-  regrow(m_cap, M, {&r, &Ap, &z});
-  if (need_x)
-    regrow(x_cap, M, {&x});
-  regrow(n_cap, N_padded, {&p});
-}
-
 int pcg_sgs(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
             const SgsPreconditioner& Mpre, const double* b, double* x, int kmax,
             double rtol, std::vector<double>* rnorm_history,
             const CgOptions* options, CgStats* stats, SgsWorkspace* workspace)
 {
   const Dims dims = check_problem("pcg_sgs", A, kmax);
-  const int64_t M = dims.M, N_padded = dims.N_padded;
-  const std::shared_ptr<const L2GMap>& col_l2g = dims.col_l2g;
   const CgOptions opt = options ? *options : CgOptions();
-  spmv_hip_ctx* ctx = exec.context();
-  const int len = dot_partials_len(ctx);
-  if (Mpre.rows() != M)
+  if (Mpre.rows() != dims.M)
     throw std::runtime_error(
         "spmv::pcg_sgs - Error: the preconditioner was built for "
         + std::to_string(Mpre.rows()) + " rows, the matrix has "
-        + std::to_string(M));
+        + std::to_string(dims.M));
   if (Mpre.negative_pivots() > 0)
     throw std::runtime_error(
         "spmv::pcg_sgs - Error: the preconditioner has "
         + std::to_string(Mpre.negative_pivots())
         + " negative pivot(s): it is not positive definite");
-  // x is the iterate from the first kernel on: it cannot share b
-  if (ranges_overlap(x, b, M))
-    throw std::runtime_error("pcg_sgs: x overlaps b (x is updated in place)");
-
-  SgsWorkspace own(exec);
-  SgsWorkspace& w = workspace ? *workspace : own;
-  const bool x_aligned = is_aligned16(x);
-  w.ensure(M, N_padded, kmax, len, !x_aligned);
-  if (opt.time_spmv)
-    w.reserve_timing(kmax);
-
-  SolveStream guard(exec, w.stream); // every launch below goes to w.stream
-
-  throw_on_error(spmv_hip_pcg_ws_reset(w.ws, rtol, nullptr),
-                 "spmv_hip_pcg_ws_reset");
-  double* partials = nullptr;
-  throw_on_error(spmv_hip_pcg_ws_partials(w.ws, &partials),
-                 "spmv_hip_pcg_ws_partials");
-
-  double* const xi = x_aligned ? x : w.x;
-  // the ghost tail of p is defined here instead of relying on fresh pages
-  if (N_padded > M)
-    exec.memset<double>(w.p + M, 0, N_padded - M);
-  exec.memset<double>(w.dot2, 0, len);
-
+  using Solve = PcgSolve<SgsWorkspace>;
   // z = M^-1 r and the partials of r.z
-  auto precondition = [&] {
-    throw_on_error(spmv_hip_mcgs_apply_f64(ctx, Mpre.plan(), w.ws, w.r, w.z,
-                                           nullptr),
+  auto precondition = [&](Solve& s) {
+    throw_on_error(spmv_hip_mcgs_apply_f64(s.ctx, Mpre.plan(), s.w.ws, s.w.r,
+                                           s.w.z, nullptr),
                    "spmv_hip_mcgs_apply_f64");
-    throw_on_error(spmv_hip_sgs_dot_rz_f64(ctx, w.ws, M, w.r, w.z, nullptr),
+    throw_on_error(spmv_hip_sgs_dot_rz_f64(s.ctx, s.w.ws, s.M, s.w.r, s.w.z,
+                                           nullptr),
                    "spmv_hip_sgs_dot_rz_f64");
   };
-
-  // r = b, x0 = 0, partials of r.r: one pass; then z0 = M^-1 r0 and p1 = z0
-  throw_on_error(spmv_hip_sgs_init_f64(ctx, w.ws, M, b, w.r, xi, nullptr),
-                 "spmv_hip_sgs_init_f64");
-  precondition();
-  exec.copy<double>(w.p, w.z, M);
-  w.flags[0] = 0;
-  w.flags[1] = -1;
-
-  // the state words alone (h == nullptr), or with the history of pairs
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_pcg_ws_read_async");
-  };
-
-  // {rz0, rr0}: one all-reduce of 2 doubles
-  throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, 0, nullptr),
-                 "spmv_hip_pcg_reduce_rz_rr");
-  comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, 0,
-                          "spmv_hip_pcg_ws_rz_rr"),
-                  2, w.stream);
-
-  std::vector<void*>& timing_ev = w.timing_ev;
-  LaggingPoll poll(exec, w, opt.poll_every, kmax);
-  int k = 0;
-  while (k < kmax && !poll.stopped) {
-    ++k;
-    col_l2g->update(w.p); // starts on the side stream
-    void* ev1 = nullptr;
-    if (opt.time_spmv) {
-      ev1 = timing_ev[2 * (size_t)(k - 1) + 1];
-      exec.record_event(timing_ev[2 * (size_t)(k - 1)], w.stream);
-    }
-    // Ap = A p with the p.Ap partials produced by the SpMV kernels themselves
-    // (local block's share + remote block's share) where they can
-    const bool fused = A.mult_dot(w.p, w.Ap, partials, w.dot2, ev1);
-    if (!fused) {
-      throw_on_error(spmv_hip_dot_partial_f64(ctx, M, w.p, w.Ap, partials,
-                                              nullptr),
-                     "spmv_hip_dot_partial_f64");
-      throw_on_error(spmv_hip_pcg_reduce_pAp(ctx, w.ws, k, nullptr),
-                     "spmv_hip_pcg_reduce_pAp");
-    } else {
-      throw_on_error(spmv_hip_pcg_reduce_pAp2(ctx, w.ws, k, w.dot2, nullptr),
-                     "spmv_hip_pcg_reduce_pAp2");
-    }
-    comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_pAp, k, "spmv_hip_pcg_ws_pAp"),
-                    1, w.stream);
-    throw_on_error(spmv_hip_sgs_update_r_f64(ctx, w.ws, k, M, w.Ap, w.r, nullptr),
-                   "spmv_hip_sgs_update_r_f64");
-    precondition();
-    throw_on_error(spmv_hip_pcg_reduce_rz_rr(ctx, w.ws, k, nullptr),
-                   "spmv_hip_pcg_reduce_rz_rr");
-    comm.reduce_sum(ws_slot(w.ws, spmv_hip_pcg_ws_rz_rr, k,
-                            "spmv_hip_pcg_ws_rz_rr"),
-                    2, w.stream); // rz[k] and rr[k] at once
-    throw_on_error(spmv_hip_cheb_update_xp_f64(ctx, w.ws, k, M, w.z, xi, w.p,
-                                               nullptr),
-                   "spmv_hip_cheb_update_xp_f64");
-
-    poll.step(k, read);
-  }
-
-  // final state: {done, kstop} and the history of pairs {rz[k], rr[k]}
-  const std::vector<double> zr
-      = read_history(spmv_hip_pcg_ws_capacity, w.ws, kmax, 2, read);
-  if (xi != x)
-    exec.copy<double>(x, xi, M);
-  exec.synchronize_stream(w.stream);
-
-  if (stats) {
-    *stats = CgStats();
-    if (opt.time_spmv)
-      sum_spmv_times(ctx, timing_ev, 2 * (size_t)k, *stats);
-  }
-
-  auto rr_at = [&](int j) { return zr[2 * (size_t)j + 1]; };
-  int k_final;
-  if (w.flags[0] != 0)
-    k_final = w.flags[1];
-  else if (rr_at(0) == 0.0)
-    k_final = 0; // (kmax == 0: no kernel ran to say so)
-  else // `done` is raised by the first reducer of the NEXT iteration
-    k_final = first_k_below(rr_at, k, rtol);
-  write_history(rnorm_history, k_final, rr_at);
-  return k_final;
+  return pcg_solve(
+      "pcg_sgs", comm, exec, A, dims, b, x, nullptr, kmax, rtol, rnorm_history,
+      opt, stats, workspace, 1, {},
+      // r = b, x0 = 0, partials of r.r: one pass; then z0 = M^-1 r0 and p1 = z0
+      [&](Solve& s) {
+        throw_on_error(spmv_hip_sgs_init_f64(s.ctx, s.w.ws, s.M, b, s.w.r, s.xi,
+                                             nullptr),
+                       "spmv_hip_sgs_init_f64");
+        precondition(s);
+        exec.copy<double>(s.w.p, s.w.z, s.M);
+      },
+      [&](Solve& s, int k) {
+        stored_z_iteration(s, k, [&] {
+          throw_on_error(spmv_hip_sgs_update_r_f64(s.ctx, s.w.ws, k, s.M, s.w.Ap,
+                                                   s.w.r, nullptr),
+                         "spmv_hip_sgs_update_r_f64");
+          precondition(s);
+        });
+      });
 }
 
 double lambda_max_estimate(const Comm& comm, HipExecutor& exec,
