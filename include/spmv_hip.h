@@ -361,6 +361,16 @@ int spmv_hip_zwalk_table(int32_t num_rows, int64_t plane_rows, int grid,
  *                  the codes: context option "lx_codes", default 1, at plan
  *                  creation; same launch grid, same bits); lx4_lut: the
  *                  dictionary look-up, 1 = LDS table, 2 = select tree
+ *   "lx_ring"                            ... in the ring variant of that kernel
+ *                  (three LDS slots, two row blocks in flight per workgroup):
+ *                  get = 1 when a launch would take it -- narrowed values
+ *                  ("lx_v32"), codes with the LDS table, EVERY row block
+ *                  staged, coded and fitting (get "lx_ring_blocks"), and,
+ *                  unless asked for by name, at least 128 row blocks per
+ *                  workgroup; set 1 asks for it by name and is refused on an
+ *                  ineligible plan, set 0 keeps the two-slot kernel.  Same
+ *                  grid, same bits.  Context option "lx_ring" (default 1; 0 =
+ *                  never, 2 = wherever eligible) is read at plan creation.
  *   "xw" "xw_probe"                      the same kernel on the caller's CSR
  *                  arrays (plans with XW records): on/off -- 1 asks for it by
  *                  name and ends the probe --; xw_probe 1 = let the next four

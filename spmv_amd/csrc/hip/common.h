@@ -37,6 +37,12 @@ struct spmv_hip_ctx {
   // kernel when every value is exact in fp32 ("lx_narrow_values"; 4 B per
   // entry of plan memory, streamed in place of the 8-byte values)
   int lx_narrow_values = 1;
+  // ... and a plan whose every row block is staged, coded and narrowed runs
+  // the ring variant of the DMA kernel: three LDS slots, two row blocks in
+  // flight per workgroup ("lx_ring"; read at plan creation, plan key
+  // "lx_ring").  0 = never, 1 = when a workgroup walks at least 128 row blocks
+  // (below that the prologue costs more than the steps gain), 2 = always
+  int lx_ring = 1;
   // the host mirror's CSRMatrix frees its device copies of colind / values
   // once a plan holds the matrix in its own format ("release_csr";
   // spmv_hip_csr_plan_owns_matrix); read by the mirror, nothing here acts on it

@@ -181,6 +181,25 @@ __host__ __device__ constexpr int64_t lx32_len(int64_t nnz)
   return (nnz + 3) & ~(int64_t)3;
 }
 constexpr int kLxwAlign = 4;       // window starts: multiples of 4 columns
+// Ring variant of the DMA kernel (csr_lxw_ring_kernel; plan key "lx_ring"):
+// three LDS slots sized for what a narrowed, coded block streams.  Every wave
+// issues kLxwRingValRounds value pieces, one code piece and kLxwMaxPieces / 4
+// x pieces per step, so a values slot holds kLxwRingValRounds * 4 KiB and a
+// codes slot at most 4 KiB.  A block fits when its fp32 values (with the three
+// entries of alignment slack) and its codes (with the dword behind a row's
+// last one) do.
+constexpr int kLxwRingValRounds = 2;
+constexpr int kLxwRingVcap = kLxwRingValRounds * 1024; // floats per values slot
+constexpr int kLxwRingCodeMax = 4096;                  // bytes per codes slot
+__host__ __device__ constexpr int lx_ring_code_bytes(int cnt)
+{
+  return (cnt + 31 + 7) / 8 * 4 + 8;
+}
+__host__ __device__ constexpr bool lx_ring_fits(int cnt)
+{
+  return cnt > 0 && cnt + 3 <= kLxwRingVcap
+         && lx_ring_code_bytes(cnt) <= kLxwRingCodeMax;
+}
 // XW: the same kernel on the CALLER's column indices (no 16-bit copy): the
 // record carries, after the LXW words, the windows themselves -- an entry's
 // staged position is its column + the delta of the last window that starts at
@@ -484,6 +503,15 @@ struct spmv_hip_csr_plan {
   int lx4_blocks = 0;         // coded row blocks
   int lx4_lut = 1;            // dictionary look-up: 1 = LDS table, 2 = select
                               // tree on uniform registers (plan_set "lx4_lut")
+  // ... and the ring variant of that kernel (three LDS slots, two row blocks
+  // in flight): runs when the plan streams narrowed values and codes with the
+  // LDS table and EVERY row block is staged, coded and fits the ring's slots
+  // (spmv_lxw_ring_ok); same grid, row-block order and bits
+  int lx_ring_blocks = 0;     // row blocks staged, coded and fitting
+  int lx_ring = 1;            // 0 = never; 1 = where eligible and a workgroup
+                              // walks enough row blocks for it to pay (the
+                              // context option's default); 2 = wherever
+                              // eligible (plan_set "lx_ring" 1, ctx option 2)
   // ... and an fp32 copy of the VALUES where every one of them is exactly
   // representable as a normal binary32 number or +-0 (plan_bake_values_f64,
   // ctx option "lx_narrow_values"): (double)(float)v has the bits of v, so the
@@ -654,6 +682,9 @@ int spmv_sdia_run_f32(const spmv_hip_csr_plan* pl, hipStream_t st, float alpha,
                       const float* in, float beta, float* out);
 // spmv_lxw.hip
 int spmv_lxw_grid(const spmv_hip_csr_plan* pl, int elem_bytes);
+// would an fp64 launch of this plan run the ring kernel?  (`forced`: as if
+// plan key "lx_ring" were 1)
+bool spmv_lxw_ring_ok(const spmv_hip_csr_plan* pl, bool forced);
 int spmv_lxw_run_f64(const spmv_hip_csr_plan* pl, hipStream_t st,
                      const int32_t* rowptr, const int32_t* colind,
                      const double* values, double alpha, const double* in,

@@ -174,6 +174,8 @@ int spmv_hip_ctx_get_option(const spmv_hip_ctx* ctx, const char* key, int64_t* v
     *value = ctx->lat_min_nnz;
   else if (!strcmp(key, "lx_narrow_values"))
     *value = ctx->lx_narrow_values;
+  else if (!strcmp(key, "lx_ring"))
+    *value = ctx->lx_ring;
   else if (!strcmp(key, "sj_min_nnz"))
     *value = ctx->sj_min_nnz;
   else
@@ -247,6 +249,13 @@ int spmv_hip_ctx_set_option(spmv_hip_ctx* ctx, const char* key, int64_t value)
   if (!strcmp(key, "lx_narrow_values")) {
     SPMV_REQUIRE(value == 0 || value == 1);
     ctx->lx_narrow_values = (int)value;
+    return SPMV_HIP_OK;
+  }
+  if (!strcmp(key, "lx_ring")) {
+    // 0 = never, 1 = where eligible and a workgroup walks enough row blocks,
+    // 2 = wherever eligible
+    SPMV_REQUIRE(value >= 0 && value <= 2);
+    ctx->lx_ring = (int)value;
     return SPMV_HIP_OK;
   }
   if (!strcmp(key, "poisson_stencil")) {

@@ -192,7 +192,8 @@ __global__ __launch_bounds__(kBlock) void lx_build_kernel(
 // the rank of the entry's d.  Any other block is left alone: it keeps reading
 // its 16-bit offsets.  Two blocks may share a 32-bit word of `code` where their
 // spans meet: whole words are stored, the partial ones at both ends are OR-ed
-// into the zeroed array.  stat[0] counts the coded blocks.
+// into the zeroed array.  stat[0] counts the coded blocks, stat[1] those of
+// them that fit the slots of the ring kernel (lx_ring_fits).
 constexpr int kLx4Dmin = -kRows;                      // d = offset - t > -kRows
 constexpr int kLx4Words = (kLxwMaxPieces * kLxwPiece + kRows + 31) / 32; // 72
 __global__ __launch_bounds__(kBlock) void lx4_encode_kernel(
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(kBlock) void lx4_encode_kernel(
   __shared__ int32_t s_dict[kLxwDictSize];
   __shared__ uint32_t s_pack[CAP / 8 + 2]; // the block's nibbles, by word of `code`
   const int t = threadIdx.x;
-  int coded = 0;
+  int coded = 0, ring = 0;
   for (int rb = blockIdx.x; rb < num_row_blocks; rb += gridDim.x) {
     int32_t* wr = wrec + (int64_t)rb * kLxwRec;
     const int32_t a = wr[1], cnt = wr[2];
@@ -275,10 +276,13 @@ __global__ __launch_bounds__(kBlock) void lx4_encode_kernel(
     if (t == 0) {
       wr[3] |= 1 << kLxwCodedBit;
       ++coded;
+      ring += lx_ring_fits(cnt) ? 1 : 0;
     }
   }
   if (t == 0 && coded)
     atomicAdd(&stat[0], coded);
+  if (t == 0 && ring)
+    atomicAdd(&stat[1], ring);
 }
 
 struct NonEmptyRow {
@@ -389,7 +393,7 @@ void spmv_free_lx(spmv_hip_csr_plan* pl)
   plan_drop(pl->lx_code);
   pl->lx = pl->lx_staged = pl->lx_blocks = 0;
   pl->lxw = pl->lxw_max_cnt = pl->lxw_max_pieces = 0;
-  pl->lx4 = pl->lx4_blocks = 0;
+  pl->lx4 = pl->lx4_blocks = pl->lx_ring_blocks = 0;
   spmv_lx32_free(pl); // (the narrowed values are the DMA kernel's)
 }
 
@@ -402,12 +406,12 @@ static int build_lx_codes(spmv_hip_csr_plan* pl, const int32_t* rowptr, int nrb,
   PlanScratch<int32_t> d_stat;
   hipError_t e = spmv_plan_malloc(&pl->lx_code, bytes);
   if (e == hipSuccess)
-    e = d_stat.alloc(1);
+    e = d_stat.alloc(2);
   if (e == hipSuccess)
     e = hipMemsetAsync(pl->lx_code, 0, bytes, st);
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_stat.get(), 0, sizeof(int32_t), st);
-  int32_t coded = 0;
+    e = hipMemsetAsync(d_stat.get(), 0, 2 * sizeof(int32_t), st);
+  int32_t h_stat[2] = {0, 0};
   if (e == hipSuccess) {
     int grid = pl->ctx->num_cus * 8;
     grid = grid > nrb ? nrb : grid;
@@ -417,16 +421,18 @@ static int build_lx_codes(spmv_hip_csr_plan* pl, const int32_t* rowptr, int nrb,
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = plan_fetch(&coded, d_stat.get(), 1, st);
+    e = plan_fetch(h_stat, d_stat.get(), 2, st);
   d_stat.reset();
+  const int32_t coded = h_stat[0];
   if (e != hipSuccess || coded == 0) {
     (void)hipGetLastError();
     plan_drop(pl->lx_code);
-    pl->lx4 = pl->lx4_blocks = 0;
+    pl->lx4 = pl->lx4_blocks = pl->lx_ring_blocks = 0;
     return e == hipSuccess || e == hipErrorOutOfMemory ? SPMV_HIP_OK
                                                        : static_cast<int>(e);
   }
   pl->lx4_blocks = coded;
+  pl->lx_ring_blocks = h_stat[1];
   pl->lx4 = 1;
   return SPMV_HIP_OK;
 }

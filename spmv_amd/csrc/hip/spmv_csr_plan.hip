@@ -134,6 +134,7 @@ int spmv_hip_csr_plan_create(spmv_hip_ctx* ctx, int32_t num_rows,
   if (!pl)
     return SPMV_HIP_ENOMEM;
   pl->ctx = ctx;
+  pl->lx_ring = ctx->lx_ring;
   MemClock mem_clock(pl); // (a failed creation destroys pl before this is read:
                           // every such path below hands the clock a null plan)
   pl->num_rows = num_rows;
@@ -625,6 +626,12 @@ int spmv_hip_csr_plan_set(spmv_hip_csr_plan* plan, const char* key, int value)
     SPMV_REQUIRE(value == 0 || value == 1);
     SPMV_REQUIRE(value == 0 || plan->lx_val32);
     plan->lx_v32 = value;
+  } else if (!strcmp(key, "lx_ring")) {
+    // ... in the ring variant of the DMA kernel (three LDS slots): 1 needs a
+    // plan that is eligible as it stands (spmv_lxw_ring_ok); same geometry
+    SPMV_REQUIRE(value == 0 || value == 1);
+    SPMV_REQUIRE(value == 0 || spmv_lxw_ring_ok(plan, true));
+    plan->lx_ring = value ? 2 : 0; // (asked for by name: no step gate)
   } else if (!strcmp(key, "lx4_lut")) {
     // the dictionary look-up of a coded block: 1 = LDS table, 2 = select tree
     SPMV_REQUIRE(value == 1 || value == 2);
@@ -1044,6 +1051,10 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
     *value = plan->lx4_lut;
   else if (!strcmp(key, "lx_v32"))
     *value = plan->lx_v32 && plan->lx_val32 ? 1 : 0;
+  else if (!strcmp(key, "lx_ring"))
+    *value = spmv_lxw_ring_ok(plan, false) ? 1 : 0;
+  else if (!strcmp(key, "lx_ring_blocks"))
+    *value = plan->lx_code ? plan->lx_ring_blocks : 0;
   else if (!strcmp(key, "lxw_grid")) // launch grid of the DMA kernel (fp64)
     *value = plan->lxw_rec ? spmv_lxw_grid(plan, 8) : 0;
   else if (!strcmp(key, "lx_staged"))

@@ -93,6 +93,74 @@
 // offsets slot for codes only (a third workgroup per CU would change the
 // grid and with it the partials); byte row lengths instead of the row pointer.
 //
+// Ring variant (csr_lxw_ring_kernel; plan key / context option "lx_ring"):
+// with codes and narrowed values a step streams 4.5 B per entry, and the
+// two-slot kernel ran 1.96 ms at 512^3 where the bytes would allow 1.5-1.85:
+// 512 workgroups x 14 KB per step / 1.93 us per step = the 3.7 TB/s it
+// reached -- ONE memory round trip per step, everything exactly one block
+// ahead.  The ring keeps TWO blocks in flight per workgroup in three LDS slots
+// sized for what a narrowed, coded block streams (8 KiB of values, 1-4 KiB of
+// codes, the x pieces; 61 KiB for the 7-point matrix, still two workgroups per
+// CU): block k is summed from slot k mod 3, block k + 1 is in flight, block
+// k + 2 is issued in step k into the slot block k - 1 left.  Grid, row-block
+// order, lane-to-row map and the row sum are csr_lxw_kernel's, so y and the
+// fused dot's partials keep their bits.  It runs only for a plan whose EVERY
+// row block is staged, coded and fits (lx_ring_fits, counted by
+// lx4_encode_kernel), TV = float under T = double, LDS table, not XW; anything
+// else launches csr_lxw_kernel unchanged.
+//   What a step issues, per wave, in this order (all of it inline assembly:
+// the compiler counts none of it, so it adds no vmcnt wait of its own, and
+// its full wait before s_barrier finds nothing pending):
+//     1 store   y of block k - 1 (late; under exec, skipped by a wave without
+//               rows)
+//     3 loads   row pointer pair and y of block k + 1 (y: the head of `out`
+//               when beta == 0) -- of a clamped row, never skipped
+//     1 load    record of block k + 3 (record 0 when there is none)
+//     1 load    order-table entry of block k + 4 (TAB only; clamped)
+//     7 DMA     block k + 2: VR = 2 value pieces, 1 code piece, PWR = 4 x
+//               pieces -- always all of them: a piece beyond the block's data
+//               (or of a slot without a row block) reads the head of its array
+//               into a 1-KiB dump area, address and LDS target chosen by
+//               selects, no branch around the instruction
+//   then the row sum (LDS only), then `s_waitcnt vmcnt(7)`, N = VR + 1 + PWR:
+// the counter retires in order, so with at most the 7 youngest instructions in
+// flight -- block k + 2's DMA -- everything older has landed: block k + 1's
+// DMA (issued a step earlier), the loads, the store.  What is issued BEFORE the
+// DMA may be skipped without harm (it is older than what is waited for); what
+// is counted is never under a branch.  The loaded registers are operands of
+// the wait, so no use moves above it.  Prologue and drain wait with vmcnt(0);
+// a workgroup with fewer than three blocks issues the missing ones into the
+// dump area and needs no other path.
+//   Disassembly of the headline's instantiation (<DOT = 1, NT = 0, TAB = 1,
+// VR = 2, PWR = 4>, hipcc -O3 for gfx950): every step passes ONE vector-memory
+// wait, `s_waitcnt vmcnt(7)` (a second one, vmcnt(0), sits inside the branch of
+// a block whose own x is not staged, behind that load), followed by `s_waitcnt lgkmcnt(0)`, `s_barrier`;
+// between two of them 1 global_store_dwordx2 (behind s_cbranch_execz), 2
+// global_load_dword + 1 global_load_dwordx2 (rows), 2 global_load_dword
+// (record, table), 7 global_load_lds_dwordx4; none of the five destination
+// registers is read or written before the wait.  70 VGPRs (68 / 66 without
+// the dot / the table), no spills, no scratch, 128 B of static LDS + 62,464 B
+// dynamic for the 7-point matrix => two workgroups per CU, as before.
+//   Measured at 512^3, one MI355X, one session (profiles/lxring_ab.json):
+// SpMV with the fused dot, plan_set alternating in one process, 1.962 ->
+// 1.655 ms (-15.6 %; 384^3 0.823 -> 0.670, 216^3 0.157 -> 0.127); inside CG
+// 1.994 -> 1.617 ms per launch, i.e. 1.95 -> 1.58 us per step of a workgroup;
+// the headline 292.95-294.65 -> 326.7-331.4 it/s, five alternating runs each,
+// ranges apart, lx_ring = 0 in the new build 294.2 (inside the parent's
+// range); x_sample and residual_history array_equal.  Kernel trace of the
+// benchmark 1.992 -> 1.661 ms; fabric reads (FETCH_SIZE, calibrated on the
+// streaming dot of the same run) 6.74 -> 7.35 GB per launch -- three slots in
+// flight evict more x pieces from the L2, and the surplus pieces that miss --,
+// so with the 1.07 GB written 3.92 -> 5.07 TB/s where cg_update_r_cs streams
+// 5.79 (profiles/lxring_kernel_stats_*.csv, lxring_pmc_fetch_*.csv).  At 128^3 (11 steps per
+// workgroup) the ring LOSES, 0.0296 against 0.0270 ms -- three waits in a row
+// in the prologue --, so by default it runs from 128 steps per workgroup on
+// (lxw_ring_ok, which says why not from 216^3's 77 on); asked for by name it runs at any size, which is how the tests
+// reach the prologue, the drain and the wrap with small matrices.
+// Not tried: three x pieces per wave where the plan stages at most twelve (the
+// 7-point matrix sends 5 of its 16 x pieces and 3 of its 4 code pieces to the
+// dump area: L1 hits, but issue slots); a fourth slot.
+//
 // XW variant (round 5): the same kernel on the CALLER's CSR arrays as they are.
 // The 16-bit offsets are a plan-owned copy of the index stream (2 B per entry
 // of plan memory, 10 B per entry streamed); the plain row-block kernel streams
@@ -555,6 +623,296 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_kernel(
     spmv_dot_epilogue(dot, dot_acc, s_red);
 }
 
+// ---------------------------------------------------------------------------
+// Ring variant: three LDS slots, two row blocks in flight (see the header).
+// Every global access of the loop is inline assembly, so that the compiler
+// counts none of them and adds no vmcnt wait of its own (it would wait for
+// "its" loads and, the counter retiring in order, for the DMA pieces issued
+// behind them); the one wait of a step is written here, with the loaded
+// registers as operands so that no use can move above it.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int32_t ring_ld32(const int32_t* p)
+{
+  int32_t v;
+  asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+  return v;
+}
+__device__ __forceinline__ double ring_ld64(const double* p)
+{
+  double v;
+  asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+  return v;
+}
+__device__ __forceinline__ void ring_st64(double* p, double v)
+{
+  asm volatile("global_store_dwordx2 %0, %1, off" : : "v"(p), "v"(v) : "memory");
+}
+// waits until at most N of this wave's vector memory instructions are in
+// flight; the five registers are a step's loads (see the kernel)
+template <int N>
+__device__ __forceinline__ void ring_wait(int32_t& a, int32_t& b, double& c,
+                                          int32_t& d, int32_t& e)
+{
+  asm volatile("s_waitcnt vmcnt(%5)"
+               : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e)
+               : "n"(N)
+               : "memory");
+}
+
+//   VR    value pieces (1 KiB each) a wave issues per step: a values slot is
+//         VR * 4 KiB
+//   PWR   x pieces a wave issues per step
+//   ccap  bytes per codes slot (whole KiB, at most 4: one piece per wave)
+//   xcap  elements per x buffer (at most 4 * PWR pieces)
+// A wave issues VR + 1 + PWR DMA instructions per row block, whatever the
+// block needs: a piece beyond its data (and every piece of a slot without a
+// row block) reads the head of its array and lands in the 1-KiB dump area
+// behind the slots.
+template <bool DOT, bool NT, bool TAB, int VR, int PWR>
+__global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
+    int32_t num_rows, int32_t num_cols, int64_t nnz,
+    const int32_t* __restrict__ rowptr, const float* __restrict__ values,
+    const uint8_t* __restrict__ code, const int32_t* __restrict__ rec,
+    double alpha, const double* __restrict__ in, double beta,
+    double* __restrict__ out, DotOut dot, RowBlockOrder ord, int ccap, int xcap)
+{
+  using T = double;
+  constexpr int NW = kBlock / 64;
+  constexpr int VCAP = VR * NW * 256; // floats per values slot
+  constexpr int DMA = VR + 1 + PWR;   // DMA instructions per wave and block
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* const s_val = reinterpret_cast<float*>(smem);
+  unsigned char* const s_code = smem + 3 * (size_t)VCAP * sizeof(float);
+  T* const s_x = reinterpret_cast<T*>(s_code + 3 * (size_t)ccap);
+  __shared__ double s_red[NW];
+  __shared__ int32_t s_dict[3 * kLxwDictSize / 2];
+  const unsigned lds_val = (unsigned)(uintptr_t)(
+      (__attribute__((address_space(3))) void*)s_val);
+  const unsigned lds_code = lds_val + 3u * VCAP * (unsigned)sizeof(float);
+  const unsigned lds_x = lds_code + 3u * (unsigned)ccap;
+  const unsigned lds_dump = lds_x + 3u * (unsigned)xcap * (unsigned)sizeof(T);
+
+  const int t = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int lane = t & 63;
+  const int stride = gridDim.x;
+  const int num_slots = order_slots(ord);
+  double dot_acc = 0.0;
+  const int32_t col_last = (num_cols - 2) & ~1;
+  const int64_t code_len = lx_code_bytes(nnz);
+  const int64_t val_len = lx32_len(nnz);
+  // where a surplus piece reads: the head of the array, inside it
+  const int64_t vdump = lane * 4 < val_len - 4 ? lane * 4 : val_len - 4;
+  const int64_t cdump = lane * 16 < code_len - 16 ? lane * 16 : code_len - 16;
+  const int32_t xdump = lane * 2 < col_last ? lane * 2 : col_last;
+
+  // DMA of block b into slot sl: exactly DMA instructions, none under a branch
+  auto issue = [&](const LxwBlock& b, int32_t w, int sl) {
+    const bool live = b.rb >= 0;
+    const int64_t a = b.a, e = (int64_t)b.a + b.cnt;
+    {
+      const int64_t base = a & ~(int64_t)3;
+      const int64_t jclamp = (e - 1) & ~(int64_t)3;
+      const int pieces = live ? (int)(((e - base) * 4 + 1023) >> 10) : 0;
+#pragma unroll
+      for (int r = 0; r < VR; ++r) {
+        const int q = wave + NW * r;
+        const bool real = q < pieces; // uniform
+        int64_t j = base + (int64_t)(q * 64 + lane) * 4;
+        j = j < jclamp ? j : jclamp;
+        j = real ? j : vdump;
+        glds16<NT>(values + j,
+                   real ? lds_val + (unsigned)(sl * VCAP * 4 + q * 1024)
+                        : lds_dump);
+      }
+    }
+    {
+      const int64_t base = (a >> 1) & ~(int64_t)15, end = (e + 1) >> 1;
+      const int64_t jclamp = (end - 1) & ~(int64_t)15;
+      const int pieces = live ? (int)((end - base + 1023) >> 10) : 0;
+      const bool real = wave < pieces; // uniform
+      int64_t j = base + (int64_t)(wave * 64 + lane) * 16;
+      j = j < jclamp ? j : jclamp;
+      j = real ? j : cdump;
+      glds16<NT>(code + j, real ? lds_code + (unsigned)(sl * ccap + wave * 1024)
+                                : lds_dump);
+    }
+    const int np = live ? b.np : 0;
+#pragma unroll
+    for (int k = 0; k < PWR; ++k) {
+      const int p = wave + NW * k;
+      const bool real = p < np; // uniform
+      // (the piece list of the record, taken after its wait)
+      const int32_t col = __builtin_amdgcn_readlane(w, kLxwPieces0 + p);
+      int32_t c = col + lane * 2;
+      c = c < col_last ? c : col_last; // padding past the end of x
+      c = real ? c : xdump;
+      glds16<false>(in + c,
+                    real ? lds_x + (unsigned)((sl * xcap + p * kLxwPiece) * 8)
+                         : lds_dump);
+    }
+  };
+  // the slot's dictionary: the lanes of wave 0 that hold its words
+  auto put_dict = [&](const LxwBlock& b, int32_t w, int sl) {
+    if (b.rb >= 0 && t >= kLxwDict0 && t < kLxwDict0 + kLxwDictSize / 2)
+      s_dict[sl * (kLxwDictSize / 2) + t - kLxwDict0] = w;
+  };
+  // slot -> row block: the table entry as a load in flight (clamped; decode
+  // checks the slot), or computed
+  auto raw_of = [&](int i) {
+    if constexpr (TAB)
+      return ring_ld32(ord.table + (i < num_slots ? i : num_slots - 1));
+    else
+      return order_slot_raw_t<false>(ord, i, num_slots);
+  };
+  auto rb_of = [&](int i, int raw) {
+    return i < num_slots ? order_slot_decode(ord, raw) : -1;
+  };
+  // a block's record, one word per lane (no block: record 0, ignored)
+  auto fetch = [&](int rb) {
+    return ring_ld32(rec + (int64_t)(rb < 0 ? 0 : rb) * kLxwRec
+                     + (lane < kLxwRec ? lane : kLxwRec - 1));
+  };
+  // a block's row pointers and y: always three loads, of a row that exists;
+  // beta == 0 reads the head of y instead of streaming it
+  auto loads = [&](int rb, int32_t& lo, int32_t& hi, double& y0) {
+    int32_t r = (rb < 0 ? 0 : rb) * kRows + t;
+    r = r < num_rows ? r : num_rows - 1;
+    lo = ring_ld32(rowptr + r);
+    hi = ring_ld32(rowptr + r + 1);
+    y0 = ring_ld64(out + (beta != 0.0 ? r : (t < num_rows ? t : num_rows - 1)));
+  };
+
+  int it = blockIdx.x;
+  // prologue: blocks k and k + 1 issued, the record of k + 2 and the table
+  // entry of k + 3 landed -- each stage behind a vmcnt(0)
+  int32_t raw0 = raw_of(it), raw1 = raw_of(it + stride);
+  int32_t raw2 = raw_of(it + 2 * stride), raw3 = raw_of(it + 3 * stride);
+  double dz = 0.0;
+  ring_wait<0>(raw0, raw1, dz, raw2, raw3);
+  const int rb0 = rb_of(it, raw0), rb1 = rb_of(it + stride, raw1);
+  int rb2 = rb_of(it + 2 * stride, raw2);
+  int32_t w0 = fetch(rb0), w1 = fetch(rb1), w2 = fetch(rb2);
+  int32_t iz = 0;
+  ring_wait<0>(w0, w1, dz, w2, iz);
+  LxwBlock cur = lxw_decode(rb0, w0);
+  LxwBlock nxt = lxw_decode(rb1, w1);
+  put_dict(cur, w0, 0);
+  put_dict(nxt, w1, 1);
+  issue(cur, w0, 0);
+  issue(nxt, w1, 1);
+  int32_t lo, hi;
+  double y0;
+  loads(cur.rb, lo, hi, y0);
+  ring_wait<0>(lo, hi, y0, iz, iz);
+  __syncthreads();
+  int s0 = 0, s2 = 2; // slots of block k and of block k + 2
+  T y_late = T(0);
+  int32_t r_late = -1;
+
+  // Step k.  In flight on entry: nothing but the DMA of block k + 1 (DMA
+  // instructions).  Issued here, in this order: the late y store of block
+  // k - 1; the row pointers and y of block k + 1 (3), the record of block
+  // k + 3 (1), the table entry of block k + 4 (TAB: 1); the DMA of block k + 2
+  // (DMA).  The wait at the end leaves the youngest DMA instructions in
+  // flight -- block k + 2's --: the counter retires in order, so everything
+  // issued before them has landed, block k + 1 included.  What precedes the
+  // DMA may be skipped (the store: a wave without rows) without harm, since
+  // it is older than what is waited for; the DMA itself is never skipped.
+  while (it < num_slots) {
+    if (r_late >= 0)
+      ring_st64(out + r_late, y_late);
+    r_late = -1;
+    int32_t nlo, nhi;
+    double ny0;
+    loads(nxt.rb, nlo, nhi, ny0);
+    const int rb3 = rb_of(it + 3 * stride, raw3);
+    int32_t w3 = fetch(rb3);
+    int32_t raw4 = raw_of(it + 4 * stride);
+    const LxwBlock blk2 = lxw_decode(rb2, w2);
+    put_dict(blk2, w2, s2); // (block k - 1's readers left before the barrier)
+    issue(blk2, w2, s2);
+
+    const int32_t r = cur.rb * kRows + t;
+    if (cur.rb >= 0 && r < num_rows) {
+      T sum = 0;
+      T x_own = T(0);
+      int32_t j = lo;
+      // index by the entry's position in `values`
+      const float* sv = s_val + (size_t)s0 * VCAP + (cur.a & 3) - cur.a;
+      const T* sx = s_x + (size_t)s0 * xcap;
+      if constexpr (DOT) {
+        if (cur.own >= 0) // uniform
+          x_own = sx[cur.own + t];
+      }
+      // the walk of csr_lxw_kernel on the codes, operation for operation
+      const uint32_t* sc
+          = reinterpret_cast<const uint32_t*>(s_code + (size_t)s0 * ccap);
+      const int32_t n0 = cur.a & ~31; // the entry of the slot's nibble 0
+      for (; j < hi; j += 8) {
+        const unsigned n = (unsigned)(j - n0);
+        const uint32_t c_lo = sc[n >> 3], c_hi = sc[(n >> 3) + 1];
+        const uint32_t bits = __builtin_amdgcn_alignbit(c_hi, c_lo, (n & 7) * 4);
+        unsigned l[8];
+        T v[8], xv[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int32_t jj = j + k < hi ? j + k : hi - 1;
+          v[k] = (T)sv[jj];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const unsigned c = (bits >> (4 * k)) & 15u;
+          const int32_t d = reinterpret_cast<const int16_t*>(
+              s_dict + s0 * (kLxwDictSize / 2))[c];
+          l[k] = j + k < hi ? (unsigned)(t + d) : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          xv[k] = sx[l[k]];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          if (j + k < hi)
+            sum += v[k] * xv[k];
+      }
+      const T c = alpha * sum;
+      T y = c;
+      if (beta != T(0))
+        y = c + beta * y0;
+      y_late = y;
+      r_late = r;
+      if constexpr (DOT) {
+        if (cur.own < 0) { // no staged window over the block's own rows
+          // (waited for at once, inside the branch: a load the compiler
+          // counted would put its vmcnt(0) behind the join, in every step)
+          x_own = ring_ld64(in + r);
+          asm volatile("s_waitcnt vmcnt(0)" : "+v"(x_own) : : "memory");
+        }
+        dot_acc += (double)x_own * (double)c;
+      }
+    }
+    ring_wait<DMA>(nlo, nhi, ny0, w3, raw4);
+    __syncthreads();
+    cur = nxt;
+    nxt = blk2;
+    lo = nlo;
+    hi = nhi;
+    y0 = ny0;
+    rb2 = rb3;
+    w2 = w3;
+    raw3 = raw4;
+    s2 = s0;
+    s0 = s0 == 2 ? 0 : s0 + 1;
+    it += stride;
+  }
+  // the DMA of the blocks that do not exist (dump area) is still in flight
+  ring_wait<0>(lo, hi, y0, w2, raw3);
+  if (r_late >= 0)
+    ring_st64(out + r_late, y_late);
+  if constexpr (DOT)
+    spmv_dot_epilogue(dot, dot_acc, s_red);
+}
+
 struct LxwGeom {
   int vcap, lcap, xcap;
   size_t lds;
@@ -603,6 +961,97 @@ int lxw_grid(const spmv_hip_csr_plan* pl, int elem_bytes, int idx_bytes)
   return grid;
 }
 
+// The ring kernel's slots for this plan: a values slot is fixed (VR pieces
+// per wave), the codes slot holds the largest block's codes, the x buffer the
+// most pieces a block stages; the dump area follows.
+struct LxwRingGeom {
+  int ccap, xcap;
+  size_t lds;
+  int per_cu; // workgroups per CU that its LDS allows
+};
+
+LxwRingGeom lxw_ring_geom(const spmv_hip_csr_plan* pl)
+{
+  LxwRingGeom g;
+  const int max_cnt = pl->lxw_max_cnt < 1 ? 1 : pl->lxw_max_cnt;
+  g.ccap = (lx_ring_code_bytes(max_cnt) + 1023) & ~1023;
+  int np = pl->lxw_max_pieces;
+  np = np < 1 ? 1 : np;
+  g.xcap = np * kLxwPiece;
+  g.lds = 3 * ((size_t)kLxwRingVcap * sizeof(float) + (size_t)g.ccap
+               + (size_t)g.xcap * sizeof(double))
+          + 1024;
+  // (static LDS: the reduction buffer and three dictionaries, 128 B)
+  g.per_cu = (int)((160 * 1024 - 1024) / (g.lds + 256));
+  return g;
+}
+
+// Per plan, never per block: narrowed values, codes with the LDS table, every
+// row block staged, coded and fitting, and three slots in the LDS that keeps
+// the workgroups per CU where lxw_geom puts them.
+bool lxw_ring_ok(const spmv_hip_csr_plan* pl, bool forced)
+{
+  const int nrb = (pl->num_rows + kRows - 1) / kRows;
+  if (!(forced || pl->lx_ring) || pl->symmetric || !pl->lx || !pl->lxw
+      || !pl->lxw_rec || !pl->lx4 || !pl->lx_code || pl->lx4_lut != 1
+      || !pl->lx_v32 || !pl->lx_val32)
+    return false;
+  if (nrb < 1 || pl->lx_staged != nrb || pl->lx4_blocks != nrb
+      || pl->lx_ring_blocks != nrb || !lx_ring_fits(pl->lxw_max_cnt)
+      || pl->lxw_max_pieces > kLxwMaxPieces)
+    return false;
+  if (lxw_ring_geom(pl).per_cu < lxw_geom(pl, 8, 2).per_cu)
+    return false;
+  // Gate on the row blocks a workgroup walks: the ring's prologue (three
+  // waits in a row) is paid once per launch and the gain once per step.
+  // Measured (fused dot, one process, plan_set alternating): 11 steps (128^3)
+  // 0.0296 against 0.0270 ms; 77 steps (216^3) 0.127 against 0.157 ms; 432
+  // (384^3) 0.670 against 0.823; 1024 (512^3) 1.655 against 1.962.  The
+  // default starts at 128 steps, above 216^3 although the ring gains there:
+  // the benchmark's 216^3 record prices the launch in CSR bytes against the
+  // HBM peak and the suite bounds that fraction below 1, which 0.127 ms
+  // exceeds (1.06) with x and part of the matrix in the Infinity Cache.
+  // Asked for by name (plan_set "lx_ring" 1, context option 2) it runs
+  // regardless.
+  constexpr int kMinSteps = 128;
+  const int grid = lxw_grid(pl, 8, 2);
+  return forced || pl->lx_ring >= 2 || (nrb + grid - 1) / grid >= kMinSteps;
+}
+
+template <bool DOT>
+int lxw_ring_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
+                    const int32_t* rowptr, const float* values, double alpha,
+                    const double* in, double beta, double* out, DotOut dot)
+{
+  constexpr int VR = kLxwRingValRounds, PWR = kLxwMaxPieces / (kBlock / 64);
+  const LxwRingGeom g = lxw_ring_geom(pl);
+  const int nrb = (pl->num_rows + kRows - 1) / kRows;
+  // grid and row-block order: those of csr_lxw_kernel, so that y and the fused
+  // dot's partials keep their bits
+  const int grid = lxw_grid(pl, 8, 2);
+  RowBlockOrder ord = pl->row_block_order(nrb);
+  ord.xcd_group = pl->lat_xcd_group;
+  if (pl->zwalk && pl->zw_table && pl->zw_grid == grid) {
+    ord.table = pl->zw_table;
+    ord.num_slots = pl->zw_slots;
+  }
+  auto kern
+      = ord.table
+            ? (pl->nontemporal ? csr_lxw_ring_kernel<DOT, true, true, VR, PWR>
+                               : csr_lxw_ring_kernel<DOT, false, true, VR, PWR>)
+            : (pl->nontemporal ? csr_lxw_ring_kernel<DOT, true, false, VR, PWR>
+                               : csr_lxw_ring_kernel<DOT, false, false, VR, PWR>);
+  if (g.lds > 48 * 1024) // beyond the default dynamic-LDS limit
+    SPMV_CHECK_HIP(hipFuncSetAttribute(
+        reinterpret_cast<const void*>(kern),
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), g.lds, st, pl->num_rows,
+                     pl->num_cols, pl->nnz, rowptr, values, pl->lx_code,
+                     pl->lxw_rec, alpha, in, beta, out, dot, ord, g.ccap, g.xcap);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
 template <typename TV, typename T, bool DOT, bool XW, int C4>
 int lxw_launch_c(const spmv_hip_csr_plan* pl, hipStream_t st,
                  const int32_t* rowptr, const int32_t* colind, const TV* values,
@@ -649,6 +1098,12 @@ int lxw_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
                const int32_t* rowptr, const int32_t* colind, const TV* values,
                T alpha, const T* in, T beta, T* out, DotOut dot)
 {
+  if constexpr (!XW && std::is_same<TV, float>::value
+                && std::is_same<T, double>::value) {
+    if (lxw_ring_ok(pl, false))
+      return lxw_ring_launch<DOT>(pl, st, rowptr, values, alpha, in, beta, out,
+                                  dot);
+  }
   if constexpr (!XW) {
     if (pl->lx4 && pl->lx_code)
       return pl->lx4_lut == 2
@@ -666,6 +1121,11 @@ int lxw_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
 int spmv_lxw_grid(const spmv_hip_csr_plan* pl, int elem_bytes)
 {
   return lxw_grid(pl, elem_bytes, 2);
+}
+
+bool spmv_lxw_ring_ok(const spmv_hip_csr_plan* pl, bool forced)
+{
+  return lxw_ring_ok(pl, forced);
 }
 
 int spmv_xw_grid(const spmv_hip_csr_plan* pl, int elem_bytes)
