@@ -371,6 +371,16 @@ int spmv_hip_zwalk_table(int32_t num_rows, int64_t plane_rows, int grid,
  *                  ineligible plan, set 0 keeps the two-slot kernel.  Same
  *                  grid, same bits.  Context option "lx_ring" (default 1; 0 =
  *                  never, 2 = wherever eligible) is read at plan creation.
+ *                  The ring kernel reads a row's span from the plan's row
+ *                  descriptors (get "lx_rowdesc" = 1 when the plan has them;
+ *                  2 B per row, built with the DMA records): a row block
+ *                  with a row of more than 31 entries is not eligible.
+ *   "lx_ring_pwr"                        x pieces a wave of the ring kernel
+ *                  issues per step: 0 = 3 where the plan stages at most 12
+ *                  pieces, else 4 (get: the figure in use); 4 = always 4
+ *   "lxw_grid_cap"                       at most that many workgroups in the
+ *                  DMA kernels' grid (0 = no cap): lets a small matrix give a
+ *                  workgroup many row blocks
  *   "xw" "xw_probe"                      the same kernel on the caller's CSR
  *                  arrays (plans with XW records): on/off -- 1 asks for it by
  *                  name and ends the probe --; xw_probe 1 = let the next four

@@ -200,6 +200,24 @@ __host__ __device__ constexpr bool lx_ring_fits(int cnt)
   return cnt > 0 && cnt + 3 <= kLxwRingVcap
          && lx_ring_code_bytes(cnt) <= kLxwRingCodeMax;
 }
+// ... and its row descriptors (plan array lx_rowdesc): one 16-bit word per
+// row, kRows per row block (512 B, 16-byte aligned), which the ring kernel
+// takes by LDS-DMA instead of loading the row pointer pair:
+//   bits 0..10   the row's first entry relative to the block's span start
+//                (record word [1]); a fitting block has at most 2045 entries
+//   bits 11..15  the row's length, at most kLxwDescMaxLen
+// A block with a longer row is not counted in lx_ring_blocks.  The array ends
+// with kLxwDescPad bytes of padding: a whole 1-KiB DMA piece starting at the
+// last block's words lies inside it.
+constexpr int kLxwDescStartBits = 11;
+constexpr int kLxwDescStartMask = (1 << kLxwDescStartBits) - 1;
+constexpr int kLxwDescMaxLen = (1 << (16 - kLxwDescStartBits)) - 1; // 31
+static_assert(kLxwRingVcap <= kLxwDescStartMask + 1, "a row's start needs more bits");
+constexpr int kLxwDescPad = 1024 - kRows * 2;
+__host__ __device__ constexpr int64_t lx_rowdesc_bytes(int64_t num_row_blocks)
+{
+  return num_row_blocks * (kRows * 2) + kLxwDescPad;
+}
 // XW: the same kernel on the CALLER's column indices (no 16-bit copy): the
 // record carries, after the LXW words, the windows themselves -- an entry's
 // staged position is its column + the delta of the last window that starts at
@@ -492,6 +510,9 @@ struct spmv_hip_csr_plan {
   int lxw_max_cnt = 0;        // most entries in a staged row block
   int lxw_max_pieces = 0;     // most staged pieces of a row block
   int lxw_blocks_per_cu = 0;  // 0 = what the LDS footprint allows
+  int lxw_grid_cap = 0;       // > 0: at most this many workgroups (plan_set
+                              // "lxw_grid_cap"; lets a small matrix give a
+                              // workgroup many row blocks)
   // ... with 4-bit codes in place of the 16-bit offsets (a SECOND index array,
   // 0.5 B per entry, beside lx_lidx): an offset is the row's lane t plus one of
   // the few distances d the block's diagonals and windows give; a row block
@@ -507,7 +528,12 @@ struct spmv_hip_csr_plan {
   // in flight): runs when the plan streams narrowed values and codes with the
   // LDS table and EVERY row block is staged, coded and fits the ring's slots
   // (spmv_lxw_ring_ok); same grid, row-block order and bits
-  int lx_ring_blocks = 0;     // row blocks staged, coded and fitting
+  int lx_ring_blocks = 0;     // row blocks staged, coded and fitting, no row
+                              // longer than a descriptor holds
+  uint16_t* lx_rowdesc = nullptr; // lx_rowdesc_bytes(row blocks); pattern only
+  int lx_ring_pwr = 0;        // x pieces a wave issues per step: 0 = 3 where
+                              // the plan stages at most 12, else 4; 4 = always
+                              // 4 (plan_set "lx_ring_pwr")
   int lx_ring = 1;            // 0 = never; 1 = where eligible and a workgroup
                               // walks enough row blocks for it to pay (the
                               // context option's default); 2 = wherever

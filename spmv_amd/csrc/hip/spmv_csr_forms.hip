@@ -193,7 +193,9 @@ __global__ __launch_bounds__(kBlock) void lx_build_kernel(
 // its 16-bit offsets.  Two blocks may share a 32-bit word of `code` where their
 // spans meet: whole words are stored, the partial ones at both ends are OR-ed
 // into the zeroed array.  stat[0] counts the coded blocks, stat[1] those of
-// them that fit the slots of the ring kernel (lx_ring_fits).
+// them the ring kernel can take: they fit its slots (lx_ring_fits) and no row
+// is longer than a row descriptor holds (kLxwDescMaxLen; the descriptors
+// themselves: lx_rowdesc_kernel).
 constexpr int kLx4Dmin = -kRows;                      // d = offset - t > -kRows
 constexpr int kLx4Words = (kLxwMaxPieces * kLxwPiece + kRows + 31) / 32; // 72
 __global__ __launch_bounds__(kBlock) void lx4_encode_kernel(
@@ -273,16 +275,47 @@ __global__ __launch_bounds__(kBlock) void lx4_encode_kernel(
     }
     if (t < kLxwDictSize / 2)
       wr[kLxwDict0 + t] = (s_dict[2 * t] & 0xffff) | (s_dict[2 * t + 1] << 16);
+    // (every lane is here: the `continue`s above are uniform)
+    const bool ringable
+        = !__syncthreads_or(hi - lo > kLxwDescMaxLen) && lx_ring_fits(cnt);
     if (t == 0) {
       wr[3] |= 1 << kLxwCodedBit;
       ++coded;
-      ring += lx_ring_fits(cnt) ? 1 : 0;
+      ring += ringable ? 1 : 0;
     }
   }
   if (t == 0 && coded)
     atomicAdd(&stat[0], coded);
   if (t == 0 && ring)
     atomicAdd(&stat[1], ring);
+}
+
+// Row descriptors of the ring kernel (csr_plan.h: first entry relative to the
+// block's span start | length << 11, one 16-bit word per row): one workgroup
+// per row block, lane = row.  Written for every staged block that fits the
+// ring's slots and has no row longer than kLxwDescMaxLen -- the blocks
+// lx4_encode_kernel counts, whether or not they end up coded; every other word
+// of the zeroed array, the rows past the matrix included, stays 0.
+__global__ __launch_bounds__(kBlock) void lx_rowdesc_kernel(
+    int32_t num_rows, const int32_t* __restrict__ rowptr,
+    const int32_t* __restrict__ wrec, uint16_t* __restrict__ desc,
+    int num_row_blocks)
+{
+  const int t = threadIdx.x;
+  for (int rb = blockIdx.x; rb < num_row_blocks; rb += gridDim.x) {
+    const int32_t* wr = wrec + (int64_t)rb * kLxwRec;
+    const int32_t a = wr[1], cnt = wr[2];
+    const int32_t r = rb * kRows + t;
+    int32_t lo = 0, hi = 0;
+    if (r < num_rows) {
+      lo = rowptr[r];
+      hi = rowptr[r + 1];
+    }
+    const bool too_long = __syncthreads_or(hi - lo > kLxwDescMaxLen);
+    if (wr[0] >= 0 && lx_ring_fits(cnt) && !too_long && r < num_rows)
+      desc[(int64_t)rb * kRows + t]
+          = (uint16_t)((lo - a) | ((hi - lo) << kLxwDescStartBits));
+  }
 }
 
 struct NonEmptyRow {
@@ -391,6 +424,7 @@ void spmv_free_lx(spmv_hip_csr_plan* pl)
   plan_drop(pl->lx_tab);
   plan_drop(pl->lxw_rec);
   plan_drop(pl->lx_code);
+  plan_drop(pl->lx_rowdesc);
   pl->lx = pl->lx_staged = pl->lx_blocks = 0;
   pl->lxw = pl->lxw_max_cnt = pl->lxw_max_pieces = 0;
   pl->lx4 = pl->lx4_blocks = pl->lx_ring_blocks = 0;
@@ -399,6 +433,34 @@ void spmv_free_lx(spmv_hip_csr_plan* pl)
 
 // The 4-bit codes of the DMA kernel (lx4_encode_kernel), after the records and
 // the 16-bit offsets: 0.5 B per entry.  Out of memory: the plan goes without.
+// The ring kernel's row descriptors (lx_rowdesc_kernel), with the DMA records:
+// 2 B per row.  They depend on the pattern alone, so no bake and no
+// plan_values_changed touches them.  Out of memory: the plan goes without and
+// keeps the two-slot kernel (spmv_lxw_ring_ok asks for the array).
+static int build_lx_rowdesc(spmv_hip_csr_plan* pl, const int32_t* rowptr, int nrb,
+                            hipStream_t st)
+{
+  const size_t bytes = (size_t)lx_rowdesc_bytes(nrb);
+  hipError_t e = spmv_plan_malloc(&pl->lx_rowdesc, bytes);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(pl->lx_rowdesc, 0, bytes, st);
+  if (e == hipSuccess) {
+    int grid = pl->ctx->num_cus * 8;
+    grid = grid > nrb ? nrb : grid;
+    hipLaunchKernelGGL(lx_rowdesc_kernel, dim3(grid), dim3(kBlock), 0, st,
+                       pl->num_rows, rowptr, pl->lxw_rec, pl->lx_rowdesc, nrb);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    plan_drop(pl->lx_rowdesc);
+    return e == hipErrorOutOfMemory ? SPMV_HIP_OK : static_cast<int>(e);
+  }
+  return SPMV_HIP_OK;
+}
+
 static int build_lx_codes(spmv_hip_csr_plan* pl, const int32_t* rowptr, int nrb,
                           hipStream_t st)
 {
@@ -815,6 +877,11 @@ int spmv_build_lx(spmv_hip_csr_plan* pl, const int32_t* rowptr,
   }
   pl->lx = 1;
   pl->lxw = pl->lxw_rec != nullptr;
+  if (pl->lxw_rec) {
+    const int rc = build_lx_rowdesc(pl, rowptr, nrb, st);
+    if (rc != SPMV_HIP_OK)
+      return rc;
+  }
   if (pl->lxw_rec && pl->ctx->lx_codes) {
     const int rc = build_lx_codes(pl, rowptr, nrb, st);
     if (rc != SPMV_HIP_OK)

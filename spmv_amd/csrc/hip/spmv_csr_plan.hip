@@ -632,6 +632,16 @@ int spmv_hip_csr_plan_set(spmv_hip_csr_plan* plan, const char* key, int value)
     SPMV_REQUIRE(value == 0 || value == 1);
     SPMV_REQUIRE(value == 0 || spmv_lxw_ring_ok(plan, true));
     plan->lx_ring = value ? 2 : 0; // (asked for by name: no step gate)
+  } else if (!strcmp(key, "lxw_grid_cap")) {
+    // at most this many workgroups in the DMA kernels' grid (0 = no cap); an
+    // order table built for another grid is not used
+    SPMV_REQUIRE(value >= 0);
+    plan->lxw_grid_cap = value;
+  } else if (!strcmp(key, "lx_ring_pwr")) {
+    // ... issuing 3 x pieces per wave and step where the plan stages at most
+    // 12 (0 or 3: the default), or 4 everywhere (4)
+    SPMV_REQUIRE(value == 0 || value == 3 || value == 4);
+    plan->lx_ring_pwr = value == 4 ? 4 : 0;
   } else if (!strcmp(key, "lx4_lut")) {
     // the dictionary look-up of a coded block: 1 = LDS table, 2 = select tree
     SPMV_REQUIRE(value == 1 || value == 2);
@@ -938,6 +948,8 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
       b += 4 * nrb * kLxwRec;
     if (plan->lx_code)
       b += lx_code_bytes(nnz);
+    if (plan->lx_rowdesc)
+      b += lx_rowdesc_bytes(nrb);
     if (plan->lx_val32)
       b += 4 * lx32_len(nnz);
     if (plan->xw_rec)
@@ -1055,6 +1067,12 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
     *value = spmv_lxw_ring_ok(plan, false) ? 1 : 0;
   else if (!strcmp(key, "lx_ring_blocks"))
     *value = plan->lx_code ? plan->lx_ring_blocks : 0;
+  else if (!strcmp(key, "lxw_grid_cap"))
+    *value = plan->lxw_grid_cap;
+  else if (!strcmp(key, "lx_ring_pwr"))
+    *value = plan->lx_ring_pwr != 4 && plan->lxw_max_pieces <= 12 ? 3 : 4;
+  else if (!strcmp(key, "lx_rowdesc")) // the ring kernel's row descriptors
+    *value = plan->lx_rowdesc ? 1 : 0;
   else if (!strcmp(key, "lxw_grid")) // launch grid of the DMA kernel (fp64)
     *value = plan->lxw_rec ? spmv_lxw_grid(plan, 8) : 0;
   else if (!strcmp(key, "lx_staged"))

@@ -100,8 +100,8 @@
 // reached -- ONE memory round trip per step, everything exactly one block
 // ahead.  The ring keeps TWO blocks in flight per workgroup in three LDS slots
 // sized for what a narrowed, coded block streams (8 KiB of values, 1-4 KiB of
-// codes, the x pieces; 61 KiB for the 7-point matrix, still two workgroups per
-// CU): block k is summed from slot k mod 3, block k + 1 is in flight, block
+// codes, the x pieces, 512 B of row descriptors; 61.6 KiB for the 7-point
+// matrix, still two workgroups per CU): block k is summed from slot k mod 3, block k + 1 is in flight, block
 // k + 2 is issued in step k into the slot block k - 1 left.  Grid, row-block
 // order, lane-to-row map and the row sum are csr_lxw_kernel's, so y and the
 // fused dot's partials keep their bits.  It runs only for a plan whose EVERY
@@ -113,53 +113,77 @@
 // its full wait before s_barrier finds nothing pending):
 //     1 store   y of block k - 1 (late; under exec, skipped by a wave without
 //               rows)
-//     3 loads   row pointer pair and y of block k + 1 (y: the head of `out`
-//               when beta == 0) -- of a clamped row, never skipped
+//     1 load    y of block k + 1 (the head of `out` when beta == 0) -- of a
+//               clamped row, never skipped
 //     1 load    record of block k + 3 (record 0 when there is none)
 //     1 load    order-table entry of block k + 4 (TAB only; clamped)
-//     7 DMA     block k + 2: VR = 2 value pieces, 1 code piece, PWR = 4 x
-//               pieces -- always all of them: a piece beyond the block's data
-//               (or of a slot without a row block) reads the head of its array
-//               into a 1-KiB dump area, address and LDS target chosen by
-//               selects, no branch around the instruction
-//   then the row sum (LDS only), then `s_waitcnt vmcnt(7)`, N = VR + 1 + PWR:
-// the counter retires in order, so with at most the 7 youngest instructions in
-// flight -- block k + 2's DMA -- everything older has landed: block k + 1's
-// DMA (issued a step earlier), the loads, the store.  What is issued BEFORE the
-// DMA may be skipped without harm (it is older than what is waited for); what
-// is counted is never under a branch.  The loaded registers are operands of
-// the wait, so no use moves above it.  Prologue and drain wait with vmcnt(0);
-// a workgroup with fewer than three blocks issues the missing ones into the
-// dump area and needs no other path.
-//   Disassembly of the headline's instantiation (<DOT = 1, NT = 0, TAB = 1,
-// VR = 2, PWR = 4>, hipcc -O3 for gfx950): every step passes ONE vector-memory
+//     N DMA     block k + 2: VR = 2 value pieces, 1 code piece -- in wave 2 the
+//               block's ROW DESCRIPTORS instead --, PWR x pieces; N = VR + 1 +
+//               PWR, always all of them: a piece beyond the block's data (or
+//               of a slot without a row block) reads the head of its array
+//               into the dump area by lane 0 alone; address, LDS target and
+//               lane count are chosen by selects
+//   then the row sum (LDS only), then `s_waitcnt vmcnt(N)`: the counter retires
+// in order, so with at most the N youngest instructions in flight -- block
+// k + 2's DMA -- everything older has landed: block k + 1's DMA (issued a step
+// earlier), the loads, the store.  What is issued BEFORE the DMA may be
+// skipped without harm (it is older than what is waited for).  Every DMA
+// instruction stands behind a lane mask (64 lanes, 32 for the descriptors, 1
+// for a surplus piece) and the s_cbranch_execz the compiler puts there; lane
+// 0 always takes part, so the branch is never taken and the count is exact.
+// The loaded registers are operands of the wait, so no use moves above it.
+// Prologue and drain wait with vmcnt(0); a workgroup with fewer than three
+// blocks issues the missing ones into the dump area and needs no other path.
+//   Row descriptors (plan array lx_rowdesc, csr_plan.h; lx_rowdesc_kernel):
+// one 16-bit word per row, bits 0..10 the row's first entry relative to the
+// block's span start `a`, bits 11..15 its length (at most 31; a block with a
+// longer row is not counted in lx_ring_blocks and the plan keeps
+// csr_lxw_kernel).  A block's 512 B arrive with its DMA -- a fitting block's
+// codes fill at most two pieces, so wave 2's code piece was surplus in every
+// block -- into 512 B per slot, and the row sum takes lo and hi from one
+// ds_read_u16 plus `a`.  Before, every lane loaded rowptr[r] and rowptr[r + 1]
+// into registers the step waited for: 0.54 GB per launch at 512^3, now 0.27.
+// A surplus piece used to be a whole 1-KiB piece read from the head of its
+// array into a 1-KiB dump area; issued by lane 0 alone it moves 16 B, the dump
+// area is 64 B, and the three descriptor slots fit where it was: 63,040 B of
+// dynamic LDS for the 7-point matrix (62,464 before), two workgroups per CU.
+//   PWR: 4 x pieces per wave cover every plan (16 pieces); a plan that stages
+// at most 12 (the 7-point matrix: 11) runs the instantiation with 3 -- one
+// DMA instruction less per wave and step, vmcnt(6).  Plan key "lx_ring_pwr" 4
+// asks for the other one.
+//   Disassembly of the instantiation <DOT = 1, NT = 0, TAB = 1, VR = 2,
+// PWR = 4> (hipcc -O3 for gfx950): every step passes ONE vector-memory
 // wait, `s_waitcnt vmcnt(7)` (a second one, vmcnt(0), sits inside the branch of
-// a block whose own x is not staged, behind that load), followed by `s_waitcnt lgkmcnt(0)`, `s_barrier`;
-// between two of them 1 global_store_dwordx2 (behind s_cbranch_execz), 2
-// global_load_dword + 1 global_load_dwordx2 (rows), 2 global_load_dword
-// (record, table), 7 global_load_lds_dwordx4; none of the five destination
-// registers is read or written before the wait.  70 VGPRs (68 / 66 without
-// the dot / the table), no spills, no scratch, 128 B of static LDS + 62,464 B
-// dynamic for the 7-point matrix => two workgroups per CU, as before.
-//   Measured at 512^3, one MI355X, one session (profiles/lxring_ab.json):
-// SpMV with the fused dot, plan_set alternating in one process, 1.962 ->
-// 1.655 ms (-15.6 %; 384^3 0.823 -> 0.670, 216^3 0.157 -> 0.127); inside CG
-// 1.994 -> 1.617 ms per launch, i.e. 1.95 -> 1.58 us per step of a workgroup;
-// the headline 292.95-294.65 -> 326.7-331.4 it/s, five alternating runs each,
-// ranges apart, lx_ring = 0 in the new build 294.2 (inside the parent's
-// range); x_sample and residual_history array_equal.  Kernel trace of the
-// benchmark 1.992 -> 1.661 ms; fabric reads (FETCH_SIZE, calibrated on the
-// streaming dot of the same run) 6.74 -> 7.35 GB per launch -- three slots in
-// flight evict more x pieces from the L2, and the surplus pieces that miss --,
-// so with the 1.07 GB written 3.92 -> 5.07 TB/s where cg_update_r_cs streams
-// 5.79 (profiles/lxring_kernel_stats_*.csv, lxring_pmc_fetch_*.csv).  At 128^3 (11 steps per
-// workgroup) the ring LOSES, 0.0296 against 0.0270 ms -- three waits in a row
-// in the prologue --, so by default it runs from 128 steps per workgroup on
-// (lxw_ring_ok, which says why not from 216^3's 77 on); asked for by name it runs at any size, which is how the tests
-// reach the prologue, the drain and the wrap with small matrices.
-// Not tried: three x pieces per wave where the plan stages at most twelve (the
-// 7-point matrix sends 5 of its 16 x pieces and 3 of its 4 code pieces to the
-// dump area: L1 hits, but issue slots); a fourth slot.
+// a block whose own x is not staged, behind that load), followed by `s_waitcnt
+// lgkmcnt(0)`, `s_barrier`; between two of them 1 global_store_dwordx2 (behind
+// s_cbranch_execz), 1 global_load_dwordx2 (y), 2 global_load_dword (record,
+// table), 7 global_load_lds_dwordx4; none of the three destination registers
+// is read or written before the wait; one ds_read_u16 per row.  70 VGPRs, no
+// spills, no scratch, 128 B of static LDS.
+//   Measured at 512^3, one MI355X, one session against the parent (three
+// slots, row pointers by register loads, PWR = 4; profiles/lxdesc_ab.json):
+// SpMV with the fused dot, plan_set alternating in one process, two-slot
+// 1.957-1.962, ring PWR = 4 1.614-1.616, PWR = 3 1.543-1.548 ms (-4.3 %,
+// ranges apart; the parent's ring measured 1.654-1.656 in its own session).
+// With PWR = 4 the headline did not move: parent 324.98-327.46, new
+// 325.29-326.62 it/s, ranges overlapping -- the descriptors alone are no gain
+// that can be told from noise.  With PWR = 3: parent 324.19-324.66, new
+// 332.09-333.11 it/s, five alternating runs each, ranges apart (+2.5 %);
+// x_sample and residual_history array_equal.  Kernel trace of the benchmark
+// 1.638 -> 1.591 ms per launch; fabric reads (FETCH_SIZE, calibrated on the
+// streaming dot of the same run) 7.12 -> 6.21 GB per launch -- 0.27 GB of row
+// pointers, the rest surplus pieces that missed and x pieces they evicted
+// (profiles/lxdesc_kernel_stats_*.csv, lxdesc_pmc_fetch_*.csv).  The ring's
+// history: profiles/lxring_ab.json (two-slot 1.962 -> ring 1.655 ms; headline
+// 292.95-294.65 -> 326.7-331.4 it/s).  At 128^3 (11 steps per workgroup) the
+// ring LOSES, 0.0296 against 0.0270 ms -- three waits in a row in the prologue
+// --, so by default it runs from 128 steps per workgroup on (lxw_ring_ok,
+// which says why not from 216^3's 77 on); asked for by name it runs at any
+// size, which is how the tests reach the prologue, the drain and the wrap
+// with small matrices (plan key "lxw_grid_cap" gives a small matrix's
+// workgroups many row blocks).
+// Not tried: a fourth slot; two x pieces per wave for plans that stage at
+// most eight.
 //
 // XW variant (round 5): the same kernel on the CALLER's CSR arrays as they are.
 // The 16-bit offsets are a plan-owned copy of the index stream (2 B per entry
@@ -648,13 +672,22 @@ __device__ __forceinline__ void ring_st64(double* p, double v)
   asm volatile("global_store_dwordx2 %0, %1, off" : : "v"(p), "v"(v) : "memory");
 }
 // waits until at most N of this wave's vector memory instructions are in
-// flight; the five registers are a step's loads (see the kernel)
+// flight; the registers are the loads in flight (see the kernel): five in the
+// prologue, three in a step
 template <int N>
 __device__ __forceinline__ void ring_wait(int32_t& a, int32_t& b, double& c,
                                           int32_t& d, int32_t& e)
 {
   asm volatile("s_waitcnt vmcnt(%5)"
                : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e)
+               : "n"(N)
+               : "memory");
+}
+template <int N>
+__device__ __forceinline__ void ring_wait(double& c, int32_t& d, int32_t& e)
+{
+  asm volatile("s_waitcnt vmcnt(%3)"
+               : "+v"(c), "+v"(d), "+v"(e)
                : "n"(N)
                : "memory");
 }
@@ -666,13 +699,23 @@ __device__ __forceinline__ void ring_wait(int32_t& a, int32_t& b, double& c,
 //   xcap  elements per x buffer (at most 4 * PWR pieces)
 // A wave issues VR + 1 + PWR DMA instructions per row block, whatever the
 // block needs: a piece beyond its data (and every piece of a slot without a
-// row block) reads the head of its array and lands in the 1-KiB dump area
-// behind the slots.
+// row block) reads the head of its array and lands in the dump area behind
+// the slots.  The "+ 1" is a code piece in waves 0, 1 and 3 and the
+// block's row descriptors (`desc`, csr_plan.h) in wave kRingDescWave: a
+// fitting block's codes fill at most two pieces, so that wave's code piece
+// was surplus in every block.
+constexpr int kRingDescWave = 2;
+// A surplus piece is issued by lane 0 alone (the other lanes sit it out: the
+// instruction still issues and is still counted), so the dump area holds one
+// lane's 16 bytes, not a piece.
+constexpr int kRingDumpBytes = 64;
+static_assert(lx_ring_code_bytes(kLxwRingVcap - 3) <= kRingDescWave * 1024,
+              "a fitting block's codes reach the descriptor wave's piece");
 template <bool DOT, bool NT, bool TAB, int VR, int PWR>
 __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
     int32_t num_rows, int32_t num_cols, int64_t nnz,
-    const int32_t* __restrict__ rowptr, const float* __restrict__ values,
-    const uint8_t* __restrict__ code, const int32_t* __restrict__ rec,
+    const float* __restrict__ values, const uint8_t* __restrict__ code,
+    const uint16_t* __restrict__ desc, const int32_t* __restrict__ rec,
     double alpha, const double* __restrict__ in, double beta,
     double* __restrict__ out, DotOut dot, RowBlockOrder ord, int ccap, int xcap)
 {
@@ -684,13 +727,17 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
   float* const s_val = reinterpret_cast<float*>(smem);
   unsigned char* const s_code = smem + 3 * (size_t)VCAP * sizeof(float);
   T* const s_x = reinterpret_cast<T*>(s_code + 3 * (size_t)ccap);
+  // row descriptors: 512 B per slot (half a DMA piece: lanes 0..31)
+  const uint16_t* const s_desc = reinterpret_cast<const uint16_t*>(
+      reinterpret_cast<unsigned char*>(s_x) + 3 * (size_t)xcap * sizeof(T));
   __shared__ double s_red[NW];
   __shared__ int32_t s_dict[3 * kLxwDictSize / 2];
   const unsigned lds_val = (unsigned)(uintptr_t)(
       (__attribute__((address_space(3))) void*)s_val);
   const unsigned lds_code = lds_val + 3u * VCAP * (unsigned)sizeof(float);
   const unsigned lds_x = lds_code + 3u * (unsigned)ccap;
-  const unsigned lds_dump = lds_x + 3u * (unsigned)xcap * (unsigned)sizeof(T);
+  const unsigned lds_desc = lds_x + 3u * (unsigned)xcap * (unsigned)sizeof(T);
+  const unsigned lds_dump = lds_desc + 3u * (unsigned)(kRows * 2);
 
   const int t = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -721,9 +768,11 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
         int64_t j = base + (int64_t)(q * 64 + lane) * 4;
         j = j < jclamp ? j : jclamp;
         j = real ? j : vdump;
-        glds16<NT>(values + j,
-                   real ? lds_val + (unsigned)(sl * VCAP * 4 + q * 1024)
-                        : lds_dump);
+        // (a surplus piece: lane 0 alone -- issued, counted, 16 B written)
+        if (lane < (real ? 64 : 1))
+          glds16<NT>(values + j,
+                     real ? lds_val + (unsigned)(sl * VCAP * 4 + q * 1024)
+                          : lds_dump);
       }
     }
     {
@@ -734,8 +783,19 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
       int64_t j = base + (int64_t)(wave * 64 + lane) * 16;
       j = j < jclamp ? j : jclamp;
       j = real ? j : cdump;
-      glds16<NT>(code + j, real ? lds_code + (unsigned)(sl * ccap + wave * 1024)
-                                : lds_dump);
+      // wave kRingDescWave: the block's 512 B of row descriptors instead (no
+      // block: those of row block 0), by its lanes 0..31 -- the others sit the
+      // instruction out, so it writes half a piece; never all lanes of a
+      // wave, so the instruction is always issued and always counted
+      const bool dsc = wave == kRingDescWave; // uniform
+      const uint8_t* const src
+          = dsc ? reinterpret_cast<const uint8_t*>(desc)
+                      + (int64_t)(live ? b.rb : 0) * (kRows * 2) + (lane & 31) * 16
+                : code + j;
+      if (lane < (dsc ? 32 : real ? 64 : 1))
+        glds16<NT>(src, dsc ? lds_desc + (unsigned)(sl * (kRows * 2))
+                            : real ? lds_code + (unsigned)(sl * ccap + wave * 1024)
+                                   : lds_dump);
     }
     const int np = live ? b.np : 0;
 #pragma unroll
@@ -747,9 +807,10 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
       int32_t c = col + lane * 2;
       c = c < col_last ? c : col_last; // padding past the end of x
       c = real ? c : xdump;
-      glds16<false>(in + c,
-                    real ? lds_x + (unsigned)((sl * xcap + p * kLxwPiece) * 8)
-                         : lds_dump);
+      if (lane < (real ? 64 : 1))
+        glds16<false>(in + c,
+                      real ? lds_x + (unsigned)((sl * xcap + p * kLxwPiece) * 8)
+                           : lds_dump);
     }
   };
   // the slot's dictionary: the lanes of wave 0 that hold its words
@@ -773,13 +834,11 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
     return ring_ld32(rec + (int64_t)(rb < 0 ? 0 : rb) * kLxwRec
                      + (lane < kLxwRec ? lane : kLxwRec - 1));
   };
-  // a block's row pointers and y: always three loads, of a row that exists;
-  // beta == 0 reads the head of y instead of streaming it
-  auto loads = [&](int rb, int32_t& lo, int32_t& hi, double& y0) {
+  // a block's y: always one load, of a row that exists; beta == 0 reads the
+  // head of y instead of streaming it
+  auto loads = [&](int rb, double& y0) {
     int32_t r = (rb < 0 ? 0 : rb) * kRows + t;
     r = r < num_rows ? r : num_rows - 1;
-    lo = ring_ld32(rowptr + r);
-    hi = ring_ld32(rowptr + r + 1);
     y0 = ring_ld64(out + (beta != 0.0 ? r : (t < num_rows ? t : num_rows - 1)));
   };
 
@@ -801,10 +860,9 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
   put_dict(nxt, w1, 1);
   issue(cur, w0, 0);
   issue(nxt, w1, 1);
-  int32_t lo, hi;
   double y0;
-  loads(cur.rb, lo, hi, y0);
-  ring_wait<0>(lo, hi, y0, iz, iz);
+  loads(cur.rb, y0);
+  ring_wait<0>(y0, iz, iz);
   __syncthreads();
   int s0 = 0, s2 = 2; // slots of block k and of block k + 2
   T y_late = T(0);
@@ -812,7 +870,7 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
 
   // Step k.  In flight on entry: nothing but the DMA of block k + 1 (DMA
   // instructions).  Issued here, in this order: the late y store of block
-  // k - 1; the row pointers and y of block k + 1 (3), the record of block
+  // k - 1; the y of block k + 1 (1), the record of block
   // k + 3 (1), the table entry of block k + 4 (TAB: 1); the DMA of block k + 2
   // (DMA).  The wait at the end leaves the youngest DMA instructions in
   // flight -- block k + 2's --: the counter retires in order, so everything
@@ -823,9 +881,8 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
     if (r_late >= 0)
       ring_st64(out + r_late, y_late);
     r_late = -1;
-    int32_t nlo, nhi;
     double ny0;
-    loads(nxt.rb, nlo, nhi, ny0);
+    loads(nxt.rb, ny0);
     const int rb3 = rb_of(it + 3 * stride, raw3);
     int32_t w3 = fetch(rb3);
     int32_t raw4 = raw_of(it + 4 * stride);
@@ -837,7 +894,10 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
     if (cur.rb >= 0 && r < num_rows) {
       T sum = 0;
       T x_own = T(0);
-      int32_t j = lo;
+      // the row's span: its descriptor (landed with the block's DMA) + cur.a
+      const int32_t dsc = s_desc[s0 * kRows + t];
+      int32_t j = cur.a + (dsc & kLxwDescStartMask);
+      const int32_t hi = j + (dsc >> kLxwDescStartBits);
       // index by the entry's position in `values`
       const float* sv = s_val + (size_t)s0 * VCAP + (cur.a & 3) - cur.a;
       const T* sx = s_x + (size_t)s0 * xcap;
@@ -891,12 +951,10 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
         dot_acc += (double)x_own * (double)c;
       }
     }
-    ring_wait<DMA>(nlo, nhi, ny0, w3, raw4);
+    ring_wait<DMA>(ny0, w3, raw4);
     __syncthreads();
     cur = nxt;
     nxt = blk2;
-    lo = nlo;
-    hi = nhi;
     y0 = ny0;
     rb2 = rb3;
     w2 = w3;
@@ -906,7 +964,7 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
     it += stride;
   }
   // the DMA of the blocks that do not exist (dump area) is still in flight
-  ring_wait<0>(lo, hi, y0, w2, raw3);
+  ring_wait<0>(y0, w2, raw3);
   if (r_late >= 0)
     ring_st64(out + r_late, y_late);
   if constexpr (DOT)
@@ -954,6 +1012,8 @@ int lxw_grid(const spmv_hip_csr_plan* pl, int elem_bytes, int idx_bytes)
     grid = pl->ctx->dot_blocks;
   if (grid > nrb)
     grid = nrb;
+  if (pl->lxw_grid_cap > 0 && grid > pl->lxw_grid_cap)
+    grid = pl->lxw_grid_cap; // (tests: many steps per workgroup, small matrix)
   if (grid < 1)
     grid = 1;
   if (grid >= 8)
@@ -979,8 +1039,8 @@ LxwRingGeom lxw_ring_geom(const spmv_hip_csr_plan* pl)
   np = np < 1 ? 1 : np;
   g.xcap = np * kLxwPiece;
   g.lds = 3 * ((size_t)kLxwRingVcap * sizeof(float) + (size_t)g.ccap
-               + (size_t)g.xcap * sizeof(double))
-          + 1024;
+               + (size_t)g.xcap * sizeof(double) + kRows * 2) // (descriptors)
+          + kRingDumpBytes;
   // (static LDS: the reduction buffer and three dictionaries, 128 B)
   g.per_cu = (int)((160 * 1024 - 1024) / (g.lds + 256));
   return g;
@@ -994,7 +1054,7 @@ bool lxw_ring_ok(const spmv_hip_csr_plan* pl, bool forced)
   const int nrb = (pl->num_rows + kRows - 1) / kRows;
   if (!(forced || pl->lx_ring) || pl->symmetric || !pl->lx || !pl->lxw
       || !pl->lxw_rec || !pl->lx4 || !pl->lx_code || pl->lx4_lut != 1
-      || !pl->lx_v32 || !pl->lx_val32)
+      || !pl->lx_v32 || !pl->lx_val32 || !pl->lx_rowdesc)
     return false;
   if (nrb < 1 || pl->lx_staged != nrb || pl->lx4_blocks != nrb
       || pl->lx_ring_blocks != nrb || !lx_ring_fits(pl->lxw_max_cnt)
@@ -1018,12 +1078,12 @@ bool lxw_ring_ok(const spmv_hip_csr_plan* pl, bool forced)
   return forced || pl->lx_ring >= 2 || (nrb + grid - 1) / grid >= kMinSteps;
 }
 
-template <bool DOT>
-int lxw_ring_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
-                    const int32_t* rowptr, const float* values, double alpha,
-                    const double* in, double beta, double* out, DotOut dot)
+template <bool DOT, int PWR>
+int lxw_ring_launch_p(const spmv_hip_csr_plan* pl, hipStream_t st,
+                      const float* values, double alpha, const double* in,
+                      double beta, double* out, DotOut dot)
 {
-  constexpr int VR = kLxwRingValRounds, PWR = kLxwMaxPieces / (kBlock / 64);
+  constexpr int VR = kLxwRingValRounds;
   const LxwRingGeom g = lxw_ring_geom(pl);
   const int nrb = (pl->num_rows + kRows - 1) / kRows;
   // grid and row-block order: those of csr_lxw_kernel, so that y and the fused
@@ -1046,10 +1106,26 @@ int lxw_ring_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
         reinterpret_cast<const void*>(kern),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), g.lds, st, pl->num_rows,
-                     pl->num_cols, pl->nnz, rowptr, values, pl->lx_code,
+                     pl->num_cols, pl->nnz, values, pl->lx_code, pl->lx_rowdesc,
                      pl->lxw_rec, alpha, in, beta, out, dot, ord, g.ccap, g.xcap);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
+}
+
+// x pieces per wave: kLxwMaxPieces / 4 covers every plan; one fewer where the
+// plan stages at most twelve pieces (the 7-point matrix: 11), unless the plan
+// key "lx_ring_pwr" asks for all four -- one DMA instruction less per wave
+// and step, `s_waitcnt vmcnt(6)`
+template <bool DOT>
+int lxw_ring_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
+                    const float* values, double alpha, const double* in,
+                    double beta, double* out, DotOut dot)
+{
+  constexpr int NW = kBlock / 64, PWR = kLxwMaxPieces / NW;
+  if (pl->lx_ring_pwr != PWR && pl->lxw_max_pieces <= (PWR - 1) * NW)
+    return lxw_ring_launch_p<DOT, PWR - 1>(pl, st, values, alpha, in, beta, out,
+                                           dot);
+  return lxw_ring_launch_p<DOT, PWR>(pl, st, values, alpha, in, beta, out, dot);
 }
 
 template <typename TV, typename T, bool DOT, bool XW, int C4>
@@ -1101,8 +1177,7 @@ int lxw_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
   if constexpr (!XW && std::is_same<TV, float>::value
                 && std::is_same<T, double>::value) {
     if (lxw_ring_ok(pl, false))
-      return lxw_ring_launch<DOT>(pl, st, rowptr, values, alpha, in, beta, out,
-                                  dot);
+      return lxw_ring_launch<DOT>(pl, st, values, alpha, in, beta, out, dot);
   }
   if constexpr (!XW) {
     if (pl->lx4 && pl->lx_code)
