@@ -1115,6 +1115,82 @@ int spmv_hip_ilu0_get_pattern(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
 int spmv_hip_ilu0_get_factor(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
                              double* l, double* u, double* d, void* stream);
 
+/* ---- Aggregation multigrid (spmv::AmgPreconditioner) ---------------------------
+ * The device half of one coarsening step of a plain aggregation multigrid
+ * hierarchy, fp64, every product, sum, difference and quotient a rounding of
+ * its own.  The host describes the step (HOST arrays):
+ *   agg[i]       the aggregate of fine row i, 0 <= agg[i] < coarse_rows
+ *   member_ptr / member   the rows of every aggregate, ascending
+ *   src_ptr / src         per entry E of the coarse operator P^T A P (P the
+ *                piecewise-constant prolongation) the fine entries it adds, in
+ *                the order they are added: src >= 0 is values[src] (below
+ *                num_values), src < 0 is diagonal[~src] (below num_diagonal,
+ *                which is 0 or fine_rows: symmetric storage keeps its diagonal
+ *                in an array)
+ *   xrow_ptr / xrow_src   optional (symmetric storage): the expanded rows of
+ *                the fine level as source lists, for amg_diag
+ * coarse_rows == 0 describes no step (the lists of the step are not read).
+ * plan_create checks every index a kernel will use -- agg in range, the member
+ * lists a partition of the rows, ascending and consistent with agg, src_ptr
+ * strictly monotone from 0, every src in range -- and returns SPMV_HIP_EINVAL
+ * otherwise.
+ *
+ *   galerkin  coarse_values[E] = v_0 + v_1 + ... over the list of E, left to
+ *             right from the first one: one lane per coarse entry
+ *   diag      per fine row i: d[i] = the sum of the row's entries on column i
+ *             in storage order from 0.0 (entries with a column >= ncols_local
+ *             are not part of the level), with a plan that has xrow lists
+ *             diagonal[i]; dinv[i] = 1.0 / d[i]; g_i = (|a_0| + |a_1| + ...) *
+ *             dinv[i] over the expanded row.  stat (a DEVICE array of
+ *             SPMV_HIP_AMG_STAT_WORDS 8-byte words, overwritten): word 0 = the
+ *             number of d that are not finite or not > 0, the other words = the
+ *             bit patterns of the workgroups' maxima of g (>= 0.0); the row-sum
+ *             bound of dinv*A is the maximum over them.
+ *   restrict  rc[I] = (t_0 + t_1) + ..., t_m = r[i_m] - w[i_m] over the members
+ *             of I ascending: one lane per aggregate
+ *   prolong   z[i] = z[i] + scale * e[agg[i]]            (z 16-byte aligned)
+ *   post0     d = b0 * (dinv * (r - w)) ; z = z + d: step 0 of a Chebyshev
+ *             iteration continued from the current z (steps >= 1: cheb_step).
+ *             d == NULL: the only step, d is not written.  16-byte aligned.
+ * No kernel waits on another workgroup; no floating-point atomics. */
+#define SPMV_HIP_AMG_STAT_WORDS 257
+typedef struct spmv_hip_amg_plan spmv_hip_amg_plan;
+typedef struct spmv_hip_amg_host {
+  int32_t fine_rows;
+  int32_t coarse_rows;
+  int64_t num_values;
+  int32_t num_diagonal;
+  int64_t coarse_nnz;
+  const int32_t* agg;
+  const int32_t* member_ptr;
+  const int32_t* member;
+  const int64_t* src_ptr;
+  const int32_t* src;
+  const int64_t* xrow_ptr;
+  const int32_t* xrow_src;
+} spmv_hip_amg_host;
+int spmv_hip_amg_plan_create(spmv_hip_ctx* ctx, const spmv_hip_amg_host* in,
+                             spmv_hip_amg_plan** plan);
+int spmv_hip_amg_plan_destroy(spmv_hip_amg_plan* plan);
+int spmv_hip_amg_plan_bytes(const spmv_hip_amg_plan* plan, int64_t* bytes);
+int spmv_hip_amg_galerkin_f64(spmv_hip_ctx* ctx, const spmv_hip_amg_plan* plan,
+                              const double* values, const double* diagonal,
+                              double* coarse_values, void* stream);
+int spmv_hip_amg_diag_f64(spmv_hip_ctx* ctx, const spmv_hip_amg_plan* plan,
+                          int32_t n, int32_t ncols_local, const int32_t* rowptr,
+                          const int32_t* colind, const double* values,
+                          const double* diagonal, double* d, double* dinv,
+                          uint64_t* stat, void* stream);
+int spmv_hip_amg_restrict_f64(spmv_hip_ctx* ctx, const spmv_hip_amg_plan* plan,
+                              const double* r, const double* w, double* rc,
+                              void* stream);
+int spmv_hip_amg_prolong_f64(spmv_hip_ctx* ctx, const spmv_hip_amg_plan* plan,
+                             double scale, const double* e, double* z,
+                             void* stream);
+int spmv_hip_amg_post0_f64(spmv_hip_ctx* ctx, int64_t n, double b0,
+                           const double* w, const double* r, const double* dinv,
+                           double* d, double* z, void* stream);
+
 /* ---- BiCGStab with an optional diagonal right preconditioner (spmv::bicgstab) ---
  * For nonsymmetric systems.  `dinv` is the inverse of the preconditioner's
  * diagonal or NULL; ph = dinv*p, sh = dinv*s (elementwise), p and s themselves

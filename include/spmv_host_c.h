@@ -563,6 +563,64 @@ int spmvh_gmres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                 double* rnorm_history, spmvh_gmres_workspace* ws, int flags,
                 double* spmv_ms_total, int* spmv_launches);
 
+/* ---- Aggregation multigrid (spmv::AmgPreconditioner, host/cg.h) -----------------
+ * spmvh_amg_check_options: the rules of spmv::AmgOptions, no device.
+ * spmvh_amg_symbolic_*: one coarsening step of host/amg_build.h on HOST
+ * arrays, no device.  Symmetric input: the stored strictly lower block and a
+ * diagonal array.  sizes[4] = {aggregates, coarse entries, sources, expanded
+ * entries}; _get copies out what is not NULL: agg (nrows), member_ptr
+ * (aggregates + 1), member (nrows), the coarse pattern rowptr (aggregates + 1)
+ * and colind, src_ptr (coarse entries + 1), src, and the expanded rows xrow_ptr
+ * (nrows + 1), xrow_col, xrow_src.  A source >= 0 indexes values, < 0 is
+ * diagonal[~src].
+ * spmvh_amg_create: options = NULL (defaults) or 7 doubles {theta, max_levels,
+ * min_coarse_rows, smooth_degree, coarse_degree, eig_ratio, coarse_scale}.
+ * spmvh_amg_info: info[4] = {levels, plan_bytes, symbolic us, numeric us}.
+ * spmvh_amg_level_info: sizes[2] = {rows, stored entries}, *lmax the bound.
+ * spmvh_amg_level_matrix: host copies of a level >= 1 (NULL outputs skipped).
+ * spmvh_amg_apply: z = M^-1 r, device vectors, the host does not wait.
+ * spmvh_pcg_amg: the arguments of spmvh_pcg_sgs.  spmvh_gmres_amg: the
+ * arguments of spmvh_gmres and the AMG handle (excludes the others). */
+typedef struct spmvh_amg spmvh_amg;
+typedef struct spmvh_amg_symbolic spmvh_amg_symbolic;
+int spmvh_amg_check_options(double theta, int max_levels,
+                            int64_t min_coarse_rows, int smooth_degree,
+                            int coarse_degree, double eig_ratio,
+                            double coarse_scale);
+int spmvh_amg_symbolic_create(const int32_t* rowptr, const int32_t* colind,
+                              const double* values, const double* diagonal,
+                              int64_t nrows, int64_t ncols_local, int symmetric,
+                              double theta, spmvh_amg_symbolic** sym,
+                              int64_t* sizes);
+int spmvh_amg_symbolic_get(spmvh_amg_symbolic* sym, int32_t* agg,
+                           int32_t* member_ptr, int32_t* member,
+                           int32_t* rowptr, int32_t* colind, int64_t* src_ptr,
+                           int32_t* src, int64_t* xrow_ptr, int32_t* xrow_col,
+                           int32_t* xrow_src);
+int spmvh_amg_symbolic_destroy(spmvh_amg_symbolic* sym);
+int spmvh_amg_create(spmvh_exec* exec, spmvh_matrix* A, const double* options,
+                     spmvh_amg** M);
+int spmvh_amg_destroy(spmvh_amg* M);
+int spmvh_amg_refresh(spmvh_amg* M, spmvh_matrix* A);
+int spmvh_amg_info(spmvh_amg* M, int64_t* info);
+int spmvh_amg_level_info(spmvh_amg* M, int level, int64_t* sizes, double* lmax);
+int spmvh_amg_aggregates(spmvh_amg* M, int level, int32_t* agg);
+int spmvh_amg_level_matrix(spmvh_amg* M, int level, int32_t* rowptr,
+                           int32_t* colind, double* values);
+int spmvh_amg_apply(spmvh_exec* exec, spmvh_amg* M, const double* r, double* z);
+int spmvh_pcg_amg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                  spmvh_amg* M, const double* b, double* x, int kmax,
+                  double rtol, int* num_its, double* rnorm_history,
+                  spmvh_sgs_workspace* ws, int flags, double* spmv_ms_total,
+                  int* spmv_launches);
+int spmvh_gmres_amg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                    const double* b, double* x, const double* dinv,
+                    int cheb_degree, double lmin, double lmax, spmvh_sgs* sgs,
+                    int restart, int kmax, double rtol, int* num_its,
+                    int* status, double* rnorm_history,
+                    spmvh_gmres_workspace* ws, int flags, double* spmv_ms_total,
+                    int* spmv_launches, spmvh_amg* amg);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,491 @@
+// spmv::AmgPreconditioner and amg_apply for HipExecutor: see cg.h.  The
+// aggregates, patterns and source lists are amg_build.h's, on the host; the
+// numbers are spmv_amg.hip's, on the device, on the executor's current stream:
+//     per coarsening step  galerkin (the coarse values) ; the coarse block's
+//                          plan ; a read-back of the values for the next step
+//     per level            diag (d, dinv, the bound) ; read of the counts
+// refresh() repeats the galerkin sums and the diag kernels only.
+#include "cg.h"
+
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <utility>
+
+#include "amg_build.h"
+#include "solver_common.h"
+
+namespace spmv
+{
+using namespace detail;
+
+struct AmgPreconditioner::Level {
+  const CSRMatrix<double>* op = nullptr; // level 0: A's local block
+  std::unique_ptr<CSRMatrix<double>> own; // levels >= 1
+  int32_t rows = 0, cols = 0;
+  int64_t nnz = 0;
+  // the step to the next level (has_step) and / or the expanded rows of
+  // symmetric storage
+  spmv_hip_amg_plan* plan = nullptr;
+  bool has_step = false;
+  std::vector<int32_t> agg;
+  // d, dinv, r, w, dd: rows; z: cols, ghost tail zero
+  double *d = nullptr, *dinv = nullptr, *z = nullptr, *r = nullptr,
+         *w = nullptr, *dd = nullptr;
+  double lmax = 0, lmin = 0;
+  double sa[kChebyshevMaxDegree], sb[kChebyshevMaxDegree]; // smoother
+  double ca[kChebyshevMaxDegree], cb[kChebyshevMaxDegree]; // coarsest level
+};
+
+namespace
+{
+
+const CSRMatrix<double>* amg_block_of(const Matrix<double>& A, const char* who)
+{
+  std::shared_ptr<L2GMap> row_map = A.row_map();
+  std::shared_ptr<const L2GMap> col_map = A.col_map();
+  if (row_map->num_ghosts() > 0
+      || row_map->local_size() != col_map->local_size()
+      || row_map->global_offset() != col_map->global_offset())
+    throw std::runtime_error(
+        std::string("spmv::AmgPreconditioner") + who
+        + " - Error: rows and owned columns are not the same index range on "
+          "this rank");
+  const auto* blk = dynamic_cast<const CSRMatrix<double>*>(A.local_block());
+  if (!blk)
+    throw std::runtime_error(std::string("spmv::AmgPreconditioner") + who
+                             + " - Error: the matrix has no local block");
+  if (blk->csr_released())
+    throw std::runtime_error(
+        std::string("spmv::AmgPreconditioner") + who
+        + " - Error: the CSR arrays of this matrix were released "
+          "(release_csr); the hierarchy reads its values");
+  return blk;
+}
+
+struct Clock {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double lap()
+  {
+    const auto t1 = std::chrono::steady_clock::now();
+    const double ms
+        = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+    return ms;
+  }
+};
+
+} // namespace
+
+AmgPreconditioner::AmgPreconditioner(HipExecutor& exec, const Matrix<double>& A,
+                                     const AmgOptions& options)
+    : _exec(exec), _opt(options)
+{
+  amg_check_options(_opt.theta, _opt.max_levels, _opt.min_coarse_rows,
+                    _opt.smooth_degree, _opt.coarse_degree, _opt.eig_ratio,
+                    _opt.coarse_scale);
+  amg_block_of(A, "");
+  _symmetric = A.symmetric();
+  try {
+    numeric(A, true);
+  } catch (...) {
+    release();
+    throw;
+  }
+}
+
+AmgPreconditioner::~AmgPreconditioner() { release(); }
+
+void AmgPreconditioner::release()
+{
+  try {
+    _exec.synchronize(); // a cycle may still be in flight
+  } catch (...) {
+  }
+  for (auto& lp : _levels) {
+    if (!lp)
+      continue;
+    spmv_hip_amg_plan_destroy(lp->plan);
+    lp->plan = nullptr;
+    for (double** v : {&lp->d, &lp->dinv, &lp->z, &lp->r, &lp->w, &lp->dd}) {
+      try {
+        if (*v)
+          _exec.free(*v);
+      } catch (...) {
+      }
+      *v = nullptr;
+    }
+  }
+  _levels.clear();
+  try {
+    if (_stat)
+      _exec.free(_stat);
+  } catch (...) {
+  }
+  _stat = nullptr;
+}
+
+void AmgPreconditioner::check_usable() const
+{
+  if (!_usable)
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner - Error: the last refresh failed (the "
+        "diagonal is not positive); refresh before using it");
+}
+
+// d, dinv, the bound and the Chebyshev coefficients of one level
+void AmgPreconditioner::level_numbers(Level& L)
+{
+  if (L.rows == 0)
+    return;
+  if (L.nnz == 0 && !_symmetric) // an empty block owns no arrays
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner - Error: the diagonal is not positive ("
+        + std::to_string(L.rows) + " of " + std::to_string(L.rows)
+        + " entries are not finite or not > 0)");
+  const CSRMatrix<double>& B = *L.op;
+  throw_on_error(spmv_hip_amg_diag_f64(_exec.context(), L.plan, L.rows, L.rows,
+                                       B.rowptr(), B.colind(), B.values(),
+                                       B.diagonal(), L.d, L.dinv, _stat,
+                                       nullptr),
+                 "spmv_hip_amg_diag_f64");
+  uint64_t words[SPMV_HIP_AMG_STAT_WORDS];
+  _exec.copy_to<uint64_t>(words, _exec.get_host(), _stat,
+                          SPMV_HIP_AMG_STAT_WORDS); // waits
+  if (words[0] != 0)
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner - Error: the diagonal is not positive ("
+        + std::to_string(words[0]) + " of " + std::to_string(L.rows)
+        + " entries are not finite or not > 0)");
+  double lmax = 0.0;
+  for (int k = 1; k < SPMV_HIP_AMG_STAT_WORDS; ++k) {
+    double g;
+    std::memcpy(&g, &words[k], sizeof g);
+    if (g > lmax)
+      lmax = g;
+  }
+  L.lmax = lmax;
+  L.lmin = lmax / _opt.eig_ratio;
+  chebyshev_coefficients(_opt.smooth_degree, L.lmin, L.lmax, L.sa, L.sb);
+  chebyshev_coefficients(_opt.coarse_degree, L.lmin, L.lmax, L.ca, L.cb);
+}
+
+void AmgPreconditioner::numeric(const Matrix<double>& A, bool build)
+{
+  const auto* blk = static_cast<const CSRMatrix<double>*>(A.local_block());
+  spmv_hip_ctx* ctx = _exec.context();
+  const DeviceExecutor& host = _exec.get_host();
+  _usable = false;
+  Clock clock;
+  if (build) {
+    _symbolic_ms = _numeric_ms = 0;
+    _stat = _exec.alloc<uint64_t>(SPMV_HIP_AMG_STAT_WORDS);
+    _num_values = blk->non_zeros();
+    const int64_t n0 = A.row_map()->local_size();
+
+    // level 0, read back (the copies wait for the device)
+    std::vector<int32_t> rowptr((size_t)n0 + 1, 0), colind((size_t)_num_values);
+    std::vector<double> values((size_t)_num_values), diagonal;
+    if (_num_values > 0) { // (an empty block owns no arrays)
+      _exec.copy_to<int32_t>(rowptr.data(), host, blk->rowptr(), (size_t)n0 + 1);
+      _exec.copy_to<int32_t>(colind.data(), host, blk->colind(),
+                             (size_t)_num_values);
+      _exec.copy_to<double>(values.data(), host, blk->values(),
+                            (size_t)_num_values);
+    }
+    if (_symmetric && n0 > 0) {
+      diagonal.resize((size_t)n0);
+      _exec.copy_to<double>(diagonal.data(), host, blk->diagonal(), (size_t)n0);
+    }
+    // coarse blocks live on this executor; the object does not own it
+    std::shared_ptr<DeviceExecutor> shared(std::shared_ptr<void>(), &_exec);
+
+    auto first = std::make_unique<Level>();
+    first->op = blk;
+    first->rows = (int32_t)n0;
+    first->cols = blk->cols();
+    first->nnz = _num_values;
+    _levels.push_back(std::move(first));
+    for (;;) {
+      Level& L = *_levels.back();
+      const bool sym = _symmetric && _levels.size() == 1;
+      const bool coarsen = L.rows > _opt.min_coarse_rows
+                           && (int)_levels.size() < _opt.max_levels;
+      if (!coarsen && !sym)
+        break;
+      const AmgExpanded x
+          = amg_expand(rowptr.data(), colind.data(), L.rows, L.rows, sym);
+      AmgStep step;
+      if (coarsen) {
+        step = amg_aggregate(x, values.data(), diagonal.data(), _opt.theta);
+        if (step.n_agg == L.rows) // nothing merged: discard it
+          step = AmgStep();
+        else
+          amg_galerkin_pattern(x, &step);
+      }
+      const int32_t nc = step.n_agg;
+      const int64_t nnz_c = (int64_t)step.colind.size();
+      spmv_hip_amg_host in{};
+      in.fine_rows = L.rows;
+      in.coarse_rows = nc;
+      in.num_values = L.nnz;
+      in.num_diagonal = sym ? L.rows : 0;
+      in.coarse_nnz = nnz_c;
+      if (nc > 0) {
+        in.agg = step.agg.data();
+        in.member_ptr = step.member_ptr.data();
+        in.member = step.member.data();
+        in.src_ptr = step.src_ptr.data();
+        in.src = step.src.data();
+      }
+      if (sym) {
+        in.xrow_ptr = x.ptr.data();
+        in.xrow_src = x.src.data();
+      }
+      throw_on_error(spmv_hip_amg_plan_create(ctx, &in, &L.plan),
+                     "spmv_hip_amg_plan_create");
+      if (nc == 0)
+        break;
+      L.has_step = true;
+      L.agg = std::move(step.agg);
+      _symbolic_ms += clock.lap();
+
+      // the coarse block: pattern uploaded, values summed on the device
+      int32_t* c_rowptr = _exec.alloc<int32_t>((size_t)nc + 1);
+      int32_t* c_colind = _exec.alloc<int32_t>((size_t)nnz_c);
+      double* c_values = _exec.alloc<double>((size_t)nnz_c);
+      auto next = std::make_unique<Level>();
+      try {
+        _exec.copy_from<int32_t>(c_rowptr, host, step.rowptr.data(),
+                                 (size_t)nc + 1);
+        _exec.copy_from<int32_t>(c_colind, host, step.colind.data(),
+                                 (size_t)nnz_c);
+        throw_on_error(spmv_hip_amg_galerkin_f64(ctx, L.plan, L.op->values(),
+                                                 L.op->diagonal(), c_values,
+                                                 nullptr),
+                       "spmv_hip_amg_galerkin_f64");
+      } catch (...) {
+        _exec.free(c_rowptr);
+        _exec.free(c_colind);
+        _exec.free(c_values);
+        throw;
+      }
+      // (the block owns the arrays from here on; its plan sees the values)
+      next->own.reset(new CSRMatrix<double>(CSRMatrix<double>::AdoptDevice(),
+                                            shared, nc, nc, nnz_c, c_rowptr,
+                                            c_colind, c_values, nullptr, false));
+      if (next->own->csr_released())
+        throw std::runtime_error(
+            "spmv::AmgPreconditioner - Error: the context released the CSR "
+            "arrays of a coarse level (release_csr); the hierarchy needs them");
+      next->op = next->own.get();
+      next->rows = next->cols = nc;
+      next->nnz = nnz_c;
+      rowptr = std::move(step.rowptr);
+      colind = std::move(step.colind);
+      values.resize((size_t)nnz_c);
+      _exec.copy_to<double>(values.data(), host, c_values, (size_t)nnz_c);
+      diagonal.clear();
+      _levels.push_back(std::move(next));
+      _numeric_ms += clock.lap();
+    }
+    for (auto& lp : _levels) {
+      Level& L = *lp;
+      if (L.rows == 0)
+        continue;
+      const size_t n = (size_t)L.rows;
+      for (double** v : {&L.d, &L.dinv, &L.r, &L.w, &L.dd})
+        *v = _exec.alloc<double>(n);
+      L.z = _exec.alloc<double>((size_t)L.cols);
+      _exec.memset<double>(L.z, 0, (size_t)L.cols);
+    }
+    _symbolic_ms += clock.lap();
+  } else {
+    Level& L0 = *_levels[0];
+    L0.op = blk;
+    for (size_t l = 0; l + 1 < _levels.size(); ++l) {
+      Level& L = *_levels[l];
+      Level& C = *_levels[l + 1];
+      throw_on_error(
+          spmv_hip_amg_galerkin_f64(ctx, L.plan, L.op->values(),
+                                    L.op->diagonal(),
+                                    const_cast<double*>(C.own->values()),
+                                    nullptr),
+          "spmv_hip_amg_galerkin_f64");
+      C.own->values_changed();
+    }
+  }
+  for (auto& lp : _levels)
+    level_numbers(*lp);
+  _numeric_ms += clock.lap();
+  _usable = true;
+}
+
+void AmgPreconditioner::refresh(const Matrix<double>& A)
+{
+  const CSRMatrix<double>* blk = amg_block_of(A, "::refresh");
+  if (A.row_map()->local_size() != rows(0) || A.symmetric() != _symmetric
+      || blk->non_zeros() != _num_values || blk->cols() != _levels[0]->cols)
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner::refresh - Error: not the pattern this object "
+        "was built for (rows, storage or number of stored entries differ)");
+  _numeric_ms = 0;
+  numeric(A, false);
+}
+
+int AmgPreconditioner::levels() const { return (int)_levels.size(); }
+
+namespace
+{
+void check_level(int level, int levels, const char* who)
+{
+  if (level < 0 || level >= levels)
+    throw std::runtime_error(std::string("spmv::AmgPreconditioner::") + who
+                             + " - Error: no such level");
+}
+} // namespace
+
+int AmgPreconditioner::rows(int level) const
+{
+  check_level(level, levels(), "rows");
+  return _levels[(size_t)level]->rows;
+}
+
+int64_t AmgPreconditioner::non_zeros(int level) const
+{
+  check_level(level, levels(), "non_zeros");
+  return _levels[(size_t)level]->nnz;
+}
+
+double AmgPreconditioner::lmax(int level) const
+{
+  check_level(level, levels(), "lmax");
+  check_usable();
+  return _levels[(size_t)level]->lmax;
+}
+
+void AmgPreconditioner::aggregates(int level, int32_t* out) const
+{
+  check_level(level, levels() - 1, "aggregates");
+  const std::vector<int32_t>& agg = _levels[(size_t)level]->agg;
+  if (!out && !agg.empty())
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner::aggregates - Error: NULL output");
+  std::copy(agg.begin(), agg.end(), out);
+}
+
+void AmgPreconditioner::level_matrix(int level, int32_t* rowptr, int32_t* colind,
+                                     double* values) const
+{
+  check_level(level, levels(), "level_matrix");
+  if (level < 1)
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner::level_matrix - Error: level 0 is the "
+        "matrix's own block");
+  const Level& L = *_levels[(size_t)level];
+  const DeviceExecutor& host = _exec.get_host();
+  if (rowptr)
+    _exec.copy_to<int32_t>(rowptr, host, L.own->rowptr(), (size_t)L.rows + 1);
+  if (colind)
+    _exec.copy_to<int32_t>(colind, host, L.own->colind(), (size_t)L.nnz);
+  if (values)
+    _exec.copy_to<double>(values, host, L.own->values(), (size_t)L.nnz);
+}
+
+int64_t AmgPreconditioner::plan_bytes() const
+{
+  int64_t total = SPMV_HIP_AMG_STAT_WORDS * 8;
+  for (const auto& lp : _levels) {
+    const Level& L = *lp;
+    int64_t bytes = 0;
+    if (L.plan)
+      throw_on_error(spmv_hip_amg_plan_bytes(L.plan, &bytes),
+                     "spmv_hip_amg_plan_bytes");
+    total += bytes;
+    if (L.own)
+      total += (int64_t)L.own->format_size()
+               + (int64_t)L.own->query("plan_kib") * 1024;
+    if (L.rows > 0)
+      total += ((int64_t)L.rows * 5 + L.cols) * 8;
+  }
+  return total;
+}
+
+void AmgPreconditioner::apply(const double* r, double* z) const
+{
+  check_usable();
+  const Level& L0 = *_levels[0];
+  const int64_t n0 = L0.rows;
+  if (ranges_overlap(z, r, n0))
+    throw std::runtime_error("amg_apply: z overlaps r");
+  if (n0 == 0)
+    return;
+  if (!r || !z)
+    throw std::runtime_error("amg_apply: NULL vector");
+  spmv_hip_ctx* ctx = _exec.context();
+  const int nl = levels(), s = _opt.smooth_degree;
+
+  // everything on the executor's current stream, nothing waits
+  const double* r0 = r;
+  if (!is_aligned16(r)) { // the streaming kernels load 16 bytes at a time
+    _exec.copy<double>(L0.r, r, (size_t)n0);
+    r0 = L0.r;
+  }
+  auto rhs = [&](int l) { return l == 0 ? r0 : _levels[(size_t)l]->r; };
+  auto product = [&](const Level& L) { L.op->mult(1.0, L.z, 0.0, L.w); };
+  // the `degree`-step Chebyshev iteration from z = 0
+  auto chebyshev = [&](const Level& L, const double* rl, int degree,
+                       const double* a, const double* b) {
+    throw_on_error(spmv_hip_cheb_apply0_f64(ctx, L.rows, b[0], rl, L.dinv,
+                                            degree > 1 ? L.dd : nullptr, L.z,
+                                            nullptr),
+                   "spmv_hip_cheb_apply0_f64");
+    for (int j = 1; j < degree; ++j) {
+      product(L);
+      throw_on_error(spmv_hip_cheb_step_f64(ctx, nullptr, L.rows, a[j], b[j],
+                                            j == degree - 1, L.w, rl, L.dinv,
+                                            L.dd, L.z, nullptr),
+                     "spmv_hip_cheb_step_f64");
+    }
+  };
+  for (int l = 0; l < nl; ++l) {
+    const Level& L = *_levels[(size_t)l];
+    if (l == nl - 1) {
+      chebyshev(L, rhs(l), _opt.coarse_degree, L.ca, L.cb);
+      break;
+    }
+    chebyshev(L, rhs(l), s, L.sa, L.sb);
+    product(L);
+    throw_on_error(spmv_hip_amg_restrict_f64(ctx, L.plan, rhs(l), L.w,
+                                             _levels[(size_t)l + 1]->r, nullptr),
+                   "spmv_hip_amg_restrict_f64");
+  }
+  for (int l = nl - 2; l >= 0; --l) {
+    const Level& L = *_levels[(size_t)l];
+    throw_on_error(spmv_hip_amg_prolong_f64(ctx, L.plan, _opt.coarse_scale,
+                                            _levels[(size_t)l + 1]->z, L.z,
+                                            nullptr),
+                   "spmv_hip_amg_prolong_f64");
+    product(L);
+    throw_on_error(spmv_hip_amg_post0_f64(ctx, L.rows, L.sb[0], L.w, rhs(l),
+                                          L.dinv, s > 1 ? L.dd : nullptr, L.z,
+                                          nullptr),
+                   "spmv_hip_amg_post0_f64");
+    for (int j = 1; j < s; ++j) {
+      product(L);
+      throw_on_error(spmv_hip_cheb_step_f64(ctx, nullptr, L.rows, L.sa[j],
+                                            L.sb[j], j == s - 1, L.w, rhs(l),
+                                            L.dinv, L.dd, L.z, nullptr),
+                     "spmv_hip_cheb_step_f64");
+    }
+  }
+  _exec.copy<double>(z, L0.z, (size_t)n0);
+}
+
+void amg_apply(HipExecutor&, const AmgPreconditioner& M, const double* r,
+               double* z)
+{
+  M.apply(r, z);
+}
+
+} // namespace spmv

@@ -15,6 +15,7 @@
 #include "l2gmap.h"
 #include "matrix.h"
 #include "read_petsc.h"
+#include "amg_build.h"
 #include "ilu0_build.h"
 #include "sgs_build.h"
 
@@ -59,6 +60,13 @@ struct spmvh_sgs_build {
 };
 struct spmvh_ilu0_symbolic {
   Ilu0Symbolic sym;
+};
+struct spmvh_amg_symbolic {
+  AmgExpanded x;
+  AmgStep step;
+};
+struct spmvh_amg {
+  std::unique_ptr<AmgPreconditioner> M;
 };
 struct spmvh_sgs {
   std::shared_ptr<HipExecutor> exec; // keeps the executor alive
@@ -1601,6 +1609,173 @@ int spmvh_pcg_sgs(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
   });
 }
 
+// ---- Aggregation multigrid ---------------------------------------------------------------
+int spmvh_amg_check_options(double theta, int max_levels,
+                            int64_t min_coarse_rows, int smooth_degree,
+                            int coarse_degree, double eig_ratio,
+                            double coarse_scale)
+{
+  return guarded([&] {
+    amg_check_options(theta, max_levels, min_coarse_rows, smooth_degree,
+                      coarse_degree, eig_ratio, coarse_scale);
+  });
+}
+
+int spmvh_amg_symbolic_create(const int32_t* rowptr, const int32_t* colind,
+                              const double* values, const double* diagonal,
+                              int64_t nrows, int64_t ncols_local, int symmetric,
+                              double theta, spmvh_amg_symbolic** sym,
+                              int64_t* sizes)
+{
+  return guarded([&] {
+    require(sym && sizes, "NULL argument");
+    require(!symmetric || nrows == 0 || diagonal, "NULL diagonal");
+    amg_check_options(theta, 1, 1, 1, 1, 2.0, 1.0);
+    auto s = std::make_unique<spmvh_amg_symbolic>();
+    s->x = amg_expand(rowptr, colind, nrows, ncols_local, symmetric != 0);
+    require(s->x.num_values == 0 || values, "NULL values");
+    s->step = amg_coarsen(s->x, values, diagonal, theta);
+    sizes[0] = s->step.n_agg;
+    sizes[1] = (int64_t)s->step.colind.size();
+    sizes[2] = (int64_t)s->step.src.size();
+    sizes[3] = (int64_t)s->x.col.size();
+    *sym = s.release();
+  });
+}
+
+int spmvh_amg_symbolic_get(spmvh_amg_symbolic* sym, int32_t* agg,
+                           int32_t* member_ptr, int32_t* member,
+                           int32_t* rowptr, int32_t* colind, int64_t* src_ptr,
+                           int32_t* src, int64_t* xrow_ptr, int32_t* xrow_col,
+                           int32_t* xrow_src)
+{
+  return guarded([&] {
+    require(sym != nullptr, "NULL argument");
+    auto out = [](const auto& v, auto* dst) {
+      if (dst)
+        std::copy(v.begin(), v.end(), dst);
+    };
+    const AmgStep& t = sym->step;
+    out(t.agg, agg);
+    out(t.member_ptr, member_ptr);
+    out(t.member, member);
+    out(t.rowptr, rowptr);
+    out(t.colind, colind);
+    out(t.src_ptr, src_ptr);
+    out(t.src, src);
+    out(sym->x.ptr, xrow_ptr);
+    out(sym->x.col, xrow_col);
+    out(sym->x.src, xrow_src);
+  });
+}
+
+int spmvh_amg_symbolic_destroy(spmvh_amg_symbolic* sym)
+{
+  return guarded([&] { delete sym; });
+}
+
+int spmvh_amg_create(spmvh_exec* exec, spmvh_matrix* A, const double* options,
+                     spmvh_amg** M)
+{
+  return guarded([&] {
+    require(exec && A && M, "NULL argument");
+    require(exec->hip != nullptr, "not a HipExecutor");
+    AmgOptions opt;
+    if (options) {
+      opt.theta = options[0];
+      opt.max_levels = (int)options[1];
+      opt.min_coarse_rows = (int64_t)options[2];
+      opt.smooth_degree = (int)options[3];
+      opt.coarse_degree = (int)options[4];
+      opt.eig_ratio = options[5];
+      opt.coarse_scale = options[6];
+    }
+    auto m = std::make_unique<spmvh_amg>();
+    m->M.reset(new AmgPreconditioner(*exec->hip, *A->A, opt));
+    *M = m.release();
+  });
+}
+
+int spmvh_amg_destroy(spmvh_amg* M)
+{
+  return guarded([&] { delete M; });
+}
+
+int spmvh_amg_refresh(spmvh_amg* M, spmvh_matrix* A)
+{
+  return guarded([&] {
+    require(M && A, "NULL argument");
+    M->M->refresh(*A->A);
+  });
+}
+
+int spmvh_amg_info(spmvh_amg* M, int64_t* info)
+{
+  return guarded([&] {
+    require(M && info, "NULL argument");
+    info[0] = M->M->levels();
+    info[1] = M->M->plan_bytes();
+    info[2] = (int64_t)(M->M->symbolic_ms() * 1000.0);
+    info[3] = (int64_t)(M->M->numeric_ms() * 1000.0);
+  });
+}
+
+int spmvh_amg_level_info(spmvh_amg* M, int level, int64_t* sizes, double* lmax)
+{
+  return guarded([&] {
+    require(M && sizes && lmax, "NULL argument");
+    sizes[0] = M->M->rows(level);
+    sizes[1] = M->M->non_zeros(level);
+    *lmax = M->M->lmax(level);
+  });
+}
+
+int spmvh_amg_aggregates(spmvh_amg* M, int level, int32_t* agg)
+{
+  return guarded([&] {
+    require(M != nullptr, "NULL argument");
+    M->M->aggregates(level, agg);
+  });
+}
+
+int spmvh_amg_level_matrix(spmvh_amg* M, int level, int32_t* rowptr,
+                           int32_t* colind, double* values)
+{
+  return guarded([&] {
+    require(M != nullptr, "NULL argument");
+    M->M->level_matrix(level, rowptr, colind, values);
+  });
+}
+
+int spmvh_amg_apply(spmvh_exec* exec, spmvh_amg* M, const double* r, double* z)
+{
+  return guarded([&] {
+    require(exec && M, "NULL argument");
+    amg_apply(*exec->hip, *M->M, r, z);
+  });
+}
+
+int spmvh_pcg_amg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                  spmvh_amg* M, const double* b, double* x, int kmax,
+                  double rtol, int* num_its, double* rnorm_history,
+                  spmvh_sgs_workspace* ws, int flags, double* spmv_ms_total,
+                  int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && M && num_its, "NULL argument");
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff) // bits 8-15: CgOptions::poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    CgStats st;
+    *num_its = pcg_amg(*comm->comm, *exec->hip, *A->A, *M->M, b, x, kmax, rtol,
+                       rnorm_history ? &hist : nullptr, &opt, &st,
+                       ws ? ws->ws.get() : nullptr);
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
+  });
+}
+
 // ---- BiCGStab ---------------------------------------------------------------------------
 int spmvh_bicgstab_workspace_create(spmvh_exec* exec,
                                     spmvh_bicgstab_workspace** ws)
@@ -1680,6 +1855,19 @@ int spmvh_gmres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                 double* rnorm_history, spmvh_gmres_workspace* ws, int flags,
                 double* spmv_ms_total, int* spmv_launches)
 {
+  return spmvh_gmres_amg(comm, exec, A, b, x, dinv, cheb_degree, lmin, lmax, sgs,
+                         restart, kmax, rtol, num_its, status, rnorm_history, ws,
+                         flags, spmv_ms_total, spmv_launches, nullptr);
+}
+
+int spmvh_gmres_amg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                    const double* b, double* x, const double* dinv,
+                    int cheb_degree, double lmin, double lmax, spmvh_sgs* sgs,
+                    int restart, int kmax, double rtol, int* num_its,
+                    int* status, double* rnorm_history,
+                    spmvh_gmres_workspace* ws, int flags, double* spmv_ms_total,
+                    int* spmv_launches, spmvh_amg* amg)
+{
   return guarded([&] {
     require(comm && exec && A && num_its, "NULL argument");
     std::vector<double> hist;
@@ -1693,6 +1881,7 @@ int spmvh_gmres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     pre.lmin = lmin;
     pre.lmax = lmax;
     pre.sgs = sgs ? sgs->M.get() : nullptr;
+    pre.amg = amg ? amg->M.get() : nullptr;
     CgStats st;
     int how = 0;
     *num_its = gmres(*comm->comm, *exec->hip, *A->A, b, x, &pre, restart, kmax,

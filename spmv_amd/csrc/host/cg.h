@@ -685,6 +685,139 @@ int pcg_sgs(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
             const CgOptions* options = nullptr, CgStats* stats = nullptr,
             SgsWorkspace* workspace = nullptr);
 
+// ---- Aggregation multigrid preconditioner ---------------------------------------
+// Every rule is checked before anything touches a device; std::runtime_error
+// names the field (amg_check_options of solver_args.h).
+struct AmgOptions {
+  double theta = 0.25;          // strength threshold, in [0, 1]
+  int max_levels = 10;          // 1..16
+  int64_t min_coarse_rows = 200; // >= 1: a level with more rows is coarsened
+  int smooth_degree = 2;        // 1..kChebyshevMaxDegree, pre and post
+  int coarse_degree = 8;        // 1..kChebyshevMaxDegree, the coarsest level
+  double eig_ratio = 4.0;       // > 1: lmin = lmax / eig_ratio
+  double coarse_scale = 1.0;    // 1 <= coarse_scale < 2
+};
+constexpr int kAmgMaxLevels = 16;
+
+// M^-1 = one V-cycle of plain (unsmoothed) aggregation multigrid on the LOCAL
+// DIAGONAL BLOCK of A: SgsPreconditioner's scope -- the rows of this rank and
+// the columns < local_size, ghost columns and the remote block ignored,
+// block-Jacobi over the ranks, no halo exchange; rows and owned columns the
+// same index range (std::runtime_error otherwise); fp64; both storages.
+//
+// Hierarchy.  The expanded row of a level: general storage, the row's stored
+// entries with a column < local_size in storage order; symmetric storage (level
+// 0 only, coarse levels are general), the stored lower entries, the diagonal
+// entry, then the mirror images of the stored entries of its column ascending by
+// row.  Per level l:
+//   A_l      level 0: A's own local block, NOT copied (A must outlive this
+//            object or be replaced by refresh()); its products are the block's
+//            mult on a vector whose ghost tail is zero
+//   d_i      Matrix::diagonal's definition; dinv_i = 1.0 / d_i; a d_i that is
+//            not finite and > 0 throws ("diagonal is not positive")
+//   g_i      (|a_e0| + |a_e1| + ...) * dinv_i over the expanded row in its order
+//   lmax_l   max_i g_i, the row-sum bound of dinv*A: a true upper bound, so the
+//            smoother converges and M is positive definite without a power
+//            iteration; lmin_l = lmax_l / eig_ratio
+//   aggregates, P^T A_l P: host/amg_build.h; the coarse values are summed on
+//            the device from per-entry source lists, left to right
+// A level is coarsened while rows_l > min_coarse_rows and levels < max_levels;
+// an aggregation that merges nothing is discarded (a diagonal matrix has one
+// level).  Context options apply to the coarse blocks as to any block; a
+// context that releases CSR arrays ("release_csr") is refused ("released").
+//
+// Cycle, z = M^-1 r, with a_j, b_j = chebyshev_coefficients(degree, lmin_l,
+// lmax_l) and s = smooth_degree:
+//   coarsest level:  z = the coarse_degree-step Chebyshev iteration from z = 0
+//   otherwise:  pre   z = the s-step Chebyshev iteration from z = 0
+//               w = A_l z; rc[I] = (t_0 + t_1) + ... over the members of I
+//                 ascending, t_m = r[i_m] - w[i_m]
+//               e = cycle(l + 1, rc);  z[i] = z[i] + coarse_scale * e[agg(i)]
+//               post  j = 0:      w = A_l z; d = b_0*(dinv*(r - w));         z = z + d
+//                     j = 1..s-1: w = A_l z; d = a_j*d + b_j*(dinv*(r - w)); z = z + d
+// Every product, sum, difference and quotient is a rounding of its own.  With a
+// symmetric A the operator is symmetric, and positive definite for 1 <=
+// coarse_scale < 2.
+//
+// The constructor is the setup and, with refresh(), the one place that waits
+// on the device.  It throws on a matrix that has released its CSR arrays
+// ("released").  refresh(A): new values on the same pattern and storage (rows,
+// storage and the number of stored entries are checked; the pattern is the
+// caller's promise): aggregates, patterns and source lists are kept, the
+// Galerkin sums, d, dinv and the bounds are recomputed on the device, no host
+// pass; the only waits are the reads of the counts and bounds.  After a failed
+// refresh the object is unusable until a later one succeeds.
+//
+// The level work vectors belong to the object: an application is NOT
+// reentrant -- one amg_apply / pcg_amg / gmres at a time per object.
+class AmgPreconditioner
+{
+public:
+  AmgPreconditioner(HipExecutor& exec, const Matrix<double>& A,
+                    const AmgOptions& options = AmgOptions());
+  ~AmgPreconditioner();
+  AmgPreconditioner(const AmgPreconditioner&) = delete;
+  AmgPreconditioner& operator=(const AmgPreconditioner&) = delete;
+
+  void refresh(const Matrix<double>& A);
+
+  int rows() const { return rows(0); }
+  int levels() const;
+  int rows(int level) const;
+  int64_t non_zeros(int level) const; // stored entries of the level's block
+  double lmax(int level) const;
+  // the aggregate of every row of `level` (rows(level) entries; the last level
+  // has none: throws)
+  void aggregates(int level, int32_t* out) const;
+  // a host copy of the operator of level >= 1 (it waits); NULL outputs skipped
+  void level_matrix(int level, int32_t* rowptr, int32_t* colind,
+                    double* values) const;
+  int64_t plan_bytes() const; // device memory beyond A: levels, lists, vectors
+  double symbolic_ms() const { return _symbolic_ms; }
+  double numeric_ms() const { return _numeric_ms; }
+  const AmgOptions& options() const { return _opt; }
+
+  // z = M^-1 r (amg_apply)
+  void apply(const double* r, double* z) const;
+
+private:
+  struct Level;
+  void numeric(const Matrix<double>& A, bool build);
+  void level_numbers(Level& L);
+  void check_usable() const;
+  void release();
+
+  HipExecutor& _exec;
+  AmgOptions _opt;
+  std::vector<std::unique_ptr<Level>> _levels;
+  uint64_t* _stat = nullptr;
+  bool _symmetric = false, _usable = false;
+  int64_t _num_values = 0;
+  double _symbolic_ms = 0, _numeric_ms = 0;
+};
+
+// z = M^-1 r.  `r`, `z`: DEVICE vectors of rows() doubles, any alignment, not
+// overlapping ("overlaps").  Runs on the executor's current stream; the host
+// does not wait.  Not reentrant (see above).
+void amg_apply(HipExecutor& exec, const AmgPreconditioner& M, const double* r,
+               double* z);
+
+// pcg_amg's workspace: the vectors and device scalars of pcg_sgs
+using AmgPcgWorkspace = SgsWorkspace;
+
+// CG with M = one AMG V-cycle from x0 = 0: pcg_sgs()'s recurrence and frame
+// with z = amg_apply(r).  pcg_sgs's contract holds word for word: the stop
+// test, the zero right-hand side, an unaligned x, "overlaps", "kmax", the
+// stream restored on every exit, and which options apply (poll_every,
+// time_spmv: ONE timed Matrix::mult per iteration).  After `done` the cycle may
+// still run on its own scratch; x, the history and k do not change.
+// M.rows() != A's rows throws.
+int pcg_amg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+            const AmgPreconditioner& M, const double* b, double* x, int kmax,
+            double rtol, std::vector<double>* rnorm_history = nullptr,
+            const CgOptions* options = nullptr, CgStats* stats = nullptr,
+            AmgPcgWorkspace* workspace = nullptr);
+
 // Work vectors + device scalars of bicgstab(), kept across calls like
 // PcgWorkspace; it regrows itself when a call needs more rows or more
 // iterations.
@@ -784,6 +917,8 @@ struct GmresPreconditioner {
   double lmin = 0, lmax = 0;
   // z = sgs_apply(*sgs, v); excludes the two above ("preconditioner")
   const SgsPreconditioner* sgs = nullptr;
+  // z = amg_apply(*amg, v); excludes the three above ("preconditioner")
+  const AmgPreconditioner* amg = nullptr;
 };
 
 // Work vectors + device scalars of gmres(), kept across calls like
@@ -824,7 +959,8 @@ public:
 
 // the argument rules of gmres() that need no device (std::runtime_error):
 // kmax < 0 ("kmax"), restart outside 1..kGmresMaxRestart ("restart"), sgs
-// together with dinv or a Chebyshev degree ("preconditioner"),
+// together with dinv or a Chebyshev degree, amg together with any of them
+// ("preconditioner"),
 // chebyshev_coefficients' rules ("degree", "bounds"), sgs->rows() != rows
 // (gmres_check_rules of solver_args.h on the fields of M)
 void gmres_check_arguments(const GmresPreconditioner* M, int restart, int kmax,
@@ -833,7 +969,7 @@ void gmres_check_arguments(const GmresPreconditioner* M, int restart, int kmax,
 // Restarted GMRES(m) from x0 = 0 with a RIGHT preconditioner and twice-iterated
 // classical Gram-Schmidt (CGS2), for a matrix that need not be symmetric.  It
 // has no breakdown except the lucky one, and M^-1 is any fixed linear operator:
-// none, dinv* (elementwise), chebyshev_apply or sgs_apply.  Only Matrix::mult
+// none, dinv* (elementwise), chebyshev_apply, sgs_apply or amg_apply.  Only Matrix::mult
 // is used: every plan form, both storages and every halo model serve.  With
 // `.` the global dot product, m = restart, every product, sum, difference,
 // quotient and square root one rounding of its own:

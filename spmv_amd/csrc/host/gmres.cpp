@@ -78,8 +78,14 @@ void gmres_check_arguments(const GmresPreconditioner* M, int restart, int kmax,
 {
   const GmresPreconditioner none;
   const GmresPreconditioner& p = M ? *M : none;
+  if (p.amg && p.sgs)
+    throw std::runtime_error(
+        "spmv::gmres - Error: one preconditioner at a time (amg excludes sgs, "
+        "dinv and the Chebyshev degree)");
+  // (amg obeys the rules of sgs)
   gmres_check_rules(restart, kmax, p.dinv != nullptr, p.cheb_degree, p.lmin,
-                    p.lmax, p.sgs != nullptr, p.sgs ? p.sgs->rows() : 0, rows);
+                    p.lmax, p.sgs || p.amg,
+                    p.amg ? p.amg->rows() : p.sgs ? p.sgs->rows() : 0, rows);
 }
 
 int gmres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
@@ -106,7 +112,7 @@ int gmres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   GmresWorkspace& w = workspace ? *workspace : own;
   const bool cheb = pre.cheb_degree >= 1;
   const bool diag = dinv && !cheb;
-  const bool any_pre = cheb || diag || pre.sgs;
+  const bool any_pre = cheb || diag || pre.sgs || pre.amg;
   const bool b_aligned = is_aligned16(b);
   const bool dinv_aligned = is_aligned16(dinv);
   const int64_t stride = gmres_basis_stride(N_padded);
@@ -171,6 +177,8 @@ int gmres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
                       pre.lmax, &w.cheb);
     else if (pre.sgs)
       sgs_apply(exec, *pre.sgs, src, w.z);
+    else if (pre.amg)
+      amg_apply(exec, *pre.amg, src, w.z);
     else
       throw_on_error(spmv_hip_gmres_diag_f64(ctx, M, di, src, w.z, nullptr),
                      "spmv_hip_gmres_diag_f64");

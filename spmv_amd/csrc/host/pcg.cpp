@@ -671,6 +671,47 @@ int pcg_sgs(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
       });
 }
 
+int pcg_amg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+            const AmgPreconditioner& Mpre, const double* b, double* x, int kmax,
+            double rtol, std::vector<double>* rnorm_history,
+            const CgOptions* options, CgStats* stats, AmgPcgWorkspace* workspace)
+{
+  const Dims dims = check_problem("pcg_amg", A, kmax);
+  const CgOptions opt = options ? *options : CgOptions();
+  if (Mpre.rows() != dims.M)
+    throw std::runtime_error(
+        "spmv::pcg_amg - Error: the preconditioner was built for "
+        + std::to_string(Mpre.rows()) + " rows, the matrix has "
+        + std::to_string(dims.M));
+  using Solve = PcgSolve<SgsWorkspace>;
+  // z = M^-1 r (the cycle runs on the object's own scratch, also after `done`)
+  // and the partials of r.z
+  auto precondition = [&](Solve& s) {
+    amg_apply(exec, Mpre, s.w.r, s.w.z);
+    throw_on_error(spmv_hip_sgs_dot_rz_f64(s.ctx, s.w.ws, s.M, s.w.r, s.w.z,
+                                           nullptr),
+                   "spmv_hip_sgs_dot_rz_f64");
+  };
+  return pcg_solve(
+      "pcg_amg", comm, exec, A, dims, b, x, nullptr, kmax, rtol, rnorm_history,
+      opt, stats, workspace, 1, {},
+      [&](Solve& s) {
+        throw_on_error(spmv_hip_sgs_init_f64(s.ctx, s.w.ws, s.M, b, s.w.r, s.xi,
+                                             nullptr),
+                       "spmv_hip_sgs_init_f64");
+        precondition(s);
+        exec.copy<double>(s.w.p, s.w.z, s.M);
+      },
+      [&](Solve& s, int k) {
+        stored_z_iteration(s, k, [&] {
+          throw_on_error(spmv_hip_sgs_update_r_f64(s.ctx, s.w.ws, k, s.M, s.w.Ap,
+                                                   s.w.r, nullptr),
+                         "spmv_hip_sgs_update_r_f64");
+          precondition(s);
+        });
+      });
+}
+
 double lambda_max_estimate(const Comm& comm, HipExecutor& exec,
                            const Matrix<double>& A, const double* dinv,
                            const double* v0, int steps)

@@ -65,6 +65,29 @@ void gmres_check_rules(int restart, int kmax, bool has_dinv, int cheb_degree,
                              + std::to_string(rows));
 }
 
+void amg_check_options(double theta, int max_levels, int64_t min_coarse_rows,
+                       int smooth_degree, int coarse_degree, double eig_ratio,
+                       double coarse_scale)
+{
+  auto refuse = [](const char* what) {
+    throw std::runtime_error(std::string("spmv::AmgOptions - Error: ") + what);
+  };
+  if (!(theta >= 0.0 && theta <= 1.0))
+    refuse("theta must be in [0, 1]");
+  if (max_levels < 1 || max_levels > 16)
+    refuse("max_levels must be 1..16");
+  if (min_coarse_rows < 1)
+    refuse("min_coarse_rows must be at least 1");
+  if (smooth_degree < 1 || smooth_degree > kChebyshevMaxDegree)
+    refuse("smooth_degree must be 1..16");
+  if (coarse_degree < 1 || coarse_degree > kChebyshevMaxDegree)
+    refuse("coarse_degree must be 1..16");
+  if (!(eig_ratio > 1.0) || !std::isfinite(eig_ratio))
+    refuse("eig_ratio must be a finite number > 1");
+  if (!(coarse_scale >= 1.0 && coarse_scale < 2.0))
+    refuse("coarse_scale must satisfy 1 <= coarse_scale < 2");
+}
+
 int64_t gmres_basis_stride(int64_t N_padded)
 {
   if (N_padded < 0 || N_padded == std::numeric_limits<int64_t>::max())

@@ -24,6 +24,13 @@ void gmres_check_rules(int restart, int kmax, bool has_dinv, int cheb_degree,
                        double lmin, double lmax, bool has_sgs, int64_t sgs_rows,
                        int64_t rows);
 
+// The rules of AmgOptions (cg.h); std::runtime_error names the field: theta in
+// [0, 1], max_levels 1..16, min_coarse_rows >= 1, smooth_degree and
+// coarse_degree 1..kChebyshevMaxDegree, eig_ratio > 1, 1 <= coarse_scale < 2.
+void amg_check_options(double theta, int max_levels, int64_t min_coarse_rows,
+                       int smooth_degree, int coarse_degree, double eig_ratio,
+                       double coarse_scale);
+
 // stride of the basis vectors: N_padded rounded up to an even number, so that
 // every v_j is 16-byte aligned
 int64_t gmres_basis_stride(int64_t N_padded);

@@ -165,6 +165,24 @@ _PROTOS = {
     "spmvh_ilu0_info": [vp, vp],
     "spmvh_ilu0_pattern": [vp, vp, vp, vp, vp],
     "spmvh_ilu0_factor": [vp, vp, vp, vp],
+    "spmvh_amg_check_options": [f64, C.c_int, i64, C.c_int, C.c_int, f64, f64],
+    "spmvh_amg_symbolic_create": [vp, vp, vp, vp, i64, i64, C.c_int, f64,
+                                  PTR(vp), vp],
+    "spmvh_amg_symbolic_get": [vp] * 11,
+    "spmvh_amg_symbolic_destroy": [vp],
+    "spmvh_amg_create": [vp, vp, vp, PTR(vp)],
+    "spmvh_amg_destroy": [vp],
+    "spmvh_amg_refresh": [vp, vp],
+    "spmvh_amg_info": [vp, vp],
+    "spmvh_amg_level_info": [vp, C.c_int, vp, PTR(f64)],
+    "spmvh_amg_aggregates": [vp, C.c_int, vp],
+    "spmvh_amg_level_matrix": [vp, C.c_int, vp, vp, vp],
+    "spmvh_amg_apply": [vp, vp, vp, vp],
+    "spmvh_pcg_amg": [vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int), vp, vp,
+                      C.c_int, PTR(f64), PTR(C.c_int)],
+    "spmvh_gmres_amg": [vp, vp, vp, vp, vp, vp, C.c_int, f64, f64, vp, C.c_int,
+                        C.c_int, f64, PTR(C.c_int), PTR(C.c_int), vp, vp,
+                        C.c_int, PTR(f64), PTR(C.c_int), vp],
     "spmvh_sgs_workspace_create": [vp, PTR(vp)],
     "spmvh_sgs_workspace_destroy": [vp],
     "spmvh_sgs_workspace_reserve_timing": [vp, C.c_int],
@@ -1175,6 +1193,164 @@ def pcg_sgs(comm, exec_, A, M, b_ptr, x_ptr, kmax, rtol, workspace=None,
     return k.value, hist[:k.value + 1]
 
 
+AMG_DEFAULTS = dict(theta=0.25, max_levels=10, min_coarse_rows=200,
+                    smooth_degree=2, coarse_degree=8, eig_ratio=4.0,
+                    coarse_scale=1.0)
+
+
+def _amg_options(options):
+    opt = dict(AMG_DEFAULTS)
+    unknown = set(options) - set(opt)
+    if unknown:
+        raise TypeError(f"unknown AmgOptions field(s): {sorted(unknown)}")
+    opt.update(options)
+    return opt
+
+
+def amg_check_options(**options):
+    """the rules of spmv::AmgOptions; raises SpmvHostError naming the field"""
+    o = _amg_options(options)
+    call("spmvh_amg_check_options", float(o["theta"]), int(o["max_levels"]),
+         int(o["min_coarse_rows"]), int(o["smooth_degree"]),
+         int(o["coarse_degree"]), float(o["eig_ratio"]),
+         float(o["coarse_scale"]))
+
+
+def amg_symbolic(rowptr, colind, values, nrows, ncols_local=None,
+                 symmetric=False, diagonal=None, theta=0.25):
+    """One coarsening step of host/amg_build.h -> dict(n_agg, agg, member_ptr,
+    member, rowptr, colind, src_ptr, src, xrow_ptr, xrow_col, xrow_src).
+    Symmetric input: the stored strictly lower block and `diagonal`.  A source
+    >= 0 indexes values, < 0 is diagonal[~src].  Host only."""
+    rp = np.ascontiguousarray(rowptr, np.int32)
+    ci = np.ascontiguousarray(colind, np.int32)
+    va = np.ascontiguousarray(values, np.float64)
+    dg = None if diagonal is None else np.ascontiguousarray(diagonal, np.float64)
+    n = int(nrows)
+    h = vp()
+    sizes = np.zeros(4, np.int64)
+    call("spmvh_amg_symbolic_create", _np_ptr(rp), _np_ptr(ci), _np_ptr(va),
+         _np_ptr(dg), n, n if ncols_local is None else int(ncols_local),
+         int(bool(symmetric)), float(theta), C.byref(h), _np_ptr(sizes))
+    try:
+        na, nnz, ns, nx = (int(v) for v in sizes)
+        out = dict(agg=np.zeros(n, np.int32),
+                   member_ptr=np.zeros(na + 1, np.int32),
+                   member=np.zeros(n, np.int32),
+                   rowptr=np.zeros(na + 1, np.int32),
+                   colind=np.zeros(nnz, np.int32),
+                   src_ptr=np.zeros(nnz + 1, np.int64),
+                   src=np.zeros(ns, np.int32),
+                   xrow_ptr=np.zeros(n + 1, np.int64),
+                   xrow_col=np.zeros(nx, np.int32),
+                   xrow_src=np.zeros(nx, np.int32))
+        call("spmvh_amg_symbolic_get", h, *[_np_ptr(a) for a in out.values()])
+    finally:
+        call("spmvh_amg_symbolic_destroy", h)
+    out["n_agg"] = na
+    return out
+
+
+class AmgPreconditioner:
+    """spmv::AmgPreconditioner: one V-cycle of plain aggregation multigrid on
+    A's local diagonal block.  Options: the fields of spmv::AmgOptions as
+    keywords.  Level 0 is A's own block: keep A alive (or refresh(A)).  An
+    application is not reentrant.  Raises SpmvHostError ("diagonal is not
+    positive", "released", "same index range", an option's name)."""
+
+    def __init__(self, exec_, A, **options):
+        o = _amg_options(options)
+        amg_check_options(**o)
+        packed = np.array([o[k] for k in AMG_DEFAULTS], np.float64)
+        h = vp()
+        call("spmvh_amg_create", exec_.h, A.h, _np_ptr(packed), C.byref(h))
+        self.h = h
+        self.options = o
+
+    def close(self):
+        if self.h:
+            call("spmvh_amg_destroy", self.h)
+            self.h = None
+
+    def refresh(self, A):
+        """new values on the same pattern: the Galerkin sums, the diagonals
+        and the bounds again, on the device alone"""
+        call("spmvh_amg_refresh", self.h, A.h)
+
+    def _info(self):
+        info = np.zeros(4, np.int64)
+        call("spmvh_amg_info", self.h, _np_ptr(info))
+        return [int(v) for v in info]
+
+    def _level(self, level):
+        sizes, lmax = np.zeros(2, np.int64), f64()
+        call("spmvh_amg_level_info", self.h, int(level), _np_ptr(sizes),
+             C.byref(lmax))
+        return int(sizes[0]), int(sizes[1]), lmax.value
+
+    def levels(self):
+        return self._info()[0]
+
+    def plan_bytes(self):
+        return self._info()[1]
+
+    def setup_ms(self):
+        """-> (host symbolic, device numeric) wall time of the constructor (of
+        the last refresh: numeric alone)"""
+        info = self._info()
+        return info[2] / 1000.0, info[3] / 1000.0
+
+    def rows(self, level=0):
+        return self._level(level)[0]
+
+    def non_zeros(self, level):
+        return self._level(level)[1]
+
+    def lmax(self, level):
+        return self._level(level)[2]
+
+    def aggregates(self, level):
+        out = np.zeros(self.rows(level), np.int32)
+        call("spmvh_amg_aggregates", self.h, int(level), _np_ptr(out))
+        return out
+
+    def level_matrix(self, level):
+        """-> (rowptr, colind, values) of the operator of a level >= 1"""
+        n, nnz, _ = self._level(level)
+        rp, ci = np.zeros(n + 1, np.int32), np.zeros(nnz, np.int32)
+        va = np.zeros(nnz)
+        call("spmvh_amg_level_matrix", self.h, int(level), _np_ptr(rp),
+             _np_ptr(ci), _np_ptr(va))
+        return rp, ci, va
+
+
+def amg_apply(exec_, M, r_ptr, z_ptr):
+    """spmv::amg_apply: z = M^-1 r on the executor's current stream; the host
+    does not wait."""
+    call("spmvh_amg_apply", exec_.h, M.h, r_ptr, z_ptr)
+
+
+AmgPcgWorkspace = SgsWorkspace
+
+
+def pcg_amg(comm, exec_, A, M, b_ptr, x_ptr, kmax, rtol, workspace=None,
+            time_spmv=False, poll_every=0, stats=None):
+    """spmv::pcg_amg: CG from x0 = 0 with the AMG V-cycle M -> (k,
+    rnorm_history); the arguments and the contract of pcg_sgs."""
+    kmax = int(kmax)
+    k, n = C.c_int(), C.c_int()
+    ms = f64()
+    hist = np.zeros(max(kmax, 0) + 1)
+    call("spmvh_pcg_amg", comm.h, exec_.h, A.h, M.h, b_ptr, x_ptr, kmax,
+         float(rtol), C.byref(k), _np_ptr(hist),
+         workspace.h if workspace else None,
+         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         C.byref(n))
+    if stats is not None:
+        stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, hist[:k.value + 1]
+
+
 class BicgstabWorkspace(_TimedWorkspace):
     """spmv::BicgstabWorkspace: work vectors kept across bicgstab() calls."""
     _prefix = "bicgstab"
@@ -1214,12 +1390,12 @@ GMRES_MAX_RESTART = 64
 
 def gmres(comm, exec_, A, b_ptr, x_ptr, restart, kmax, rtol, dinv_ptr=None,
           cheb=None, sgs=None, ws=None, time_spmv=False, poll_every=0,
-          stats=None):
+          stats=None, amg=None):
     """spmv::gmres: restarted GMRES from x0 = 0 with a right preconditioner for
     a matrix that need not be symmetric -> (k, rnorm_history, status).
     Preconditioner: none; dinv_ptr (the inverse diagonal); cheb = (degree, lmin,
-    lmax) for chebyshev_apply (with dinv_ptr or without); or sgs, an
-    SgsPreconditioner.  status: 0 converged or kmax reached, 1 the lucky
+    lmax) for chebyshev_apply (with dinv_ptr or without); sgs, an
+    SgsPreconditioner; or amg, an AmgPreconditioner.  status: 0 converged or kmax reached, 1 the lucky
     breakdown, 2 a zero pivot (host/cg.h).  stats (optional dict) receives
     spmv_ms_total and spmv_launches of a time_spmv solve (one SpMV per inner
     step)."""
@@ -1228,12 +1404,16 @@ def gmres(comm, exec_, A, b_ptr, x_ptr, restart, kmax, rtol, dinv_ptr=None,
     ms = f64()
     hist = np.zeros(max(kmax, 0) + 1)
     degree, lmin, lmax = cheb if cheb else (0, 0.0, 0.0)
-    call("spmvh_gmres", comm.h, exec_.h, A.h, b_ptr, x_ptr, dinv_ptr or None,
-         int(degree), float(lmin), float(lmax), sgs.h if sgs else None,
-         int(restart), kmax, float(rtol), C.byref(k), C.byref(status),
-         _np_ptr(hist), ws.h if ws else None,
-         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
-         C.byref(n))
+    args = [comm.h, exec_.h, A.h, b_ptr, x_ptr, dinv_ptr or None,
+            int(degree), float(lmin), float(lmax), sgs.h if sgs else None,
+            int(restart), kmax, float(rtol), C.byref(k), C.byref(status),
+            _np_ptr(hist), ws.h if ws else None,
+            int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+            C.byref(n)]
+    if amg is None:
+        call("spmvh_gmres", *args)
+    else:
+        call("spmvh_gmres_amg", *args, amg.h)
     if stats is not None:
         stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
     return k.value, hist[:k.value + 1], status.value
