@@ -1145,7 +1145,10 @@ int spmv_hip_ilu0_get_factor(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
  *             SPMV_HIP_AMG_STAT_WORDS 8-byte words, overwritten): word 0 = the
  *             number of d that are not finite or not > 0, the other words = the
  *             bit patterns of the workgroups' maxima of g (>= 0.0); the row-sum
- *             bound of dinv*A is the maximum over them.
+ *             bound of dinv*A is the maximum over them.  A g that is NaN never
+ *             replaces a number; the maximum may be +Inf (dinv of a subnormal
+ *             d, a sum that overflows), which word 0 does not count: the
+ *             caller refuses a bound that is not finite and > 0.
  *   restrict  rc[I] = (t_0 + t_1) + ..., t_m = r[i_m] - w[i_m] over the members
  *             of I ascending: one lane per aggregate
  *   prolong   z[i] = z[i] + scale * e[agg[i]]            (z 16-byte aligned)

@@ -575,6 +575,9 @@ int spmvh_gmres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
  * diagonal[~src].
  * spmvh_amg_create: options = NULL (defaults) or 7 doubles {theta, max_levels,
  * min_coarse_rows, smooth_degree, coarse_degree, eig_ratio, coarse_scale}.
+ * It and spmvh_amg_refresh fail with "diagonal is not positive" or, where a
+ * level's bound max_i |row i| / d_i is not finite and > 0, "the row-sum bound
+ * is not finite"; after a failed refresh every use fails until one succeeds.
  * spmvh_amg_info: info[4] = {levels, plan_bytes, symbolic us, numeric us}.
  * spmvh_amg_level_info: sizes[2] = {rows, stored entries}, *lmax the bound.
  * spmvh_amg_level_matrix: host copies of a level >= 1 (NULL outputs skipped).

@@ -130,7 +130,8 @@ void AmgPreconditioner::check_usable() const
   if (!_usable)
     throw std::runtime_error(
         "spmv::AmgPreconditioner - Error: the last refresh failed (the "
-        "diagonal is not positive); refresh before using it");
+        "diagonal is not positive, or the row-sum bound is not finite); "
+        "refresh before using it");
 }
 
 // d, dinv, the bound and the Chebyshev coefficients of one level
@@ -164,6 +165,16 @@ void AmgPreconditioner::level_numbers(Level& L)
     if (g > lmax)
       lmax = g;
   }
+  // d > 0 does not bound g: a subnormal d has dinv = Inf, and a row of huge
+  // entries overflows its sum.  (Rows whose g is NaN took no part: a level
+  // of such rows alone has the bound 0.0.)
+  if (!(lmax - lmax == 0.0) || !(lmax > 0.0))
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner - Error: the row-sum bound is not finite (max "
+        "of |row| / d = "
+        + std::to_string(lmax) + " on a level of " + std::to_string(L.rows)
+        + " rows: a diagonal entry too small to invert, or entries whose sum "
+          "overflows)");
   L.lmax = lmax;
   L.lmin = lmax / _opt.eig_ratio;
   chebyshev_coefficients(_opt.smooth_degree, L.lmin, L.lmax, L.sa, L.sb);

@@ -718,7 +718,11 @@ constexpr int kAmgMaxLevels = 16;
 //   g_i      (|a_e0| + |a_e1| + ...) * dinv_i over the expanded row in its order
 //   lmax_l   max_i g_i, the row-sum bound of dinv*A: a true upper bound, so the
 //            smoother converges and M is positive definite without a power
-//            iteration; lmin_l = lmax_l / eig_ratio
+//            iteration; lmin_l = lmax_l / eig_ratio.  A g_i that is NaN takes no
+//            part in the maximum (a NaN never replaces a number).  An lmax_l
+//            that is not finite and > 0 -- a subnormal d_i has dinv_i = Inf,
+//            a row of huge entries overflows its sum -- throws ("the row-sum
+//            bound is not finite")
 //   aggregates, P^T A_l P: host/amg_build.h; the coarse values are summed on
 //            the device from per-entry source lists, left to right
 // A level is coarsened while rows_l > min_coarse_rows and levels < max_levels;

@@ -1256,7 +1256,10 @@ class AmgPreconditioner:
     A's local diagonal block.  Options: the fields of spmv::AmgOptions as
     keywords.  Level 0 is A's own block: keep A alive (or refresh(A)).  An
     application is not reentrant.  Raises SpmvHostError ("diagonal is not
-    positive", "released", "same index range", an option's name)."""
+    positive"; "row-sum bound is not finite": a level's max_i |row i| / d_i is
+    Inf or 0, from a diagonal entry too small to invert or entries whose sum
+    overflows; "released", "same index range", an option's name).  After a
+    refresh that raised, the object raises until a refresh succeeds."""
 
     def __init__(self, exec_, A, **options):
         o = _amg_options(options)

@@ -33,6 +33,13 @@ def seq_sum(ptr, vals, from_zero=False):
     return out
 
 
+def nanless_max(g):
+    """the maximum from 0.0 in which a NaN never replaces a number (amg_diag's
+    `if (g > max) max = g`); -> float"""
+    g = np.asarray(g, np.float64)
+    return float(g[~np.isnan(g)].max(initial=0.0))
+
+
 def spmv_ltr(csr, x):
     """row sums left to right from 0.0, product rounded first"""
     rp, ci, va = csr
@@ -218,7 +225,9 @@ class AmgRef:
                 raise ValueError("diagonal is not positive")
             L["dinv"] = 1.0 / L["d"]
             g = seq_sum(ptr, np.abs(val)) * L["dinv"]
-            L["lmax"] = float(g.max(initial=0.0))
+            L["lmax"] = nanless_max(g)
+            if not (np.isfinite(L["lmax"]) and L["lmax"] > 0):
+                raise ValueError("the row-sum bound is not finite")
             L["lmin"] = L["lmax"] / o["eig_ratio"]
             self.levels.append(L)
             if frozen is not None:
