@@ -398,7 +398,8 @@ int spmv_hip_zwalk_table(int32_t num_rows, int64_t plane_rows, int grid,
  *   "sym_det"                            transposed-map kernel (0: atomics)
  *   "sym_window" "sym_rows"              the atomic symmetric kernels */
 int spmv_hip_csr_plan_set(spmv_hip_csr_plan* plan, const char* key, int value);
-/* What the plan decided and what it cost: "algo"; "lat", "lx", "slat", "sdia",
+/* What the plan decided and what it cost: "algo", "lanes_per_row" (of
+ * SPMV_HIP_ALGO_VECTOR; the fused AMG tail asks for it); "lat", "lx", "slat", "sdia",
  * "sym_det" (1 = that form is in use), "lat_blocks", "lx_blocks", "lx_staged";
  * "lattice_d1", "lattice_d2" (row distance of the next grid line / plane when
  * the matrix is a 3-D lattice, else 0), "zwalk", "zwalk_segments",
@@ -1193,6 +1194,69 @@ int spmv_hip_amg_prolong_f64(spmv_hip_ctx* ctx, const spmv_hip_amg_plan* plan,
 int spmv_hip_amg_post0_f64(spmv_hip_ctx* ctx, int64_t n, double b0,
                            const double* w, const double* r, const double* dinv,
                            double* d, double* z, void* stream);
+
+/* ---- The fused tail of the AMG V-cycle ------------------------------------------
+ * The levels t .. last of one application -- small levels, where a launch costs
+ * more than its work -- in ONE launch of one workgroup of 1024 threads: per
+ * level the Chebyshev smoother from z = 0, the product and the restrict on the
+ * way down, the coarsest level's iteration, then prolong and the continued
+ * smoother on the way up.  In: levels[0].r.  Out: levels[0].z.  The arithmetic
+ * per element is that of cheb_apply0 / cheb_step / amg_restrict / amg_prolong /
+ * amg_post0 (one definition, hip/amg_elem.h), and a level's product w = A z
+ * runs in the order `lanes_per_row` names:
+ *   0        one lane per row, left to right from 0.0, the product rounded
+ *            first (every plan form but the next one gives these bits)
+ *   4 .. 64  SPMV_HIP_ALGO_VECTOR's: lane l of the row adds the products l,
+ *            l + lanes, ... from 0.0, then lane l += lane l + off for off =
+ *            lanes / 2 .. 1 (ask the level's plan: csr_plan_get "algo" and
+ *            "lanes_per_row")
+ * so the result has the bits of the separate launches.
+ * All pointers of a level are DEVICE pointers except a and b (HOST, the
+ * level's Chebyshev coefficients: smooth_degree of them below the last level,
+ * coarse_degree on it).  rowptr / colind / values: the level's CSR block, square;
+ * dinv, r, w, dd, z: rows doubles each, 8-byte aligned; step: the coarsening
+ * step to the next level (NULL on the last), whose fine_rows / coarse_rows must
+ * be the two levels' rows.  tail_create reads rowptr and colind back and checks
+ * every index the kernel will use (the step's lists were checked by
+ * spmv_hip_amg_plan_create); SPMV_HIP_EINVAL otherwise, nothing is launched or
+ * written.  It waits for the device.  The arrays and steps must outlive the
+ * tail.  tail_set_coefficients rewrites one level's a, b in the device table
+ * (blocking; not while a run is in flight).  No second workgroup, no
+ * floating-point atomics, no scratch. */
+#define SPMV_HIP_AMG_TAIL_MAX_LEVELS 16
+#define SPMV_HIP_AMG_TAIL_MAX_DEGREE 16
+typedef struct spmv_hip_amg_tail spmv_hip_amg_tail;
+typedef struct spmv_hip_amg_tail_level {
+  int32_t rows;
+  int32_t lanes_per_row;
+  int64_t nnz;
+  const int32_t* rowptr;
+  const int32_t* colind;
+  const double* values;
+  const double* dinv;
+  double* r;
+  double* w;
+  double* dd;
+  double* z;
+  const spmv_hip_amg_plan* step;
+  const double* a;
+  const double* b;
+} spmv_hip_amg_tail_level;
+typedef struct spmv_hip_amg_tail_host {
+  int32_t num_levels;
+  int32_t smooth_degree;
+  int32_t coarse_degree;
+  double coarse_scale;
+  const spmv_hip_amg_tail_level* levels;
+} spmv_hip_amg_tail_host;
+int spmv_hip_amg_tail_create(spmv_hip_ctx* ctx, const spmv_hip_amg_tail_host* in,
+                             spmv_hip_amg_tail** tail);
+int spmv_hip_amg_tail_destroy(spmv_hip_amg_tail* tail);
+int spmv_hip_amg_tail_bytes(const spmv_hip_amg_tail* tail, int64_t* bytes);
+int spmv_hip_amg_tail_set_coefficients(spmv_hip_amg_tail* tail, int level,
+                                       const double* a, const double* b);
+int spmv_hip_amg_tail_run_f64(spmv_hip_ctx* ctx, const spmv_hip_amg_tail* tail,
+                              void* stream);
 
 /* ---- BiCGStab with an optional diagonal right preconditioner (spmv::bicgstab) ---
  * For nonsymmetric systems.  `dinv` is the inverse of the preconditioner's

@@ -582,6 +582,15 @@ int spmvh_gmres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
  * spmvh_amg_level_info: sizes[2] = {rows, stored entries}, *lmax the bound.
  * spmvh_amg_level_matrix: host copies of a level >= 1 (NULL outputs skipped).
  * spmvh_amg_apply: z = M^-1 r, device vectors, the host does not wait.
+ * spmvh_amg_set_tail_rows: AmgPreconditioner::set_tail_rows (0 = no tail; a
+ * negative value fails with "tail_rows" before anything else is looked at);
+ * spmvh_amg_check_tail_rows: that rule alone, no device.
+ * spmvh_amg_tail_levels: the number of levels the fused launch runs, 0 = none.
+ * spmvh_amg_tail_lanes (an addition for the tests alone, so that a case can
+ * assert which row order ran): lanes per row of `level`'s product inside the
+ * tail as its plan reported them (0 = one lane per row), -1 = not a level of
+ * the tail.  It reads spmv_hip_csr_plan_get's keys "algo" and "lanes_per_row",
+ * the latter a getter added for this purpose.
  * spmvh_pcg_amg: the arguments of spmvh_pcg_sgs.  spmvh_gmres_amg: the
  * arguments of spmvh_gmres and the AMG handle (excludes the others). */
 typedef struct spmvh_amg spmvh_amg;
@@ -611,6 +620,10 @@ int spmvh_amg_aggregates(spmvh_amg* M, int level, int32_t* agg);
 int spmvh_amg_level_matrix(spmvh_amg* M, int level, int32_t* rowptr,
                            int32_t* colind, double* values);
 int spmvh_amg_apply(spmvh_exec* exec, spmvh_amg* M, const double* r, double* z);
+int spmvh_amg_check_tail_rows(int64_t max_rows);
+int spmvh_amg_set_tail_rows(spmvh_amg* M, int64_t max_rows);
+int spmvh_amg_tail_levels(spmvh_amg* M, int* tail_levels);
+int spmvh_amg_tail_lanes(spmvh_amg* M, int level, int* lanes);
 int spmvh_pcg_amg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                   spmvh_amg* M, const double* b, double* x, int kmax,
                   double rtol, int* num_its, double* rnorm_history,

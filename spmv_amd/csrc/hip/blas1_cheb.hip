@@ -45,6 +45,7 @@
 #include "common.h"
 #include "blas1_stream.h"
 #include "pcg_ws.h"
+#include "amg_elem.h"
 
 #include <cmath>
 
@@ -64,12 +65,7 @@ __device__ __forceinline__ void store_partials(double acc,
   __syncthreads(); // s_red may be written again
 }
 
-// dinv*v, or v itself without a preconditioner diagonal
-template <bool PRE>
-__device__ __forceinline__ double scaled(double dv, double v)
-{
-  return PRE ? dv * v : v;
-}
+// (scaled<PRE>, cheb_first, cheb_corr, cheb_next: amg_elem.h)
 
 // ---- step 0 on a stored r: d = b0 * (dinv*r) ; z = d --------------------------
 template <bool NT, bool PRE, bool LAST>
@@ -91,8 +87,8 @@ __global__ __launch_bounds__(kBlock) void cheb_apply0_kernel(
     SPMV_FOR_LANE_ELEMS(i, n2)
     {
       f64x2 t;
-      t.x = b0 * scaled<PRE>(dv[u].x, rv[u].x);
-      t.y = b0 * scaled<PRE>(dv[u].y, rv[u].y);
+      t.x = cheb_first<PRE>(b0, dv[u].x, rv[u].x);
+      t.y = cheb_first<PRE>(b0, dv[u].y, rv[u].y);
       if constexpr (!LAST)
         vstore<NT>(d, i, t);
       vstore<NT>(z, i, t);
@@ -100,7 +96,7 @@ __global__ __launch_bounds__(kBlock) void cheb_apply0_kernel(
   }
   if (odd_tail(n)) {
     const int64_t i = n - 1;
-    const double t = b0 * scaled<PRE>(PRE ? dinv[i] : 0.0, r[i]);
+    const double t = cheb_first<PRE>(b0, PRE ? dinv[i] : 0.0, r[i]);
     if constexpr (!LAST)
       d[i] = t;
     z[i] = t;
@@ -135,12 +131,10 @@ __global__ __launch_bounds__(kBlock) void cheb_step_kernel(
     }
     SPMV_FOR_LANE_ELEMS(i, n2)
     {
-      const double tx = b * scaled<PRE>(dv[u].x, rv[u].x - wv[u].x);
-      const double ty = b * scaled<PRE>(dv[u].y, rv[u].y - wv[u].y);
-      ev[u].x = a * ev[u].x;
-      ev[u].y = a * ev[u].y;
-      ev[u].x += tx;
-      ev[u].y += ty;
+      const double tx = cheb_corr<PRE>(b, dv[u].x, rv[u].x, wv[u].x);
+      const double ty = cheb_corr<PRE>(b, dv[u].y, rv[u].y, wv[u].y);
+      ev[u].x = cheb_next(a, ev[u].x, tx);
+      ev[u].y = cheb_next(a, ev[u].y, ty);
       if constexpr (!LAST)
         vstore<NT>(d, i, ev[u]);
       zv[u].x += ev[u].x;
@@ -154,8 +148,8 @@ __global__ __launch_bounds__(kBlock) void cheb_step_kernel(
   }
   if (odd_tail(n)) {
     const int64_t i = n - 1;
-    const double t = b * scaled<PRE>(PRE ? dinv[i] : 0.0, r[i] - w[i]);
-    const double e = a * d[i] + t;
+    const double t = cheb_corr<PRE>(b, PRE ? dinv[i] : 0.0, r[i], w[i]);
+    const double e = cheb_next(a, d[i], t);
     if constexpr (!LAST)
       d[i] = e;
     const double zi = z[i] + e;

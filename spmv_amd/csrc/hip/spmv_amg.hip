@@ -22,14 +22,26 @@
 //   amg_prolong    z[i] = z[i] + scale * e[agg[i]]                     (streams z)
 //   amg_post0      d = b0 * (dinv * (r - w)) ; z = z + d     (streams, step 0 of
 //                  the post-smoother; steps >= 1 are cheb_step of blas1_cheb.hip)
+//   amg_tail       the levels t .. last of one application in ONE launch of one
+//                  workgroup of 1024 threads: the smoother, the products, the
+//                  restricts, the coarsest level and the way back up, level
+//                  after level from a descriptor table on the device.  The
+//                  element arithmetic is amg_elem.h's, shared with the kernels
+//                  above and blas1_cheb.hip; a level's product runs in the
+//                  order of its plan (one lane per row left to right, or the
+//                  sub-wavefront kernel's lanes and pairwise adds), so the bits
+//                  are those of the separate launches.
 //
 // No kernel waits on another workgroup; no floating-point atomics.  Built with
 // -ffp-contract=off: every product, sum, difference and quotient is a rounding
 // of its own.  plan_create checks every index a kernel will use.
 #include "common.h"
 #include "blas1_stream.h"
+#include "amg_elem.h"
+#include "amg_tail_rules.h"
 
 #include <new>
+#include <vector>
 
 #include "plan_scratch.h"
 
@@ -168,18 +180,7 @@ __global__ __launch_bounds__(kBlock) void amg_restrict_kernel(
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t I = (int64_t)blockIdx.x * kBlock + threadIdx.x; I < coarse_rows;
        I += stride) {
-    const int32_t m0 = member_ptr[I], m1 = member_ptr[I + 1];
-    double acc = 0.0; // (an aggregate has a member)
-    if (m0 < m1) {
-      const int32_t i = member[m0];
-      acc = r[i] - w[i];
-    }
-    for (int32_t m = m0 + 1; m < m1; ++m) {
-      const int32_t i = member[m];
-      const double t = r[i] - w[i];
-      acc = acc + t;
-    }
-    rc[I] = acc;
+    rc[I] = amg_restrict_sum(member_ptr[I], member_ptr[I + 1], member, r, w);
   }
 }
 
@@ -201,17 +202,14 @@ __global__ __launch_bounds__(kBlock) void amg_prolong_kernel(
     }
     SPMV_FOR_LANE_ELEMS(i, n2)
     {
-      const double tx = scale * ev[u].x;
-      const double ty = scale * ev[u].y;
-      zv[u].x = zv[u].x + tx;
-      zv[u].y = zv[u].y + ty;
+      zv[u].x = amg_prolong_elem(zv[u].x, scale, ev[u].x);
+      zv[u].y = amg_prolong_elem(zv[u].y, scale, ev[u].y);
       vstore<NT>(z, i, zv[u]);
     }
   }
   if (odd_tail(n)) {
     const int64_t i = n - 1;
-    const double t = scale * e[agg[i]];
-    z[i] = z[i] + t;
+    z[i] = amg_prolong_elem(z[i], scale, e[agg[i]]);
   }
 }
 
@@ -236,8 +234,8 @@ __global__ __launch_bounds__(kBlock) void amg_post0_kernel(
     SPMV_FOR_LANE_ELEMS(i, n2)
     {
       f64x2 t;
-      t.x = b0 * (dv[u].x * (rv[u].x - wv[u].x));
-      t.y = b0 * (dv[u].y * (rv[u].y - wv[u].y));
+      t.x = cheb_corr<true>(b0, dv[u].x, rv[u].x, wv[u].x);
+      t.y = cheb_corr<true>(b0, dv[u].y, rv[u].y, wv[u].y);
       if constexpr (!LAST)
         vstore<NT>(d, i, t);
       zv[u].x = zv[u].x + t.x;
@@ -247,7 +245,7 @@ __global__ __launch_bounds__(kBlock) void amg_post0_kernel(
   }
   if (odd_tail(n)) {
     const int64_t i = n - 1;
-    const double t = b0 * (dinv[i] * (r[i] - w[i]));
+    const double t = cheb_corr<true>(b0, dinv[i], r[i], w[i]);
     if constexpr (!LAST)
       d[i] = t;
     z[i] = z[i] + t;
@@ -336,9 +334,263 @@ bool amg_is_sound(const spmv_hip_amg_host& in)
   return true;
 }
 
+// ---- the fused tail ---------------------------------------------------------------
+// (AmgTailDev, the table entry the kernel reads, and its builder:
+// amg_tail_rules.h)
+constexpr int kTailBlock = kAmgTailBlock;
+
+// w = A z in the order the level's plan runs; ends with the barrier
+__device__ __forceinline__ void tail_product(const AmgTailDev* L)
+{
+  const int32_t n = L->rows;
+  const int lanes = L->lanes;
+  const int32_t* rowptr = L->rowptr;
+  const int32_t* colind = L->colind;
+  const double* values = L->values;
+  const double* z = L->z;
+  double* w = L->w;
+  if (lanes == 0) { // one lane per row, left to right from 0.0
+    for (int32_t i = threadIdx.x; i < n; i += kTailBlock) {
+      double sum = 0.0;
+      const int32_t hi = rowptr[i + 1];
+      for (int32_t e = rowptr[i]; e < hi; ++e)
+        sum += values[e] * z[colind[e]];
+      w[i] = sum;
+    }
+  } else { // csr_vector_kernel's order (spmv_csr.hip)
+    const int sub = threadIdx.x & (lanes - 1);
+    const int32_t grp = threadIdx.x / lanes, rpb = kTailBlock / lanes;
+    // (the same number of rounds for every thread: the shuffles are inside)
+    const int32_t rounds = (n + rpb - 1) / rpb;
+    for (int32_t rd = 0; rd < rounds; ++rd) {
+      const int32_t i = rd * rpb + grp;
+      double sum = 0.0;
+      if (i < n) {
+        const int32_t hi = rowptr[i + 1];
+        for (int32_t e = rowptr[i] + sub; e < hi; e += lanes)
+          sum += values[e] * z[colind[e]];
+      }
+      for (int off = lanes >> 1; off > 0; off >>= 1)
+        sum += __shfl_down(sum, off, lanes);
+      if (i < n && sub == 0)
+        w[i] = sum;
+    }
+  }
+  __syncthreads();
+}
+
+// the `degree`-step Chebyshev iteration for A z = r from z = 0
+__device__ __forceinline__ void tail_chebyshev(const AmgTailDev* L, int degree)
+{
+  const int32_t n = L->rows;
+  const double* r = L->r;
+  const double* dinv = L->dinv;
+  double* dd = L->dd;
+  double* z = L->z;
+  const double b0 = L->b[0];
+  for (int32_t i = threadIdx.x; i < n; i += kTailBlock) {
+    const double t = cheb_first<true>(b0, dinv[i], r[i]);
+    if (degree > 1)
+      dd[i] = t;
+    z[i] = t;
+  }
+  __syncthreads();
+  for (int j = 1; j < degree; ++j) {
+    tail_product(L);
+    const double a = L->a[j], b = L->b[j];
+    const double* w = L->w;
+    for (int32_t i = threadIdx.x; i < n; i += kTailBlock) {
+      const double t = cheb_corr<true>(b, dinv[i], r[i], w[i]);
+      const double e = cheb_next(a, dd[i], t);
+      if (j < degree - 1)
+        dd[i] = e;
+      z[i] = z[i] + e;
+    }
+    __syncthreads();
+  }
+}
+
+// Levels tab[0 .. nlev): down, the coarsest level, up.  ONE workgroup; the
+// phases are separated by __syncthreads() alone, and every loop around a barrier
+// or a shuffle has the same trip count in every thread.  In: tab[0].r.  Out:
+// tab[0].z.
+__global__ __launch_bounds__(kTailBlock) void amg_tail_kernel(
+    const AmgTailDev* __restrict__ tab, int nlev, int s, int c, double scale)
+{
+  for (int l = 0; l < nlev; ++l) {
+    const AmgTailDev* L = tab + l;
+    if (l == nlev - 1) {
+      tail_chebyshev(L, c);
+      break;
+    }
+    tail_chebyshev(L, s);
+    tail_product(L);
+    const int32_t nc = L->coarse_rows;
+    const int32_t* member_ptr = L->member_ptr;
+    double* rc = tab[l + 1].r;
+    for (int32_t I = threadIdx.x; I < nc; I += kTailBlock)
+      rc[I] = amg_restrict_sum(member_ptr[I], member_ptr[I + 1], L->member, L->r,
+                               L->w);
+    __syncthreads();
+  }
+  for (int l = nlev - 2; l >= 0; --l) {
+    const AmgTailDev* L = tab + l;
+    const int32_t n = L->rows;
+    const int32_t* agg = L->agg;
+    const double* e = tab[l + 1].z;
+    const double* r = L->r;
+    const double* dinv = L->dinv;
+    double* dd = L->dd;
+    double* z = L->z;
+    for (int32_t i = threadIdx.x; i < n; i += kTailBlock)
+      z[i] = amg_prolong_elem(z[i], scale, e[agg[i]]);
+    __syncthreads();
+    for (int j = 0; j < s; ++j) {
+      tail_product(L);
+      const double a = L->a[j], b = L->b[j];
+      const double* w = L->w;
+      for (int32_t i = threadIdx.x; i < n; i += kTailBlock) {
+        const double t = cheb_corr<true>(b, dinv[i], r[i], w[i]);
+        const double d = j == 0 ? t : cheb_next(a, dd[i], t);
+        if (j < s - 1)
+          dd[i] = d;
+        z[i] = z[i] + d;
+      }
+      __syncthreads();
+    }
+  }
+}
+
 } // namespace
 
+struct spmv_hip_amg_tail {
+  spmv_hip_ctx* ctx = nullptr;
+  int nlev = 0, s = 0, c = 0;
+  double scale = 1.0;
+  std::vector<AmgTailDev> host; // the table as uploaded
+  AmgTailDev* dev = nullptr;
+  int64_t bytes = 0;
+};
+
 extern "C" {
+
+int spmv_hip_amg_tail_create(spmv_hip_ctx* ctx, const spmv_hip_amg_tail_host* in,
+                             spmv_hip_amg_tail** tail)
+{
+  SPMV_REQUIRE(ctx && in && tail);
+  *tail = nullptr;
+  const int nlev = in->num_levels;
+  SPMV_REQUIRE(nlev >= 1 && nlev <= SPMV_HIP_AMG_TAIL_MAX_LEVELS && in->levels);
+  SPMV_SET_DEVICE(ctx);
+  spmv_hip_amg_tail* t = new (std::nothrow) spmv_hip_amg_tail();
+  if (!t)
+    return SPMV_HIP_ENOMEM;
+  t->ctx = ctx;
+  t->nlev = nlev;
+  t->s = in->smooth_degree;
+  t->c = in->coarse_degree;
+  t->scale = in->coarse_scale;
+  // Everything the kernel will index with is checked here, once: sizes,
+  // vectors and steps by the device-free builder (amg_tail_fill_table; a
+  // step's lists were checked by spmv_hip_amg_plan_create against the sizes it
+  // records), then the CSR arrays, read back from the device.
+  int rc = SPMV_HIP_OK;
+  std::vector<int32_t> rowptr, colind;
+  try {
+    t->host.resize((size_t)nlev);
+    std::vector<AmgTailStep> steps((size_t)nlev);
+    for (int l = 0; l < nlev; ++l) {
+      const spmv_hip_amg_plan* p = in->levels[l].step;
+      AmgTailStep& st = steps[(size_t)l];
+      st = AmgTailStep();
+      if (p && p->ctx == ctx) {
+        st.present = true;
+        st.fine_rows = p->fine_rows;
+        st.coarse_rows = p->coarse_rows;
+        st.agg = p->agg;
+        st.member_ptr = p->member_ptr;
+        st.member = p->member;
+      }
+    }
+    if (!amg_tail_fill_table(*in, steps.data(), t->host.data()))
+      rc = SPMV_HIP_EINVAL;
+    for (int l = 0; l < nlev && rc == SPMV_HIP_OK; ++l) {
+      const spmv_hip_amg_tail_level& h = in->levels[l];
+      rowptr.resize((size_t)h.rows + 1);
+      colind.resize((size_t)h.nnz);
+      hipError_t e = hipMemcpy(rowptr.data(), h.rowptr, rowptr.size() * 4,
+                               hipMemcpyDeviceToHost);
+      if (e == hipSuccess && h.nnz > 0)
+        e = hipMemcpy(colind.data(), h.colind, colind.size() * 4,
+                      hipMemcpyDeviceToHost);
+      if (e != hipSuccess)
+        rc = plan_fail(e);
+      else if (!amg_tail_csr_is_sound(h.rows, h.rows, h.nnz, rowptr.data(),
+                                      colind.data()))
+        rc = SPMV_HIP_EINVAL;
+    }
+  } catch (const std::bad_alloc&) {
+    rc = SPMV_HIP_ENOMEM;
+  }
+  if (rc == SPMV_HIP_OK) {
+    const size_t bytes = (size_t)nlev * sizeof(AmgTailDev);
+    hipError_t e = spmv_plan_malloc(&t->dev, bytes);
+    if (e == hipSuccess) {
+      t->bytes = (int64_t)bytes;
+      e = hipMemcpy(t->dev, t->host.data(), bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess)
+      rc = plan_fail(e);
+  }
+  if (rc != SPMV_HIP_OK) {
+    spmv_hip_amg_tail_destroy(t);
+    return rc;
+  }
+  *tail = t;
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_amg_tail_destroy(spmv_hip_amg_tail* tail)
+{
+  if (!tail)
+    return SPMV_HIP_OK;
+  (void)hipSetDevice(tail->ctx->device);
+  plan_drop(tail->dev);
+  delete tail;
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_amg_tail_bytes(const spmv_hip_amg_tail* tail, int64_t* bytes)
+{
+  SPMV_REQUIRE(tail && bytes);
+  *bytes = tail->bytes;
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_amg_tail_set_coefficients(spmv_hip_amg_tail* tail, int level,
+                                       const double* a, const double* b)
+{
+  SPMV_REQUIRE(tail && a && b && level >= 0 && level < tail->nlev);
+  SPMV_SET_DEVICE(tail->ctx);
+  const int degree = level == tail->nlev - 1 ? tail->c : tail->s;
+  AmgTailDev& d = tail->host[(size_t)level];
+  amg_tail_set_entry_coefficients(d, degree, a, b);
+  // (a blocking copy: the table is complete when this returns)
+  SPMV_CHECK_HIP(hipMemcpy(tail->dev + level, &d, sizeof d, hipMemcpyHostToDevice));
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_amg_tail_run_f64(spmv_hip_ctx* ctx, const spmv_hip_amg_tail* tail,
+                              void* stream)
+{
+  SPMV_REQUIRE(ctx && tail && tail->ctx == ctx && tail->dev);
+  SPMV_SET_DEVICE(ctx);
+  hipLaunchKernelGGL(amg_tail_kernel, dim3(1), dim3(kTailBlock), 0,
+                     spmv_stream(ctx, stream), tail->dev, tail->nlev, tail->s,
+                     tail->c, tail->scale);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
 
 int spmv_hip_amg_plan_create(spmv_hip_ctx* ctx, const spmv_hip_amg_host* in,
                              spmv_hip_amg_plan** plan)

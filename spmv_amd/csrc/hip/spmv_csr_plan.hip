@@ -833,6 +833,8 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
   SPMV_REQUIRE(plan && key && value);
   if (!strcmp(key, "algo"))
     *value = plan->algo;
+  else if (!strcmp(key, "lanes_per_row")) // of SPMV_HIP_ALGO_VECTOR
+    *value = plan->lanes_per_row;
   else if (!strcmp(key, "sym_det"))
     *value = plan->sym_det;
   else if (!strcmp(key, "slat"))

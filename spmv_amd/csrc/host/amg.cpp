@@ -5,6 +5,9 @@
 //                          plan ; a read-back of the values for the next step
 //     per level            diag (d, dinv, the bound) ; read of the counts
 // refresh() repeats the galerkin sums and the diag kernels only.
+// The tail (set_tail_rows): a descriptor table of the levels t .. last, built
+// by spmv_hip_amg_tail_create from the level objects as they are; apply() puts
+// one launch in the place of everything that touches those levels.
 #include "cg.h"
 
 #include <chrono>
@@ -12,6 +15,7 @@
 #include <string>
 #include <utility>
 
+#include "../hip/amg_tail_rules.h"
 #include "amg_build.h"
 #include "solver_common.h"
 
@@ -102,6 +106,8 @@ void AmgPreconditioner::release()
     _exec.synchronize(); // a cycle may still be in flight
   } catch (...) {
   }
+  spmv_hip_amg_tail_destroy(_tail); // (it refers to the levels' arrays)
+  _tail = nullptr;
   for (auto& lp : _levels) {
     if (!lp)
       continue;
@@ -328,8 +334,106 @@ void AmgPreconditioner::numeric(const Matrix<double>& A, bool build)
   }
   for (auto& lp : _levels)
     level_numbers(*lp);
+  // the tail's table holds coefficients of its own (the reads above waited:
+  // nothing is in flight)
+  for (int l = _tail ? _tail_first : levels(); l < levels(); ++l) {
+    const Level& L = *_levels[(size_t)l];
+    const bool last = l == levels() - 1;
+    throw_on_error(spmv_hip_amg_tail_set_coefficients(
+                       _tail, l - _tail_first, last ? L.ca : L.sa,
+                       last ? L.cb : L.sb),
+                   "spmv_hip_amg_tail_set_coefficients");
+  }
   _numeric_ms += clock.lap();
   _usable = true;
+}
+
+void AmgPreconditioner::drop_tail()
+{
+  if (!_tail)
+    return;
+  _exec.synchronize(); // an application may still be in flight
+  spmv_hip_amg_tail_destroy(_tail);
+  _tail = nullptr;
+  _tail_first = 0;
+  _tail_lanes.clear();
+}
+
+void AmgPreconditioner::build_tail()
+{
+  drop_tail();
+  const int nl = levels();
+  std::vector<int64_t> rows((size_t)nl);
+  for (int l = 0; l < nl; ++l)
+    rows[(size_t)l] = _levels[(size_t)l]->rows;
+  const int t = amg_tail_first_level(rows.data(), nl, _tail_rows);
+  if (t >= nl)
+    return;
+  _exec.synchronize(); // tail_create reads the levels' index arrays back
+  std::vector<spmv_hip_amg_tail_level> desc((size_t)(nl - t));
+  std::vector<int> lanes((size_t)(nl - t));
+  for (int l = t; l < nl; ++l) {
+    const Level& L = *_levels[(size_t)l];
+    const CSRMatrix<double>& B = *L.own;
+    const bool last = l == nl - 1;
+    // the order of the level's product is the plan's to say
+    const int vec = B.query("algo") == SPMV_HIP_ALGO_VECTOR
+                        ? B.query("lanes_per_row")
+                        : 0;
+    spmv_hip_amg_tail_level& d = desc[(size_t)(l - t)];
+    d = spmv_hip_amg_tail_level();
+    d.rows = L.rows;
+    d.lanes_per_row = lanes[(size_t)(l - t)] = vec;
+    d.nnz = L.nnz;
+    d.rowptr = B.rowptr();
+    d.colind = B.colind();
+    d.values = B.values();
+    d.dinv = L.dinv;
+    d.r = L.r;
+    d.w = L.w;
+    d.dd = L.dd;
+    d.z = L.z;
+    d.step = last ? nullptr : L.plan;
+    d.a = last ? L.ca : L.sa;
+    d.b = last ? L.cb : L.sb;
+  }
+  spmv_hip_amg_tail_host in{};
+  in.num_levels = nl - t;
+  in.smooth_degree = _opt.smooth_degree;
+  in.coarse_degree = _opt.coarse_degree;
+  in.coarse_scale = _opt.coarse_scale;
+  in.levels = desc.data();
+  throw_on_error(spmv_hip_amg_tail_create(_exec.context(), &in, &_tail),
+                 "spmv_hip_amg_tail_create");
+  _tail_first = t;
+  _tail_lanes = std::move(lanes);
+}
+
+void AmgPreconditioner::set_tail_rows(int64_t max_rows)
+{
+  amg_check_tail_rows(max_rows);
+  _tail_rows = max_rows;
+  try {
+    build_tail();
+  } catch (...) {
+    _tail_rows = 0; // no tail exists: the setting says so
+    throw;
+  }
+}
+
+int AmgPreconditioner::tail_levels() const
+{
+  return _tail ? levels() - _tail_first : 0;
+}
+
+int AmgPreconditioner::tail_lanes(int level) const
+{
+  if (level < 0 || level >= levels())
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner::tail_lanes - Error: no such level");
+  if (!_tail || level < _tail_first)
+    return -1;
+  return _tail_lanes[(size_t)(level - _tail_first)];
 }
 
 void AmgPreconditioner::refresh(const Matrix<double>& A)
@@ -406,6 +510,12 @@ void AmgPreconditioner::level_matrix(int level, int32_t* rowptr, int32_t* colind
 int64_t AmgPreconditioner::plan_bytes() const
 {
   int64_t total = SPMV_HIP_AMG_STAT_WORDS * 8;
+  if (_tail) {
+    int64_t bytes = 0;
+    throw_on_error(spmv_hip_amg_tail_bytes(_tail, &bytes),
+                   "spmv_hip_amg_tail_bytes");
+    total += bytes;
+  }
   for (const auto& lp : _levels) {
     const Level& L = *lp;
     int64_t bytes = 0;
@@ -459,8 +569,16 @@ void AmgPreconditioner::apply(const double* r, double* z) const
                      "spmv_hip_cheb_step_f64");
     }
   };
+  // the first level of the tail (nl: none): everything from its smoother down
+  // to the coarsest level and back up to its post-smoother is one launch
+  const int t = _tail ? _tail_first : nl;
   for (int l = 0; l < nl; ++l) {
     const Level& L = *_levels[(size_t)l];
+    if (l == t) {
+      throw_on_error(spmv_hip_amg_tail_run_f64(ctx, _tail, nullptr),
+                     "spmv_hip_amg_tail_run_f64");
+      break;
+    }
     if (l == nl - 1) {
       chebyshev(L, rhs(l), _opt.coarse_degree, L.ca, L.cb);
       break;
@@ -471,7 +589,7 @@ void AmgPreconditioner::apply(const double* r, double* z) const
                                              _levels[(size_t)l + 1]->r, nullptr),
                    "spmv_hip_amg_restrict_f64");
   }
-  for (int l = nl - 2; l >= 0; --l) {
+  for (int l = std::min(nl - 2, t - 1); l >= 0; --l) {
     const Level& L = *_levels[(size_t)l];
     throw_on_error(spmv_hip_amg_prolong_f64(ctx, L.plan, _opt.coarse_scale,
                                             _levels[(size_t)l + 1]->z, L.z,

@@ -1747,6 +1747,36 @@ int spmvh_amg_level_matrix(spmvh_amg* M, int level, int32_t* rowptr,
   });
 }
 
+int spmvh_amg_check_tail_rows(int64_t max_rows)
+{
+  return guarded([&] { amg_check_tail_rows(max_rows); });
+}
+
+int spmvh_amg_set_tail_rows(spmvh_amg* M, int64_t max_rows)
+{
+  return guarded([&] {
+    amg_check_tail_rows(max_rows); // (before the handle: no device is needed)
+    require(M != nullptr, "NULL argument");
+    M->M->set_tail_rows(max_rows);
+  });
+}
+
+int spmvh_amg_tail_levels(spmvh_amg* M, int* tail_levels)
+{
+  return guarded([&] {
+    require(M && tail_levels, "NULL argument");
+    *tail_levels = M->M->tail_levels();
+  });
+}
+
+int spmvh_amg_tail_lanes(spmvh_amg* M, int level, int* lanes)
+{
+  return guarded([&] {
+    require(M && lanes, "NULL argument");
+    *lanes = M->M->tail_lanes(level);
+  });
+}
+
 int spmvh_amg_apply(spmvh_exec* exec, spmvh_amg* M, const double* r, double* z)
 {
   return guarded([&] {

@@ -19,6 +19,7 @@ struct spmv_hip_bicg_ws;
 struct spmv_hip_gmres_ws;
 struct spmv_hip_mcgs_plan;
 struct spmv_hip_ilu0_plan;
+struct spmv_hip_amg_tail;
 
 namespace spmv
 {
@@ -754,6 +755,25 @@ constexpr int kAmgMaxLevels = 16;
 //
 // The level work vectors belong to the object: an application is NOT
 // reentrant -- one amg_apply / pcg_amg / gmres at a time per object.
+//
+// The tail.  The levels below the finest are small, and an application spends
+// most of its time launching their kernels.  set_tail_rows(max_rows) names the
+// longest suffix t .. levels()-1, t >= 1, in which every level has rows(l) <=
+// max_rows (amg_tail_first_level); apply() then runs levels 0 .. t-1 as before,
+// the restrict from level t-1 included, everything that touches the levels >= t
+// in ONE launch of one workgroup (spmv_hip_amg_tail_run_f64), and goes on with
+// the prolong into level t-1: (levels()-1-t)(4s+3) + 2c-1 launches become one.
+// The bits do not change: the same element arithmetic, and every level's product
+// in the order of its plan, as the plan reports it when set_tail_rows builds
+// the tail (a coarse block's plan does not change afterwards).  Level 0 is
+// never part of it; a hierarchy of one level has none.  0 (the default) = no
+// tail, the launches of the plain cycle.  A negative value throws ("tail_rows",
+// amg_check_tail_rows of solver_args.h) before anything touches a device.  It
+// may be called between applications, not while one is in flight; it waits for
+// the device.  refresh() keeps the setting and rewrites the tail's coefficients
+// before it returns.  Advice (one MI355X): 8192 -- levels
+// of about 3 000 rows gain (Poisson 64^3: an application 0.90 -> 0.41 ms), a
+// level of 21 000 to 32 000 rows in one workgroup loses several-fold.
 class AmgPreconditioner
 {
 public:
@@ -781,6 +801,13 @@ public:
   double numeric_ms() const { return _numeric_ms; }
   const AmgOptions& options() const { return _opt; }
 
+  void set_tail_rows(int64_t max_rows);
+  int tail_levels() const; // 0: no tail
+  // lanes per row of the product of `level` inside the tail (0 = one lane per
+  // row, left to right), as its plan reported them; -1: not a level of the tail.
+  // For tests: it lets a case assert WHICH order ran, nothing else needs it.
+  int tail_lanes(int level) const;
+
   // z = M^-1 r (amg_apply)
   void apply(const double* r, double* z) const;
 
@@ -790,11 +817,17 @@ private:
   void level_numbers(Level& L);
   void check_usable() const;
   void release();
+  void drop_tail();
+  void build_tail();
 
   HipExecutor& _exec;
   AmgOptions _opt;
   std::vector<std::unique_ptr<Level>> _levels;
   uint64_t* _stat = nullptr;
+  spmv_hip_amg_tail* _tail = nullptr;
+  int _tail_first = 0;
+  int64_t _tail_rows = 0;
+  std::vector<int> _tail_lanes;
   bool _symmetric = false, _usable = false;
   int64_t _num_values = 0;
   double _symbolic_ms = 0, _numeric_ms = 0;

@@ -65,6 +65,14 @@ void gmres_check_rules(int restart, int kmax, bool has_dinv, int cheb_degree,
                              + std::to_string(rows));
 }
 
+void amg_check_tail_rows(int64_t max_rows)
+{
+  if (max_rows < 0)
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner::set_tail_rows - Error: tail_rows must be at "
+        "least 0 (0 = no tail)");
+}
+
 void amg_check_options(double theta, int max_levels, int64_t min_coarse_rows,
                        int smooth_degree, int coarse_degree, double eig_ratio,
                        double coarse_scale)

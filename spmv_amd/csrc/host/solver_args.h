@@ -30,6 +30,9 @@ void gmres_check_rules(int restart, int kmax, bool has_dinv, int cheb_degree,
 void amg_check_options(double theta, int max_levels, int64_t min_coarse_rows,
                        int smooth_degree, int coarse_degree, double eig_ratio,
                        double coarse_scale);
+// The rule of AmgPreconditioner::set_tail_rows: max_rows >= 0; a negative value
+// throws std::runtime_error naming "tail_rows".
+void amg_check_tail_rows(int64_t max_rows);
 
 // stride of the basis vectors: N_padded rounded up to an even number, so that
 // every v_j is 16-byte aligned

@@ -385,3 +385,66 @@ def poisson3d_block(ctx, n, row_begin, row_end, part, with_diagonal=False,
     blk.owned += [b for b in (rowptr, colind, values, diag) if b is not None]
     blk.ghosts_below, blk.ghosts_above = gb.value, ga.value
     return blk
+
+
+class AmgTailLevel(C.Structure):
+    """spmv_hip_amg_tail_level: device pointers but for a, b (host)"""
+    _fields_ = [("rows", C.c_int32), ("lanes_per_row", C.c_int32),
+                ("nnz", C.c_int64), ("rowptr", C.c_void_p),
+                ("colind", C.c_void_p), ("values", C.c_void_p),
+                ("dinv", C.c_void_p), ("r", C.c_void_p), ("w", C.c_void_p),
+                ("dd", C.c_void_p), ("z", C.c_void_p), ("step", C.c_void_p),
+                ("a", C.c_void_p), ("b", C.c_void_p)]
+
+
+class AmgTailHost(C.Structure):
+    """spmv_hip_amg_tail_host"""
+    _fields_ = [("num_levels", C.c_int32), ("smooth_degree", C.c_int32),
+                ("coarse_degree", C.c_int32), ("coarse_scale", C.c_double),
+                ("levels", C.POINTER(AmgTailLevel))]
+
+
+class AmgTail:
+    """spmv_hip_amg_tail: the levels of an AMG cycle that one launch runs.
+    `ctx`: a spmv_hip_ctx pointer.  levels: dicts with the fields of
+    AmgTailLevel; a, b: the level's Chebyshev coefficients (numpy).  The
+    arrays and steps must outlive the handle.  Raises _lib.SpmvHipError
+    (EINVAL: an index out of range, a NULL or unaligned vector, a step that
+    does not fit the levels' rows) without launching anything."""
+
+    def __init__(self, ctx, levels, smooth_degree, coarse_degree, coarse_scale):
+        self.ctx, self.h = ctx, None
+        keep, arr = [], (AmgTailLevel * len(levels))()
+        for d, lv in zip(arr, levels):
+            for k, v in lv.items():
+                if k in ("a", "b"):
+                    v = np.ascontiguousarray(v, np.float64)
+                    keep.append(v)
+                    v = v.ctypes.data
+                elif hasattr(v, "value"):  # a c_void_p handle
+                    v = v.value
+                setattr(d, k, v)
+        desc = AmgTailHost(len(levels), smooth_degree, coarse_degree,
+                           coarse_scale, arr)
+        h = C.c_void_p()
+        call("spmv_hip_amg_tail_create", ctx, C.byref(desc), C.byref(h))
+        self.h = h
+
+    def set_coefficients(self, level, a, b):
+        a = np.ascontiguousarray(a, np.float64)
+        b = np.ascontiguousarray(b, np.float64)
+        call("spmv_hip_amg_tail_set_coefficients", self.h, int(level),
+             a.ctypes.data, b.ctypes.data)
+
+    def bytes(self):
+        n = C.c_int64()
+        call("spmv_hip_amg_tail_bytes", self.h, C.byref(n))
+        return n.value
+
+    def run(self, stream=None):
+        call("spmv_hip_amg_tail_run_f64", self.ctx, self.h, stream)
+
+    def close(self):
+        if self.h:
+            call("spmv_hip_amg_tail_destroy", self.h)
+            self.h = None

@@ -178,6 +178,10 @@ _PROTOS = {
     "spmvh_amg_aggregates": [vp, C.c_int, vp],
     "spmvh_amg_level_matrix": [vp, C.c_int, vp, vp, vp],
     "spmvh_amg_apply": [vp, vp, vp, vp],
+    "spmvh_amg_check_tail_rows": [i64],
+    "spmvh_amg_set_tail_rows": [vp, i64],
+    "spmvh_amg_tail_levels": [vp, PTR(C.c_int)],
+    "spmvh_amg_tail_lanes": [vp, C.c_int, PTR(C.c_int)],
     "spmvh_pcg_amg": [vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int), vp, vp,
                       C.c_int, PTR(f64), PTR(C.c_int)],
     "spmvh_gmres_amg": [vp, vp, vp, vp, vp, vp, C.c_int, f64, f64, vp, C.c_int,
@@ -1216,6 +1220,12 @@ def amg_check_options(**options):
          float(o["coarse_scale"]))
 
 
+def amg_check_tail_rows(max_rows):
+    """the rule of AmgPreconditioner.set_tail_rows; raises SpmvHostError
+    naming "tail_rows"; no device"""
+    call("spmvh_amg_check_tail_rows", int(max_rows))
+
+
 def amg_symbolic(rowptr, colind, values, nrows, ncols_local=None,
                  symmetric=False, diagonal=None, theta=0.25):
     """One coarsening step of host/amg_build.h -> dict(n_agg, agg, member_ptr,
@@ -1279,6 +1289,25 @@ class AmgPreconditioner:
         """new values on the same pattern: the Galerkin sums, the diagonals
         and the bounds again, on the device alone"""
         call("spmvh_amg_refresh", self.h, A.h)
+
+    def set_tail_rows(self, max_rows):
+        """Run the longest suffix of levels >= 1 whose levels all have at most
+        max_rows rows in ONE launch per application (0 = off, the default).
+        Same bits.  Between applications only; it waits for the device."""
+        call("spmvh_amg_set_tail_rows", self.h, int(max_rows))
+
+    def tail_levels(self):
+        """levels the fused launch runs; 0 = no tail"""
+        n = C.c_int()
+        call("spmvh_amg_tail_levels", self.h, C.byref(n))
+        return n.value
+
+    def tail_lanes(self, level):
+        """lanes per row of the level's product inside the tail, as its plan
+        reported them (0 = one lane per row); -1 = not in the tail"""
+        n = C.c_int()
+        call("spmvh_amg_tail_lanes", self.h, int(level), C.byref(n))
+        return n.value
 
     def _info(self):
         info = np.zeros(4, np.int64)

@@ -28,6 +28,12 @@ One JSON record per case with
   coarse_apply_ms    amg_apply of a hierarchy built on the matrix of level 1
                      alone: the share of an application spent below the finest
                      level, where the launches are small
+  tail               with --tail-rows (a comma list, 0 = off): per value, on the
+                     SAME object in the same process and with the same repeats,
+                     tail_levels, launches_per_apply (the tail's launches taken
+                     off, its one launch added), amg_apply_ms and
+                     pcg_amg_ms_per_iter, each as {min, median, max} of the
+                     repeats.  The yardstick is the line of 0 of the same run
   solvers            cg, pcg_sgs, pcg_amg at coarse_scale 1.0 and 1.6:
                      ms_per_iter of a fixed-length solve (rtol = 0, `--iters`
                      iterations) and iterations / ms_to_solution to `--rtol`
@@ -90,12 +96,21 @@ def run_case(case, args):
     s, c = M.options["smooth_degree"], M.options["coarse_degree"]
     launches = (nl - 1) * ((2 * s + 1) + 2 * s + 2) + (2 * c - 1) + 1
 
-    def many(fn):
+    def spread(ms):
+        ms = sorted(ms)
+        return dict(min=ms[0], median=ms[len(ms) // 2], max=ms[-1])
+
+    def many_all(fn):
+        """ms per call of every repeat"""
         def run():
             for _ in range(args.apply_reps):
                 fn()
             exec_.synchronize()
-        return min(timed(run, args.repeats, args.warmup)) / args.apply_reps
+        return [v / args.apply_reps
+                for v in timed(run, args.repeats, args.warmup)]
+
+    def many(fn):
+        return min(many_all(fn))
 
     mult_ms = many(lambda: A.mult(d_b, d_x))
     amg_apply_ms = many(lambda: host.amg_apply(exec_, M, d_b, d_x))
@@ -137,6 +152,21 @@ def run_case(case, args):
                          ms_to_solution=min(ms_sol),
                          final_rel_residual=float(h[-1] / h[0]),
                          converged=bool(h[-1] / h[0] < args.rtol))
+    tail = []
+    for tail_rows in args.tail_rows:
+        M.set_tail_rows(tail_rows)
+        tl = M.tail_levels()
+        t = nl - tl
+        saved = (nl - 1 - t) * (4 * s + 3) + (2 * c - 1) - 1 if tl else 0
+        tail.append(dict(
+            tail_rows=tail_rows, tail_levels=tl,
+            launches_per_apply=launches - saved,
+            amg_apply_ms=spread(
+                many_all(lambda: host.amg_apply(exec_, M, d_b, d_x))),
+            pcg_amg_ms_per_iter=spread(
+                [v / it for v in timed(lambda: solvers["pcg_amg_1.0"](it, 0.0),
+                                       args.repeats, args.warmup)])))
+    M.set_tail_rows(0)
     rec = dict(case=case, rows=rows, nnz=nnz, iters=it, repeats=args.repeats,
                rtol=args.rtol, kmax=args.kmax, levels=levels,
                operator_complexity=sum(v["entries"] for v in levels) / max(nnz, 1),
@@ -145,7 +175,7 @@ def run_case(case, args):
                refresh_ms=refresh_ms, launches_per_apply=launches,
                mult_ms=mult_ms, amg_apply_ms=amg_apply_ms,
                sgs_apply_ms=sgs_apply_ms, coarse_apply_ms=coarse_apply_ms,
-               solvers=out)
+               solvers=out, tail=tail)
     print(json.dumps(rec), flush=True)
     ws.close()
     cws.close()
@@ -171,6 +201,9 @@ def main():
     ap.add_argument("--kmax", type=int, default=5000,
                     help="iteration limit of the solves to rtol")
     ap.add_argument("--only", default=None, help="comma list of cases")
+    ap.add_argument("--tail-rows", default="",
+                    type=lambda v: [int(x) for x in v.split(",") if x != ""],
+                    help="comma list of set_tail_rows settings to time, 0 = off")
     ap.add_argument("--timeout", type=int, default=540, help="seconds per case")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles",
                                                   "amgbench.json"))
@@ -188,7 +221,8 @@ def main():
                "--rows", str(args.rows), "--iters", str(args.iters),
                "--repeats", str(args.repeats), "--warmup", str(args.warmup),
                "--apply-reps", str(args.apply_reps), "--rtol", str(args.rtol),
-               "--kmax", str(args.kmax)]
+               "--kmax", str(args.kmax), "--tail-rows",
+               ",".join(str(v) for v in args.tail_rows)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(p.stdout)
         sys.stdout.flush()
