@@ -33,6 +33,7 @@ import pytest
 import gmres_cases as gc
 import ilu0_cases as ic
 import oracle
+import sgs_layout
 import test_gpu_chebyshev as tc
 import test_gpu_gmres as tg
 import test_gpu_pcg as tp
@@ -42,6 +43,10 @@ from test_gpu_bicgstab import _dot_chunked
 from test_gpu_pcg import comm, exec_  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
+
+_McgsPart, _McgsHost = sgs_layout._McgsPart, sgs_layout._McgsHost
+_Ilu0Part, _Ilu0Host = sgs_layout._Ilu0Part, sgs_layout._Ilu0Host
+_sliced = sgs_layout._sliced
 
 SENTINEL, GUARD = tp.SENTINEL, tp.GUARD
 KMAX, RTOL = tp.KMAX, tp.RTOL
@@ -645,55 +650,6 @@ def test_slab_ranks_threaded_solves(world):
 
 
 # ---- 6. plan_create checks what a kernel will index with ------------------------------
-class _McgsPart(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in (
-        "color_slice", "slice_pos0", "slice_ptr", "len", "col", "val",
-        "color_long", "long_pos", "long_ptr", "long_col", "long_val")]
-
-
-class _McgsHost(C.Structure):
-    _fields_ = [("num_rows", C.c_int32), ("num_colors", C.c_int32),
-                ("perm", C.c_void_p), ("color_start", C.c_void_p),
-                ("dinv", C.c_void_p), ("before", _McgsPart), ("after", _McgsPart)]
-
-
-class _Ilu0Part(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("ptr", "cpos", "src", "slot")]
-
-
-class _Ilu0Host(C.Structure):
-    _fields_ = [("mcgs", _McgsHost), ("num_values", C.c_int64),
-                ("before", _Ilu0Part), ("after", _Ilu0Part)]
-
-
-def _sliced(sym, part):
-    """sgs_build.h's layout of a part without long rows, restated"""
-    n, start = len(sym["perm"]), sym["color_start"]
-    ptr, cols = part["ptr"], sym["perm"][part["cpos"]]
-    lens = np.diff(ptr).astype(np.int32)
-    assert lens.max() <= 64
-    color_slice, pos0, slice_ptr, col = [0], [], [0], []
-    for c in range(sym["num_colors"]):
-        for p0 in range(start[c], start[c + 1], 64):
-            p1 = min(p0 + 64, start[c + 1])
-            block = np.zeros((int(lens[p0:p1].max()), 64), np.int32)
-            for pos in range(p0, p1):
-                block[:lens[pos], pos - p0] = cols[ptr[pos]:ptr[pos + 1]]
-            col.append(block.ravel())
-            pos0.append(p0)
-            slice_ptr.append(slice_ptr[-1] + block.size)
-        color_slice.append(len(pos0))
-    col = np.concatenate(col).astype(np.int32)
-    assert np.array_equal(col, part["sliced_col"])  # the builder's own
-    return dict(color_slice=np.array(color_slice, np.int32),
-                slice_pos0=np.array(pos0, np.int32),
-                slice_ptr=np.array(slice_ptr, np.int64), len=lens, col=col,
-                val=np.zeros(len(col)),
-                color_long=np.zeros(sym["num_colors"] + 1, np.int32),
-                long_pos=None, long_ptr=np.zeros(1, np.int64), long_col=None,
-                long_val=None)
-
-
 def test_plan_create_refuses_every_bad_index(exec_):  # noqa: F811
     """spmv_hip_ilu0_plan_create through the C ABI on hand-built input: the
     sound input is taken, and each corrupted index a kernel would dereference
