@@ -48,6 +48,7 @@ typedef struct spmv_hip_csr_plan spmv_hip_csr_plan; /* CSRSpMV::_aux_data  */
 typedef struct spmv_hip_cg_ws spmv_hip_cg_ws;       /* cg() work vectors   */
 typedef struct spmv_hip_cgb_ws spmv_hip_cgb_ws;     /* cg_block() scalars  */
 typedef struct spmv_hip_pcg_ws spmv_hip_pcg_ws;     /* pcg() scalars       */
+typedef struct spmv_hip_pcgb_ws spmv_hip_pcgb_ws;   /* pcg_block() scalars */
 typedef struct spmv_hip_bicg_ws spmv_hip_bicg_ws;   /* bicgstab() scalars  */
 typedef struct spmv_hip_gmres_ws spmv_hip_gmres_ws; /* gmres() scalars     */
 typedef struct spmv_hip_comm spmv_hip_comm;         /* RCCL communicator   */
@@ -1056,6 +1057,77 @@ int spmv_hip_sgs_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
                               void* stream);
 int spmv_hip_sgs_dot_rz_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
                             const double* r, const double* z, void* stream);
+
+/* ---- Preconditioned CG for a block of right-hand sides (spmv::pcg_block) ----------
+ * pcg_sgs's recurrence with a stored Z = M^-1 R, once per column and in
+ * lockstep, on INTERLEAVED blocks (V[i * nrhs + c], 1 <= nrhs <=
+ * SPMV_HIP_CGB_MAX_NRHS, anything else SPMV_HIP_EINVAL), under the column rules
+ * of cg_block above: own alpha, beta and stop per column, a stopped column
+ * frozen, rr[0][c] == 0 stops at k = 0 with x = 0, the bits of column c depend
+ * on the matrix, M, column c of B, nrhs and c only.
+ *
+ * mcgs_apply_block: Z = M^-1 R for the nrhs interleaved vectors on the plan as
+ * it is (no second copy): 2 num_colors - 1 launches ordered by the stream
+ * alone; column c has the bits of mcgs_apply on column c.  R, Z: num_rows *
+ * nrhs doubles, any alignment (16-byte aligned ones take 16-byte gathers at
+ * nrhs = 2, 4, 8), not overlapping.  ws == NULL: the plain application; with
+ * the workspace of a solve (created for the same nrhs) every launch returns at
+ * once after all_done.
+ *
+ * Device state of a workspace: per k the 2 nrhs contiguous doubles
+ * {rz[k][0:nrhs], rr[k][0:nrhs]} (one all-reduce of 2 nrhs doubles) and
+ * pAp[k][0:nrhs]; done[c], kstop[c], all_done as for cg_block, the state words
+ * of SPMV_HIP_CGB_STATE_WORDS; two partial arrays [dot_partials_len][nrhs]
+ * (p.Ap then r.z; r.r), added in index order per column.
+ *   init         : R = B ; X = 0 ; partials of r.r (B: any alignment)
+ *   dot_pAp      : partials of p.Ap
+ *   dot_rz       : partials of r.z ; dinv == NULL: Z as the sweeps left it;
+ *                  else Z = dinv * R first (dinv: num_rows doubles, row i's
+ *                  for all its columns, any alignment), in the same pass
+ *   reduce_pAp   : partials -> pAp[k] ; raises done[c] and all_done (k >= 1)
+ *   reduce_rz_rr : partials -> {rz[k], rr[k]} (k >= 0)
+ *   update_r     : r -= alpha_c Ap, alpha_c = rz[k-1][c] / pAp[k][c] ;
+ *                  partials of r.r
+ *   update_xp    : x += alpha_c p ; stop test sqrt(rr[k][c]) / sqrt(rr[0][c]) <
+ *                  rtol ; p = beta_c p + z, beta_c = rz[k][c] / rz[k-1][c]
+ * nrhs = 2, 4, 8 stream 16-byte elements (every block 16-byte aligned, except
+ * B of init); k outside its range is SPMV_HIP_EINVAL. */
+int spmv_hip_mcgs_apply_block_f64(spmv_hip_ctx* ctx,
+                                  const spmv_hip_mcgs_plan* plan,
+                                  spmv_hip_pcgb_ws* ws, const double* R,
+                                  double* Z, int nrhs, void* stream);
+int spmv_hip_pcgb_ws_create(spmv_hip_ctx* ctx, int kmax, int nrhs,
+                            spmv_hip_pcgb_ws** ws);
+int spmv_hip_pcgb_ws_destroy(spmv_hip_pcgb_ws* ws);
+int spmv_hip_pcgb_ws_reset(spmv_hip_pcgb_ws* ws, double rtol, void* stream);
+int spmv_hip_pcgb_ws_capacity(const spmv_hip_pcgb_ws* ws, int* kmax, int* nrhs);
+/* device addresses of the scalars of iteration k (for the all-reduces): the
+ * 2 nrhs doubles {rz[k], rr[k]}, the nrhs doubles pAp[k] */
+int spmv_hip_pcgb_ws_rz_rr(spmv_hip_pcgb_ws* ws, int k, double** slot);
+int spmv_hip_pcgb_ws_pAp(spmv_hip_pcgb_ws* ws, int k, double** slot);
+/* copies the state words and {rz, rr}[0..kmax] (2 (kmax + 1) nrhs doubles of
+ * the workspace's capacity) to the host, async on stream; a short destination
+ * is SPMV_HIP_EINVAL and nothing is copied; either may be NULL. */
+int spmv_hip_pcgb_ws_read_async(spmv_hip_pcgb_ws* ws, int32_t* host_state,
+                                size_t host_state_len, double* host_rz_rr,
+                                size_t host_rz_rr_len, void* stream);
+int spmv_hip_pcgb_init_f64(spmv_hip_ctx* ctx, spmv_hip_pcgb_ws* ws, int64_t M,
+                           const double* B, double* R, double* X, void* stream);
+int spmv_hip_pcgb_dot_pAp_f64(spmv_hip_ctx* ctx, spmv_hip_pcgb_ws* ws, int64_t M,
+                              const double* P, const double* AP, void* stream);
+int spmv_hip_pcgb_dot_rz_f64(spmv_hip_ctx* ctx, spmv_hip_pcgb_ws* ws, int64_t M,
+                             const double* dinv, const double* R, double* Z,
+                             void* stream);
+int spmv_hip_pcgb_reduce_pAp(spmv_hip_ctx* ctx, spmv_hip_pcgb_ws* ws, int k,
+                             void* stream);
+int spmv_hip_pcgb_reduce_rz_rr(spmv_hip_ctx* ctx, spmv_hip_pcgb_ws* ws, int k,
+                               void* stream);
+int spmv_hip_pcgb_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcgb_ws* ws, int k,
+                               int64_t M, const double* AP, double* R,
+                               void* stream);
+int spmv_hip_pcgb_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_pcgb_ws* ws, int k,
+                                int64_t M, const double* Z, double* X,
+                                double* P, void* stream);
 
 /* ---- Multicolour ILU(0) factored on the device (spmv::Ilu0Preconditioner) ---------
  * M = (D~ + L~) D~^-1 (D~ + U~) on the local diagonal block in the colour-major

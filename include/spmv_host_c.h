@@ -477,6 +477,38 @@ int spmvh_pcg_sgs(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                   spmvh_sgs_workspace* ws, int flags, double* spmv_ms_total,
                   int* spmv_launches);
 
+/* ---- Preconditioned CG for several right-hand sides (spmv::pcg_block) -----------
+ * Blocks are INTERLEAVED as for spmvh_cg_block: element (i, c) at V[i * nrhs +
+ * c], 1 <= nrhs <= 8.
+ * spmvh_sgs_apply_block: spmv::sgs_apply_block -- Z = M^-1 R for nrhs vectors
+ * (device, rows * nrhs doubles each, any alignment, not overlapping:
+ * "overlaps"; "nrhs"), on the executor's current stream; M from spmvh_sgs_create
+ * or spmvh_ilu0_create.  Column c has the bits of spmvh_sgs_apply on column c.
+ * spmvh_pcg_block: spmv::pcg_block; arguments as spmvh_cg_block plus the
+ * preconditioner: exactly one of dinv (device, rows doubles, shared by all
+ * columns) and M is not NULL.  Errors name "nrhs", "kmax", "preconditioner",
+ * "rows", "pivot" or "overlaps".  ws: a reusable spmv::PcgBlockWorkspace (may
+ * be NULL).  flags as for spmvh_cg_block.
+ * spmvh_pcg_block_check_arguments: those rules alone (no device; the pointers
+ * are compared, never read). */
+typedef struct spmvh_pcg_block_workspace spmvh_pcg_block_workspace;
+int spmvh_sgs_apply_block(spmvh_exec* exec, spmvh_sgs* M, const double* R,
+                          double* Z, int nrhs);
+int spmvh_pcg_block_workspace_create(spmvh_exec* exec,
+                                     spmvh_pcg_block_workspace** ws);
+int spmvh_pcg_block_workspace_destroy(spmvh_pcg_block_workspace* ws);
+int spmvh_pcg_block_check_arguments(int nrhs, int kmax, int has_dinv,
+                                    int has_sgs, int64_t sgs_rows,
+                                    int64_t sgs_negative_pivots, int64_t rows,
+                                    const double* B, const double* X,
+                                    const double* dinv);
+int spmvh_pcg_block(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                    const double* B, double* X, int nrhs, const double* dinv,
+                    spmvh_sgs* M, int kmax, double rtol, int* max_its,
+                    int* iterations, double* rnorm_history,
+                    spmvh_pcg_block_workspace* ws, int flags,
+                    double* spmv_ms_total, int* spmv_launches);
+
 /* ---- Multicolour ILU(0) (spmv::Ilu0Preconditioner, host/cg.h) ----------------
  * spmvh_ilu0_symbolic_*: host/ilu0_build.h, no device.  Input as
  * spmvh_sgs_color; sizes[7] = {colours, entries of `before`, of `after`, sliced

@@ -23,9 +23,23 @@
 // loop above.  The long rows of a colour are served by extra wavefronts of the
 // same launch.
 //
+// The block form (mcgs_sweep_block_kernel, spmv_hip_mcgs_apply_block_f64) runs
+// the same sweeps on nrhs INTERLEAVED vectors, element (i, c) at V[i * nrhs +
+// c], on the same plan: a lane loads val[e] and col[e] once per entry, gathers
+// the nrhs contiguous doubles of z at that column and keeps nrhs sums, each
+// added in the entries' order -- column c has the bits of the single-vector
+// sweep on column c.  Inside a launch a row of colour c writes only its own
+// nrhs elements of Z and reads Z only at rows of other colours, so the in-place
+// update has no hazard here either.  nrhs = 2, 4, 8 are compiled widths with
+// 16-byte gathers and stores where R and Z are 16-byte aligned (a row of the
+// block is then 16-byte aligned too) and the scalar form of the same kernel
+// where they are not; one instantiation with nrhs at run time serves 1, 3, 5,
+// 6 and 7.
+//
 // Built with -ffp-contract=off: every product and sum is a rounding of its own.
 #include "common.h"
 #include "pcg_ws.h"
+#include "pcgb_ws.h"
 
 #include <vector>
 
@@ -96,6 +110,144 @@ __global__ __launch_bounds__(kBlock) void mcgs_sweep_kernel(
       z[i] = (r[i] - acc) * dinv[i];
     else
       z[i] = z[i] - dinv[i] * acc;
+  }
+}
+
+// ---- the block form -----------------------------------------------------------
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+// the KM slots of row i of a block: VEC 16 bytes at a time (KM == nrhs, even),
+// else one double at a time, slots c >= nrhs left at zero
+template <bool VEC, int KM>
+__device__ __forceinline__ void block_load(const double* v, int64_t i, int nrhs,
+                                           double (&out)[KM])
+{
+  const double* q = v + i * nrhs;
+#pragma unroll
+  for (int c = 0; c < KM; c += VEC ? 2 : 1) {
+    if constexpr (VEC) {
+      const f64x2 t = *reinterpret_cast<const f64x2*>(q + c);
+      out[c] = t.x;
+      out[c + 1] = t.y;
+    } else {
+      out[c] = c < nrhs ? q[c] : 0.0;
+    }
+  }
+}
+
+template <bool VEC, int KM>
+__device__ __forceinline__ void block_store(double* v, int64_t i, int nrhs,
+                                            const double (&in)[KM])
+{
+  double* q = v + i * nrhs;
+#pragma unroll
+  for (int c = 0; c < KM; c += VEC ? 2 : 1) {
+    if constexpr (VEC) {
+      f64x2 t;
+      t.x = in[c];
+      t.y = in[c + 1];
+      *reinterpret_cast<f64x2*>(q + c) = t;
+    } else {
+      if (c < nrhs)
+        q[c] = in[c];
+    }
+  }
+}
+
+// z(i, :) from the sums of row i, as mcgs_sweep_kernel does for one vector
+template <bool VEC, bool FORWARD, int KM>
+__device__ __forceinline__ void block_finish(int64_t i, int nrhs, double d,
+                                             const double (&acc)[KM],
+                                             const double* r, double* z)
+{
+  double out[KM];
+  block_load<VEC, KM>(FORWARD ? r : z, i, nrhs, out);
+#pragma unroll
+  for (int c = 0; c < KM; ++c) {
+    if constexpr (FORWARD)
+      out[c] = (out[c] - acc[c]) * d;
+    else
+      out[c] = out[c] - d * acc[c];
+  }
+  block_store<VEC, KM>(z, i, nrhs, out);
+}
+
+// One colour, one direction, nrhs interleaved vectors; the wavefronts are
+// mcgs_sweep_kernel's.  K = 2, 4, 8: the width at compile time (VEC: 16-byte
+// accesses); K = 0: nrhs at run time, 1..8.  Every index of an accumulator is
+// a constant after unrolling: they stay in registers.
+template <int K, bool VEC, bool FORWARD>
+__global__ __launch_bounds__(kBlock) void mcgs_sweep_block_kernel(
+    int32_t first_slice, int32_t num_slices, int32_t pos_end,
+    int32_t first_long, int32_t num_long,
+    const int32_t* __restrict__ slice_pos0,
+    const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ len,
+    const int32_t* __restrict__ col, const double* __restrict__ val,
+    const int32_t* __restrict__ long_pos, const int64_t* __restrict__ long_ptr,
+    const int32_t* __restrict__ long_col, const double* __restrict__ long_val,
+    const int32_t* __restrict__ perm, const double* __restrict__ dinv,
+    int nrhs_rt, const double* __restrict__ r, double* z,
+    const CgbState* __restrict__ st)
+{
+  constexpr int KM = K ? K : SPMV_CGB_MAX;
+  static_assert(!VEC || K != 0, "16-byte accesses need a compiled width");
+  const int nrhs = K ? K : nrhs_rt;
+  if (st && st->all_done)
+    return;
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (w < num_slices) {
+    const int64_t s = first_slice + w;
+    const int32_t pos = slice_pos0[s] + lane;
+    if (pos >= pos_end)
+      return;
+    const int32_t m = len[pos];
+    if (m < 0) // a long row: another wavefront's
+      return;
+    const int64_t base = slice_ptr[s] + lane;
+    double acc[KM] = {};
+#pragma unroll 2
+    for (int32_t k = 0; k < m; ++k) {
+      const int64_t e = base + (int64_t)k * 64;
+      const double a = val[e];
+      double zv[KM];
+      block_load<VEC, KM>(z, col[e], nrhs, zv);
+#pragma unroll
+      for (int c = 0; c < KM; ++c)
+        acc[c] = acc[c] + a * zv[c];
+    }
+    const int32_t i = perm[pos];
+    block_finish<VEC, FORWARD, KM>(i, nrhs, dinv[i], acc, r, z);
+    return;
+  }
+  const int64_t l = w - num_slices;
+  if (l >= num_long)
+    return;
+  const int32_t pos = long_pos[first_long + l];
+  const int64_t e0 = long_ptr[first_long + l], e1 = long_ptr[first_long + l + 1];
+  double acc[KM] = {};
+  for (int64_t e = e0; e < e1; e += 64) {
+    const int64_t mine = e + lane;
+    double prod[KM] = {};
+    if (mine < e1) {
+      const double a = long_val[mine];
+      double zv[KM];
+      block_load<VEC, KM>(z, long_col[mine], nrhs, zv);
+#pragma unroll
+      for (int c = 0; c < KM; ++c)
+        prod[c] = a * zv[c];
+    }
+    const int cnt = e1 - e < 64 ? (int)(e1 - e) : 64;
+    for (int j = 0; j < cnt; ++j) { // in the entries' order, every lane the same
+#pragma unroll
+      for (int c = 0; c < KM; ++c)
+        if (c < nrhs)
+          acc[c] = acc[c] + __shfl(prod[c], j, 64);
+    }
+  }
+  if (lane == 0) {
+    const int32_t i = perm[pos];
+    block_finish<VEC, FORWARD, KM>(i, nrhs, dinv[i], acc, r, z);
   }
 }
 
@@ -214,6 +366,39 @@ void launch_colour(const spmv_hip_mcgs_plan* plan, const McgsPartDev& p, int c,
                      p.long_val, plan->perm, plan->dinv, r, z, sc);
 }
 
+template <int K, bool VEC, bool FORWARD>
+void launch_colour_block(const spmv_hip_mcgs_plan* plan, const McgsPartDev& p,
+                         int c, int nrhs, const double* r, double* z,
+                         const CgbState* state, hipStream_t st)
+{
+  const int32_t ns = p.color_slice[c + 1] - p.color_slice[c];
+  const int32_t nl = p.color_long[c + 1] - p.color_long[c];
+  const int64_t waves = (int64_t)ns + nl;
+  if (waves == 0)
+    return;
+  const unsigned grid = (unsigned)((waves + kWaves - 1) / kWaves);
+  hipLaunchKernelGGL((mcgs_sweep_block_kernel<K, VEC, FORWARD>), dim3(grid),
+                     dim3(kBlock), 0, st, p.color_slice[c], ns,
+                     plan->color_start[c + 1], p.color_long[c], nl, p.slice_pos0,
+                     p.slice_ptr, p.len, p.col, p.val, p.long_pos, p.long_ptr,
+                     p.long_col, p.long_val, plan->perm, plan->dinv, nrhs, r, z,
+                     state);
+}
+
+// the 2C - 1 launches of one width
+template <int K, bool VEC>
+void apply_block(const spmv_hip_mcgs_plan* plan, int nrhs, const double* r,
+                 double* z, const CgbState* state, hipStream_t st)
+{
+  const int C = plan->num_colors;
+  for (int c = 0; c < C; ++c)
+    launch_colour_block<K, VEC, true>(plan, plan->before, c, nrhs, r, z, state,
+                                      st);
+  for (int c = C - 2; c >= 0; --c)
+    launch_colour_block<K, VEC, false>(plan, plan->after, c, nrhs, r, z, state,
+                                       st);
+}
+
 } // namespace
 
 extern "C" {
@@ -287,6 +472,39 @@ int spmv_hip_mcgs_apply_f64(spmv_hip_ctx* ctx, const spmv_hip_mcgs_plan* plan,
     launch_colour<true>(plan, plan->before, c, r, z, sc, st);
   for (int c = C - 2; c >= 0; --c)
     launch_colour<false>(plan, plan->after, c, r, z, sc, st);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_mcgs_apply_block_f64(spmv_hip_ctx* ctx,
+                                  const spmv_hip_mcgs_plan* plan,
+                                  spmv_hip_pcgb_ws* ws, const double* R,
+                                  double* Z, int nrhs, void* stream)
+{
+  SPMV_REQUIRE(nrhs >= 1 && nrhs <= SPMV_CGB_MAX);
+  SPMV_REQUIRE(ctx && plan && plan->ctx == ctx);
+  SPMV_REQUIRE(!ws || (ws->ctx == ctx && ws->nrhs == nrhs));
+  SPMV_REQUIRE(plan->n == 0 || (R && Z));
+  SPMV_SET_DEVICE(ctx);
+  hipStream_t st = spmv_stream(ctx, stream);
+  const CgbState* state = ws ? ws->st : nullptr;
+  const bool vec
+      = ((reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(Z)) & 15u)
+        == 0;
+  if (nrhs == 2 && vec)
+    apply_block<2, true>(plan, nrhs, R, Z, state, st);
+  else if (nrhs == 2)
+    apply_block<2, false>(plan, nrhs, R, Z, state, st);
+  else if (nrhs == 4 && vec)
+    apply_block<4, true>(plan, nrhs, R, Z, state, st);
+  else if (nrhs == 4)
+    apply_block<4, false>(plan, nrhs, R, Z, state, st);
+  else if (nrhs == 8 && vec)
+    apply_block<8, true>(plan, nrhs, R, Z, state, st);
+  else if (nrhs == 8)
+    apply_block<8, false>(plan, nrhs, R, Z, state, st);
+  else
+    apply_block<0, false>(plan, nrhs, R, Z, state, st);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }

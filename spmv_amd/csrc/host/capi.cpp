@@ -54,6 +54,7 @@ struct spmvh_pcg_workspace : WorkspaceHandle<PcgWorkspace> {};
 struct spmvh_chebyshev_workspace : WorkspaceHandle<ChebyshevWorkspace> {};
 struct spmvh_bicgstab_workspace : WorkspaceHandle<BicgstabWorkspace> {};
 struct spmvh_sgs_workspace : WorkspaceHandle<SgsWorkspace> {};
+struct spmvh_pcg_block_workspace : WorkspaceHandle<PcgBlockWorkspace> {};
 struct spmvh_gmres_workspace : WorkspaceHandle<GmresWorkspace> {};
 struct spmvh_sgs_build {
   SgsHostPlan plan;
@@ -1605,6 +1606,66 @@ int spmvh_pcg_sgs(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     *num_its = pcg_sgs(*comm->comm, *exec->hip, *A->A, *M->M, b, x, kmax, rtol,
                        rnorm_history ? &hist : nullptr, &opt, &st,
                        ws ? ws->ws.get() : nullptr);
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
+  });
+}
+
+// ---- Preconditioned CG for several right-hand sides -----------------------------------------
+int spmvh_sgs_apply_block(spmvh_exec* exec, spmvh_sgs* M, const double* R,
+                          double* Z, int nrhs)
+{
+  return guarded([&] {
+    require(exec && M, "NULL argument");
+    sgs_apply_block(*exec->hip, *M->M, R, Z, nrhs);
+  });
+}
+
+int spmvh_pcg_block_workspace_create(spmvh_exec* exec,
+                                     spmvh_pcg_block_workspace** ws)
+{
+  return workspace_create<PcgBlockWorkspace>(exec, ws);
+}
+
+int spmvh_pcg_block_workspace_destroy(spmvh_pcg_block_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_pcg_block_check_arguments(int nrhs, int kmax, int has_dinv,
+                                    int has_sgs, int64_t sgs_rows,
+                                    int64_t sgs_negative_pivots, int64_t rows,
+                                    const double* B, const double* X,
+                                    const double* dinv)
+{
+  return guarded([&] {
+    pcg_block_check_rules(nrhs, kmax, has_dinv != 0, has_sgs != 0, sgs_rows,
+                          sgs_negative_pivots, rows, B, X, dinv);
+  });
+}
+
+int spmvh_pcg_block(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                    const double* B, double* X, int nrhs, const double* dinv,
+                    spmvh_sgs* M, int kmax, double rtol, int* max_its,
+                    int* iterations, double* rnorm_history,
+                    spmvh_pcg_block_workspace* ws, int flags,
+                    double* spmv_ms_total, int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && max_its && iterations, "NULL argument");
+    std::vector<int> its;
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff)
+      opt.poll_every = (flags >> 8) & 0xff;
+    CgStats st;
+    BlockPreconditioner pre;
+    pre.dinv = dinv;
+    pre.sgs = M ? M->M.get() : nullptr;
+    *max_its = pcg_block(*comm->comm, *exec->hip, *A->A, B, X, nrhs, pre, kmax,
+                         rtol, &its, rnorm_history ? &hist : nullptr, &opt, &st,
+                         ws ? ws->ws.get() : nullptr);
+    std::copy(its.begin(), its.end(), iterations);
     copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
   });
 }

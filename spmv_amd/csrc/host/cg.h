@@ -15,6 +15,7 @@
 struct spmv_hip_cg_ws;
 struct spmv_hip_cgb_ws;
 struct spmv_hip_pcg_ws;
+struct spmv_hip_pcgb_ws;
 struct spmv_hip_bicg_ws;
 struct spmv_hip_gmres_ws;
 struct spmv_hip_mcgs_plan;
@@ -685,6 +686,97 @@ int pcg_sgs(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
             double rtol, std::vector<double>* rnorm_history = nullptr,
             const CgOptions* options = nullptr, CgStats* stats = nullptr,
             SgsWorkspace* workspace = nullptr);
+
+// ---- Preconditioned CG for several right-hand sides -----------------------------
+// Z = M^-1 R for nrhs INTERLEAVED vectors, the layout of Matrix::mult_block:
+// element (i, c) at R[i * nrhs + c] and Z[i * nrhs + c], DEVICE blocks of
+// M.rows() * nrhs doubles, 1 <= nrhs <= 8 ("nrhs"), any alignment, not
+// overlapping ("overlaps").  M is an SgsPreconditioner or an
+// Ilu0Preconditioner as it is: the sweeps read the plan sgs_apply reads, once
+// for all columns.  Column c of Z has the bits of sgs_apply on column c.  Runs
+// on the executor's current stream; the host does not wait.
+void sgs_apply_block(HipExecutor& exec, const SgsPreconditioner& M,
+                     const double* R, double* Z, int nrhs);
+
+// The preconditioner of pcg_block(): exactly one of the two is set.
+struct BlockPreconditioner {
+  // a positive DEVICE vector of rows doubles (any alignment), shared by all
+  // columns: z(i, c) = dinv[i] * r(i, c)
+  const double* dinv = nullptr;
+  // Z = sgs_apply_block(*sgs, R): an SgsPreconditioner or an Ilu0Preconditioner
+  const SgsPreconditioner* sgs = nullptr;
+};
+
+// Work vectors + device scalars of pcg_block(), kept across calls like
+// CgBlockWorkspace; it regrows itself when a call needs more rows, more
+// iterations or another nrhs.
+class PcgBlockWorkspace : public SolverWorkspace
+{
+public:
+  explicit PcgBlockWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
+  ~PcgBlockWorkspace();
+
+  // ---- internal to pcg_block() ----
+  void ensure(int64_t m_elems, int64_t n_elems, int kmax, int nrhs,
+              bool need_x);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(2 * (size_t)std::max(iterations, 0));
+  }
+  void release();
+
+  spmv_hip_pcgb_ws* ws = nullptr;
+  int kmax_cap = -1, nrhs_cap = 0;
+  int64_t m_cap = -1, n_cap = -1, x_cap = -1;
+  double *r = nullptr, *Ap = nullptr, *z = nullptr; // m_cap
+  double* x = nullptr; // x_cap: the iterate when the caller's X is unaligned
+  double* p = nullptr; // n_cap: padded, the ghost tail is zeroed by every solve
+  // flags: {all_done, done[], kstop[]} (spmv_hip.h); timing_ev: 2 events per
+  // iteration
+};
+
+// Preconditioned CG for several right-hand sides: pcg_sgs()'s recurrence with
+// a stored Z = M^-1 R, once per column of A X = B and in lockstep the way
+// cg_block() runs cg() -- one halo exchange of the block P, one
+// Matrix::mult_block, one application of M to the block and two all-reduces
+// (nrhs doubles: p.Ap; 2 nrhs doubles: {rz, rr}) per iteration.
+//
+//   R = B; Z = M^-1 R; P = Z; rz[0][c] = r_c.z_c; rr[0][c] = r_c.r_c
+//   for k = 1..kmax, per column c that has not stopped:
+//     AP = A P;  alpha_c = rz[k-1][c] / (p_c.Ap_c)
+//     r_c -= alpha_c Ap_c;  rr[k][c] = r_c.r_c;  Z = M^-1 R;  rz[k][c] = r_c.z_c
+//     x_c += alpha_c p_c
+//     if sqrt(rr[k][c]) / sqrt(rr[0][c]) < rtol: column c stops (p_c not updated)
+//     beta_c = rz[k][c] / rz[k-1][c];  p_c = beta_c p_c + z_c
+//
+// Layout, nrhs (1..8), X as the iterate, the 16-byte rule for X, iterations,
+// rnorm_history (nrhs * (kmax + 1) entries, -1.0 beyond a column's k) and the
+// value returned are cg_block()'s, and so are its column rules: own alpha,
+// beta, stop and count per column; a stopped column's x, r and p are frozen; a
+// column with r_0 . r_0 == 0 stops at k = 0 with x = 0; the bits of column c
+// depend on A, M, column c of B, nrhs and c, not on the other columns or on
+// when they stop.  With several ranks M is block-Jacobi over the ranks, as for
+// pcg_sgs().
+//
+// With M.dinv, Z = dinv * R is formed by the kernel that leaves the r.z
+// partials; with M.sgs the 2C - 1 block sweeps run instead (they may go on
+// writing a stopped column's Z: nothing reads it).  Per iteration beside the
+// mult_block: 3 streaming launches and 2 reducers (+ the sweeps).
+//
+// The arguments are checked before anything touches a device
+// (pcg_block_check_rules of solver_args.h; std::runtime_error): "nrhs", "kmax",
+// "preconditioner" (both or neither of dinv and sgs), "rows" (sgs->rows()),
+// "pivot" (an Ilu0Preconditioner with negative_pivots() > 0), "overlaps" (X
+// with B or dinv).  The executor's stream is restored on every exit path.
+// options: poll_every and time_spmv apply (one timed mult_block per
+// iteration); consumer_reductions, defer_x and mixed are IGNORED, as in
+// cg_block().
+int pcg_block(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+              const double* B, double* X, int nrhs, const BlockPreconditioner& M,
+              int kmax, double rtol, std::vector<int>* iterations = nullptr,
+              std::vector<double>* rnorm_history = nullptr,
+              const CgOptions* options = nullptr, CgStats* stats = nullptr,
+              PcgBlockWorkspace* workspace = nullptr);
 
 // ---- Aggregation multigrid preconditioner ---------------------------------------
 // Every rule is checked before anything touches a device; std::runtime_error

@@ -24,6 +24,17 @@ void gmres_check_rules(int restart, int kmax, bool has_dinv, int cheb_degree,
                        double lmin, double lmax, bool has_sgs, int64_t sgs_rows,
                        int64_t rows);
 
+// The argument rules of pcg_block() (std::runtime_error), in this order: nrhs
+// outside 1..8 ("nrhs"), kmax < 0 ("kmax"), both or neither of dinv and sgs
+// ("preconditioner"), an SGS / ILU(0) preconditioner of sgs_rows != rows rows
+// ("rows") or with negative pivots ("pivot"), X sharing a byte with B (rows *
+// nrhs doubles each) or with dinv (rows doubles) ("overlaps").  The pointers are
+// compared, never dereferenced.
+void pcg_block_check_rules(int nrhs, int kmax, bool has_dinv, bool has_sgs,
+                           int64_t sgs_rows, int64_t sgs_negative_pivots,
+                           int64_t rows, const double* B, const double* X,
+                           const double* dinv);
+
 // The rules of AmgOptions (cg.h); std::runtime_error names the field: theta in
 // [0, 1], max_levels 1..16, min_coarse_rows >= 1, smooth_degree and
 // coarse_degree 1..kChebyshevMaxDegree, eig_ratio > 1, 1 <= coarse_scale < 2.

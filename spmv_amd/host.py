@@ -155,6 +155,14 @@ _PROTOS = {
     "spmvh_sgs_info": [vp, PTR(C.c_int), PTR(C.c_int), PTR(i64)],
     "spmvh_sgs_colors": [vp, vp],
     "spmvh_sgs_apply": [vp, vp, vp, vp],
+    "spmvh_sgs_apply_block": [vp, vp, vp, vp, C.c_int],
+    "spmvh_pcg_block_workspace_create": [vp, PTR(vp)],
+    "spmvh_pcg_block_workspace_destroy": [vp],
+    "spmvh_pcg_block_check_arguments": [C.c_int, C.c_int, C.c_int, C.c_int, i64,
+                                        i64, i64, vp, vp, vp],
+    "spmvh_pcg_block": [vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, f64,
+                        PTR(C.c_int), vp, vp, vp, C.c_int, PTR(f64),
+                        PTR(C.c_int)],
     "spmvh_matrix_local_values": [vp, PTR(vp), PTR(vp)],
     "spmvh_matrix_plan_values_changed": [vp],
     "spmvh_ilu0_symbolic_create": [vp, vp, i64, i64, C.c_int, PTR(vp), vp],
@@ -1195,6 +1203,39 @@ def pcg_sgs(comm, exec_, A, M, b_ptr, x_ptr, kmax, rtol, workspace=None,
     if stats is not None:
         stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
     return k.value, hist[:k.value + 1]
+
+
+def sgs_apply_block(exec_, M, r_ptr, z_ptr, nrhs):
+    """spmv::sgs_apply_block: Z = M^-1 R for nrhs interleaved vectors (element
+    (i, c) at R[i * nrhs + c]) on the executor's current stream; M is an
+    SgsPreconditioner or an Ilu0Preconditioner.  Column c has the bits of
+    sgs_apply on column c."""
+    call("spmvh_sgs_apply_block", exec_.h, M.h, r_ptr, z_ptr, int(nrhs))
+
+
+class PcgBlockWorkspace(_Workspace):
+    """spmv::PcgBlockWorkspace: work vectors kept across pcg_block() calls."""
+    _prefix = "pcg_block"
+
+
+def pcg_block(comm, exec_, A, b_ptr, x_ptr, nrhs, kmax, rtol, dinv=None,
+              sgs=None, workspace=None, time_spmv=False, poll_every=0):
+    """spmv::pcg_block: preconditioned CG on A X = B for nrhs interleaved
+    right-hand sides; exactly one of dinv (device pointer, rows doubles) and
+    sgs (an SgsPreconditioner or Ilu0Preconditioner) -> (iterations[nrhs],
+    history[nrhs, kmax + 1], stats), as cg_block returns them."""
+    nrhs, kmax = int(nrhs), int(kmax)
+    kmx, n = C.c_int(), C.c_int()
+    ms = f64()
+    its = np.zeros(max(nrhs, 1), np.int32)
+    hist = np.full((max(nrhs, 1), max(kmax, 0) + 1), -1.0)
+    call("spmvh_pcg_block", comm.h, exec_.h, A.h, b_ptr, x_ptr, nrhs, dinv,
+         sgs.h if sgs is not None else None, kmax, float(rtol), C.byref(kmx),
+         _np_ptr(its), _np_ptr(hist), workspace.h if workspace else None,
+         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         C.byref(n))
+    return its, hist, dict(max_iterations=kmx.value, spmv_ms_total=ms.value,
+                           spmv_launches=n.value)
 
 
 AMG_DEFAULTS = dict(theta=0.25, max_levels=10, min_coarse_rows=200,
