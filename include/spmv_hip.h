@@ -1267,6 +1267,46 @@ int spmv_hip_amg_post0_f64(spmv_hip_ctx* ctx, int64_t n, double b0,
                            const double* w, const double* r, const double* dinv,
                            double* d, double* z, void* stream);
 
+/* ---- The V-cycle's vector kernels for nrhs INTERLEAVED vectors ------------------
+ * (spmv::amg_apply_block).  Element (i, c) of a block at V[i * nrhs + c], 1 <=
+ * nrhs <= SPMV_HIP_CGB_MAX_NRHS (anything else: SPMV_HIP_EINVAL); blocks of n *
+ * nrhs doubles (restrict / prolong: the plan's fine_rows or coarse_rows times
+ * nrhs); dinv (n doubles), agg and the member lists are shared by the columns.
+ * Column c of every result has the bits of the single-vector entry point above
+ * on column c, whatever the other columns hold.
+ *   cheb_apply0_block  d = b0 * (dinv*r) ; z = d.  d == NULL: the only step.
+ *   cheb_step_block    d = a*d + b*(dinv*(r - w)) ; z = z + d.  last != 0: d is
+ *                      read, not written.  (No workspace form: no dot product.)
+ *   amg_post0_block    d = b0 * (dinv*(r - w)) ; z = z + d.  d == NULL: the only
+ *                      step.
+ *   amg_restrict_block rc(I, c) = (t_0 + t_1) + ... over the members of I
+ *                      ascending, t_m = r(i_m, c) - w(i_m, c)
+ *   amg_prolong_block  z(i, c) = z(i, c) + scale * e(agg[i], c)
+ * dinv is required.  Any alignment: nrhs = 2, 4, 8 with every block pointer
+ * 16-byte aligned run the streaming form (16-byte accesses, non-temporal from
+ * the context's blas1_nt_min_elems doubles per block on), everything else one
+ * thread per row with scalar accesses -- the same bits.  n == 0 launches
+ * nothing. */
+int spmv_hip_cheb_apply0_block_f64(spmv_hip_ctx* ctx, int64_t n, int nrhs,
+                                   double b0, const double* r, const double* dinv,
+                                   double* d, double* z, void* stream);
+int spmv_hip_cheb_step_block_f64(spmv_hip_ctx* ctx, int64_t n, int nrhs, double a,
+                                 double b, int last, const double* w,
+                                 const double* r, const double* dinv, double* d,
+                                 double* z, void* stream);
+int spmv_hip_amg_post0_block_f64(spmv_hip_ctx* ctx, int64_t n, int nrhs, double b0,
+                                 const double* w, const double* r,
+                                 const double* dinv, double* d, double* z,
+                                 void* stream);
+int spmv_hip_amg_restrict_block_f64(spmv_hip_ctx* ctx,
+                                    const spmv_hip_amg_plan* plan, int nrhs,
+                                    const double* r, const double* w, double* rc,
+                                    void* stream);
+int spmv_hip_amg_prolong_block_f64(spmv_hip_ctx* ctx,
+                                   const spmv_hip_amg_plan* plan, int nrhs,
+                                   double scale, const double* e, double* z,
+                                   void* stream);
+
 /* ---- The fused tail of the AMG V-cycle ------------------------------------------
  * The levels t .. last of one application -- small levels, where a launch costs
  * more than its work -- in ONE launch of one workgroup of 1024 threads: per

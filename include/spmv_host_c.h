@@ -623,6 +623,19 @@ int spmvh_gmres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
  * tail as its plan reported them (0 = one lane per row), -1 = not a level of
  * the tail.  It reads spmv_hip_csr_plan_get's keys "algo" and "lanes_per_row",
  * the latter a getter added for this purpose.
+ * spmvh_amg_apply_block: spmv::amg_apply_block -- Z = M^-1 R for nrhs
+ * INTERLEAVED vectors (element (i, c) at V[i * nrhs + c], device, rows * nrhs
+ * doubles each, any alignment, not overlapping: "overlaps"; 1 <= nrhs <= 8:
+ * "nrhs"), on the executor's current stream; column c has the bits of
+ * spmvh_amg_apply on column c.  spmvh_amg_apply_block_check_arguments: those
+ * two rules alone, no device, the pointers are compared, never read.
+ * spmvh_amg_release_block_scratch: frees the block scratch (it waits); the
+ * next block application allocates it again.
+ * spmvh_pcg_block_amg: spmv::pcg_block with BlockPreconditioner::amg = M; the
+ * arguments of spmvh_pcg_block with M in place of dinv / the SGS handle.
+ * spmvh_pcg_block_amg_check_arguments: the rules of pcg_block with the third
+ * preconditioner (exactly one of the three: "preconditioner"; "rows" also for
+ * amg_rows), no device.
  * spmvh_pcg_amg: the arguments of spmvh_pcg_sgs.  spmvh_gmres_amg: the
  * arguments of spmvh_gmres and the AMG handle (excludes the others). */
 typedef struct spmvh_amg spmvh_amg;
@@ -652,6 +665,23 @@ int spmvh_amg_aggregates(spmvh_amg* M, int level, int32_t* agg);
 int spmvh_amg_level_matrix(spmvh_amg* M, int level, int32_t* rowptr,
                            int32_t* colind, double* values);
 int spmvh_amg_apply(spmvh_exec* exec, spmvh_amg* M, const double* r, double* z);
+int spmvh_amg_apply_block(spmvh_exec* exec, spmvh_amg* M, const double* R,
+                          double* Z, int nrhs);
+int spmvh_amg_apply_block_check_arguments(int nrhs, int64_t rows,
+                                          const double* R, const double* Z);
+int spmvh_amg_release_block_scratch(spmvh_amg* M);
+int spmvh_pcg_block_amg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                        const double* B, double* X, int nrhs, spmvh_amg* M,
+                        int kmax, double rtol, int* max_its, int* iterations,
+                        double* rnorm_history, spmvh_pcg_block_workspace* ws,
+                        int flags, double* spmv_ms_total, int* spmv_launches);
+int spmvh_pcg_block_amg_check_arguments(int nrhs, int kmax, int has_dinv,
+                                        int has_sgs, int has_amg,
+                                        int64_t sgs_rows,
+                                        int64_t sgs_negative_pivots,
+                                        int64_t amg_rows, int64_t rows,
+                                        const double* B, const double* X,
+                                        const double* dinv);
 int spmvh_amg_check_tail_rows(int64_t max_rows);
 int spmvh_amg_set_tail_rows(spmvh_amg* M, int64_t max_rows);
 int spmvh_amg_tail_levels(spmvh_amg* M, int* tail_levels);

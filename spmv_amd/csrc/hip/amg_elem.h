@@ -44,6 +44,17 @@ __device__ __forceinline__ double amg_prolong_elem(double z, double scale,
   return z + t;
 }
 
+// the two operations of amg_restrict_sum, for the block kernels
+// (spmv_amg_block.hip), which keep one sum per column and walk the members once
+__device__ __forceinline__ double amg_restrict_term(double r, double w)
+{
+  return r - w;
+}
+__device__ __forceinline__ double amg_restrict_add(double acc, double t)
+{
+  return acc + t;
+}
+
 // rc[I] = (t_0 + t_1) + ..., t_m = r[i_m] - w[i_m] over member[m0 .. m1)
 __device__ __forceinline__ double amg_restrict_sum(int32_t m0, int32_t m1,
                                                    const int32_t* member,

@@ -36,6 +36,8 @@ struct AmgPreconditioner::Level {
   // d, dinv, r, w, dd: rows; z: cols, ghost tail zero
   double *d = nullptr, *dinv = nullptr, *z = nullptr, *r = nullptr,
          *w = nullptr, *dd = nullptr;
+  // apply_block: r, w, dd of rows * _block_cap, z of cols * _block_cap doubles
+  double *rb = nullptr, *wb = nullptr, *ddb = nullptr, *zb = nullptr;
   double lmax = 0, lmin = 0;
   double sa[kChebyshevMaxDegree], sb[kChebyshevMaxDegree]; // smoother
   double ca[kChebyshevMaxDegree], cb[kChebyshevMaxDegree]; // coarsest level
@@ -108,6 +110,7 @@ void AmgPreconditioner::release()
   }
   spmv_hip_amg_tail_destroy(_tail); // (it refers to the levels' arrays)
   _tail = nullptr;
+  free_block_scratch();
   for (auto& lp : _levels) {
     if (!lp)
       continue;
@@ -528,7 +531,15 @@ int64_t AmgPreconditioner::plan_bytes() const
                + (int64_t)L.own->query("plan_kib") * 1024;
     if (L.rows > 0)
       total += ((int64_t)L.rows * 5 + L.cols) * 8;
+    // the block scratch, once it exists: the vectors, and the columns a coarse
+    // block's plan keeps for its per-column product (the plan's own: they stay
+    // with it after release_block_scratch)
+    if (L.rows > 0 && _block_cap > 0)
+      total += ((int64_t)L.rows * 3 + L.cols) * 8 * _block_cap;
+    if (L.own)
+      total += (int64_t)L.own->query("mv_kib") * 1024;
   }
+  total += _block_cols_elems * 8;
   return total;
 }
 
@@ -615,6 +626,204 @@ void amg_apply(HipExecutor&, const AmgPreconditioner& M, const double* r,
                double* z)
 {
   M.apply(r, z);
+}
+
+// ---- the block cycle --------------------------------------------------------------
+namespace
+{
+// column stride of level 0's per-column product: whole units of 4 doubles, so
+// that every column starts 16-byte aligned
+int64_t block_col_stride(int64_t n) { return (n + 3) & ~(int64_t)3; }
+} // namespace
+
+void AmgPreconditioner::free_block_scratch() const
+{
+  for (auto& lp : _levels) {
+    if (!lp)
+      continue;
+    for (double** v : {&lp->rb, &lp->wb, &lp->ddb, &lp->zb}) {
+      try {
+        if (*v)
+          _exec.free(*v);
+      } catch (...) {
+      }
+      *v = nullptr;
+    }
+  }
+  try {
+    if (_block_cols)
+      _exec.free(_block_cols);
+  } catch (...) {
+  }
+  _block_cols = nullptr;
+  _block_cols_elems = 0;
+  _block_cap = _block_last = 0;
+}
+
+void AmgPreconditioner::release_block_scratch()
+{
+  if (_block_cap == 0 && !_block_cols)
+    return;
+  _exec.synchronize(); // a cycle may still be in flight
+  free_block_scratch();
+}
+
+void AmgPreconditioner::ensure_block_scratch(int nrhs) const
+{
+  if (nrhs <= _block_cap)
+    return;
+  if (_block_cap > 0 || _block_cols) {
+    _exec.synchronize(); // an application of the narrower width may be in flight
+    free_block_scratch();
+  }
+  try {
+    for (auto& lp : _levels) {
+      Level& L = *lp;
+      if (L.rows == 0)
+        continue;
+      const size_t n = (size_t)L.rows * (size_t)nrhs;
+      for (double** v : {&L.rb, &L.wb, &L.ddb})
+        *v = _exec.alloc<double>(n);
+      L.zb = _exec.alloc<double>((size_t)L.cols * (size_t)nrhs);
+      // A coarse block whose single-vector product adds in the sub-wavefront
+      // order: its mult_block takes that launch per column from now on
+      if (L.own && L.own->query("algo") == SPMV_HIP_ALGO_VECTOR)
+        L.own->tune("mv_native", 0);
+    }
+  } catch (...) {
+    free_block_scratch();
+    throw;
+  }
+  _block_cap = nrhs;
+  _block_last = 0;
+}
+
+void AmgPreconditioner::apply_block(const double* R, double* Z, int nrhs) const
+{
+  const int64_t n0 = _levels.empty() ? 0 : _levels[0]->rows;
+  amg_apply_block_check_rules(nrhs, n0, R, Z);
+  if (nrhs == 1) {
+    apply(R, Z);
+    return;
+  }
+  check_usable();
+  if (n0 == 0)
+    return;
+  if (!R || !Z)
+    throw std::runtime_error("amg_apply_block: NULL vector");
+  ensure_block_scratch(nrhs);
+  spmv_hip_ctx* ctx = _exec.context();
+  const Level& L0 = *_levels[0];
+  const int nl = levels(), s = _opt.smooth_degree;
+  const size_t m0 = (size_t)n0 * (size_t)nrhs;
+
+  // everything on the executor's current stream, nothing waits
+  if (nrhs != _block_last) { // the ghost tail of z sits where this width puts it
+    if (L0.cols > L0.rows)
+      _exec.memset<double>(L0.zb + m0, 0,
+                           (size_t)(L0.cols - L0.rows) * (size_t)nrhs);
+    _block_last = nrhs;
+  }
+  const double* r0 = R;
+  if (!is_aligned16(R)) { // the streaming kernels load 16 bytes at a time
+    _exec.copy<double>(L0.rb, R, m0);
+    r0 = L0.rb;
+  }
+  auto rhs = [&](int l) { return l == 0 ? r0 : _levels[(size_t)l]->rb; };
+  // w = A z.  mult_block's columns have mult's bits except where the native
+  // multi-vector kernel would replace the sub-wavefront kernel (nrhs 2, 4, 8):
+  // the coarse blocks were told not to take it (ensure_block_scratch); level 0
+  // is the caller's matrix and is multiplied column by column here.
+  auto product = [&](const Level& L) {
+    const bool native = nrhs == 2 || nrhs == 4 || nrhs == 8;
+    if (L.own || !native || L.op->symmetric() || L.nnz == 0
+        || L.op->query("algo") != SPMV_HIP_ALGO_VECTOR) {
+      L.op->mult_block(1.0, L.zb, 0.0, L.wb, nrhs);
+      return;
+    }
+    const int64_t ldx = block_col_stride(L.cols), ldy = block_col_stride(L.rows);
+    const int64_t need = (ldx + ldy) * nrhs;
+    if (need > _block_cols_elems) {
+      if (_block_cols) {
+        _exec.synchronize();
+        _exec.free(_block_cols);
+        _block_cols = nullptr;
+        _block_cols_elems = 0;
+      }
+      _block_cols = _exec.alloc<double>((size_t)need);
+      _block_cols_elems = need;
+    }
+    double* xs = _block_cols;
+    double* ys = xs + ldx * nrhs;
+    throw_on_error(spmv_hip_deinterleave_f64(ctx, L.cols, nrhs, L.zb, ldx, xs,
+                                             nullptr),
+                   "spmv_hip_deinterleave_f64");
+    for (int c = 0; c < nrhs; ++c)
+      L.op->mult(1.0, xs + ldx * c, 0.0, ys + ldy * c);
+    throw_on_error(spmv_hip_interleave_f64(ctx, L.rows, nrhs, ys, ldy, L.wb,
+                                           nullptr),
+                   "spmv_hip_interleave_f64");
+  };
+  auto chebyshev = [&](const Level& L, const double* rl, int degree,
+                       const double* a, const double* b) {
+    throw_on_error(spmv_hip_cheb_apply0_block_f64(ctx, L.rows, nrhs, b[0], rl,
+                                                  L.dinv,
+                                                  degree > 1 ? L.ddb : nullptr,
+                                                  L.zb, nullptr),
+                   "spmv_hip_cheb_apply0_block_f64");
+    for (int j = 1; j < degree; ++j) {
+      product(L);
+      throw_on_error(spmv_hip_cheb_step_block_f64(ctx, L.rows, nrhs, a[j], b[j],
+                                                  j == degree - 1, L.wb, rl,
+                                                  L.dinv, L.ddb, L.zb, nullptr),
+                     "spmv_hip_cheb_step_block_f64");
+    }
+  };
+  // (the fused tail is a single-vector kernel: every level runs launch by
+  // launch, with the same bits)
+  for (int l = 0; l < nl; ++l) {
+    const Level& L = *_levels[(size_t)l];
+    if (l == nl - 1) {
+      chebyshev(L, rhs(l), _opt.coarse_degree, L.ca, L.cb);
+      break;
+    }
+    chebyshev(L, rhs(l), s, L.sa, L.sb);
+    product(L);
+    throw_on_error(spmv_hip_amg_restrict_block_f64(ctx, L.plan, nrhs, rhs(l),
+                                                   L.wb,
+                                                   _levels[(size_t)l + 1]->rb,
+                                                   nullptr),
+                   "spmv_hip_amg_restrict_block_f64");
+  }
+  for (int l = nl - 2; l >= 0; --l) {
+    const Level& L = *_levels[(size_t)l];
+    throw_on_error(spmv_hip_amg_prolong_block_f64(ctx, L.plan, nrhs,
+                                                  _opt.coarse_scale,
+                                                  _levels[(size_t)l + 1]->zb,
+                                                  L.zb, nullptr),
+                   "spmv_hip_amg_prolong_block_f64");
+    product(L);
+    throw_on_error(spmv_hip_amg_post0_block_f64(ctx, L.rows, nrhs, L.sb[0], L.wb,
+                                                rhs(l), L.dinv,
+                                                s > 1 ? L.ddb : nullptr, L.zb,
+                                                nullptr),
+                   "spmv_hip_amg_post0_block_f64");
+    for (int j = 1; j < s; ++j) {
+      product(L);
+      throw_on_error(spmv_hip_cheb_step_block_f64(ctx, L.rows, nrhs, L.sa[j],
+                                                  L.sb[j], j == s - 1, L.wb,
+                                                  rhs(l), L.dinv, L.ddb, L.zb,
+                                                  nullptr),
+                     "spmv_hip_cheb_step_block_f64");
+    }
+  }
+  _exec.copy<double>(Z, L0.zb, m0);
+}
+
+void amg_apply_block(HipExecutor&, const AmgPreconditioner& M, const double* R,
+                     double* Z, int nrhs)
+{
+  M.apply_block(R, Z, nrhs);
 }
 
 } // namespace spmv

@@ -1670,6 +1670,52 @@ int spmvh_pcg_block(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
   });
 }
 
+int spmvh_pcg_block_amg_check_arguments(int nrhs, int kmax, int has_dinv,
+                                        int has_sgs, int has_amg,
+                                        int64_t sgs_rows,
+                                        int64_t sgs_negative_pivots,
+                                        int64_t amg_rows, int64_t rows,
+                                        const double* B, const double* X,
+                                        const double* dinv)
+{
+  return guarded([&] {
+    pcg_block_check_rules(nrhs, kmax, has_dinv != 0, has_sgs != 0, has_amg != 0,
+                          sgs_rows, sgs_negative_pivots, amg_rows, rows, B, X,
+                          dinv);
+  });
+}
+
+int spmvh_amg_apply_block_check_arguments(int nrhs, int64_t rows,
+                                          const double* R, const double* Z)
+{
+  return guarded([&] { amg_apply_block_check_rules(nrhs, rows, R, Z); });
+}
+
+int spmvh_pcg_block_amg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                        const double* B, double* X, int nrhs, spmvh_amg* M,
+                        int kmax, double rtol, int* max_its, int* iterations,
+                        double* rnorm_history, spmvh_pcg_block_workspace* ws,
+                        int flags, double* spmv_ms_total, int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && max_its && iterations, "NULL argument");
+    std::vector<int> its;
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff)
+      opt.poll_every = (flags >> 8) & 0xff;
+    CgStats st;
+    BlockPreconditioner pre;
+    pre.amg = M ? M->M.get() : nullptr;
+    *max_its = pcg_block(*comm->comm, *exec->hip, *A->A, B, X, nrhs, pre, kmax,
+                         rtol, &its, rnorm_history ? &hist : nullptr, &opt, &st,
+                         ws ? ws->ws.get() : nullptr);
+    std::copy(its.begin(), its.end(), iterations);
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
+  });
+}
+
 // ---- Aggregation multigrid ---------------------------------------------------------------
 int spmvh_amg_check_options(double theta, int max_levels,
                             int64_t min_coarse_rows, int smooth_degree,
@@ -1843,6 +1889,23 @@ int spmvh_amg_apply(spmvh_exec* exec, spmvh_amg* M, const double* r, double* z)
   return guarded([&] {
     require(exec && M, "NULL argument");
     amg_apply(*exec->hip, *M->M, r, z);
+  });
+}
+
+int spmvh_amg_apply_block(spmvh_exec* exec, spmvh_amg* M, const double* R,
+                          double* Z, int nrhs)
+{
+  return guarded([&] {
+    require(exec && M, "NULL argument");
+    amg_apply_block(*exec->hip, *M->M, R, Z, nrhs);
+  });
+}
+
+int spmvh_amg_release_block_scratch(spmvh_amg* M)
+{
+  return guarded([&] {
+    require(M, "NULL argument");
+    M->M->release_block_scratch();
   });
 }
 

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <initializer_list>
+#include <memory>
 #include <vector>
 
 #include "comm.h"
@@ -698,13 +699,17 @@ int pcg_sgs(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
 void sgs_apply_block(HipExecutor& exec, const SgsPreconditioner& M,
                      const double* R, double* Z, int nrhs);
 
-// The preconditioner of pcg_block(): exactly one of the two is set.
+class AmgPreconditioner;
+
+// The preconditioner of pcg_block(): exactly one of the three is set.
 struct BlockPreconditioner {
   // a positive DEVICE vector of rows doubles (any alignment), shared by all
   // columns: z(i, c) = dinv[i] * r(i, c)
   const double* dinv = nullptr;
   // Z = sgs_apply_block(*sgs, R): an SgsPreconditioner or an Ilu0Preconditioner
   const SgsPreconditioner* sgs = nullptr;
+  // Z = amg_apply_block(*amg, R): one V-cycle per column (see below)
+  const AmgPreconditioner* amg = nullptr;
 };
 
 // Work vectors + device scalars of pcg_block(), kept across calls like
@@ -733,6 +738,9 @@ public:
   double* p = nullptr; // n_cap: padded, the ghost tail is zeroed by every solve
   // flags: {all_done, done[], kstop[]} (spmv_hip.h); timing_ev: 2 events per
   // iteration
+  // nrhs == 1 with an AmgPreconditioner: the solve IS pcg_amg, on this
+  // workspace of its own (made on first use, released with the rest)
+  std::unique_ptr<SgsWorkspace> single;
 };
 
 // Preconditioned CG for several right-hand sides: pcg_sgs()'s recurrence with
@@ -760,14 +768,24 @@ public:
 //
 // With M.dinv, Z = dinv * R is formed by the kernel that leaves the r.z
 // partials; with M.sgs the 2C - 1 block sweeps run instead (they may go on
-// writing a stopped column's Z: nothing reads it).  Per iteration beside the
-// mult_block: 3 streaming launches and 2 reducers (+ the sweeps).
+// writing a stopped column's Z: nothing reads it); with M.amg one
+// amg_apply_block into Z, then the same r.z launch (the cycle runs on the
+// object's own scratch and goes on for a stopped column: nothing reads it).
+// Per iteration beside the mult_block: 3 streaming launches and 2 reducers (+
+// the sweeps or the cycle).  With several ranks the cycle is block-Jacobi over
+// the ranks, no halo exchange, as for pcg_amg().  A block of ONE column with
+// M.amg is pcg_amg() itself (as amg_apply_block with nrhs == 1 is amg_apply):
+// after the argument rules the call is handed to it, on a workspace kept inside
+// the PcgBlockWorkspace, so k, the history and x have pcg_amg's bits; the
+// history is laid out as for any block (kmax + 1 entries, -1.0 beyond k).
 //
 // The arguments are checked before anything touches a device
 // (pcg_block_check_rules of solver_args.h; std::runtime_error): "nrhs", "kmax",
-// "preconditioner" (both or neither of dinv and sgs), "rows" (sgs->rows()),
-// "pivot" (an Ilu0Preconditioner with negative_pivots() > 0), "overlaps" (X
-// with B or dinv).  The executor's stream is restored on every exit path.
+// "preconditioner" (not exactly one of dinv, sgs and amg), "rows" (sgs->rows()
+// or amg->rows(0)), "pivot" (an Ilu0Preconditioner with negative_pivots() > 0),
+// "overlaps" (X with B or dinv).  An AmgPreconditioner whose last refresh
+// failed throws as amg_apply does.  The executor's stream is restored on every
+// exit path.
 // options: poll_every and time_spmv apply (one timed mult_block per
 // iteration); consumer_reductions, defer_x and mixed are IGNORED, as in
 // cg_block().
@@ -902,9 +920,16 @@ public:
 
   // z = M^-1 r (amg_apply)
   void apply(const double* r, double* z) const;
+  // Z = M^-1 R for nrhs interleaved vectors (amg_apply_block)
+  void apply_block(const double* R, double* Z, int nrhs) const;
+  // frees the block scratch of apply_block (it waits for the device); the next
+  // block application allocates it again.  A no-op when there is none.
+  void release_block_scratch();
 
 private:
   struct Level;
+  void ensure_block_scratch(int nrhs) const;
+  void free_block_scratch() const;
   void numeric(const Matrix<double>& A, bool build);
   void level_numbers(Level& L);
   void check_usable() const;
@@ -923,6 +948,12 @@ private:
   bool _symmetric = false, _usable = false;
   int64_t _num_values = 0;
   double _symbolic_ms = 0, _numeric_ms = 0;
+  // apply_block: the width the levels' block vectors hold (0: none), the width
+  // of the last application (the ghost tail of level 0's z is zeroed for it),
+  // and the columns of level 0's per-column product (see amg_apply_block)
+  mutable int _block_cap = 0, _block_last = 0;
+  mutable double* _block_cols = nullptr;
+  mutable int64_t _block_cols_elems = 0;
 };
 
 // z = M^-1 r.  `r`, `z`: DEVICE vectors of rows() doubles, any alignment, not
@@ -930,6 +961,47 @@ private:
 // does not wait.  Not reentrant (see above).
 void amg_apply(HipExecutor& exec, const AmgPreconditioner& M, const double* r,
                double* z);
+
+// Z = M^-1 R for nrhs INTERLEAVED vectors, the layout of Matrix::mult_block:
+// element (i, c) at R[i * nrhs + c] and Z[i * nrhs + c], DEVICE blocks of
+// M.rows(0) * nrhs doubles, 1 <= nrhs <= 8 ("nrhs"), any alignment, Z not
+// overlapping R ("overlaps").  Runs on the executor's current stream; the host
+// does not wait; R is unchanged.  Not reentrant per object, like amg_apply; an
+// object whose last refresh failed throws as amg_apply does.
+//
+// Column c of Z has the bits of amg_apply on column c of R -- for every nrhs,
+// every alignment, both storages and every AmgOptions, whatever the other
+// columns hold (NaN and Inf included): column c depends on M, column c of R,
+// nrhs and c alone.  nrhs == 1 IS amg_apply.
+//
+// The cycle is amg_apply's with every vector a block: the block kernels of
+// hip/spmv_amg_block.hip (the element arithmetic of hip/amg_elem.h, shared
+// with the single-vector kernels; dinv, the aggregates and the member lists
+// read once for all columns) and one CSRMatrix::mult_block per product, which
+// streams the level's matrix once for all columns.  mult_block's columns have
+// mult's bits for every plan form but one: a level whose plan reports algo ==
+// SPMV_HIP_ALGO_VECTOR adds a row in the sub-wavefront kernel's pairwise order,
+// the native multi-vector kernel left to right.  Such a level takes the plan's
+// own single-vector launch per column instead: the object's coarse blocks get
+// the plan key "mv_native" = 0 at the first block application (mult_block then
+// de-interleaves by itself; mult is not affected); level 0 is the CALLER'S
+// matrix, no key of its plan is ever changed: its block is de-interleaved here
+// (spmv_hip_deinterleave_f64), multiplied column by column and interleaved back.
+//
+// The fused tail (set_tail_rows) is a single-vector kernel and is NOT used by
+// the block path: the block cycle runs those levels with the block kernels,
+// launch by launch.  The tail has the bits of the separate launches, so the
+// criterion above holds with a tail set, and tail_levels() does not change.  A
+// block tail kernel does not exist.
+//
+// Scratch.  Per level r, w, dd of rows * nrhs and z of cols * nrhs doubles
+// (ghost tail zero); d and dinv are shared with amg_apply.  Allocated by the
+// first block application, regrown (it waits for the device) for a larger
+// nrhs, reused for a smaller one, freed with the object or by
+// release_block_scratch(); counted in plan_bytes() while it exists.  An R that
+// is not 16-byte aligned is copied into level 0's block r first.
+void amg_apply_block(HipExecutor& exec, const AmgPreconditioner& M,
+                     const double* R, double* Z, int nrhs);
 
 // pcg_amg's workspace: the vectors and device scalars of pcg_sgs
 using AmgPcgWorkspace = SgsWorkspace;

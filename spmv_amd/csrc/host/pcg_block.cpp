@@ -29,8 +29,8 @@ void sgs_apply_block(HipExecutor& exec, const SgsPreconditioner& M,
 //     mult_block: local block [wait halo event] remote block
 //     block dot partials of p.Ap ; reducer -> pAp[k][0:nrhs] ; all-reduce of nrhs
 //     r -= alpha_c Ap with the r.r partials
-//     Z = M^-1 R: the 2C - 1 block sweeps and the r.z partials, or (dinv) both
-//       in one kernel
+//     Z = M^-1 R: the 2C - 1 block sweeps or the block V-cycle and the r.z
+//       partials, or (dinv) both in one kernel
 //     reducer -> {rz[k], rr[k]}[0:nrhs] ; all-reduce of 2 nrhs
 //     x += alpha_c p ; stop test ; p = beta_c p + z
 // ---------------------------------------------------------------------------
@@ -41,6 +41,7 @@ void PcgBlockWorkspace::release()
   release_common();
   spmv_hip_pcgb_ws_destroy(ws);
   ws = nullptr;
+  single.reset();
   free_vectors({&r, &Ap, &z, &x, &p});
   kmax_cap = -1;
   nrhs_cap = 0;
@@ -78,9 +79,25 @@ int pcg_block(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   // (rows() and negative_pivots() are host fields of the object)
   const int64_t rows = A.row_map()->local_size();
   pcg_block_check_rules(nrhs, kmax, M.dinv != nullptr, M.sgs != nullptr,
-                        M.sgs ? M.sgs->rows() : 0,
-                        M.sgs ? M.sgs->negative_pivots() : 0, rows, B, X,
-                        M.dinv);
+                        M.amg != nullptr, M.sgs ? M.sgs->rows() : 0,
+                        M.sgs ? M.sgs->negative_pivots() : 0,
+                        M.amg ? M.amg->rows(0) : 0, rows, B, X, M.dinv);
+  if (M.amg && nrhs == 1) { // a block of one column: pcg_amg itself
+    PcgBlockWorkspace own1(exec);
+    PcgBlockWorkspace& w1 = workspace ? *workspace : own1;
+    if (!w1.single)
+      w1.single = std::make_unique<SgsWorkspace>(exec);
+    std::vector<double> hist;
+    const int k = pcg_amg(comm, exec, A, *M.amg, B, X, kmax, rtol, &hist,
+                          options, stats, w1.single.get());
+    if (iterations)
+      iterations->assign(1, k);
+    if (rnorm_history) {
+      rnorm_history->assign((size_t)kmax + 1, -1.0);
+      std::copy(hist.begin(), hist.end(), rnorm_history->begin());
+    }
+    return k;
+  }
   const Dims dims = check_problem("pcg_block", A, kmax);
   const int64_t M_rows = dims.M;
   const int64_t m_elems = M_rows * nrhs, n_elems = dims.N_padded * nrhs;
@@ -111,6 +128,8 @@ int pcg_block(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
       throw_on_error(spmv_hip_mcgs_apply_block_f64(ctx, plan, w.ws, w.r, w.z,
                                                    nrhs, nullptr),
                      "spmv_hip_mcgs_apply_block_f64");
+    else if (M.amg) // (on the object's own scratch, stopped columns included)
+      amg_apply_block(exec, *M.amg, w.r, w.z, nrhs);
     throw_on_error(spmv_hip_pcgb_dot_rz_f64(ctx, w.ws, M_rows, M.dinv, w.r, w.z,
                                             nullptr),
                    "spmv_hip_pcgb_dot_rz_f64");

@@ -66,8 +66,40 @@ void gmres_check_rules(int restart, int kmax, bool has_dinv, int cheb_degree,
                              + std::to_string(rows));
 }
 
+namespace
+{
+// u[0:n) and v[0:m) doubles share a byte
+bool doubles_overlap(const double* u, int64_t n, const double* v, int64_t m)
+{
+  const std::uintptr_t ub = reinterpret_cast<std::uintptr_t>(u);
+  const std::uintptr_t vb = reinterpret_cast<std::uintptr_t>(v);
+  return n > 0 && m > 0 && ub < vb + (std::uintptr_t)m * sizeof(double)
+         && vb < ub + (std::uintptr_t)n * sizeof(double);
+}
+} // namespace
+
 void pcg_block_check_rules(int nrhs, int kmax, bool has_dinv, bool has_sgs,
                            int64_t sgs_rows, int64_t sgs_negative_pivots,
+                           int64_t rows, const double* B, const double* X,
+                           const double* dinv)
+{
+  pcg_block_check_rules(nrhs, kmax, has_dinv, has_sgs, false, sgs_rows,
+                        sgs_negative_pivots, 0, rows, B, X, dinv);
+}
+
+void amg_apply_block_check_rules(int nrhs, int64_t rows, const double* R,
+                                 const double* Z)
+{
+  if (nrhs < 1 || nrhs > 8)
+    throw std::runtime_error(
+        "spmv::amg_apply_block - Error: nrhs must be in 1..8");
+  if (doubles_overlap(Z, rows * nrhs, R, rows * nrhs))
+    throw std::runtime_error("amg_apply_block: Z overlaps R");
+}
+
+void pcg_block_check_rules(int nrhs, int kmax, bool has_dinv, bool has_sgs,
+                           bool has_amg, int64_t sgs_rows,
+                           int64_t sgs_negative_pivots, int64_t amg_rows,
                            int64_t rows, const double* B, const double* X,
                            const double* dinv)
 {
@@ -75,31 +107,27 @@ void pcg_block_check_rules(int nrhs, int kmax, bool has_dinv, bool has_sgs,
     throw std::runtime_error("spmv::pcg_block - Error: nrhs must be in 1..8");
   if (kmax < 0)
     throw std::runtime_error("spmv::pcg_block - Error: kmax < 0");
-  if (has_dinv == has_sgs)
+  if ((int)has_dinv + (int)has_sgs + (int)has_amg != 1)
     throw std::runtime_error(
-        "spmv::pcg_block - Error: exactly one preconditioner (dinv or sgs)");
-  if (has_sgs && sgs_rows != rows)
+        has_amg ? "spmv::pcg_block - Error: exactly one preconditioner (dinv, "
+                  "sgs or amg)"
+                : "spmv::pcg_block - Error: exactly one preconditioner (dinv or "
+                  "sgs)");
+  if ((has_sgs && sgs_rows != rows) || (has_amg && amg_rows != rows))
     throw std::runtime_error(
         "spmv::pcg_block - Error: the preconditioner was built for "
-        + std::to_string(sgs_rows) + " rows, the matrix has "
-        + std::to_string(rows));
+        + std::to_string(has_sgs ? sgs_rows : amg_rows)
+        + " rows, the matrix has " + std::to_string(rows));
   if (has_sgs && sgs_negative_pivots > 0)
     throw std::runtime_error(
         "spmv::pcg_block - Error: the preconditioner has "
         + std::to_string(sgs_negative_pivots)
         + " negative pivot(s): it is not positive definite");
-  // u[0:n) and v[0:m) doubles share a byte
-  auto overlap = [](const double* u, int64_t n, const double* v, int64_t m) {
-    const std::uintptr_t ub = reinterpret_cast<std::uintptr_t>(u);
-    const std::uintptr_t vb = reinterpret_cast<std::uintptr_t>(v);
-    return n > 0 && m > 0 && ub < vb + (std::uintptr_t)m * sizeof(double)
-           && vb < ub + (std::uintptr_t)n * sizeof(double);
-  };
   const int64_t elems = rows * nrhs;
-  if (overlap(X, elems, B, elems))
+  if (doubles_overlap(X, elems, B, elems))
     throw std::runtime_error(
         "pcg_block: X overlaps B (X is updated in place)");
-  if (has_dinv && overlap(X, elems, dinv, rows))
+  if (has_dinv && doubles_overlap(X, elems, dinv, rows))
     throw std::runtime_error(
         "pcg_block: X overlaps dinv (X is updated in place)");
 }

@@ -35,6 +35,20 @@ void pcg_block_check_rules(int nrhs, int kmax, bool has_dinv, bool has_sgs,
                            int64_t rows, const double* B, const double* X,
                            const double* dinv);
 
+// ... with the third preconditioner, an AmgPreconditioner of amg_rows rows:
+// "preconditioner" unless exactly one of dinv, sgs and amg is set, "rows" also
+// for amg_rows != rows; the other rules and their order as above.
+void pcg_block_check_rules(int nrhs, int kmax, bool has_dinv, bool has_sgs,
+                           bool has_amg, int64_t sgs_rows,
+                           int64_t sgs_negative_pivots, int64_t amg_rows,
+                           int64_t rows, const double* B, const double* X,
+                           const double* dinv);
+// The argument rules of amg_apply_block() (std::runtime_error): nrhs outside
+// 1..8 ("nrhs"), Z sharing a byte with R, rows * nrhs doubles each
+// ("overlaps").  The pointers are compared, never dereferenced.
+void amg_apply_block_check_rules(int nrhs, int64_t rows, const double* R,
+                                 const double* Z);
+
 // The rules of AmgOptions (cg.h); std::runtime_error names the field: theta in
 // [0, 1], max_levels 1..16, min_coarse_rows >= 1, smooth_degree and
 // coarse_degree 1..kChebyshevMaxDegree, eig_ratio > 1, 1 <= coarse_scale < 2.

@@ -186,6 +186,15 @@ _PROTOS = {
     "spmvh_amg_aggregates": [vp, C.c_int, vp],
     "spmvh_amg_level_matrix": [vp, C.c_int, vp, vp, vp],
     "spmvh_amg_apply": [vp, vp, vp, vp],
+    "spmvh_amg_apply_block": [vp, vp, vp, vp, C.c_int],
+    "spmvh_amg_apply_block_check_arguments": [C.c_int, i64, vp, vp],
+    "spmvh_amg_release_block_scratch": [vp],
+    "spmvh_pcg_block_amg": [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, f64,
+                            PTR(C.c_int), vp, vp, vp, C.c_int, PTR(f64),
+                            PTR(C.c_int)],
+    "spmvh_pcg_block_amg_check_arguments": [C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, i64, i64, i64, i64, vp, vp,
+                                            vp],
     "spmvh_amg_check_tail_rows": [i64],
     "spmvh_amg_set_tail_rows": [vp, i64],
     "spmvh_amg_tail_levels": [vp, PTR(C.c_int)],
@@ -1219,21 +1228,32 @@ class PcgBlockWorkspace(_Workspace):
 
 
 def pcg_block(comm, exec_, A, b_ptr, x_ptr, nrhs, kmax, rtol, dinv=None,
-              sgs=None, workspace=None, time_spmv=False, poll_every=0):
+              sgs=None, workspace=None, time_spmv=False, poll_every=0,
+              amg=None):
     """spmv::pcg_block: preconditioned CG on A X = B for nrhs interleaved
-    right-hand sides; exactly one of dinv (device pointer, rows doubles) and
-    sgs (an SgsPreconditioner or Ilu0Preconditioner) -> (iterations[nrhs],
-    history[nrhs, kmax + 1], stats), as cg_block returns them."""
+    right-hand sides; exactly one of dinv (device pointer, rows doubles), sgs
+    (an SgsPreconditioner or Ilu0Preconditioner) and amg (an
+    AmgPreconditioner) -> (iterations[nrhs], history[nrhs, kmax + 1], stats),
+    as cg_block returns them."""
     nrhs, kmax = int(nrhs), int(kmax)
     kmx, n = C.c_int(), C.c_int()
     ms = f64()
     its = np.zeros(max(nrhs, 1), np.int32)
     hist = np.full((max(nrhs, 1), max(kmax, 0) + 1), -1.0)
-    call("spmvh_pcg_block", comm.h, exec_.h, A.h, b_ptr, x_ptr, nrhs, dinv,
-         sgs.h if sgs is not None else None, kmax, float(rtol), C.byref(kmx),
-         _np_ptr(its), _np_ptr(hist), workspace.h if workspace else None,
-         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
-         C.byref(n))
+    tail = (kmax, float(rtol), C.byref(kmx), _np_ptr(its), _np_ptr(hist),
+            workspace.h if workspace else None,
+            int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8),
+            C.byref(ms), C.byref(n))
+    if amg is not None and dinv is None and sgs is None:
+        call("spmvh_pcg_block_amg", comm.h, exec_.h, A.h, b_ptr, x_ptr, nrhs,
+             amg.h, *tail)
+    else:
+        if amg is not None:  # more than one: the rule, without a device
+            call("spmvh_pcg_block_amg_check_arguments", nrhs, kmax,
+                 int(dinv is not None), int(sgs is not None), 1, 0, 0, 0, 0,
+                 None, None, None)
+        call("spmvh_pcg_block", comm.h, exec_.h, A.h, b_ptr, x_ptr, nrhs, dinv,
+             sgs.h if sgs is not None else None, *tail)
     return its, hist, dict(max_iterations=kmx.value, spmv_ms_total=ms.value,
                            spmv_launches=n.value)
 
@@ -1337,6 +1357,11 @@ class AmgPreconditioner:
         Same bits.  Between applications only; it waits for the device."""
         call("spmvh_amg_set_tail_rows", self.h, int(max_rows))
 
+    def release_block_scratch(self):
+        """Frees the block scratch of amg_apply_block (it waits for the
+        device); the next block application allocates it again."""
+        call("spmvh_amg_release_block_scratch", self.h)
+
     def tail_levels(self):
         """levels the fused launch runs; 0 = no tail"""
         n = C.c_int()
@@ -1401,6 +1426,13 @@ def amg_apply(exec_, M, r_ptr, z_ptr):
     """spmv::amg_apply: z = M^-1 r on the executor's current stream; the host
     does not wait."""
     call("spmvh_amg_apply", exec_.h, M.h, r_ptr, z_ptr)
+
+
+def amg_apply_block(exec_, M, r_ptr, z_ptr, nrhs):
+    """spmv::amg_apply_block: Z = M^-1 R for nrhs interleaved vectors (element
+    (i, c) at R[i * nrhs + c]) on the executor's current stream.  Column c has
+    the bits of amg_apply on column c, whatever the other columns hold."""
+    call("spmvh_amg_apply_block", exec_.h, M.h, r_ptr, z_ptr, int(nrhs))
 
 
 AmgPcgWorkspace = SgsWorkspace
