@@ -1586,6 +1586,93 @@ int spmv_hip_gmres_residual_f64(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws,
 int spmv_hip_gmres_diag_f64(spmv_hip_ctx* ctx, int64_t n, const double* dinv,
                             const double* v, double* z, void* stream);
 
+/* ---- Preconditioned MINRES (spmv::minres, host/cg.h) -------------------------
+ * Vectors: n doubles, 16-byte aligned.  Every product, sum, difference,
+ * quotient and square root is one rounding.  One iteration (the recurrence is
+ * spelled out in host/cg.h):
+ *   Av = A v with the partials of alfa = v.Av in PART_ALFA (the SpMV's fused dot
+ *     or spmv_hip_dot_partial_f64)
+ *   [several ranks: reduce(ALFA) ; all-reduce of the slot]
+ *   update_r ; [M^-1 and spmv_hip_dot_partial_f64 into PART_RY] ; reduce(RY) ;
+ *   [all-reduce of the slot] ; step ; update_xwv(k)
+ * and once in front: init ; reduce(RY) ; start ; update_xwv(0).
+ * Device state of a workspace: the 16 doubles of SPMV_HIP_MINRES_SCALARS, in
+ * this order: rtol, alfa, ry, beta, oldb, dbar, epsln, phibar, cs, sn, bob
+ * (= beta / oldb), oldeps, delta, inv_gamma, phi, inv_beta; the words done,
+ * kstop, status (0 converged / kmax / running, 1 beta == 0, 2 ry < 0, 3 gamma
+ * == 0), k (steps completed), kmax; hist[0..kmax]; two partial arrays of
+ * spmv_hip_dot_partials_len() doubles.
+ * `done` is raised by start or step; after it init, reduce, update_r, start
+ * and step return at once.  update_xwv(k) runs only while the state's k equals
+ * its own: the step that stopped with a new iterate still gets its x, once;
+ * nothing afterwards writes x, the history or k. */
+typedef struct spmv_hip_minres_ws spmv_hip_minres_ws; /* minres() scalars */
+enum {
+  SPMV_HIP_MINRES_ALFA = 0,      /* 1: v.Av where a reducer (or update_r) put it */
+  SPMV_HIP_MINRES_RY = 1,        /* 1: r2.y where the reducer put it             */
+  SPMV_HIP_MINRES_HIST = 2,      /* kmax + 1                                     */
+  SPMV_HIP_MINRES_PART_ALFA = 3, /* dot_partials_len                             */
+  SPMV_HIP_MINRES_PART_RY = 4,   /* dot_partials_len                             */
+  SPMV_HIP_MINRES_SCALARS = 5    /* 16: see above (tests read and install them)  */
+};
+int spmv_hip_minres_ws_create(spmv_hip_ctx* ctx, int kmax,
+                              spmv_hip_minres_ws** ws);
+int spmv_hip_minres_ws_destroy(spmv_hip_minres_ws* ws);
+/* kmax <= the capacity; zeroes the scalars and the history */
+int spmv_hip_minres_ws_reset(spmv_hip_minres_ws* ws, double rtol, int kmax,
+                             void* stream);
+int spmv_hip_minres_ws_capacity(const spmv_hip_minres_ws* ws, int* kmax);
+/* device address and length of one array of the state (the slots of ALFA and
+ * RY for the all-reduce, the partial arrays for the dot kernels) */
+int spmv_hip_minres_ws_array(spmv_hip_minres_ws* ws, int which, double** p,
+                             int64_t* count);
+/* copies {done, kstop, status} (3 x int32) and hist[0..capacity] to the host
+ * (async; either may be NULL; host_hist_len >= capacity + 1 or nothing is
+ * enqueued) */
+int spmv_hip_minres_ws_read_async(spmv_hip_minres_ws* ws,
+                                  int32_t* host_done_kstop_status,
+                                  double* host_hist, size_t host_hist_len,
+                                  void* stream);
+/* TEST HOOKS: install k and done (kstop = k when done; status 0; waits), read
+ * {done, kstop, status, k, kmax} */
+int spmv_hip_minres_ws_set_state(spmv_hip_minres_ws* ws, int k, int done,
+                                 void* stream);
+int spmv_hip_minres_ws_get_state(spmv_hip_minres_ws* ws, int32_t* host_words5,
+                                 void* stream);
+/* y = dinv * r2 ; partials of r2.y into PART_RY (dinv == NULL: the partials of
+ * r2.r2, y is not written and may be NULL) */
+int spmv_hip_minres_init_f64(spmv_hip_ctx* ctx, spmv_hip_minres_ws* ws,
+                             int64_t n, const double* r2, const double* dinv,
+                             double* y, void* stream);
+/* PART_ALFA (+ partials2, the remote block's share, may be NULL) -> ALFA, or
+ * PART_RY -> RY (partials2 must be NULL); one workgroup */
+int spmv_hip_minres_reduce(spmv_hip_ctx* ctx, spmv_hip_minres_ws* ws, int which,
+                           const double* partials2, void* stream);
+/* one wave: beta1 = sqrt(ry), hist[0], the state in front of the first step;
+ * ry < 0: done, status 2; ry == 0: done, status 0 */
+int spmv_hip_minres_start(spmv_hip_ctx* ctx, spmv_hip_minres_ws* ws,
+                          void* stream);
+/* t = (Av - bob * r1) - (alfa / beta) * r2, written over r1 (state k == 0: t =
+ * Av - (alfa / beta) * r2, r1 is not read).  alfa: the slot (reduced != 0), or
+ * PART_ALFA (+ partials2) added by every workgroup in the reducer's order and
+ * left in the slot.  dinv != NULL: y = dinv * t.  want_dot: the partials of
+ * t.y (dinv == NULL: of t.t) into PART_RY.  r1 must differ from r2 and Av. */
+int spmv_hip_minres_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_minres_ws* ws,
+                                 int64_t n, const double* Av, double* r1,
+                                 const double* r2, const double* dinv, double* y,
+                                 int reduced, const double* partials2,
+                                 int want_dot, void* stream);
+/* one wave: the scalar part of an iteration from the slots ALFA and RY */
+int spmv_hip_minres_step(spmv_hip_ctx* ctx, spmv_hip_minres_ws* ws,
+                         void* stream);
+/* k >= 1, state k == k: w = ((v - oldeps * w1) - delta * w2) * inv_gamma,
+ * written over w1 ; x = x + phi * w ; not done: v = y * inv_beta.
+ * k == 0, state k == 0, not done: v = y * inv_beta alone (w1, w2, x unused). */
+int spmv_hip_minres_update_xwv_f64(spmv_hip_ctx* ctx, spmv_hip_minres_ws* ws,
+                                   int k, int64_t n, double* v, double* w1,
+                                   const double* w2, double* x, const double* y,
+                                   void* stream);
+
 /* ---- 3-D Poisson generator (not in the reference)
  * 7-point stencil on an n^3 grid, natural ordering, diag 6, off-diag -1.
  * Generates, directly in device memory, the CSR block of global rows

@@ -699,6 +699,34 @@ int spmvh_gmres_amg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                     spmvh_gmres_workspace* ws, int flags, double* spmv_ms_total,
                     int* spmv_launches, spmvh_amg* amg);
 
+/* ---- Preconditioned MINRES (spmv::minres, host/cg.h; not in the reference) ---
+ * spmvh_minres: MINRES from x0 = 0 for a symmetric matrix that need not be
+ * definite.  At most one of dinv (a positive device vector), sgs (SGS, or
+ * ILU(0) without negative pivots) and amg may be given; all NULL: no
+ * preconditioner.  rnorm_history (may be NULL): kmax + 1 doubles, receives
+ * hist[0..*num_its], the residual in the M^-1-norm.  *status (may be NULL): 0
+ * converged or kmax reached, 1 the Lanczos process ended (x is exact), 2 the
+ * preconditioner is not positive definite (r.M^-1 r < 0), 3 a singular
+ * direction.  ws: a reusable spmv::MinresWorkspace (may be NULL).  flags: bit 0
+ * -> CgOptions::time_spmv, bits 8-15 -> poll_every (0 = default).
+ * spmvh_minres_check_rules: minres_check_rules of solver_args.h alone (no
+ * device; the pointers are compared, never dereferenced). */
+typedef struct spmvh_minres_workspace spmvh_minres_workspace;
+int spmvh_minres_workspace_create(spmvh_exec* exec, spmvh_minres_workspace** ws);
+int spmvh_minres_workspace_destroy(spmvh_minres_workspace* ws);
+int spmvh_minres_workspace_reserve_timing(spmvh_minres_workspace* ws,
+                                          int iterations);
+int spmvh_minres_check_rules(int kmax, int has_dinv, int has_sgs, int has_amg,
+                             int64_t sgs_rows, int64_t sgs_negative_pivots,
+                             int64_t amg_rows, int64_t rows, const double* b,
+                             const double* x, const double* dinv);
+int spmvh_minres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                 const double* b, double* x, const double* dinv,
+                 spmvh_sgs* sgs, spmvh_amg* amg, int kmax, double rtol,
+                 int* num_its, int* status, double* rnorm_history,
+                 spmvh_minres_workspace* ws, int flags, double* spmv_ms_total,
+                 int* spmv_launches);
+
 #ifdef __cplusplus
 }
 #endif

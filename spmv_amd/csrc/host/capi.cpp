@@ -56,6 +56,7 @@ struct spmvh_bicgstab_workspace : WorkspaceHandle<BicgstabWorkspace> {};
 struct spmvh_sgs_workspace : WorkspaceHandle<SgsWorkspace> {};
 struct spmvh_pcg_block_workspace : WorkspaceHandle<PcgBlockWorkspace> {};
 struct spmvh_gmres_workspace : WorkspaceHandle<GmresWorkspace> {};
+struct spmvh_minres_workspace : WorkspaceHandle<MinresWorkspace> {};
 struct spmvh_sgs_build {
   SgsHostPlan plan;
 };
@@ -2041,6 +2042,64 @@ int spmvh_gmres_amg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     *num_its = gmres(*comm->comm, *exec->hip, *A->A, b, x, &pre, restart, kmax,
                      rtol, rnorm_history ? &hist : nullptr, &opt, &st,
                      ws ? ws->ws.get() : nullptr, &how);
+    if (status)
+      *status = how;
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
+  });
+}
+
+// ---- MINRES -----------------------------------------------------------------------------
+int spmvh_minres_workspace_create(spmvh_exec* exec, spmvh_minres_workspace** ws)
+{
+  return workspace_create<MinresWorkspace>(exec, ws);
+}
+
+int spmvh_minres_workspace_destroy(spmvh_minres_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_minres_workspace_reserve_timing(spmvh_minres_workspace* ws,
+                                          int iterations)
+{
+  return workspace_reserve_timing(ws, iterations);
+}
+
+int spmvh_minres_check_rules(int kmax, int has_dinv, int has_sgs, int has_amg,
+                             int64_t sgs_rows, int64_t sgs_negative_pivots,
+                             int64_t amg_rows, int64_t rows, const double* b,
+                             const double* x, const double* dinv)
+{
+  return guarded([&] {
+    minres_check_rules(kmax, has_dinv != 0, has_sgs != 0, has_amg != 0,
+                       sgs_rows, sgs_negative_pivots, amg_rows, rows, b, x,
+                       dinv);
+  });
+}
+
+int spmvh_minres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                 const double* b, double* x, const double* dinv,
+                 spmvh_sgs* sgs, spmvh_amg* amg, int kmax, double rtol,
+                 int* num_its, int* status, double* rnorm_history,
+                 spmvh_minres_workspace* ws, int flags, double* spmv_ms_total,
+                 int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && num_its, "NULL argument");
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff) // bits 8-15: CgOptions::poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    MinresPreconditioner pre;
+    pre.dinv = dinv;
+    pre.sgs = sgs ? sgs->M.get() : nullptr;
+    pre.amg = amg ? amg->M.get() : nullptr;
+    CgStats st;
+    int how = 0;
+    *num_its = minres(*comm->comm, *exec->hip, *A->A, b, x, &pre, kmax, rtol,
+                      rnorm_history ? &hist : nullptr, &opt, &st,
+                      ws ? ws->ws.get() : nullptr, &how);
     if (status)
       *status = how;
     copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);

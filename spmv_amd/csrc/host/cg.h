@@ -19,6 +19,7 @@ struct spmv_hip_pcg_ws;
 struct spmv_hip_pcgb_ws;
 struct spmv_hip_bicg_ws;
 struct spmv_hip_gmres_ws;
+struct spmv_hip_minres_ws;
 struct spmv_hip_mcgs_plan;
 struct spmv_hip_ilu0_plan;
 struct spmv_hip_amg_tail;
@@ -1236,5 +1237,130 @@ int gmres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
           int kmax, double rtol, std::vector<double>* rnorm_history = nullptr,
           const CgOptions* options = nullptr, CgStats* stats = nullptr,
           GmresWorkspace* workspace = nullptr, int* status = nullptr);
+
+// ---- Preconditioned MINRES ----------------------------------------------------
+
+// The preconditioner of minres(): symmetric positive definite.  All defaults:
+// none.  At most one may be set ("preconditioner").
+struct MinresPreconditioner {
+  // a POSITIVE device vector, z = dinv*r (Jacobi: 1 / |diag|)
+  const double* dinv = nullptr;
+  // z = sgs_apply(*sgs, r): SGS, or ILU(0) / IC(0) with negative_pivots() == 0
+  // ("pivot")
+  const SgsPreconditioner* sgs = nullptr;
+  // z = amg_apply(*amg, r)
+  const AmgPreconditioner* amg = nullptr;
+};
+
+// Work vectors + device scalars of minres(), kept across calls like
+// GmresWorkspace; it regrows itself when a call needs more rows or more
+// iterations.
+class MinresWorkspace : public SolverWorkspace
+{
+public:
+  explicit MinresWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
+  ~MinresWorkspace();
+
+  // ---- internal to minres() ----
+  // need_y: a preconditioner is set; need_x / need_dinv: the caller's x / dinv
+  // is not 16-byte aligned and lives in the workspace's copy
+  void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len,
+              bool need_y, bool need_x, bool need_dinv);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(2 * (size_t)std::max(iterations, 0));
+  }
+  void release();
+
+  spmv_hip_minres_ws* ws = nullptr;
+  int kmax_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, y_cap = -1, x_cap = -1, dinv_cap = -1;
+  // m_cap: Av; r1 and r2 rotate over ra, rb (t is written over r1); w1 and w2
+  // rotate over wa, wb (w is written over w1)
+  double *Av = nullptr, *ra = nullptr, *rb = nullptr, *wa = nullptr,
+         *wb = nullptr;
+  double* v = nullptr;    // n_cap: padded, what the SpMV reads
+  double* y = nullptr;    // y_cap: M^-1 r2 (without a preconditioner y IS r2)
+  double* x = nullptr;    // x_cap: the iterate of an unaligned x
+  double* dinv = nullptr; // dinv_cap: the copy of an unaligned dinv
+  double* dot2 = nullptr; // partials of the remote block's v.Av share
+  // flags: {done, kstop, status}; timing_ev: 2 events per iteration
+};
+
+// Preconditioned MINRES from x0 = 0 for a SYMMETRIC matrix that need not be
+// definite (a shifted operator A - sigma I, a saddle-point system), in either
+// storage, and a symmetric positive definite preconditioner M: none, dinv*
+// (elementwise), sgs_apply or amg_apply.  One SpMV, one application of M^-1 and
+// a fixed number of vector passes per iteration; the residual in the M^-1-norm
+// never grows.  Only Matrix::mult (mult_dot) is used: every plan form and halo
+// model serves.  With `.` the global dot product, every product, sum,
+// difference, quotient and square root one rounding of its own:
+//
+//   x = 0; r1 = r2 = b; y = M^-1 r2; ry = r2.y
+//   ry < 0: status 2, return 0.     beta1 = sqrt(ry); hist[0] = beta1
+//   beta1 == 0: return 0 with x = 0            (the rule of pcg / gmres)
+//   oldb = 0; beta = beta1; dbar = 0; epsln = 0; phibar = beta1; cs = -1;
+//   sn = 0; w = w2 = 0; k = 0
+//   v = y * (1.0 / beta)
+//   while k < kmax:
+//     Av   = A v                     halo update of v first; alfa = v.Av
+//     t    = (Av - (beta/oldb)*r1) - (alfa/beta)*r2
+//                                    (k == 0: t = Av - (alfa/beta)*r2)
+//     r1 = r2; r2 = t; y = M^-1 r2; ry = r2.y
+//     ry < 0: status 2; stop (x is the iterate of k)
+//     oldb = beta; beta = sqrt(ry)
+//     oldeps = epsln; delta = cs*dbar + sn*alfa; gbar = sn*dbar - cs*alfa
+//     epsln = sn*beta; dbar = -cs*beta
+//     gamma = sqrt(gbar*gbar + beta*beta)
+//     gamma == 0: status 3; stop (singular direction; x is the iterate of k)
+//     cs = gbar/gamma; sn = beta/gamma; phi = cs*phibar; phibar = sn*phibar
+//     w1 = w2; w2 = w; w = ((v - oldeps*w1) - delta*w2) * (1.0/gamma)
+//     x = x + phi*w
+//     k += 1; hist[k] = |phibar|
+//     beta == 0: status 1 (the Lanczos process ended: x is exact); stop
+//     hist[k] / hist[0] < rtol: stop
+//     v = y * (1.0 / beta)
+//
+// alfa is taken as v.(A v), BEFORE r1 is subtracted: equal in exact arithmetic
+// (v is M-orthogonal to the previous Lanczos vector), it lets the SpMV's fused
+// dot serve and makes the whole update of t one kernel.
+//
+// rnorm_history receives hist[0..k]: the residual in the M^-1-norm, sqrt(r .
+// M^-1 r).  Without a preconditioner that is the 2-norm and the histories
+// compare with cg()'s; with one they do NOT compare with pcg()'s, which are
+// 2-norms.  Returns k; `status` (optional) receives 0 (converged, or kmax
+// reached), 1, 2 or 3 as above.  A non-finite scalar takes the "go on" branch of
+// every comparison, so such a solve ends at kmax, as in gmres().
+//
+// Launches of one iteration on one rank, beside the SpMV (with its fused
+// v.Av; symmetric storage: plus one dot kernel): update_r (adds the partials of
+// alfa itself; t over r1's buffer, y = dinv*t, partials of r2.y), the reducer,
+// step (one wave: all the scalars above, the history, the stop), update_xwv (w
+// over w1's buffer, x, the next v): 4 launches and 14 vector passes with dinv
+// (update_r: Av, r1, r2, dinv in, r2, y out; update_xwv: v, w1, w2, x, y in, w,
+// x, v out), 12 without a preconditioner (y is r2 itself).  With sgs or amg the
+// application and the dot-partials kernel follow update_r.  With several ranks:
+// one reducer more and two all-reduces of 1 double (alfa, ry).
+//
+// As in gmres(): the scalars stay on the device, reductions are two-stage and
+// deterministic, the decision to stop is taken on the device and the host only
+// looks at a pinned flag every `poll_every` iterations.  After the stop every
+// kernel returns at once, so x is exactly the iterate of the returned k (the
+// SpMV and the preconditioner may still run on scratch).  `x` IS the iterate,
+// as in pcg(): zeroed at the start, updated in place, and after a throw it
+// holds whatever had been reached; an `x` or `dinv` that is not 16-byte
+// aligned goes through the workspace's copy (b is copied anyway: it is the
+// first r2).  The argument rules are minres_check_rules' (solver_args.h:
+// "kmax", "preconditioner", "rows", "pivot", "overlaps"), checked before
+// anything touches a device; the executor's stream is restored on every exit
+// path.
+//
+// options: poll_every and time_spmv apply (one timed Matrix::mult per
+//          iteration); consumer_reductions, defer_x and mixed are IGNORED.
+int minres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+           const double* b, double* x, const MinresPreconditioner* M, int kmax,
+           double rtol, std::vector<double>* rnorm_history = nullptr,
+           const CgOptions* options = nullptr, CgStats* stats = nullptr,
+           MinresWorkspace* workspace = nullptr, int* status = nullptr);
 
 } // namespace spmv

@@ -132,6 +132,32 @@ void pcg_block_check_rules(int nrhs, int kmax, bool has_dinv, bool has_sgs,
         "pcg_block: X overlaps dinv (X is updated in place)");
 }
 
+void minres_check_rules(int kmax, bool has_dinv, bool has_sgs, bool has_amg,
+                        int64_t sgs_rows, int64_t sgs_negative_pivots,
+                        int64_t amg_rows, int64_t rows, const double* b,
+                        const double* x, const double* dinv)
+{
+  if (kmax < 0)
+    throw std::runtime_error("spmv::minres - Error: kmax < 0");
+  if ((int)has_dinv + (int)has_sgs + (int)has_amg > 1)
+    throw std::runtime_error(
+        "spmv::minres - Error: one preconditioner at a time (dinv, sgs or amg)");
+  if ((has_sgs && sgs_rows != rows) || (has_amg && amg_rows != rows))
+    throw std::runtime_error(
+        "spmv::minres - Error: the preconditioner was built for "
+        + std::to_string(has_sgs ? sgs_rows : amg_rows)
+        + " rows, the matrix has " + std::to_string(rows));
+  if (has_sgs && sgs_negative_pivots > 0)
+    throw std::runtime_error(
+        "spmv::minres - Error: the preconditioner has "
+        + std::to_string(sgs_negative_pivots)
+        + " negative pivot(s): it is not positive definite");
+  if (doubles_overlap(x, rows, b, rows))
+    throw std::runtime_error("minres: x overlaps b (x is updated in place)");
+  if (has_dinv && doubles_overlap(x, rows, dinv, rows))
+    throw std::runtime_error("minres: x overlaps dinv (x is updated in place)");
+}
+
 void amg_check_tail_rows(int64_t max_rows)
 {
   if (max_rows < 0)

@@ -59,6 +59,17 @@ void amg_check_options(double theta, int max_levels, int64_t min_coarse_rows,
 // throws std::runtime_error naming "tail_rows".
 void amg_check_tail_rows(int64_t max_rows);
 
+// The argument rules of minres() (std::runtime_error), in this order: kmax < 0
+// ("kmax"), more than one of dinv, sgs and amg ("preconditioner"), an SGS /
+// ILU(0) or AMG preconditioner built for other than `rows` rows ("rows"), an
+// ILU(0) preconditioner with negative pivots ("pivot": it is not positive
+// definite), x sharing a byte with b or dinv, rows doubles each ("overlaps").
+// The pointers are compared, never dereferenced.
+void minres_check_rules(int kmax, bool has_dinv, bool has_sgs, bool has_amg,
+                        int64_t sgs_rows, int64_t sgs_negative_pivots,
+                        int64_t amg_rows, int64_t rows, const double* b,
+                        const double* x, const double* dinv);
+
 // stride of the basis vectors: N_padded rounded up to an even number, so that
 // every v_j is 16-byte aligned
 int64_t gmres_basis_stride(int64_t N_padded);

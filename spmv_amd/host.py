@@ -212,6 +212,13 @@ _PROTOS = {
     "spmvh_bicgstab_workspace_create": [vp, PTR(vp)],
     "spmvh_bicgstab_workspace_destroy": [vp],
     "spmvh_bicgstab_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_minres_workspace_create": [vp, PTR(vp)],
+    "spmvh_minres_workspace_destroy": [vp],
+    "spmvh_minres_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_minres_check_rules": [C.c_int, C.c_int, C.c_int, C.c_int, i64, i64,
+                                 i64, i64, vp, vp, vp],
+    "spmvh_minres": [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int),
+                     PTR(C.c_int), vp, vp, C.c_int, PTR(f64), PTR(C.c_int)],
     "spmvh_gmres_workspace_create": [vp, PTR(vp)],
     "spmvh_gmres_workspace_destroy": [vp],
     "spmvh_gmres_workspace_reserve_timing": [vp, C.c_int],
@@ -1519,6 +1526,48 @@ def gmres(comm, exec_, A, b_ptr, x_ptr, restart, kmax, rtol, dinv_ptr=None,
         call("spmvh_gmres", *args)
     else:
         call("spmvh_gmres_amg", *args, amg.h)
+    if stats is not None:
+        stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, hist[:k.value + 1], status.value
+
+
+class MinresWorkspace(_TimedWorkspace):
+    """spmv::MinresWorkspace: work vectors and device scalars kept across
+    minres() calls."""
+    _prefix = "minres"
+
+
+def minres_check_rules(kmax, has_dinv=False, has_sgs=False, has_amg=False,
+                       sgs_rows=0, sgs_negative_pivots=0, amg_rows=0, rows=0,
+                       b_ptr=None, x_ptr=None, dinv_ptr=None):
+    """spmv::minres_check_rules alone (no device; the pointers are compared,
+    never dereferenced); raises SpmvHostError naming the rule."""
+    call("spmvh_minres_check_rules", int(kmax), int(bool(has_dinv)),
+         int(bool(has_sgs)), int(bool(has_amg)), int(sgs_rows),
+         int(sgs_negative_pivots), int(amg_rows), int(rows), b_ptr or None,
+         x_ptr or None, dinv_ptr or None)
+
+
+def minres(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, dinv_ptr=None, sgs=None,
+           amg=None, ws=None, time_spmv=False, poll_every=0, stats=None):
+    """spmv::minres: preconditioned MINRES from x0 = 0 for a symmetric matrix
+    that need not be definite -> (k, rnorm_history, status).  Preconditioner
+    (symmetric positive definite, at most one): dinv_ptr, a positive device
+    vector; sgs, an SgsPreconditioner or an Ilu0Preconditioner without negative
+    pivots; amg, an AmgPreconditioner.  rnorm_history is the residual in the
+    M^-1-norm (the 2-norm without a preconditioner).  status: 0 converged or
+    kmax reached, 1 the Lanczos process ended, 2 r.M^-1 r < 0, 3 a singular
+    direction (host/cg.h).  stats (optional dict) receives spmv_ms_total and
+    spmv_launches of a time_spmv solve (one SpMV per iteration)."""
+    kmax = int(kmax)
+    k, n, status = C.c_int(), C.c_int(), C.c_int()
+    ms = f64()
+    hist = np.zeros(max(kmax, 0) + 1)
+    call("spmvh_minres", comm.h, exec_.h, A.h, b_ptr, x_ptr, dinv_ptr or None,
+         sgs.h if sgs else None, amg.h if amg else None, kmax, float(rtol),
+         C.byref(k), C.byref(status), _np_ptr(hist), ws.h if ws else None,
+         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         C.byref(n))
     if stats is not None:
         stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
     return k.value, hist[:k.value + 1], status.value
