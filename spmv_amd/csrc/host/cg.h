@@ -1332,6 +1332,17 @@ public:
 // reached), 1, 2 or 3 as above.  A non-finite scalar takes the "go on" branch of
 // every comparison, so such a solve ends at kmax, as in gmres().
 //
+// Scaling.  (2^s A, 2^t b) repeats the solve of (A, b) bit for bit (x times
+// 2^(t-s); the history times 2^t without a preconditioner, times 2^(t - s/2)
+// for an even s with an M^-1 that scales by 2^-s) only while gbar*gbar +
+// beta*beta stays a normal number: roughly |s| < 510 without a preconditioner,
+// any s with one, since alfa, gbar and (from k = 1) beta then do not scale.
+// Outside that range the sum overflows (gamma = Inf: a non-finite history that
+// runs to kmax, or, where beta == 0, status 1 with hist[k] = 0 and an x that
+// never moved) or underflows to 0 (gamma == 0: status 3 on a regular system).
+// A right-hand side whose r.M^-1 r underflows to 0 (b = 1e-200) stops at the
+// start with beta1 == 0, k = 0 and x = 0 although b != 0.
+//
 // Launches of one iteration on one rank, beside the SpMV (with its fused
 // v.Av; symmetric storage: plus one dot kernel): update_r (adds the partials of
 // alfa itself; t over r1's buffer, y = dinv*t, partials of r2.y), the reducer,
