@@ -1673,6 +1673,92 @@ int spmv_hip_minres_update_xwv_f64(spmv_hip_ctx* ctx, spmv_hip_minres_ws* ws,
                                    const double* w2, double* x, const double* y,
                                    void* stream);
 
+/* ---- LSQR (spmv::lsqr, host/cg.h) ---------------------------------------------
+ * Vectors: doubles at any 8-byte aligned address; where every vector of a call
+ * is 16-byte aligned the kernels use 16-byte accesses, otherwise pairs of 8-byte
+ * ones, with the same bits.  Every product, sum, difference, quotient and
+ * square root is one rounding.  ut (m doubles, the row space) and vt (n doubles,
+ * the owned part of the column space) are the UN-NORMALISED vectors of the
+ * bidiagonalisation, ib = 1 / beta and ia = 1 / alpha their scales.  One
+ * iteration (the recurrence is spelled out in host/cg.h):
+ *   Av = A vt ; update_u ; [several ranks: reduce(UU) ; all-reduce of the slot]
+ *   Atu = A^T ut (+ reverse halo) ; update_v ;
+ *   [reduce(VV) ; all-reduce of the slot] ; step ; update_xw(k)
+ * and once in front: spmv_hip_dot_partial_f64(ut, ut) into PART_UU ; [reduce(UU)
+ * ; all-reduce] ; Atu = A^T ut ; update_v(first) ; [reduce(VV) ; all-reduce] ;
+ * start ; update_xw(0).
+ * Device state of a workspace: the 15 doubles of SPMV_HIP_LSQR_SCALARS, in this
+ * order: rtol, ltol, damp, uu, vv, alpha, beta, phibar, rhobar, anorm2, psi2,
+ * ia, ib, t1 (= phi / rho), t2 (= theta / rho); the words done, kstop, status
+ * (0 converged / kmax / running, 1 the least-squares test, 2 the
+ * bidiagonalisation ended), k (steps completed), kmax; hist_r[0..kmax] and
+ * hist_ar[0..kmax]; two partial arrays of spmv_hip_dot_partials_len() doubles.
+ * `done` is raised by start or step; after it update_u, update_v, reduce, start
+ * and step return at once.  update_xw(k) runs only while the state's k equals
+ * its own: the step that stopped still gets its x, once; nothing afterwards
+ * writes x, w, the histories or k. */
+typedef struct spmv_hip_lsqr_ws spmv_hip_lsqr_ws; /* lsqr() scalars */
+enum {
+  SPMV_HIP_LSQR_UU = 0,      /* 1: ut.ut where a reducer (or update_v) put it     */
+  SPMV_HIP_LSQR_VV = 1,      /* 1: vn.vn where a reducer (or start / step) put it */
+  SPMV_HIP_LSQR_HIST_R = 2,  /* kmax + 1                                          */
+  SPMV_HIP_LSQR_HIST_AR = 3, /* kmax + 1, right behind HIST_R                     */
+  SPMV_HIP_LSQR_PART_UU = 4, /* dot_partials_len                                  */
+  SPMV_HIP_LSQR_PART_VV = 5, /* dot_partials_len                                  */
+  SPMV_HIP_LSQR_SCALARS = 6  /* 15: see above (tests read and install them)       */
+};
+int spmv_hip_lsqr_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_lsqr_ws** ws);
+int spmv_hip_lsqr_ws_destroy(spmv_hip_lsqr_ws* ws);
+/* kmax <= the capacity; zeroes the scalars and both histories */
+int spmv_hip_lsqr_ws_reset(spmv_hip_lsqr_ws* ws, double rtol, double ltol,
+                           double damp, int kmax, void* stream);
+int spmv_hip_lsqr_ws_capacity(const spmv_hip_lsqr_ws* ws, int* kmax);
+/* device address and length of one array of the state */
+int spmv_hip_lsqr_ws_array(spmv_hip_lsqr_ws* ws, int which, double** p,
+                           int64_t* count);
+/* copies {done, kstop, status} (3 x int32) and hist_r[0..capacity] followed by
+ * hist_ar[0..capacity] to the host (async; either may be NULL; host_hist_len >=
+ * 2 * (capacity + 1) or nothing is enqueued) */
+int spmv_hip_lsqr_ws_read_async(spmv_hip_lsqr_ws* ws,
+                                int32_t* host_done_kstop_status,
+                                double* host_hist, size_t host_hist_len,
+                                void* stream);
+/* TEST HOOKS: install k and done (kstop = k when done; status 0; waits), read
+ * {done, kstop, status, k, kmax} */
+int spmv_hip_lsqr_ws_set_state(spmv_hip_lsqr_ws* ws, int k, int done,
+                               void* stream);
+int spmv_hip_lsqr_ws_get_state(spmv_hip_lsqr_ws* ws, int32_t* host_words5,
+                               void* stream);
+/* ut = Av * ia - alpha * (ut * ib) in place ; partials of ut.ut into PART_UU */
+int spmv_hip_lsqr_update_u_f64(spmv_hip_ctx* ctx, spmv_hip_lsqr_ws* ws,
+                               int64_t n, const double* Av, double* ut,
+                               void* stream);
+/* uu: the slot (reduced != 0), or PART_UU added by every workgroup in the
+ * reducer's order and left in the slot.  beta = sqrt(uu).  beta != 0: vn = Atu *
+ * (1 / beta) - beta * (vt * ia), written over vt (first != 0: vn = Atu * (1 /
+ * beta), vt is not read) ; partials of vn.vn into PART_VV.  beta == 0: vt stays
+ * and the partials are zero. */
+int spmv_hip_lsqr_update_v_f64(spmv_hip_ctx* ctx, spmv_hip_lsqr_ws* ws,
+                               int64_t n, const double* Atu, double* vt,
+                               int first, int reduced, void* stream);
+/* PART_UU -> UU or PART_VV -> VV; one workgroup */
+int spmv_hip_lsqr_reduce(spmv_hip_ctx* ctx, spmv_hip_lsqr_ws* ws, int which,
+                         void* stream);
+/* one workgroup: vv from the slot (reduced != 0) or from PART_VV in the
+ * reducer's order; thread 0: beta = sqrt(uu), hist_r[0] = beta (0: done, status
+ * 0), alpha = sqrt(vv), hist_ar[0] = alpha * beta (alpha == 0: done, status 2),
+ * the state in front of the first step */
+int spmv_hip_lsqr_start(spmv_hip_ctx* ctx, spmv_hip_lsqr_ws* ws, int reduced,
+                        void* stream);
+/* one workgroup: vv as in start; thread 0: the scalar part of an iteration */
+int spmv_hip_lsqr_step(spmv_hip_ctx* ctx, spmv_hip_lsqr_ws* ws, int reduced,
+                       void* stream);
+/* k >= 1, state k == k: x = x + t1 * w ; not done: w = vt * ia - t2 * w.
+ * k == 0, state k == 0, not done: w = vt * ia alone (x unused). */
+int spmv_hip_lsqr_update_xw_f64(spmv_hip_ctx* ctx, spmv_hip_lsqr_ws* ws, int k,
+                                int64_t n, const double* vt, double* w,
+                                double* x, void* stream);
+
 /* ---- 3-D Poisson generator (not in the reference)
  * 7-point stencil on an n^3 grid, natural ordering, diag 6, off-diag -1.
  * Generates, directly in device memory, the CSR block of global rows

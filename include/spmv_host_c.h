@@ -727,6 +727,31 @@ int spmvh_minres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                  spmvh_minres_workspace* ws, int flags, double* spmv_ms_total,
                  int* spmv_launches);
 
+/* ---- LSQR (spmv::lsqr, host/cg.h; not in the reference) -----------------------
+ * spmvh_lsqr: LSQR from x0 = 0 for any matrix, rectangular or square: min ||A x
+ * - b||, with damp > 0 min ||A x - b||^2 + damp^2 ||x||^2.  b: the matrix's
+ * local rows, x: its owned columns (device pointers of any alignment).  hist_r
+ * and hist_ar (each may be NULL): kmax + 1 doubles, receive [0..*num_its] of
+ * the estimates of ||b - A x|| and of ||A^T (b - A x) - damp^2 x||.  *status
+ * (may be NULL): 0 kmax reached or hist_r[k] / hist_r[0] < rtol, 1 the
+ * least-squares test hist_ar[k] / (||A|| hist_r[k]) < ltol, 2 the
+ * bidiagonalisation ended (x is exact).  ws: a reusable spmv::LsqrWorkspace (may
+ * be NULL).  flags: bit 0 -> CgOptions::time_spmv (both products are counted: 2
+ * launches per iteration), bits 8-15 -> poll_every (0 = default).
+ * spmvh_lsqr_check_rules: lsqr_check_rules of solver_args.h alone (no device;
+ * the pointers are compared, never dereferenced). */
+typedef struct spmvh_lsqr_workspace spmvh_lsqr_workspace;
+int spmvh_lsqr_workspace_create(spmvh_exec* exec, spmvh_lsqr_workspace** ws);
+int spmvh_lsqr_workspace_destroy(spmvh_lsqr_workspace* ws);
+int spmvh_lsqr_workspace_reserve_timing(spmvh_lsqr_workspace* ws, int iterations);
+int spmvh_lsqr_check_rules(int kmax, double ltol, double damp, int64_t rows,
+                           int64_t cols, const double* b, const double* x);
+int spmvh_lsqr(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+               const double* b, double* x, int kmax, double rtol, double ltol,
+               double damp, int* num_its, int* status, double* hist_r,
+               double* hist_ar, spmvh_lsqr_workspace* ws, int flags,
+               double* spmv_ms_total, int* spmv_launches);
+
 #ifdef __cplusplus
 }
 #endif

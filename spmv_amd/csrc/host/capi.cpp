@@ -57,6 +57,7 @@ struct spmvh_sgs_workspace : WorkspaceHandle<SgsWorkspace> {};
 struct spmvh_pcg_block_workspace : WorkspaceHandle<PcgBlockWorkspace> {};
 struct spmvh_gmres_workspace : WorkspaceHandle<GmresWorkspace> {};
 struct spmvh_minres_workspace : WorkspaceHandle<MinresWorkspace> {};
+struct spmvh_lsqr_workspace : WorkspaceHandle<LsqrWorkspace> {};
 struct spmvh_sgs_build {
   SgsHostPlan plan;
 };
@@ -2103,6 +2104,54 @@ int spmvh_minres(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     if (status)
       *status = how;
     copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
+  });
+}
+
+// ---- LSQR -------------------------------------------------------------------------------
+int spmvh_lsqr_workspace_create(spmvh_exec* exec, spmvh_lsqr_workspace** ws)
+{
+  return workspace_create<LsqrWorkspace>(exec, ws);
+}
+
+int spmvh_lsqr_workspace_destroy(spmvh_lsqr_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_lsqr_workspace_reserve_timing(spmvh_lsqr_workspace* ws, int iterations)
+{
+  return workspace_reserve_timing(ws, iterations);
+}
+
+int spmvh_lsqr_check_rules(int kmax, double ltol, double damp, int64_t rows,
+                           int64_t cols, const double* b, const double* x)
+{
+  return guarded([&] { lsqr_check_rules(kmax, ltol, damp, rows, cols, b, x); });
+}
+
+int spmvh_lsqr(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+               const double* b, double* x, int kmax, double rtol, double ltol,
+               double damp, int* num_its, int* status, double* hist_r,
+               double* hist_ar, spmvh_lsqr_workspace* ws, int flags,
+               double* spmv_ms_total, int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && num_its, "NULL argument");
+    std::vector<double> hr, har;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff) // bits 8-15: CgOptions::poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    CgStats st;
+    int how = 0;
+    *num_its = lsqr(*comm->comm, *exec->hip, *A->A, b, x, kmax, rtol, ltol, damp,
+                    hist_r ? &hr : nullptr, hist_ar ? &har : nullptr, &how, &opt,
+                    &st, ws ? ws->ws.get() : nullptr);
+    if (status)
+      *status = how;
+    if (hist_ar)
+      std::copy(har.begin(), har.end(), hist_ar);
+    copy_out(hr, hist_r, st, spmv_ms_total, spmv_launches);
   });
 }
 

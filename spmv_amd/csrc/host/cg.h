@@ -20,6 +20,7 @@ struct spmv_hip_pcgb_ws;
 struct spmv_hip_bicg_ws;
 struct spmv_hip_gmres_ws;
 struct spmv_hip_minres_ws;
+struct spmv_hip_lsqr_ws;
 struct spmv_hip_mcgs_plan;
 struct spmv_hip_ilu0_plan;
 struct spmv_hip_amg_tail;
@@ -1373,5 +1374,118 @@ int minres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
            double rtol, std::vector<double>* rnorm_history = nullptr,
            const CgOptions* options = nullptr, CgStats* stats = nullptr,
            MinresWorkspace* workspace = nullptr, int* status = nullptr);
+
+// ---- LSQR -----------------------------------------------------------------------
+
+// Work vectors + device scalars of lsqr(), kept across calls like
+// MinresWorkspace; it regrows itself when a call needs more rows, more columns
+// or more iterations.
+class LsqrWorkspace : public SolverWorkspace
+{
+public:
+  explicit LsqrWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
+  ~LsqrWorkspace();
+
+  // ---- internal to lsqr() ----
+  // need_x: the caller's x is not 16-byte aligned and lives in the workspace's
+  // copy
+  void ensure(int64_t M, int64_t N, int64_t N_padded, int kmax, bool need_x);
+  // two products per iteration
+  void reserve_timing(int iterations)
+  {
+    reserve_events(4 * (size_t)std::max(iterations, 0));
+  }
+  void release();
+
+  spmv_hip_lsqr_ws* ws = nullptr;
+  int kmax_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, w_cap = -1, x_cap = -1;
+  double *ut = nullptr, *Av = nullptr;  // m_cap: the row space
+  double *vt = nullptr, *Atu = nullptr; // n_cap: padded, what mult reads and
+                                        // transpmult writes
+  double* w = nullptr;                  // w_cap: the owned columns
+  double* x = nullptr;                  // x_cap: the iterate of an unaligned x
+  // flags: {done, kstop, status}; timing_ev: 4 events per iteration
+};
+
+// LSQR (Paige and Saunders, 1982) from x0 = 0 for ANY matrix, rectangular or
+// square, in either storage: min ||A x - b|| of an over-determined system, the
+// damped fit min ||A x - b||^2 + damp^2 ||x||^2, the minimum-norm solution of
+// an under-determined system, and a breakdown-free solver for the square
+// nonsymmetric systems on which bicgstab() gives up.  Only Matrix::mult,
+// Matrix::transpmult, col_map()->update and reverse_update are used: every plan
+// form and halo model serves.  b: A.row_map()->local_size() doubles; x:
+// A.col_map()->local_size() doubles.  With `.` the global dot product, A^T u
+// the transposed product followed by the reverse halo update, taken over the
+// owned columns, every product, sum, difference, quotient and square root one
+// rounding of its own:
+//
+//   x = 0; ut = b; beta = sqrt(ut.ut); hist_r[0] = beta
+//   beta == 0: return 0 with x = 0
+//   ib = 1/beta; vt = (A^T ut)*ib; alpha = sqrt(vt.vt); hist_ar[0] = alpha*beta
+//   alpha == 0: status 2, return 0
+//   ia = 1/alpha; w = vt*ia; phibar = beta; rhobar = alpha; anorm2 = 0;
+//   psi2 = 0; k = 0
+//   while k < kmax:
+//     ut = (A vt)*ia - alpha*(ut*ib)          halo update of vt first
+//     beta = sqrt(ut.ut)
+//     anorm2 = ((anorm2 + alpha*alpha) + beta*beta) + damp*damp
+//     beta != 0: ib = 1/beta; vn = (A^T ut)*ib - beta*(vt*ia);
+//                alpha_n = sqrt(vn.vn)        (else alpha_n = 0)
+//     rhobar1 = sqrt(rhobar*rhobar + damp*damp); cs1 = rhobar/rhobar1;
+//     sn1 = damp/rhobar1
+//     psi = sn1*phibar; phibar = cs1*phibar; psi2 = psi2 + psi*psi
+//     rho = sqrt(rhobar1*rhobar1 + beta*beta); cs = rhobar1/rho; sn = beta/rho
+//     theta = sn*alpha_n; rhobar = -cs*alpha_n; phi = cs*phibar;
+//     phibar = sn*phibar
+//     x = x + (phi/rho)*w;  k += 1
+//     hist_r[k] = sqrt(phibar*phibar + psi2)
+//     hist_ar[k] = |(phibar*alpha_n)*cs|
+//     beta == 0 or alpha_n == 0: status 2; stop (the bidiagonalisation ended:
+//                                x is the solution in exact arithmetic)
+//     hist_r[k] / hist_r[0] < rtol: stop
+//     hist_ar[k] / (sqrt(anorm2)*hist_r[k]) < ltol: status 1; stop
+//     vt = vn; alpha = alpha_n; ia = 1/alpha; w = vt*ia - (theta/rho)*w
+//
+// ut and vt are the UN-NORMALISED vectors of the Golub-Kahan process: their
+// scales ib and ia ride into the kernel that consumes the next product (A and
+// A^T are linear), which saves two read-and-write passes per iteration.  vt is
+// the padded column-space vector mult reads; its ghost tail is zeroed by every
+// solve and refreshed by the halo update before each mult.
+//
+// hist_r receives hist_r[0..k]: the estimate of ||b - A x|| (damp > 0: of
+// sqrt(||b - A x||^2 + damp^2 ||x||^2)); hist_ar receives hist_ar[0..k]: the
+// estimate of ||A^T (b - A x) - damp^2 x||.  Returns k; `status` (optional)
+// receives 0 (kmax reached, or the rtol test), 1 (the least-squares test) or 2.
+// A non-finite scalar takes the "go on" branch of every comparison, so such a
+// solve ends at kmax with status 0, as in minres(); the workspace is usable
+// afterwards.
+//
+// Launches of one iteration on one rank, beside mult and transpmult: update_u
+// (3 passes of m), update_v (adds the partials of ut.ut itself, in the
+// reducer's order; 3 passes of n), step (one workgroup adds the partials of
+// vn.vn in the reducer's order, its thread 0 does all the scalar arithmetic),
+// update_xw (5 passes of n): 4 launches, 11 vector passes.  With several ranks:
+// two reducer launches more and two all-reduces of 1 double (ut.ut, vn.vn).
+//
+// As in minres(): the scalars stay on the device, the decision to stop is
+// taken there and the host only looks at a pinned flag every `poll_every`
+// iterations.  update_xw runs exactly when step k completed, so x is the
+// iterate of the returned k whatever poll_every is, and w is not written on the
+// step that stops.  `x` IS the iterate: zeroed at the start, updated in place;
+// an x that is not 16-byte aligned goes through the workspace's copy (b is
+// copied anyway: it is the first ut).  The argument rules are
+// lsqr_check_rules' (solver_args.h: "kmax", "ltol", "damp", "overlaps"),
+// checked before anything touches a device; the executor's stream is restored
+// on every exit path.
+//
+// options: poll_every and time_spmv apply (both products are bracketed:
+//          spmv_launches is 2 per iteration); the other CgOptions are IGNORED.
+int lsqr(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+         const double* b, double* x, int kmax, double rtol, double ltol,
+         double damp, std::vector<double>* hist_r = nullptr,
+         std::vector<double>* hist_ar = nullptr, int* status = nullptr,
+         const CgOptions* options = nullptr, CgStats* stats = nullptr,
+         LsqrWorkspace* workspace = nullptr);
 
 } // namespace spmv

@@ -158,6 +158,21 @@ void minres_check_rules(int kmax, bool has_dinv, bool has_sgs, bool has_amg,
     throw std::runtime_error("minres: x overlaps dinv (x is updated in place)");
 }
 
+void lsqr_check_rules(int kmax, double ltol, double damp, int64_t rows,
+                      int64_t cols, const double* b, const double* x)
+{
+  if (kmax < 0)
+    throw std::runtime_error("spmv::lsqr - Error: kmax < 0");
+  if (!(ltol >= 0.0) || !std::isfinite(ltol))
+    throw std::runtime_error(
+        "spmv::lsqr - Error: ltol must be finite and not negative");
+  if (!(damp >= 0.0) || !std::isfinite(damp))
+    throw std::runtime_error(
+        "spmv::lsqr - Error: damp must be finite and not negative");
+  if (doubles_overlap(x, cols, b, rows))
+    throw std::runtime_error("lsqr: x overlaps b (x is updated in place)");
+}
+
 void amg_check_tail_rows(int64_t max_rows)
 {
   if (max_rows < 0)

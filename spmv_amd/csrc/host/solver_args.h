@@ -70,6 +70,13 @@ void minres_check_rules(int kmax, bool has_dinv, bool has_sgs, bool has_amg,
                         int64_t amg_rows, int64_t rows, const double* b,
                         const double* x, const double* dinv);
 
+// The argument rules of lsqr() (std::runtime_error), in this order: kmax < 0
+// ("kmax"), ltol negative or not finite ("ltol"), damp negative or not finite
+// ("damp"), x (cols doubles) sharing a byte with b (rows doubles) ("overlaps").
+// The pointers are compared, never dereferenced.
+void lsqr_check_rules(int kmax, double ltol, double damp, int64_t rows,
+                      int64_t cols, const double* b, const double* x);
+
 // stride of the basis vectors: N_padded rounded up to an even number, so that
 // every v_j is 16-byte aligned
 int64_t gmres_basis_stride(int64_t N_padded);

@@ -219,6 +219,12 @@ _PROTOS = {
                                  i64, i64, vp, vp, vp],
     "spmvh_minres": [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int),
                      PTR(C.c_int), vp, vp, C.c_int, PTR(f64), PTR(C.c_int)],
+    "spmvh_lsqr_workspace_create": [vp, PTR(vp)],
+    "spmvh_lsqr_workspace_destroy": [vp],
+    "spmvh_lsqr_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_lsqr_check_rules": [C.c_int, f64, f64, i64, i64, vp, vp],
+    "spmvh_lsqr": [vp, vp, vp, vp, vp, C.c_int, f64, f64, f64, PTR(C.c_int),
+                   PTR(C.c_int), vp, vp, vp, C.c_int, PTR(f64), PTR(C.c_int)],
     "spmvh_gmres_workspace_create": [vp, PTR(vp)],
     "spmvh_gmres_workspace_destroy": [vp],
     "spmvh_gmres_workspace_reserve_timing": [vp, C.c_int],
@@ -1571,6 +1577,46 @@ def minres(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, dinv_ptr=None, sgs=None,
     if stats is not None:
         stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
     return k.value, hist[:k.value + 1], status.value
+
+
+class LsqrWorkspace(_TimedWorkspace):
+    """spmv::LsqrWorkspace: work vectors and device scalars kept across lsqr()
+    calls."""
+    _prefix = "lsqr"
+
+
+def lsqr_check_rules(kmax, ltol=0.0, damp=0.0, rows=0, cols=0, b_ptr=None,
+                     x_ptr=None):
+    """spmv::lsqr_check_rules alone (no device; the pointers are compared, never
+    dereferenced); raises SpmvHostError naming the rule."""
+    call("spmvh_lsqr_check_rules", int(kmax), float(ltol), float(damp),
+         int(rows), int(cols), b_ptr or None, x_ptr or None)
+
+
+def lsqr(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, ltol=0.0, damp=0.0, ws=None,
+         time_spmv=False, poll_every=0, stats=None):
+    """spmv::lsqr: LSQR from x0 = 0 for any matrix, rectangular or square ->
+    (k, hist_r, hist_ar, status).  Minimises ||A x - b||^2 + damp^2 ||x||^2 on
+    Matrix::mult and Matrix::transpmult; b_ptr: the matrix's local rows, x_ptr:
+    its owned columns.  hist_r estimates ||b - A x|| (with damp:
+    sqrt(||b - A x||^2 + damp^2 ||x||^2)), hist_ar ||A^T (b - A x) - damp^2 x||.
+    status: 0 kmax reached or hist_r[k] / hist_r[0] < rtol, 1 the least-squares
+    test hist_ar[k] / (||A|| hist_r[k]) < ltol, 2 the bidiagonalisation ended
+    (host/cg.h).  stats (optional dict) receives spmv_ms_total and
+    spmv_launches of a time_spmv solve (two products per iteration)."""
+    kmax = int(kmax)
+    k, n, status = C.c_int(), C.c_int(), C.c_int()
+    ms = f64()
+    hist_r = np.zeros(max(kmax, 0) + 1)
+    hist_ar = np.zeros(max(kmax, 0) + 1)
+    call("spmvh_lsqr", comm.h, exec_.h, A.h, b_ptr, x_ptr, kmax, float(rtol),
+         float(ltol), float(damp), C.byref(k), C.byref(status), _np_ptr(hist_r),
+         _np_ptr(hist_ar), ws.h if ws else None,
+         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         C.byref(n))
+    if stats is not None:
+        stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, hist_r[:k.value + 1], hist_ar[:k.value + 1], status.value
 
 
 def host_executor_rejects_compute():
