@@ -49,6 +49,7 @@ typedef struct spmv_hip_cg_ws spmv_hip_cg_ws;       /* cg() work vectors   */
 typedef struct spmv_hip_cgb_ws spmv_hip_cgb_ws;     /* cg_block() scalars  */
 typedef struct spmv_hip_pcg_ws spmv_hip_pcg_ws;     /* pcg() scalars       */
 typedef struct spmv_hip_pcgb_ws spmv_hip_pcgb_ws;   /* pcg_block() scalars */
+typedef struct spmv_hip_lobpcg_ws spmv_hip_lobpcg_ws; /* lobpcg() scalars */
 typedef struct spmv_hip_bicg_ws spmv_hip_bicg_ws;   /* bicgstab() scalars  */
 typedef struct spmv_hip_gmres_ws spmv_hip_gmres_ws; /* gmres() scalars     */
 typedef struct spmv_hip_comm spmv_hip_comm;         /* RCCL communicator   */
@@ -1585,6 +1586,86 @@ int spmv_hip_gmres_residual_f64(spmv_hip_ctx* ctx, spmv_hip_gmres_ws* ws,
 /* z = dinv * v (elementwise): the diagonal right preconditioner */
 int spmv_hip_gmres_diag_f64(spmv_hip_ctx* ctx, int64_t n, const double* dinv,
                             const double* v, double* z, void* stream);
+
+/* ---- LOBPCG (spmv::lobpcg, host/cg.h) ----------------------------------------
+ * Kernels of the block eigensolver on blocks of nev interleaved vectors (element
+ * (i, c) at V[i * nev + c], 1 <= nev <= 8); hip/blas1_lobpcg.hip states the
+ * arithmetic and the summation orders.  The basis of a step is S = [X, W, P]
+ * (blocks = 3) or [X] (blocks = 1: the prologue), AS = [AX, AW, AP].
+ *
+ * Device state words (spmv_hip_lobpcg_ws_read_async): {done, kstop, status, it,
+ * active, has_p, restarts, basis}.  Once `done` is raised every kernel returns
+ * at once, except residual / norms called with final != 0 (the epilogue).
+ *   gram         one pass over the 2 * blocks blocks -> per-workgroup partials
+ *   gram_reduce  partials -> the slot SPMV_HIP_LOBPCG_GRAM (several ranks: the
+ *                all-reduce of 2 m m doubles, m = blocks * nev, works on it).
+ *                One thread per entry adds the workgroups' partials LEFT TO
+ *                RIGHT in index order from 0.0.  This is NOT the order of
+ *                sum_partials / spmv_block_sum (thread-strided sums, then the
+ *                shuffle tree) that every dot product of the library uses: a
+ *                reference written for those does not give these bits.  rr
+ *                with reduced == 0 adds the partials in this same order.
+ *   rr           one workgroup.  mode 0: Rayleigh-Ritz on (Ga, Gb) -> theta,
+ *                the coefficients, the basis mask; mode 1: C = D R^-1 alone.
+ *                reduced: read the slot, not the partials.  advance: a step
+ *                that succeeds completes an iteration.  A collapsed basis
+ *                (twice) raises done with status 1.
+ *   update       X' = S C, P' = [W, P] C_wp, and with AX != NULL AX', AP', in
+ *                place, one pass
+ *   residual     R = AX - X diag(theta); W (may be NULL) = dinv * R, or R when
+ *                dinv is NULL; partials of ||r_c||^2
+ *   norms        phase 0: partials -> sums -> history, mask, done; phase 1: the
+ *                sums alone into SPMV_HIP_LOBPCG_RN; phase 2: the decision from
+ *                that slot.  final: sums into the slot's second half, nothing
+ *                else. */
+enum {
+  SPMV_HIP_LOBPCG_HIST = 0,  /* (kmax + 1) * nev                              */
+  SPMV_HIP_LOBPCG_THETA = 1, /* nev                                           */
+  SPMV_HIP_LOBPCG_COEF = 2,  /* 3 nev * nev, row j = basis column j           */
+  SPMV_HIP_LOBPCG_GRAM = 3,  /* 2 * m * m: Gb then Ga, upper triangles        */
+  SPMV_HIP_LOBPCG_GPART = 4, /* the Gram kernel's partials, 2 m m per group   */
+  SPMV_HIP_LOBPCG_RN = 5,    /* 2 * nev: ||r_c||^2, then the epilogue's       */
+  SPMV_HIP_LOBPCG_RPART = 6  /* dot_partials_len * nev                        */
+};
+#define SPMV_HIP_LOBPCG_STATE_WORDS 8
+int spmv_hip_lobpcg_ws_create(spmv_hip_ctx* ctx, int kmax, int nev,
+                              spmv_hip_lobpcg_ws** ws);
+int spmv_hip_lobpcg_ws_destroy(spmv_hip_lobpcg_ws* ws);
+int spmv_hip_lobpcg_ws_reset(spmv_hip_lobpcg_ws* ws, double rtol, double atol,
+                             int kmax, int largest, void* stream);
+int spmv_hip_lobpcg_ws_capacity(const spmv_hip_lobpcg_ws* ws, int* kmax,
+                                int* nev);
+int spmv_hip_lobpcg_ws_array(spmv_hip_lobpcg_ws* ws, int which, double** p,
+                             int64_t* len);
+/* host_hist (may be NULL): at least (capacity kmax + 1) * nev doubles;
+ * host_scalars (may be NULL): 3 nev doubles, theta then SPMV_HIP_LOBPCG_RN */
+int spmv_hip_lobpcg_ws_read_async(spmv_hip_lobpcg_ws* ws, int32_t* host_state,
+                                  double* host_hist, size_t host_hist_len,
+                                  double* host_scalars, void* stream);
+/* tests: install the words a kernel reads */
+int spmv_hip_lobpcg_ws_set_state(spmv_hip_lobpcg_ws* ws, int active, int has_p,
+                                 int it, int done, void* stream);
+/* workgroups (= partials) of the Gram kernel for M rows */
+int spmv_hip_lobpcg_gram_grid(const spmv_hip_lobpcg_ws* ws, int64_t M, int* grid);
+int spmv_hip_lobpcg_gram_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
+                             int64_t M, int blocks, const double* X,
+                             const double* W, const double* P, const double* AX,
+                             const double* AW, const double* AP, void* stream);
+int spmv_hip_lobpcg_gram_reduce(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
+                                int64_t M, int blocks, void* stream);
+int spmv_hip_lobpcg_rr(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws, int64_t M,
+                       int blocks, int mode, int reduced, int advance,
+                       void* stream);
+int spmv_hip_lobpcg_update_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
+                               int64_t M, int blocks, double* X, const double* W,
+                               double* P, double* AX, const double* AW,
+                               double* AP, void* stream);
+int spmv_hip_lobpcg_residual_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
+                                 int64_t M, const double* X, const double* AX,
+                                 const double* dinv, double* R, double* W,
+                                 int final, void* stream);
+int spmv_hip_lobpcg_norms(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws, int phase,
+                          int final, void* stream);
 
 /* ---- Preconditioned MINRES (spmv::minres, host/cg.h) -------------------------
  * Vectors: n doubles, 16-byte aligned.  Every product, sum, difference,

@@ -752,6 +752,33 @@ int spmvh_lsqr(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                double* hist_ar, spmvh_lsqr_workspace* ws, int flags,
                double* spmv_ms_total, int* spmv_launches);
 
+/* ---- LOBPCG (spmv::lobpcg, host/cg.h; not in the reference) -------------------
+ * spmvh_lobpcg: the nev smallest (flags bit 1: largest) eigenpairs of a symmetric
+ * matrix.  X: device block of rows * nev doubles in the mult_block layout, the
+ * initial guess on entry, the Ritz vectors on exit.  At most one of dinv, sgs and
+ * amg (each may be NULL).  eigenvalues, true_resnorm: nev doubles;
+ * resnorm_history: nev * (kmax + 1) doubles, -1.0 beyond a column's last (each
+ * may be NULL).  *status (may be NULL): 0, or 1 the basis collapsed.  ws: a
+ * reusable spmv::LobpcgWorkspace (may be NULL).  flags: bit 0 -> time_spmv, bit 1
+ * -> largest, bits 8-15 -> poll_every (0 = default).
+ * spmvh_lobpcg_check_rules: lobpcg_check_rules of solver_args.h alone (no
+ * device). */
+typedef struct spmvh_lobpcg_workspace spmvh_lobpcg_workspace;
+int spmvh_lobpcg_workspace_create(spmvh_exec* exec, spmvh_lobpcg_workspace** ws);
+int spmvh_lobpcg_workspace_destroy(spmvh_lobpcg_workspace* ws);
+int spmvh_lobpcg_workspace_reserve_timing(spmvh_lobpcg_workspace* ws,
+                                          int iterations);
+int spmvh_lobpcg_check_rules(int nev, int kmax, double rtol, double atol,
+                             int has_dinv, int has_sgs, int has_amg,
+                             int64_t sgs_rows, int64_t sgs_negative_pivots,
+                             int64_t amg_rows, int64_t rows);
+int spmvh_lobpcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A, double* X,
+                 int nev, const double* dinv, spmvh_sgs* sgs, spmvh_amg* amg,
+                 int kmax, double rtol, double atol, int* num_its, int* status,
+                 double* eigenvalues, double* resnorm_history,
+                 double* true_resnorm, int* restarts, spmvh_lobpcg_workspace* ws,
+                 int flags, double* spmv_ms_total, int* spmv_launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,7 @@ struct spmvh_pcg_block_workspace : WorkspaceHandle<PcgBlockWorkspace> {};
 struct spmvh_gmres_workspace : WorkspaceHandle<GmresWorkspace> {};
 struct spmvh_minres_workspace : WorkspaceHandle<MinresWorkspace> {};
 struct spmvh_lsqr_workspace : WorkspaceHandle<LsqrWorkspace> {};
+struct spmvh_lobpcg_workspace : WorkspaceHandle<LobpcgWorkspace> {};
 struct spmvh_sgs_build {
   SgsHostPlan plan;
 };
@@ -2152,6 +2153,71 @@ int spmvh_lsqr(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     if (hist_ar)
       std::copy(har.begin(), har.end(), hist_ar);
     copy_out(hr, hist_r, st, spmv_ms_total, spmv_launches);
+  });
+}
+
+// ---- LOBPCG -----------------------------------------------------------------------------
+int spmvh_lobpcg_workspace_create(spmvh_exec* exec, spmvh_lobpcg_workspace** ws)
+{
+  return workspace_create<LobpcgWorkspace>(exec, ws);
+}
+
+int spmvh_lobpcg_workspace_destroy(spmvh_lobpcg_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_lobpcg_workspace_reserve_timing(spmvh_lobpcg_workspace* ws,
+                                          int iterations)
+{
+  return workspace_reserve_timing(ws, iterations);
+}
+
+int spmvh_lobpcg_check_rules(int nev, int kmax, double rtol, double atol,
+                             int has_dinv, int has_sgs, int has_amg,
+                             int64_t sgs_rows, int64_t sgs_negative_pivots,
+                             int64_t amg_rows, int64_t rows)
+{
+  return guarded([&] {
+    lobpcg_check_rules(nev, kmax, rtol, atol, has_dinv != 0, has_sgs != 0,
+                       has_amg != 0, sgs_rows, sgs_negative_pivots, amg_rows,
+                       rows);
+  });
+}
+
+int spmvh_lobpcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A, double* X,
+                 int nev, const double* dinv, spmvh_sgs* sgs, spmvh_amg* amg,
+                 int kmax, double rtol, double atol, int* num_its, int* status,
+                 double* eigenvalues, double* resnorm_history,
+                 double* true_resnorm, int* restarts, spmvh_lobpcg_workspace* ws,
+                 int flags, double* spmv_ms_total, int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && num_its, "NULL argument");
+    std::vector<double> eig, hist;
+    LobpcgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    opt.largest = (flags & 2) != 0;
+    if ((flags >> 8) & 0xff) // bits 8-15: poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    LobpcgStats st;
+    BlockPreconditioner pre;
+    pre.dinv = dinv;
+    pre.sgs = sgs ? sgs->M.get() : nullptr;
+    pre.amg = amg ? amg->M.get() : nullptr;
+    int how = 0;
+    *num_its = lobpcg(*comm->comm, *exec->hip, *A->A, X, nev, pre, kmax, rtol,
+                      atol, &eig, resnorm_history ? &hist : nullptr, &how, &opt,
+                      &st, ws ? ws->ws.get() : nullptr);
+    if (status)
+      *status = how;
+    if (eigenvalues)
+      std::copy(eig.begin(), eig.end(), eigenvalues);
+    if (true_resnorm)
+      std::copy(st.true_resnorm.begin(), st.true_resnorm.end(), true_resnorm);
+    if (restarts)
+      *restarts = st.restarts;
+    copy_out(hist, resnorm_history, st, spmv_ms_total, spmv_launches);
   });
 }
 

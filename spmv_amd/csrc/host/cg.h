@@ -21,6 +21,7 @@ struct spmv_hip_bicg_ws;
 struct spmv_hip_gmres_ws;
 struct spmv_hip_minres_ws;
 struct spmv_hip_lsqr_ws;
+struct spmv_hip_lobpcg_ws;
 struct spmv_hip_mcgs_plan;
 struct spmv_hip_ilu0_plan;
 struct spmv_hip_amg_tail;
@@ -1487,5 +1488,118 @@ int lsqr(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
          std::vector<double>* hist_ar = nullptr, int* status = nullptr,
          const CgOptions* options = nullptr, CgStats* stats = nullptr,
          LsqrWorkspace* workspace = nullptr);
+
+// ---- LOBPCG ---------------------------------------------------------------------
+struct LobpcgOptions {
+  int poll_every = 16;    // host looks at the device's `done` flag this often
+  bool time_spmv = false; // bracket the one mult_block of every iteration
+  // the Rayleigh-Ritz step keeps the nev LARGEST Ritz values (eigenvalues come
+  // back descending): a converged lambda_max with a residual bound, where
+  // lambda_max_estimate() gives an estimate
+  bool largest = false;
+};
+
+// CgStats plus what the epilogue measured
+struct LobpcgStats : CgStats {
+  // ||A x_c - theta_c x_c|| with AX = A X computed explicitly after the loop
+  // (the loop's AX is updated implicitly and drifts), nev entries
+  std::vector<double> true_resnorm;
+  int restarts = 0; // Rayleigh-Ritz steps repeated without P
+};
+
+// Work blocks + device scalars of lobpcg(), kept across calls like
+// PcgBlockWorkspace; it regrows itself when a call needs more rows, more
+// iterations or another nev.  Every block is rewritten by the next prologue.
+class LobpcgWorkspace : public SolverWorkspace
+{
+public:
+  explicit LobpcgWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
+  ~LobpcgWorkspace();
+
+  // ---- internal to lobpcg() ----
+  void ensure(int64_t m_elems, int64_t n_elems, int kmax, int nev, bool need_x);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(2 * (size_t)std::max(iterations, 0));
+  }
+  void release();
+
+  // (flags: {done, kstop, status, it, active, has_p, restarts, basis})
+  spmv_hip_lobpcg_ws* ws = nullptr;
+  int kmax_cap = -1, nev_cap = 0;
+  int64_t m_cap = -1, n_cap = -1, x_cap = -1;
+  double *r = nullptr, *p = nullptr, *ax = nullptr, *aw = nullptr,
+         *ap = nullptr;  // m_cap
+  double* x = nullptr;   // x_cap: the iterate when the caller's X is unaligned
+  double* w = nullptr;   // n_cap: padded, the ghost tail is zeroed by every solve
+};
+
+// LOBPCG (Knyazev, 2001): the nev smallest (options->largest: largest)
+// eigenpairs of a SYMMETRIC A in either storage, fp64, rows and owned columns
+// the same index range, 1 <= nev <= 8.  X is a device block of local_size * nev
+// doubles in the mult_block layout: the initial guess on entry (never all
+// zero), the Ritz vectors, orthonormal to rounding, on exit.  Every product,
+// sum, difference, quotient and square root is one rounding; k = nev:
+//
+//   prologue: G = X^T X; X = X R^-1 (R = chol(G)); AX = A X; Rayleigh-Ritz on
+//             (X^T AX, X^T X), k x k: X, AX, theta
+//   it = 0:   R = AX - X diag(theta); rn_c = ||r_c||; hist[c][0] = rn_c
+//             column c has met its test when rn_c < max(rtol |theta_c|, atol)
+//             (a NaN says "go on"); it is then inactive for good
+//   while some column is active and it < kmax:
+//     W  = M^-1 R     (dinv * R in the residual kernel, sgs_apply_block,
+//                      amg_apply_block, or W = R)
+//     AW = A W        (update_block of the padded W, then mult_block)
+//     S  = [X, W_act, P_act], AS likewise: soft locking, X keeps all columns;
+//          P is absent in the first iteration and after a restart
+//     Gb = S^T S, Ga = S^T AS: one pass over the six blocks, masked columns
+//          summed as well and ignored by the next step
+//     Rayleigh-Ritz on (Ga, Gb), m = k + 2 n_act <= 24 -> theta, C (m x k)
+//     X' = S C; AX' = AS C; P' = [W_act, P_act] C_wp; AP' likewise: one pass,
+//          in place; P and AP of an inactive column are left alone
+//     R = AX - X diag(theta); rn; hist; the mask; it += 1
+//   epilogue: AX = A X explicitly, R and ||r_c|| from it -> stats->true_resnorm
+//
+// The Rayleigh-Ritz step (one workgroup, blas1_lobpcg.hip states every rule):
+// Gram sums finished in a fixed order (the workgroups' partials of an entry
+// added left to right in index order -- NOT sum_partials' tree, which the dot
+// products of the other solvers use), compacted by the active mask, scaled by
+// 1 / sqrt(diag Gb), Gb = R^T R by Cholesky, R^-T Ga R^-1, cyclic Jacobi with a
+// fixed pair order, nev Ritz values selected ascending (largest: descending),
+// ties by index, C = R^-1 Z with the scaling undone.  A Cholesky pivot that
+// fails piv > 0 (a NaN fails it), or a Ritz value that is not finite, repeats
+// the step with S = [X, W_act] (a restart); if that fails too the solve ends
+// with status 1 and X the last iterate.  Non-finite data end that way as well,
+// and so does a rank-deficient initial X whenever its factorisation meets a
+// pivot that is not positive (status 1 at k = 0).  In rounded arithmetic the
+// pivot of a dependent column is a difference of nearly equal numbers and may
+// come out a tiny positive one: no threshold other than > 0 decides, so such a
+// block is not guaranteed to be refused; it then runs on a basis of rounding
+// noise and usually collapses at a later step.
+//
+// Returns the number of iterations.  eigenvalues (optional): nev Ritz values.
+// resnorm_history (optional): nev * (kmax + 1) entries, column c at
+// [c * (kmax + 1) + it], -1.0 beyond the iteration at which the column met its
+// test.  status (optional): 0 every column met its test or kmax was reached,
+// 1 the basis collapsed.  The scalars stay on the device, the decision to stop
+// is taken there and the host only looks at a pinned flag every poll_every
+// iterations; after `done` every kernel returns at once, so X is exactly the
+// iterate of the returned k.  An X that is not 16-byte aligned goes through the
+// workspace's copy.
+//
+// M: at most one member set; none: W = R.  The arguments are checked before
+// anything touches a device (lobpcg_check_rules of solver_args.h;
+// std::runtime_error): "nev", "kmax", "tol" (rtol, atol finite, >= 0, not both
+// 0), "preconditioner", "rows", "pivot".  Several ranks: one all-reduce of the
+// Gram sums (2 m m doubles) and one of nev doubles per iteration, the halo
+// exchange of W before mult_block, preconditioners block-Jacobi over the ranks.
+// Launches of one iteration on one rank beside mult_block and M: gram,
+// gram_reduce, rr, update, residual, norms; 6 + 10 + 3 (+1 with W) block passes.
+int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+           double* X, int nev, const BlockPreconditioner& M, int kmax,
+           double rtol, double atol, std::vector<double>* eigenvalues = nullptr,
+           std::vector<double>* resnorm_history = nullptr, int* status = nullptr,
+           const LobpcgOptions* options = nullptr, LobpcgStats* stats = nullptr,
+           LobpcgWorkspace* workspace = nullptr);
 
 } // namespace spmv

@@ -1,0 +1,244 @@
+// spmv::lobpcg for HipExecutor: see cg.h.
+#include "cg.h"
+
+#include "solver_common.h"
+
+namespace spmv
+{
+using namespace detail;
+
+// ---------------------------------------------------------------------------
+// lobpcg: see cg.h.  On the compute stream, k = nev, "Gram" = the Gram kernel, its
+// reducer and, with several ranks, the all-reduce of 2 m m doubles:
+//     prologue: rules, workspace, aligned copy of X, ghost tail of W, P = AP = 0
+//       Gram(X, X) ; rr(orth) ; update(X alone)         X = X R^-1
+//       W = X ; halo ; AX = A W
+//       Gram(X, AX) ; rr ; update(X, AX)                 the first Ritz pairs
+//       residual (+ W) ; norms                           it = 0
+//     it = 1..kmax, until the lagging poll sees `done`:
+//       [W = M^-1 R] ; halo of W ; AW = A W
+//       Gram(six blocks) ; rr ; update ; residual (+ W) ; norms
+//     epilogue: W = X ; halo ; AW = A W ; residual(final) ; norms(final) ; the
+//       history, copy back of an unaligned X, sync, times
+// ---------------------------------------------------------------------------
+LobpcgWorkspace::~LobpcgWorkspace() { release(); }
+
+void LobpcgWorkspace::release()
+{
+  release_common();
+  spmv_hip_lobpcg_ws_destroy(ws);
+  ws = nullptr;
+  free_vectors({&r, &p, &ax, &aw, &ap, &x, &w});
+  kmax_cap = -1;
+  nev_cap = 0;
+  m_cap = n_cap = x_cap = -1;
+}
+
+void LobpcgWorkspace::ensure(int64_t m_elems, int64_t n_elems, int kmax, int nev,
+                             bool need_x)
+{
+  open(SPMV_HIP_LOBPCG_STATE_WORDS);
+  if (kmax > kmax_cap || nev != nev_cap) {
+    // (an earlier solve on this workspace has been synchronised: nothing
+    // still reads the old scalars)
+    spmv_hip_lobpcg_ws_destroy(ws);
+    ws = nullptr;
+    kmax_cap = -1;
+    nev_cap = 0;
+    throw_on_error(spmv_hip_lobpcg_ws_create(_exec.context(), kmax, nev, &ws),
+                   "spmv_hip_lobpcg_ws_create");
+    kmax_cap = kmax;
+    nev_cap = nev;
+  }
+  regrow(m_cap, m_elems, {&r, &p, &ax, &aw, &ap});
+  if (need_x)
+    regrow(x_cap, m_elems, {&x});
+  regrow(n_cap, n_elems, {&w});
+}
+
+int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+           double* X, int nev, const BlockPreconditioner& M, int kmax,
+           double rtol, double atol, std::vector<double>* eigenvalues,
+           std::vector<double>* resnorm_history, int* status,
+           const LobpcgOptions* options, LobpcgStats* stats,
+           LobpcgWorkspace* workspace)
+{
+  // plain argument rules first: nothing below has touched a device yet
+  const int64_t rows = A.row_map()->local_size();
+  lobpcg_check_rules(nev, kmax, rtol, atol, M.dinv != nullptr, M.sgs != nullptr,
+                     M.amg != nullptr, M.sgs ? M.sgs->rows() : 0,
+                     M.sgs ? M.sgs->negative_pivots() : 0,
+                     M.amg ? M.amg->rows(0) : 0, rows);
+  const Dims dims = check_problem("lobpcg", A, kmax);
+  const int64_t M_rows = dims.M;
+  const int64_t m_elems = M_rows * nev, n_elems = dims.N_padded * nev;
+  const std::shared_ptr<const L2GMap>& col_l2g = dims.col_l2g;
+  const LobpcgOptions opt = options ? *options : LobpcgOptions();
+  spmv_hip_ctx* ctx = exec.context();
+  const bool several = comm.size() > 1;
+  const bool applied = M.sgs || M.amg; // M^-1 is a call of its own
+
+  LobpcgWorkspace own(exec);
+  LobpcgWorkspace& w = workspace ? *workspace : own;
+  const bool x_aligned = is_aligned16(X);
+  w.ensure(m_elems, n_elems, kmax, nev, !x_aligned);
+  if (opt.time_spmv)
+    w.reserve_timing(kmax);
+
+  SolveStream guard(exec, w.stream); // every launch below goes to w.stream
+
+  throw_on_error(spmv_hip_lobpcg_ws_reset(w.ws, rtol, atol, kmax, opt.largest,
+                                          nullptr),
+                 "spmv_hip_lobpcg_ws_reset");
+  auto slot = [&](int which) {
+    double* q = nullptr;
+    throw_on_error(spmv_hip_lobpcg_ws_array(w.ws, which, &q, nullptr),
+                   "spmv_hip_lobpcg_ws_array");
+    return q;
+  };
+  double* const slot_gram = slot(SPMV_HIP_LOBPCG_GRAM);
+  double* const slot_rn = slot(SPMV_HIP_LOBPCG_RN);
+
+  double* const Xi = x_aligned ? X : w.x;
+  if (!x_aligned)
+    exec.copy<double>(w.x, X, m_elems);
+  // the ghost tail of W is defined here instead of relying on fresh pages; P
+  // and AP are summed by the first Gram pass before anything wrote them
+  if (n_elems > m_elems)
+    exec.memset<double>(w.w + m_elems, 0, n_elems - m_elems);
+  exec.memset<double>(w.p, 0, m_elems);
+  exec.memset<double>(w.ap, 0, m_elems);
+  for (int i = 0; i < SPMV_HIP_LOBPCG_STATE_WORDS; ++i)
+    w.flags[i] = 0;
+
+  // Gram sums of `blocks` blocks, then the one-workgroup step on them
+  auto gram_rr = [&](int blocks, const double* ax, int mode, int advance) {
+    throw_on_error(spmv_hip_lobpcg_gram_f64(ctx, w.ws, M_rows, blocks, Xi, w.w,
+                                            w.p, ax, w.aw, w.ap, nullptr),
+                   "spmv_hip_lobpcg_gram_f64");
+    // (one thread per entry: the rr kernel's one wave would walk the partials
+    // of 18 entries per lane one after the other)
+    throw_on_error(spmv_hip_lobpcg_gram_reduce(ctx, w.ws, M_rows, blocks,
+                                               nullptr),
+                   "spmv_hip_lobpcg_gram_reduce");
+    if (several) {
+      const size_t m = (size_t)blocks * nev;
+      comm.reduce_sum(slot_gram, 2 * m * m, w.stream);
+    }
+    throw_on_error(spmv_hip_lobpcg_rr(ctx, w.ws, M_rows, blocks, mode, 1,
+                                      advance, nullptr),
+                   "spmv_hip_lobpcg_rr");
+  };
+  // R = AX - X diag(theta) (+ W where that is no call of its own), the norms
+  auto residual_norms = [&](const double* ax, int final) {
+    throw_on_error(spmv_hip_lobpcg_residual_f64(
+                       ctx, w.ws, M_rows, Xi, ax, M.dinv, w.r,
+                       final || applied ? nullptr : w.w, final, nullptr),
+                   "spmv_hip_lobpcg_residual_f64");
+    if (several) {
+      throw_on_error(spmv_hip_lobpcg_norms(ctx, w.ws, 1, final, nullptr),
+                     "spmv_hip_lobpcg_norms");
+      comm.reduce_sum(slot_rn + (final ? nev : 0), nev, w.stream);
+      if (!final)
+        throw_on_error(spmv_hip_lobpcg_norms(ctx, w.ws, 2, 0, nullptr),
+                       "spmv_hip_lobpcg_norms");
+    } else {
+      throw_on_error(spmv_hip_lobpcg_norms(ctx, w.ws, 0, final, nullptr),
+                     "spmv_hip_lobpcg_norms");
+    }
+  };
+  // out = A X through the padded block W (not guarded by the state: what it
+  // leaves after `done` is not used)
+  auto mult_x = [&](double* out) {
+    exec.copy<double>(w.w, Xi, m_elems);
+    col_l2g->update_block(w.w, nev);
+    A.mult_block(w.w, out, nev, nullptr);
+  };
+
+  gram_rr(1, Xi, 1, 0);
+  throw_on_error(spmv_hip_lobpcg_update_f64(ctx, w.ws, M_rows, 1, Xi, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr,
+                                            nullptr),
+                 "spmv_hip_lobpcg_update_f64");
+  mult_x(w.ax);
+  gram_rr(1, w.ax, 0, 0);
+  throw_on_error(spmv_hip_lobpcg_update_f64(ctx, w.ws, M_rows, 1, Xi, nullptr,
+                                            nullptr, w.ax, nullptr, nullptr,
+                                            nullptr),
+                 "spmv_hip_lobpcg_update_f64");
+  residual_norms(w.ax, 0);
+
+  auto read = [&](double* h, size_t n) {
+    throw_on_error(spmv_hip_lobpcg_ws_read_async(w.ws, w.flags, h, n, nullptr,
+                                                 nullptr),
+                   "spmv_hip_lobpcg_ws_read_async");
+  };
+
+  std::vector<void*>& timing_ev = w.timing_ev;
+  LaggingPoll poll(exec, w, opt.poll_every, kmax);
+  int k = 0;
+  while (k < kmax && !poll.stopped) {
+    ++k;
+    if (M.sgs)
+      sgs_apply_block(exec, *M.sgs, w.r, w.w, nev);
+    else if (M.amg) // (on the object's own scratch)
+      amg_apply_block(exec, *M.amg, w.r, w.w, nev);
+    col_l2g->update_block(w.w, nev); // starts on the side stream
+    void* ev1 = nullptr;
+    if (opt.time_spmv) {
+      ev1 = timing_ev[2 * (size_t)(k - 1) + 1];
+      exec.record_event(timing_ev[2 * (size_t)(k - 1)], w.stream);
+    }
+    A.mult_block(w.w, w.aw, nev, ev1);
+    gram_rr(3, w.ax, 0, 1);
+    throw_on_error(spmv_hip_lobpcg_update_f64(ctx, w.ws, M_rows, 3, Xi, w.w, w.p,
+                                              w.ax, w.aw, w.ap, nullptr),
+                   "spmv_hip_lobpcg_update_f64");
+    residual_norms(w.ax, 0);
+    poll.step(k, read);
+  }
+
+  // the true residuals: AX from X itself
+  mult_x(w.aw);
+  residual_norms(w.aw, 1);
+
+  int cap = 0, cap_nev = 0;
+  throw_on_error(spmv_hip_lobpcg_ws_capacity(w.ws, &cap, &cap_nev),
+                 "spmv_hip_lobpcg_ws_capacity");
+  std::vector<double> hist(((size_t)std::max(kmax, cap) + 1) * nev, -1.0);
+  std::vector<double> scal(3 * (size_t)nev, 0.0);
+  throw_on_error(spmv_hip_lobpcg_ws_read_async(w.ws, w.flags, hist.data(),
+                                               hist.size(), scal.data(), nullptr),
+                 "spmv_hip_lobpcg_ws_read_async");
+  if (Xi != X)
+    exec.copy<double>(X, Xi, m_elems);
+  exec.synchronize_stream(w.stream);
+
+  if (stats) {
+    *stats = LobpcgStats();
+    if (opt.time_spmv)
+      sum_spmv_times(ctx, timing_ev, 2 * (size_t)k, *stats);
+    stats->true_resnorm.resize(nev);
+    for (int c = 0; c < nev; ++c)
+      stats->true_resnorm[c] = std::sqrt(scal[2 * (size_t)nev + c]);
+    stats->restarts = w.flags[6];
+  }
+
+  // every way out of the loop raises `done` on the device (norms does at
+  // it == kmax)
+  const int k_final = w.flags[0] != 0 ? w.flags[1] : 0;
+  if (status)
+    *status = w.flags[2];
+  if (eigenvalues)
+    eigenvalues->assign(scal.begin(), scal.begin() + nev);
+  if (resnorm_history) {
+    resnorm_history->assign((size_t)nev * ((size_t)kmax + 1), -1.0);
+    for (int c = 0; c < nev; ++c)
+      for (int j = 0; j <= k_final; ++j)
+        (*resnorm_history)[(size_t)c * ((size_t)kmax + 1) + j]
+            = hist[(size_t)j * nev + c];
+  }
+  return k_final;
+}
+
+} // namespace spmv

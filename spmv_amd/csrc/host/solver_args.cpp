@@ -173,6 +173,35 @@ void lsqr_check_rules(int kmax, double ltol, double damp, int64_t rows,
     throw std::runtime_error("lsqr: x overlaps b (x is updated in place)");
 }
 
+void lobpcg_check_rules(int nev, int kmax, double rtol, double atol,
+                        bool has_dinv, bool has_sgs, bool has_amg,
+                        int64_t sgs_rows, int64_t sgs_negative_pivots,
+                        int64_t amg_rows, int64_t rows)
+{
+  if (nev < 1 || nev > 8)
+    throw std::runtime_error("spmv::lobpcg - Error: nev must be in 1..8");
+  if (kmax < 0)
+    throw std::runtime_error("spmv::lobpcg - Error: kmax < 0");
+  if (!(rtol >= 0.0) || !std::isfinite(rtol) || !(atol >= 0.0)
+      || !std::isfinite(atol) || (rtol == 0.0 && atol == 0.0))
+    throw std::runtime_error(
+        "spmv::lobpcg - Error: tol: rtol and atol must be finite, not negative "
+        "and not both 0");
+  if ((int)has_dinv + (int)has_sgs + (int)has_amg > 1)
+    throw std::runtime_error(
+        "spmv::lobpcg - Error: one preconditioner at a time (dinv, sgs or amg)");
+  if ((has_sgs && sgs_rows != rows) || (has_amg && amg_rows != rows))
+    throw std::runtime_error(
+        "spmv::lobpcg - Error: the preconditioner was built for "
+        + std::to_string(has_sgs ? sgs_rows : amg_rows)
+        + " rows, the matrix has " + std::to_string(rows));
+  if (has_sgs && sgs_negative_pivots > 0)
+    throw std::runtime_error(
+        "spmv::lobpcg - Error: the preconditioner has "
+        + std::to_string(sgs_negative_pivots)
+        + " negative pivot(s): it is not positive definite");
+}
+
 void amg_check_tail_rows(int64_t max_rows)
 {
   if (max_rows < 0)

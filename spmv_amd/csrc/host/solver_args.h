@@ -70,6 +70,14 @@ void minres_check_rules(int kmax, bool has_dinv, bool has_sgs, bool has_amg,
                         int64_t amg_rows, int64_t rows, const double* b,
                         const double* x, const double* dinv);
 
+// The argument rules of lobpcg() (std::runtime_error), in this order: "nev" not
+// in 1..8, "kmax" < 0, "tol" (rtol and atol finite, >= 0, not both 0), more
+// than one "preconditioner", its "rows", a negative "pivot".
+void lobpcg_check_rules(int nev, int kmax, double rtol, double atol,
+                        bool has_dinv, bool has_sgs, bool has_amg,
+                        int64_t sgs_rows, int64_t sgs_negative_pivots,
+                        int64_t amg_rows, int64_t rows);
+
 // The argument rules of lsqr() (std::runtime_error), in this order: kmax < 0
 // ("kmax"), ltol negative or not finite ("ltol"), damp negative or not finite
 // ("damp"), x (cols doubles) sharing a byte with b (rows doubles) ("overlaps").

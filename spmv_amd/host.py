@@ -219,6 +219,14 @@ _PROTOS = {
                                  i64, i64, vp, vp, vp],
     "spmvh_minres": [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, f64, PTR(C.c_int),
                      PTR(C.c_int), vp, vp, C.c_int, PTR(f64), PTR(C.c_int)],
+    "spmvh_lobpcg_workspace_create": [vp, PTR(vp)],
+    "spmvh_lobpcg_workspace_destroy": [vp],
+    "spmvh_lobpcg_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_lobpcg_check_rules": [C.c_int, C.c_int, f64, f64, C.c_int, C.c_int,
+                                 C.c_int, i64, i64, i64, i64],
+    "spmvh_lobpcg": [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, f64, f64,
+                     PTR(C.c_int), PTR(C.c_int), vp, vp, vp, PTR(C.c_int), vp,
+                     C.c_int, PTR(f64), PTR(C.c_int)],
     "spmvh_lsqr_workspace_create": [vp, PTR(vp)],
     "spmvh_lsqr_workspace_destroy": [vp],
     "spmvh_lsqr_workspace_reserve_timing": [vp, C.c_int],
@@ -1617,6 +1625,53 @@ def lsqr(comm, exec_, A, b_ptr, x_ptr, kmax, rtol, ltol=0.0, damp=0.0, ws=None,
     if stats is not None:
         stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
     return k.value, hist_r[:k.value + 1], hist_ar[:k.value + 1], status.value
+
+
+class LobpcgWorkspace(_TimedWorkspace):
+    """spmv::LobpcgWorkspace: work blocks and device scalars kept across
+    lobpcg() calls."""
+    _prefix = "lobpcg"
+
+
+def lobpcg_check_rules(nev, kmax, rtol=1e-8, atol=0.0, has_dinv=False,
+                       has_sgs=False, has_amg=False, sgs_rows=0,
+                       sgs_negative_pivots=0, amg_rows=0, rows=0):
+    """spmv::lobpcg_check_rules alone (no device); raises SpmvHostError naming
+    the rule."""
+    call("spmvh_lobpcg_check_rules", int(nev), int(kmax), float(rtol),
+         float(atol), int(has_dinv), int(has_sgs), int(has_amg), int(sgs_rows),
+         int(sgs_negative_pivots), int(amg_rows), int(rows))
+
+
+def lobpcg(comm, exec_, A, x_ptr, nev, kmax, rtol, atol=0.0, dinv=None,
+           sgs=None, amg=None, largest=False, workspace=None, time_spmv=False,
+           poll_every=0, stats=None):
+    """spmv::lobpcg: the nev smallest (largest=True: largest) eigenpairs of a
+    symmetric A -> (k, eigenvalues[nev], history[nev, kmax + 1], status).
+    x_ptr: device block of rows * nev doubles (mult_block layout), the initial
+    guess on entry, the Ritz vectors on exit.  At most one of dinv (device
+    pointer, rows doubles), sgs (an SgsPreconditioner or Ilu0Preconditioner)
+    and amg (an AmgPreconditioner).  history: -1.0 beyond the iteration at
+    which a column met rn < max(rtol |theta|, atol).  status: 0, or 1 the basis
+    collapsed (host/cg.h).  stats (optional dict) receives true_resnorm (from
+    A X computed after the loop), restarts, spmv_ms_total and spmv_launches."""
+    nev, kmax = int(nev), int(kmax)
+    k, n, status, restarts = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    ms = f64()
+    eig = np.zeros(max(nev, 1))
+    true_rn = np.zeros(max(nev, 1))
+    hist = np.full((max(nev, 1), max(kmax, 0) + 1), -1.0)
+    call("spmvh_lobpcg", comm.h, exec_.h, A.h, x_ptr, nev, dinv,
+         sgs.h if sgs is not None else None, amg.h if amg is not None else None,
+         kmax, float(rtol), float(atol), C.byref(k), C.byref(status),
+         _np_ptr(eig), _np_ptr(hist), _np_ptr(true_rn), C.byref(restarts),
+         workspace.h if workspace else None,
+         int(bool(time_spmv)) | (int(bool(largest)) << 1)
+         | ((int(poll_every) & 0xff) << 8), C.byref(ms), C.byref(n))
+    if stats is not None:
+        stats.update(true_resnorm=true_rn[:nev].copy(), restarts=restarts.value,
+                     spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, eig[:nev], hist[:nev], status.value
 
 
 def host_executor_rejects_compute():
