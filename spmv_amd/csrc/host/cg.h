@@ -1577,6 +1577,35 @@ public:
 // block is not guaranteed to be refused; it then runs on a basis of rounding
 // noise and usually collapses at a later step.
 //
+// Edges (tests/lobpcg_edges.py, found on the restatement, held on the device):
+//  - Rows.  With local rows = nev the prologue's pairs are exact to rounding and
+//    the solve returns at k = 0, status 0.  With fewer than 3 nev rows [X, W, P]
+//    cannot have full rank: the pivots are rounding noise and the solve usually
+//    ends with status 1 within a few iterations, unless it converges first.
+//    Such a run may also reach kmax with status 0 and Ritz values far outside
+//    the spectrum (diag(1..8), nev 3: theta = -2.5e59): check true_resnorm.
+//  - The test rn_c < max(rtol |theta_c|, atol) is strict.  An exactly converged
+//    pair with theta_c = 0 (rn_c = 0) does not meet it at atol = 0: the column
+//    stays active, W = 0, and the step collapses (status 1); pass atol > 0.
+//  - Scales.  2^s A gives the same X and theta, history times 2^s for
+//    -335 <= s <= 339 without a preconditioner (W = R carries 2^s, W^T A W
+//    2^3s) and for -490 <= s <= 510 with dinv 2^-s; columns of X0 times 2^t
+//    give the same result for -512 <= t <= 507 (x0.x0 = 2^(2t) 443 on the
+//    Poisson matrix of 11^3 rows).  Beyond: status 1 at k = 0 where a Gram sum
+//    overflows; where products underflow, first other bits, further out a
+//    status 1 some iterations later.
+//  - A NaN or Inf in dinv meets the first step's Gram sums: status 1 at k = 0,
+//    and X is the prologue's orthonormalised and rotated block, not the X0
+//    passed in.  A NaN or Inf in X0 returns X0 itself (the first factorisation
+//    fails); an Inf in A returns the orthonormalised X0; an entry of A whose
+//    products overflow (1e200) ends at k = 0 with the prologue's rotated block,
+//    finite theta and true_resnorm = Inf.
+//  - Several ranks take every branch from their own copy of the all-reduced
+//    Gram sums and norms: Comm::reduce_sum must leave the same bits on every
+//    rank (it does on the peer windows and on the transports of this
+//    repository), else one rank restarts or stops alone and the
+//    others wait in the next all-reduce.
+//
 // Returns the number of iterations.  eigenvalues (optional): nev Ritz values.
 // resnorm_history (optional): nev * (kmax + 1) entries, column c at
 // [c * (kmax + 1) + it], -1.0 beyond the iteration at which the column met its
