@@ -1666,6 +1666,38 @@ int spmv_hip_lobpcg_residual_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
                                  int final, void* stream);
 int spmv_hip_lobpcg_norms(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws, int phase,
                           int final, void* stream);
+/* The pencil A x = lambda B x (lobpcg() with B): a third triple BS = [BX, BW,
+ * BP] beside S and AS.  gram_reduce, rr, norms and the workspace are the ones
+ * above; the state words and `done` are honoured alike.
+ *   gram_gen     one pass over the 3 * blocks blocks: Gb = S^T BS, Ga = S^T AS,
+ *                entry (i, j), i <= j, the sum over the rows of s_i * (Bs)_j.
+ *                Tiles, row groups, summation order and the layout of the
+ *                partials are gram's: BX = X, BW = W, BP = P gives gram's bits.
+ *   update_gen   update on the three triples, one triple per thread (the grid's
+ *                y dimension): X' = S C, P' = [W, P] C_wp, likewise for AS and
+ *                BS, in place; each of the nine blocks is read once, each of the
+ *                six outputs written once.  AX == NULL skips the second triple
+ *                (the prologue's X R^-1, BX R^-1).  Every output has the bits
+ *                update gives the same operands.
+ *   residual_gen R = AX - BX diag(theta): residual with BX in X's place (the
+ *                same kernel; W, the partials and final as there) */
+int spmv_hip_lobpcg_gram_gen_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
+                                 int64_t M, int blocks, const double* X,
+                                 const double* W, const double* P,
+                                 const double* AX, const double* AW,
+                                 const double* AP, const double* BX,
+                                 const double* BW, const double* BP,
+                                 void* stream);
+int spmv_hip_lobpcg_update_gen_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
+                                   int64_t M, int blocks, double* X,
+                                   const double* W, double* P, double* AX,
+                                   const double* AW, double* AP, double* BX,
+                                   const double* BW, double* BP, void* stream);
+int spmv_hip_lobpcg_residual_gen_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
+                                     int64_t M, const double* AX,
+                                     const double* BX, const double* dinv,
+                                     double* R, double* W, int final,
+                                     void* stream);
 
 /* ---- Preconditioned MINRES (spmv::minres, host/cg.h) -------------------------
  * Vectors: n doubles, 16-byte aligned.  Every product, sum, difference,

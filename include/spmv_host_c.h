@@ -778,6 +778,23 @@ int spmvh_lobpcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A, double* X,
                  double* eigenvalues, double* resnorm_history,
                  double* true_resnorm, int* restarts, spmvh_lobpcg_workspace* ws,
                  int flags, double* spmv_ms_total, int* spmv_launches);
+/* spmvh_lobpcg_gen: the pencil A x = lambda B x, B symmetric positive definite
+ * with A's rows and A's ghosts (rule "pencil"; B == NULL: spmvh_lobpcg).  X is
+ * B-orthonormal on exit, true_resnorm is ||A x_c - theta_c B x_c||, a B that is
+ * not positive definite ends with *status 1.  Everything else as spmvh_lobpcg.
+ * spmvh_lobpcg_check_pencil: lobpcg_check_pencil of solver_args.h alone (no
+ * device): the local row counts and the ghost lists (global indices) of A and
+ * B. */
+int spmvh_lobpcg_check_pencil(int64_t rows_a, int64_t rows_b,
+                              const int64_t* ghosts_a, int64_t num_ghosts_a,
+                              const int64_t* ghosts_b, int64_t num_ghosts_b);
+int spmvh_lobpcg_gen(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                     spmvh_matrix* B, double* X, int nev, const double* dinv,
+                     spmvh_sgs* sgs, spmvh_amg* amg, int kmax, double rtol,
+                     double atol, int* num_its, int* status, double* eigenvalues,
+                     double* resnorm_history, double* true_resnorm,
+                     int* restarts, spmvh_lobpcg_workspace* ws, int flags,
+                     double* spmv_ms_total, int* spmv_launches);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,14 @@
 //             partials of ||r_c||^2
 //   norms     partials -> ||r_c||, the history, the convergence mask, `done`
 //
+// The pencil A x = lambda B x (lobpcg() with B) adds BS = [BX, BW, BP]:
+//   gram_gen    the gram kernel with the rows staged as [S | AS | BS]:
+//               Gb = S^T BS (entry (i, j), i <= j: the sum of s_i * (Bs)_j), Ga
+//               as before, the partials in the same layout and order, so
+//               gram_reduce and rr read them unchanged and BS = S gives gram's bits
+//   update_gen  the update on three triples, a thread owns a row of one triple
+//   residual    with BX in X's place: R = AX - BX diag(theta)
+//
 // The `done` protocol is minres's: once it is raised every kernel returns at
 // once, so X is exactly the iterate of the returned k.
 //
@@ -124,19 +132,25 @@ __device__ __forceinline__ void stage_block(const double* __restrict__ src,
   }
 }
 
-template <bool NT, bool VEC>
+// GEN: the pencil form.  The rows are staged as [S | AS | BS] and the Gb tiles
+// take their right-hand operand from BS; the tiles, the row groups and the
+// partials are the same, so BS = S gives the bits of the form without B.
+template <bool NT, bool VEC, bool GEN>
 __global__ __launch_bounds__(kBlock) void lobpcg_gram_kernel(
     int64_t M, int k, int nb, const LobpcgState* __restrict__ st,
     const double* __restrict__ S0, const double* __restrict__ S1,
     const double* __restrict__ S2, const double* __restrict__ A0,
     const double* __restrict__ A1, const double* __restrict__ A2,
-    double* __restrict__ partials)
+    const double* __restrict__ B0, const double* __restrict__ B1,
+    const double* __restrict__ B2, double* __restrict__ partials)
 {
-  // the staged rows (kGramRows x 2 mp <= 3072), then the row groups' tiles
-  __shared__ double s_buf[kBlock * 16];
+  // the staged rows (kGramRows x 2 mp <= 3072; GEN: x 3 mp <= 4608), then the
+  // row groups' tiles (<= kBlock * 16)
+  __shared__ double s_buf[GEN ? kGramRows * 3 * kMaxM : kBlock * 16];
   if (st->done)
     return;
-  const int m = nb * k, mt = (m + 3) / 4, mp = 4 * mt, stride = 2 * mp;
+  const int m = nb * k, mt = (m + 3) / 4, mp = 4 * mt;
+  const int stride = (GEN ? 3 : 2) * mp;
   const int nt = mt * (mt + 1) / 2, jobs = 2 * nt, G = kBlock / jobs;
   const int t = threadIdx.x;
   const int job = t % jobs, g = t / jobs; // g == G: a thread without a tile
@@ -147,7 +161,8 @@ __global__ __launch_bounds__(kBlock) void lobpcg_gram_kernel(
     ++ti;
   }
   tj += ti;
-  const int a_off = 4 * ti, b_off = (which ? mp : 0) + 4 * tj;
+  const int a_off = 4 * ti;
+  const int b_off = (which ? mp : GEN ? 2 * mp : 0) + 4 * tj;
 
   // the padding columns stay zero: no load writes them
   for (int i = t; i < kGramRows * stride; i += kBlock)
@@ -167,6 +182,13 @@ __global__ __launch_bounds__(kBlock) void lobpcg_gram_kernel(
     if (nb > 2) {
       stage_block<NT, VEC>(S2, r0, nr, k, s_buf, stride, 2 * k);
       stage_block<NT, VEC>(A2, r0, nr, k, s_buf, stride, mp + 2 * k);
+    }
+    if constexpr (GEN) {
+      stage_block<NT, VEC>(B0, r0, nr, k, s_buf, stride, 2 * mp);
+      if (nb > 1)
+        stage_block<NT, VEC>(B1, r0, nr, k, s_buf, stride, 2 * mp + k);
+      if (nb > 2)
+        stage_block<NT, VEC>(B2, r0, nr, k, s_buf, stride, 2 * mp + 2 * k);
     }
     __syncthreads();
     if (g < G) {
@@ -568,8 +590,51 @@ __global__ __launch_bounds__(kBlock) void lobpcg_update_kernel(
   }
 }
 
+// The pencil form: the triples [X, W, P], [AX, AW, AP], [BX, BW, BP] are
+// independent given C, so blockIdx.y picks one and a thread holds 3 nev values
+// of a row, not 6 nev (or 9 nev).  combine_row is the arithmetic of the kernel
+// above.  A triple whose first block is NULL is skipped.
+struct LobpcgTriples {
+  double* x[3];
+  const double* w[3];
+  double* p[3];
+};
+
+template <int K, bool NT, bool VEC>
+__global__ __launch_bounds__(kBlock) void lobpcg_update_triple_kernel(
+    int64_t M, int nev, int nb, const LobpcgState* __restrict__ st,
+    const double* __restrict__ coef, LobpcgTriples tr)
+{
+  constexpr int KK = K ? K : SPMV_CGB_MAX;
+  __shared__ double s_c[kMaxM * SPMV_CGB_MAX];
+  double* __restrict__ X = tr.x[blockIdx.y];
+  const double* __restrict__ W = tr.w[blockIdx.y];
+  double* __restrict__ P = tr.p[blockIdx.y];
+  if (st->done || !X)
+    return;
+  const int k = K ? K : nev;
+  for (int e = threadIdx.x; e < nb * k * k; e += kBlock)
+    s_c[e] = coef[e];
+  const int basis = st->basis, active = st->active;
+  __syncthreads();
+  SPMV_FOR_ROWS(row, M)
+  {
+    double s[3][KK] = {}, xo[KK], po[KK];
+    load_row<KK, NT, VEC>(X, row, k, s[0]);
+    if (nb == 3) {
+      load_row<KK, NT, VEC>(W, row, k, s[1]);
+      load_row<KK, NT, VEC>(P, row, k, s[2]);
+    }
+    combine_row<KK>(s, k, nb, basis, active, s_c, xo, po);
+    store_row<KK, NT, VEC>(X, row, k, xo);
+    if (nb == 3)
+      store_row<KK, NT, VEC>(P, row, k, po);
+  }
+}
+
 // ---- residual ------------------------------------------------------------------------
-// R = AX - X diag(theta); W (optional) = dinv * R, or R; partials of ||r_c||^2.
+// R = AX - X diag(theta) (the pencil: BX stands in X's place); W (optional) =
+// dinv * R, or R; partials of ||r_c||^2.
 // final: the epilogue's call, which runs although `done` is raised
 template <int K, bool NT, bool VEC>
 __global__ __launch_bounds__(kBlock) void lobpcg_residual_kernel(
@@ -932,10 +997,49 @@ int spmv_hip_lobpcg_gram_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
                                    : aligned16(X, W, P, AX, AW, AP));
   hipStream_t st = spmv_stream(ctx, stream);
   const int grid = gram_grid(ws, M);
+  const double* const none = nullptr;
 #define SPMV_LOBPCG_GRAM(NT, VEC)                                              \
-  hipLaunchKernelGGL((lobpcg_gram_kernel<NT, VEC>), dim3(grid), dim3(kBlock),  \
-                     0, st, M, nev, blocks, ws->st, X, W, P, AX, AW, AP,       \
-                     ws->gpart)
+  hipLaunchKernelGGL((lobpcg_gram_kernel<NT, VEC, false>), dim3(grid),         \
+                     dim3(kBlock), 0, st, M, nev, blocks, ws->st, X, W, P, AX, \
+                     AW, AP, none, none, none, ws->gpart)
+  if (nt && vec)
+    SPMV_LOBPCG_GRAM(true, true);
+  else if (nt)
+    SPMV_LOBPCG_GRAM(true, false);
+  else if (vec)
+    SPMV_LOBPCG_GRAM(false, true);
+  else
+    SPMV_LOBPCG_GRAM(false, false);
+#undef SPMV_LOBPCG_GRAM
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_lobpcg_gram_gen_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
+                                 int64_t M, int blocks, const double* X,
+                                 const double* W, const double* P,
+                                 const double* AX, const double* AW,
+                                 const double* AP, const double* BX,
+                                 const double* BW, const double* BP,
+                                 void* stream)
+{
+  SPMV_LOBPCG_REQUIRE(ctx, ws);
+  SPMV_REQUIRE(M >= 0 && blocks_ok(blocks));
+  SPMV_REQUIRE(M == 0 || (X && AX && BX));
+  SPMV_REQUIRE(M == 0 || blocks == 1 || (W && P && AW && AP && BW && BP));
+  SPMV_SET_DEVICE(ctx);
+  const int nev = ws->nev;
+  const bool nt = M * nev >= ctx->blas1_nt_min_elems;
+  const bool vec
+      = nev % 2 == 0
+        && (blocks == 1 ? aligned16(X, AX, BX)
+                        : aligned16(X, W, P, AX, AW, AP, BX, BW, BP));
+  hipStream_t st = spmv_stream(ctx, stream);
+  const int grid = gram_grid(ws, M);
+#define SPMV_LOBPCG_GRAM(NT, VEC)                                              \
+  hipLaunchKernelGGL((lobpcg_gram_kernel<NT, VEC, true>), dim3(grid),          \
+                     dim3(kBlock), 0, st, M, nev, blocks, ws->st, X, W, P, AX, \
+                     AW, AP, BX, BW, BP, ws->gpart)
   if (nt && vec)
     SPMV_LOBPCG_GRAM(true, true);
   else if (nt)
@@ -1021,6 +1125,44 @@ int spmv_hip_lobpcg_residual_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
                           ctx->dot_blocks);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
+}
+
+int spmv_hip_lobpcg_update_gen_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
+                                   int64_t M, int blocks, double* X,
+                                   const double* W, double* P, double* AX,
+                                   const double* AW, double* AP, double* BX,
+                                   const double* BW, double* BP, void* stream)
+{
+  SPMV_LOBPCG_REQUIRE(ctx, ws);
+  SPMV_REQUIRE(M >= 0 && blocks_ok(blocks));
+  SPMV_REQUIRE(M == 0 || (X && BX));
+  SPMV_REQUIRE(M == 0 || blocks == 1 || (W && P && BW && BP));
+  SPMV_REQUIRE(M == 0 || blocks == 1 || !AX || (AW && AP));
+  SPMV_SET_DEVICE(ctx);
+  const int nev = ws->nev;
+  const bool nt = M * nev >= ctx->blas1_nt_min_elems;
+  bool vec = nev % 2 == 0 && aligned16(X, AX, BX);
+  if (blocks == 3)
+    vec = vec && aligned16(W, P, AW, AP, BW, BP);
+  hipStream_t st = spmv_stream(ctx, stream);
+  const LobpcgTriples tr = {{X, AX, BX}, {W, AW, BW}, {P, AP, BP}};
+  // y: the triple
+  SPMV_LOBPCG_LAUNCH_ROWS(lobpcg_update_triple_kernel, nev, nt, vec,
+                          dim3(rows_grid(ctx, M), 3), st, M, nev, blocks,
+                          ws->st, ws->coef, tr);
+  SPMV_CHECK_LAUNCH();
+  return SPMV_HIP_OK;
+}
+
+// (the residual kernel itself: BX stands where X stands without B)
+int spmv_hip_lobpcg_residual_gen_f64(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws,
+                                     int64_t M, const double* AX,
+                                     const double* BX, const double* dinv,
+                                     double* R, double* W, int final,
+                                     void* stream)
+{
+  return spmv_hip_lobpcg_residual_f64(ctx, ws, M, BX, AX, dinv, R, W, final,
+                                      stream);
 }
 
 int spmv_hip_lobpcg_norms(spmv_hip_ctx* ctx, spmv_hip_lobpcg_ws* ws, int phase,

@@ -2185,12 +2185,38 @@ int spmvh_lobpcg_check_rules(int nev, int kmax, double rtol, double atol,
   });
 }
 
+int spmvh_lobpcg_check_pencil(int64_t rows_a, int64_t rows_b,
+                              const int64_t* ghosts_a, int64_t num_ghosts_a,
+                              const int64_t* ghosts_b, int64_t num_ghosts_b)
+{
+  return guarded([&] {
+    require((ghosts_a || num_ghosts_a <= 0) && (ghosts_b || num_ghosts_b <= 0),
+            "NULL argument");
+    lobpcg_check_pencil(rows_a, rows_b, ghosts_a, num_ghosts_a, ghosts_b,
+                        num_ghosts_b);
+  });
+}
+
 int spmvh_lobpcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A, double* X,
                  int nev, const double* dinv, spmvh_sgs* sgs, spmvh_amg* amg,
                  int kmax, double rtol, double atol, int* num_its, int* status,
                  double* eigenvalues, double* resnorm_history,
                  double* true_resnorm, int* restarts, spmvh_lobpcg_workspace* ws,
                  int flags, double* spmv_ms_total, int* spmv_launches)
+{
+  return spmvh_lobpcg_gen(comm, exec, A, nullptr, X, nev, dinv, sgs, amg, kmax,
+                          rtol, atol, num_its, status, eigenvalues,
+                          resnorm_history, true_resnorm, restarts, ws, flags,
+                          spmv_ms_total, spmv_launches);
+}
+
+int spmvh_lobpcg_gen(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                     spmvh_matrix* B, double* X, int nev, const double* dinv,
+                     spmvh_sgs* sgs, spmvh_amg* amg, int kmax, double rtol,
+                     double atol, int* num_its, int* status, double* eigenvalues,
+                     double* resnorm_history, double* true_resnorm,
+                     int* restarts, spmvh_lobpcg_workspace* ws, int flags,
+                     double* spmv_ms_total, int* spmv_launches)
 {
   return guarded([&] {
     require(comm && exec && A && num_its, "NULL argument");
@@ -2208,7 +2234,8 @@ int spmvh_lobpcg(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A, double* X,
     int how = 0;
     *num_its = lobpcg(*comm->comm, *exec->hip, *A->A, X, nev, pre, kmax, rtol,
                       atol, &eig, resnorm_history ? &hist : nullptr, &how, &opt,
-                      &st, ws ? ws->ws.get() : nullptr);
+                      &st, ws ? ws->ws.get() : nullptr,
+                      B ? B->A.get() : nullptr);
     if (status)
       *status = how;
     if (eigenvalues)

@@ -1501,8 +1501,9 @@ struct LobpcgOptions {
 
 // CgStats plus what the epilogue measured
 struct LobpcgStats : CgStats {
-  // ||A x_c - theta_c x_c|| with AX = A X computed explicitly after the loop
-  // (the loop's AX is updated implicitly and drifts), nev entries
+  // ||A x_c - theta_c x_c|| (with B: ||A x_c - theta_c B x_c||) with AX = A X
+  // (and BX = B X) computed explicitly after the loop (the loop's AX and BX are
+  // updated implicitly and drift), nev entries
   std::vector<double> true_resnorm;
   int restarts = 0; // Rayleigh-Ritz steps repeated without P
 };
@@ -1517,7 +1518,9 @@ public:
   ~LobpcgWorkspace();
 
   // ---- internal to lobpcg() ----
-  void ensure(int64_t m_elems, int64_t n_elems, int kmax, int nev, bool need_x);
+  // with_b: the blocks of a solve with B as well (they stay for later solves)
+  void ensure(int64_t m_elems, int64_t n_elems, int kmax, int nev, bool need_x,
+              bool with_b = false);
   void reserve_timing(int iterations)
   {
     reserve_events(2 * (size_t)std::max(iterations, 0));
@@ -1527,9 +1530,10 @@ public:
   // (flags: {done, kstop, status, it, active, has_p, restarts, basis})
   spmv_hip_lobpcg_ws* ws = nullptr;
   int kmax_cap = -1, nev_cap = 0;
-  int64_t m_cap = -1, n_cap = -1, x_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, x_cap = -1, b_cap = -1;
   double *r = nullptr, *p = nullptr, *ax = nullptr, *aw = nullptr,
          *ap = nullptr;  // m_cap
+  double *bx = nullptr, *bw = nullptr, *bp = nullptr; // b_cap: solves with B
   double* x = nullptr;   // x_cap: the iterate when the caller's X is unaligned
   double* w = nullptr;   // n_cap: padded, the ghost tail is zeroed by every solve
 };
@@ -1624,11 +1628,65 @@ public:
 // exchange of W before mult_block, preconditioners block-Jacobi over the ranks.
 // Launches of one iteration on one rank beside mult_block and M: gram,
 // gram_reduce, rr, update, residual, norms; 6 + 10 + 3 (+1 with W) block passes.
+//
+// B != nullptr: the GENERALISED problem A x = lambda B x, A symmetric, B
+// SYMMETRIC POSITIVE DEFINITE, both fp64, each in either storage (the storages
+// may differ).  The nev smallest (largest) eigenpairs of the pencil; on exit X
+// is B-orthonormal to rounding (X^T B X = I) and the eigenvalues are the Ritz
+// values of the pencil.  M approximates A^-1 as before.  One rounding per
+// operation; k = nev:
+//
+//   prologue: BX = B X (through the padded W, like AX); Gb = X^T BX;
+//             R = chol(Gb); X = X R^-1, BX = BX R^-1 (one update, the same
+//             coefficients: BX is updated implicitly); AX = A X; Rayleigh-Ritz
+//             on (X^T AX, X^T BX); X, AX, BX <- . C
+//   it = 0:   R = AX - BX diag(theta); rn_c = ||r_c||; the test is the one
+//             above, rn_c < max(rtol |theta_c|, atol)
+//   while some column is active and it < kmax:
+//     W  = M^-1 R
+//     one update_block of the padded W, then AW = A W and BW = B W
+//     S  = [X, W_act, P_act], AS and BS likewise
+//     Gb = S^T BS, Ga = S^T AS: one pass over the nine blocks; the upper
+//          triangle entry (i, j), i <= j, is sum_rows s_i * (Bs)_j, in the
+//          summation order of the pass over six blocks
+//     Rayleigh-Ritz on (Ga, Gb): the step above, unchanged (gram_reduce, the
+//          all-reduce of 2 m m doubles, rr)
+//     X' = S C, P' = [W_act, P_act] C_wp, likewise AX', AP' and BX', BP': in
+//          place, each of the nine blocks read once and each of the six
+//          outputs written once (one launch, a thread owns a row of ONE triple)
+//     R = AX - BX diag(theta); rn; hist; the mask; it += 1
+//   epilogue: AX = A X and BX = B X explicitly, R and ||r_c|| from them ->
+//             stats->true_resnorm = ||A x_c - theta_c B x_c||
+//
+// Restarts, the collapse, soft locking, the state words and `done` are exactly
+// those above: they hang off the Rayleigh-Ritz step.  A B that is not positive
+// definite shows up as a Cholesky pivot of Gb that fails piv > 0, and the solve
+// ends with status 1 like a rank-deficient block; NO OTHER TEST of definiteness
+// (or of symmetry) is made, and an indefinite B whose Gb happens to factor is
+// not refused.  With B the identity the solve has the bits of the solve
+// without B: BX then goes through the arithmetic of X.
+//
+// The rule "pencil" (lobpcg_check_pencil of solver_args.h, checked with the
+// other rules before anything touches a device): B has A's local row count and
+// B's column map exactly A's ghost list, the same global indices in the same
+// order -- what two operators assembled on one mesh have.  One halo exchange of
+// the padded W (A's column map) then serves both products: B's product runs
+// behind A's, which waits for the exchange; where B's product comes alone (the
+// prologue's BX = B X) lobpcg() makes the stream wait for A's exchange itself
+// (update_finalise_block), since B's own column map has nothing in flight.
+// Launches of one
+// iteration on one rank beside the two mult_block and M: gram_gen,
+// gram_reduce, rr, update_gen, residual, norms (six, as above); 9 + 15 + 3
+// (+1 with W) block passes.  Several ranks: the same two all-reduces, of the
+// same sizes.  options->time_spmv brackets A's product alone.  The workspace
+// grows bx, bw, bp at the first solve with B and may alternate between solves
+// with and without B.
 int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
            double* X, int nev, const BlockPreconditioner& M, int kmax,
            double rtol, double atol, std::vector<double>* eigenvalues = nullptr,
            std::vector<double>* resnorm_history = nullptr, int* status = nullptr,
            const LobpcgOptions* options = nullptr, LobpcgStats* stats = nullptr,
-           LobpcgWorkspace* workspace = nullptr);
+           LobpcgWorkspace* workspace = nullptr,
+           const Matrix<double>* B = nullptr);
 
 } // namespace spmv

@@ -20,6 +20,17 @@ using namespace detail;
 //       Gram(six blocks) ; rr ; update ; residual (+ W) ; norms
 //     epilogue: W = X ; halo ; AW = A W ; residual(final) ; norms(final) ; the
 //       history, copy back of an unaligned X, sync, times
+// With B (the pencil): Gram is gram_gen over [S | AS | BS], update is
+// update_gen over the three triples, BX stands in X's place in the residual:
+//     prologue: ... BP = 0
+//       W = X ; halo ; BX = B W
+//       Gram(X, BX) ; rr(orth) ; update(X, BX)           X = X R^-1, BX likewise
+//       W = X ; halo ; AX = A W
+//       Gram(X, AX, BX) ; rr ; update(X, AX, BX)
+//       residual (+ W) ; norms
+//     it: ... halo of W ; AW = A W ; BW = B W ; Gram(nine blocks) ; rr ; update ;
+//       residual (+ W) ; norms
+//     epilogue: W = X ; halo ; AW = A W ; BW = B W ; residual(final) ; ...
 // ---------------------------------------------------------------------------
 LobpcgWorkspace::~LobpcgWorkspace() { release(); }
 
@@ -28,14 +39,14 @@ void LobpcgWorkspace::release()
   release_common();
   spmv_hip_lobpcg_ws_destroy(ws);
   ws = nullptr;
-  free_vectors({&r, &p, &ax, &aw, &ap, &x, &w});
+  free_vectors({&r, &p, &ax, &aw, &ap, &x, &w, &bx, &bw, &bp});
   kmax_cap = -1;
   nev_cap = 0;
-  m_cap = n_cap = x_cap = -1;
+  m_cap = n_cap = x_cap = b_cap = -1;
 }
 
 void LobpcgWorkspace::ensure(int64_t m_elems, int64_t n_elems, int kmax, int nev,
-                             bool need_x)
+                             bool need_x, bool with_b)
 {
   open(SPMV_HIP_LOBPCG_STATE_WORDS);
   if (kmax > kmax_cap || nev != nev_cap) {
@@ -54,6 +65,8 @@ void LobpcgWorkspace::ensure(int64_t m_elems, int64_t n_elems, int kmax, int nev
   if (need_x)
     regrow(x_cap, m_elems, {&x});
   regrow(n_cap, n_elems, {&w});
+  if (with_b)
+    regrow(b_cap, m_elems, {&bx, &bw, &bp});
 }
 
 int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
@@ -61,7 +74,7 @@ int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
            double rtol, double atol, std::vector<double>* eigenvalues,
            std::vector<double>* resnorm_history, int* status,
            const LobpcgOptions* options, LobpcgStats* stats,
-           LobpcgWorkspace* workspace)
+           LobpcgWorkspace* workspace, const Matrix<double>* B)
 {
   // plain argument rules first: nothing below has touched a device yet
   const int64_t rows = A.row_map()->local_size();
@@ -69,7 +82,16 @@ int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
                      M.amg != nullptr, M.sgs ? M.sgs->rows() : 0,
                      M.sgs ? M.sgs->negative_pivots() : 0,
                      M.amg ? M.amg->rows(0) : 0, rows);
+  const bool gen = B != nullptr;
+  if (gen) {
+    const std::vector<std::int64_t>& ga = A.col_map()->ghosts();
+    const std::vector<std::int64_t>& gb = B->col_map()->ghosts();
+    lobpcg_check_pencil(rows, B->row_map()->local_size(), ga.data(),
+                        (int64_t)ga.size(), gb.data(), (int64_t)gb.size());
+  }
   const Dims dims = check_problem("lobpcg", A, kmax);
+  if (gen)
+    check_problem("lobpcg", *B, kmax); // (no ghost rows in B either)
   const int64_t M_rows = dims.M;
   const int64_t m_elems = M_rows * nev, n_elems = dims.N_padded * nev;
   const std::shared_ptr<const L2GMap>& col_l2g = dims.col_l2g;
@@ -81,7 +103,7 @@ int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   LobpcgWorkspace own(exec);
   LobpcgWorkspace& w = workspace ? *workspace : own;
   const bool x_aligned = is_aligned16(X);
-  w.ensure(m_elems, n_elems, kmax, nev, !x_aligned);
+  w.ensure(m_elems, n_elems, kmax, nev, !x_aligned, gen);
   if (opt.time_spmv)
     w.reserve_timing(kmax);
 
@@ -108,14 +130,22 @@ int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
     exec.memset<double>(w.w + m_elems, 0, n_elems - m_elems);
   exec.memset<double>(w.p, 0, m_elems);
   exec.memset<double>(w.ap, 0, m_elems);
+  if (gen)
+    exec.memset<double>(w.bp, 0, m_elems);
   for (int i = 0; i < SPMV_HIP_LOBPCG_STATE_WORDS; ++i)
     w.flags[i] = 0;
 
   // Gram sums of `blocks` blocks, then the one-workgroup step on them
   auto gram_rr = [&](int blocks, const double* ax, int mode, int advance) {
-    throw_on_error(spmv_hip_lobpcg_gram_f64(ctx, w.ws, M_rows, blocks, Xi, w.w,
-                                            w.p, ax, w.aw, w.ap, nullptr),
-                   "spmv_hip_lobpcg_gram_f64");
+    if (gen)
+      throw_on_error(spmv_hip_lobpcg_gram_gen_f64(ctx, w.ws, M_rows, blocks, Xi,
+                                                  w.w, w.p, ax, w.aw, w.ap, w.bx,
+                                                  w.bw, w.bp, nullptr),
+                     "spmv_hip_lobpcg_gram_gen_f64");
+    else
+      throw_on_error(spmv_hip_lobpcg_gram_f64(ctx, w.ws, M_rows, blocks, Xi, w.w,
+                                              w.p, ax, w.aw, w.ap, nullptr),
+                     "spmv_hip_lobpcg_gram_f64");
     // (one thread per entry: the rr kernel's one wave would walk the partials
     // of 18 entries per lane one after the other)
     throw_on_error(spmv_hip_lobpcg_gram_reduce(ctx, w.ws, M_rows, blocks,
@@ -129,10 +159,11 @@ int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
                                       advance, nullptr),
                    "spmv_hip_lobpcg_rr");
   };
-  // R = AX - X diag(theta) (+ W where that is no call of its own), the norms
-  auto residual_norms = [&](const double* ax, int final) {
+  // R = AX - X diag(theta) (+ W where that is no call of its own), the norms;
+  // bx (the pencil): R = AX - BX diag(theta)
+  auto residual_norms = [&](const double* ax, const double* bx, int final) {
     throw_on_error(spmv_hip_lobpcg_residual_f64(
-                       ctx, w.ws, M_rows, Xi, ax, M.dinv, w.r,
+                       ctx, w.ws, M_rows, bx ? bx : Xi, ax, M.dinv, w.r,
                        final || applied ? nullptr : w.w, final, nullptr),
                    "spmv_hip_lobpcg_residual_f64");
     if (several) {
@@ -149,24 +180,42 @@ int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   };
   // out = A X through the padded block W (not guarded by the state: what it
   // leaves after `done` is not used)
-  auto mult_x = [&](double* out) {
+  // out_b (the pencil): B X as well, from the same exchange.  The exchange
+  // runs on A's column map; with an overlapping model only A's product waits
+  // for it (B's own map has nothing in flight), so B's product alone is put
+  // behind it here
+  auto mult_x = [&](double* out_a, double* out_b) {
     exec.copy<double>(w.w, Xi, m_elems);
     col_l2g->update_block(w.w, nev);
-    A.mult_block(w.w, out, nev, nullptr);
+    if (out_a)
+      A.mult_block(w.w, out_a, nev, nullptr);
+    else
+      col_l2g->update_finalise_block(w.w, nev);
+    if (out_b)
+      B->mult_block(w.w, out_b, nev, nullptr);
+  };
+  // the one-block update of the prologue; ax: AX as well
+  auto update_x = [&](double* ax) {
+    if (gen)
+      throw_on_error(spmv_hip_lobpcg_update_gen_f64(
+                         ctx, w.ws, M_rows, 1, Xi, nullptr, nullptr, ax, nullptr,
+                         nullptr, w.bx, nullptr, nullptr, nullptr),
+                     "spmv_hip_lobpcg_update_gen_f64");
+    else
+      throw_on_error(spmv_hip_lobpcg_update_f64(ctx, w.ws, M_rows, 1, Xi,
+                                                nullptr, nullptr, ax, nullptr,
+                                                nullptr, nullptr),
+                     "spmv_hip_lobpcg_update_f64");
   };
 
-  gram_rr(1, Xi, 1, 0);
-  throw_on_error(spmv_hip_lobpcg_update_f64(ctx, w.ws, M_rows, 1, Xi, nullptr,
-                                            nullptr, nullptr, nullptr, nullptr,
-                                            nullptr),
-                 "spmv_hip_lobpcg_update_f64");
-  mult_x(w.ax);
+  if (gen)
+    mult_x(nullptr, w.bx);
+  gram_rr(1, gen ? w.bx : Xi, 1, 0); // (mode 1 reads Gb alone)
+  update_x(nullptr);
+  mult_x(w.ax, nullptr);
   gram_rr(1, w.ax, 0, 0);
-  throw_on_error(spmv_hip_lobpcg_update_f64(ctx, w.ws, M_rows, 1, Xi, nullptr,
-                                            nullptr, w.ax, nullptr, nullptr,
-                                            nullptr),
-                 "spmv_hip_lobpcg_update_f64");
-  residual_norms(w.ax, 0);
+  update_x(w.ax);
+  residual_norms(w.ax, gen ? w.bx : nullptr, 0);
 
   auto read = [&](double* h, size_t n) {
     throw_on_error(spmv_hip_lobpcg_ws_read_async(w.ws, w.flags, h, n, nullptr,
@@ -190,17 +239,25 @@ int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
       exec.record_event(timing_ev[2 * (size_t)(k - 1)], w.stream);
     }
     A.mult_block(w.w, w.aw, nev, ev1);
+    if (gen) // (behind A's product, which waited for the halo of W)
+      B->mult_block(w.w, w.bw, nev, nullptr);
     gram_rr(3, w.ax, 0, 1);
-    throw_on_error(spmv_hip_lobpcg_update_f64(ctx, w.ws, M_rows, 3, Xi, w.w, w.p,
-                                              w.ax, w.aw, w.ap, nullptr),
-                   "spmv_hip_lobpcg_update_f64");
-    residual_norms(w.ax, 0);
+    if (gen)
+      throw_on_error(spmv_hip_lobpcg_update_gen_f64(
+                         ctx, w.ws, M_rows, 3, Xi, w.w, w.p, w.ax, w.aw, w.ap,
+                         w.bx, w.bw, w.bp, nullptr),
+                     "spmv_hip_lobpcg_update_gen_f64");
+    else
+      throw_on_error(spmv_hip_lobpcg_update_f64(ctx, w.ws, M_rows, 3, Xi, w.w,
+                                                w.p, w.ax, w.aw, w.ap, nullptr),
+                     "spmv_hip_lobpcg_update_f64");
+    residual_norms(w.ax, gen ? w.bx : nullptr, 0);
     poll.step(k, read);
   }
 
-  // the true residuals: AX from X itself
-  mult_x(w.aw);
-  residual_norms(w.aw, 1);
+  // the true residuals: AX (and BX) from X itself
+  mult_x(w.aw, gen ? w.bw : nullptr);
+  residual_norms(w.aw, gen ? w.bw : nullptr, 1);
 
   int cap = 0, cap_nev = 0;
   throw_on_error(spmv_hip_lobpcg_ws_capacity(w.ws, &cap, &cap_nev),

@@ -202,6 +202,27 @@ void lobpcg_check_rules(int nev, int kmax, double rtol, double atol,
         + " negative pivot(s): it is not positive definite");
 }
 
+void lobpcg_check_pencil(int64_t rows_a, int64_t rows_b, const int64_t* ghosts_a,
+                         int64_t num_ghosts_a, const int64_t* ghosts_b,
+                         int64_t num_ghosts_b)
+{
+  if (rows_a != rows_b)
+    throw std::runtime_error("spmv::lobpcg - Error: pencil: B has "
+                             + std::to_string(rows_b) + " local rows, A has "
+                             + std::to_string(rows_a));
+  if (num_ghosts_a != num_ghosts_b)
+    throw std::runtime_error("spmv::lobpcg - Error: pencil: B has "
+                             + std::to_string(num_ghosts_b) + " ghosts, A has "
+                             + std::to_string(num_ghosts_a));
+  for (int64_t i = 0; i < num_ghosts_a; ++i)
+    if (ghosts_a[i] != ghosts_b[i])
+      throw std::runtime_error(
+          "spmv::lobpcg - Error: pencil: ghost " + std::to_string(i) + " of B is "
+          + std::to_string(ghosts_b[i]) + ", of A "
+          + std::to_string(ghosts_a[i])
+          + " (B must have A's ghosts in A's order)");
+}
+
 void amg_check_tail_rows(int64_t max_rows)
 {
   if (max_rows < 0)

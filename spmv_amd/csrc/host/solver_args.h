@@ -77,6 +77,14 @@ void lobpcg_check_rules(int nev, int kmax, double rtol, double atol,
                         bool has_dinv, bool has_sgs, bool has_amg,
                         int64_t sgs_rows, int64_t sgs_negative_pivots,
                         int64_t amg_rows, int64_t rows);
+// The rule "pencil" of lobpcg() with B (std::runtime_error): B has A's local
+// row count, and B's column map has exactly A's ghost list, the same global
+// indices in the same order (two operators assembled on one mesh), so that one
+// halo exchange of the padded W serves both products.  The lists are read,
+// nothing else; a list of length 0 may be NULL.
+void lobpcg_check_pencil(int64_t rows_a, int64_t rows_b, const int64_t* ghosts_a,
+                         int64_t num_ghosts_a, const int64_t* ghosts_b,
+                         int64_t num_ghosts_b);
 
 // The argument rules of lsqr() (std::runtime_error), in this order: kmax < 0
 // ("kmax"), ltol negative or not finite ("ltol"), damp negative or not finite

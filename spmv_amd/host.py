@@ -227,6 +227,10 @@ _PROTOS = {
     "spmvh_lobpcg": [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, f64, f64,
                      PTR(C.c_int), PTR(C.c_int), vp, vp, vp, PTR(C.c_int), vp,
                      C.c_int, PTR(f64), PTR(C.c_int)],
+    "spmvh_lobpcg_check_pencil": [i64, i64, vp, i64, vp, i64],
+    "spmvh_lobpcg_gen": [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, f64,
+                         f64, PTR(C.c_int), PTR(C.c_int), vp, vp, vp,
+                         PTR(C.c_int), vp, C.c_int, PTR(f64), PTR(C.c_int)],
     "spmvh_lsqr_workspace_create": [vp, PTR(vp)],
     "spmvh_lsqr_workspace_destroy": [vp],
     "spmvh_lsqr_workspace_reserve_timing": [vp, C.c_int],
@@ -1643,11 +1647,25 @@ def lobpcg_check_rules(nev, kmax, rtol=1e-8, atol=0.0, has_dinv=False,
          int(sgs_negative_pivots), int(amg_rows), int(rows))
 
 
+def lobpcg_check_pencil(rows_a, rows_b, ghosts_a=(), ghosts_b=()):
+    """spmv::lobpcg_check_pencil alone (no device): B must have A's local row
+    count and exactly A's ghost list (global indices, same order); raises
+    SpmvHostError naming the rule "pencil"."""
+    ga = np.ascontiguousarray(ghosts_a, np.int64)
+    gb = np.ascontiguousarray(ghosts_b, np.int64)
+    call("spmvh_lobpcg_check_pencil", int(rows_a), int(rows_b), _np_ptr(ga),
+         ga.size, _np_ptr(gb), gb.size)
+
+
 def lobpcg(comm, exec_, A, x_ptr, nev, kmax, rtol, atol=0.0, dinv=None,
            sgs=None, amg=None, largest=False, workspace=None, time_spmv=False,
-           poll_every=0, stats=None):
+           poll_every=0, stats=None, B=None):
     """spmv::lobpcg: the nev smallest (largest=True: largest) eigenpairs of a
     symmetric A -> (k, eigenvalues[nev], history[nev, kmax + 1], status).
+    B (optional, a Matrix): the pencil A x = lambda B x with a symmetric
+    positive definite B that has A's rows and A's ghosts (rule "pencil"); X is
+    then B-orthonormal on exit, the residual is A x - theta B x, and a B that
+    is not positive definite ends with status 1.
     x_ptr: device block of rows * nev doubles (mult_block layout), the initial
     guess on entry, the Ritz vectors on exit.  At most one of dinv (device
     pointer, rows doubles), sgs (an SgsPreconditioner or Ilu0Preconditioner)
@@ -1661,7 +1679,9 @@ def lobpcg(comm, exec_, A, x_ptr, nev, kmax, rtol, atol=0.0, dinv=None,
     eig = np.zeros(max(nev, 1))
     true_rn = np.zeros(max(nev, 1))
     hist = np.full((max(nev, 1), max(kmax, 0) + 1), -1.0)
-    call("spmvh_lobpcg", comm.h, exec_.h, A.h, x_ptr, nev, dinv,
+    entry = ("spmvh_lobpcg", comm.h, exec_.h, A.h) if B is None else (
+        "spmvh_lobpcg_gen", comm.h, exec_.h, A.h, B.h)
+    call(*entry, x_ptr, nev, dinv,
          sgs.h if sgs is not None else None, amg.h if amg is not None else None,
          kmax, float(rtol), float(atol), C.byref(k), C.byref(status),
          _np_ptr(eig), _np_ptr(hist), _np_ptr(true_rn), C.byref(restarts),

@@ -18,6 +18,21 @@ One JSON record per case (none, jacobi, sgs, amg):
            blocks read) and update (6 read, 4 written) kernels the achieved
            bytes per second
 
+    python tools/lobpcgbench.py --mass     # -> profiles/lobpcgbench_gen.json
+
+`--mass`: the same cases once more in the same process with a mass-like B on A's
+pattern (1.1 on the diagonal, 0.1 beside it), the pencil A x = lambda B x.  Each
+record then also has
+
+  solve_gen, step_gen   as solve and step, with B; step_gen adds mult_block(B)
+           (B.mult_block launched `--launches` times on its own) beside
+           mult_block(A) from time_spmv
+  kernels  (case none only) the nine-block Gram kernel (9 blocks read) and the
+           three-triple update (9 read, 6 written) with their bytes per second,
+           beside the six-block kernels' figures from the same process, and
+           split_gen_ms: one iteration with B as mult_block(A), mult_block(B),
+           Gram (+ reducer), Rayleigh-Ritz, update and residual (+ norms)
+
 The driver starts one child process per case under `timeout` and stops at the
 first child that fails, so trouble in one case ends the run.
 """
@@ -64,6 +79,12 @@ def run_case(case, args):
     ws.reserve_timing(max(args.iters, args.kmax))
     rec = dict(case=case, n=args.n, rows=rows, nev=nev, nnz=A.non_zeros())
 
+    B = None
+    if args.mass:
+        vb = np.where(ci == np.repeat(np.arange(rows), np.diff(rp)), 1.1, 0.1)
+        B = host.Matrix.create_matrix(comm, exec_, rp, ci, vb, rows, rows, [], [],
+                                      False, host.P2P_BLOCKING)
+
     def solve(kmax, rtol, **kw):
         exec_.copy_from_host(d_x, X0)
         exec_.synchronize()
@@ -73,37 +94,48 @@ def run_case(case, args):
                                              workspace=ws, stats=st, **pre, **kw)
         return (time.perf_counter() - t0) * 1e3, k, theta, status, st
 
-    solve(2, 1e-30)  # warm-up: plans, workspace
-    ms, k, theta, status, st = solve(args.kmax, args.rtol)
-    rec["solve"] = dict(rtol=args.rtol, kmax=args.kmax, iterations=k,
-                        status=status, ms=ms, theta=theta.tolist(),
-                        true_resnorm=st["true_resnorm"].tolist(),
-                        restarts=st["restarts"])
-    best = min(solve(args.iters, 1e-30)[0] for _ in range(args.repeats))
-    _, k2, _, _, st = solve(args.iters, 1e-30, time_spmv=True)
-    rec["step"] = dict(iters=k2, ms_per_iteration=best / max(k2, 1),
-                       mult_block_ms=st["spmv_ms_total"]
-                       / max(st["spmv_launches"], 1))
+    def per_launch(fn):
+        fn()
+        exec_.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.launches):
+            fn()
+        exec_.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / args.launches
+
+    for tag, kw in (("", {}),) + ((("_gen", dict(B=B)),) if B is not None else ()):
+        solve(2, 1e-30, **kw)  # warm-up: plans, workspace
+        ms, k, theta, status, st = solve(args.kmax, args.rtol, **kw)
+        rec["solve" + tag] = dict(rtol=args.rtol, kmax=args.kmax, iterations=k,
+                                  status=status, ms=ms, theta=theta.tolist(),
+                                  true_resnorm=st["true_resnorm"].tolist(),
+                                  restarts=st["restarts"])
+        best = min(solve(args.iters, 1e-30, **kw)[0]
+                   for _ in range(args.repeats))
+        _, k2, _, _, st = solve(args.iters, 1e-30, time_spmv=True, **kw)
+        rec["step" + tag] = dict(iters=k2, ms_per_iteration=best / max(k2, 1),
+                                 mult_block_ms=st["spmv_ms_total"]
+                                 / max(st["spmv_launches"], 1))
+    if B is not None:
+        d_in, d_out = exec_.alloc(rows * nev), exec_.alloc(rows * nev)
+        exec_.copy_from_host(d_in, X0)
+        rec["step_gen"]["mult_block_b_ms"] = per_launch(
+            lambda: B.mult_block(d_in, d_out, nev))
+        rec["step_gen"]["mult_block_a_alone_ms"] = per_launch(
+            lambda: A.mult_block(d_in, d_out, nev))
+        exec_.free(d_in)
+        exec_.free(d_out)
 
     if case == "none":
         ctx = exec_.context
         h = C.c_void_p()
         _lib.call("spmv_hip_lobpcg_ws_create", ctx, 4, nev, C.byref(h))
-        blocks = [exec_.alloc(rows * nev) for _ in range(7)]
+        blocks = [exec_.alloc(rows * nev) for _ in range(10)]
         rng = np.random.default_rng(2)
         for b in blocks:  # independent blocks: the Rayleigh-Ritz step succeeds
             exec_.copy_from_host(b, rng.uniform(-1.0, 1.0, (rows, nev)))
 
-        def per_launch(fn):
-            fn()
-            exec_.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(args.launches):
-                fn()
-            exec_.synchronize()
-            return (time.perf_counter() - t0) * 1e3 / args.launches
-
-        X, W, P, AX, AW, AP, R = blocks
+        X, W, P, AX, AW, AP, R, BX, BW, BP = blocks
         _lib.call("spmv_hip_lobpcg_ws_reset", h, 1e-30, 0.0, 4, 0, None)
         nbytes = rows * nev * 8
         kern = {}
@@ -132,6 +164,37 @@ def run_case(case, args):
         kern["residual_ms"] = per_launch(lambda: _lib.call(
             "spmv_hip_lobpcg_residual_f64", ctx, h, rows, X, AX, None, R, W, 0,
             None))
+        if B is not None:
+            kern["norms_ms"] = per_launch(lambda: _lib.call(
+                "spmv_hip_lobpcg_norms", ctx, h, 0, 1, None))
+            kern["gram_gen_ms"] = per_launch(lambda: _lib.call(
+                "spmv_hip_lobpcg_gram_gen_f64", ctx, h, rows, 3, X, W, P, AX, AW,
+                AP, BX, BW, BP, None))
+            kern["gram_gen_bytes_per_s"] = 9 * nbytes / (kern["gram_gen_ms"] * 1e-3)
+            _lib.call("spmv_hip_lobpcg_gram_f64", ctx, h, rows, 3, X, W, P, AX, AW,
+                      AP, None)  # (finite coefficients again for the update)
+            _lib.call("spmv_hip_lobpcg_gram_reduce", ctx, h, rows, 3, None)
+            rr()
+            kern["update_gen_ms"] = per_launch(lambda: _lib.call(
+                "spmv_hip_lobpcg_update_gen_f64", ctx, h, rows, 3, X, W, P, AX, AW,
+                AP, BX, BW, BP, None))
+            kern["update_gen_bytes_per_s"] = (15 * nbytes
+                                              / (kern["update_gen_ms"] * 1e-3))
+            kern["residual_gen_ms"] = per_launch(lambda: _lib.call(
+                "spmv_hip_lobpcg_residual_gen_f64", ctx, h, rows, AX, BX, None, R,
+                W, 0, None))
+            g = rec["step_gen"]
+            kern["split_gen_ms"] = dict(
+                mult_block_a=g["mult_block_a_alone_ms"],
+                mult_block_b=g["mult_block_b_ms"],
+                gram=kern["gram_gen_ms"] + kern["gram_reduce_ms"],
+                rayleigh_ritz=kern["rr_ms"], update=kern["update_gen_ms"],
+                residual=kern["residual_gen_ms"] + kern["norms_ms"])
+            kern["split_ms"] = dict(
+                mult_block_a=g["mult_block_a_alone_ms"],
+                gram=kern["gram_ms"] + kern["gram_reduce_ms"],
+                rayleigh_ritz=kern["rr_ms"], update=kern["update_ms"],
+                residual=kern["residual_ms"] + kern["norms_ms"])
         sgs = host.SgsPreconditioner(exec_, A)
         kern["sgs_apply_block_ms"] = per_launch(
             lambda: host.sgs_apply_block(exec_, sgs, R, W, nev))
@@ -151,6 +214,8 @@ def run_case(case, args):
         M.close()
     exec_.free(d_x)
     exec_.free(d_dinv)
+    if B is not None:
+        B.close()
     A.close()
     comm.close()
     exec_.close()
@@ -168,10 +233,16 @@ def main():
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--only", default=None, help="comma list of cases")
     ap.add_argument("--timeout", type=int, default=300, help="seconds per case")
-    ap.add_argument("--out",
-                    default=os.path.join(ROOT, "profiles", "lobpcgbench.json"))
+    ap.add_argument("--mass", action="store_true",
+                    help="also the pencil with a mass-like B on A's pattern")
+    ap.add_argument("--out", default=None,
+                    help="default: profiles/lobpcgbench.json "
+                         "(--mass: profiles/lobpcgbench_gen.json)")
     ap.add_argument("--case", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "lobpcgbench_gen.json"
+                                if args.mass else "lobpcgbench.json")
     if args.case:  # a child: one case in this process
         run_case(args.case, args)
         return 0
@@ -183,6 +254,8 @@ def main():
                os.path.abspath(__file__), "--case", case]
         for key in ("n", "nev", "iters", "kmax", "rtol", "repeats", "launches"):
             cmd += ["--" + key, str(getattr(args, key))]
+        if args.mass:
+            cmd.append("--mass")
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(p.stdout)
         sys.stdout.flush()

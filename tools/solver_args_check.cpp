@@ -13,7 +13,9 @@
 // gmres_basis_elems is stride * (restart + 1) and refuses a product that does
 // not fit; chebyshev_coefficients fills exactly `degree` entries (the arrays
 // here are exactly that long, so a write past them is the sanitizer's to find)
-// with the recurrence of cg.h, and refuses its bad arguments.
+// with the recurrence of cg.h, and refuses its bad arguments;
+// lobpcg_check_pencil accepts equal row counts and ghost lists and names
+// "pencil" for every difference, reading exactly the announced lengths.
 // Exit status 0 and "solver_args_check: OK" when everything holds.
 #include <cmath>
 #include <cstdint>
@@ -154,6 +156,30 @@ void chebyshev()
              "NULL"),
          "NULL b");
 }
+// lobpcg_check_pencil: the ghost lists are exactly as long as announced, on the
+// heap (reading past them is the sanitizer's to find); lists of length 0 are NULL
+void pencil()
+{
+  auto r = [](int64_t ra, int64_t rb, const std::vector<int64_t>& a,
+              const std::vector<int64_t>& b) {
+    return raised([&] {
+      lobpcg_check_pencil(ra, rb, a.empty() ? nullptr : a.data(),
+                          (int64_t)a.size(), b.empty() ? nullptr : b.data(),
+                          (int64_t)b.size());
+    });
+  };
+  expect(r(5, 5, {}, {}).empty(), "pencil: no ghosts");
+  expect(r(0, 0, {}, {}).empty(), "pencil: no rows");
+  expect(r(5, 5, {7, 9, 12}, {7, 9, 12}).empty(), "pencil: the same ghosts");
+  expect(has(r(5, 4, {}, {}), "pencil"), "pencil: rows");
+  expect(has(r(5, 5, {7, 9, 12}, {7, 9}), "pencil"), "pencil: a missing ghost");
+  expect(has(r(5, 5, {7, 9}, {7, 9, 12}), "pencil"), "pencil: one too many");
+  expect(has(r(5, 5, {}, {3}), "pencil"), "pencil: ghosts against none");
+  expect(has(r(5, 5, {7, 9, 12}, {7, 12, 9}), "pencil"), "pencil: permuted");
+  expect(has(r(5, 5, {7, 9, 12}, {7, 9, 13}), "pencil"), "pencil: another ghost");
+  // the rows come first
+  expect(has(r(5, 4, {7}, {8, 9}), "local rows"), "pencil: order");
+}
 } // namespace
 
 int main()
@@ -161,6 +187,7 @@ int main()
   rules();
   sizes();
   chebyshev();
+  pencil();
   if (failures) {
     std::printf("solver_args_check: %d FAILED\n", failures);
     return 1;
