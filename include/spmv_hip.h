@@ -1872,6 +1872,94 @@ int spmv_hip_lsqr_update_xw_f64(spmv_hip_ctx* ctx, spmv_hip_lsqr_ws* ws, int k,
                                 int64_t n, const double* vt, double* w,
                                 double* x, void* stream);
 
+/* ---- multi-shift CG (spmv::cg_shifted, host/cg.h) ------------------------------
+ * (A + sigma_s I) x_s = b for s < ns <= SPMV_HIP_CGS_MAX_NS on the Krylov space
+ * of the seed A.  Vectors: doubles at any 8-byte aligned address; where every
+ * vector of a call is 16-byte aligned (and the column strides are even) the
+ * kernels use 16-byte accesses, otherwise pairs of 8-byte ones, with the same
+ * bits.  x_s = X + s * ldx and p_s = PS + s * ldp are contiguous vectors.
+ * Every product, sum, difference, quotient and square root is one rounding.
+ * One iteration (the recurrence is spelled out in host/cg.h):
+ *   q = A p with the partials of p.q in PART_PQ (+ a second array: the remote
+ *   block's share) ; [several ranks: reduce(PQ) ; all-reduce of the slot] ;
+ *   update_r ; [reduce(RRN) ; all-reduce of the slot] ; step ; update_xp(k)
+ * and once in front: spmv_hip_dot_partial_f64(r, r) into PART_RRN ;
+ * [reduce(RRN) ; all-reduce] ; start.
+ * Device state of a workspace: the 48 doubles of SPMV_HIP_CGS_SCALARS, in this
+ * order: rtol, pq, rrn, rr, a_old, b_old, bn, hist0, then 8 each of sigma, zeta,
+ * rho, cx (= a * rho_n), cp (= bn * rho_n^2); the 32 words of get_words: done,
+ * kstop, status (0 converged / kmax / running, 1 p.q was not positive),
+ * its[8], k (steps completed), kmax, ns, n_act, n_upd, act[8] (the shifts the
+ * next step moves, ascending), upd[8] (the shifts the last step moved: s, or
+ * s | 8 where p_s moves too); hist_s[0..kmax] at s * (capacity + 1); two
+ * partial arrays of spmv_hip_dot_partials_len() doubles.
+ * `done` is raised by start or step; after it update_r, reduce, start and step
+ * return at once.  update_xp(k) runs only while the state's k equals its own:
+ * the step that stopped still gets its x updates, once; nothing afterwards
+ * writes X, PS, p, the histories or k. */
+typedef struct spmv_hip_cgs_ws spmv_hip_cgs_ws; /* cg_shifted() scalars */
+#define SPMV_HIP_CGS_MAX_NS 8
+/* {done, kstop, status, its[8]}: what read_async copies */
+#define SPMV_HIP_CGS_STATE_WORDS (3 + SPMV_HIP_CGS_MAX_NS)
+#define SPMV_HIP_CGS_WORDS 32
+enum {
+  SPMV_HIP_CGS_PQ = 0,       /* 1: p.q where a reducer (or update_r) put it    */
+  SPMV_HIP_CGS_RRN = 1,      /* 1: r.r where a reducer (or start / step) put it */
+  SPMV_HIP_CGS_HIST = 2,     /* 8 * (capacity + 1)                             */
+  SPMV_HIP_CGS_PART_PQ = 3,  /* dot_partials_len                               */
+  SPMV_HIP_CGS_PART_RRN = 4, /* dot_partials_len                               */
+  SPMV_HIP_CGS_SCALARS = 5   /* 48: see above (tests read and install them)    */
+};
+int spmv_hip_cgs_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_cgs_ws** ws);
+int spmv_hip_cgs_ws_destroy(spmv_hip_cgs_ws* ws);
+/* kmax <= the capacity, 1 <= ns <= 8, host_shifts: ns doubles on the host
+ * (copied before the call returns); the state in front of start: zeta = rho =
+ * 1, a_old = 1, b_old = 0, every shift active; zeroes the histories */
+int spmv_hip_cgs_ws_reset(spmv_hip_cgs_ws* ws, double rtol, int kmax, int ns,
+                          const double* host_shifts, void* stream);
+int spmv_hip_cgs_ws_capacity(const spmv_hip_cgs_ws* ws, int* kmax);
+/* device address and length of one array of the state */
+int spmv_hip_cgs_ws_array(spmv_hip_cgs_ws* ws, int which, double** p,
+                          int64_t* count);
+/* copies the SPMV_HIP_CGS_STATE_WORDS words and the histories to the host
+ * (async; either may be NULL; host_hist_len >= 8 * (capacity + 1) or nothing
+ * is enqueued) */
+int spmv_hip_cgs_ws_read_async(spmv_hip_cgs_ws* ws, int32_t* host_state,
+                               double* host_hist, size_t host_hist_len,
+                               void* stream);
+/* TEST HOOKS: install / read the SPMV_HIP_CGS_WORDS words (set waits; ns must
+ * be the reset's, the list entries below it, k <= kmax <= the capacity) */
+int spmv_hip_cgs_ws_set_words(spmv_hip_cgs_ws* ws, const int32_t* host_words,
+                              void* stream);
+int spmv_hip_cgs_ws_get_words(spmv_hip_cgs_ws* ws, int32_t* host_words,
+                              void* stream);
+/* pq: the slot (reduced != 0), or PART_PQ (+ pq_partials2, may be NULL) added
+ * by every workgroup in the reducer's order and left in the slot.  pq > 0: a =
+ * rr / pq ; r = r - a * q in place ; partials of r.r into PART_RRN.  Otherwise
+ * (a NaN too) nothing is written: step ends the solve with status 1. */
+int spmv_hip_cgs_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_cgs_ws* ws, int64_t n,
+                              const double* q, double* r,
+                              const double* pq_partials2, int reduced,
+                              void* stream);
+/* PART_PQ (+ partials2) -> PQ or PART_RRN -> RRN; one workgroup */
+int spmv_hip_cgs_reduce(spmv_hip_ctx* ctx, spmv_hip_cgs_ws* ws, int which,
+                        const double* partials2, void* stream);
+/* one workgroup: rr from the slot RRN (reduced != 0) or from PART_RRN in the
+ * reducer's order; hist_s[0] = sqrt(rr) for s < ns; rr == 0: done, status 0 */
+int spmv_hip_cgs_start(spmv_hip_ctx* ctx, spmv_hip_cgs_ws* ws, int reduced,
+                       void* stream);
+/* one workgroup: rrn as in start; thread 0: the scalar part of an iteration
+ * for every shift of act[], upd[] and the next act[] */
+int spmv_hip_cgs_step(spmv_hip_ctx* ctx, spmv_hip_cgs_ws* ws, int reduced,
+                      void* stream);
+/* k >= 1, state k == k: for every entry of upd[]: x_s = x_s + cx_s * p_s and,
+ * with bit 3 and not done, p_s = zeta_s * r + cp_s * p_s; not done: p = r + bn
+ * * p.  Columns outside upd[] are neither read nor written.  ldx, ldp >= n. */
+int spmv_hip_cgs_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_cgs_ws* ws, int k,
+                               int64_t n, const double* r, double* p, double* X,
+                               int64_t ldx, double* PS, int64_t ldp,
+                               void* stream);
+
 /* ---- 3-D Poisson generator (not in the reference)
  * 7-point stencil on an n^3 grid, natural ordering, diag 6, off-diag -1.
  * Generates, directly in device memory, the CSR block of global rows

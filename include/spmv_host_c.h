@@ -796,6 +796,33 @@ int spmvh_lobpcg_gen(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                      int* restarts, spmvh_lobpcg_workspace* ws, int flags,
                      double* spmv_ms_total, int* spmv_launches);
 
+/* ---- multi-shift CG (spmv::cg_shifted, host/cg.h; not in the reference) ---------
+ * spmvh_cg_shifted: (A + shifts[s] I) x_s = b for s < ns (1..8) from x_s = 0 with
+ * one product per iteration; A symmetric positive definite, every shift finite
+ * and >= 0 (a HOST array of ns doubles).  b: the matrix's local rows; solution s
+ * is the contiguous device vector X + s * ldx, ldx >= rows (any alignment).
+ * iterations (may be NULL): ns ints; rnorm_history (may be NULL): ns * (kmax + 1)
+ * doubles, hist_s[j] at s * (kmax + 1) + j, -1.0 beyond iterations[s]; *num_its:
+ * the largest count.  *status (may be NULL): 0 every shift met rtol or kmax was
+ * reached, 1 p.(A p) was not positive (A is not positive definite, or the data
+ * are not finite): X is the last iterate.  ws: a reusable
+ * spmv::CgShiftedWorkspace (may be NULL).  flags: bit 0 -> CgOptions::time_spmv,
+ * bits 8-15 -> poll_every (0 = default).
+ * spmvh_cgs_check_rules: cgs_check_rules of solver_args.h alone (no device;
+ * shifts is read on the host, b and X are compared, never dereferenced). */
+typedef struct spmvh_cgs_workspace spmvh_cgs_workspace;
+int spmvh_cgs_workspace_create(spmvh_exec* exec, spmvh_cgs_workspace** ws);
+int spmvh_cgs_workspace_destroy(spmvh_cgs_workspace* ws);
+int spmvh_cgs_workspace_reserve_timing(spmvh_cgs_workspace* ws, int iterations);
+int spmvh_cgs_check_rules(int ns, int kmax, int64_t rows, int64_t ldx,
+                          const double* shifts, const double* b, const double* X);
+int spmvh_cg_shifted(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                     const double* b, double* X, int64_t ldx,
+                     const double* shifts, int ns, int kmax, double rtol,
+                     int* num_its, int* iterations, double* rnorm_history,
+                     int* status, spmvh_cgs_workspace* ws, int flags,
+                     double* spmv_ms_total, int* spmv_launches);
+
 #ifdef __cplusplus
 }
 #endif

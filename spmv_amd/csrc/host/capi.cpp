@@ -58,6 +58,7 @@ struct spmvh_pcg_block_workspace : WorkspaceHandle<PcgBlockWorkspace> {};
 struct spmvh_gmres_workspace : WorkspaceHandle<GmresWorkspace> {};
 struct spmvh_minres_workspace : WorkspaceHandle<MinresWorkspace> {};
 struct spmvh_lsqr_workspace : WorkspaceHandle<LsqrWorkspace> {};
+struct spmvh_cgs_workspace : WorkspaceHandle<CgShiftedWorkspace> {};
 struct spmvh_lobpcg_workspace : WorkspaceHandle<LobpcgWorkspace> {};
 struct spmvh_sgs_build {
   SgsHostPlan plan;
@@ -2245,6 +2246,57 @@ int spmvh_lobpcg_gen(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
     if (restarts)
       *restarts = st.restarts;
     copy_out(hist, resnorm_history, st, spmv_ms_total, spmv_launches);
+  });
+}
+
+// ---- multi-shift CG ---------------------------------------------------------------------
+int spmvh_cgs_workspace_create(spmvh_exec* exec, spmvh_cgs_workspace** ws)
+{
+  return workspace_create<CgShiftedWorkspace>(exec, ws);
+}
+
+int spmvh_cgs_workspace_destroy(spmvh_cgs_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_cgs_workspace_reserve_timing(spmvh_cgs_workspace* ws, int iterations)
+{
+  return workspace_reserve_timing(ws, iterations);
+}
+
+int spmvh_cgs_check_rules(int ns, int kmax, int64_t rows, int64_t ldx,
+                          const double* shifts, const double* b, const double* X)
+{
+  return guarded([&] { cgs_check_rules(ns, kmax, rows, ldx, shifts, b, X); });
+}
+
+int spmvh_cg_shifted(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+                     const double* b, double* X, int64_t ldx,
+                     const double* shifts, int ns, int kmax, double rtol,
+                     int* num_its, int* iterations, double* rnorm_history,
+                     int* status, spmvh_cgs_workspace* ws, int flags,
+                     double* spmv_ms_total, int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && num_its, "NULL argument");
+    std::vector<int> its;
+    std::vector<double> hist;
+    CgOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff) // bits 8-15: CgOptions::poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    CgStats st;
+    int how = 0;
+    *num_its = cg_shifted(*comm->comm, *exec->hip, *A->A, b, X, ldx, shifts, ns,
+                          kmax, rtol, iterations ? &its : nullptr,
+                          rnorm_history ? &hist : nullptr, &how, &opt, &st,
+                          ws ? ws->ws.get() : nullptr);
+    if (status)
+      *status = how;
+    if (iterations)
+      std::copy(its.begin(), its.end(), iterations);
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
   });
 }
 

@@ -22,6 +22,7 @@ struct spmv_hip_gmres_ws;
 struct spmv_hip_minres_ws;
 struct spmv_hip_lsqr_ws;
 struct spmv_hip_lobpcg_ws;
+struct spmv_hip_cgs_ws;
 struct spmv_hip_mcgs_plan;
 struct spmv_hip_ilu0_plan;
 struct spmv_hip_amg_tail;
@@ -1688,5 +1689,115 @@ int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
            const LobpcgOptions* options = nullptr, LobpcgStats* stats = nullptr,
            LobpcgWorkspace* workspace = nullptr,
            const Matrix<double>* B = nullptr);
+
+// ---- multi-shift CG -------------------------------------------------------------
+
+// Work vectors + device scalars of cg_shifted(), kept across calls like
+// LsqrWorkspace; it regrows itself when a call needs more rows, more
+// iterations or more shifts.
+class CgShiftedWorkspace : public SolverWorkspace
+{
+public:
+  explicit CgShiftedWorkspace(HipExecutor& exec) : SolverWorkspace(exec) {}
+  ~CgShiftedWorkspace();
+
+  // ---- internal to cg_shifted() ----
+  // need_x: a column of the caller's X is not 16-byte aligned and the iterate
+  // lives in the workspace's copy
+  void ensure(int64_t M, int64_t N_padded, int ns, int kmax, int len,
+              bool need_x);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(2 * (size_t)std::max(iterations, 0));
+  }
+  void release();
+
+  spmv_hip_cgs_ws* ws = nullptr;
+  int kmax_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, ps_cap = -1, x_cap = -1;
+  int64_t ld = 0;           // stride of ps and x: M rounded up to an even number
+  double *r = nullptr, *q = nullptr; // m_cap
+  double* p = nullptr;      // n_cap: the padded seed direction mult_dot reads
+  double* ps = nullptr;     // ps_cap = ns * ld: the directions p_s
+  double* x = nullptr;      // x_cap = ns * ld: the iterate of an unaligned X
+  double* dot2 = nullptr;   // len: the remote block's share of p.q
+  // flags: {done, kstop, status, its[8]}; timing_ev: 2 events per iteration
+};
+
+// Multi-shift CG (Frommer; Jegerlehner 1996): solves (A + sigma_s I) x_s = b for
+// ns shifts with ONE product per iteration.  The Krylov space of A + sigma I is
+// that of A and the residuals are collinear, r_s = zeta_s r, so every shifted
+// system rides on the seed recurrence of A for three scalars and two vector
+// updates per iteration, and its stopping test is free: ||r_s|| = |zeta_s| ||r||.
+// A: symmetric positive definite, in either storage; only Matrix::mult_dot and
+// col_map()->update are used: every plan form and halo model serves.  1 <= ns
+// <= 8; every sigma_s finite and >= 0, in any order, duplicates allowed; the
+// seed is always A.  b: A.row_map()->local_size() doubles; solution s is the
+// CONTIGUOUS vector X + s * ldx, ldx >= rows (not the interleaved layout of
+// mult_block: most of a solve runs with few shifts active, and a stopped column
+// of an interleaved block still travels in every cache line; here it is neither
+// read nor written, and each x_s is handed on as an ordinary vector).  With `.`
+// the global dot product, every product, sum, difference, quotient and square
+// root one rounding of its own, the parentheses as written (the RATIO form: it
+// carries rho_s = zeta_s^(k+1) / zeta_s^k, not the product of two zetas, so a
+// zeta that underflows does no harm):
+//
+//   r = b; p = b; rr = r.r; hist_s[0] = sqrt(rr) for every s
+//   for every s: x_s = 0; p_s = b; zeta_s = 1; rho_s = 1
+//   a_old = 1; b_old = 0; k = 0
+//   rr == 0: every shift stopped at k = 0, status 0
+//   while k < kmax and some shift is active:
+//     q = A p; pq = p.q                       halo update of p first
+//     not (pq > 0): status 1; stop            (a NaN fails it; X stays the last
+//                                             iterate)
+//     a = rr / pq
+//     for every active s:
+//       rhon_s = a_old / ((a*b_old)*(1 - rho_s) + a_old*(1 + sigma_s*a))
+//     r = r - a*q; rrn = r.r; bn = rrn / rr; k += 1
+//     for every active s:
+//       x_s = x_s + (a*rhon_s)*p_s
+//       zeta_s = zeta_s*rhon_s; rho_s = rhon_s
+//       hist_s[k] = |zeta_s| * sqrt(rrn); iterations_s = k
+//       hist_s[k] / hist_s[0] < rtol: s stops (x_s updated, p_s left alone)
+//       else p_s = zeta_s*r + (bn*(rhon_s*rhon_s))*p_s
+//     p = r + bn*p; rr = rrn; a_old = a; b_old = bn
+//     rrn == 0: every active shift stops, status 0
+//
+// A stopped shift is frozen for good.  A non-finite scalar takes the "go on"
+// branch of the rtol comparison, as in minres() and lsqr().  Returns the largest
+// iterations_s; `iterations` (optional) receives the ns counts, `rnorm_history`
+// (optional) ns * (kmax + 1) doubles in cg_block's layout, hist_s[j] at
+// s * (kmax + 1) + j, -1.0 beyond iterations_s; `status` (optional) 0 or 1.
+//
+// Launches of one iteration on one rank, beside mult_dot: update_r (adds the
+// partials of p.q itself, in the reducer's order; 3 passes), step (one
+// workgroup adds the partials of r.r in the reducer's order, its thread 0 does
+// the scalar arithmetic of every active shift and leaves the compacted lists),
+// update_xp (reads r once; 4 passes per shift it moves, 2 for one that stops in
+// this step, 2 for the seed's p): 3 launches (4 where mult_dot cannot fuse its
+// dot), 4 n_act + 6 vector passes.  With several ranks: two reducer launches
+// more and two all-reduces of 1 double (pq, rrn), whatever ns is.
+//
+// As in lsqr(): the scalars stay on the device, the decision to stop is taken
+// there and the host only looks at a pinned flag every `poll_every` iterations.
+// update_xp runs exactly when step k completed, so X is the iterate of the
+// returned counts whatever poll_every is.  `X` IS the iterate: zeroed at the
+// start, updated in place; columns that are not 16-byte aligned (an odd ldx
+// with ns > 1, or X 8 bytes off) go through the workspace's copy and one copy
+// back at the end.  The argument rules are cgs_check_rules' (solver_args.h:
+// "ns", "kmax", "ldx", "shifts", "overlaps"), checked before anything touches a
+// device; the executor's stream is restored on every exit path; the workspace
+// is usable after every exit.
+//
+// options: poll_every and time_spmv apply (spmv_launches is 1 per iteration);
+//          the other CgOptions are IGNORED.
+int cg_shifted(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+               const double* b, double* X, int64_t ldx, const double* shifts,
+               int ns, int kmax, double rtol,
+               std::vector<int>* iterations = nullptr,
+               std::vector<double>* rnorm_history = nullptr,
+               int* status = nullptr, const CgOptions* options = nullptr,
+               CgStats* stats = nullptr,
+               CgShiftedWorkspace* workspace = nullptr);
 
 } // namespace spmv

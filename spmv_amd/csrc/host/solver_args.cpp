@@ -223,6 +223,25 @@ void lobpcg_check_pencil(int64_t rows_a, int64_t rows_b, const int64_t* ghosts_a
           + " (B must have A's ghosts in A's order)");
 }
 
+void cgs_check_rules(int ns, int kmax, int64_t rows, int64_t ldx,
+                     const double* shifts, const double* b, const double* X)
+{
+  if (ns < 1 || ns > 8)
+    throw std::runtime_error("spmv::cg_shifted - Error: ns must be in 1..8");
+  if (kmax < 0)
+    throw std::runtime_error("spmv::cg_shifted - Error: kmax < 0");
+  if (ldx < rows)
+    throw std::runtime_error("spmv::cg_shifted - Error: ldx < the local rows");
+  if (!shifts)
+    throw std::runtime_error("spmv::cg_shifted - Error: shifts is NULL");
+  for (int s = 0; s < ns; ++s)
+    if (!(shifts[s] >= 0.0) || !std::isfinite(shifts[s]))
+      throw std::runtime_error("spmv::cg_shifted - Error: shifts must be "
+                               "finite and not negative");
+  if (doubles_overlap(X, (int64_t)(ns - 1) * ldx + rows, b, rows))
+    throw std::runtime_error("cg_shifted: X overlaps b (X is updated in place)");
+}
+
 void amg_check_tail_rows(int64_t max_rows)
 {
   if (max_rows < 0)

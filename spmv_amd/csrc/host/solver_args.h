@@ -93,6 +93,14 @@ void lobpcg_check_pencil(int64_t rows_a, int64_t rows_b, const int64_t* ghosts_a
 void lsqr_check_rules(int kmax, double ltol, double damp, int64_t rows,
                       int64_t cols, const double* b, const double* x);
 
+// The argument rules of cg_shifted() (std::runtime_error), in this order: ns
+// outside 1..8 ("ns"), kmax < 0 ("kmax"), ldx < rows ("ldx"), a shift that is
+// negative or not finite, or shifts == NULL ("shifts"), X ((ns - 1) * ldx + rows
+// doubles) sharing a byte with b (rows doubles) ("overlaps").  shifts is a HOST
+// array and is read; b and X are compared, never dereferenced.
+void cgs_check_rules(int ns, int kmax, int64_t rows, int64_t ldx,
+                     const double* shifts, const double* b, const double* X);
+
 // stride of the basis vectors: N_padded rounded up to an even number, so that
 // every v_j is 16-byte aligned
 int64_t gmres_basis_stride(int64_t N_padded);

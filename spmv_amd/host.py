@@ -237,6 +237,13 @@ _PROTOS = {
     "spmvh_lsqr_check_rules": [C.c_int, f64, f64, i64, i64, vp, vp],
     "spmvh_lsqr": [vp, vp, vp, vp, vp, C.c_int, f64, f64, f64, PTR(C.c_int),
                    PTR(C.c_int), vp, vp, vp, C.c_int, PTR(f64), PTR(C.c_int)],
+    "spmvh_cgs_workspace_create": [vp, PTR(vp)],
+    "spmvh_cgs_workspace_destroy": [vp],
+    "spmvh_cgs_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_cgs_check_rules": [C.c_int, C.c_int, i64, i64, vp, vp, vp],
+    "spmvh_cg_shifted": [vp, vp, vp, vp, vp, i64, vp, C.c_int, C.c_int, f64,
+                         PTR(C.c_int), vp, vp, PTR(C.c_int), vp, C.c_int,
+                         PTR(f64), PTR(C.c_int)],
     "spmvh_gmres_workspace_create": [vp, PTR(vp)],
     "spmvh_gmres_workspace_destroy": [vp],
     "spmvh_gmres_workspace_reserve_timing": [vp, C.c_int],
@@ -1692,6 +1699,51 @@ def lobpcg(comm, exec_, A, x_ptr, nev, kmax, rtol, atol=0.0, dinv=None,
         stats.update(true_resnorm=true_rn[:nev].copy(), restarts=restarts.value,
                      spmv_ms_total=ms.value, spmv_launches=n.value)
     return k.value, eig[:nev], hist[:nev], status.value
+
+
+class CgShiftedWorkspace(_TimedWorkspace):
+    """spmv::CgShiftedWorkspace: work vectors and device scalars kept across
+    cg_shifted() calls."""
+    _prefix = "cgs"
+
+
+def cgs_check_rules(ns, kmax, rows=0, ldx=0, shifts=None, b_ptr=None,
+                    x_ptr=None):
+    """spmv::cgs_check_rules alone (no device; shifts: a sequence of floats or
+    None, read on the host; the pointers are compared, never dereferenced);
+    raises SpmvHostError naming the rule."""
+    sh = None if shifts is None else np.ascontiguousarray(shifts, np.float64)
+    call("spmvh_cgs_check_rules", int(ns), int(kmax), int(rows), int(ldx),
+         _np_ptr(sh), b_ptr or None, x_ptr or None)
+
+
+def cg_shifted(comm, exec_, A, b_ptr, x_ptr, ldx, shifts, kmax, rtol, ws=None,
+               time_spmv=False, poll_every=0, stats=None):
+    """spmv::cg_shifted: multi-shift CG, (A + shifts[s] I) x_s = b for every s
+    from x_s = 0 with one product per iteration -> (k, iterations, history,
+    status).  A symmetric positive definite, 1..8 shifts, each finite and >= 0;
+    b_ptr: the matrix's local rows; solution s is the contiguous device vector
+    x_ptr + 8 * s * ldx.  iterations: the ns counts (k is the largest);
+    history: an array [ns, kmax + 1], row s holding ||r_s|| of iterations
+    0..iterations[s] and -1.0 beyond; status: 0, or 1 when p.(A p) was not
+    positive (host/cg.h).  stats (optional dict) receives spmv_ms_total and
+    spmv_launches of a time_spmv solve."""
+    kmax = int(kmax)
+    sh = np.ascontiguousarray(shifts, np.float64).reshape(-1)
+    ns = len(sh)
+    k, n, status = C.c_int(), C.c_int(), C.c_int()
+    ms = f64()
+    its = np.zeros(max(ns, 1), np.int32)
+    hist = np.zeros((max(ns, 1), max(kmax, 0) + 1))
+    call("spmvh_cg_shifted", comm.h, exec_.h, A.h, b_ptr, x_ptr, int(ldx),
+         _np_ptr(sh), ns, kmax, float(rtol), C.byref(k),
+         its.ctypes.data_as(vp), _np_ptr(hist), C.byref(status),
+         ws.h if ws else None,
+         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         C.byref(n))
+    if stats is not None:
+        stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, its[:ns].copy(), hist[:ns], status.value
 
 
 def host_executor_rejects_compute():
