@@ -1960,6 +1960,130 @@ int spmv_hip_cgs_update_xp_f64(spmv_hip_ctx* ctx, spmv_hip_cgs_ws* ws, int k,
                                int64_t ldx, double* PS, int64_t ldp,
                                void* stream);
 
+/* ---- IDR(s) (spmv::idrs, host/cg.h) ----------------------------------------------
+ * The biortho variant of van Gijzen and Sonneveld (2011), 1 <= s <=
+ * SPMV_HIP_IDRS_MAX_S, on SIGN shadow vectors: p_j(i) = +1.0 where bit j of
+ *   z = gi + seed*0x9E3779B97F4A7C15 + 0x9E3779B97F4A7C15   (uint64, wrapping)
+ *   z = (z ^ z>>30) * 0xBF58476D1CE4E5B9 ; z = (z ^ z>>27) * 0x94D049BB133111EB
+ *   z ^= z>>31
+ * is clear and -1.0 where it is set, gi = row0 + i the GLOBAL row.  P is never
+ * stored.  Vectors: doubles at any 8-byte aligned address; where every vector of
+ * a call is 16-byte aligned (and ld is even) the kernels use 16-byte accesses,
+ * otherwise pairs of 8-byte ones, with the same bits.  g_i = G + i * ld and
+ * u_i = U + i * ld are contiguous vectors.  Every product, sum, difference,
+ * quotient and square root is one rounding.  Launch sequence (the recurrence is
+ * spelled out in host/cg.h; [..]: several ranks only, each followed by one
+ * all-reduce of the slots named):
+ *   sign_dot(b, with_ww) ; [reduce(HRR): s + 1] ; start
+ *   inner step q: prep(q) ; g = A u ; sign_dot(g) ; [reduce(H): s] ; biortho(q)
+ *                 ; update(q) ; [reduce(RR): 1] ; step(q)
+ *   after q = s - 1: vh ; t = A vh ; omega_dot ; [reduce(OM): 2] ; omega ;
+ *                 omega_update ; [reduce(HRR): s + 1] ; step(s)
+ * Device state of a workspace: the SPMV_HIP_IDRS_DOUBLES doubles of
+ * SPMV_HIP_IDRS_SCALARS, in this order: rtol, kappa, om, rr, hist0, be, f[8],
+ * c[8], a[8], red[11], M[64] (M[i][j] at 8 i + j); the 6 words of get_words:
+ * done, kstop, status (0 rtol / kmax / running, 1 a zero or non-finite pivot of
+ * M, 2 t.t not positive or om zero or non-finite), k, kmax, s; hist[0..kmax];
+ * the partial array, 11 rows of spmv_hip_dot_partials_len() doubles: rows 0..7
+ * the sign sums, 8 r.r, 9 t.r, 10 t.t.  The reducers' slots `red`: the sign sums
+ * at 0..s-1, r.r at [s], t.r and t.t at [9] and [10].
+ * `done` is raised by start, step, biortho or omega; every kernel enqueued after
+ * it returns at once, so x is exactly the iterate of the recorded k. */
+typedef struct spmv_hip_idrs_ws spmv_hip_idrs_ws; /* idrs() scalars */
+#define SPMV_HIP_IDRS_MAX_S 8
+/* {done, kstop, status, k}: what read_async copies */
+#define SPMV_HIP_IDRS_STATE_WORDS 4
+#define SPMV_HIP_IDRS_WORDS 6
+#define SPMV_HIP_IDRS_DOUBLES 105
+#define SPMV_HIP_IDRS_ROWS 11
+enum {
+  SPMV_HIP_IDRS_RED = 0,    /* 11: the reducers' slots (all-reduced in place) */
+  SPMV_HIP_IDRS_HIST = 1,   /* capacity + 1                                   */
+  SPMV_HIP_IDRS_PART = 2,   /* 11 * dot_partials_len                          */
+  SPMV_HIP_IDRS_SCALARS = 3 /* 105: see above (tests read and install them)   */
+};
+enum { /* spmv_hip_idrs_reduce: partial rows -> slots */
+  SPMV_HIP_IDRS_REDUCE_H = 0,   /* rows 0..s-1 -> red[0..s-1]                  */
+  SPMV_HIP_IDRS_REDUCE_RR = 1,  /* row 8 -> red[s]                             */
+  SPMV_HIP_IDRS_REDUCE_OM = 2,  /* rows 9, 10 -> red[9], red[10]               */
+  SPMV_HIP_IDRS_REDUCE_HRR = 3  /* rows 0..s-1, 8 -> red[0..s]                 */
+};
+enum { /* spmv_hip_idrs_prep_f64 */
+  SPMV_HIP_IDRS_FUSED = 0,   /* out = om*(dinv*v) + c_q u_q + .. ; v = src - c_q
+                                g_q - .. stays in registers (dinv may be NULL) */
+  SPMV_HIP_IDRS_STORE_V = 1, /* out = v                                        */
+  SPMV_HIP_IDRS_FROM_VH = 2, /* out = om*out + c_q u_q + .. (src == out)        */
+  SPMV_HIP_IDRS_PLAIN = 3    /* out = dinv*src, or src (q == s)                */
+};
+int spmv_hip_idrs_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_idrs_ws** ws);
+int spmv_hip_idrs_ws_destroy(spmv_hip_idrs_ws* ws);
+/* kmax <= the capacity, 1 <= s <= 8; the state in front of start: M = I, om = 1,
+ * everything else 0; zeroes the history */
+int spmv_hip_idrs_ws_reset(spmv_hip_idrs_ws* ws, double rtol, double kappa,
+                           int kmax, int s, uint64_t seed, void* stream);
+int spmv_hip_idrs_ws_capacity(const spmv_hip_idrs_ws* ws, int* kmax);
+/* device address and length of one array of the state */
+int spmv_hip_idrs_ws_array(spmv_hip_idrs_ws* ws, int which, double** p,
+                           int64_t* count);
+/* copies the SPMV_HIP_IDRS_STATE_WORDS words and the history to the host (async;
+ * either may be NULL; host_hist_len >= capacity + 1 or nothing is enqueued) */
+int spmv_hip_idrs_ws_read_async(spmv_hip_idrs_ws* ws, int32_t* host_state,
+                                double* host_hist, size_t host_hist_len,
+                                void* stream);
+/* TEST HOOKS: install / read the SPMV_HIP_IDRS_WORDS words (set waits; s must be
+ * the reset's, 0 <= k <= kmax <= the capacity) */
+int spmv_hip_idrs_ws_set_words(spmv_hip_idrs_ws* ws, const int32_t* host_words,
+                               void* stream);
+int spmv_hip_idrs_ws_get_words(spmv_hip_idrs_ws* ws, int32_t* host_words,
+                               void* stream);
+/* rows 0..s-1 of the partials: this rank's share of p_j . w, one hash per row,
+ * w read once, each sum in the order of the streaming dot product; with_ww:
+ * w.w in row 8 as well.  row0: the global index of w[0]. */
+int spmv_hip_idrs_sign_dot_f64(spmv_hip_ctx* ctx, spmv_hip_idrs_ws* ws,
+                               int64_t n, int64_t row0, const double* w,
+                               int with_ww, void* stream);
+/* see the modes above; c and om are the state's.  ld >= n. */
+int spmv_hip_idrs_prep_f64(spmv_hip_ctx* ctx, spmv_hip_idrs_ws* ws, int q,
+                           int mode, int64_t n, const double* src,
+                           const double* G, const double* U, int64_t ld,
+                           const double* dinv, double* out, void* stream);
+/* g_q = g - a_0 g_0 - .. ; u_q = u - a_0 u_0 - .. ; r = r - be*g_q ; x = x +
+ * be*u_q ; partials of r.r in row 8.  Columns other than 0..q are neither read
+ * nor written. */
+int spmv_hip_idrs_update_f64(spmv_hip_ctx* ctx, spmv_hip_idrs_ws* ws, int q,
+                             int64_t n, const double* g, const double* u,
+                             double* G, double* U, int64_t ld, double* r,
+                             double* x, void* stream);
+/* partials of t.r (row 9) and t.t (row 10) in one pass */
+int spmv_hip_idrs_omega_dot_f64(spmv_hip_ctx* ctx, spmv_hip_idrs_ws* ws,
+                                int64_t n, const double* t, const double* r,
+                                void* stream);
+/* r = r - om*t ; x = x + om*vh ; partials of r.r (row 8) and of the sign sums
+ * of the new r (rows 0..s-1) in the same pass */
+int spmv_hip_idrs_omega_update_f64(spmv_hip_ctx* ctx, spmv_hip_idrs_ws* ws,
+                                   int64_t n, int64_t row0, const double* t,
+                                   const double* vh, double* r, double* x,
+                                   void* stream);
+/* one workgroup per row: partial rows -> the slots (SPMV_HIP_IDRS_REDUCE_*) */
+int spmv_hip_idrs_reduce(spmv_hip_ctx* ctx, spmv_hip_idrs_ws* ws, int which,
+                         void* stream);
+/* One workgroup; sums from the slots (reduced != 0) or from the partial rows in
+ * the reducer's order.  q = -1 (start): f, rr, hist[0]; rr == 0 or kmax == 0:
+ * done.  0 <= q < s: rr, k += 1, hist[k], the stop test, f_i -= be*M[i][q] for
+ * i > q.  q = s: rr, f, k += 1, hist[k], the stop test.  Each leaves the
+ * coefficients c of the step that follows. */
+int spmv_hip_idrs_step(spmv_hip_ctx* ctx, spmv_hip_idrs_ws* ws, int q,
+                       int reduced, void* stream);
+int spmv_hip_idrs_start(spmv_hip_ctx* ctx, spmv_hip_idrs_ws* ws, int reduced,
+                        void* stream); /* step(-1) */
+/* one workgroup: a_0..a_{q-1}, column q of M, be = f_q / M[q][q]; a zero or
+ * non-finite pivot: done, status 1 */
+int spmv_hip_idrs_biortho(spmv_hip_ctx* ctx, spmv_hip_idrs_ws* ws, int q,
+                          int reduced, void* stream);
+/* one workgroup: om from t.r, t.t and rr; status 2 exits */
+int spmv_hip_idrs_omega(spmv_hip_ctx* ctx, spmv_hip_idrs_ws* ws, int reduced,
+                        void* stream);
+
 /* ---- 3-D Poisson generator (not in the reference)
  * 7-point stencil on an n^3 grid, natural ordering, diag 6, off-diag -1.
  * Generates, directly in device memory, the CSR block of global rows

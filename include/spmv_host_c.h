@@ -823,6 +823,35 @@ int spmvh_cg_shifted(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
                      int* status, spmvh_cgs_workspace* ws, int flags,
                      double* spmv_ms_total, int* spmv_launches);
 
+/* ---- IDR(s) (spmv::idrs, host/cg.h; not in the reference) -------------------------
+ * spmvh_idrs: IDR(s), 1 <= s <= 8, from x = 0 on sign shadow vectors, with the
+ * right preconditioner of spmvh_gmres_amg (dinv, the Chebyshev degree and
+ * bounds, sgs / ILU(0), amg; at most one), for a matrix that need not be
+ * symmetric: one product per step.  b, x: the matrix's local rows (x at any
+ * 8-byte alignment, updated in place).  kappa: 0.7 is the usual choice; seed:
+ * of the shadow signs.  rnorm_history (may be NULL): kmax + 1 doubles, hist[0..
+ * *num_its] written.  *status (may be NULL): 0 rtol or kmax was reached, 1 a
+ * zero or non-finite pivot of M, 2 a zero or non-finite om.  ws: a reusable
+ * spmv::IdrsWorkspace (may be NULL).  flags: bit 0 -> time_spmv, bits 8-15 ->
+ * poll_every (0 = default).
+ * spmvh_idrs_check_rules: idrs_check_rules of solver_args.h alone (no device;
+ * the pointers are compared, never dereferenced). */
+typedef struct spmvh_idrs_workspace spmvh_idrs_workspace;
+int spmvh_idrs_workspace_create(spmvh_exec* exec, spmvh_idrs_workspace** ws);
+int spmvh_idrs_workspace_destroy(spmvh_idrs_workspace* ws);
+int spmvh_idrs_workspace_reserve_timing(spmvh_idrs_workspace* ws, int iterations);
+int spmvh_idrs_check_rules(int s, int kmax, double kappa, int has_dinv,
+                           int cheb_degree, double lmin, double lmax,
+                           int has_sgs, int has_amg, int64_t pre_rows,
+                           int64_t rows, const double* b, const double* x,
+                           const double* dinv);
+int spmvh_idrs(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+               const double* b, double* x, const double* dinv, int cheb_degree,
+               double lmin, double lmax, spmvh_sgs* sgs, spmvh_amg* amg, int s,
+               int kmax, double rtol, double kappa, uint64_t seed, int* num_its,
+               int* status, double* rnorm_history, spmvh_idrs_workspace* ws,
+               int flags, double* spmv_ms_total, int* spmv_launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,7 @@ struct spmvh_gmres_workspace : WorkspaceHandle<GmresWorkspace> {};
 struct spmvh_minres_workspace : WorkspaceHandle<MinresWorkspace> {};
 struct spmvh_lsqr_workspace : WorkspaceHandle<LsqrWorkspace> {};
 struct spmvh_cgs_workspace : WorkspaceHandle<CgShiftedWorkspace> {};
+struct spmvh_idrs_workspace : WorkspaceHandle<IdrsWorkspace> {};
 struct spmvh_lobpcg_workspace : WorkspaceHandle<LobpcgWorkspace> {};
 struct spmvh_sgs_build {
   SgsHostPlan plan;
@@ -2296,6 +2297,68 @@ int spmvh_cg_shifted(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
       *status = how;
     if (iterations)
       std::copy(its.begin(), its.end(), iterations);
+    copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
+  });
+}
+
+// ---- IDR(s) -----------------------------------------------------------------------------
+int spmvh_idrs_workspace_create(spmvh_exec* exec, spmvh_idrs_workspace** ws)
+{
+  return workspace_create<IdrsWorkspace>(exec, ws);
+}
+
+int spmvh_idrs_workspace_destroy(spmvh_idrs_workspace* ws)
+{
+  return guarded([&] { delete ws; });
+}
+
+int spmvh_idrs_workspace_reserve_timing(spmvh_idrs_workspace* ws, int iterations)
+{
+  return workspace_reserve_timing(ws, iterations);
+}
+
+int spmvh_idrs_check_rules(int s, int kmax, double kappa, int has_dinv,
+                           int cheb_degree, double lmin, double lmax,
+                           int has_sgs, int has_amg, int64_t pre_rows,
+                           int64_t rows, const double* b, const double* x,
+                           const double* dinv)
+{
+  return guarded([&] {
+    idrs_check_rules(s, kmax, kappa, has_dinv != 0, cheb_degree, lmin, lmax,
+                     has_sgs != 0, has_amg != 0, pre_rows, rows, b, x, dinv);
+  });
+}
+
+int spmvh_idrs(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
+               const double* b, double* x, const double* dinv, int cheb_degree,
+               double lmin, double lmax, spmvh_sgs* sgs, spmvh_amg* amg, int s,
+               int kmax, double rtol, double kappa, uint64_t seed, int* num_its,
+               int* status, double* rnorm_history, spmvh_idrs_workspace* ws,
+               int flags, double* spmv_ms_total, int* spmv_launches)
+{
+  return guarded([&] {
+    require(comm && exec && A && num_its, "NULL argument");
+    std::vector<double> hist;
+    IdrsOptions opt;
+    opt.time_spmv = (flags & 1) != 0;
+    if ((flags >> 8) & 0xff) // bits 8-15: poll_every (0 = default)
+      opt.poll_every = (flags >> 8) & 0xff;
+    opt.kappa = kappa;
+    opt.seed = seed;
+    GmresPreconditioner pre;
+    pre.dinv = dinv;
+    pre.cheb_degree = cheb_degree;
+    pre.lmin = lmin;
+    pre.lmax = lmax;
+    pre.sgs = sgs ? sgs->M.get() : nullptr;
+    pre.amg = amg ? amg->M.get() : nullptr;
+    CgStats st;
+    int how = 0;
+    *num_its = idrs(*comm->comm, *exec->hip, *A->A, b, x, &pre, s, kmax, rtol,
+                    rnorm_history ? &hist : nullptr, &opt, &st,
+                    ws ? ws->ws.get() : nullptr, &how);
+    if (status)
+      *status = how;
     copy_out(hist, rnorm_history, st, spmv_ms_total, spmv_launches);
   });
 }

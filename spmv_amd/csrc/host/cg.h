@@ -23,6 +23,7 @@ struct spmv_hip_minres_ws;
 struct spmv_hip_lsqr_ws;
 struct spmv_hip_lobpcg_ws;
 struct spmv_hip_cgs_ws;
+struct spmv_hip_idrs_ws;
 struct spmv_hip_mcgs_plan;
 struct spmv_hip_ilu0_plan;
 struct spmv_hip_amg_tail;
@@ -1799,5 +1800,137 @@ int cg_shifted(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
                int* status = nullptr, const CgOptions* options = nullptr,
                CgStats* stats = nullptr,
                CgShiftedWorkspace* workspace = nullptr);
+
+// ---- IDR(s) ---------------------------------------------------------------------
+
+struct IdrsOptions {
+  int poll_every = 16;    // host looks at the device's `done` flag this often
+  bool time_spmv = false; // bracket every Matrix::mult of the recurrence
+  uint64_t seed = 0;      // of the shadow signs
+  double kappa = 0.7;     // the om step is lengthened where |rho| < kappa
+};
+
+// Work vectors + device scalars of idrs(), kept across calls like
+// GmresWorkspace; it regrows itself when a call needs more rows, a larger s or
+// more iterations, and is usable after every exit.  Owns the ChebyshevWorkspace
+// of a Chebyshev preconditioner.
+class IdrsWorkspace : public SolverWorkspace
+{
+public:
+  explicit IdrsWorkspace(HipExecutor& exec);
+  ~IdrsWorkspace();
+
+  // ---- internal to idrs() ----
+  // need_v: a stored preconditioner (sgs / ILU(0) / amg / Chebyshev) reads v;
+  // need_dinv: Chebyshev's dinv is not 16-byte aligned
+  void ensure(int64_t M, int64_t N_padded, int s, int kmax, bool need_v,
+              bool need_dinv);
+  void reserve_timing(int iterations)
+  {
+    reserve_events(2 * (size_t)std::max(iterations, 0));
+  }
+  void release();
+
+  spmv_hip_idrs_ws* ws = nullptr;
+  ChebyshevWorkspace cheb;
+  int kmax_cap = -1;
+  int64_t m_cap = -1, n_cap = -1, gu_cap = -1, v_cap = -1, dinv_cap = -1;
+  int64_t ld = 0;          // stride of G and U: M rounded up to an even number
+  double *r = nullptr, *t = nullptr; // m_cap (t: g, then A vh)
+  double* u = nullptr;     // n_cap: the padded u / vh the SpMV reads
+  double *G = nullptr, *U = nullptr; // gu_cap = s * ld each
+  double* v = nullptr;     // v_cap: what a stored preconditioner reads
+  double* dinv = nullptr;  // dinv_cap: the copy of an unaligned dinv
+  // flags: {done, kstop, status, k}; timing_ev: 2 events per product
+};
+
+// the argument rules of idrs() that need no device (idrs_check_rules of
+// solver_args.h on the fields of M and the options)
+void idrs_check_arguments(const GmresPreconditioner* M, int s, int kmax,
+                          double kappa, int64_t rows, const double* b,
+                          const double* x);
+
+// IDR(s) (Sonneveld and van Gijzen; the biortho variant of 2011) from x0 = 0
+// with a RIGHT preconditioner B^-1 (GmresPreconditioner: none, dinv*,
+// chebyshev_apply, sgs_apply / ILU(0) or amg_apply), for a matrix that need not
+// be symmetric: short recurrences, ONE product per step, 2 s + 4 vectors
+// whatever the iteration count.  IDR(1) is mathematically BiCGStab; s = 4 or 8
+// is markedly more robust on convection-dominated systems.  Only Matrix::mult
+// and col_map()->update are used: every plan form, both storages and every halo
+// model serve.  1 <= s <= 8.
+//
+// Shadow space.  P has s columns of random SIGNS: with gi the global index of a
+// row, in uint64 arithmetic with wraparound,
+//     z = gi + seed*0x9E3779B97F4A7C15 + 0x9E3779B97F4A7C15
+//     z = (z ^ z>>30) * 0xBF58476D1CE4E5B9
+//     z = (z ^ z>>27) * 0x94D049BB133111EB
+//     z ^= z>>31
+//     p_j(i) = +1.0 if bit j of z is clear, else -1.0
+// P is never stored and never streamed; p_j . w adds w_i or -w_i; the signs
+// depend on the global row alone, so a partition changes only the summation
+// order.
+//
+// With `.` the deterministic two-stage dot product, M the s x s lower
+// triangular scalar matrix, every product, sum, difference, quotient and square
+// root one rounding of its own:
+//
+//   x = 0; r = b; G = U = 0 (n x s); M = I; om = 1; k = 0; status = 0
+//   f = P^T r; rr = r.r; hist[0] = sqrt(rr);   rr == 0: return 0
+//   cycle:
+//     for q = 0..s-1:
+//       c_i, i = q..s-1 in order: t = f_i; for j = q..i-1: t = t - M[i][j]*c_j;
+//                                 c_i = t / M[i][i]
+//       v  = r - c_q g_q - ... - c_{s-1} g_{s-1}            (in that order)
+//       u  = om*(B^-1 v) + c_q u_q + ... + c_{s-1} u_{s-1}  (in that order)
+//       g  = A u                                            (halo update first)
+//       h  = P^T g                      (ONE launch, s sums; one all-reduce of s)
+//       a_i, i = 0..q-1 in order: t = h_i; for j < i: t = t - a_j*M[i][j];
+//                                 a_i = t / M[i][i]
+//       g_q = g - a_0 g_0 - ...;  u_q = u - a_0 u_0 - ...
+//       M[i][q], i = q..s-1: t = h_i; for j < q: t = t - a_j*M[i][j]; M[i][q] = t
+//       M[q][q] is zero or not finite: status = 1, stop (nothing of this step
+//                                      is written to x, r, G, U)
+//       be = f_q / M[q][q]; r = r - be*g_q; x = x + be*u_q; rr = r.r; k += 1;
+//       hist[k] = sqrt(rr)
+//       hist[k]/hist[0] < rtol or k == kmax: stop
+//       f_i = f_i - be*M[i][q], i = q+1..s-1
+//     vh = B^-1 r; t = A vh; tr = t.r; tt = t.t
+//     not (tt > 0): status = 2, stop
+//     om = tr/tt; rho = tr/(sqrt(tt)*sqrt(rr));
+//     |rho| < kappa: om = om*kappa/|rho|
+//     om is zero or not finite: status = 2, stop
+//     r = r - om*t; x = x + om*vh; rr = r.r; f = P^T r; k += 1;
+//     hist[k] = sqrt(rr); the same stop test
+//
+// The biorthogonalisation is the one-synchronisation form: one multi-dot of the
+// un-orthogonalised g yields every a_i and the new column of M by scalar
+// arithmetic on the device, because p_i . g_j = M[i][j] is already known.  A
+// non-finite scalar takes the "go on" branch of the rtol test.  Returns k, the
+// products completed; x is exactly the iterate of that k; rnorm_history
+// receives hist[0..k] (the recurrence's residual norms); `status` (optional)
+// 0 at rtol or kmax, 1 on a zero pivot of M, 2 on a zero or non-finite om.
+//
+// Launches of an inner step on one rank, beside the product: prep, sign_dot,
+// biortho, update, step -- 5 launches and 2 s + 11 vector passes with no
+// preconditioner (dinv: one more; a stored preconditioner: prep twice and its
+// own kernels).  An om step: prep, omega_dot, omega, omega_update, step -- 5
+// launches, 10 passes.  With several ranks a reducer launch and an all-reduce
+// follow each multi-dot: s and 1 doubles per inner step, 2 and s + 1 per om
+// step.  The scalars, M, f, the history and k never leave the device inside the
+// loop; the host polls a pinned flag every `poll_every` steps, and kernels
+// enqueued after `done` return at once.  `x` IS the iterate (zeroed at the
+// start, updated in place, at any 8-byte alignment).  x must not overlap b or
+// dinv ("overlaps"); the argument rules are idrs_check_rules' (solver_args.h:
+// "s", "kmax", "kappa", "preconditioner", "rows", "overlaps"), checked before
+// anything touches a device; the executor's stream is restored on every exit
+// path.
+//
+// options: poll_every, time_spmv (one timed Matrix::mult per step: spmv_launches
+//          is the number of steps enqueued), seed and kappa.
+int idrs(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
+         const double* b, double* x, const GmresPreconditioner* M, int s,
+         int kmax, double rtol, std::vector<double>* rnorm_history = nullptr,
+         const IdrsOptions* options = nullptr, CgStats* stats = nullptr,
+         IdrsWorkspace* workspace = nullptr, int* status = nullptr);
 
 } // namespace spmv

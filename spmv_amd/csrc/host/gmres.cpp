@@ -172,14 +172,7 @@ int gmres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   auto apply_pre = [&](double* src) -> double* {
     if (!any_pre)
       return src;
-    if (cheb)
-      chebyshev_apply(exec, A, src, w.z, di, pre.cheb_degree, pre.lmin,
-                      pre.lmax, &w.cheb);
-    else if (pre.sgs)
-      sgs_apply(exec, *pre.sgs, src, w.z);
-    else if (pre.amg)
-      amg_apply(exec, *pre.amg, src, w.z);
-    else
+    if (!apply_stored_preconditioner(exec, A, pre, di, &w.cheb, src, w.z))
       throw_on_error(spmv_hip_gmres_diag_f64(ctx, M, di, src, w.z, nullptr),
                      "spmv_hip_gmres_diag_f64");
     return w.z;

@@ -242,6 +242,40 @@ void cgs_check_rules(int ns, int kmax, int64_t rows, int64_t ldx,
     throw std::runtime_error("cg_shifted: X overlaps b (X is updated in place)");
 }
 
+void idrs_check_rules(int s, int kmax, double kappa, bool has_dinv,
+                      int cheb_degree, double lmin, double lmax, bool has_sgs,
+                      bool has_amg, int64_t pre_rows, int64_t rows,
+                      const double* b, const double* x, const double* dinv)
+{
+  if (s < 1 || s > 8)
+    throw std::runtime_error("spmv::idrs - Error: s must be in 1..8");
+  if (kmax < 0)
+    throw std::runtime_error("spmv::idrs - Error: kmax < 0");
+  if (!std::isfinite(kappa) || !(kappa >= 0.0) || !(kappa < 1.0))
+    throw std::runtime_error(
+        "spmv::idrs - Error: kappa must be finite with 0 <= kappa < 1");
+  if (has_amg && has_sgs)
+    throw std::runtime_error(
+        "spmv::idrs - Error: one preconditioner at a time (amg excludes sgs, "
+        "dinv and the Chebyshev degree)");
+  if ((has_sgs || has_amg) && (has_dinv || cheb_degree != 0))
+    throw std::runtime_error(
+        "spmv::idrs - Error: one preconditioner at a time (sgs and amg exclude "
+        "dinv and the Chebyshev degree)");
+  if (cheb_degree != 0) {
+    double ca[kChebyshevMaxDegree], cb[kChebyshevMaxDegree];
+    chebyshev_coefficients(cheb_degree, lmin, lmax, ca, cb);
+  }
+  if ((has_sgs || has_amg) && pre_rows != rows)
+    throw std::runtime_error("spmv::idrs - Error: the preconditioner has "
+                             + std::to_string(pre_rows) + " rows, A has "
+                             + std::to_string(rows));
+  if (doubles_overlap(x, rows, b, rows))
+    throw std::runtime_error("idrs: x overlaps b (x is updated in place)");
+  if (has_dinv && doubles_overlap(x, rows, dinv, rows))
+    throw std::runtime_error("idrs: x overlaps dinv");
+}
+
 void amg_check_tail_rows(int64_t max_rows)
 {
   if (max_rows < 0)

@@ -101,6 +101,17 @@ void lsqr_check_rules(int kmax, double ltol, double damp, int64_t rows,
 void cgs_check_rules(int ns, int kmax, int64_t rows, int64_t ldx,
                      const double* shifts, const double* b, const double* X);
 
+// The argument rules of idrs() (std::runtime_error), in this order: s outside
+// 1..8 ("s"), kmax < 0 ("kmax"), kappa not finite or outside [0, 1) ("kappa"),
+// gmres_check_rules' rules on the preconditioner ("preconditioner", "degree",
+// "bounds", "rows"; amg obeys the rules of sgs), x sharing a byte with b or dinv,
+// rows doubles each ("overlaps").  The pointers are compared, never
+// dereferenced.
+void idrs_check_rules(int s, int kmax, double kappa, bool has_dinv,
+                      int cheb_degree, double lmin, double lmax, bool has_sgs,
+                      bool has_amg, int64_t pre_rows, int64_t rows,
+                      const double* b, const double* x, const double* dinv);
+
 // stride of the basis vectors: N_padded rounded up to an even number, so that
 // every v_j is 16-byte aligned
 int64_t gmres_basis_stride(int64_t N_padded);

@@ -90,6 +90,29 @@ struct SolveStream {
   SolveStream& operator=(const SolveStream&) = delete;
 };
 
+// z (padded) = M^-1 src for the right preconditioners of gmres() and idrs() that
+// run kernels of their own: Chebyshev (cheb_dinv: null or 16-byte aligned), sgs
+// / ILU(0), amg.  False, and nothing done, where `pre` names none of them (no
+// preconditioner, or dinv alone, which each solver applies in its own kernels).
+inline bool apply_stored_preconditioner(HipExecutor& exec,
+                                        const Matrix<double>& A,
+                                        const GmresPreconditioner& pre,
+                                        const double* cheb_dinv,
+                                        ChebyshevWorkspace* cheb_ws,
+                                        const double* src, double* z)
+{
+  if (pre.cheb_degree >= 1)
+    chebyshev_apply(exec, A, src, z, cheb_dinv, pre.cheb_degree, pre.lmin,
+                    pre.lmax, cheb_ws);
+  else if (pre.sgs)
+    sgs_apply(exec, *pre.sgs, src, z);
+  else if (pre.amg)
+    amg_apply(exec, *pre.amg, src, z);
+  else
+    return false;
+  return true;
+}
+
 // The device address of one scalar slot of a solver's workspace (for the
 // all-reduce): `get` is its spmv_hip_*_ws_<name> getter.
 template <class Ws>

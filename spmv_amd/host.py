@@ -244,6 +244,14 @@ _PROTOS = {
     "spmvh_cg_shifted": [vp, vp, vp, vp, vp, i64, vp, C.c_int, C.c_int, f64,
                          PTR(C.c_int), vp, vp, PTR(C.c_int), vp, C.c_int,
                          PTR(f64), PTR(C.c_int)],
+    "spmvh_idrs_workspace_create": [vp, PTR(vp)],
+    "spmvh_idrs_workspace_destroy": [vp],
+    "spmvh_idrs_workspace_reserve_timing": [vp, C.c_int],
+    "spmvh_idrs_check_rules": [C.c_int, C.c_int, f64, C.c_int, C.c_int, f64, f64,
+                               C.c_int, C.c_int, i64, i64, vp, vp, vp],
+    "spmvh_idrs": [vp, vp, vp, vp, vp, vp, C.c_int, f64, f64, vp, vp, C.c_int,
+                   C.c_int, f64, f64, C.c_uint64, PTR(C.c_int), PTR(C.c_int), vp,
+                   vp, C.c_int, PTR(f64), PTR(C.c_int)],
     "spmvh_gmres_workspace_create": [vp, PTR(vp)],
     "spmvh_gmres_workspace_destroy": [vp],
     "spmvh_gmres_workspace_reserve_timing": [vp, C.c_int],
@@ -1744,6 +1752,53 @@ def cg_shifted(comm, exec_, A, b_ptr, x_ptr, ldx, shifts, kmax, rtol, ws=None,
     if stats is not None:
         stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
     return k.value, its[:ns].copy(), hist[:ns], status.value
+
+
+class IdrsWorkspace(_TimedWorkspace):
+    """spmv::IdrsWorkspace: G, U, the work vectors and device scalars kept
+    across idrs() calls."""
+    _prefix = "idrs"
+
+
+IDRS_MAX_S = 8
+
+
+def idrs_check_rules(s, kmax, kappa=0.7, has_dinv=False, cheb=None,
+                     has_sgs=False, has_amg=False, pre_rows=0, rows=0,
+                     b_ptr=None, x_ptr=None, dinv_ptr=None):
+    """spmv::idrs_check_rules alone (no device; the pointers are compared, never
+    dereferenced); raises SpmvHostError naming the rule."""
+    degree, lmin, lmax = cheb if cheb else (0, 0.0, 0.0)
+    call("spmvh_idrs_check_rules", int(s), int(kmax), float(kappa),
+         int(bool(has_dinv)), int(degree), float(lmin), float(lmax),
+         int(bool(has_sgs)), int(bool(has_amg)), int(pre_rows), int(rows),
+         b_ptr or None, x_ptr or None, dinv_ptr or None)
+
+
+def idrs(comm, exec_, A, b_ptr, x_ptr, s, kmax, rtol, dinv_ptr=None, cheb=None,
+         sgs=None, amg=None, ws=None, kappa=0.7, seed=0, time_spmv=False,
+         poll_every=0, stats=None):
+    """spmv::idrs: IDR(s), 1 <= s <= 8, from x0 = 0 on sign shadow vectors with a
+    right preconditioner, for a matrix that need not be symmetric -> (k,
+    rnorm_history, status).  Preconditioner: as gmres().  status: 0 rtol or kmax
+    reached, 1 a zero pivot of M, 2 a zero or non-finite om (host/cg.h).  stats
+    (optional dict) receives spmv_ms_total and spmv_launches of a time_spmv
+    solve (one SpMV per step)."""
+    kmax = int(kmax)
+    k, n, status = C.c_int(), C.c_int(), C.c_int()
+    ms = f64()
+    hist = np.zeros(max(kmax, 0) + 1)
+    degree, lmin, lmax = cheb if cheb else (0, 0.0, 0.0)
+    call("spmvh_idrs", comm.h, exec_.h, A.h, b_ptr, x_ptr, dinv_ptr or None,
+         int(degree), float(lmin), float(lmax), sgs.h if sgs else None,
+         amg.h if amg else None, int(s), kmax, float(rtol), float(kappa),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(k), C.byref(status),
+         _np_ptr(hist), ws.h if ws else None,
+         int(bool(time_spmv)) | ((int(poll_every) & 0xff) << 8), C.byref(ms),
+         C.byref(n))
+    if stats is not None:
+        stats.update(spmv_ms_total=ms.value, spmv_launches=n.value)
+    return k.value, hist[:k.value + 1], status.value
 
 
 def host_executor_rejects_compute():
