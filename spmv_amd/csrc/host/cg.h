@@ -1462,7 +1462,28 @@ public:
 // receives 0 (kmax reached, or the rtol test), 1 (the least-squares test) or 2.
 // A non-finite scalar takes the "go on" branch of every comparison, so such a
 // solve ends at kmax with status 0, as in minres(); the workspace is usable
-// afterwards.
+// afterwards.  In the kernels' order: start tests beta == 0 (status 0), writes
+// hist_ar[0], then tests alpha == 0 (status 2); step writes every scalar, k and
+// both histories, then tests the breakdown, rtol, ltol and k == kmax in that
+// order, so an exit that coincides with kmax keeps its status.
+//
+// Non-finite and extreme data.  A NaN in b or A: kmax, status 0, x all NaN.  An
+// Inf in b: the same with hist_r[0] = Inf.  A b whose b.b overflows (1e200):
+// beta = Inf, ib = 0, vt = 0 and alpha == 0: k = 0, status 2, hist_r (Inf),
+// hist_ar (NaN), x = 0.  A b whose b.b underflows to 0 (1e-200) stops at the
+// start with k = 0, status 0 and x = 0 although b != 0.  A damp whose square
+// overflows (1e200) makes rhobar1 and rho infinite: phibar = 0 passes the rtol
+// test while phi is a NaN, so the solve returns k = 1, status 0, hist_r[1] = 0
+// and an x of NaN -- a wrong answer that looks converged.  A damp whose square
+// underflows (1e-200) is the solve of damp = 0, bit for bit.
+//
+// Scaling.  (2^s A, 2^t b, 2^s damp) repeats the solve of (A, b, damp) bit for
+// bit (x times 2^(t-s), hist_r times 2^t, hist_ar times 2^(s+t), the same k
+// and status); so do (A, -b) and (-A, b) with -x.  vt is un-normalised, of size
+// 2^s |A^T b| / |b|, so the relation holds only while vt.vt stays a normal
+// number, roughly |s| < 510.  Above, vt.vt overflows: alpha = Inf, ia = 0 and
+// the solve runs to kmax on NaN with status 0.  Below, it underflows to 0:
+// alpha == 0, k = 0 and status 2 on a regular system.
 //
 // Launches of one iteration on one rank, beside mult and transpmult: update_u
 // (3 passes of m), update_v (adds the partials of ut.ut itself, in the
@@ -1769,6 +1790,26 @@ public:
 // iterations_s; `iterations` (optional) receives the ns counts, `rnorm_history`
 // (optional) ns * (kmax + 1) doubles in cg_block's layout, hist_s[j] at
 // s * (kmax + 1) + j, -1.0 beyond iterations_s; `status` (optional) 0 or 1.
+// In the kernels' order: start writes hist_s[0], then tests rr == 0; step tests
+// not (pq > 0) first, then forms a, bn and every rhon_s (whose divisor has no
+// zero test of its own), writes hist_s[k], tests rtol per shift, and last "no
+// shift left, rrn == 0 or k == kmax".  No step runs beyond kmax, so a pq <= 0
+// that step kmax + 1 would have met is not found: status 0.
+//
+// Non-finite and extreme data.  A NaN or Inf in b, or a NaN in A, makes the
+// first pq a NaN: k = 0, status 1, X = 0.  A b whose b.b overflows (1e200): rr =
+// pq = Inf, a is a NaN, the second pq is a NaN: k = 1, status 1, X all NaN.  A b
+// whose b.b underflows to 0 (1e-200): k = 0, status 0, X = 0 although b != 0.  A
+// huge finite shift (1e300) beside others: rhon_s = 1 / (sigma_s a) and zeta_s
+// are tiny, x_s = b / sigma_s after one step, the shift stops there and the
+// other columns have the bits they have without it.
+//
+// Scaling.  (2^s A, 2^t b, 2^s sigma) repeats the solve of (A, b, sigma) bit
+// for bit, every x_s times 2^(t-s) and every history times 2^t, with the same
+// counts; (A, -b) gives -X; (-A, b) is status 1 at k = 0.  No square of an
+// entry of A is formed, so s alone has no floor (s = +-540 repeats the exact
+// solves); the relation ends where rr = 2^(2t) r.r or pq = 2^(2t+s) p.Ap leaves
+// the normal range, e.g. (s, t) = (-400, -300).
 //
 // Launches of one iteration on one rank, beside mult_dot: update_r (adds the
 // partials of p.q itself, in the reducer's order; 3 passes), step (one
@@ -1905,7 +1946,34 @@ void idrs_check_arguments(const GmresPreconditioner* M, int s, int kmax,
 // The biorthogonalisation is the one-synchronisation form: one multi-dot of the
 // un-orthogonalised g yields every a_i and the new column of M by scalar
 // arithmetic on the device, because p_i . g_j = M[i][j] is already known.  A
-// non-finite scalar takes the "go on" branch of the rtol test.  Returns k, the
+// non-finite scalar takes the "go on" branch of the rtol test, but that test is
+// not the first one a NaN meets.  In the kernels' order: step(start) writes
+// hist[0] and tests rr == 0 (false on a NaN); biortho of inner step 0 then
+// tests "M[0][0] is zero or not finite", which a NaN or Inf in b, A or dinv
+// makes true through h = P^T (A u): such a solve ends at k = 0 with status 1
+// and x = 0, before any rtol test is reached.  Only a solve whose pivots and om
+// stay finite while rr overflows (hist[k] / hist[0] = Inf / Inf) goes on.
+// omega tests not (tt > 0) first; where tt > 0 and t.r == 0 (a skew-symmetric
+// A) om = 0 and rho = 0, the kappa rule makes om = 0 * kappa / 0 a NaN, and it
+// is "not finite" that ends the solve.  A stop at kmax wins over a breakdown
+// that only the next step would find.
+//
+// Non-finite and extreme data.  A NaN or Inf in b, a NaN in A, a NaN or Inf in
+// dinv: k = 0, status 1, x = 0 (hist[0] is NaN, Inf or finite).  A b whose b.b
+// overflows (1e200): the s inner steps run on finite sums with hist = Inf, the
+// om step finds tt = Inf and om = 0: k = s, status 2, x finite.  A b whose b.b
+// underflows to 0 (1e-200): k = 0, status 0, x = 0 although b != 0.
+//
+// Scaling.  (2^s A, 2^t b), with a B^-1 that scales by 2^-s (dinv 2^-s;
+// Chebyshev with the same bounds; SGS, ILU(0), AMG built from the scaled
+// matrix), repeats the solve of (A, b) bit for bit, x times 2^(t-s) and the
+// history times 2^t, at odd s + t too; so do (A, -b) and, with dinv left
+// alone, (-A, b), with -x.  With such a B^-1 no s has a floor.  Without one tt
+// = t.t carries 2^(2(s+t)): beyond |s + t| of about 510 it overflows (om = 0:
+// status 2 at the first om step on a regular system) or underflows to 0 (not
+// (tt > 0): the same exit); a solve that ends inside its first cycle never
+// forms tt and has no floor.
+// Returns k, the
 // products completed; x is exactly the iterate of that k; rnorm_history
 // receives hist[0..k] (the recurrence's residual norms); `status` (optional)
 // 0 at rtol or kmax, 1 on a zero pivot of M, 2 on a zero or non-finite om.
