@@ -1059,6 +1059,82 @@ int spmv_hip_sgs_update_r_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int k,
 int spmv_hip_sgs_dot_rz_f64(spmv_hip_ctx* ctx, spmv_hip_pcg_ws* ws, int64_t n,
                             const double* r, const double* z, void* stream);
 
+/* ---- The setup of the multicolour sweeps on the device (additive, ABI 5) -----
+ * Both entries read a block's CSR arrays where they lie (device pointers): the
+ * rows of a rank with local column numbers, num_cols >= num_rows columns of
+ * which those >= num_rows are ghosts and ignored; column == row is the
+ * diagonal; symmetric != 0: only column < row is an off-diagonal entry and the
+ * block stands for B + B^T.  rowptr may be NULL when nnz == 0.  Nothing of the
+ * matrix is copied to the host; rowptr (from 0 to nnz, monotone) and the
+ * columns are checked on the device before anything is indexed
+ * (SPMV_HIP_EINVAL).  Both wait for the device.
+ *
+ * mcgs_color: greedy first-fit in a priority order over B + B^T, colour(i) =
+ * the smallest colour not worn by a neighbour j with prio(j) > prio(i).
+ * order SPMV_HIP_MCGS_NATURAL: prio(i) = -i, the colouring of the host's
+ * sgs_color entry for entry (as many rounds as the longest ascending path:
+ * slow on long dependency chains); SPMV_HIP_MCGS_HASHED: prio(i) =
+ * mix64((i + 1) * 0x9E3779B97F4A7C15), unsigned.  Jones-Plassmann rounds, one
+ * launch each, ordered by the stream alone; the result does not depend on
+ * scheduling.  colors: num_rows int32 (device).  *rounds: launches until no row
+ * was left (counted in batches read back together).  SPMV_HIP_ERANGE if
+ * num_rows + 1 rounds did not suffice.
+ *
+ * mcgs_plan_build: the plan mcgs_plan_create would make from the host
+ * builder's arrays for the same colours -- every array equal.  diagonal: the
+ * diagonal array of symmetric storage (ignored otherwise: d_i is the sum of
+ * the entries (i, i) in storage order).  long_threshold: 64 in the mirror.
+ * info[SPMV_HIP_MCGS_INFO_WORDS]: [0] diagonal entries not finite or not > 0
+ * (the plan is built all the same: the caller decides), [1] why
+ * SPMV_HIP_EINVAL (SPMV_HIP_MCGS_BAD_*, 0: an argument), [2] peak bytes of the
+ * temporaries, [3] a row of an improper colouring.  A failure leaves nothing
+ * allocated.
+ *
+ * mcgs_plan_sizes / _export: a plan's arrays copied to host buffers, for
+ * plans of either builder.  sizes[SPMV_HIP_MCGS_SIZES_WORDS] = {rows, colours,
+ * slices, before: sliced entries, long rows, long entries, after: the same
+ * three, device bytes}.  export: every pointer may be NULL; perm / dinv / len
+ * rows entries, color_start / color_slice / color_long colours + 1, slice_pos0
+ * slices, slice_ptr slices + 1, long_ptr long rows + 1. */
+#define SPMV_HIP_MCGS_HASHED 0
+#define SPMV_HIP_MCGS_NATURAL 1
+#define SPMV_HIP_MCGS_INFO_WORDS 4
+#define SPMV_HIP_MCGS_SIZES_WORDS 10
+#define SPMV_HIP_MCGS_BAD_ROWPTR 1
+#define SPMV_HIP_MCGS_BAD_COLUMN 2
+#define SPMV_HIP_MCGS_BAD_COLOR 3
+#define SPMV_HIP_MCGS_UNWORN_COLOR 4
+#define SPMV_HIP_MCGS_IMPROPER 5
+typedef struct spmv_hip_mcgs_export {
+  int32_t* color_slice;
+  int32_t* slice_pos0;
+  int64_t* slice_ptr;
+  int32_t* len;
+  int32_t* col;
+  double* val;
+  int32_t* color_long;
+  int32_t* long_pos;
+  int64_t* long_ptr;
+  int32_t* long_col;
+  double* long_val;
+} spmv_hip_mcgs_export;
+int spmv_hip_mcgs_color(spmv_hip_ctx* ctx, int32_t num_rows, int32_t num_cols,
+                        int64_t nnz, const int32_t* rowptr, const int32_t* colind,
+                        int symmetric, int order, int32_t* colors,
+                        int* num_colors, int* rounds, void* stream);
+int spmv_hip_mcgs_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
+                             int32_t num_cols, int64_t nnz, const int32_t* rowptr,
+                             const int32_t* colind, const double* values,
+                             const double* diagonal, int symmetric,
+                             const int32_t* colors, int32_t num_colors,
+                             int long_threshold, spmv_hip_mcgs_plan** plan,
+                             int64_t* info, void* stream);
+int spmv_hip_mcgs_plan_sizes(const spmv_hip_mcgs_plan* plan, int64_t* sizes);
+int spmv_hip_mcgs_plan_export(const spmv_hip_mcgs_plan* plan, int32_t* perm,
+                              int32_t* color_start, double* dinv,
+                              const spmv_hip_mcgs_export* before,
+                              const spmv_hip_mcgs_export* after);
+
 /* ---- Preconditioned CG for a block of right-hand sides (spmv::pcg_block) ----------
  * pcg_sgs's recurrence with a stored Z = M^-1 R, once per column and in
  * lockstep, on INTERLEAVED blocks (V[i * nrhs + c], 1 <= nrhs <=

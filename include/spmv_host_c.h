@@ -439,6 +439,21 @@ int spmvh_lambda_max_estimate(spmvh_comm* comm, spmvh_exec* exec,
  *
  * spmvh_sgs_create: spmv::SgsPreconditioner(exec, A) -- the setup; errors whose
  * text says "diagonal is not positive", "released" or "same index range".
+ * spmvh_sgs_create_ex: SgsPreconditioner(exec, A, SgsOptions) -- setup 0 host,
+ * 1 device (colouring and plan built on the device: nothing of the matrix is
+ * read back); order -1 not given, 0 hashed, 1 natural (as many rounds as the
+ * longest ascending path: slow on long dependency chains); colors NULL or rows
+ * entries (host) that replace the colouring.  setup 0 with an order or colors
+ * is an error; further errors say "not proper", "colour".
+ * spmvh_sgs_setup_info: rounds of the device colouring (0 otherwise) and the
+ * wall time of the constructor; _setup_detail: the device setup's colouring
+ * and build times and the peak bytes of its temporaries (each may be NULL).
+ * spmvh_sgs_export_sizes: sizes[10] = {rows, colours, slices, before: sliced
+ * entries, long rows, long entries, after: the same three, device bytes};
+ * spmvh_sgs_export: the plan's arrays to host buffers of those sizes; before /
+ * after: 11 pointers each in the order of spmv_hip_mcgs_export (color_slice,
+ * slice_pos0, slice_ptr, len, col, val, color_long, long_pos, long_ptr,
+ * long_col, long_val); every pointer may be NULL.
  * spmvh_sgs_info: rows, colours, device bytes of the plan (each may be NULL).
  * spmvh_sgs_colors: the colours, rows entries (host).
  * spmvh_sgs_apply: spmv::sgs_apply -- z = M^-1 r (device, rows doubles each, any
@@ -463,6 +478,14 @@ int spmvh_sgs_build_get(spmvh_sgs_build* build, int32_t* colors, int32_t* perm,
                         double* after_val);
 int spmvh_sgs_build_destroy(spmvh_sgs_build* build);
 int spmvh_sgs_create(spmvh_exec* exec, spmvh_matrix* A, spmvh_sgs** M);
+int spmvh_sgs_create_ex(spmvh_exec* exec, spmvh_matrix* A, int setup, int order,
+                        const int32_t* colors, spmvh_sgs** M);
+int spmvh_sgs_setup_info(spmvh_sgs* M, int* rounds, double* setup_ms);
+int spmvh_sgs_setup_detail(spmvh_sgs* M, double* color_ms, double* build_ms,
+                           int64_t* temp_bytes);
+int spmvh_sgs_export_sizes(spmvh_sgs* M, int64_t* sizes);
+int spmvh_sgs_export(spmvh_sgs* M, int32_t* perm, int32_t* color_start,
+                     double* dinv, void* const* before, void* const* after);
 int spmvh_sgs_destroy(spmvh_sgs* M);
 int spmvh_sgs_info(spmvh_sgs* M, int* rows, int* num_colors,
                    int64_t* plan_bytes);

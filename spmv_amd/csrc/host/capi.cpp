@@ -18,6 +18,7 @@
 #include "amg_build.h"
 #include "ilu0_build.h"
 #include "sgs_build.h"
+#include "spmv_hip.h"
 
 using namespace spmv;
 
@@ -1423,6 +1424,88 @@ int spmvh_sgs_create(spmvh_exec* exec, spmvh_matrix* A, spmvh_sgs** M)
     m->exec = exec->hip;
     m->M.reset(new SgsPreconditioner(*exec->hip, *A->A));
     *M = m.release();
+  });
+}
+
+int spmvh_sgs_create_ex(spmvh_exec* exec, spmvh_matrix* A, int setup, int order,
+                        const int32_t* colors, spmvh_sgs** M)
+{
+  return guarded([&] {
+    // the rules of the options first: they need no handle
+    require(setup == 0 || setup == 1, "setup: 0 (host) or 1 (device)");
+    require(order >= -1 && order <= 1,
+            "order: -1 (default), 0 (hashed) or 1 (natural)");
+    // (an order given explicitly counts as given, the default included)
+    require(setup == 1 || (order == -1 && !colors),
+            "setup = host colours by itself: it takes neither colors nor an "
+            "order");
+    require(exec && A && M, "NULL argument");
+    require(exec->hip != nullptr, "not a HipExecutor");
+    SgsOptions opt;
+    opt.setup = setup == 1 ? SgsSetup::device : SgsSetup::host;
+    opt.order = order == 1 ? SgsOrder::natural : SgsOrder::hashed;
+    opt.colors = colors;
+    auto m = std::make_unique<spmvh_sgs>();
+    m->exec = exec->hip;
+    m->M.reset(new SgsPreconditioner(*exec->hip, *A->A, opt));
+    *M = m.release();
+  });
+}
+
+int spmvh_sgs_setup_info(spmvh_sgs* M, int* rounds, double* setup_ms)
+{
+  return guarded([&] {
+    require(M != nullptr, "NULL argument");
+    if (rounds)
+      *rounds = M->M->rounds();
+    if (setup_ms)
+      *setup_ms = M->M->setup_ms();
+  });
+}
+
+int spmvh_sgs_setup_detail(spmvh_sgs* M, double* color_ms, double* build_ms,
+                           int64_t* temp_bytes)
+{
+  return guarded([&] {
+    require(M != nullptr, "NULL argument");
+    if (color_ms)
+      *color_ms = M->M->color_ms();
+    if (build_ms)
+      *build_ms = M->M->build_ms();
+    if (temp_bytes)
+      *temp_bytes = M->M->setup_temp_bytes();
+  });
+}
+
+int spmvh_sgs_export_sizes(spmvh_sgs* M, int64_t* sizes)
+{
+  return guarded([&] {
+    require(M && sizes, "NULL argument");
+    throw_on_error(spmv_hip_mcgs_plan_sizes(M->M->plan(), sizes),
+                   "spmv_hip_mcgs_plan_sizes");
+  });
+}
+
+int spmvh_sgs_export(spmvh_sgs* M, int32_t* perm, int32_t* color_start,
+                     double* dinv, void* const* before, void* const* after)
+{
+  return guarded([&] {
+    require(M != nullptr, "NULL argument");
+    auto part_of = [](void* const* q) {
+      return spmv_hip_mcgs_export{
+          (int32_t*)q[0], (int32_t*)q[1], (int64_t*)q[2],  (int32_t*)q[3],
+          (int32_t*)q[4], (double*)q[5],  (int32_t*)q[6],  (int32_t*)q[7],
+          (int64_t*)q[8], (int32_t*)q[9], (double*)q[10]};
+    };
+    spmv_hip_mcgs_export b{}, a{};
+    if (before)
+      b = part_of(before);
+    if (after)
+      a = part_of(after);
+    throw_on_error(spmv_hip_mcgs_plan_export(M->M->plan(), perm, color_start,
+                                             dinv, before ? &b : nullptr,
+                                             after ? &a : nullptr),
+                   "spmv_hip_mcgs_plan_export");
   });
 }
 

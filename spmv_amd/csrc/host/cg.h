@@ -501,17 +501,56 @@ double lambda_max_estimate(const Comm& comm, HipExecutor& exec,
 // range on the rank, as for Matrix::diagonal (std::runtime_error).  A diagonal
 // entry that is not finite or not > 0 throws with jacobi_inverse's message
 // ("... diagonal is not positive ...").
+//
+// SgsOptions chooses where that setup runs.  setup = host (the default, and the
+// two-argument constructor) is the path above.  setup = device reads nothing of
+// the matrix back: the block is coloured where it lies (spmv_hip_mcgs_color:
+// greedy first-fit in a priority order, Jones-Plassmann rounds) and the plan is
+// built from the device arrays (spmv_hip_mcgs_plan_build: every array equal to
+// what the host builder makes from the same colours); only counters and the
+// tables of num_colors + 1 entries cross to the host.  order = hashed (the
+// default) colours in a pseudo-random order -- a handful of rounds, but more
+// colours than the host's greedy (7-point Poisson: 6 against 2, so 11 launches
+// per application against 3, and another iteration count); order = natural is
+// the host's colouring entry for entry, in as many rounds as the longest
+// ascending path of the pattern (about 3 n for Poisson n^3): slow on long
+// dependency chains.  colors (host, rows entries, 0-based, every colour up to
+// the largest worn, proper on B + B^T) replaces the colouring; it is checked
+// on the device ("the colouring is not proper", "colour").  The entry checks
+// and messages are the same on both paths.  setup = host with colors, or with
+// an order other than the default, throws std::invalid_argument: the host
+// builder colours by itself.
+enum class SgsSetup { host, device };
+enum class SgsOrder { hashed, natural };
+struct SgsOptions {
+  SgsSetup setup = SgsSetup::host;
+  SgsOrder order = SgsOrder::hashed;
+  const int32_t* colors = nullptr;
+};
+
 class SgsPreconditioner
 {
 public:
   SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A);
+  SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A,
+                    const SgsOptions& options);
   virtual ~SgsPreconditioner();
   SgsPreconditioner(const SgsPreconditioner&) = delete;
   SgsPreconditioner& operator=(const SgsPreconditioner&) = delete;
 
-  int rows() const { return (int)_colors.size(); }
+  int rows() const { return _rows; }
   int num_colors() const { return _num_colors; }
-  void colors(int32_t* out) const;    // host copy, rows() entries
+  // host copy, rows() entries (setup = device: fetched from the plan on the
+  // first call)
+  void colors(int32_t* out) const;
+  // rounds of the device colouring (0: host setup, or colours of the caller's)
+  int rounds() const { return _rounds; }
+  // wall time of the constructor; of which colouring and plan (device setup)
+  double setup_ms() const { return _setup_ms; }
+  double color_ms() const { return _color_ms; }
+  double build_ms() const { return _build_ms; }
+  // peak device memory of the device setup's temporaries (0: host setup)
+  int64_t setup_temp_bytes() const { return _temp_bytes; }
   virtual int64_t plan_bytes() const; // device memory of the plan
   // the plan the sweeps run on (a derived class may refuse: check_usable)
   spmv_hip_mcgs_plan* plan() const
@@ -535,7 +574,15 @@ protected:
   spmv_hip_mcgs_plan* _plan = nullptr;
   bool _owns_plan = true;
   int _num_colors = 0;
-  std::vector<int32_t> _colors;
+  int _rows = 0;
+  mutable std::vector<int32_t> _colors; // (device setup: empty until asked for)
+
+private:
+  void build_on_host(const Matrix<double>& A);
+  void build_on_device(const Matrix<double>& A, const SgsOptions& options);
+  int _rounds = 0;
+  double _setup_ms = 0, _color_ms = 0, _build_ms = 0;
+  int64_t _temp_bytes = 0;
 };
 
 // ---- Multicolour ILU(0), factored on the device ---------------------------------

@@ -2,7 +2,11 @@
 // symmetric Gauss-Seidel preconditioner for HipExecutor: see cg.h.
 #include "cg.h"
 
+#include <algorithm>
+#include <chrono>
 #include <initializer_list>
+#include <limits>
+#include <string>
 #include <type_traits>
 #include <utility>
 
@@ -492,8 +496,10 @@ int pcg_chebyshev(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
       });
 }
 
-SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A)
-    : _exec(exec)
+namespace
+{
+// the entry checks of both setup paths -> the local block
+const CSRMatrix<double>* sgs_local_block(const Matrix<double>& A)
 {
   std::shared_ptr<L2GMap> row_map = A.row_map();
   std::shared_ptr<const L2GMap> col_map = A.col_map();
@@ -512,6 +518,139 @@ SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A)
         "spmv::SgsPreconditioner - Error: the CSR arrays of this matrix were "
         "released (release_csr); build the preconditioner before releasing "
         "them");
+  return blk;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0)
+{
+  return std::chrono::duration<double, std::milli>(
+             std::chrono::steady_clock::now() - t0)
+      .count();
+}
+
+[[noreturn]] void throw_bad_diagonal(int64_t bad, int64_t n)
+{
+  // jacobi_inverse's rule and message
+  throw std::runtime_error(
+      "spmv::SgsPreconditioner - Error: the diagonal is not positive ("
+      + std::to_string(bad) + " of " + std::to_string(n)
+      + " entries are not finite or not > 0)");
+}
+} // namespace
+
+SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A)
+    : _exec(exec)
+{
+  build_on_host(A);
+}
+
+SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A,
+                                     const SgsOptions& options)
+    : _exec(exec)
+{
+  if (options.setup == SgsSetup::host) {
+    if (options.colors || options.order != SgsOrder::hashed)
+      throw std::invalid_argument(
+          "spmv::SgsPreconditioner - Error: setup = host colours by itself: it "
+          "takes neither colors nor an order");
+    build_on_host(A);
+    return;
+  }
+  try {
+    build_on_device(A, options);
+  } catch (...) { // (the destructor does not run)
+    spmv_hip_mcgs_plan_destroy(_plan);
+    throw;
+  }
+}
+
+void SgsPreconditioner::build_on_device(const Matrix<double>& A,
+                                        const SgsOptions& options)
+{
+  const auto t0 = std::chrono::steady_clock::now();
+  const CSRMatrix<double>* blk = sgs_local_block(A);
+  const int64_t n = A.row_map()->local_size();
+  const int64_t nnz = blk->non_zeros();
+  const bool symmetric = A.symmetric();
+  if (n >= std::numeric_limits<int32_t>::max() || blk->cols() < n)
+    throw std::runtime_error(
+        "spmv::SgsPreconditioner - Error: rows and owned columns are not the "
+        "same index range on this rank");
+  spmv_hip_ctx* ctx = _exec.context();
+  // an empty block owns no arrays
+  const int32_t* rowptr = nnz > 0 ? blk->rowptr() : nullptr;
+  const int32_t* colind = nnz > 0 ? blk->colind() : nullptr;
+  const double* values = nnz > 0 ? blk->values() : nullptr;
+
+  struct DeviceInts { // the colours, for the time of the setup
+    HipExecutor& exec;
+    int32_t* p = nullptr;
+    ~DeviceInts()
+    {
+      if (p)
+        exec.free(p);
+    }
+  } d_colors{_exec};
+  if (n > 0)
+    d_colors.p = _exec.alloc<int32_t>((size_t)n);
+  int num_colors = 0;
+  if (options.colors) {
+    int32_t lo = 0, hi = -1;
+    for (int64_t i = 0; i < n; ++i) {
+      lo = std::min(lo, options.colors[i]);
+      hi = std::max(hi, options.colors[i]);
+    }
+    if (lo < 0)
+      throw std::runtime_error(
+          "spmv::SgsPreconditioner - Error: a colour is negative");
+    num_colors = hi + 1;
+    if (n > 0)
+      _exec.copy_from<int32_t>(d_colors.p, _exec.get_host(), options.colors,
+                               (size_t)n);
+  } else {
+    throw_on_error(
+        spmv_hip_mcgs_color(ctx, (int32_t)n, blk->cols(), nnz, rowptr, colind,
+                            symmetric ? 1 : 0,
+                            options.order == SgsOrder::natural
+                                ? SPMV_HIP_MCGS_NATURAL
+                                : SPMV_HIP_MCGS_HASHED,
+                            d_colors.p, &num_colors, &_rounds, nullptr),
+        "spmv_hip_mcgs_color");
+  }
+  _color_ms = ms_since(t0);
+
+  int64_t info[SPMV_HIP_MCGS_INFO_WORDS] = {};
+  const int rc = spmv_hip_mcgs_plan_build(
+      ctx, (int32_t)n, blk->cols(), nnz, rowptr, colind, values,
+      symmetric ? blk->diagonal() : nullptr, symmetric ? 1 : 0, d_colors.p,
+      num_colors, kSgsLongThreshold, &_plan, info, nullptr);
+  if (rc == SPMV_HIP_EINVAL && info[1] == SPMV_HIP_MCGS_IMPROPER)
+    throw std::runtime_error(
+        "spmv::sgs_build - Error: the colouring is not proper (row "
+        + std::to_string(info[3]) + ")");
+  if (rc == SPMV_HIP_EINVAL && info[1] == SPMV_HIP_MCGS_UNWORN_COLOR)
+    throw std::runtime_error(
+        "spmv::SgsPreconditioner - Error: a colour below the largest is not "
+        "worn by any row");
+  if (rc == SPMV_HIP_EINVAL && info[1] == SPMV_HIP_MCGS_BAD_COLOR)
+    throw std::runtime_error(
+        "spmv::SgsPreconditioner - Error: a colour is out of range");
+  throw_on_error(rc, "spmv_hip_mcgs_plan_build");
+  if (info[0] != 0)
+    throw_bad_diagonal(info[0], n);
+  _num_colors = num_colors;
+  _rows = (int)n;
+  _temp_bytes = info[2];
+  _setup_ms = ms_since(t0);
+  _build_ms = _setup_ms - _color_ms;
+}
+
+void SgsPreconditioner::build_on_host(const Matrix<double>& A)
+{
+  const auto t0 = std::chrono::steady_clock::now();
+  HipExecutor& exec = _exec;
+  const CSRMatrix<double>* blk = sgs_local_block(A);
+  std::shared_ptr<L2GMap> row_map = A.row_map();
   const int64_t n = row_map->local_size();
   const int64_t nnz = blk->non_zeros();
   const bool symmetric = A.symmetric();
@@ -546,10 +685,7 @@ SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A)
       ++bad;
   }
   if (bad != 0)
-    throw std::runtime_error(
-        "spmv::SgsPreconditioner - Error: the diagonal is not positive ("
-        + std::to_string(bad) + " of " + std::to_string(n)
-        + " entries are not finite or not > 0)");
+    throw_bad_diagonal(bad, n);
 
   auto part_of = [](const SgsSlicedPart& s) {
     return spmv_hip_mcgs_part{s.color_slice.data(), s.slice_pos0.data(),
@@ -575,6 +711,8 @@ SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A)
                  "spmv_hip_mcgs_plan_create");
   _num_colors = hp.num_colors;
   _colors = std::move(hp.colors);
+  _rows = hp.n;
+  _setup_ms = ms_since(t0);
 }
 
 SgsPreconditioner::~SgsPreconditioner()
@@ -594,12 +732,24 @@ void SgsPreconditioner::adopt(spmv_hip_mcgs_plan* plan, int num_colors,
   _plan = plan;
   _num_colors = num_colors;
   _colors = std::move(colors);
+  _rows = (int)_colors.size();
 }
 
 void SgsPreconditioner::colors(int32_t* out) const
 {
-  if (!out && !_colors.empty())
+  if (!out && _rows > 0)
     throw std::runtime_error("spmv::SgsPreconditioner::colors - Error: NULL output");
+  if (_colors.empty() && _rows > 0) {
+    // device setup: the colour of a row is the colour of its position
+    std::vector<int32_t> perm((size_t)_rows), start((size_t)_num_colors + 1);
+    throw_on_error(spmv_hip_mcgs_plan_export(_plan, perm.data(), start.data(),
+                                             nullptr, nullptr, nullptr),
+                   "spmv_hip_mcgs_plan_export");
+    _colors.resize((size_t)_rows);
+    for (int c = 0; c < _num_colors; ++c)
+      for (int32_t pos = start[(size_t)c]; pos < start[(size_t)c + 1]; ++pos)
+        _colors[(size_t)perm[(size_t)pos]] = c;
+  }
   std::copy(_colors.begin(), _colors.end(), out);
 }
 

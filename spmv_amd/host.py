@@ -151,6 +151,11 @@ _PROTOS = {
     "spmvh_sgs_build_get": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "spmvh_sgs_build_destroy": [vp],
     "spmvh_sgs_create": [vp, vp, PTR(vp)],
+    "spmvh_sgs_create_ex": [vp, vp, C.c_int, C.c_int, vp, PTR(vp)],
+    "spmvh_sgs_setup_info": [vp, PTR(C.c_int), PTR(f64)],
+    "spmvh_sgs_setup_detail": [vp, PTR(f64), PTR(f64), PTR(i64)],
+    "spmvh_sgs_export_sizes": [vp, vp],
+    "spmvh_sgs_export": [vp, vp, vp, vp, vp, vp],
     "spmvh_sgs_destroy": [vp],
     "spmvh_sgs_info": [vp, PTR(C.c_int), PTR(C.c_int), PTR(i64)],
     "spmvh_sgs_colors": [vp, vp],
@@ -1096,11 +1101,31 @@ class SgsPreconditioner:
     """spmv::SgsPreconditioner: the multicolour symmetric Gauss-Seidel
     preconditioner of A's local diagonal block.  Owns its copy: A may
     release_csr() afterwards.  Raises SpmvHostError ("diagonal is not
-    positive", "released", "same index range")."""
+    positive", "released", "same index range").
 
-    def __init__(self, exec_, A):
+    setup="host" (the default) reads the block back and colours and reorders
+    it on the host; setup="device" colours it and builds the plan where it
+    lies.  order (device setup only): "hashed" (the default there: few rounds,
+    more colours than the host's greedy) or "natural" (the host's colouring
+    entry for entry; as many rounds as the longest ascending path of the
+    pattern, slow on long dependency chains).  colors (device setup only):
+    rows entries that replace the colouring, checked on the device ("not
+    proper", "colour").  setup="host" with an order or colors raises."""
+
+    _SETUPS = {"host": 0, "device": 1}
+    _ORDERS = {None: -1, "hashed": 0, "natural": 1}
+
+    def __init__(self, exec_, A, setup="host", order=None, colors=None):
         h = vp()
-        call("spmvh_sgs_create", exec_.h, A.h, C.byref(h))
+        if setup == "host" and order is None and colors is None:
+            call("spmvh_sgs_create", exec_.h, A.h, C.byref(h))
+        else:
+            if setup not in self._SETUPS or order not in self._ORDERS:
+                raise ValueError(f"setup {setup!r} / order {order!r}")
+            keep = (None if colors is None
+                    else np.ascontiguousarray(colors, np.int32))
+            call("spmvh_sgs_create_ex", exec_.h, A.h, self._SETUPS[setup],
+                 self._ORDERS[order], _np_ptr(keep), C.byref(h))
         self.h = h
 
     def close(self):
@@ -1126,6 +1151,54 @@ class SgsPreconditioner:
     def colors(self):
         out = np.zeros(self.rows(), np.int32)
         call("spmvh_sgs_colors", self.h, _np_ptr(out))
+        return out
+
+    def rounds(self):
+        """rounds of the device colouring (0: host setup or caller's colours)"""
+        r, ms = C.c_int(), f64()
+        call("spmvh_sgs_setup_info", self.h, C.byref(r), C.byref(ms))
+        return r.value
+
+    def setup_ms(self):
+        """wall time of the constructor"""
+        r, ms = C.c_int(), f64()
+        call("spmvh_sgs_setup_info", self.h, C.byref(r), C.byref(ms))
+        return ms.value
+
+    def setup_detail(self):
+        """device setup -> dict(color_ms, build_ms, temp_bytes); zeros otherwise"""
+        cm, bm, tb = f64(), f64(), i64()
+        call("spmvh_sgs_setup_detail", self.h, C.byref(cm), C.byref(bm),
+             C.byref(tb))
+        return dict(color_ms=cm.value, build_ms=bm.value, temp_bytes=tb.value)
+
+    _PART_KEYS = (("color_slice", np.int32), ("slice_pos0", np.int32),
+                  ("slice_ptr", np.int64), ("len", np.int32), ("col", np.int32),
+                  ("val", np.float64), ("color_long", np.int32),
+                  ("long_pos", np.int32), ("long_ptr", np.int64),
+                  ("long_col", np.int32), ("long_val", np.float64))
+
+    def plan_arrays(self):
+        """the plan's arrays, copied from the device -> dict(perm, color_start,
+        dinv, before, after); a part is a dict of the arrays of SgsSlicedPart
+        (host/sgs_build.h)"""
+        sizes = np.zeros(10, np.int64)
+        call("spmvh_sgs_export_sizes", self.h, _np_ptr(sizes))
+        n, nc, ns = (int(v) for v in sizes[:3])
+        out = dict(perm=np.zeros(n, np.int32),
+                   color_start=np.zeros(nc + 1, np.int32), dinv=np.zeros(n))
+        ptrs = []
+        for h, name in enumerate(("before", "after")):
+            ent, nl, lent = (int(v) for v in sizes[3 + 3 * h:6 + 3 * h])
+            count = dict(color_slice=nc + 1, slice_pos0=ns, slice_ptr=ns + 1,
+                         len=n, col=ent, val=ent, color_long=nc + 1,
+                         long_pos=nl, long_ptr=nl + 1, long_col=lent,
+                         long_val=lent)
+            out[name] = {k: np.zeros(count[k], t) for k, t in self._PART_KEYS}
+            ptrs.append((vp * 11)(*[out[name][k].ctypes.data
+                                    for k, _ in self._PART_KEYS]))
+        call("spmvh_sgs_export", self.h, _np_ptr(out["perm"]),
+             _np_ptr(out["color_start"]), _np_ptr(out["dinv"]), ptrs[0], ptrs[1])
         return out
 
 
