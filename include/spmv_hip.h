@@ -1265,6 +1265,48 @@ int spmv_hip_ilu0_get_pattern(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
 int spmv_hip_ilu0_get_factor(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
                              double* l, double* u, double* d, void* stream);
 
+/* ---- The symbolic setup of ILU(0) on the device (additive, ABI 5) --------------
+ * ilu0_plan_build: the plan ilu0_plan_create would make from the arrays of
+ * host/ilu0_build.h's ilu0_symbolic for the same colours -- every array equal --
+ * from the block's CSR arrays where they lie, under the input rules of
+ * mcgs_plan_build above (device pointers, ghosts ignored, rowptr may be NULL
+ * when nnz == 0, the same checks and reason codes in info[1], info[2] the peak
+ * bytes of the temporaries, info[3] a row of an improper colouring or of a
+ * duplicate).  No value is read: the inner plan's values, padding and dinv are
+ * +0.0 until ilu0_factor writes them, and a diagonal that is not positive is
+ * the factorisation's to count (ilu0_pivots), not this call's.  The parts
+ * ascend by the POSITION of the column.  Two entries of one row with the same
+ * column -- in symmetric storage among the row's stored lower entries and the
+ * mirror images of its column -- are SPMV_HIP_EINVAL with info[1] =
+ * SPMV_HIP_ILU0_DUPLICATE: a factor entry has one source.  src of a mirror
+ * image is the index of the stored lower entry.  A failure leaves nothing
+ * allocated.  The plan serves ilu0_factor, _pivots, _get_pattern, _get_factor,
+ * _mcgs_plan, _plan_bytes and _plan_destroy like one of ilu0_plan_create.
+ *
+ * ilu0_plan_sizes / _export: the part arrays copied to host buffers, for plans
+ * of either builder (the inner plan: mcgs_plan_export on ilu0_mcgs_plan).
+ * sizes[SPMV_HIP_ILU0_SIZES_WORDS] = {rows, entries of before, of after, device
+ * bytes without the inner plan's}.  export: every pointer may be NULL; ptr rows
+ * + 1 (none for 0 rows), cpos / src / slot the part's entries. */
+#define SPMV_HIP_ILU0_DUPLICATE 6
+#define SPMV_HIP_ILU0_SIZES_WORDS 4
+typedef struct spmv_hip_ilu0_export {
+  int64_t* ptr;
+  int32_t* cpos;
+  int32_t* src;
+  int64_t* slot;
+} spmv_hip_ilu0_export;
+int spmv_hip_ilu0_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
+                             int32_t num_cols, int64_t nnz, const int32_t* rowptr,
+                             const int32_t* colind, int symmetric,
+                             const int32_t* colors, int32_t num_colors,
+                             int long_threshold, spmv_hip_ilu0_plan** plan,
+                             int64_t* info, void* stream);
+int spmv_hip_ilu0_plan_sizes(const spmv_hip_ilu0_plan* plan, int64_t* sizes);
+int spmv_hip_ilu0_plan_export(const spmv_hip_ilu0_plan* plan,
+                              const spmv_hip_ilu0_export* before,
+                              const spmv_hip_ilu0_export* after);
+
 /* ---- Aggregation multigrid (spmv::AmgPreconditioner) ---------------------------
  * The device half of one coarsening step of a plain aggregation multigrid
  * hierarchy, fp64, every product, sum, difference and quotient a rounding of

@@ -546,7 +546,17 @@ int spmvh_pcg_block(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
  * spmvh_ilu0_refactor: refactor(A) -- device only; errors "pivot", "released".
  * spmvh_ilu0_info: info[6] = {entries of before, of after, negative pivots,
  * plan bytes, the constructor's symbolic and numeric wall time in microseconds}.
- * spmvh_ilu0_pattern / _factor: the host copies of cg.h (outputs may be NULL). */
+ * spmvh_ilu0_pattern / _factor: the host copies of cg.h (outputs may be NULL).
+ * spmvh_ilu0_create_ex: Ilu0Preconditioner(exec, A, SgsOptions) -- the
+ * arguments and their rules are spmvh_sgs_create_ex's; setup 1 colours the
+ * block and builds the plan on the device (spmv_hip_ilu0_plan_build), nothing
+ * of the matrix is read back; errors say "duplicate", "not proper", "colour",
+ * "pivot".  spmvh_sgs_setup_info / _setup_detail / _export_sizes / _export
+ * answer for the handle.
+ * spmvh_ilu0_export_sizes: sizes[4] = {rows, entries of before, of after, device
+ * bytes without the sweep plan's}; spmvh_ilu0_export: the part arrays of the
+ * device plan, of either setup; before / after: 4 pointers each (ptr rows + 1
+ * int64, cpos int32, src int32, slot int64), every pointer may be NULL. */
 typedef struct spmvh_ilu0_symbolic spmvh_ilu0_symbolic;
 int spmvh_ilu0_symbolic_create(const int32_t* rowptr, const int32_t* colind,
                                int64_t nrows, int64_t ncols_local, int symmetric,
@@ -566,6 +576,10 @@ int spmvh_ilu0_info(spmvh_sgs* M, int64_t* info);
 int spmvh_ilu0_pattern(spmvh_sgs* M, int64_t* before_ptr, int32_t* before_col,
                        int64_t* after_ptr, int32_t* after_col);
 int spmvh_ilu0_factor(spmvh_sgs* M, double* l, double* u, double* d);
+int spmvh_ilu0_create_ex(spmvh_exec* exec, spmvh_matrix* A, int setup, int order,
+                         const int32_t* colors, spmvh_sgs** M);
+int spmvh_ilu0_export_sizes(spmvh_sgs* M, int64_t* sizes);
+int spmvh_ilu0_export(spmvh_sgs* M, void* const* before, void* const* after);
 
 /* ---- BiCGStab (spmv::bicgstab, host/cg.h; not in the reference) -------------
  * spmvh_bicgstab: BiCGStab from x0 = 0 for a matrix that need not be

@@ -3,9 +3,10 @@
 // block in the colour-major ordering; its application is spmv_mcgs.hip's two
 // sweeps on a plan whose values and dinv THIS file writes.
 //
-// The host (host/ilu0_build.h) delivers, per part (before / after) and by
-// POSITION: the row pointer, the position of every entry's column (ascending in
-// a row), the index of its value in the matrix's value array and its slot in
+// The host (host/ilu0_build.h, through ilu0_plan_create) or the device builder
+// (spmv_mcgs_build.hip: ilu0_plan_build) delivers, per part (before / after) and
+// by POSITION: the row pointer, the position of every entry's column (ascending
+// in a row), the index of its value in the matrix's value array and its slot in
 // the sliced layout.  A factorisation is, on one stream and in its order alone:
 //
 //   ilu0_gather   the working values of both parts from the matrix's values
@@ -55,29 +56,8 @@
 #include <new>
 #include <vector>
 
-#include "mcgs_plan.h"
+#include "ilu0_plan.h"
 #include "plan_scratch.h"
-
-struct Ilu0PartDev {
-  int64_t* ptr = nullptr;  // n + 1, by position
-  int32_t* cpos = nullptr; // position of the column
-  int32_t* src = nullptr;  // index into the matrix's values
-  int64_t* slot = nullptr; // >= 0: sliced val; < 0: long_val[~slot]
-  double* w = nullptr;     // the working values = the factor, part-CSR order
-  int64_t count = 0;
-};
-
-struct spmv_hip_ilu0_plan {
-  spmv_hip_ctx* ctx = nullptr;
-  spmv_hip_mcgs_plan* inner = nullptr;
-  int32_t n = 0;
-  int64_t num_values = 0;
-  Ilu0PartDev before, after;
-  double* wd = nullptr;       // n: d~ by position
-  double* wdinv = nullptr;    // n: 1.0 / d~ by position
-  unsigned* counts = nullptr; // {not finite or zero, negative}, 16 bytes
-  int64_t bytes = 0;          // without the inner plan's
-};
 
 namespace
 {
@@ -413,6 +393,43 @@ int spmv_hip_ilu0_plan_bytes(const spmv_hip_ilu0_plan* plan, int64_t* bytes)
 {
   SPMV_REQUIRE(plan && bytes);
   *bytes = plan->bytes + plan->inner->bytes;
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_ilu0_plan_sizes(const spmv_hip_ilu0_plan* plan, int64_t* sizes)
+{
+  SPMV_REQUIRE(plan && sizes);
+  sizes[0] = plan->n;
+  sizes[1] = plan->before.count;
+  sizes[2] = plan->after.count;
+  sizes[3] = plan->bytes;
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_ilu0_plan_export(const spmv_hip_ilu0_plan* plan,
+                              const spmv_hip_ilu0_export* before,
+                              const spmv_hip_ilu0_export* after)
+{
+  SPMV_REQUIRE(plan != nullptr);
+  SPMV_SET_DEVICE(plan->ctx);
+  SPMV_CHECK_HIP(hipStreamSynchronize(plan->ctx->stream));
+  auto fetch = [](void* dst, const void* src, size_t bytes) {
+    return dst && bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)
+                        : hipSuccess;
+  };
+  const size_t n1 = plan->n > 0 ? (size_t)plan->n + 1 : 0;
+  const Ilu0PartDev* parts[2] = {&plan->before, &plan->after};
+  const spmv_hip_ilu0_export* outs[2] = {before, after};
+  for (int h = 0; h < 2; ++h) {
+    const spmv_hip_ilu0_export* o = outs[h];
+    if (!o)
+      continue;
+    const size_t cnt = (size_t)parts[h]->count;
+    SPMV_CHECK_HIP(fetch(o->ptr, parts[h]->ptr, n1 * 8));
+    SPMV_CHECK_HIP(fetch(o->cpos, parts[h]->cpos, cnt * 4));
+    SPMV_CHECK_HIP(fetch(o->src, parts[h]->src, cnt * 4));
+    SPMV_CHECK_HIP(fetch(o->slot, parts[h]->slot, cnt * 8));
+  }
   return SPMV_HIP_OK;
 }
 

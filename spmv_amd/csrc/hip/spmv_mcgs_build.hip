@@ -47,6 +47,21 @@
 //   5 scans of the lengths; the sorted entries scattered into the slices and
 //     the long lists.  Padding is memset: column 0, value +0.0.
 // Temporaries are PlanScratch arrays, gone at return; a failure frees all.
+//
+// ILU(0) PLAN (spmv_hip_ilu0_plan_build).  The same five steps make the plan
+// spmv_ilu0.hip factors on, every array as host/ilu0_build.cpp's ilu0_symbolic
+// and spmv_hip_ilu0_plan_create produce it.  What differs (kIlu / `ilu`):
+//   - no value is read; values, padding and dinv are +0.0 (memset), the
+//     factorisation's to write; a diagonal is not looked at
+//   4 the key's low field is the POSITION of the column: a part ascends by it
+//     (the elimination's order), and the layout holds the column perm[field]
+//   4b adjacent equal keys are two entries of one row with one column -- in
+//     symmetric storage a stored entry and a mirror image, or two of either:
+//     refused (SPMV_HIP_ILU0_DUPLICATE), a factor entry has ONE source
+//   5 the scatter also writes the parts' CSR over positions: cpos, src (the
+//     index of the stored entry, for its mirror image too) and slot, the place
+//     it has just written (index into val, ~index into long_val); ptr is the
+//     scan of the parts' counts
 #include "common.h"
 
 #include <hipcub/hipcub.hpp>
@@ -56,6 +71,7 @@
 #include <vector>
 
 #include "csr_plan.h"
+#include "ilu0_plan.h"
 #include "mcgs_plan.h"
 #include "plan_scratch.h"
 
@@ -225,7 +241,9 @@ __global__ __launch_bounds__(kBlock) void mcgs_color_start_kernel(
 // Per row: the entries of the two parts counted (by position), the colouring
 // proved proper on B + B^T (symmetric storage: the row's stored entries and its
 // column's; general storage: every stored entry is seen from its own row), the
-// diagonal by Matrix::diagonal's rule and its inverse.
+// diagonal by Matrix::diagonal's rule and its inverse.  kIlu: no value is read
+// and dinv stays the placeholder the caller has set.
+template <bool kIlu>
 __global__ __launch_bounds__(kBlock) void mcgs_count_kernel(
     int32_t n, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ colind, const double* __restrict__ values,
@@ -245,7 +263,7 @@ __global__ __launch_bounds__(kBlock) void mcgs_count_kernel(
     double d = 0.0;
     for (int32_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
       const int32_t c = colind[e];
-      if (c == i && !diagonal)
+      if (!kIlu && c == i && !diagonal)
         d = d + values[e];
       if (!off_diagonal(i, c, n, symmetric))
         continue;
@@ -264,11 +282,13 @@ __global__ __launch_bounds__(kBlock) void mcgs_count_kernel(
         nb += cc < ci;
         na += cc > ci;
       }
-    if (diagonal)
-      d = diagonal[i];
-    dinv[i] = 1.0 / d;
-    if (!(d > 0.0) || !isfinite(d))
-      atomicAdd(bad_diag, 1ull);
+    if (!kIlu) {
+      if (diagonal)
+        d = diagonal[i];
+      dinv[i] = 1.0 / d;
+      if (!(d > 0.0) || !isfinite(d))
+        atomicAdd(bad_diag, 1ull);
+    }
     if (improper)
       atomicMin(improper_row, i);
     const int32_t pos = pos_of[i];
@@ -344,8 +364,8 @@ __global__ void mcgs_color_long_kernel(int32_t num_colors,
   }
 }
 
-// Key of an entry: position, part (0 before, 1 after), column; `bits` each for
-// position and column.
+// Key of an entry: position, part (0 before, 1 after), column -- for the ILU(0)
+// plan the POSITION of the column --; `bits` each for position and column.
 __device__ __forceinline__ uint64_t entry_key(int32_t pos, int part, int32_t col,
                                               int bits)
 {
@@ -353,7 +373,9 @@ __device__ __forceinline__ uint64_t entry_key(int32_t pos, int part, int32_t col
 }
 
 // Per row: its entries as keys, in the order "stored entries, then the
-// column's", at first[position]; the payload is the index of the value.
+// column's", at first[position]; the payload is the index of the value (of the
+// stored lower entry, for a mirror image).
+template <bool kIlu>
 __global__ __launch_bounds__(kBlock) void mcgs_expand_kernel(
     int32_t n, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ colind, const int32_t* __restrict__ t_ptr,
@@ -371,7 +393,7 @@ __global__ __launch_bounds__(kBlock) void mcgs_expand_kernel(
       const int32_t c = colind[e];
       if (!off_diagonal(i, c, n, symmetric))
         continue;
-      keys[q] = entry_key(pos, colour[c] > ci, c, bits);
+      keys[q] = entry_key(pos, colour[c] > ci, kIlu ? pos_of[c] : c, bits);
       src[q++] = e;
     }
     if (symmetric && t_ptr)
@@ -379,7 +401,7 @@ __global__ __launch_bounds__(kBlock) void mcgs_expand_kernel(
         const int32_t j = t_row[k];
         if (!off_diagonal_t(i, j, 1))
           continue;
-        keys[q] = entry_key(pos, colour[j] > ci, j, bits);
+        keys[q] = entry_key(pos, colour[j] > ci, kIlu ? pos_of[j] : j, bits);
         src[q++] = t_pos[k];
       }
   }
@@ -396,15 +418,30 @@ struct PartOut {
   double* long_val;
 };
 
+// The ILU(0) plan's own arrays of a part (host/ilu0_build.h's Ilu0Part), CSR
+// over positions.
+struct IluOut {
+  const int64_t* ptr;
+  int32_t* cpos;
+  int32_t* src;
+  int64_t* slot;
+};
+
 // Per sorted entry: into its slice (entry k of lane l at slice_ptr[s] + 64 k +
-// l) or its long row.
+// l) or its long row.  kIlu: the key's low field is the column's position; the
+// layout receives the column perm[position] and NO value (the placeholders are
+// memset, the factorisation writes them), and the entry's position, source and
+// slot (fill_slots' rule: the index into val, or ~index into long_val) go to
+// the part's CSR arrays.
+template <bool kIlu>
 __global__ __launch_bounds__(kBlock) void mcgs_scatter_kernel(
     int64_t num_entries, const uint64_t* __restrict__ keys,
     const int32_t* __restrict__ src, const double* __restrict__ values, int bits,
     int32_t threshold, const int64_t* __restrict__ first,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ colour,
     const int32_t* __restrict__ color_start,
-    const int32_t* __restrict__ color_slice, PartOut before, PartOut after)
+    const int32_t* __restrict__ color_slice, PartOut before, PartOut after,
+    IluOut ilu_before, IluOut ilu_after)
 {
   const uint64_t low = ((uint64_t)1 << bits) - 1;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < num_entries;
@@ -412,24 +449,57 @@ __global__ __launch_bounds__(kBlock) void mcgs_scatter_kernel(
     const uint64_t key = keys[q];
     const int32_t pos = (int32_t)(key >> (bits + 1));
     const int part = (int)((key >> bits) & 1);
-    const int32_t col = (int32_t)(key & low);
-    const double v = values[src[q]];
+    const int32_t field = (int32_t)(key & low);
+    const int32_t col = kIlu ? perm[field] : field;
     const PartOut& out = part ? after : before;
     // the part's k-th entry of the row
     const int64_t k = q - first[pos] - (part ? before.cnt[pos] : 0);
+    int64_t slot;
     if (out.cnt[pos] > threshold) {
       const int64_t at = out.long_ptr[out.long_index[pos]] + k;
       out.long_col[at] = col;
-      out.long_val[at] = v;
+      if (!kIlu)
+        out.long_val[at] = values[src[q]];
+      slot = ~at;
     } else {
       const int32_t c = colour[perm[pos]];
       const int32_t in_colour = pos - color_start[c];
       const int64_t s = color_slice[c] + (in_colour >> 6);
       const int64_t at = out.slice_ptr[s] + 64 * k + (in_colour & 63);
       out.col[at] = col;
-      out.val[at] = v;
+      if (!kIlu)
+        out.val[at] = values[src[q]];
+      slot = at;
+    }
+    if (kIlu) {
+      const IluOut& o = part ? ilu_after : ilu_before;
+      const int64_t e = o.ptr[pos] + k;
+      o.cpos[e] = field;
+      o.src[e] = src[q];
+      o.slot[e] = slot;
     }
   }
+}
+
+// ILU(0): a factor entry has ONE source.  Two entries of a row with the same
+// column are adjacent equal keys after the sort; the smallest such row.
+__global__ __launch_bounds__(kBlock) void ilu0_duplicate_kernel(
+    int64_t num_entries, const uint64_t* __restrict__ keys, int bits,
+    const int32_t* __restrict__ perm, int32_t* __restrict__ duplicate_row)
+{
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1;
+       q < num_entries; q += (int64_t)gridDim.x * blockDim.x)
+    if (keys[q] == keys[q - 1])
+      atomicMin(duplicate_row, perm[(int32_t)(keys[q] >> (bits + 1))]);
+}
+
+// ILU(0): the addends of a part's ptr (int64, by position)
+__global__ __launch_bounds__(kBlock) void ilu0_widen_kernel(
+    int32_t n, const int32_t* __restrict__ cnt, int64_t* __restrict__ out)
+{
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n;
+       p += (int64_t)gridDim.x * blockDim.x)
+    out[p] = cnt[p];
 }
 
 // ---- host side ---------------------------------------------------------------
@@ -682,37 +752,25 @@ int spmv_hip_mcgs_color(spmv_hip_ctx* ctx, int32_t num_rows, int32_t num_cols,
   return SPMV_HIP_OK;
 }
 
-int spmv_hip_mcgs_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
-                             int32_t num_cols, int64_t nnz, const int32_t* rowptr,
-                             const int32_t* colind, const double* values,
-                             const double* diagonal, int symmetric,
-                             const int32_t* colors, int32_t num_colors,
-                             int long_threshold, spmv_hip_mcgs_plan** plan,
-                             int64_t* info, void* stream)
-{
-  SPMV_REQUIRE(ctx && plan && info);
-  *plan = nullptr;
-  for (int k = 0; k < SPMV_HIP_MCGS_INFO_WORDS; ++k)
-    info[k] = 0;
-  SPMV_REQUIRE(args_ok(num_rows, num_cols, nnz, rowptr, colind));
-  SPMV_REQUIRE(nnz == 0 || values);
-  SPMV_REQUIRE(long_threshold >= 0 && num_colors >= 0);
-  SPMV_REQUIRE((num_rows == 0) == (num_colors == 0));
-  SPMV_REQUIRE(num_rows == 0 || colors);
-  SPMV_REQUIRE(!symmetric || num_rows == 0 || diagonal);
-  SPMV_SET_DEVICE(ctx);
-  hipStream_t st = spmv_stream(ctx, stream);
-  const int32_t n = num_rows, C = num_colors;
-  const int sym = symmetric ? 1 : 0;
-  if (!sym)
-    diagonal = nullptr;
-  TempBytes book;
+} // extern "C"
 
-  PlanDeleter guard;
-  guard.p = new (std::nothrow) spmv_hip_mcgs_plan();
-  if (!guard.p)
-    return SPMV_HIP_ENOMEM;
-  spmv_hip_mcgs_plan* p = guard.p;
+namespace
+{
+
+// The builder of both plans, after the callers' argument checks, into `p` (the
+// caller's to destroy on failure).  ilu == nullptr: the sweep plan of
+// spmv_hip_mcgs_plan_build.  Otherwise the inner plan of an ILU(0) plan and
+// the part arrays of `ilu` (ptr, cpos, src, slot; count): the entries ascend by
+// the column's POSITION, a duplicate is refused, no value is read (values and
+// diagonal are NULL) and every value, padding and dinv is +0.0.
+int build_plan(spmv_hip_ctx* ctx, int32_t n, int32_t num_cols, int64_t nnz,
+               const int32_t* rowptr, const int32_t* colind,
+               const double* values, const double* diagonal, int sym,
+               const int32_t* colors, int32_t C, int long_threshold,
+               spmv_hip_mcgs_plan* p, spmv_hip_ilu0_plan* ilu, int64_t* info,
+               hipStream_t st)
+{
+  TempBytes book;
   p->ctx = ctx;
   p->n = n;
   p->num_colors = C;
@@ -803,9 +861,10 @@ int spmv_hip_mcgs_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
     }
     MB_HIP(hipStreamSynchronize(st));
     info[2] = book.peak;
-    *plan = guard.release();
     return SPMV_HIP_OK;
   }
+  if (ilu) // the placeholder: the factorisation writes dinv
+    MB_HIP(hipMemsetAsync(p->dinv, 0, sizeof(double) * (size_t)n, st));
   Temp<int32_t> d_slice_end, d_cslice;
   MB_HIP(d_slice_end.alloc(ns, &book));
   MB_HIP(d_cslice.alloc((size_t)C + 1, &book));
@@ -836,10 +895,11 @@ int spmv_hip_mcgs_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
   const int32_t no_row = INT32_MAX; // (n < INT32_MAX: args_ok)
   MB_HIP(hipMemcpy(improper.get(), &no_row, sizeof(int32_t), hipMemcpyHostToDevice));
   MB_HIP(hipMemsetAsync(bad_diag.get(), 0, sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(mcgs_count_kernel, dim3(grid_n), dim3(kBlock), 0, st, n,
-                     rowptr, colind, values, diagonal, t.ptr, t.row, sym, colors,
-                     pos_of.get(), cnt[0].get(), cnt[1].get(), first.get(),
-                     p->dinv, improper.get(), bad_diag.get());
+  hipLaunchKernelGGL(ilu ? mcgs_count_kernel<true> : mcgs_count_kernel<false>,
+                     dim3(grid_n), dim3(kBlock), 0, st, n, rowptr, colind, values,
+                     diagonal, t.ptr, t.row, sym, colors, pos_of.get(),
+                     cnt[0].get(), cnt[1].get(), first.get(), p->dinv,
+                     improper.get(), bad_diag.get());
   MB_HIP(hipGetLastError());
   int32_t improper_row = 0;
   unsigned long long bad = 0;
@@ -878,6 +938,23 @@ int spmv_hip_mcgs_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
   if (num_entries > INT32_MAX)
     return SPMV_HIP_ERANGE;
 
+  // ILU(0): the parts' own CSR over positions
+  Ilu0PartDev* ilu_parts[2] = {ilu ? &ilu->before : nullptr,
+                               ilu ? &ilu->after : nullptr};
+  if (ilu)
+    for (int h = 0; h < 2; ++h) {
+      Ilu0PartDev* d = ilu_parts[h];
+      MB_HIP(plan_array(&d->ptr, (size_t)n + 1, &ilu->bytes));
+      hipLaunchKernelGGL(ilu0_widen_kernel, dim3(grid_n), dim3(kBlock), 0, st, n,
+                         cnt[h].get(), d->ptr);
+      MB_HIP(hipGetLastError());
+      MB_HIP(scan_in_place(d->ptr, n, st));
+      MB_HIP(plan_fetch(&d->count, d->ptr + n, 1, st));
+      MB_HIP(plan_array(&d->cpos, (size_t)d->count, &ilu->bytes));
+      MB_HIP(plan_array(&d->src, (size_t)d->count, &ilu->bytes));
+      MB_HIP(plan_array(&d->slot, (size_t)d->count, &ilu->bytes));
+    }
+
   // the long lists' tables
   Temp<int32_t> d_clong;
   MB_HIP(d_clong.alloc(2 * ((size_t)C + 1), &book));
@@ -893,6 +970,9 @@ int spmv_hip_mcgs_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
       MB_HIP(hipMemsetAsync(d->col, 0, sizeof(int32_t) * (size_t)sliced[h], st));
       MB_HIP(hipMemsetAsync(d->val, 0, sizeof(double) * (size_t)sliced[h], st));
     }
+    if (ilu && long_entries[h])
+      MB_HIP(hipMemsetAsync(d->long_val, 0,
+                            sizeof(double) * (size_t)long_entries[h], st));
     hipLaunchKernelGGL(mcgs_long_rows_kernel, dim3(grid_n), dim3(kBlock), 0, st,
                        n, d->len, long_index[h].get(), long_first[h].get(),
                        num_long[h], long_entries[h], d->long_pos, d->long_ptr);
@@ -915,9 +995,10 @@ int spmv_hip_mcgs_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
     MB_HIP(keys_sorted.alloc((size_t)num_entries, &book));
     MB_HIP(src.alloc((size_t)num_entries, &book));
     MB_HIP(src_sorted.alloc((size_t)num_entries, &book));
-    hipLaunchKernelGGL(mcgs_expand_kernel, dim3(grid_n), dim3(kBlock), 0, st, n,
-                       rowptr, colind, t.ptr, t.pos, t.row, sym, colors,
-                       pos_of.get(), first.get(), bits, keys.get(), src.get());
+    hipLaunchKernelGGL(ilu ? mcgs_expand_kernel<true> : mcgs_expand_kernel<false>,
+                       dim3(grid_n), dim3(kBlock), 0, st, n, rowptr, colind, t.ptr,
+                       t.pos, t.row, sym, colors, pos_of.get(), first.get(), bits,
+                       keys.get(), src.get());
     MB_HIP(hipGetLastError());
     CubTemp tmp;
     MB_HIP(tmp.run(&book, [&](void* tm, size_t& tb) {
@@ -925,21 +1006,135 @@ int spmv_hip_mcgs_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
           tm, tb, keys.get(), keys_sorted.get(), src.get(), src_sorted.get(),
           (int)num_entries, 0, 2 * bits + 1, st);
     }));
+    const int grid_e = spmv_grid_for(ctx, num_entries, kBlock);
+    if (ilu) { // (`improper` has done its work and holds INT32_MAX)
+      hipLaunchKernelGGL(ilu0_duplicate_kernel, dim3(grid_e), dim3(kBlock), 0, st,
+                         num_entries, keys_sorted.get(), bits, p->perm,
+                         improper.get());
+      MB_HIP(hipGetLastError());
+      int32_t duplicate_row = 0;
+      MB_HIP(plan_fetch(&duplicate_row, improper.get(), 1, st));
+      if (duplicate_row < n) {
+        info[1] = SPMV_HIP_ILU0_DUPLICATE;
+        info[3] = duplicate_row;
+        return SPMV_HIP_EINVAL;
+      }
+    }
     PartOut out[2];
-    for (int h = 0; h < 2; ++h)
+    IluOut iout[2] = {};
+    for (int h = 0; h < 2; ++h) {
       out[h] = PartOut{cnt[h].get(),       long_index[h].get(), parts[h]->slice_ptr,
                        parts[h]->long_ptr, parts[h]->col,       parts[h]->val,
                        parts[h]->long_col, parts[h]->long_val};
-    hipLaunchKernelGGL(mcgs_scatter_kernel,
-                       dim3(spmv_grid_for(ctx, num_entries, kBlock)), dim3(kBlock),
-                       0, st, num_entries, keys_sorted.get(), src_sorted.get(),
-                       values, bits, (int32_t)long_threshold, first.get(), p->perm,
-                       colors, d_cstart.get(), d_cslice.get(), out[0], out[1]);
+      if (ilu)
+        iout[h] = IluOut{ilu_parts[h]->ptr, ilu_parts[h]->cpos, ilu_parts[h]->src,
+                         ilu_parts[h]->slot};
+    }
+    hipLaunchKernelGGL(ilu ? mcgs_scatter_kernel<true> : mcgs_scatter_kernel<false>,
+                       dim3(grid_e), dim3(kBlock), 0, st, num_entries,
+                       keys_sorted.get(), src_sorted.get(), values, bits,
+                       (int32_t)long_threshold, first.get(), p->perm, colors,
+                       d_cstart.get(), d_cslice.get(), out[0], out[1], iout[0],
+                       iout[1]);
     MB_HIP(hipGetLastError());
     MB_HIP(hipStreamSynchronize(st)); // the temporaries go with this scope
   }
   MB_HIP(hipStreamSynchronize(st));
   info[2] = book.peak;
+  return SPMV_HIP_OK;
+}
+
+struct Ilu0PlanDeleter {
+  spmv_hip_ilu0_plan* p = nullptr;
+  ~Ilu0PlanDeleter() { spmv_hip_ilu0_plan_destroy(p); }
+  spmv_hip_ilu0_plan* release()
+  {
+    spmv_hip_ilu0_plan* q = p;
+    p = nullptr;
+    return q;
+  }
+};
+
+} // namespace
+
+extern "C" {
+
+int spmv_hip_mcgs_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
+                             int32_t num_cols, int64_t nnz, const int32_t* rowptr,
+                             const int32_t* colind, const double* values,
+                             const double* diagonal, int symmetric,
+                             const int32_t* colors, int32_t num_colors,
+                             int long_threshold, spmv_hip_mcgs_plan** plan,
+                             int64_t* info, void* stream)
+{
+  SPMV_REQUIRE(ctx && plan && info);
+  *plan = nullptr;
+  for (int k = 0; k < SPMV_HIP_MCGS_INFO_WORDS; ++k)
+    info[k] = 0;
+  SPMV_REQUIRE(args_ok(num_rows, num_cols, nnz, rowptr, colind));
+  SPMV_REQUIRE(nnz == 0 || values);
+  SPMV_REQUIRE(long_threshold >= 0 && num_colors >= 0);
+  SPMV_REQUIRE((num_rows == 0) == (num_colors == 0));
+  SPMV_REQUIRE(num_rows == 0 || colors);
+  SPMV_REQUIRE(!symmetric || num_rows == 0 || diagonal);
+  SPMV_SET_DEVICE(ctx);
+  hipStream_t st = spmv_stream(ctx, stream);
+  const int sym = symmetric ? 1 : 0;
+  if (!sym)
+    diagonal = nullptr;
+  PlanDeleter guard;
+  guard.p = new (std::nothrow) spmv_hip_mcgs_plan();
+  if (!guard.p)
+    return SPMV_HIP_ENOMEM;
+  const int rc = build_plan(ctx, num_rows, num_cols, nnz, rowptr, colind, values,
+                            diagonal, sym, colors, num_colors, long_threshold,
+                            guard.p, nullptr, info, st);
+  if (rc == SPMV_HIP_OK)
+    *plan = guard.release();
+  return rc;
+}
+
+int spmv_hip_ilu0_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
+                             int32_t num_cols, int64_t nnz, const int32_t* rowptr,
+                             const int32_t* colind, int symmetric,
+                             const int32_t* colors, int32_t num_colors,
+                             int long_threshold, spmv_hip_ilu0_plan** plan,
+                             int64_t* info, void* stream)
+{
+  SPMV_REQUIRE(ctx && plan && info);
+  *plan = nullptr;
+  for (int k = 0; k < SPMV_HIP_MCGS_INFO_WORDS; ++k)
+    info[k] = 0;
+  SPMV_REQUIRE(args_ok(num_rows, num_cols, nnz, rowptr, colind));
+  SPMV_REQUIRE(long_threshold >= 0 && num_colors >= 0);
+  SPMV_REQUIRE((num_rows == 0) == (num_colors == 0));
+  SPMV_REQUIRE(num_rows == 0 || colors);
+  SPMV_SET_DEVICE(ctx);
+  hipStream_t st = spmv_stream(ctx, stream);
+  Ilu0PlanDeleter guard; // (destroys the inner plan with its owner)
+  guard.p = new (std::nothrow) spmv_hip_ilu0_plan();
+  if (!guard.p)
+    return SPMV_HIP_ENOMEM;
+  spmv_hip_ilu0_plan* p = guard.p;
+  p->ctx = ctx;
+  p->n = num_rows;
+  p->num_values = nnz;
+  p->inner = new (std::nothrow) spmv_hip_mcgs_plan();
+  if (!p->inner)
+    return SPMV_HIP_ENOMEM;
+  p->inner->ctx = ctx;
+  const int rc = build_plan(ctx, num_rows, num_cols, nnz, rowptr, colind, nullptr,
+                            nullptr, symmetric ? 1 : 0, colors, num_colors,
+                            long_threshold, p->inner, p, info, st);
+  if (rc != SPMV_HIP_OK)
+    return rc;
+  // the working arrays, as ilu0_plan_create reserves them
+  const size_t n = (size_t)num_rows;
+  MB_HIP(plan_array(&p->before.w, (size_t)p->before.count, &p->bytes));
+  MB_HIP(plan_array(&p->after.w, (size_t)p->after.count, &p->bytes));
+  MB_HIP(plan_array(&p->wd, n, &p->bytes));
+  MB_HIP(plan_array(&p->wdinv, n, &p->bytes));
+  MB_HIP(plan_array(&p->counts, (size_t)4, &p->bytes));
   *plan = guard.release();
   return SPMV_HIP_OK;
 }

@@ -1616,6 +1616,30 @@ int spmvh_ilu0_create(spmvh_exec* exec, spmvh_matrix* A, spmvh_sgs** M)
   });
 }
 
+int spmvh_ilu0_create_ex(spmvh_exec* exec, spmvh_matrix* A, int setup, int order,
+                         const int32_t* colors, spmvh_sgs** M)
+{
+  return guarded([&] {
+    // the rules of spmvh_sgs_create_ex
+    require(setup == 0 || setup == 1, "setup: 0 (host) or 1 (device)");
+    require(order >= -1 && order <= 1,
+            "order: -1 (default), 0 (hashed) or 1 (natural)");
+    require(setup == 1 || (order == -1 && !colors),
+            "setup = host colours by itself: it takes neither colors nor an "
+            "order");
+    require(exec && A && M, "NULL argument");
+    require(exec->hip != nullptr, "not a HipExecutor");
+    SgsOptions opt;
+    opt.setup = setup == 1 ? SgsSetup::device : SgsSetup::host;
+    opt.order = order == 1 ? SgsOrder::natural : SgsOrder::hashed;
+    opt.colors = colors;
+    auto m = std::make_unique<spmvh_sgs>();
+    m->exec = exec->hip;
+    m->M.reset(new Ilu0Preconditioner(*exec->hip, *A->A, opt));
+    *M = m.release();
+  });
+}
+
 namespace
 {
 Ilu0Preconditioner& ilu0_of(spmvh_sgs* M)
@@ -1660,6 +1684,34 @@ int spmvh_ilu0_pattern(spmvh_sgs* M, int64_t* before_ptr, int32_t* before_col,
 int spmvh_ilu0_factor(spmvh_sgs* M, double* l, double* u, double* d)
 {
   return guarded([&] { ilu0_of(M).factor(l, u, d); });
+}
+
+int spmvh_ilu0_export_sizes(spmvh_sgs* M, int64_t* sizes)
+{
+  return guarded([&] {
+    require(sizes != nullptr, "NULL argument");
+    throw_on_error(spmv_hip_ilu0_plan_sizes(ilu0_of(M).ilu_plan(), sizes),
+                   "spmv_hip_ilu0_plan_sizes");
+  });
+}
+
+int spmvh_ilu0_export(spmvh_sgs* M, void* const* before, void* const* after)
+{
+  return guarded([&] {
+    auto part_of = [](void* const* q) {
+      return spmv_hip_ilu0_export{(int64_t*)q[0], (int32_t*)q[1], (int32_t*)q[2],
+                                  (int64_t*)q[3]};
+    };
+    spmv_hip_ilu0_export b{}, a{};
+    if (before)
+      b = part_of(before);
+    if (after)
+      a = part_of(after);
+    throw_on_error(spmv_hip_ilu0_plan_export(ilu0_of(M).ilu_plan(),
+                                             before ? &b : nullptr,
+                                             after ? &a : nullptr),
+                   "spmv_hip_ilu0_plan_export");
+  });
 }
 
 int spmvh_sgs_workspace_create(spmvh_exec* exec, spmvh_sgs_workspace** ws)

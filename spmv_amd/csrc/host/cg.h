@@ -3,6 +3,7 @@
 #pragma once
 
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 #include <initializer_list>
 #include <memory>
@@ -567,6 +568,12 @@ protected:
   explicit SgsPreconditioner(HipExecutor& exec) : _exec(exec), _owns_plan(false) {}
   void adopt(spmv_hip_mcgs_plan* plan, int num_colors,
              std::vector<int32_t> colors);
+  // ... of a plan built on the device: colors() fetches them when asked
+  void adopt(spmv_hip_mcgs_plan* plan, int num_colors, int rows);
+  // what rounds(), color_ms(), build_ms() (setup_ms() their sum) and
+  // setup_temp_bytes() answer for a derived class's device setup
+  void set_setup_record(int rounds, double color_ms, double build_ms,
+                        int64_t temp_bytes);
   // called by plan(): throws when the plan must not be used now
   virtual void check_usable() const {}
 
@@ -630,11 +637,30 @@ private:
 // arrays ("released"); release_csr() afterwards is fine until the next
 // refactor.  refactor checks rows, storage and the number of stored entries;
 // that the pattern is the same is the caller's promise.
+//
+// SgsOptions (above) chooses where the symbolic half runs.  setup = host (the
+// default, and the two-argument constructor) is the path above; with colors or
+// an order it throws std::invalid_argument.  setup = device reads nothing of
+// the matrix back: spmv_hip_mcgs_color colours the block (hashed or natural) or
+// the caller's colors are taken, and spmv_hip_ilu0_plan_build makes every array
+// of the plan from the CSR arrays where they lie, equal to what the host makes
+// from the same colours (order = natural: the host-built object, bit for bit
+// in factor(), sgs_apply, pcg_sgs and gmres).  A duplicate column, an improper
+// colouring and the block rules are refused with the host path's words
+// ("duplicate", "not proper", "same index range", "released"); a diagonal that
+// is not positive is left to the factorisation's pivot counts on both paths.
+// colors() and pattern() fetch the colours from the plan on their first call.
+// rounds(), color_ms(), build_ms() and setup_temp_bytes() describe the device
+// setup; symbolic_ms() is the wall time of colouring and build together.
 class Ilu0Preconditioner : public SgsPreconditioner
 {
 public:
   Ilu0Preconditioner(HipExecutor& exec, const Matrix<double>& A);
+  Ilu0Preconditioner(HipExecutor& exec, const Matrix<double>& A,
+                     const SgsOptions& options);
   ~Ilu0Preconditioner() override;
+  // the device plan, for copies of its part arrays (spmv_hip_ilu0_plan_export)
+  const spmv_hip_ilu0_plan* ilu_plan() const { return _ilu; }
 
   void refactor(const Matrix<double>& A);
   int64_t negative_pivots() const override { return _negative; }
@@ -661,6 +687,11 @@ protected:
   void check_usable() const override;
 
 private:
+  void construct(const Matrix<double>& A, const SgsOptions& options);
+  void symbolic_on_host(const CSRMatrix<double>* blk, int64_t n);
+  void symbolic_on_device(const CSRMatrix<double>* blk, int64_t n,
+                          const SgsOptions& options,
+                          std::chrono::steady_clock::time_point t0);
   void numeric(const Matrix<double>& A);
   bool _usable = true;
 

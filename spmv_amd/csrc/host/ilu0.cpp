@@ -1,12 +1,15 @@
 // spmv::Ilu0Preconditioner for HipExecutor: see cg.h.  The symbolic half is
-// ilu0_build.h's, on the host; the numeric half is spmv_ilu0.hip's, on the
-// device, on the executor's current stream:
+// ilu0_build.h's, on the host, or (SgsOptions::setup = device) the colouring and
+// spmv_hip_ilu0_plan_build of spmv_mcgs_build.hip, on the device; the numeric
+// half is spmv_ilu0.hip's, on the device, on the executor's current stream:
 //     Matrix::diagonal (general storage; symmetric storage has the array)
 //     gather ; C - 1 factor launches ; finish ; scatter
 //     read of the two pivot counts (the one wait)
 #include "cg.h"
 
+#include <algorithm>
 #include <chrono>
+#include <limits>
 #include <string>
 #include <utility>
 
@@ -55,13 +58,58 @@ double ms_since(std::chrono::steady_clock::time_point t0)
 Ilu0Preconditioner::Ilu0Preconditioner(HipExecutor& exec, const Matrix<double>& A)
     : SgsPreconditioner(exec)
 {
+  construct(A, SgsOptions());
+}
+
+Ilu0Preconditioner::Ilu0Preconditioner(HipExecutor& exec, const Matrix<double>& A,
+                                       const SgsOptions& options)
+    : SgsPreconditioner(exec)
+{
+  if (options.setup == SgsSetup::host
+      && (options.colors || options.order != SgsOrder::hashed))
+    throw std::invalid_argument(
+        "spmv::Ilu0Preconditioner - Error: setup = host colours by itself: it "
+        "takes neither colors nor an order");
+  construct(A, options);
+}
+
+void Ilu0Preconditioner::construct(const Matrix<double>& A,
+                                   const SgsOptions& options)
+{
   const CSRMatrix<double>* blk = block_of(A, "");
   const auto t0 = std::chrono::steady_clock::now();
   const int64_t n = A.row_map()->local_size();
-  const int64_t nnz = blk->non_zeros();
   _symmetric = A.symmetric();
-  _num_values = nnz;
+  _num_values = blk->non_zeros();
+  try { // (the destructor does not run)
+    if (options.setup == SgsSetup::host)
+      symbolic_on_host(blk, n);
+    else
+      symbolic_on_device(blk, n, options, t0);
+  } catch (...) {
+    spmv_hip_ilu0_plan_destroy(_ilu);
+    throw;
+  }
+  _symbolic_ms = ms_since(t0);
 
+  const auto t1 = std::chrono::steady_clock::now();
+  try {
+    if (!_symmetric && n > 0)
+      _diag = _exec.alloc<double>((size_t)n);
+    numeric(A);
+  } catch (...) {
+    if (_diag)
+      _exec.free(_diag);
+    spmv_hip_ilu0_plan_destroy(_ilu);
+    throw;
+  }
+  _numeric_ms = ms_since(t1);
+}
+
+void Ilu0Preconditioner::symbolic_on_host(const CSRMatrix<double>* blk, int64_t n)
+{
+  HipExecutor& exec = _exec;
+  const int64_t nnz = blk->non_zeros();
   // the pattern, read back (the copies wait for the device); no values
   const DeviceExecutor& host = exec.get_host();
   std::vector<int32_t> rowptr((size_t)n + 1, 0), colind((size_t)nnz);
@@ -103,20 +151,91 @@ Ilu0Preconditioner::Ilu0Preconditioner(HipExecutor& exec, const Matrix<double>& 
   spmv_hip_mcgs_plan* inner = nullptr;
   spmv_hip_ilu0_mcgs_plan(_ilu, &inner);
   adopt(inner, sym.num_colors, std::move(sym.colors));
-  _symbolic_ms = ms_since(t0);
+}
 
-  const auto t1 = std::chrono::steady_clock::now();
-  try {
-    if (!_symmetric && n > 0)
-      _diag = exec.alloc<double>((size_t)n);
-    numeric(A);
-  } catch (...) {
-    if (_diag)
-      exec.free(_diag);
-    spmv_hip_ilu0_plan_destroy(_ilu);
-    throw;
+// Nothing of the matrix crosses to the host: the colouring of
+// SgsPreconditioner's device setup (or the caller's colours), then
+// spmv_hip_ilu0_plan_build on the arrays where they lie.
+void Ilu0Preconditioner::symbolic_on_device(
+    const CSRMatrix<double>* blk, int64_t n, const SgsOptions& options,
+    std::chrono::steady_clock::time_point t0)
+{
+  const int64_t nnz = blk->non_zeros();
+  if (n >= std::numeric_limits<int32_t>::max() || blk->cols() < n)
+    throw std::runtime_error(
+        "spmv::Ilu0Preconditioner - Error: rows and owned columns are not the "
+        "same index range on this rank");
+  spmv_hip_ctx* ctx = _exec.context();
+  // an empty block owns no arrays
+  const int32_t* rowptr = nnz > 0 ? blk->rowptr() : nullptr;
+  const int32_t* colind = nnz > 0 ? blk->colind() : nullptr;
+
+  struct DeviceInts { // the colours, for the time of the setup
+    HipExecutor& exec;
+    int32_t* p = nullptr;
+    ~DeviceInts()
+    {
+      if (p)
+        exec.free(p);
+    }
+  } d_colors{_exec};
+  if (n > 0)
+    d_colors.p = _exec.alloc<int32_t>((size_t)n);
+  int num_colors = 0, rounds = 0;
+  if (options.colors) {
+    int32_t lo = 0, hi = -1;
+    for (int64_t i = 0; i < n; ++i) {
+      lo = std::min(lo, options.colors[i]);
+      hi = std::max(hi, options.colors[i]);
+    }
+    if (lo < 0)
+      throw std::runtime_error(
+          "spmv::Ilu0Preconditioner - Error: a colour is negative");
+    num_colors = hi + 1;
+    if (n > 0)
+      _exec.copy_from<int32_t>(d_colors.p, _exec.get_host(), options.colors,
+                               (size_t)n);
+  } else {
+    throw_on_error(
+        spmv_hip_mcgs_color(ctx, (int32_t)n, blk->cols(), nnz, rowptr, colind,
+                            _symmetric ? 1 : 0,
+                            options.order == SgsOrder::natural
+                                ? SPMV_HIP_MCGS_NATURAL
+                                : SPMV_HIP_MCGS_HASHED,
+                            d_colors.p, &num_colors, &rounds, nullptr),
+        "spmv_hip_mcgs_color");
   }
-  _numeric_ms = ms_since(t1);
+  const double color_ms = ms_since(t0);
+
+  int64_t info[SPMV_HIP_MCGS_INFO_WORDS] = {};
+  const int rc = spmv_hip_ilu0_plan_build(
+      ctx, (int32_t)n, blk->cols(), nnz, rowptr, colind, _symmetric ? 1 : 0,
+      d_colors.p, num_colors, kSgsLongThreshold, &_ilu, info, nullptr);
+  if (rc == SPMV_HIP_EINVAL && info[1] == SPMV_HIP_ILU0_DUPLICATE)
+    throw std::runtime_error(
+        "spmv::ilu0_symbolic - Error: duplicate column in row "
+        + std::to_string(info[3]) + " of the local diagonal block");
+  if (rc == SPMV_HIP_EINVAL && info[1] == SPMV_HIP_MCGS_IMPROPER)
+    throw std::runtime_error(
+        "spmv::ilu0_symbolic - Error: the colouring is not proper (row "
+        + std::to_string(info[3]) + ")");
+  if (rc == SPMV_HIP_EINVAL && info[1] == SPMV_HIP_MCGS_UNWORN_COLOR)
+    throw std::runtime_error(
+        "spmv::Ilu0Preconditioner - Error: a colour below the largest is not "
+        "worn by any row");
+  if (rc == SPMV_HIP_EINVAL && info[1] == SPMV_HIP_MCGS_BAD_COLOR)
+    throw std::runtime_error(
+        "spmv::Ilu0Preconditioner - Error: a colour is out of range");
+  throw_on_error(rc, "spmv_hip_ilu0_plan_build");
+  int64_t sizes[SPMV_HIP_ILU0_SIZES_WORDS] = {};
+  throw_on_error(spmv_hip_ilu0_plan_sizes(_ilu, sizes), "spmv_hip_ilu0_plan_sizes");
+  _nbefore = sizes[1];
+  _nafter = sizes[2];
+  spmv_hip_mcgs_plan* inner = nullptr;
+  spmv_hip_ilu0_mcgs_plan(_ilu, &inner);
+  // (the colours stay on the device until colors() or pattern() asks)
+  adopt(inner, num_colors, (int)n);
+  set_setup_record(rounds, color_ms, ms_since(t0) - color_ms, info[2]);
 }
 
 Ilu0Preconditioner::~Ilu0Preconditioner()
@@ -193,15 +312,18 @@ void Ilu0Preconditioner::pattern(int64_t* before_ptr, int32_t* before_col,
   throw_on_error(spmv_hip_ilu0_get_pattern(_exec.context(), _ilu, before_ptr,
                                            before_col, after_ptr, after_col),
                  "spmv_hip_ilu0_get_pattern");
-  // positions -> rows: perm, the stable counting sort of the colours
+  // positions -> rows: perm, the stable counting sort of the colours (device
+  // setup: fetched from the plan on the first call)
   const int32_t n = rows();
   std::vector<int32_t> next((size_t)_num_colors + 1, 0), perm((size_t)n);
+  std::vector<int32_t> colour((size_t)n);
+  colors(colour.data());
   for (int32_t i = 0; i < n; ++i)
-    ++next[(size_t)_colors[i] + 1];
+    ++next[(size_t)colour[i] + 1];
   for (int c = 0; c < _num_colors; ++c)
     next[(size_t)c + 1] += next[c];
   for (int32_t i = 0; i < n; ++i)
-    perm[(size_t)next[_colors[i]]++] = i;
+    perm[(size_t)next[colour[i]]++] = i;
   if (before_col)
     for (int64_t e = 0; e < _nbefore; ++e)
       before_col[e] = perm[(size_t)before_col[e]];

@@ -735,6 +735,24 @@ void SgsPreconditioner::adopt(spmv_hip_mcgs_plan* plan, int num_colors,
   _rows = (int)_colors.size();
 }
 
+void SgsPreconditioner::adopt(spmv_hip_mcgs_plan* plan, int num_colors, int rows)
+{
+  _plan = plan;
+  _num_colors = num_colors;
+  _colors.clear();
+  _rows = rows;
+}
+
+void SgsPreconditioner::set_setup_record(int rounds, double color_ms,
+                                         double build_ms, int64_t temp_bytes)
+{
+  _rounds = rounds;
+  _color_ms = color_ms;
+  _build_ms = build_ms;
+  _setup_ms = color_ms + build_ms;
+  _temp_bytes = temp_bytes;
+}
+
 void SgsPreconditioner::colors(int32_t* out) const
 {
   if (!out && _rows > 0)

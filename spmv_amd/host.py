@@ -178,6 +178,9 @@ _PROTOS = {
     "spmvh_ilu0_info": [vp, vp],
     "spmvh_ilu0_pattern": [vp, vp, vp, vp, vp],
     "spmvh_ilu0_factor": [vp, vp, vp, vp],
+    "spmvh_ilu0_create_ex": [vp, vp, C.c_int, C.c_int, vp, PTR(vp)],
+    "spmvh_ilu0_export_sizes": [vp, vp],
+    "spmvh_ilu0_export": [vp, vp, vp],
     "spmvh_amg_check_options": [f64, C.c_int, i64, C.c_int, C.c_int, f64, f64],
     "spmvh_amg_symbolic_create": [vp, vp, vp, vp, i64, i64, C.c_int, f64,
                                   PTR(vp), vp],
@@ -1249,12 +1252,45 @@ class Ilu0Preconditioner(SgsPreconditioner):
     factored on the device (IC(0) as L D L^T for a symmetric A).  Accepted
     wherever an SgsPreconditioner is (sgs_apply, pcg_sgs, gmres(sgs=...)).
     Raises SpmvHostError ("pivot", "duplicate", "released", "same index
-    range")."""
+    range").
 
-    def __init__(self, exec_, A):
+    setup, order and colors are SgsPreconditioner's: setup="host" (the
+    default) does the symbolic work on the host from the pattern read back;
+    setup="device" colours the block and builds every array of the plan where
+    the matrix lies (order="natural": the host-built object bit for bit).
+    setup="host" with an order or colors raises."""
+
+    def __init__(self, exec_, A, setup="host", order=None, colors=None):
         h = vp()
-        call("spmvh_ilu0_create", exec_.h, A.h, C.byref(h))
+        if setup == "host" and order is None and colors is None:
+            call("spmvh_ilu0_create", exec_.h, A.h, C.byref(h))
+        else:
+            if setup not in self._SETUPS or order not in self._ORDERS:
+                raise ValueError(f"setup {setup!r} / order {order!r}")
+            keep = (None if colors is None
+                    else np.ascontiguousarray(colors, np.int32))
+            call("spmvh_ilu0_create_ex", exec_.h, A.h, self._SETUPS[setup],
+                 self._ORDERS[order], _np_ptr(keep), C.byref(h))
         self.h = h
+
+    _ILU_KEYS = (("ptr", np.int64), ("cpos", np.int32), ("src", np.int32),
+                 ("slot", np.int64))
+
+    def ilu_arrays(self):
+        """the part arrays of the device plan, copied from the device ->
+        dict(before, after); a part is dict(ptr, cpos, src, slot), CSR over
+        positions (host/ilu0_build.h's Ilu0Part)"""
+        sizes = np.zeros(4, np.int64)
+        call("spmvh_ilu0_export_sizes", self.h, _np_ptr(sizes))
+        n = int(sizes[0])
+        out, ptrs = {}, []
+        for name, m in (("before", int(sizes[1])), ("after", int(sizes[2]))):
+            count = dict(ptr=n + 1 if n > 0 else 0, cpos=m, src=m, slot=m)
+            out[name] = {k: np.zeros(count[k], t) for k, t in self._ILU_KEYS}
+            ptrs.append((vp * 4)(*[out[name][k].ctypes.data
+                                   for k, _ in self._ILU_KEYS]))
+        call("spmvh_ilu0_export", self.h, ptrs[0], ptrs[1])
+        return out
 
     def refactor(self, A):
         """the numeric factorisation again, on the device alone, for a matrix

@@ -26,6 +26,16 @@ time limit, and the records before it stand.
 
 The driver starts one child process per case under `timeout` and stops at the
 first child that fails, so trouble in one case ends the run.
+
+    python tools/sgssetupbench.py --ilu0    # -> profiles/ilu0setup.json
+
+measures Ilu0Preconditioner the same way: the host constructor (symbolic work
+on the host from the pattern read back) next to the device setup.  Its records
+add symbolic_ms (colouring + build, the part the two paths differ in) and
+numeric_ms (the factorisation, the same kernels on both paths) of the fastest
+construction, host_symbolic_ms and symbolic_ratio (host over this path, same
+process and run), and negative_pivots; sgs_apply_ms is ilu0_apply; a factor
+with negative pivots is not handed to pcg_sgs (iterations null).
 """
 import argparse
 import json
@@ -61,13 +71,15 @@ def run_case(case, args):
               None)
     exec_.synchronize()
     ws = host.SgsWorkspace(exec_)
+    make = host.Ilu0Preconditioner if args.ilu0 else host.SgsPreconditioner
+    host_symbolic_ms = None
     paths = [p for p in PATHS if not args.paths or p[0] in args.paths.split(",")]
     for name, kw in paths:
         best = None
         for rep in range(args.warmup + args.repeats):
             exec_.synchronize()
             t0 = time.perf_counter()
-            M = host.SgsPreconditioner(exec_, A, **kw)
+            M = make(exec_, A, **kw)
             ms = (time.perf_counter() - t0) * 1e3
             if rep >= args.warmup and (best is None or ms < best[0]):
                 if best is not None:
@@ -88,22 +100,33 @@ def run_case(case, args):
             apply_many()
             if rep >= args.warmup:
                 apply_ms.append((time.perf_counter() - t0) * 1e3 / args.apply_reps)
-        sol = []
-        for rep in range(2):
+        sol, k, h = [], None, None
+        for rep in range(0 if args.ilu0 and M.negative_pivots() else 2):
             exec_.synchronize()
             t0 = time.perf_counter()
             k, h = host.pcg_sgs(comm, exec_, A, M, d_b, d_x, args.kmax, args.rtol,
                                 ws)
             sol.append((time.perf_counter() - t0) * 1e3)
+        extra = dict(object_setup_ms=M.setup_ms())
+        if args.ilu0:
+            symbolic_ms, numeric_ms = M.setup_ms()
+            if name == "host":
+                host_symbolic_ms = symbolic_ms
+            extra = dict(symbolic_ms=symbolic_ms, numeric_ms=numeric_ms,
+                         host_symbolic_ms=host_symbolic_ms,
+                         symbolic_ratio=(host_symbolic_ms / symbolic_ms
+                                         if host_symbolic_ms else None),
+                         negative_pivots=M.negative_pivots())
         rec = dict(case=case, path=name, rows=rows, nnz=nnz, repeats=args.repeats,
-                   setup_ms=setup_ms, object_setup_ms=M.setup_ms(),
+                   setup_ms=setup_ms, **extra,
                    color_ms=detail["color_ms"], build_ms=detail["build_ms"],
                    temp_bytes=detail["temp_bytes"], rounds=M.rounds(),
                    colors=M.num_colors(), plan_bytes=M.plan_bytes(),
                    matrix_bytes=A.format_size(), sgs_apply_ms=min(apply_ms),
-                   iterations=k, ms_to_solution=min(sol), rtol=args.rtol,
-                   final_rel_residual=float(h[-1] / h[0]),
-                   converged=bool(h[-1] / h[0] < args.rtol))
+                   iterations=k, ms_to_solution=min(sol) if sol else None,
+                   rtol=args.rtol,
+                   final_rel_residual=float(h[-1] / h[0]) if sol else None,
+                   converged=bool(h[-1] / h[0] < args.rtol) if sol else None)
         print(json.dumps(rec), flush=True)
         M.close()
     ws.close()
@@ -129,10 +152,14 @@ def main():
     ap.add_argument("--only", default=None, help="comma list of cases")
     ap.add_argument("--paths", default=None, help="comma list of paths")
     ap.add_argument("--timeout", type=int, default=540, help="seconds per case")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles",
-                                                  "sgssetup.json"))
+    ap.add_argument("--ilu0", action="store_true",
+                    help="measure Ilu0Preconditioner (-> profiles/ilu0setup.json)")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--case", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "ilu0setup.json" if args.ilu0
+                                else "sgssetup.json")
     if args.case:  # a child: one case in this process
         run_case(args.case, args)
         return 0
@@ -147,6 +174,8 @@ def main():
                "--rtol", str(args.rtol), "--kmax", str(args.kmax)]
         if args.paths:
             cmd += ["--paths", args.paths]
+        if args.ilu0:
+            cmd += ["--ilu0"]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(p.stdout)
         sys.stdout.flush()
