@@ -19,9 +19,9 @@
 // Streaming shape: see blas1_stream.h.
 #include "common.h"
 #include "blas1_stream.h"
+#include "solver_ws.h"
 
 #include <cmath>
-#include <new>
 
 namespace
 {
@@ -704,6 +704,7 @@ int launch_indexed(void (*kernel)(int, const int32_t*, const T*, T*),
 struct spmv_hip_cg_ws {
   spmv_hip_ctx* ctx = nullptr;
   int kmax = 0;
+  SolverArrays own;
   double* rr = nullptr;       // kmax + 1
   double* pAp = nullptr;      // kmax + 1
   double* partials = nullptr; // ctx->dot_blocks
@@ -844,40 +845,18 @@ int spmv_hip_cg_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_cg_ws** out)
 {
   SPMV_SET_DEVICE(ctx);
   SPMV_REQUIRE(out && kmax >= 0);
-  spmv_hip_cg_ws* ws = new (std::nothrow) spmv_hip_cg_ws;
-  if (!ws)
-    return SPMV_HIP_ENOMEM;
-  ws->ctx = ctx;
-  ws->kmax = kmax;
-  hipError_t e = hipMalloc(&ws->rr, sizeof(double) * (kmax + 1));
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->pAp, sizeof(double) * (kmax + 1));
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->partials, sizeof(double) * ctx->dot_blocks);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->partials_rr, sizeof(double) * ctx->dot_blocks);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->sc, sizeof(CgScalars));
-  if (e != hipSuccess) {
-    spmv_hip_cg_ws_destroy(ws);
-    return static_cast<int>(e);
-  }
-  *out = ws;
-  return SPMV_HIP_OK;
+  return solver_ws_create(ctx, kmax, out, [&](spmv_hip_cg_ws& w) {
+    w.own.alloc(w.rr, (size_t)kmax + 1);
+    w.own.alloc(w.pAp, (size_t)kmax + 1);
+    w.own.alloc(w.partials, ctx->dot_blocks);
+    w.own.alloc(w.partials_rr, ctx->dot_blocks);
+    w.own.alloc(w.sc, 1);
+  });
 }
 
 int spmv_hip_cg_ws_destroy(spmv_hip_cg_ws* ws)
 {
-  if (!ws)
-    return SPMV_HIP_OK;
-  (void)hipSetDevice(ws->ctx->device);
-  (void)hipFree(ws->rr);
-  (void)hipFree(ws->pAp);
-  (void)hipFree(ws->partials);
-  (void)hipFree(ws->partials_rr);
-  (void)hipFree(ws->sc);
-  delete ws;
-  return SPMV_HIP_OK;
+  return solver_ws_destroy(ws);
 }
 
 int spmv_hip_cg_ws_reset(spmv_hip_cg_ws* ws, double rtol, void* stream)
@@ -885,9 +864,9 @@ int spmv_hip_cg_ws_reset(spmv_hip_cg_ws* ws, double rtol, void* stream)
   SPMV_REQUIRE(ws);
   SPMV_SET_DEVICE(ws->ctx);
   const int n = ws->kmax + 1;
-  hipLaunchKernelGGL(cg_reset_kernel, dim3((n + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, spmv_stream(ws->ctx, stream), ws->sc,
-                     rtol, ws->rr, ws->pAp, ws->kmax);
+  hipLaunchKernelGGL(cg_reset_kernel, ws_reset_grid(n), dim3(kBlock), 0,
+                     spmv_stream(ws->ctx, stream), ws->sc, rtol, ws->rr,
+                     ws->pAp, ws->kmax);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -922,28 +901,15 @@ int spmv_hip_cg_ws_done_flag(spmv_hip_cg_ws* ws, const int32_t** done)
 
 int spmv_hip_cg_ws_capacity(const spmv_hip_cg_ws* ws, int* kmax)
 {
-  SPMV_REQUIRE(ws && kmax);
-  *kmax = ws->kmax;
-  return SPMV_HIP_OK;
+  return solver_ws_capacity(ws, kmax);
 }
 
 int spmv_hip_cg_ws_read_async(spmv_hip_cg_ws* ws, int32_t* host_done_kstop,
                               double* host_rr, size_t host_rr_len, void* stream)
 {
   SPMV_REQUIRE(ws);
-  // checked before anything is enqueued: a short buffer gets nothing at all
-  SPMV_REQUIRE(!host_rr || host_rr_len >= (size_t)ws->kmax + 1);
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  if (host_done_kstop)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_done_kstop, &ws->sc->done,
-                                  2 * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                  st));
-  if (host_rr)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_rr, ws->rr,
-                                  sizeof(double) * (ws->kmax + 1),
-                                  hipMemcpyDeviceToHost, st));
-  return SPMV_HIP_OK;
+  return ws_read_async(ws->ctx, stream, host_done_kstop, &ws->sc->done, 2,
+                       host_rr, host_rr_len, ws->rr, (size_t)ws->kmax + 1);
 }
 
 int spmv_hip_cg_dot_rr_f64(spmv_hip_ctx* ctx, spmv_hip_cg_ws* ws, int64_t n,

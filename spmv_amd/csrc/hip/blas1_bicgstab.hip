@@ -39,9 +39,9 @@
 // doubles on).
 #include "common.h"
 #include "blas1_stream.h"
+#include "solver_ws.h"
 
 #include <cmath>
-#include <new>
 
 struct BicgScalars {
   double rtol;
@@ -54,6 +54,7 @@ struct BicgScalars {
 struct spmv_hip_bicg_ws {
   spmv_hip_ctx* ctx = nullptr;
   int kmax = 0;
+  SolverArrays own;
   double* rv = nullptr;   // kmax + 1: rhat.v
   double* tstt = nullptr; // [kmax + 1][2]: {ts[k], tt[k]}
   double* rrho = nullptr; // [kmax + 1][2]: {rr[k], rho[k]}
@@ -558,49 +559,20 @@ extern "C" {
 int spmv_hip_bicg_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_bicg_ws** out)
 {
   SPMV_REQUIRE(ctx && out && kmax >= 0);
-  SPMV_SET_DEVICE(ctx);
-  spmv_hip_bicg_ws* ws = new (std::nothrow) spmv_hip_bicg_ws;
-  if (!ws)
-    return SPMV_HIP_ENOMEM;
-  ws->ctx = ctx;
-  ws->kmax = kmax;
-  const size_t hist = sizeof(double) * ((size_t)kmax + 1);
-  const size_t part = sizeof(double) * (size_t)ctx->dot_blocks;
-  hipError_t e = hipMalloc(&ws->rv, hist);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->tstt, 2 * hist);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->rrho, 2 * hist);
-  double** parts[] = {&ws->p_rv, &ws->p_ts, &ws->p_tt, &ws->p_rr, &ws->p_rho};
-  for (double** p : parts)
-    if (e == hipSuccess)
-      e = hipMalloc(p, part);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->sc, sizeof(BicgScalars));
-  if (e != hipSuccess) {
-    spmv_hip_bicg_ws_destroy(ws);
-    return static_cast<int>(e);
-  }
-  *out = ws;
-  return SPMV_HIP_OK;
+  return solver_ws_create(ctx, kmax, out, [&](spmv_hip_bicg_ws& w) {
+    const size_t hist = (size_t)kmax + 1;
+    w.own.alloc(w.rv, hist);
+    w.own.alloc(w.tstt, 2 * hist);
+    w.own.alloc(w.rrho, 2 * hist);
+    for (double** p : {&w.p_rv, &w.p_ts, &w.p_tt, &w.p_rr, &w.p_rho})
+      w.own.alloc(*p, ctx->dot_blocks);
+    w.own.alloc(w.sc, 1);
+  });
 }
 
 int spmv_hip_bicg_ws_destroy(spmv_hip_bicg_ws* ws)
 {
-  if (!ws)
-    return SPMV_HIP_OK;
-  (void)hipSetDevice(ws->ctx->device);
-  (void)hipFree(ws->rv);
-  (void)hipFree(ws->tstt);
-  (void)hipFree(ws->rrho);
-  (void)hipFree(ws->p_rv);
-  (void)hipFree(ws->p_ts);
-  (void)hipFree(ws->p_tt);
-  (void)hipFree(ws->p_rr);
-  (void)hipFree(ws->p_rho);
-  (void)hipFree(ws->sc);
-  delete ws;
-  return SPMV_HIP_OK;
+  return solver_ws_destroy(ws);
 }
 
 int spmv_hip_bicg_ws_reset(spmv_hip_bicg_ws* ws, double rtol, void* stream)
@@ -608,18 +580,16 @@ int spmv_hip_bicg_ws_reset(spmv_hip_bicg_ws* ws, double rtol, void* stream)
   SPMV_REQUIRE(ws);
   SPMV_SET_DEVICE(ws->ctx);
   const int n = ws->kmax + 1;
-  hipLaunchKernelGGL(bicg_reset_kernel, dim3((n + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, spmv_stream(ws->ctx, stream), ws->sc,
-                     rtol, ws->rv, ws->tstt, ws->rrho, ws->kmax);
+  hipLaunchKernelGGL(bicg_reset_kernel, ws_reset_grid(n), dim3(kBlock), 0,
+                     spmv_stream(ws->ctx, stream), ws->sc, rtol, ws->rv,
+                     ws->tstt, ws->rrho, ws->kmax);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
 
 int spmv_hip_bicg_ws_capacity(const spmv_hip_bicg_ws* ws, int* kmax)
 {
-  SPMV_REQUIRE(ws && kmax);
-  *kmax = ws->kmax;
-  return SPMV_HIP_OK;
+  return solver_ws_capacity(ws, kmax);
 }
 
 int spmv_hip_bicg_ws_rv(spmv_hip_bicg_ws* ws, int k, double** slot)
@@ -656,19 +626,9 @@ int spmv_hip_bicg_ws_read_async(spmv_hip_bicg_ws* ws,
                                 void* stream)
 {
   SPMV_REQUIRE(ws);
-  // checked before anything is enqueued: a short buffer gets nothing at all
-  SPMV_REQUIRE(!host_rr_rho || host_rr_rho_len >= 2 * ((size_t)ws->kmax + 1));
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  if (host_done_kstop_status)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_done_kstop_status, &ws->sc->done,
-                                  3 * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                  st));
-  if (host_rr_rho)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_rr_rho, ws->rrho,
-                                  2 * sizeof(double) * ((size_t)ws->kmax + 1),
-                                  hipMemcpyDeviceToHost, st));
-  return SPMV_HIP_OK;
+  return ws_read_async(ws->ctx, stream, host_done_kstop_status, &ws->sc->done,
+                       3, host_rr_rho, host_rr_rho_len, ws->rrho,
+                       2 * ((size_t)ws->kmax + 1));
 }
 
 // ---- kernels ------------------------------------------------------------------

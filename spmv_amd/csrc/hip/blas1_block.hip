@@ -35,15 +35,16 @@
 // with blas1_pcg_block.hip.
 #include "common.h"
 #include "blas1_block.h"
+#include "solver_ws.h"
 
 #include <climits>
 #include <cmath>
-#include <new>
 
 struct spmv_hip_cgb_ws {
   spmv_hip_ctx* ctx = nullptr;
   int kmax = 0;
   int nrhs = 0;
+  SolverArrays own;
   double* rr = nullptr;       // [kmax + 1][nrhs]
   double* pAp = nullptr;      // [kmax + 1][nrhs]
   double* partials = nullptr; // [ctx->dot_blocks][nrhs]
@@ -411,40 +412,19 @@ int spmv_hip_cgb_ws_create(spmv_hip_ctx* ctx, int kmax, int nrhs,
 {
   SPMV_REQUIRE(ctx && out && nrhs_ok(nrhs));
   SPMV_REQUIRE(kmax >= 0 && kmax < INT_MAX / (2 * SPMV_CGB_MAX));
-  SPMV_SET_DEVICE(ctx);
-  spmv_hip_cgb_ws* ws = new (std::nothrow) spmv_hip_cgb_ws;
-  if (!ws)
-    return SPMV_HIP_ENOMEM;
-  ws->ctx = ctx;
-  ws->kmax = kmax;
-  ws->nrhs = nrhs;
-  const size_t hist = sizeof(double) * (size_t)(kmax + 1) * nrhs;
-  hipError_t e = hipMalloc(&ws->rr, hist);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->pAp, hist);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->partials, sizeof(double) * ctx->dot_blocks * nrhs);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->st, sizeof(CgbState));
-  if (e != hipSuccess) {
-    spmv_hip_cgb_ws_destroy(ws);
-    return static_cast<int>(e);
-  }
-  *out = ws;
-  return SPMV_HIP_OK;
+  return solver_ws_create(ctx, kmax, out, [&](spmv_hip_cgb_ws& w) {
+    w.nrhs = nrhs;
+    const size_t hist = (size_t)(kmax + 1) * nrhs;
+    w.own.alloc(w.rr, hist);
+    w.own.alloc(w.pAp, hist);
+    w.own.alloc(w.partials, (size_t)ctx->dot_blocks * nrhs);
+    w.own.alloc(w.st, 1);
+  });
 }
 
 int spmv_hip_cgb_ws_destroy(spmv_hip_cgb_ws* ws)
 {
-  if (!ws)
-    return SPMV_HIP_OK;
-  (void)hipSetDevice(ws->ctx->device);
-  (void)hipFree(ws->rr);
-  (void)hipFree(ws->pAp);
-  (void)hipFree(ws->partials);
-  (void)hipFree(ws->st);
-  delete ws;
-  return SPMV_HIP_OK;
+  return solver_ws_destroy(ws);
 }
 
 int spmv_hip_cgb_ws_reset(spmv_hip_cgb_ws* ws, double rtol, void* stream)
@@ -452,9 +432,9 @@ int spmv_hip_cgb_ws_reset(spmv_hip_cgb_ws* ws, double rtol, void* stream)
   SPMV_REQUIRE(ws);
   SPMV_SET_DEVICE(ws->ctx);
   const int count = (ws->kmax + 1) * ws->nrhs;
-  hipLaunchKernelGGL(cgb_reset_kernel, dim3((count + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, spmv_stream(ws->ctx, stream), ws->st, rtol,
-                     ws->rr, ws->pAp, count);
+  hipLaunchKernelGGL(cgb_reset_kernel, ws_reset_grid(count), dim3(kBlock), 0,
+                     spmv_stream(ws->ctx, stream), ws->st, rtol, ws->rr,
+                     ws->pAp, count);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -500,22 +480,11 @@ int spmv_hip_cgb_ws_read_async(spmv_hip_cgb_ws* ws, int32_t* host_state,
                                size_t host_rr_len, void* stream)
 {
   SPMV_REQUIRE(ws);
-  // checked before anything is enqueued: a short buffer gets nothing at all
+  // a short state buffer gets nothing at all either
   SPMV_REQUIRE(!host_state || host_state_len >= SPMV_HIP_CGB_STATE_WORDS);
-  SPMV_REQUIRE(!host_rr
-               || host_rr_len >= ((size_t)ws->kmax + 1) * (size_t)ws->nrhs);
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  if (host_state)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_state, &ws->st->all_done,
-                                  SPMV_HIP_CGB_STATE_WORDS * sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, st));
-  if (host_rr)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_rr, ws->rr,
-                                  sizeof(double) * ((size_t)ws->kmax + 1)
-                                      * (size_t)ws->nrhs,
-                                  hipMemcpyDeviceToHost, st));
-  return SPMV_HIP_OK;
+  return ws_read_async(ws->ctx, stream, host_state, &ws->st->all_done,
+                       SPMV_HIP_CGB_STATE_WORDS, host_rr, host_rr_len, ws->rr,
+                       ((size_t)ws->kmax + 1) * (size_t)ws->nrhs);
 }
 
 int spmv_hip_cgb_init_f64(spmv_hip_ctx* ctx, spmv_hip_cgb_ws* ws, int64_t M,

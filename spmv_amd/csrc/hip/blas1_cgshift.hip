@@ -47,7 +47,6 @@
 
 #include <cmath>
 #include <cstddef>
-#include <new>
 
 namespace
 {
@@ -391,39 +390,17 @@ extern "C" {
 int spmv_hip_cgs_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_cgs_ws** out)
 {
   SPMV_REQUIRE(ctx && out && kmax >= 0);
-  SPMV_SET_DEVICE(ctx);
-  spmv_hip_cgs_ws* ws = new (std::nothrow) spmv_hip_cgs_ws;
-  if (!ws)
-    return SPMV_HIP_ENOMEM;
-  ws->ctx = ctx;
-  ws->kmax = kmax;
-  hipError_t e
-      = hipMalloc(&ws->hist, sizeof(double) * kCgsMaxNs * ((size_t)kmax + 1));
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->p_pq, sizeof(double) * (size_t)ctx->dot_blocks);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->p_rrn, sizeof(double) * (size_t)ctx->dot_blocks);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->sc, sizeof(CgsScalars));
-  if (e != hipSuccess) {
-    spmv_hip_cgs_ws_destroy(ws);
-    return static_cast<int>(e);
-  }
-  *out = ws;
-  return SPMV_HIP_OK;
+  return solver_ws_create(ctx, kmax, out, [&](spmv_hip_cgs_ws& w) {
+    w.own.alloc(w.hist, kCgsMaxNs * ((size_t)kmax + 1));
+    w.own.alloc(w.p_pq, ctx->dot_blocks);
+    w.own.alloc(w.p_rrn, ctx->dot_blocks);
+    w.own.alloc(w.sc, 1);
+  });
 }
 
 int spmv_hip_cgs_ws_destroy(spmv_hip_cgs_ws* ws)
 {
-  if (!ws)
-    return SPMV_HIP_OK;
-  (void)hipSetDevice(ws->ctx->device);
-  (void)hipFree(ws->hist);
-  (void)hipFree(ws->p_pq);
-  (void)hipFree(ws->p_rrn);
-  (void)hipFree(ws->sc);
-  delete ws;
-  return SPMV_HIP_OK;
+  return solver_ws_destroy(ws);
 }
 
 int spmv_hip_cgs_ws_reset(spmv_hip_cgs_ws* ws, double rtol, int kmax, int ns,
@@ -437,18 +414,16 @@ int spmv_hip_cgs_ws_reset(spmv_hip_cgs_ws* ws, double rtol, int kmax, int ns,
     sh.v[s] = s < ns ? host_shifts[s] : 0.0;
   ws->ns = ns;
   const int n = kCgsMaxNs * (ws->kmax + 1);
-  hipLaunchKernelGGL(cgs_reset_kernel, dim3((n + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, spmv_stream(ws->ctx, stream), ws->sc,
-                     rtol, kmax, ns, sh, ws->hist, n);
+  hipLaunchKernelGGL(cgs_reset_kernel, ws_reset_grid(n), dim3(kBlock), 0,
+                     spmv_stream(ws->ctx, stream), ws->sc, rtol, kmax, ns, sh,
+                     ws->hist, n);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
 
 int spmv_hip_cgs_ws_capacity(const spmv_hip_cgs_ws* ws, int* kmax)
 {
-  SPMV_REQUIRE(ws && kmax);
-  *kmax = ws->kmax;
-  return SPMV_HIP_OK;
+  return solver_ws_capacity(ws, kmax);
 }
 
 int spmv_hip_cgs_ws_array(spmv_hip_cgs_ws* ws, int which, double** p,
@@ -481,19 +456,9 @@ int spmv_hip_cgs_ws_read_async(spmv_hip_cgs_ws* ws, int32_t* host_state,
                                void* stream)
 {
   SPMV_REQUIRE(ws);
-  // checked before anything is enqueued: a short buffer gets nothing at all
-  const size_t len = kCgsMaxNs * ((size_t)ws->kmax + 1);
-  SPMV_REQUIRE(!host_hist || host_hist_len >= len);
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  if (host_state)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_state, &ws->sc->done,
-                                  SPMV_HIP_CGS_STATE_WORDS * sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, st));
-  if (host_hist)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_hist, ws->hist, sizeof(double) * len,
-                                  hipMemcpyDeviceToHost, st));
-  return SPMV_HIP_OK;
+  return ws_read_async(ws->ctx, stream, host_state, &ws->sc->done,
+                       SPMV_HIP_CGS_STATE_WORDS, host_hist, host_hist_len,
+                       ws->hist, kCgsMaxNs * ((size_t)ws->kmax + 1));
 }
 
 int spmv_hip_cgs_ws_set_words(spmv_hip_cgs_ws* ws, const int32_t* host_words,
@@ -513,25 +478,14 @@ int spmv_hip_cgs_ws_set_words(spmv_hip_cgs_ws* ws, const int32_t* host_words,
     SPMV_REQUIRE(w[8 + 2 * kCgsMaxNs + j] >= 0
                  && (w[8 + 2 * kCgsMaxNs + j] & 7) < ns
                  && w[8 + 2 * kCgsMaxNs + j] < 16);
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  SPMV_CHECK_HIP(hipMemcpyAsync(&ws->sc->done, host_words,
-                                kCgsWords * sizeof(int32_t),
-                                hipMemcpyHostToDevice, st));
-  SPMV_CHECK_HIP(hipStreamSynchronize(st)); // the caller's buffer is pageable
-  return SPMV_HIP_OK;
+  return ws_put_words(ws->ctx, stream, &ws->sc->done, host_words, kCgsWords);
 }
 
 int spmv_hip_cgs_ws_get_words(spmv_hip_cgs_ws* ws, int32_t* host_words,
                               void* stream)
 {
   SPMV_REQUIRE(ws && host_words);
-  SPMV_SET_DEVICE(ws->ctx);
-  SPMV_CHECK_HIP(hipMemcpyAsync(host_words, &ws->sc->done,
-                                kCgsWords * sizeof(int32_t),
-                                hipMemcpyDeviceToHost,
-                                spmv_stream(ws->ctx, stream)));
-  return SPMV_HIP_OK;
+  return ws_get_words(ws->ctx, stream, host_words, &ws->sc->done, kCgsWords);
 }
 
 // ---- kernels ------------------------------------------------------------------

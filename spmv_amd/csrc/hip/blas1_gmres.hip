@@ -44,9 +44,9 @@
 // square root above is a rounding of its own.  Streaming shape: blas1_stream.h.
 #include "common.h"
 #include "blas1_stream.h"
+#include "solver_ws.h"
 
 #include <cmath>
-#include <new>
 
 constexpr int kGmresMaxRestart = SPMV_HIP_GMRES_MAX_RESTART; // 64
 constexpr int kGmresGroup = SPMV_HIP_GMRES_GROUP;            // 8 accumulators
@@ -70,6 +70,7 @@ struct GmresScalars {
 struct spmv_hip_gmres_ws {
   spmv_hip_ctx* ctx = nullptr;
   int kmax = 0;             // capacity of hist
+  SolverArrays own;
   double* small = nullptr;  // one allocation: the arrays below up to hist
   double* h = nullptr;      // kGmresMaxRestart: first-pass / summed coefficients
   double* c = nullptr;      // kGmresMaxRestart: second-pass coefficients
@@ -631,48 +632,27 @@ int spmv_hip_gmres_ws_create(spmv_hip_ctx* ctx, int kmax,
                              spmv_hip_gmres_ws** out)
 {
   SPMV_REQUIRE(ctx && out && kmax >= 0);
-  SPMV_SET_DEVICE(ctx);
-  spmv_hip_gmres_ws* ws = new (std::nothrow) spmv_hip_gmres_ws;
-  if (!ws)
-    return SPMV_HIP_ENOMEM;
-  ws->ctx = ctx;
-  ws->kmax = kmax;
   const size_t m = kGmresMaxRestart;
-  hipError_t e
-      = hipMalloc(&ws->small, sizeof(double) * (kGmresSmall + (size_t)kmax + 1));
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->part, sizeof(double) * m * (size_t)ctx->dot_blocks);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->p_ww, sizeof(double) * (size_t)ctx->dot_blocks);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->sc, sizeof(GmresScalars));
-  if (e != hipSuccess) {
-    spmv_hip_gmres_ws_destroy(ws);
-    return static_cast<int>(e);
-  }
-  ws->h = ws->small;
-  ws->c = ws->h + m;
-  ws->cs = ws->c + m;
-  ws->sn = ws->cs + m;
-  ws->y = ws->sn + m;
-  ws->g = ws->y + m; // m + 1
-  ws->R = ws->g + m + 1;
-  ws->hist = ws->R + m * m;
-  *out = ws;
-  return SPMV_HIP_OK;
+  return solver_ws_create(ctx, kmax, out, [&](spmv_hip_gmres_ws& w) {
+    w.own.alloc(w.small, kGmresSmall + (size_t)kmax + 1);
+    w.own.alloc(w.part, m * (size_t)ctx->dot_blocks);
+    w.own.alloc(w.p_ww, ctx->dot_blocks);
+    if (w.own.alloc(w.sc, 1) != 0)
+      return;
+    w.h = w.small;
+    w.c = w.h + m;
+    w.cs = w.c + m;
+    w.sn = w.cs + m;
+    w.y = w.sn + m;
+    w.g = w.y + m; // m + 1
+    w.R = w.g + m + 1;
+    w.hist = w.R + m * m;
+  });
 }
 
 int spmv_hip_gmres_ws_destroy(spmv_hip_gmres_ws* ws)
 {
-  if (!ws)
-    return SPMV_HIP_OK;
-  (void)hipSetDevice(ws->ctx->device);
-  (void)hipFree(ws->small);
-  (void)hipFree(ws->part);
-  (void)hipFree(ws->p_ww);
-  (void)hipFree(ws->sc);
-  delete ws;
-  return SPMV_HIP_OK;
+  return solver_ws_destroy(ws);
 }
 
 int spmv_hip_gmres_ws_reset(spmv_hip_gmres_ws* ws, double rtol, int kmax,
@@ -682,18 +662,16 @@ int spmv_hip_gmres_ws_reset(spmv_hip_gmres_ws* ws, double rtol, int kmax,
   SPMV_REQUIRE(restart >= 1 && restart <= kGmresMaxRestart);
   SPMV_SET_DEVICE(ws->ctx);
   const int n = (int)(kGmresSmall + (size_t)ws->kmax + 1);
-  hipLaunchKernelGGL(gmres_reset_kernel, dim3((n + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, spmv_stream(ws->ctx, stream), ws->sc,
-                     rtol, kmax, restart, ws->small, n);
+  hipLaunchKernelGGL(gmres_reset_kernel, ws_reset_grid(n), dim3(kBlock), 0,
+                     spmv_stream(ws->ctx, stream), ws->sc, rtol, kmax, restart,
+                     ws->small, n);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
 
 int spmv_hip_gmres_ws_capacity(const spmv_hip_gmres_ws* ws, int* kmax)
 {
-  SPMV_REQUIRE(ws && kmax);
-  *kmax = ws->kmax;
-  return SPMV_HIP_OK;
+  return solver_ws_capacity(ws, kmax);
 }
 
 int spmv_hip_gmres_ws_done_flag(spmv_hip_gmres_ws* ws, const int32_t** done)
@@ -737,19 +715,9 @@ int spmv_hip_gmres_ws_read_async(spmv_hip_gmres_ws* ws,
                                  void* stream)
 {
   SPMV_REQUIRE(ws);
-  // checked before anything is enqueued: a short buffer gets nothing at all
-  SPMV_REQUIRE(!host_hist || host_hist_len >= (size_t)ws->kmax + 1);
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  if (host_done_kstop_status_k)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_done_kstop_status_k, &ws->sc->done,
-                                  4 * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                  st));
-  if (host_hist)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_hist, ws->hist,
-                                  sizeof(double) * ((size_t)ws->kmax + 1),
-                                  hipMemcpyDeviceToHost, st));
-  return SPMV_HIP_OK;
+  return ws_read_async(ws->ctx, stream, host_done_kstop_status_k,
+                       &ws->sc->done, 4, host_hist, host_hist_len, ws->hist,
+                       (size_t)ws->kmax + 1);
 }
 
 int spmv_hip_gmres_ws_set_state(spmv_hip_gmres_ws* ws, int k, int jn, int done,
@@ -757,25 +725,16 @@ int spmv_hip_gmres_ws_set_state(spmv_hip_gmres_ws* ws, int k, int jn, int done,
 {
   SPMV_REQUIRE(ws && k >= 0 && k <= ws->kmax && jn >= 0
                && jn <= kGmresMaxRestart);
-  SPMV_SET_DEVICE(ws->ctx);
   const int32_t words[6] = {done ? 1 : 0, done ? k : -1, 0, k, jn,
                             finished ? 1 : 0};
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  SPMV_CHECK_HIP(hipMemcpyAsync(&ws->sc->done, words, sizeof(words),
-                                hipMemcpyHostToDevice, st));
-  SPMV_CHECK_HIP(hipStreamSynchronize(st)); // `words` goes out of scope
-  return SPMV_HIP_OK;
+  return ws_put_words(ws->ctx, stream, &ws->sc->done, words, 6);
 }
 
 int spmv_hip_gmres_ws_get_state(spmv_hip_gmres_ws* ws, int32_t* host_words6,
                                 void* stream)
 {
   SPMV_REQUIRE(ws && host_words6);
-  SPMV_SET_DEVICE(ws->ctx);
-  SPMV_CHECK_HIP(hipMemcpyAsync(host_words6, &ws->sc->done, 6 * sizeof(int32_t),
-                                hipMemcpyDeviceToHost,
-                                spmv_stream(ws->ctx, stream)));
-  return SPMV_HIP_OK;
+  return ws_get_words(ws->ctx, stream, host_words6, &ws->sc->done, 6);
 }
 
 // ---- kernels ------------------------------------------------------------------

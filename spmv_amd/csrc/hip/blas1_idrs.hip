@@ -53,7 +53,6 @@
 
 #include <cmath>
 #include <cstddef>
-#include <new>
 
 namespace
 {
@@ -681,36 +680,16 @@ extern "C" {
 int spmv_hip_idrs_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_idrs_ws** out)
 {
   SPMV_REQUIRE(ctx && out && kmax >= 0);
-  SPMV_SET_DEVICE(ctx);
-  spmv_hip_idrs_ws* ws = new (std::nothrow) spmv_hip_idrs_ws;
-  if (!ws)
-    return SPMV_HIP_ENOMEM;
-  ws->ctx = ctx;
-  ws->kmax = kmax;
-  hipError_t e = hipMalloc(&ws->hist, sizeof(double) * ((size_t)kmax + 1));
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->part,
-                  sizeof(double) * kIdrsRows * (size_t)ctx->dot_blocks);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->sc, sizeof(IdrsScalars));
-  if (e != hipSuccess) {
-    spmv_hip_idrs_ws_destroy(ws);
-    return static_cast<int>(e);
-  }
-  *out = ws;
-  return SPMV_HIP_OK;
+  return solver_ws_create(ctx, kmax, out, [&](spmv_hip_idrs_ws& w) {
+    w.own.alloc(w.hist, (size_t)kmax + 1);
+    w.own.alloc(w.part, kIdrsRows * (size_t)ctx->dot_blocks);
+    w.own.alloc(w.sc, 1);
+  });
 }
 
 int spmv_hip_idrs_ws_destroy(spmv_hip_idrs_ws* ws)
 {
-  if (!ws)
-    return SPMV_HIP_OK;
-  (void)hipSetDevice(ws->ctx->device);
-  (void)hipFree(ws->hist);
-  (void)hipFree(ws->part);
-  (void)hipFree(ws->sc);
-  delete ws;
-  return SPMV_HIP_OK;
+  return solver_ws_destroy(ws);
 }
 
 int spmv_hip_idrs_ws_reset(spmv_hip_idrs_ws* ws, double rtol, double kappa,
@@ -722,18 +701,16 @@ int spmv_hip_idrs_ws_reset(spmv_hip_idrs_ws* ws, double rtol, double kappa,
   ws->s = s;
   ws->seed = seed;
   const int n = ws->kmax + 1;
-  hipLaunchKernelGGL(idrs_reset_kernel, dim3((n + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, spmv_stream(ws->ctx, stream), ws->sc,
-                     rtol, kappa, kmax, s, ws->hist, n);
+  hipLaunchKernelGGL(idrs_reset_kernel, ws_reset_grid(n), dim3(kBlock), 0,
+                     spmv_stream(ws->ctx, stream), ws->sc, rtol, kappa, kmax, s,
+                     ws->hist, n);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
 
 int spmv_hip_idrs_ws_capacity(const spmv_hip_idrs_ws* ws, int* kmax)
 {
-  SPMV_REQUIRE(ws && kmax);
-  *kmax = ws->kmax;
-  return SPMV_HIP_OK;
+  return solver_ws_capacity(ws, kmax);
 }
 
 int spmv_hip_idrs_ws_array(spmv_hip_idrs_ws* ws, int which, double** p,
@@ -764,19 +741,9 @@ int spmv_hip_idrs_ws_read_async(spmv_hip_idrs_ws* ws, int32_t* host_state,
                                 void* stream)
 {
   SPMV_REQUIRE(ws);
-  // checked before anything is enqueued: a short buffer gets nothing at all
-  const size_t len = (size_t)ws->kmax + 1;
-  SPMV_REQUIRE(!host_hist || host_hist_len >= len);
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  if (host_state)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_state, &ws->sc->done,
-                                  SPMV_HIP_IDRS_STATE_WORDS * sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, st));
-  if (host_hist)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_hist, ws->hist, sizeof(double) * len,
-                                  hipMemcpyDeviceToHost, st));
-  return SPMV_HIP_OK;
+  return ws_read_async(ws->ctx, stream, host_state, &ws->sc->done,
+                       SPMV_HIP_IDRS_STATE_WORDS, host_hist, host_hist_len,
+                       ws->hist, (size_t)ws->kmax + 1);
 }
 
 int spmv_hip_idrs_ws_set_words(spmv_hip_idrs_ws* ws, const int32_t* host_words,
@@ -786,25 +753,14 @@ int spmv_hip_idrs_ws_set_words(spmv_hip_idrs_ws* ws, const int32_t* host_words,
   // the words the kernels turn into addresses are checked here
   const int32_t k = host_words[3], kmax = host_words[4], s = host_words[5];
   SPMV_REQUIRE(k >= 0 && kmax >= k && kmax <= ws->kmax && s == ws->s);
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  SPMV_CHECK_HIP(hipMemcpyAsync(&ws->sc->done, host_words,
-                                kIdrsWords * sizeof(int32_t),
-                                hipMemcpyHostToDevice, st));
-  SPMV_CHECK_HIP(hipStreamSynchronize(st)); // the caller's buffer is pageable
-  return SPMV_HIP_OK;
+  return ws_put_words(ws->ctx, stream, &ws->sc->done, host_words, kIdrsWords);
 }
 
 int spmv_hip_idrs_ws_get_words(spmv_hip_idrs_ws* ws, int32_t* host_words,
                                void* stream)
 {
   SPMV_REQUIRE(ws && host_words);
-  SPMV_SET_DEVICE(ws->ctx);
-  SPMV_CHECK_HIP(hipMemcpyAsync(host_words, &ws->sc->done,
-                                kIdrsWords * sizeof(int32_t),
-                                hipMemcpyDeviceToHost,
-                                spmv_stream(ws->ctx, stream)));
-  return SPMV_HIP_OK;
+  return ws_get_words(ws->ctx, stream, host_words, &ws->sc->done, kIdrsWords);
 }
 
 // ---- kernels ------------------------------------------------------------------

@@ -55,7 +55,6 @@
 
 #include <climits>
 #include <cmath>
-#include <new>
 
 namespace
 {
@@ -812,57 +811,27 @@ int spmv_hip_lobpcg_ws_create(spmv_hip_ctx* ctx, int kmax, int nev,
   *out = nullptr;
   SPMV_REQUIRE(ctx && nrhs_ok(nev));
   SPMV_REQUIRE(kmax >= 0 && kmax < INT_MAX / (4 * SPMV_CGB_MAX));
-  SPMV_SET_DEVICE(ctx);
-  spmv_hip_lobpcg_ws* ws = new (std::nothrow) spmv_hip_lobpcg_ws;
-  if (!ws)
-    return SPMV_HIP_ENOMEM;
-  ws->ctx = ctx;
-  ws->kmax = kmax;
-  ws->nev = nev;
-  const int two_per_cu = 2 * ctx->num_cus;
-  ws->gram_cap = two_per_cu < ctx->dot_blocks ? two_per_cu : ctx->dot_blocks;
-  if (ws->gram_cap < 1)
-    ws->gram_cap = 1;
-  const size_t mm2 = 2 * (size_t)(3 * nev) * (3 * nev);
-  hipError_t e
-      = hipMalloc(&ws->hist, sizeof(double) * ((size_t)kmax + 1) * nev);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->theta, sizeof(double) * nev);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->coef, sizeof(double) * 3 * nev * nev);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->gram, sizeof(double) * mm2);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->gpart, sizeof(double) * mm2 * ws->gram_cap);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->rn, sizeof(double) * 2 * nev);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->rpart, sizeof(double) * (size_t)ctx->dot_blocks * nev);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->st, sizeof(LobpcgState));
-  if (e != hipSuccess) {
-    spmv_hip_lobpcg_ws_destroy(ws);
-    return static_cast<int>(e);
-  }
-  *out = ws;
-  return SPMV_HIP_OK;
+  return solver_ws_create(ctx, kmax, out, [&](spmv_hip_lobpcg_ws& w) {
+    w.nev = nev;
+    const int two_per_cu = 2 * ctx->num_cus;
+    w.gram_cap = two_per_cu < ctx->dot_blocks ? two_per_cu : ctx->dot_blocks;
+    if (w.gram_cap < 1)
+      w.gram_cap = 1;
+    const size_t mm2 = 2 * (size_t)(3 * nev) * (3 * nev);
+    w.own.alloc(w.hist, ((size_t)kmax + 1) * nev);
+    w.own.alloc(w.theta, nev);
+    w.own.alloc(w.coef, (size_t)3 * nev * nev);
+    w.own.alloc(w.gram, mm2);
+    w.own.alloc(w.gpart, mm2 * w.gram_cap);
+    w.own.alloc(w.rn, (size_t)2 * nev);
+    w.own.alloc(w.rpart, (size_t)ctx->dot_blocks * nev);
+    w.own.alloc(w.st, 1);
+  });
 }
 
 int spmv_hip_lobpcg_ws_destroy(spmv_hip_lobpcg_ws* ws)
 {
-  if (!ws)
-    return SPMV_HIP_OK;
-  (void)hipSetDevice(ws->ctx->device);
-  (void)hipFree(ws->hist);
-  (void)hipFree(ws->theta);
-  (void)hipFree(ws->coef);
-  (void)hipFree(ws->gram);
-  (void)hipFree(ws->gpart);
-  (void)hipFree(ws->rn);
-  (void)hipFree(ws->rpart);
-  (void)hipFree(ws->st);
-  delete ws;
-  return SPMV_HIP_OK;
+  return solver_ws_destroy(ws);
 }
 
 int spmv_hip_lobpcg_ws_reset(spmv_hip_lobpcg_ws* ws, double rtol, double atol,
@@ -871,10 +840,10 @@ int spmv_hip_lobpcg_ws_reset(spmv_hip_lobpcg_ws* ws, double rtol, double atol,
   SPMV_REQUIRE(ws && kmax >= 0 && kmax <= ws->kmax);
   SPMV_SET_DEVICE(ws->ctx);
   const int count = (ws->kmax + 1) * ws->nev;
-  hipLaunchKernelGGL(lobpcg_reset_kernel, dim3((count + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, spmv_stream(ws->ctx, stream), ws->st, rtol,
-                     atol, kmax, largest ? 1 : 0, ws->nev, ws->hist, count,
-                     ws->theta, ws->rn);
+  hipLaunchKernelGGL(lobpcg_reset_kernel, ws_reset_grid(count), dim3(kBlock), 0,
+                     spmv_stream(ws->ctx, stream), ws->st, rtol, atol, kmax,
+                     largest ? 1 : 0, ws->nev, ws->hist, count, ws->theta,
+                     ws->rn);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -937,18 +906,13 @@ int spmv_hip_lobpcg_ws_read_async(spmv_hip_lobpcg_ws* ws, int32_t* host_state,
                                   double* host_scalars, void* stream)
 {
   SPMV_REQUIRE(ws);
-  // checked before anything is enqueued: a short buffer gets nothing at all
-  const size_t count = ((size_t)ws->kmax + 1) * (size_t)ws->nev;
-  SPMV_REQUIRE(!host_hist || host_hist_len >= count);
-  SPMV_SET_DEVICE(ws->ctx);
+  const int rc = ws_read_async(ws->ctx, stream, host_state, &ws->st->done,
+                               SPMV_HIP_LOBPCG_STATE_WORDS, host_hist,
+                               host_hist_len, ws->hist,
+                               ((size_t)ws->kmax + 1) * (size_t)ws->nev);
+  if (rc != SPMV_HIP_OK)
+    return rc;
   hipStream_t st = spmv_stream(ws->ctx, stream);
-  if (host_state)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_state, &ws->st->done,
-                                  SPMV_HIP_LOBPCG_STATE_WORDS * sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, st));
-  if (host_hist)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_hist, ws->hist, sizeof(double) * count,
-                                  hipMemcpyDeviceToHost, st));
   if (host_scalars) { // theta[nev], then rn[2][nev]
     SPMV_CHECK_HIP(hipMemcpyAsync(host_scalars, ws->theta,
                                   sizeof(double) * ws->nev,

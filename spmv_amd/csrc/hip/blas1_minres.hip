@@ -41,7 +41,6 @@
 
 #include <cmath>
 #include <cstddef>
-#include <new>
 
 namespace
 {
@@ -377,38 +376,17 @@ int spmv_hip_minres_ws_create(spmv_hip_ctx* ctx, int kmax,
                               spmv_hip_minres_ws** out)
 {
   SPMV_REQUIRE(ctx && out && kmax >= 0);
-  SPMV_SET_DEVICE(ctx);
-  spmv_hip_minres_ws* ws = new (std::nothrow) spmv_hip_minres_ws;
-  if (!ws)
-    return SPMV_HIP_ENOMEM;
-  ws->ctx = ctx;
-  ws->kmax = kmax;
-  hipError_t e = hipMalloc(&ws->hist, sizeof(double) * ((size_t)kmax + 1));
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->p_alfa, sizeof(double) * (size_t)ctx->dot_blocks);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->p_ry, sizeof(double) * (size_t)ctx->dot_blocks);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->sc, sizeof(MinresScalars));
-  if (e != hipSuccess) {
-    spmv_hip_minres_ws_destroy(ws);
-    return static_cast<int>(e);
-  }
-  *out = ws;
-  return SPMV_HIP_OK;
+  return solver_ws_create(ctx, kmax, out, [&](spmv_hip_minres_ws& w) {
+    w.own.alloc(w.hist, (size_t)kmax + 1);
+    w.own.alloc(w.p_alfa, ctx->dot_blocks);
+    w.own.alloc(w.p_ry, ctx->dot_blocks);
+    w.own.alloc(w.sc, 1);
+  });
 }
 
 int spmv_hip_minres_ws_destroy(spmv_hip_minres_ws* ws)
 {
-  if (!ws)
-    return SPMV_HIP_OK;
-  (void)hipSetDevice(ws->ctx->device);
-  (void)hipFree(ws->hist);
-  (void)hipFree(ws->p_alfa);
-  (void)hipFree(ws->p_ry);
-  (void)hipFree(ws->sc);
-  delete ws;
-  return SPMV_HIP_OK;
+  return solver_ws_destroy(ws);
 }
 
 int spmv_hip_minres_ws_reset(spmv_hip_minres_ws* ws, double rtol, int kmax,
@@ -417,18 +395,16 @@ int spmv_hip_minres_ws_reset(spmv_hip_minres_ws* ws, double rtol, int kmax,
   SPMV_REQUIRE(ws && kmax >= 0 && kmax <= ws->kmax);
   SPMV_SET_DEVICE(ws->ctx);
   const int n = ws->kmax + 1;
-  hipLaunchKernelGGL(minres_reset_kernel, dim3((n + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, spmv_stream(ws->ctx, stream), ws->sc,
-                     rtol, kmax, ws->hist, n);
+  hipLaunchKernelGGL(minres_reset_kernel, ws_reset_grid(n), dim3(kBlock), 0,
+                     spmv_stream(ws->ctx, stream), ws->sc, rtol, kmax, ws->hist,
+                     n);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
 
 int spmv_hip_minres_ws_capacity(const spmv_hip_minres_ws* ws, int* kmax)
 {
-  SPMV_REQUIRE(ws && kmax);
-  *kmax = ws->kmax;
-  return SPMV_HIP_OK;
+  return solver_ws_capacity(ws, kmax);
 }
 
 int spmv_hip_minres_ws_array(spmv_hip_minres_ws* ws, int which, double** p,
@@ -460,43 +436,24 @@ int spmv_hip_minres_ws_read_async(spmv_hip_minres_ws* ws,
                                   void* stream)
 {
   SPMV_REQUIRE(ws);
-  // checked before anything is enqueued: a short buffer gets nothing at all
-  SPMV_REQUIRE(!host_hist || host_hist_len >= (size_t)ws->kmax + 1);
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  if (host_done_kstop_status)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_done_kstop_status, &ws->sc->done,
-                                  3 * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                  st));
-  if (host_hist)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_hist, ws->hist,
-                                  sizeof(double) * ((size_t)ws->kmax + 1),
-                                  hipMemcpyDeviceToHost, st));
-  return SPMV_HIP_OK;
+  return ws_read_async(ws->ctx, stream, host_done_kstop_status, &ws->sc->done,
+                       3, host_hist, host_hist_len, ws->hist,
+                       (size_t)ws->kmax + 1);
 }
 
 int spmv_hip_minres_ws_set_state(spmv_hip_minres_ws* ws, int k, int done,
                                  void* stream)
 {
   SPMV_REQUIRE(ws && k >= 0 && k <= ws->kmax);
-  SPMV_SET_DEVICE(ws->ctx);
   const int32_t words[4] = {done ? 1 : 0, done ? k : -1, 0, k};
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  SPMV_CHECK_HIP(hipMemcpyAsync(&ws->sc->done, words, sizeof(words),
-                                hipMemcpyHostToDevice, st));
-  SPMV_CHECK_HIP(hipStreamSynchronize(st)); // `words` goes out of scope
-  return SPMV_HIP_OK;
+  return ws_put_words(ws->ctx, stream, &ws->sc->done, words, 4);
 }
 
 int spmv_hip_minres_ws_get_state(spmv_hip_minres_ws* ws, int32_t* host_words5,
                                  void* stream)
 {
   SPMV_REQUIRE(ws && host_words5);
-  SPMV_SET_DEVICE(ws->ctx);
-  SPMV_CHECK_HIP(hipMemcpyAsync(host_words5, &ws->sc->done, 5 * sizeof(int32_t),
-                                hipMemcpyDeviceToHost,
-                                spmv_stream(ws->ctx, stream)));
-  return SPMV_HIP_OK;
+  return ws_get_words(ws->ctx, stream, host_words5, &ws->sc->done, 5);
 }
 
 // ---- kernels ------------------------------------------------------------------

@@ -35,7 +35,6 @@
 #include "pcg_ws.h"
 
 #include <cmath>
-#include <new>
 
 namespace
 {
@@ -386,46 +385,20 @@ extern "C" {
 int spmv_hip_pcg_ws_create(spmv_hip_ctx* ctx, int kmax, spmv_hip_pcg_ws** out)
 {
   SPMV_REQUIRE(ctx && out && kmax >= 0);
-  SPMV_SET_DEVICE(ctx);
-  spmv_hip_pcg_ws* ws = new (std::nothrow) spmv_hip_pcg_ws;
-  if (!ws)
-    return SPMV_HIP_ENOMEM;
-  ws->ctx = ctx;
-  ws->kmax = kmax;
-  const size_t hist = sizeof(double) * ((size_t)kmax + 1);
-  const size_t part = sizeof(double) * (size_t)ctx->dot_blocks;
-  hipError_t e = hipMalloc(&ws->zr, 2 * hist);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->pAp, hist);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->partials, part);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->partials_rz, part);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->partials_rr, part);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->sc, sizeof(PcgScalars));
-  if (e != hipSuccess) {
-    spmv_hip_pcg_ws_destroy(ws);
-    return static_cast<int>(e);
-  }
-  *out = ws;
-  return SPMV_HIP_OK;
+  return solver_ws_create(ctx, kmax, out, [&](spmv_hip_pcg_ws& w) {
+    const size_t hist = (size_t)kmax + 1, part = (size_t)ctx->dot_blocks;
+    w.own.alloc(w.zr, 2 * hist);
+    w.own.alloc(w.pAp, hist);
+    w.own.alloc(w.partials, part);
+    w.own.alloc(w.partials_rz, part);
+    w.own.alloc(w.partials_rr, part);
+    w.own.alloc(w.sc, 1);
+  });
 }
 
 int spmv_hip_pcg_ws_destroy(spmv_hip_pcg_ws* ws)
 {
-  if (!ws)
-    return SPMV_HIP_OK;
-  (void)hipSetDevice(ws->ctx->device);
-  (void)hipFree(ws->zr);
-  (void)hipFree(ws->pAp);
-  (void)hipFree(ws->partials);
-  (void)hipFree(ws->partials_rz);
-  (void)hipFree(ws->partials_rr);
-  (void)hipFree(ws->sc);
-  delete ws;
-  return SPMV_HIP_OK;
+  return solver_ws_destroy(ws);
 }
 
 int spmv_hip_pcg_ws_reset(spmv_hip_pcg_ws* ws, double rtol, void* stream)
@@ -433,18 +406,16 @@ int spmv_hip_pcg_ws_reset(spmv_hip_pcg_ws* ws, double rtol, void* stream)
   SPMV_REQUIRE(ws);
   SPMV_SET_DEVICE(ws->ctx);
   const int n = ws->kmax + 1;
-  hipLaunchKernelGGL(pcg_reset_kernel, dim3((n + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, spmv_stream(ws->ctx, stream), ws->sc,
-                     rtol, ws->zr, ws->pAp, ws->kmax);
+  hipLaunchKernelGGL(pcg_reset_kernel, ws_reset_grid(n), dim3(kBlock), 0,
+                     spmv_stream(ws->ctx, stream), ws->sc, rtol, ws->zr,
+                     ws->pAp, ws->kmax);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
 
 int spmv_hip_pcg_ws_capacity(const spmv_hip_pcg_ws* ws, int* kmax)
 {
-  SPMV_REQUIRE(ws && kmax);
-  *kmax = ws->kmax;
-  return SPMV_HIP_OK;
+  return solver_ws_capacity(ws, kmax);
 }
 
 int spmv_hip_pcg_ws_rz_rr(spmv_hip_pcg_ws* ws, int k, double** pair)
@@ -480,19 +451,9 @@ int spmv_hip_pcg_ws_read_async(spmv_hip_pcg_ws* ws, int32_t* host_done_kstop,
                                void* stream)
 {
   SPMV_REQUIRE(ws);
-  // checked before anything is enqueued: a short buffer gets nothing at all
-  SPMV_REQUIRE(!host_rz_rr || host_rz_rr_len >= 2 * ((size_t)ws->kmax + 1));
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  if (host_done_kstop)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_done_kstop, &ws->sc->done,
-                                  2 * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                  st));
-  if (host_rz_rr)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_rz_rr, ws->zr,
-                                  2 * sizeof(double) * ((size_t)ws->kmax + 1),
-                                  hipMemcpyDeviceToHost, st));
-  return SPMV_HIP_OK;
+  return ws_read_async(ws->ctx, stream, host_done_kstop, &ws->sc->done, 2,
+                       host_rz_rr, host_rz_rr_len, ws->zr,
+                       2 * ((size_t)ws->kmax + 1));
 }
 
 // ---- kernels ------------------------------------------------------------------

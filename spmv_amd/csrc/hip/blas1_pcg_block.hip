@@ -36,7 +36,6 @@
 
 #include <climits>
 #include <cmath>
-#include <new>
 
 namespace
 {
@@ -440,44 +439,21 @@ int spmv_hip_pcgb_ws_create(spmv_hip_ctx* ctx, int kmax, int nrhs,
   *out = nullptr;
   SPMV_REQUIRE(ctx && nrhs_ok(nrhs));
   SPMV_REQUIRE(kmax >= 0 && kmax < INT_MAX / (4 * SPMV_CGB_MAX));
-  SPMV_SET_DEVICE(ctx);
-  spmv_hip_pcgb_ws* ws = new (std::nothrow) spmv_hip_pcgb_ws;
-  if (!ws)
-    return SPMV_HIP_ENOMEM;
-  ws->ctx = ctx;
-  ws->kmax = kmax;
-  ws->nrhs = nrhs;
-  const size_t hist = sizeof(double) * (size_t)(kmax + 1) * nrhs;
-  const size_t part = sizeof(double) * (size_t)ctx->dot_blocks * nrhs;
-  hipError_t e = hipMalloc(&ws->zr, 2 * hist);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->pAp, hist);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->partials, part);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->partials_rr, part);
-  if (e == hipSuccess)
-    e = hipMalloc(&ws->st, sizeof(CgbState));
-  if (e != hipSuccess) {
-    spmv_hip_pcgb_ws_destroy(ws);
-    return static_cast<int>(e);
-  }
-  *out = ws;
-  return SPMV_HIP_OK;
+  return solver_ws_create(ctx, kmax, out, [&](spmv_hip_pcgb_ws& w) {
+    w.nrhs = nrhs;
+    const size_t hist = (size_t)(kmax + 1) * nrhs;
+    const size_t part = (size_t)ctx->dot_blocks * nrhs;
+    w.own.alloc(w.zr, 2 * hist);
+    w.own.alloc(w.pAp, hist);
+    w.own.alloc(w.partials, part);
+    w.own.alloc(w.partials_rr, part);
+    w.own.alloc(w.st, 1);
+  });
 }
 
 int spmv_hip_pcgb_ws_destroy(spmv_hip_pcgb_ws* ws)
 {
-  if (!ws)
-    return SPMV_HIP_OK;
-  (void)hipSetDevice(ws->ctx->device);
-  (void)hipFree(ws->zr);
-  (void)hipFree(ws->pAp);
-  (void)hipFree(ws->partials);
-  (void)hipFree(ws->partials_rr);
-  (void)hipFree(ws->st);
-  delete ws;
-  return SPMV_HIP_OK;
+  return solver_ws_destroy(ws);
 }
 
 int spmv_hip_pcgb_ws_reset(spmv_hip_pcgb_ws* ws, double rtol, void* stream)
@@ -485,9 +461,9 @@ int spmv_hip_pcgb_ws_reset(spmv_hip_pcgb_ws* ws, double rtol, void* stream)
   SPMV_REQUIRE(ws);
   SPMV_SET_DEVICE(ws->ctx);
   const int count = (ws->kmax + 1) * ws->nrhs;
-  hipLaunchKernelGGL(pcgb_reset_kernel, dim3((count + kBlock - 1) / kBlock),
-                     dim3(kBlock), 0, spmv_stream(ws->ctx, stream), ws->st, rtol,
-                     ws->zr, ws->pAp, count);
+  hipLaunchKernelGGL(pcgb_reset_kernel, ws_reset_grid(count), dim3(kBlock), 0,
+                     spmv_stream(ws->ctx, stream), ws->st, rtol, ws->zr,
+                     ws->pAp, count);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -519,20 +495,11 @@ int spmv_hip_pcgb_ws_read_async(spmv_hip_pcgb_ws* ws, int32_t* host_state,
                                 size_t host_rz_rr_len, void* stream)
 {
   SPMV_REQUIRE(ws);
-  // checked before anything is enqueued: a short buffer gets nothing at all
-  const size_t count = 2 * ((size_t)ws->kmax + 1) * (size_t)ws->nrhs;
+  // a short state buffer gets nothing at all either
   SPMV_REQUIRE(!host_state || host_state_len >= SPMV_HIP_CGB_STATE_WORDS);
-  SPMV_REQUIRE(!host_rz_rr || host_rz_rr_len >= count);
-  SPMV_SET_DEVICE(ws->ctx);
-  hipStream_t st = spmv_stream(ws->ctx, stream);
-  if (host_state)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_state, &ws->st->all_done,
-                                  SPMV_HIP_CGB_STATE_WORDS * sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, st));
-  if (host_rz_rr)
-    SPMV_CHECK_HIP(hipMemcpyAsync(host_rz_rr, ws->zr, sizeof(double) * count,
-                                  hipMemcpyDeviceToHost, st));
-  return SPMV_HIP_OK;
+  return ws_read_async(ws->ctx, stream, host_state, &ws->st->all_done,
+                       SPMV_HIP_CGB_STATE_WORDS, host_rz_rr, host_rz_rr_len,
+                       ws->zr, 2 * ((size_t)ws->kmax + 1) * (size_t)ws->nrhs);
 }
 
 int spmv_hip_pcgb_init_f64(spmv_hip_ctx* ctx, spmv_hip_pcgb_ws* ws, int64_t M,

@@ -1,7 +1,7 @@
 // Device state of spmv::cg_shifted (blas1_cgshift.hip).
 #pragma once
 
-#include "common.h"
+#include "solver_ws.h"
 
 constexpr int kCgsMaxNs = 8; // SPMV_HIP_CGS_MAX_NS
 
@@ -41,6 +41,7 @@ struct spmv_hip_cgs_ws {
   spmv_hip_ctx* ctx = nullptr;
   int kmax = 0;            // capacity of every history
   int ns = 0;              // of the last reset
+  SolverArrays own;
   double* hist = nullptr;  // kCgsMaxNs * (kmax + 1): hist_s at s * (kmax + 1)
   double* p_pq = nullptr;  // ctx->dot_blocks: partials of p.q
   double* p_rrn = nullptr; // ctx->dot_blocks: partials of r.r

@@ -1,7 +1,7 @@
 // Device state of spmv::idrs (blas1_idrs.hip).
 #pragma once
 
-#include "common.h"
+#include "solver_ws.h"
 
 constexpr int kIdrsMaxS = 8; // SPMV_HIP_IDRS_MAX_S
 // rows of the partial array and slots of `red`
@@ -42,6 +42,7 @@ struct spmv_hip_idrs_ws {
   int kmax = 0;           // capacity of the history
   int s = 0;              // of the last reset
   uint64_t seed = 0;      // of the last reset
+  SolverArrays own;
   double* hist = nullptr; // kmax + 1
   double* part = nullptr; // kIdrsRows * ctx->dot_blocks: row j at j * dot_blocks
   IdrsScalars* sc = nullptr;

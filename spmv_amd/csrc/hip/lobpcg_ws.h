@@ -1,7 +1,7 @@
 // Device state of spmv::lobpcg (blas1_lobpcg.hip).
 #pragma once
 
-#include "common.h"
+#include "solver_ws.h"
 
 struct LobpcgState {
   double rtol, atol;
@@ -23,6 +23,7 @@ struct spmv_hip_lobpcg_ws {
   int kmax = 0; // capacity of hist
   int nev = 0;
   int gram_cap = 0;        // workgroups of the Gram kernel at most
+  SolverArrays own;
   double* hist = nullptr;  // [kmax + 1][nev]: ||r_c|| per iteration, -1.0 where
                            // the column had met its test before
   double* theta = nullptr; // [nev]

@@ -1,7 +1,7 @@
 // Device state of spmv::lsqr (blas1_lsqr.hip).
 #pragma once
 
-#include "common.h"
+#include "solver_ws.h"
 
 // The doubles first, in the order of SPMV_HIP_LSQR_SCALARS (spmv_hip.h).
 struct LsqrScalars {
@@ -28,6 +28,7 @@ constexpr int kLsqrDoubles = 15;
 struct spmv_hip_lsqr_ws {
   spmv_hip_ctx* ctx = nullptr;
   int kmax = 0;            // capacity of either history
+  SolverArrays own;
   double* hist = nullptr;  // 2 * (kmax + 1): hist_r, then hist_ar
   double* p_uu = nullptr;  // ctx->dot_blocks: partials of ut.ut
   double* p_vv = nullptr;  // ctx->dot_blocks: partials of vn.vn

@@ -1,7 +1,7 @@
 // Device state of spmv::minres (blas1_minres.hip).
 #pragma once
 
-#include "common.h"
+#include "solver_ws.h"
 
 // The doubles first, in the order of SPMV_HIP_MINRES_SCALARS (spmv_hip.h).
 struct MinresScalars {
@@ -30,6 +30,7 @@ constexpr int kMinresDoubles = 16;
 struct spmv_hip_minres_ws {
   spmv_hip_ctx* ctx = nullptr;
   int kmax = 0;            // capacity of hist
+  SolverArrays own;
   double* hist = nullptr;  // kmax + 1
   double* p_alfa = nullptr; // ctx->dot_blocks: partials of v.Av
   double* p_ry = nullptr;   // ctx->dot_blocks: partials of r2.y

@@ -3,7 +3,7 @@
 // pcg_chebyshev, which runs on the same scalars and reducers).
 #pragma once
 
-#include "common.h"
+#include "solver_ws.h"
 
 struct PcgScalars {
   double rtol;
@@ -14,6 +14,7 @@ struct PcgScalars {
 struct spmv_hip_pcg_ws {
   spmv_hip_ctx* ctx = nullptr;
   int kmax = 0;
+  SolverArrays own;
   double* zr = nullptr;          // [kmax + 1][2]: {rz[k], rr[k]}
   double* pAp = nullptr;         // kmax + 1
   double* partials = nullptr;    // p.Ap, ctx->dot_blocks

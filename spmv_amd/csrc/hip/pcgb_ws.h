@@ -4,7 +4,7 @@
 // sweeps of spmv_mcgs.hip look at its all_done.
 #pragma once
 
-#include "common.h"
+#include "solver_ws.h"
 
 #define SPMV_CGB_MAX SPMV_HIP_CGB_MAX_NRHS
 
@@ -22,6 +22,7 @@ struct spmv_hip_pcgb_ws {
   spmv_hip_ctx* ctx = nullptr;
   int kmax = 0;
   int nrhs = 0;
+  SolverArrays own;
   double* zr = nullptr;  // [kmax + 1][2][nrhs]: rz[k][0:nrhs], then rr[k][0:nrhs]
   double* pAp = nullptr; // [kmax + 1][nrhs]
   double* partials = nullptr;    // p.Ap, then r.z: [ctx->dot_blocks][nrhs]

@@ -30,10 +30,8 @@ BicgstabWorkspace::~BicgstabWorkspace() { release(); }
 void BicgstabWorkspace::release()
 {
   release_common();
-  spmv_hip_bicg_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_bicg_ws_destroy);
   free_vectors({&r, &rhat, &v, &t, &p, &s, &ph, &sh, &x, &dinv});
-  kmax_cap = -1;
   m_cap = n_cap = h_cap = x_cap = dinv_cap = -1;
 }
 
@@ -41,16 +39,12 @@ void BicgstabWorkspace::ensure(int64_t M, int64_t N_padded, int kmax,
                                bool need_x, bool need_dinv, bool need_h)
 {
   open(4);
-  if (kmax > kmax_cap) {
-    // (an earlier solve on this workspace has been synchronised: nothing
-    // still reads the old scalars)
-    spmv_hip_bicg_ws_destroy(ws);
-    ws = nullptr;
-    kmax_cap = -1;
-    throw_on_error(spmv_hip_bicg_ws_create(_exec.context(), kmax, &ws),
-                   "spmv_hip_bicg_ws_create");
-    kmax_cap = kmax;
-  }
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap, spmv_hip_bicg_ws_destroy,
+      [&](auto out) {
+        return spmv_hip_bicg_ws_create(_exec.context(), kmax, out);
+      },
+      "spmv_hip_bicg_ws_create");
   regrow(m_cap, M, {&r, &rhat, &v, &t});
   regrow(n_cap, N_padded, {&p, &s});
   if (need_h)
@@ -114,10 +108,8 @@ int bicgstab(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   w.flags[2] = 0;
 
   // the state words alone (h == nullptr), or with the history of pairs
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_bicg_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_bicg_ws_read_async");
-  };
+  auto read = ws_reader(w.ws, w.flags, spmv_hip_bicg_ws_read_async,
+                        "spmv_hip_bicg_ws_read_async");
 
   // {rr0, rho0}: one all-reduce of 2 doubles
   throw_on_error(spmv_hip_bicg_reduce_rr_rho(ctx, w.ws, 0, nullptr),

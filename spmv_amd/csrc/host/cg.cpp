@@ -93,10 +93,8 @@ CgWorkspace::~CgWorkspace() { release(); }
 void CgWorkspace::release()
 {
   release_common();
-  spmv_hip_cg_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_cg_ws_destroy);
   free_vectors({&r, &Ap, &x, &p, &p2, &dot2});
-  kmax_cap = -1;
   m_cap = n_cap = -1;
 }
 
@@ -105,16 +103,12 @@ void CgWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len)
   open(2);
   if (!dot2)
     dot2 = _exec.alloc<double>(len);
-  if (kmax > kmax_cap) {
-    // (an earlier solve on this workspace has been synchronised: nothing
-    // still reads the old scalars)
-    spmv_hip_cg_ws_destroy(ws);
-    ws = nullptr;
-    kmax_cap = -1;
-    throw_on_error(spmv_hip_cg_ws_create(_exec.context(), kmax, &ws),
-                   "spmv_hip_cg_ws_create");
-    kmax_cap = kmax;
-  }
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap, spmv_hip_cg_ws_destroy,
+      [&](auto out) {
+        return spmv_hip_cg_ws_create(_exec.context(), kmax, out);
+      },
+      "spmv_hip_cg_ws_create");
   regrow(m_cap, M, {&r, &Ap}); // cg.cpp:39-40
   if (N_padded > n_cap) { // ensure_p2() brings it back at the new size
     _exec.free(p2);
@@ -184,10 +178,8 @@ int cg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   w.flags[1] = -1;
 
   // the state words alone (h == nullptr), or with the squared-residual history
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_cg_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_cg_ws_read_async");
-  };
+  auto read = ws_reader(w.ws, w.flags, spmv_hip_cg_ws_read_async,
+                        "spmv_hip_cg_ws_read_async");
 
   // rnorm0 (cg.cpp:47-50)
   throw_on_error(spmv_hip_cg_reduce_rr(ctx, w.ws, 0, nullptr),
@@ -426,10 +418,8 @@ CgBlockWorkspace::~CgBlockWorkspace() { release(); }
 void CgBlockWorkspace::release()
 {
   release_common();
-  spmv_hip_cgb_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_cgb_ws_destroy);
   free_vectors({&r, &Ap, &x, &p});
-  kmax_cap = -1;
   nrhs_cap = 0;
   m_cap = n_cap = x_cap = -1;
 }
@@ -438,18 +428,15 @@ void CgBlockWorkspace::ensure(int64_t m_elems, int64_t n_elems, int kmax,
                               int nrhs, bool need_x)
 {
   open(SPMV_HIP_CGB_STATE_WORDS);
-  if (kmax > kmax_cap || nrhs != nrhs_cap) {
-    // (an earlier solve on this workspace has been synchronised: nothing
-    // still reads the old scalars)
-    spmv_hip_cgb_ws_destroy(ws);
-    ws = nullptr;
-    kmax_cap = -1;
-    nrhs_cap = 0;
-    throw_on_error(spmv_hip_cgb_ws_create(_exec.context(), kmax, nrhs, &ws),
-                   "spmv_hip_cgb_ws_create");
-    kmax_cap = kmax;
-    nrhs_cap = nrhs;
-  }
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap || nrhs != nrhs_cap,
+      spmv_hip_cgb_ws_destroy,
+      [&](auto out) {
+        nrhs_cap = 0; // while they are gone
+        return spmv_hip_cgb_ws_create(_exec.context(), kmax, nrhs, out);
+      },
+      "spmv_hip_cgb_ws_create");
+  nrhs_cap = nrhs;
   regrow(m_cap, m_elems, {&r, &Ap});
   if (need_x)
     regrow(x_cap, m_elems, {&x});

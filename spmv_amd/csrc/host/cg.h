@@ -47,6 +47,14 @@ public:
   void* poll_event = nullptr;
   std::vector<void*> timing_ev; // CgOptions::time_spmv: 2 events per SpMV
 
+  // events for CgOptions::time_spmv of a solve with up to `spmvs` timed SpMVs
+  // (one per iteration; pcg_chebyshev: iterations * degree), created ahead of
+  // it (a benchmark keeps them out of its timed region)
+  void reserve_timing(int spmvs)
+  {
+    reserve_events(2 * (size_t)std::max(spmvs, 0));
+  }
+
 protected:
   explicit SolverWorkspace(HipExecutor& exec) : _exec(exec) {}
   ~SolverWorkspace() = default;
@@ -75,12 +83,6 @@ public:
 
   // ---- internal to cg() ----
   void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len);
-  // events for CgOptions::time_spmv of a solve of up to `iterations` steps,
-  // created ahead of it (a benchmark keeps them out of its timed region)
-  void reserve_timing(int iterations)
-  {
-    reserve_events(2 * (size_t)std::max(iterations, 0));
-  }
   // the second p buffer of CgOptions::defer_x, allocated by the first solve
   // that takes that path (after ensure())
   void ensure_p2();
@@ -175,10 +177,6 @@ public:
   // caller's X is not 16-byte aligned, the iterate lives in `x`
   void ensure(int64_t m_elems, int64_t n_elems, int kmax, int nrhs,
               bool need_x);
-  void reserve_timing(int iterations)
-  {
-    reserve_events(2 * (size_t)std::max(iterations, 0));
-  }
   void release();
 
   spmv_hip_cgb_ws* ws = nullptr;
@@ -235,13 +233,6 @@ int cg_block(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
 class PcgFamilyWorkspace : public SolverWorkspace
 {
 public:
-  // events for CgOptions::time_spmv of a solve with up to `spmvs` timed SpMVs
-  // (pcg_chebyshev: iterations * degree, else iterations), created ahead of it
-  void reserve_timing(int spmvs)
-  {
-    reserve_events(2 * (size_t)std::max(spmvs, 0));
-  }
-
   spmv_hip_pcg_ws* ws = nullptr;
   int kmax_cap = -1;
   int64_t m_cap = -1, n_cap = -1, x_cap = -1;
@@ -807,10 +798,6 @@ public:
   // ---- internal to pcg_block() ----
   void ensure(int64_t m_elems, int64_t n_elems, int kmax, int nrhs,
               bool need_x);
-  void reserve_timing(int iterations)
-  {
-    reserve_events(2 * (size_t)std::max(iterations, 0));
-  }
   void release();
 
   spmv_hip_pcgb_ws* ws = nullptr;
@@ -1220,10 +1207,6 @@ public:
   // dinv is not 16-byte aligned and lives in the workspace's copy
   void ensure(int64_t M, int64_t N_padded, int64_t basis_elems, int kmax,
               bool need_b, bool need_dinv);
-  void reserve_timing(int iterations)
-  {
-    reserve_events(2 * (size_t)std::max(iterations, 0));
-  }
   void release();
 
   spmv_hip_gmres_ws* ws = nullptr;
@@ -1348,10 +1331,6 @@ public:
   // is not 16-byte aligned and lives in the workspace's copy
   void ensure(int64_t M, int64_t N_padded, int kmax, int partials_len,
               bool need_y, bool need_x, bool need_dinv);
-  void reserve_timing(int iterations)
-  {
-    reserve_events(2 * (size_t)std::max(iterations, 0));
-  }
   void release();
 
   spmv_hip_minres_ws* ws = nullptr;
@@ -1622,10 +1601,6 @@ public:
   // with_b: the blocks of a solve with B as well (they stay for later solves)
   void ensure(int64_t m_elems, int64_t n_elems, int kmax, int nev, bool need_x,
               bool with_b = false);
-  void reserve_timing(int iterations)
-  {
-    reserve_events(2 * (size_t)std::max(iterations, 0));
-  }
   void release();
 
   // (flags: {done, kstop, status, it, active, has_p, restarts, basis})
@@ -1806,10 +1781,6 @@ public:
   // lives in the workspace's copy
   void ensure(int64_t M, int64_t N_padded, int ns, int kmax, int len,
               bool need_x);
-  void reserve_timing(int iterations)
-  {
-    reserve_events(2 * (size_t)std::max(iterations, 0));
-  }
   void release();
 
   spmv_hip_cgs_ws* ws = nullptr;
@@ -1944,10 +1915,6 @@ public:
   // need_dinv: Chebyshev's dinv is not 16-byte aligned
   void ensure(int64_t M, int64_t N_padded, int s, int kmax, bool need_v,
               bool need_dinv);
-  void reserve_timing(int iterations)
-  {
-    reserve_events(2 * (size_t)std::max(iterations, 0));
-  }
   void release();
 
   spmv_hip_idrs_ws* ws = nullptr;

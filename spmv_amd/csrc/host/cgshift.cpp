@@ -23,10 +23,8 @@ CgShiftedWorkspace::~CgShiftedWorkspace() { release(); }
 void CgShiftedWorkspace::release()
 {
   release_common();
-  spmv_hip_cgs_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_cgs_ws_destroy);
   free_vectors({&r, &q, &p, &ps, &x, &dot2});
-  kmax_cap = -1;
   m_cap = n_cap = ps_cap = x_cap = -1;
   ld = 0;
 }
@@ -37,16 +35,12 @@ void CgShiftedWorkspace::ensure(int64_t M, int64_t N_padded, int ns, int kmax,
   open(SPMV_HIP_CGS_STATE_WORDS);
   if (!dot2)
     dot2 = _exec.alloc<double>(len);
-  if (kmax > kmax_cap) {
-    // (an earlier solve on this workspace has been synchronised: nothing
-    // still reads the old scalars)
-    spmv_hip_cgs_ws_destroy(ws);
-    ws = nullptr;
-    kmax_cap = -1;
-    throw_on_error(spmv_hip_cgs_ws_create(_exec.context(), kmax, &ws),
-                   "spmv_hip_cgs_ws_create");
-    kmax_cap = kmax;
-  }
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap, spmv_hip_cgs_ws_destroy,
+      [&](auto out) {
+        return spmv_hip_cgs_ws_create(_exec.context(), kmax, out);
+      },
+      "spmv_hip_cgs_ws_create");
   regrow(m_cap, M, {&r, &q});
   regrow(n_cap, N_padded, {&p});
   // every solve lays its columns out afresh: the stride is this call's
@@ -84,10 +78,8 @@ int cg_shifted(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   throw_on_error(spmv_hip_cgs_ws_reset(w.ws, rtol, kmax, ns, shifts, nullptr),
                  "spmv_hip_cgs_ws_reset");
   auto slot = [&](int which) {
-    double* at = nullptr;
-    throw_on_error(spmv_hip_cgs_ws_array(w.ws, which, &at, nullptr),
-                   "spmv_hip_cgs_ws_array");
-    return at;
+    return ws_array(w.ws, spmv_hip_cgs_ws_array, which,
+                    "spmv_hip_cgs_ws_array");
   };
   double* const slot_pq = slot(SPMV_HIP_CGS_PQ);
   double* const slot_rrn = slot(SPMV_HIP_CGS_RRN);
@@ -111,10 +103,8 @@ int cg_shifted(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
     w.flags[i] = 0;
   w.flags[1] = -1;
 
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_cgs_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_cgs_ws_read_async");
-  };
+  auto read = ws_reader(w.ws, w.flags, spmv_hip_cgs_ws_read_async,
+                        "spmv_hip_cgs_ws_read_async");
   // a partial array -> its slot, summed over the ranks
   auto finish = [&](int which, const double* part2, double* at) {
     if (!several)
@@ -161,12 +151,10 @@ int cg_shifted(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   }
 
   // final state: {done, kstop, status, its[8]} and the histories, hist_s at
-  // s * (the WORKSPACE's capacity + 1)
-  int cap = 0;
-  throw_on_error(spmv_hip_cgs_ws_capacity(w.ws, &cap),
-                 "spmv_hip_cgs_ws_capacity");
+  // s * (the WORKSPACE's capacity + 1): the stride read_history sized them by
   const std::vector<double> hist = read_history(
       spmv_hip_cgs_ws_capacity, w.ws, kmax, SPMV_HIP_CGS_MAX_NS, read);
+  const size_t stride = hist.size() / SPMV_HIP_CGS_MAX_NS;
   if (Xi != X)
     for (int s = 0; s < ns; ++s)
       exec.copy<double>(X + s * ldx, Xi + s * ldi, M);
@@ -193,8 +181,7 @@ int cg_shifted(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
     if (iterations)
       (*iterations)[s] = ks;
     if (rnorm_history)
-      std::copy(hist.begin() + (size_t)s * (cap + 1),
-                hist.begin() + (size_t)s * (cap + 1) + ks + 1,
+      std::copy(hist.begin() + s * stride, hist.begin() + s * stride + ks + 1,
                 rnorm_history->begin() + (size_t)s * ((size_t)kmax + 1));
   }
   return k_max;

@@ -43,10 +43,8 @@ GmresWorkspace::~GmresWorkspace() { release(); }
 void GmresWorkspace::release()
 {
   release_common();
-  spmv_hip_gmres_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_gmres_ws_destroy);
   free_vectors({&r, &ax, &u, &z, &x, &V, &b, &dinv});
-  kmax_cap = -1;
   m_cap = n_cap = v_cap = b_cap = dinv_cap = -1;
 }
 
@@ -54,16 +52,12 @@ void GmresWorkspace::ensure(int64_t M, int64_t N_padded, int64_t basis_elems,
                             int kmax, bool need_b, bool need_dinv)
 {
   open(4);
-  if (kmax > kmax_cap) {
-    // (an earlier solve on this workspace has been synchronised: nothing
-    // still reads the old scalars)
-    spmv_hip_gmres_ws_destroy(ws);
-    ws = nullptr;
-    kmax_cap = -1;
-    throw_on_error(spmv_hip_gmres_ws_create(_exec.context(), kmax, &ws),
-                   "spmv_hip_gmres_ws_create");
-    kmax_cap = kmax;
-  }
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap, spmv_hip_gmres_ws_destroy,
+      [&](auto out) {
+        return spmv_hip_gmres_ws_create(_exec.context(), kmax, out);
+      },
+      "spmv_hip_gmres_ws_create");
   regrow(m_cap, M, {&r, &ax, &u});
   regrow(n_cap, N_padded, {&z, &x});
   regrow(v_cap, basis_elems, {&V});
@@ -152,15 +146,11 @@ int gmres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   w.flags[2] = 0;
   w.flags[3] = 0;
 
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_gmres_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_gmres_ws_read_async");
-  };
+  auto read = ws_reader(w.ws, w.flags, spmv_hip_gmres_ws_read_async,
+                        "spmv_hip_gmres_ws_read_async");
   auto slot = [&](int which) {
-    double* q = nullptr;
-    throw_on_error(spmv_hip_gmres_ws_array(w.ws, which, &q, nullptr),
-                   "spmv_hip_gmres_ws_array");
-    return q;
+    return ws_array(w.ws, spmv_hip_gmres_ws_array, which,
+                    "spmv_hip_gmres_ws_array");
   };
   const bool several = comm.size() > 1;
   double* const slot_h = slot(SPMV_HIP_GMRES_H);

@@ -32,10 +32,8 @@ IdrsWorkspace::~IdrsWorkspace() { release(); }
 void IdrsWorkspace::release()
 {
   release_common();
-  spmv_hip_idrs_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_idrs_ws_destroy);
   free_vectors({&r, &t, &u, &G, &U, &v, &dinv});
-  kmax_cap = -1;
   m_cap = n_cap = gu_cap = v_cap = dinv_cap = -1;
   ld = 0;
 }
@@ -44,16 +42,12 @@ void IdrsWorkspace::ensure(int64_t M, int64_t N_padded, int s, int kmax,
                            bool need_v, bool need_dinv)
 {
   open(SPMV_HIP_IDRS_STATE_WORDS);
-  if (kmax > kmax_cap) {
-    // (an earlier solve on this workspace has been synchronised: nothing
-    // still reads the old scalars)
-    spmv_hip_idrs_ws_destroy(ws);
-    ws = nullptr;
-    kmax_cap = -1;
-    throw_on_error(spmv_hip_idrs_ws_create(_exec.context(), kmax, &ws),
-                   "spmv_hip_idrs_ws_create");
-    kmax_cap = kmax;
-  }
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap, spmv_hip_idrs_ws_destroy,
+      [&](auto out) {
+        return spmv_hip_idrs_ws_create(_exec.context(), kmax, out);
+      },
+      "spmv_hip_idrs_ws_create");
   regrow(m_cap, M, {&r, &t});
   regrow(n_cap, N_padded, {&u});
   // every solve lays its columns out afresh: the stride is this call's
@@ -127,10 +121,8 @@ int idrs(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
     w.flags[i] = 0;
   w.flags[1] = -1;
 
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_idrs_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_idrs_ws_read_async");
-  };
+  auto read = ws_reader(w.ws, w.flags, spmv_hip_idrs_ws_read_async,
+                        "spmv_hip_idrs_ws_read_async");
   double* red = nullptr;
   throw_on_error(spmv_hip_idrs_ws_array(w.ws, SPMV_HIP_IDRS_RED, &red, nullptr),
                  "spmv_hip_idrs_ws_array");

@@ -37,10 +37,8 @@ LobpcgWorkspace::~LobpcgWorkspace() { release(); }
 void LobpcgWorkspace::release()
 {
   release_common();
-  spmv_hip_lobpcg_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_lobpcg_ws_destroy);
   free_vectors({&r, &p, &ax, &aw, &ap, &x, &w, &bx, &bw, &bp});
-  kmax_cap = -1;
   nev_cap = 0;
   m_cap = n_cap = x_cap = b_cap = -1;
 }
@@ -49,18 +47,15 @@ void LobpcgWorkspace::ensure(int64_t m_elems, int64_t n_elems, int kmax, int nev
                              bool need_x, bool with_b)
 {
   open(SPMV_HIP_LOBPCG_STATE_WORDS);
-  if (kmax > kmax_cap || nev != nev_cap) {
-    // (an earlier solve on this workspace has been synchronised: nothing
-    // still reads the old scalars)
-    spmv_hip_lobpcg_ws_destroy(ws);
-    ws = nullptr;
-    kmax_cap = -1;
-    nev_cap = 0;
-    throw_on_error(spmv_hip_lobpcg_ws_create(_exec.context(), kmax, nev, &ws),
-                   "spmv_hip_lobpcg_ws_create");
-    kmax_cap = kmax;
-    nev_cap = nev;
-  }
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap || nev != nev_cap,
+      spmv_hip_lobpcg_ws_destroy,
+      [&](auto out) {
+        nev_cap = 0; // while they are gone
+        return spmv_hip_lobpcg_ws_create(_exec.context(), kmax, nev, out);
+      },
+      "spmv_hip_lobpcg_ws_create");
+  nev_cap = nev;
   regrow(m_cap, m_elems, {&r, &p, &ax, &aw, &ap});
   if (need_x)
     regrow(x_cap, m_elems, {&x});
@@ -112,14 +107,12 @@ int lobpcg(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   throw_on_error(spmv_hip_lobpcg_ws_reset(w.ws, rtol, atol, kmax, opt.largest,
                                           nullptr),
                  "spmv_hip_lobpcg_ws_reset");
-  auto slot = [&](int which) {
-    double* q = nullptr;
-    throw_on_error(spmv_hip_lobpcg_ws_array(w.ws, which, &q, nullptr),
-                   "spmv_hip_lobpcg_ws_array");
-    return q;
-  };
-  double* const slot_gram = slot(SPMV_HIP_LOBPCG_GRAM);
-  double* const slot_rn = slot(SPMV_HIP_LOBPCG_RN);
+  double* const slot_gram
+      = ws_array(w.ws, spmv_hip_lobpcg_ws_array, SPMV_HIP_LOBPCG_GRAM,
+                 "spmv_hip_lobpcg_ws_array");
+  double* const slot_rn
+      = ws_array(w.ws, spmv_hip_lobpcg_ws_array, SPMV_HIP_LOBPCG_RN,
+                 "spmv_hip_lobpcg_ws_array");
 
   double* const Xi = x_aligned ? X : w.x;
   if (!x_aligned)

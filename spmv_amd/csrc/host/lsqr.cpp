@@ -24,10 +24,8 @@ LsqrWorkspace::~LsqrWorkspace() { release(); }
 void LsqrWorkspace::release()
 {
   release_common();
-  spmv_hip_lsqr_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_lsqr_ws_destroy);
   free_vectors({&ut, &Av, &vt, &Atu, &w, &x});
-  kmax_cap = -1;
   m_cap = n_cap = w_cap = x_cap = -1;
 }
 
@@ -35,16 +33,12 @@ void LsqrWorkspace::ensure(int64_t M, int64_t N, int64_t N_padded, int kmax,
                            bool need_x)
 {
   open(4);
-  if (kmax > kmax_cap) {
-    // (an earlier solve on this workspace has been synchronised: nothing
-    // still reads the old scalars)
-    spmv_hip_lsqr_ws_destroy(ws);
-    ws = nullptr;
-    kmax_cap = -1;
-    throw_on_error(spmv_hip_lsqr_ws_create(_exec.context(), kmax, &ws),
-                   "spmv_hip_lsqr_ws_create");
-    kmax_cap = kmax;
-  }
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap, spmv_hip_lsqr_ws_destroy,
+      [&](auto out) {
+        return spmv_hip_lsqr_ws_create(_exec.context(), kmax, out);
+      },
+      "spmv_hip_lsqr_ws_create");
   regrow(m_cap, M, {&ut, &Av});
   regrow(n_cap, N_padded, {&vt, &Atu});
   regrow(w_cap, N, {&w});
@@ -80,10 +74,8 @@ int lsqr(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   throw_on_error(spmv_hip_lsqr_ws_reset(w.ws, rtol, ltol, damp, kmax, nullptr),
                  "spmv_hip_lsqr_ws_reset");
   auto slot = [&](int which) {
-    double* q = nullptr;
-    throw_on_error(spmv_hip_lsqr_ws_array(w.ws, which, &q, nullptr),
-                   "spmv_hip_lsqr_ws_array");
-    return q;
+    return ws_array(w.ws, spmv_hip_lsqr_ws_array, which,
+                    "spmv_hip_lsqr_ws_array");
   };
   double* const slot_uu = slot(SPMV_HIP_LSQR_UU);
   double* const slot_vv = slot(SPMV_HIP_LSQR_VV);
@@ -100,10 +92,8 @@ int lsqr(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   w.flags[1] = -1;
   w.flags[2] = 0;
 
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_lsqr_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_lsqr_ws_read_async");
-  };
+  auto read = ws_reader(w.ws, w.flags, spmv_hip_lsqr_ws_read_async,
+                        "spmv_hip_lsqr_ws_read_async");
   // a partial array -> its slot, summed over the ranks
   auto finish = [&](int which, double* at) {
     if (!several)
@@ -166,12 +156,10 @@ int lsqr(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   }
 
   // final state: {done, kstop, status} and both histories, hist_ar behind the
-  // WORKSPACE's capacity of hist_r
-  int cap = 0;
-  throw_on_error(spmv_hip_lsqr_ws_capacity(w.ws, &cap),
-                 "spmv_hip_lsqr_ws_capacity");
+  // WORKSPACE's capacity of hist_r: half of what read_history sized
   const std::vector<double> hist
       = read_history(spmv_hip_lsqr_ws_capacity, w.ws, kmax, 2, read);
+  const size_t half = hist.size() / 2;
   if (xi != x)
     exec.copy<double>(x, xi, N);
   exec.synchronize_stream(w.stream);
@@ -190,7 +178,7 @@ int lsqr(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   if (hist_r)
     hist_r->assign(hist.begin(), hist.begin() + k_final + 1);
   if (hist_ar)
-    hist_ar->assign(hist.begin() + cap + 1, hist.begin() + cap + 1 + k_final + 1);
+    hist_ar->assign(hist.begin() + half, hist.begin() + half + k_final + 1);
   return k_final;
 }
 

@@ -30,10 +30,8 @@ MinresWorkspace::~MinresWorkspace() { release(); }
 void MinresWorkspace::release()
 {
   release_common();
-  spmv_hip_minres_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_minres_ws_destroy);
   free_vectors({&Av, &ra, &rb, &wa, &wb, &v, &y, &x, &dinv, &dot2});
-  kmax_cap = -1;
   m_cap = n_cap = y_cap = x_cap = dinv_cap = -1;
 }
 
@@ -43,16 +41,12 @@ void MinresWorkspace::ensure(int64_t M, int64_t N_padded, int kmax, int len,
   open(4);
   if (!dot2)
     dot2 = _exec.alloc<double>(len);
-  if (kmax > kmax_cap) {
-    // (an earlier solve on this workspace has been synchronised: nothing
-    // still reads the old scalars)
-    spmv_hip_minres_ws_destroy(ws);
-    ws = nullptr;
-    kmax_cap = -1;
-    throw_on_error(spmv_hip_minres_ws_create(_exec.context(), kmax, &ws),
-                   "spmv_hip_minres_ws_create");
-    kmax_cap = kmax;
-  }
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap, spmv_hip_minres_ws_destroy,
+      [&](auto out) {
+        return spmv_hip_minres_ws_create(_exec.context(), kmax, out);
+      },
+      "spmv_hip_minres_ws_create");
   regrow(m_cap, M, {&Av, &ra, &rb, &wa, &wb});
   regrow(n_cap, N_padded, {&v});
   if (need_y)
@@ -99,10 +93,8 @@ int minres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   throw_on_error(spmv_hip_minres_ws_reset(w.ws, rtol, kmax, nullptr),
                  "spmv_hip_minres_ws_reset");
   auto slot = [&](int which) {
-    double* q = nullptr;
-    throw_on_error(spmv_hip_minres_ws_array(w.ws, which, &q, nullptr),
-                   "spmv_hip_minres_ws_array");
-    return q;
+    return ws_array(w.ws, spmv_hip_minres_ws_array, which,
+                    "spmv_hip_minres_ws_array");
   };
   double* const slot_alfa = slot(SPMV_HIP_MINRES_ALFA);
   double* const slot_ry = slot(SPMV_HIP_MINRES_RY);
@@ -130,10 +122,8 @@ int minres(const Comm& comm, HipExecutor& exec, const Matrix<double>& A,
   w.flags[1] = -1;
   w.flags[2] = 0;
 
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_minres_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_minres_ws_read_async");
-  };
+  auto read = ws_reader(w.ws, w.flags, spmv_hip_minres_ws_read_async,
+                        "spmv_hip_minres_ws_read_async");
   // y = M^-1 r2 where that is a call of its own, and the partials of r2.y
   auto apply_and_dot = [&]() {
     if (pre.sgs)

@@ -53,25 +53,6 @@ using namespace detail;
 //                  (partials of r.z).
 // The last two keep z and share cheb_update_xp (x ; stop test ; p).
 // ---------------------------------------------------------------------------
-namespace
-{
-// the device scalars of the family for up to kmax iterations
-void regrow_scalars(spmv_hip_ctx* ctx, spmv_hip_pcg_ws*& ws, int& kmax_cap,
-                    int kmax)
-{
-  if (kmax <= kmax_cap)
-    return;
-  // (an earlier solve on this workspace has been synchronised: nothing
-  // still reads the old scalars)
-  spmv_hip_pcg_ws_destroy(ws);
-  ws = nullptr;
-  kmax_cap = -1;
-  throw_on_error(spmv_hip_pcg_ws_create(ctx, kmax, &ws),
-                 "spmv_hip_pcg_ws_create");
-  kmax_cap = kmax;
-}
-} // namespace
-
 void PcgFamilyWorkspace::ensure_common(int64_t M, int kmax, int len,
                                        bool need_x,
                                        std::initializer_list<double**> m_vecs)
@@ -79,7 +60,13 @@ void PcgFamilyWorkspace::ensure_common(int64_t M, int kmax, int len,
   open(2);
   if (!dot2)
     dot2 = _exec.alloc<double>(len);
-  regrow_scalars(_exec.context(), ws, kmax_cap, kmax);
+  // the device scalars of the family for up to kmax iterations
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap, spmv_hip_pcg_ws_destroy,
+      [&](auto out) {
+        return spmv_hip_pcg_ws_create(_exec.context(), kmax, out);
+      },
+      "spmv_hip_pcg_ws_create");
   regrow(m_cap, M, m_vecs);
   if (need_x)
     regrow(x_cap, M, {&x});
@@ -89,11 +76,9 @@ void PcgFamilyWorkspace::release_family(
     std::initializer_list<double**> own_vecs)
 {
   release_common();
-  spmv_hip_pcg_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_pcg_ws_destroy);
   free_vectors({&r, &Ap, &x, &p, &dot2});
   free_vectors(own_vecs);
-  kmax_cap = -1;
   m_cap = n_cap = x_cap = -1;
 }
 
@@ -271,10 +256,8 @@ int pcg_solve(const char* who, const Comm& comm, HipExecutor& exec,
   w.flags[1] = -1;
 
   // the state words alone (h == nullptr), or with the history of pairs
-  auto read = [&](double* h, size_t n) {
-    throw_on_error(spmv_hip_pcg_ws_read_async(w.ws, w.flags, h, n, nullptr),
-                   "spmv_hip_pcg_ws_read_async");
-  };
+  auto read = ws_reader(w.ws, w.flags, spmv_hip_pcg_ws_read_async,
+                        "spmv_hip_pcg_ws_read_async");
 
   s.reduce_rz_rr(0);
   LaggingPoll poll(exec, w, opt.poll_every, kmax);

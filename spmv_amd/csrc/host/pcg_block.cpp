@@ -39,11 +39,9 @@ PcgBlockWorkspace::~PcgBlockWorkspace() { release(); }
 void PcgBlockWorkspace::release()
 {
   release_common();
-  spmv_hip_pcgb_ws_destroy(ws);
-  ws = nullptr;
+  drop_scalars(ws, kmax_cap, spmv_hip_pcgb_ws_destroy);
   single.reset();
   free_vectors({&r, &Ap, &z, &x, &p});
-  kmax_cap = -1;
   nrhs_cap = 0;
   m_cap = n_cap = x_cap = -1;
 }
@@ -52,18 +50,15 @@ void PcgBlockWorkspace::ensure(int64_t m_elems, int64_t n_elems, int kmax,
                                int nrhs, bool need_x)
 {
   open(SPMV_HIP_CGB_STATE_WORDS);
-  if (kmax > kmax_cap || nrhs != nrhs_cap) {
-    // (an earlier solve on this workspace has been synchronised: nothing
-    // still reads the old scalars)
-    spmv_hip_pcgb_ws_destroy(ws);
-    ws = nullptr;
-    kmax_cap = -1;
-    nrhs_cap = 0;
-    throw_on_error(spmv_hip_pcgb_ws_create(_exec.context(), kmax, nrhs, &ws),
-                   "spmv_hip_pcgb_ws_create");
-    kmax_cap = kmax;
-    nrhs_cap = nrhs;
-  }
+  regrow_scalars(
+      ws, kmax_cap, kmax, kmax > kmax_cap || nrhs != nrhs_cap,
+      spmv_hip_pcgb_ws_destroy,
+      [&](auto out) {
+        nrhs_cap = 0; // while they are gone
+        return spmv_hip_pcgb_ws_create(_exec.context(), kmax, nrhs, out);
+      },
+      "spmv_hip_pcgb_ws_create");
+  nrhs_cap = nrhs;
   regrow(m_cap, m_elems, {&r, &Ap, &z});
   if (need_x)
     regrow(x_cap, m_elems, {&x});

@@ -123,6 +123,54 @@ double* ws_slot(Ws* ws, int (*get)(Ws*, int, double**), int k, const char* what)
   return q;
 }
 
+// ... and of one array of its state: `get` is its spmv_hip_*_ws_array.
+template <class Ws>
+double* ws_array(Ws* ws, int (*get)(Ws*, int, double**, int64_t*), int which,
+                 const char* what)
+{
+  double* q = nullptr;
+  throw_on_error(get(ws, which, &q, nullptr), what);
+  return q;
+}
+
+// The `read` of LaggingPoll::step and read_history from a solver's
+// spmv_hip_*_ws_read_async: the state words into `flags`, and the history into
+// h[0:n] unless h is null.
+template <class Ws>
+auto ws_reader(Ws* ws, int32_t* flags,
+               int (*read_async)(Ws*, int32_t*, double*, size_t, void*),
+               const char* what)
+{
+  return [=](double* h, size_t n) {
+    throw_on_error(read_async(ws, flags, h, n, nullptr), what);
+  };
+}
+
+// The lifetime of a workspace's device scalars, `ws` with its capacity
+// `kmax_cap`.  regrow_scalars: when `stale` (kmax > kmax_cap, or a block width
+// that changed) they are destroyed and `create(&ws)` makes them anew for kmax
+// iterations -- an earlier solve on the workspace has been synchronised, so
+// nothing still reads the old ones.  While they are gone ws is null and
+// kmax_cap -1, also when create throws.  drop_scalars: what a release() does.
+template <class Ws>
+void drop_scalars(Ws*& ws, int& kmax_cap, int (*destroy)(Ws*))
+{
+  destroy(ws);
+  ws = nullptr;
+  kmax_cap = -1;
+}
+
+template <class Ws, class Create>
+void regrow_scalars(Ws*& ws, int& kmax_cap, int kmax, bool stale,
+                    int (*destroy)(Ws*), Create&& create, const char* what)
+{
+  if (!stale)
+    return;
+  drop_scalars(ws, kmax_cap, destroy);
+  throw_on_error(create(&ws), what);
+  kmax_cap = kmax;
+}
+
 // Lagging look at the flag: every `poll_every` iterations wait for the copy
 // issued `poll_every` iterations ago (bounds the host's run-ahead, never drains
 // the queue), then issue the next one.  `read(nullptr, 0)` is the solver's

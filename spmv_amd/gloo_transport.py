@@ -24,6 +24,14 @@ def init_gloo():
     return rank, world
 
 
+def shutdown():
+    """Ends what init_gloo() began.  A process that exits with the group still
+    alive leaves its teardown to interpreter exit, where torch's background
+    threads can be destroyed while they run: `terminate called without an
+    active exception`, seen on a loaded host after every rank had finished."""
+    dist.destroy_process_group()
+
+
 def make_allgather(world):
     def allgather(user, send, recv, nbytes):
         try:

@@ -263,6 +263,7 @@ def main():
     comm.close()
     exec_.close()
     print(f"rank {rank}/{world}: multirank OK", flush=True)
+    dist_util.shutdown()
 
 
 if __name__ == "__main__":

@@ -134,6 +134,7 @@ def main():
                 assert np.array_equal(got["diagonal"], exp["diagonal"])
     comm.close()
     print(f"rank {rank}/{world}: plan + split OK", flush=True)
+    dist_util.shutdown()
 
 
 if __name__ == "__main__":
