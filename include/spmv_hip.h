@@ -223,6 +223,12 @@ int spmv_hip_csr_plan_create(spmv_hip_ctx* ctx, int32_t num_rows,
                              int symmetric, int algo,
                              spmv_hip_csr_plan** plan);
 int spmv_hip_csr_plan_destroy(spmv_hip_csr_plan* plan);
+/* Bookkeeping for tests: the number of device arrays the CALLING THREAD has
+ * allocated inside the plan builders (csr, mcgs, ilu0, amg plans and their
+ * temporaries) and not yet freed there.  A builder that refuses its input
+ * leaves it where it was.  An array a builder hands to the caller (the coarse
+ * colind of spmv_hip_amg_plan_build) leaves the count with the hand-over. */
+int spmv_hip_plan_live_allocations(int64_t* count);
 /* Optional: let the plan keep its OWN copy of the matrix values in the layout
  * its kernel streams best -- one array per lower offset plus the diagonal
  * ("symmetric diagonal form", a DIA fast path).  This is what
@@ -1385,6 +1391,79 @@ int spmv_hip_amg_prolong_f64(spmv_hip_ctx* ctx, const spmv_hip_amg_plan* plan,
 int spmv_hip_amg_post0_f64(spmv_hip_ctx* ctx, int64_t n, double b0,
                            const double* w, const double* r, const double* dinv,
                            double* d, double* z, void* stream);
+
+/* ---- The symbolic setup of the hierarchy on the device ---------------------------
+ * (hip/spmv_amg_build.hip; spmv::AmgOptions::setup = device.)  The block's CSR
+ * arrays are DEVICE pointers, as a CSRMatrix holds them: num_rows rows, columns
+ * in [0, num_cols), columns >= num_rows are ghosts and ignored; symmetric
+ * storage: only the entries with a column < their row count, the diagonal is
+ * an array.  rowptr == NULL with nnz == 0: an empty block.  Nothing of the
+ * matrix crosses to the host, only counters.  Both entries wait for the device.
+ *
+ * spmv_hip_amg_aggregate: the aggregates of host/amg_build.h's three passes with
+ * "i ascending" read as "i in descending priority" -- order
+ * SPMV_HIP_MCGS_NATURAL: prio(i) = num_rows - i (row order; positive, since 0
+ * stands for "no bid"), amg_aggregate's result entry for entry;
+ * SPMV_HIP_MCGS_HASHED: the hash of spmv_hip_mcgs_color.  agg: num_rows ints on
+ * the device; *n_agg the number of aggregates; rounds[2]: the rounds of pass 1
+ * and of pass 3 (they depend on the matrix and the order alone).  `diagonal` is
+ * accepted for symmetry with the block's arrays and not read (the diagonal
+ * entry is nobody's neighbour).  theta outside [0, 1]: SPMV_HIP_EINVAL.
+ * SPMV_HIP_ERANGE: num_rows + 1 rounds of a pass did not suffice (a fault of
+ * the library, not of the input).
+ *
+ * spmv_hip_amg_plan_build: from an aggregate per row (a DEVICE array, the
+ * caller's own or spmv_hip_amg_aggregate's; every aggregate of [0, n_agg) must
+ * have a member) the plan spmv_hip_amg_plan_create makes from amg_coarsen's
+ * lists for the same aggregates, array for array, with the same plan_bytes;
+ * symmetric storage adds the xrow lists.  The coarse pattern: coarse_rowptr,
+ * n_agg + 1 ints the caller has allocated on the device; *coarse_colind, a
+ * device array of *coarse_nnz ints that becomes the caller's (spmv_hip_free;
+ * NULL for none).  n_agg == 0 describes no step: symmetric storage still gets
+ * its xrow lists.  Values are not read.
+ *
+ * Both check their input on the device before anything is indexed;
+ * SPMV_HIP_EINVAL with info[0] = the reason, nothing is left allocated.
+ * info (SPMV_HIP_AMG_INFO_WORDS): [0] reason, [1] the peak of the temporaries
+ * in bytes, [2] the number of expanded entries (plan_build).
+ *
+ * spmv_hip_amg_plan_sizes / _export: a plan of either builder copied out (host
+ * arrays, NULL skipped).  sizes (SPMV_HIP_AMG_SIZES_WORDS): fine_rows,
+ * coarse_rows, num_values, num_diagonal, coarse_nnz, the length of src, whether
+ * xrow lists exist, the length of xrow_src, plan_bytes.  Lengths: agg, member
+ * fine_rows; member_ptr coarse_rows + 1; src_ptr coarse_nnz + 1; xrow_ptr
+ * fine_rows + 1; a plan without a step has none of the first five. */
+#define SPMV_HIP_AMG_INFO_WORDS 4
+#define SPMV_HIP_AMG_SIZES_WORDS 9
+#define SPMV_HIP_AMG_BAD_ROWPTR 1
+#define SPMV_HIP_AMG_BAD_COLUMN 2
+#define SPMV_HIP_AMG_BAD_AGG 3
+#define SPMV_HIP_AMG_EMPTY_AGG 4
+typedef struct spmv_hip_amg_export {
+  int32_t* agg;
+  int32_t* member_ptr;
+  int32_t* member;
+  int64_t* src_ptr;
+  int32_t* src;
+  int64_t* xrow_ptr;
+  int32_t* xrow_src;
+} spmv_hip_amg_export;
+int spmv_hip_amg_aggregate(spmv_hip_ctx* ctx, int32_t num_rows, int32_t num_cols,
+                           int64_t nnz, const int32_t* rowptr,
+                           const int32_t* colind, const double* values,
+                           const double* diagonal, int symmetric, double theta,
+                           int order, int32_t* agg, int32_t* n_agg, int* rounds,
+                           int64_t* info, void* stream);
+int spmv_hip_amg_plan_build(spmv_hip_ctx* ctx, int32_t num_rows, int32_t num_cols,
+                            int64_t nnz, const int32_t* rowptr,
+                            const int32_t* colind, int symmetric,
+                            const int32_t* agg, int32_t n_agg,
+                            int32_t* coarse_rowptr, int32_t** coarse_colind,
+                            int64_t* coarse_nnz, spmv_hip_amg_plan** plan,
+                            int64_t* info, void* stream);
+int spmv_hip_amg_plan_sizes(const spmv_hip_amg_plan* plan, int64_t* sizes);
+int spmv_hip_amg_plan_export(const spmv_hip_amg_plan* plan,
+                             const spmv_hip_amg_export* out);
 
 /* ---- The V-cycle's vector kernels for nrhs INTERLEAVED vectors ------------------
  * (spmv::amg_apply_block).  Element (i, c) of a block at V[i * nrhs + c], 1 <=

@@ -694,6 +694,22 @@ int spmvh_amg_symbolic_get(spmvh_amg_symbolic* sym, int32_t* agg,
 int spmvh_amg_symbolic_destroy(spmvh_amg_symbolic* sym);
 int spmvh_amg_create(spmvh_exec* exec, spmvh_matrix* A, const double* options,
                      spmvh_amg** M);
+/* spmvh_amg_create_ex: spmvh_amg_create with AmgOptions::setup (0 host, 1
+ * device) and ::order (-1 none given, 0 hashed, 1 natural; device only: setup =
+ * 0 with an order >= 0 fails).  spmvh_amg_setup_info: info[4] = {aggregate us, build us, the
+ * peak of the device setup's temporaries in bytes, setup}; zeros for setup =
+ * host.  spmvh_amg_level_rounds: rounds[2] = the rounds of pass 1 and pass 3
+ * of the step from `level` (0: host, or no step).  spmvh_amg_step_sizes /
+ * _export: spmv_hip_amg_plan_sizes / _export of the level's plan (sizes all 0
+ * and _export an error where the level has none); host arrays, NULL skipped. */
+int spmvh_amg_create_ex(spmvh_exec* exec, spmvh_matrix* A, const double* options,
+                        int setup, int order, spmvh_amg** M);
+int spmvh_amg_setup_info(spmvh_amg* M, int64_t* info);
+int spmvh_amg_level_rounds(spmvh_amg* M, int level, int* rounds);
+int spmvh_amg_step_sizes(spmvh_amg* M, int level, int64_t* sizes);
+int spmvh_amg_step_export(spmvh_amg* M, int level, int32_t* agg,
+                          int32_t* member_ptr, int32_t* member, int64_t* src_ptr,
+                          int32_t* src, int64_t* xrow_ptr, int32_t* xrow_src);
 int spmvh_amg_destroy(spmvh_amg* M);
 int spmvh_amg_refresh(spmvh_amg* M, spmvh_matrix* A);
 int spmvh_amg_info(spmvh_amg* M, int64_t* info);

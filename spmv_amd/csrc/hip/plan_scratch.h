@@ -21,6 +21,10 @@
 #include "spmv_hip.h"
 
 extern thread_local int64_t spmv_plan_mem_ns; // spmv_csr_plan.hip
+// arrays this thread has allocated through spmv_plan_malloc and not yet freed
+// through spmv_plan_free (spmv_hip_plan_live_allocations): the builders'
+// tests read it around a refused call to see that nothing was left behind
+extern thread_local int64_t spmv_plan_live_allocs; // spmv_csr_plan.hip
 
 template <typename P>
 static inline hipError_t spmv_plan_malloc(P** p, size_t bytes)
@@ -30,12 +34,16 @@ static inline hipError_t spmv_plan_malloc(P** p, size_t bytes)
   spmv_plan_mem_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(
                           std::chrono::steady_clock::now() - t0)
                           .count();
+  if (e == hipSuccess && bytes > 0)
+    ++spmv_plan_live_allocs;
   return e;
 }
 static inline hipError_t spmv_plan_free(void* p)
 {
   const auto t0 = std::chrono::steady_clock::now();
   const hipError_t e = hipFree(p);
+  if (p)
+    --spmv_plan_live_allocs;
   spmv_plan_mem_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(
                           std::chrono::steady_clock::now() - t0)
                           .count();

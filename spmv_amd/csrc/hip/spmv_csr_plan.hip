@@ -18,6 +18,14 @@
 #include "plan_scratch.h"
 
 thread_local int64_t spmv_plan_mem_ns = 0; // (plan_scratch.h)
+thread_local int64_t spmv_plan_live_allocs = 0;
+
+extern "C" int spmv_hip_plan_live_allocations(int64_t* count)
+{
+  SPMV_REQUIRE(count != nullptr);
+  *count = spmv_plan_live_allocs;
+  return SPMV_HIP_OK;
+}
 
 namespace
 {

@@ -1,5 +1,6 @@
 // spmv::AmgPreconditioner and amg_apply for HipExecutor: see cg.h.  The
-// aggregates, patterns and source lists are amg_build.h's, on the host; the
+// aggregates, patterns and source lists are amg_build.h's, on the host, or
+// (AmgOptions::setup = device) spmv_amg_build.hip's, on the device; the
 // numbers are spmv_amg.hip's, on the device, on the executor's current stream:
 //     per coarsening step  galerkin (the coarse values) ; the coarse block's
 //                          plan ; a read-back of the values for the next step
@@ -32,7 +33,8 @@ struct AmgPreconditioner::Level {
   // symmetric storage
   spmv_hip_amg_plan* plan = nullptr;
   bool has_step = false;
-  std::vector<int32_t> agg;
+  std::vector<int32_t> agg; // setup = device: fetched by aggregates()
+  int rounds[2] = {0, 0};   // setup = device: of pass 1 and pass 3
   // d, dinv, r, w, dd: rows; z: cols, ghost tail zero
   double *d = nullptr, *dinv = nullptr, *z = nullptr, *r = nullptr,
          *w = nullptr, *dd = nullptr;
@@ -41,6 +43,18 @@ struct AmgPreconditioner::Level {
   double lmax = 0, lmin = 0;
   double sa[kChebyshevMaxDegree], sb[kChebyshevMaxDegree]; // smoother
   double ca[kChebyshevMaxDegree], cb[kChebyshevMaxDegree]; // coarsest level
+};
+
+struct AmgPreconditioner::Clock {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double lap()
+  {
+    const auto t1 = std::chrono::steady_clock::now();
+    const double ms
+        = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+    return ms;
+  }
 };
 
 namespace
@@ -69,18 +83,6 @@ const CSRMatrix<double>* amg_block_of(const Matrix<double>& A, const char* who)
   return blk;
 }
 
-struct Clock {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  double lap()
-  {
-    const auto t1 = std::chrono::steady_clock::now();
-    const double ms
-        = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t0 = t1;
-    return ms;
-  }
-};
-
 } // namespace
 
 AmgPreconditioner::AmgPreconditioner(HipExecutor& exec, const Matrix<double>& A,
@@ -90,6 +92,10 @@ AmgPreconditioner::AmgPreconditioner(HipExecutor& exec, const Matrix<double>& A,
   amg_check_options(_opt.theta, _opt.max_levels, _opt.min_coarse_rows,
                     _opt.smooth_degree, _opt.coarse_degree, _opt.eig_ratio,
                     _opt.coarse_scale);
+  if (_opt.setup == SgsSetup::host && _opt.order != SgsOrder::hashed)
+    throw std::invalid_argument(
+        "spmv::AmgPreconditioner - Error: setup = host aggregates in row order: "
+        "it takes no order");
   amg_block_of(A, "");
   _symmetric = A.symmetric();
   try {
@@ -190,125 +196,240 @@ void AmgPreconditioner::level_numbers(Level& L)
   chebyshev_coefficients(_opt.coarse_degree, L.lmin, L.lmax, L.ca, L.cb);
 }
 
+// One step of the device setup: the aggregates of L and the plan of its step
+// (symmetric storage: the xrow lists, step or no step), from L's arrays where
+// they lie.  -> the rows of the coarse level, 0: no step; then *c_rowptr /
+// *c_colind are the coarse pattern on the device, the caller's to free or to
+// hand on.
+int32_t AmgPreconditioner::step_on_device(Level& L, bool sym, bool coarsen,
+                                       int32_t** c_rowptr, int32_t** c_colind,
+                                       int64_t* c_nnz)
+{
+  spmv_hip_ctx* ctx = _exec.context();
+  const CSRMatrix<double>& B = *L.op;
+  const bool has = L.nnz > 0; // (an empty block owns no arrays)
+  const int32_t* rowptr = has ? B.rowptr() : nullptr;
+  const int32_t* colind = has ? B.colind() : nullptr;
+  int64_t info[SPMV_HIP_AMG_INFO_WORDS];
+  int32_t* agg = nullptr;
+  int32_t nc = 0;
+  *c_rowptr = *c_colind = nullptr;
+  *c_nnz = 0;
+  Clock clock;
+  try {
+    if (coarsen) {
+      agg = _exec.alloc<int32_t>((size_t)L.rows);
+      throw_on_error(
+          spmv_hip_amg_aggregate(ctx, L.rows, L.cols, L.nnz, rowptr, colind,
+                                 has ? B.values() : nullptr,
+                                 sym ? B.diagonal() : nullptr, sym ? 1 : 0,
+                                 _opt.theta,
+                                 _opt.order == SgsOrder::natural
+                                     ? SPMV_HIP_MCGS_NATURAL
+                                     : SPMV_HIP_MCGS_HASHED,
+                                 agg, &nc, L.rounds, info, nullptr),
+          "spmv_hip_amg_aggregate");
+      _setup_temp_bytes = std::max(_setup_temp_bytes, info[1]);
+      if (nc == L.rows) // nothing merged: discard it
+        nc = 0;
+      if (nc == 0)
+        L.rounds[0] = L.rounds[1] = 0;
+    }
+    _aggregate_ms += clock.lap();
+    if (nc > 0)
+      *c_rowptr = _exec.alloc<int32_t>((size_t)nc + 1);
+    throw_on_error(spmv_hip_amg_plan_build(ctx, L.rows, L.cols, L.nnz, rowptr,
+                                           colind, sym ? 1 : 0,
+                                           nc > 0 ? agg : nullptr, nc, *c_rowptr,
+                                           c_colind, c_nnz, &L.plan, info,
+                                           nullptr),
+                   "spmv_hip_amg_plan_build");
+    _setup_temp_bytes = std::max(_setup_temp_bytes, info[1]);
+  } catch (...) {
+    if (agg)
+      _exec.free(agg);
+    if (*c_rowptr)
+      _exec.free(*c_rowptr);
+    *c_rowptr = nullptr;
+    throw;
+  }
+  if (agg)
+    _exec.free(agg);
+  _build_ms += clock.lap();
+  return nc;
+}
+
+// The coarse level of L's step: the pattern arrays (device, filled; this
+// function owns them from the call on) are adopted by a new block whose values
+// the device sums from L's plan.
+void AmgPreconditioner::add_coarse_level(Level& L, int32_t nc, int64_t nnz_c,
+                                         int32_t* c_rowptr, int32_t* c_colind)
+{
+  // coarse blocks live on this executor; the object does not own it
+  std::shared_ptr<DeviceExecutor> shared(std::shared_ptr<void>(), &_exec);
+  double* c_values = nullptr;
+  std::unique_ptr<Level> next;
+  try {
+    c_values = _exec.alloc<double>((size_t)nnz_c);
+    next = std::make_unique<Level>();
+    throw_on_error(spmv_hip_amg_galerkin_f64(_exec.context(), L.plan,
+                                             L.op->values(), L.op->diagonal(),
+                                             c_values, nullptr),
+                   "spmv_hip_amg_galerkin_f64");
+  } catch (...) {
+    for (void* p : {(void*)c_rowptr, (void*)c_colind, (void*)c_values})
+      if (p)
+        _exec.free(p);
+    throw;
+  }
+  // (the block owns the arrays from here on; its plan sees the values)
+  next->own.reset(new CSRMatrix<double>(CSRMatrix<double>::AdoptDevice(), shared,
+                                        nc, nc, nnz_c, c_rowptr, c_colind,
+                                        c_values, nullptr, false));
+  if (next->own->csr_released())
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner - Error: the context released the CSR "
+        "arrays of a coarse level (release_csr); the hierarchy needs them");
+  next->op = next->own.get();
+  next->rows = next->cols = nc;
+  next->nnz = nnz_c;
+  _levels.push_back(std::move(next));
+}
+
+// setup = host: every level is read back and coarsened by amg_build.h
+void AmgPreconditioner::levels_on_host(Clock& clock)
+{
+  spmv_hip_ctx* ctx = _exec.context();
+  const DeviceExecutor& host = _exec.get_host();
+  const CSRMatrix<double>* blk = _levels[0]->op;
+  const int64_t n0 = _levels[0]->rows;
+  // level 0, read back (the copies wait for the device)
+  std::vector<int32_t> rowptr((size_t)n0 + 1, 0), colind((size_t)_num_values);
+  std::vector<double> values((size_t)_num_values), diagonal;
+  if (_num_values > 0) { // (an empty block owns no arrays)
+    _exec.copy_to<int32_t>(rowptr.data(), host, blk->rowptr(), (size_t)n0 + 1);
+    _exec.copy_to<int32_t>(colind.data(), host, blk->colind(),
+                           (size_t)_num_values);
+    _exec.copy_to<double>(values.data(), host, blk->values(),
+                          (size_t)_num_values);
+  }
+  if (_symmetric && n0 > 0) {
+    diagonal.resize((size_t)n0);
+    _exec.copy_to<double>(diagonal.data(), host, blk->diagonal(), (size_t)n0);
+  }
+  for (;;) {
+    Level& L = *_levels.back();
+    const bool sym = _symmetric && _levels.size() == 1;
+    const bool coarsen = L.rows > _opt.min_coarse_rows
+                         && (int)_levels.size() < _opt.max_levels;
+    if (!coarsen && !sym)
+      break;
+    const AmgExpanded x
+        = amg_expand(rowptr.data(), colind.data(), L.rows, L.rows, sym);
+    AmgStep step;
+    if (coarsen) {
+      step = amg_aggregate(x, values.data(), diagonal.data(), _opt.theta);
+      if (step.n_agg == L.rows) // nothing merged: discard it
+        step = AmgStep();
+      else
+        amg_galerkin_pattern(x, &step);
+    }
+    const int32_t nc = step.n_agg;
+    const int64_t nnz_c = (int64_t)step.colind.size();
+    spmv_hip_amg_host in{};
+    in.fine_rows = L.rows;
+    in.coarse_rows = nc;
+    in.num_values = L.nnz;
+    in.num_diagonal = sym ? L.rows : 0;
+    in.coarse_nnz = nnz_c;
+    if (nc > 0) {
+      in.agg = step.agg.data();
+      in.member_ptr = step.member_ptr.data();
+      in.member = step.member.data();
+      in.src_ptr = step.src_ptr.data();
+      in.src = step.src.data();
+    }
+    if (sym) {
+      in.xrow_ptr = x.ptr.data();
+      in.xrow_src = x.src.data();
+    }
+    throw_on_error(spmv_hip_amg_plan_create(ctx, &in, &L.plan),
+                   "spmv_hip_amg_plan_create");
+    if (nc == 0)
+      break;
+    L.has_step = true;
+    L.agg = std::move(step.agg);
+    _symbolic_ms += clock.lap();
+
+    // the coarse block: pattern uploaded, values summed on the device
+    int32_t *c_rowptr = nullptr, *c_colind = nullptr;
+    try {
+      c_rowptr = _exec.alloc<int32_t>((size_t)nc + 1);
+      c_colind = _exec.alloc<int32_t>((size_t)nnz_c);
+      _exec.copy_from<int32_t>(c_rowptr, host, step.rowptr.data(), (size_t)nc + 1);
+      _exec.copy_from<int32_t>(c_colind, host, step.colind.data(), (size_t)nnz_c);
+    } catch (...) {
+      for (int32_t* p : {c_rowptr, c_colind})
+        if (p)
+          _exec.free(p);
+      throw;
+    }
+    add_coarse_level(L, nc, nnz_c, c_rowptr, c_colind);
+    // the next step aggregates on the host
+    rowptr = std::move(step.rowptr);
+    colind = std::move(step.colind);
+    values.resize((size_t)nnz_c);
+    _exec.copy_to<double>(values.data(), host, _levels.back()->own->values(),
+                          (size_t)nnz_c);
+    diagonal.clear();
+    _numeric_ms += clock.lap();
+  }
+}
+
+// setup = device: nothing of any level's matrix is read back
+void AmgPreconditioner::levels_on_device(Clock& clock)
+{
+  for (;;) {
+    Level& L = *_levels.back();
+    const bool sym = _symmetric && _levels.size() == 1;
+    const bool coarsen = L.rows > _opt.min_coarse_rows
+                         && (int)_levels.size() < _opt.max_levels;
+    if (!coarsen && !sym)
+      break;
+    int32_t *c_rowptr = nullptr, *c_colind = nullptr;
+    int64_t nnz_c = 0;
+    const int32_t nc
+        = step_on_device(L, sym, coarsen, &c_rowptr, &c_colind, &nnz_c);
+    if (nc == 0)
+      break;
+    L.has_step = true;
+    _symbolic_ms += clock.lap();
+    add_coarse_level(L, nc, nnz_c, c_rowptr, c_colind);
+    _numeric_ms += clock.lap();
+  }
+}
+
 void AmgPreconditioner::numeric(const Matrix<double>& A, bool build)
 {
   const auto* blk = static_cast<const CSRMatrix<double>*>(A.local_block());
   spmv_hip_ctx* ctx = _exec.context();
-  const DeviceExecutor& host = _exec.get_host();
   _usable = false;
   Clock clock;
   if (build) {
-    _symbolic_ms = _numeric_ms = 0;
+    _symbolic_ms = _numeric_ms = _aggregate_ms = _build_ms = 0;
+    _setup_temp_bytes = 0;
     _stat = _exec.alloc<uint64_t>(SPMV_HIP_AMG_STAT_WORDS);
     _num_values = blk->non_zeros();
-    const int64_t n0 = A.row_map()->local_size();
-
-    // level 0, read back (the copies wait for the device)
-    std::vector<int32_t> rowptr((size_t)n0 + 1, 0), colind((size_t)_num_values);
-    std::vector<double> values((size_t)_num_values), diagonal;
-    if (_num_values > 0) { // (an empty block owns no arrays)
-      _exec.copy_to<int32_t>(rowptr.data(), host, blk->rowptr(), (size_t)n0 + 1);
-      _exec.copy_to<int32_t>(colind.data(), host, blk->colind(),
-                             (size_t)_num_values);
-      _exec.copy_to<double>(values.data(), host, blk->values(),
-                            (size_t)_num_values);
-    }
-    if (_symmetric && n0 > 0) {
-      diagonal.resize((size_t)n0);
-      _exec.copy_to<double>(diagonal.data(), host, blk->diagonal(), (size_t)n0);
-    }
-    // coarse blocks live on this executor; the object does not own it
-    std::shared_ptr<DeviceExecutor> shared(std::shared_ptr<void>(), &_exec);
-
     auto first = std::make_unique<Level>();
     first->op = blk;
-    first->rows = (int32_t)n0;
+    first->rows = (int32_t)A.row_map()->local_size();
     first->cols = blk->cols();
     first->nnz = _num_values;
     _levels.push_back(std::move(first));
-    for (;;) {
-      Level& L = *_levels.back();
-      const bool sym = _symmetric && _levels.size() == 1;
-      const bool coarsen = L.rows > _opt.min_coarse_rows
-                           && (int)_levels.size() < _opt.max_levels;
-      if (!coarsen && !sym)
-        break;
-      const AmgExpanded x
-          = amg_expand(rowptr.data(), colind.data(), L.rows, L.rows, sym);
-      AmgStep step;
-      if (coarsen) {
-        step = amg_aggregate(x, values.data(), diagonal.data(), _opt.theta);
-        if (step.n_agg == L.rows) // nothing merged: discard it
-          step = AmgStep();
-        else
-          amg_galerkin_pattern(x, &step);
-      }
-      const int32_t nc = step.n_agg;
-      const int64_t nnz_c = (int64_t)step.colind.size();
-      spmv_hip_amg_host in{};
-      in.fine_rows = L.rows;
-      in.coarse_rows = nc;
-      in.num_values = L.nnz;
-      in.num_diagonal = sym ? L.rows : 0;
-      in.coarse_nnz = nnz_c;
-      if (nc > 0) {
-        in.agg = step.agg.data();
-        in.member_ptr = step.member_ptr.data();
-        in.member = step.member.data();
-        in.src_ptr = step.src_ptr.data();
-        in.src = step.src.data();
-      }
-      if (sym) {
-        in.xrow_ptr = x.ptr.data();
-        in.xrow_src = x.src.data();
-      }
-      throw_on_error(spmv_hip_amg_plan_create(ctx, &in, &L.plan),
-                     "spmv_hip_amg_plan_create");
-      if (nc == 0)
-        break;
-      L.has_step = true;
-      L.agg = std::move(step.agg);
-      _symbolic_ms += clock.lap();
-
-      // the coarse block: pattern uploaded, values summed on the device
-      int32_t* c_rowptr = _exec.alloc<int32_t>((size_t)nc + 1);
-      int32_t* c_colind = _exec.alloc<int32_t>((size_t)nnz_c);
-      double* c_values = _exec.alloc<double>((size_t)nnz_c);
-      auto next = std::make_unique<Level>();
-      try {
-        _exec.copy_from<int32_t>(c_rowptr, host, step.rowptr.data(),
-                                 (size_t)nc + 1);
-        _exec.copy_from<int32_t>(c_colind, host, step.colind.data(),
-                                 (size_t)nnz_c);
-        throw_on_error(spmv_hip_amg_galerkin_f64(ctx, L.plan, L.op->values(),
-                                                 L.op->diagonal(), c_values,
-                                                 nullptr),
-                       "spmv_hip_amg_galerkin_f64");
-      } catch (...) {
-        _exec.free(c_rowptr);
-        _exec.free(c_colind);
-        _exec.free(c_values);
-        throw;
-      }
-      // (the block owns the arrays from here on; its plan sees the values)
-      next->own.reset(new CSRMatrix<double>(CSRMatrix<double>::AdoptDevice(),
-                                            shared, nc, nc, nnz_c, c_rowptr,
-                                            c_colind, c_values, nullptr, false));
-      if (next->own->csr_released())
-        throw std::runtime_error(
-            "spmv::AmgPreconditioner - Error: the context released the CSR "
-            "arrays of a coarse level (release_csr); the hierarchy needs them");
-      next->op = next->own.get();
-      next->rows = next->cols = nc;
-      next->nnz = nnz_c;
-      rowptr = std::move(step.rowptr);
-      colind = std::move(step.colind);
-      values.resize((size_t)nnz_c);
-      _exec.copy_to<double>(values.data(), host, c_values, (size_t)nnz_c);
-      diagonal.clear();
-      _levels.push_back(std::move(next));
-      _numeric_ms += clock.lap();
-    }
+    if (_opt.setup == SgsSetup::device)
+      levels_on_device(clock);
+    else
+      levels_on_host(clock);
     for (auto& lp : _levels) {
       Level& L = *lp;
       if (L.rows == 0)
@@ -482,10 +603,34 @@ double AmgPreconditioner::lmax(int level) const
   return _levels[(size_t)level]->lmax;
 }
 
+int AmgPreconditioner::rounds(int level, int pass) const
+{
+  check_level(level, levels(), "rounds");
+  const Level& L = *_levels[(size_t)level];
+  if (pass > 1)
+    throw std::runtime_error(
+        "spmv::AmgPreconditioner::rounds - Error: no such pass");
+  return pass < 0 ? L.rounds[0] + L.rounds[1] : L.rounds[pass];
+}
+
+const spmv_hip_amg_plan* AmgPreconditioner::step_plan(int level) const
+{
+  check_level(level, levels(), "step_plan");
+  return _levels[(size_t)level]->plan;
+}
+
 void AmgPreconditioner::aggregates(int level, int32_t* out) const
 {
   check_level(level, levels() - 1, "aggregates");
-  const std::vector<int32_t>& agg = _levels[(size_t)level]->agg;
+  Level& L = *_levels[(size_t)level];
+  if (L.agg.empty() && L.rows > 0) { // setup = device keeps no host copy
+    L.agg.resize((size_t)L.rows);
+    spmv_hip_amg_export ex{};
+    ex.agg = L.agg.data();
+    throw_on_error(spmv_hip_amg_plan_export(L.plan, &ex),
+                   "spmv_hip_amg_plan_export");
+  }
+  const std::vector<int32_t>& agg = L.agg;
   if (!out && !agg.empty())
     throw std::runtime_error(
         "spmv::AmgPreconditioner::aggregates - Error: NULL output");

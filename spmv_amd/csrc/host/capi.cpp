@@ -1943,6 +1943,83 @@ int spmvh_amg_create(spmvh_exec* exec, spmvh_matrix* A, const double* options,
   });
 }
 
+int spmvh_amg_create_ex(spmvh_exec* exec, spmvh_matrix* A, const double* options,
+                        int setup, int order, spmvh_amg** M)
+{
+  return guarded([&] {
+    require(exec && A && M, "NULL argument");
+    require(exec->hip != nullptr, "not a HipExecutor");
+    require(setup == 0 || setup == 1, "setup is 0 (host) or 1 (device)");
+    require(order >= -1 && order <= 1,
+            "order is -1 (none given), 0 (hashed) or 1 (natural)");
+    if (setup == 0 && order >= 0)
+      throw std::invalid_argument(
+          "spmv::AmgPreconditioner - Error: setup = host aggregates in row "
+          "order: it takes no order");
+    AmgOptions opt;
+    if (options) {
+      opt.theta = options[0];
+      opt.max_levels = (int)options[1];
+      opt.min_coarse_rows = (int64_t)options[2];
+      opt.smooth_degree = (int)options[3];
+      opt.coarse_degree = (int)options[4];
+      opt.eig_ratio = options[5];
+      opt.coarse_scale = options[6];
+    }
+    opt.setup = setup == 1 ? SgsSetup::device : SgsSetup::host;
+    opt.order = order == 1 ? SgsOrder::natural : SgsOrder::hashed;
+    auto m = std::make_unique<spmvh_amg>();
+    m->M.reset(new AmgPreconditioner(*exec->hip, *A->A, opt));
+    *M = m.release();
+  });
+}
+
+int spmvh_amg_setup_info(spmvh_amg* M, int64_t* info)
+{
+  return guarded([&] {
+    require(M && info, "NULL argument");
+    info[0] = (int64_t)(M->M->aggregate_ms() * 1000.0);
+    info[1] = (int64_t)(M->M->build_ms() * 1000.0);
+    info[2] = M->M->setup_temp_bytes();
+    info[3] = M->M->options().setup == SgsSetup::device ? 1 : 0;
+  });
+}
+
+int spmvh_amg_level_rounds(spmvh_amg* M, int level, int* rounds)
+{
+  return guarded([&] {
+    require(M && rounds, "NULL argument");
+    rounds[0] = M->M->rounds(level, 0);
+    rounds[1] = M->M->rounds(level, 1);
+  });
+}
+
+int spmvh_amg_step_sizes(spmvh_amg* M, int level, int64_t* sizes)
+{
+  return guarded([&] {
+    require(M && sizes, "NULL argument");
+    const spmv_hip_amg_plan* p = M->M->step_plan(level);
+    for (int k = 0; k < SPMV_HIP_AMG_SIZES_WORDS; ++k)
+      sizes[k] = 0;
+    if (p)
+      throw_on_error(spmv_hip_amg_plan_sizes(p, sizes), "spmv_hip_amg_plan_sizes");
+  });
+}
+
+int spmvh_amg_step_export(spmvh_amg* M, int level, int32_t* agg,
+                          int32_t* member_ptr, int32_t* member, int64_t* src_ptr,
+                          int32_t* src, int64_t* xrow_ptr, int32_t* xrow_src)
+{
+  return guarded([&] {
+    require(M != nullptr, "NULL argument");
+    const spmv_hip_amg_plan* p = M->M->step_plan(level);
+    require(p != nullptr, "the level has no plan");
+    const spmv_hip_amg_export ex{agg, member_ptr, member, src_ptr,
+                                 src, xrow_ptr,   xrow_src};
+    throw_on_error(spmv_hip_amg_plan_export(p, &ex), "spmv_hip_amg_plan_export");
+  });
+}
+
 int spmvh_amg_destroy(spmvh_amg* M)
 {
   return guarded([&] { delete M; });

@@ -28,6 +28,7 @@ struct spmv_hip_idrs_ws;
 struct spmv_hip_mcgs_plan;
 struct spmv_hip_ilu0_plan;
 struct spmv_hip_amg_tail;
+struct spmv_hip_amg_plan;
 
 namespace spmv
 {
@@ -877,6 +878,10 @@ struct AmgOptions {
   int coarse_degree = 8;        // 1..kChebyshevMaxDegree, the coarsest level
   double eig_ratio = 4.0;       // > 1: lmin = lmax / eig_ratio
   double coarse_scale = 1.0;    // 1 <= coarse_scale < 2
+  // Where the symbolic setup runs (see "Setup" below).  An order with setup =
+  // host throws std::invalid_argument, as SgsOptions does.
+  SgsSetup setup = SgsSetup::host;
+  SgsOrder order = SgsOrder::hashed; // device only
 };
 constexpr int kAmgMaxLevels = 16;
 
@@ -936,6 +941,21 @@ constexpr int kAmgMaxLevels = 16;
 // The level work vectors belong to the object: an application is NOT
 // reentrant -- one amg_apply / pcg_amg / gmres at a time per object.
 //
+// Setup.  setup = host (the default): the constructor reads every level's
+// matrix back and runs host/amg_build.h single-threaded.  setup = device: the
+// aggregates (spmv_hip_amg_aggregate) and every list of a step
+// (spmv_hip_amg_plan_build) are made on the device from the arrays where they
+// lie; nothing of any level's matrix crosses to the host, only counts (n_agg,
+// the coarse entries, rounds) and the words of the diagonal check and the
+// bound.  The three passes are amg_build.h's with "i ascending" read as "i in
+// descending priority": order = natural, prio(i) = rows - i, gives the host's
+// hierarchy entry for entry, bit for bit, but needs as many rounds as the
+// longest dependency chain (slow on a lattice in row order); order = hashed
+// (the default of the device setup), mcgs_color's hash, decides a lattice in a
+// few dozen rounds and gives OTHER aggregates.
+// refresh(), the cycle, the tail and the solvers take the object unchanged;
+// no host copy of agg is kept, aggregates() fetches it on its first call.
+//
 // The tail.  The levels below the finest are small, and an application spends
 // most of its time launching their kernels.  set_tail_rows(max_rows) names the
 // longest suffix t .. levels()-1, t >= 1, in which every level has rows(l) <=
@@ -979,6 +999,17 @@ public:
   int64_t plan_bytes() const; // device memory beyond A: levels, lists, vectors
   double symbolic_ms() const { return _symbolic_ms; }
   double numeric_ms() const { return _numeric_ms; }
+  // The device setup's record; setup = host: 0.  rounds: of pass 1 (pass = 0),
+  // of pass 3 (pass = 1) or of both (pass < 0) of the step from `level`; 0 for
+  // the last level.  aggregate_ms + build_ms is the part of symbolic_ms spent in
+  // the two device builders; setup_temp_bytes the peak of their temporaries.
+  int rounds(int level, int pass = -1) const;
+  double aggregate_ms() const { return _aggregate_ms; }
+  double build_ms() const { return _build_ms; }
+  int64_t setup_temp_bytes() const { return _setup_temp_bytes; }
+  // the device plan of the step from `level` (or of the expanded rows of
+  // symmetric storage), for spmv_hip_amg_plan_sizes / _export; may be NULL
+  const spmv_hip_amg_plan* step_plan(int level) const;
   const AmgOptions& options() const { return _opt; }
 
   void set_tail_rows(int64_t max_rows);
@@ -1001,6 +1032,13 @@ private:
   void ensure_block_scratch(int nrhs) const;
   void free_block_scratch() const;
   void numeric(const Matrix<double>& A, bool build);
+  struct Clock;
+  void levels_on_host(Clock& clock);
+  void levels_on_device(Clock& clock);
+  void add_coarse_level(Level& L, int32_t nc, int64_t nnz_c, int32_t* c_rowptr,
+                        int32_t* c_colind);
+  int32_t step_on_device(Level& L, bool sym, bool coarsen, int32_t** c_rowptr,
+                         int32_t** c_colind, int64_t* c_nnz);
   void level_numbers(Level& L);
   void check_usable() const;
   void release();
@@ -1017,7 +1055,8 @@ private:
   std::vector<int> _tail_lanes;
   bool _symmetric = false, _usable = false;
   int64_t _num_values = 0;
-  double _symbolic_ms = 0, _numeric_ms = 0;
+  double _symbolic_ms = 0, _numeric_ms = 0, _aggregate_ms = 0, _build_ms = 0;
+  int64_t _setup_temp_bytes = 0;
   // apply_block: the width the levels' block vectors hold (0: none), the width
   // of the last application (the ghost tail of level 0's z is zeroed for it),
   // and the columns of level 0's per-column product (see amg_apply_block)

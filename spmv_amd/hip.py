@@ -448,3 +448,100 @@ class AmgTail:
         if self.h:
             call("spmv_hip_amg_tail_destroy", self.h)
             self.h = None
+
+
+class AmgExport(C.Structure):
+    """spmv_hip_amg_export: host pointers, NULL skipped"""
+    _fields_ = [("agg", C.c_void_p), ("member_ptr", C.c_void_p),
+                ("member", C.c_void_p), ("src_ptr", C.c_void_p),
+                ("src", C.c_void_p), ("xrow_ptr", C.c_void_p),
+                ("xrow_src", C.c_void_p)]
+
+
+AMG_HASHED, AMG_NATURAL = 0, 1
+_AMG_EXPORT = (("agg", np.int32), ("member_ptr", np.int32), ("member", np.int32),
+               ("src_ptr", np.int64), ("src", np.int32), ("xrow_ptr", np.int64),
+               ("xrow_src", np.int32))
+
+
+def amg_aggregate(ctx, num_rows, num_cols, nnz, rowptr, colind, values, diagonal,
+                  symmetric, theta, order, agg):
+    """spmv_hip_amg_aggregate on DEVICE pointers (`ctx`: a spmv_hip_ctx pointer;
+    agg: num_rows ints) -> (n_agg, (rounds of pass 1, of pass 3), info).  Raises
+    _lib.SpmvHipError; .info holds the words then."""
+    n_agg, rounds, info = C.c_int32(), (C.c_int * 2)(), np.zeros(4, np.int64)
+    try:
+        call("spmv_hip_amg_aggregate", ctx, num_rows, num_cols, nnz, rowptr,
+             colind, values, diagonal, int(bool(symmetric)), float(theta),
+             int(order), agg, C.byref(n_agg), rounds, info.ctypes.data, None)
+    except _lib.SpmvHipError as e:
+        e.info = info
+        raise
+    return n_agg.value, (int(rounds[0]), int(rounds[1])), info
+
+
+class AmgBuiltPlan:
+    """spmv_hip_amg_plan made by spmv_hip_amg_plan_build from DEVICE arrays and
+    a DEVICE agg.  coarse_rowptr: n_agg + 1 ints the caller allocated on the
+    device; .coarse_colind (a device address, freed by close()) and .coarse_nnz
+    are returned.  A failure raises _lib.SpmvHipError with .info and leaves
+    nothing allocated."""
+
+    def __init__(self, ctx, num_rows, num_cols, nnz, rowptr, colind, symmetric,
+                 agg, n_agg, coarse_rowptr):
+        self.ctx, self.h, self.coarse_colind = ctx, None, None
+        h, ci, nnz_c = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self.info = np.zeros(4, np.int64)
+        try:
+            call("spmv_hip_amg_plan_build", ctx, num_rows, num_cols, nnz, rowptr,
+                 colind, int(bool(symmetric)), agg, n_agg, coarse_rowptr,
+                 C.byref(ci), C.byref(nnz_c), C.byref(h), self.info.ctypes.data,
+                 None)
+        except _lib.SpmvHipError as e:
+            e.info = self.info
+            raise
+        self.h, self.coarse_colind, self.coarse_nnz = h, ci.value, nnz_c.value
+
+    def sizes(self):
+        return plan_sizes(self.h)
+
+    def export(self):
+        return plan_export(self.h)
+
+    def bytes(self):
+        n = C.c_int64()
+        call("spmv_hip_amg_plan_bytes", self.h, C.byref(n))
+        return n.value
+
+    def close(self):
+        if self.coarse_colind:
+            call("spmv_hip_free", self.ctx, self.coarse_colind)
+            self.coarse_colind = None
+        if self.h:
+            call("spmv_hip_amg_plan_destroy", self.h)
+            self.h = None
+
+
+def plan_sizes(plan):
+    """spmv_hip_amg_plan_sizes of a plan of either builder -> dict"""
+    s = np.zeros(9, np.int64)
+    call("spmv_hip_amg_plan_sizes", plan, s.ctypes.data)
+    keys = ("fine_rows", "coarse_rows", "num_values", "num_diagonal",
+            "coarse_nnz", "src_count", "has_xrow", "xrow_count", "bytes")
+    return dict(zip(keys, (int(v) for v in s)))
+
+
+def plan_export(plan):
+    """spmv_hip_amg_plan_export of a plan of either builder -> dict of numpy
+    arrays (those the plan has)"""
+    s = plan_sizes(plan)
+    n, nc = s["fine_rows"], s["coarse_rows"]
+    size = dict(agg=n, member_ptr=nc + 1, member=n, src_ptr=s["coarse_nnz"] + 1,
+                src=s["src_count"]) if nc else {}
+    if s["has_xrow"]:
+        size.update(xrow_ptr=n + 1, xrow_src=s["xrow_count"])
+    out = {k: np.zeros(size[k], t) for k, t in _AMG_EXPORT if k in size}
+    ex = AmgExport(*[out[k].ctypes.data if k in out else None
+                     for k, _ in _AMG_EXPORT])
+    call("spmv_hip_amg_plan_export", plan, C.byref(ex))
+    return out

@@ -187,6 +187,11 @@ _PROTOS = {
     "spmvh_amg_symbolic_get": [vp] * 11,
     "spmvh_amg_symbolic_destroy": [vp],
     "spmvh_amg_create": [vp, vp, vp, PTR(vp)],
+    "spmvh_amg_create_ex": [vp, vp, vp, C.c_int, C.c_int, PTR(vp)],
+    "spmvh_amg_setup_info": [vp, vp],
+    "spmvh_amg_level_rounds": [vp, C.c_int, vp],
+    "spmvh_amg_step_sizes": [vp, C.c_int, vp],
+    "spmvh_amg_step_export": [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp],
     "spmvh_amg_destroy": [vp],
     "spmvh_amg_refresh": [vp, vp],
     "spmvh_amg_info": [vp, vp],
@@ -1479,16 +1484,33 @@ class AmgPreconditioner:
     positive"; "row-sum bound is not finite": a level's max_i |row i| / d_i is
     Inf or 0, from a diagonal entry too small to invert or entries whose sum
     overflows; "released", "same index range", an option's name).  After a
-    refresh that raised, the object raises until a refresh succeeds."""
+    refresh that raised, the object raises until a refresh succeeds.
 
-    def __init__(self, exec_, A, **options):
+    setup="host" (the default) reads every level back and aggregates on the
+    host; setup="device" aggregates and builds every list of the hierarchy
+    where the matrices lie.  order (device setup only): "hashed" (the default
+    there: few rounds, other aggregates than the host's) or "natural" (the
+    host's hierarchy bit for bit; as many rounds as the longest dependency
+    chain).  setup="host" with an order raises."""
+
+    _SETUPS = {"host": 0, "device": 1}
+    _ORDERS = {None: -1, "hashed": 0, "natural": 1}
+
+    def __init__(self, exec_, A, setup="host", order=None, **options):
         o = _amg_options(options)
         amg_check_options(**o)
         packed = np.array([o[k] for k in AMG_DEFAULTS], np.float64)
         h = vp()
-        call("spmvh_amg_create", exec_.h, A.h, _np_ptr(packed), C.byref(h))
+        if setup == "host" and order is None:
+            call("spmvh_amg_create", exec_.h, A.h, _np_ptr(packed), C.byref(h))
+        else:
+            if setup not in self._SETUPS or order not in self._ORDERS:
+                raise ValueError(f"setup {setup!r} / order {order!r}")
+            call("spmvh_amg_create_ex", exec_.h, A.h, _np_ptr(packed),
+                 self._SETUPS[setup], self._ORDERS[order], C.byref(h))
         self.h = h
         self.options = o
+        self.setup = setup
 
     def close(self):
         if self.h:
@@ -1546,6 +1568,46 @@ class AmgPreconditioner:
         the last refresh: numeric alone)"""
         info = self._info()
         return info[2] / 1000.0, info[3] / 1000.0
+
+    def setup_detail(self):
+        """the device setup's record -> dict(aggregate_ms, build_ms (both part
+        of the symbolic time), temp_bytes: the peak of its temporaries); zeros
+        for the host setup"""
+        info = np.zeros(4, np.int64)
+        call("spmvh_amg_setup_info", self.h, _np_ptr(info))
+        return dict(aggregate_ms=int(info[0]) / 1000.0,
+                    build_ms=int(info[1]) / 1000.0, temp_bytes=int(info[2]))
+
+    def rounds(self, level):
+        """-> (pass 1, pass 3): the rounds the device setup took to aggregate
+        `level`; (0, 0) for setup="host" and for a level without a step"""
+        r = (C.c_int * 2)()
+        call("spmvh_amg_level_rounds", self.h, int(level), r)
+        return int(r[0]), int(r[1])
+
+    _STEP_KEYS = (("agg", np.int32), ("member_ptr", np.int32),
+                  ("member", np.int32), ("src_ptr", np.int64), ("src", np.int32),
+                  ("xrow_ptr", np.int64), ("xrow_src", np.int32))
+
+    def step_arrays(self, level):
+        """host copies of the device plan of `level` (spmv_hip_amg_plan_export)
+        -> dict of the arrays that exist, plus coarse_rows, coarse_nnz and
+        bytes; {} where the level has no plan"""
+        s = np.zeros(9, np.int64)
+        call("spmvh_amg_step_sizes", self.h, int(level), _np_ptr(s))
+        n, nc, nnz_c, nsrc, has_x, nx = (int(s[0]), int(s[1]), int(s[4]),
+                                         int(s[5]), int(s[6]), int(s[7]))
+        if not (nc or has_x):
+            return {}
+        size = dict(agg=n, member_ptr=nc + 1, member=n, src_ptr=nnz_c + 1,
+                    src=nsrc) if nc else {}
+        if has_x:
+            size.update(xrow_ptr=n + 1, xrow_src=nx)
+        out = {k: np.zeros(size[k], t) for k, t in self._STEP_KEYS if k in size}
+        call("spmvh_amg_step_export", self.h, int(level),
+             *[_np_ptr(out.get(k)) for k, _ in self._STEP_KEYS])
+        out.update(coarse_rows=nc, coarse_nnz=nnz_c, bytes=int(s[8]))
+        return out
 
     def rows(self, level=0):
         return self._level(level)[0]
