@@ -383,6 +383,20 @@ int spmv_hip_zwalk_table(int32_t num_rows, int64_t plane_rows, int grid,
  *                  descriptors (get "lx_rowdesc" = 1 when the plan has them;
  *                  2 B per row, built with the DMA records): a row block
  *                  with a row of more than 31 entries is not eligible.
+ *   "lx_vcode"                           ... streaming 4-bit VALUE codes and a
+ *                  16-entry fp64 dictionary per row block in place of the
+ *                  values (fp64 plans; built by plan_bake_values_f64 on a
+ *                  ring-eligible plan when EVERY row block's stored values
+ *                  have at most 16 distinct bit patterns; they need not be
+ *                  exact in fp32 and take precedence over "lx_v32").  get = 1
+ *                  when the plan has them and they are switched on; set 0
+ *                  gives the launch without them, set 1 switches them back
+ *                  on.  get "lx_vcode_blocks": row blocks that qualified at
+ *                  the last bake, "lx_vcode_all": 1 when all did (the arrays
+ *                  exist only then: 0.5 B per entry + 128 B per row block).
+ *                  Context option "lx_vcode" (default 1) is read at plan
+ *                  creation (the switch) and at every bake (the arrays).
+ *                  Same grid, same bits.
  *   "lx_ring_pwr"                        x pieces a wave of the ring kernel
  *                  issues per step: 0 = 3 where the plan stages at most 12
  *                  pieces, else 4 (get: the figure in use); 4 = always 4

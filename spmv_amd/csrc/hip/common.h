@@ -43,6 +43,13 @@ struct spmv_hip_ctx {
   // "lx_ring").  0 = never, 1 = when a workgroup walks at least 128 row blocks
   // (below that the prologue costs more than the steps gain), 2 = always
   int lx_ring = 1;
+  // ... and plan_bake_values_f64 gives a ring-eligible plan 4-bit VALUE codes:
+  // a 16-entry fp64 dictionary per row block and one nibble per entry, where
+  // every row block's stored values have at most 16 distinct bit patterns
+  // ("lx_vcode"; read at plan creation, plan key "lx_vcode"; 0.5 B per entry
+  // and 128 B per row block of plan memory, streamed by the ring kernel in
+  // place of the 4-byte values)
+  int lx_vcode = 1;
   // the host mirror's CSRMatrix frees its device copies of colind / values
   // once a plan holds the matrix in its own format ("release_csr";
   // spmv_hip_csr_plan_owns_matrix); read by the mirror, nothing here acts on it

@@ -218,6 +218,12 @@ __host__ __device__ constexpr int64_t lx_rowdesc_bytes(int64_t num_row_blocks)
 {
   return num_row_blocks * (kRows * 2) + kLxwDescPad;
 }
+// ... and its 4-bit value codes (plan arrays lx_vcode, lx_vdict): entry j's
+// code is nibble j & 1 of byte j / 2 of lx_vcode, exactly as in lx_code (so
+// the two streams of a block share their DMA addresses), and row block rb's
+// dictionary is lx_vdict[rb * kLxVcDictSize, + kLxVcDictSize): 128 B, eight
+// lanes of one DMA instruction.
+constexpr int kLxVcDictSize = 16;
 // XW: the same kernel on the CALLER's column indices (no 16-bit copy): the
 // record carries, after the LXW words, the windows themselves -- an entry's
 // staged position is its column + the delta of the last window that starts at
@@ -548,6 +554,20 @@ struct spmv_hip_csr_plan {
   float* lx_val32 = nullptr;  // lx32_len(nnz) floats
   const void* lx32_values0 = nullptr; // the fp64 array the copy was made from
   int lx_v32 = 0;             // use it (plan_set "lx_v32")
+  // ... or 4-bit VALUE codes (plan_bake_values_f64 on a ring-eligible plan, ctx
+  // option "lx_vcode"; lxvc_encode_kernel): a row block whose stored values
+  // have at most kLxVcDictSize distinct 64-bit patterns gets them, ascending as
+  // unsigned integers, as an fp64 dictionary (unused entries 0) and one nibble
+  // per entry, laid out like lx_code.  The ring kernel streams them in place
+  // of the values when EVERY row block has them; a dictionary entry has the
+  // bits of the value, so products, adds and their order are the fp64
+  // stream's -- whether or not the values are exact in fp32.  They take
+  // precedence over the fp32 copy, which stays.
+  uint8_t* lx_vcode = nullptr; // lx_code_bytes(nnz)
+  double* lx_vdict = nullptr;  // kLxVcDictSize doubles per row block
+  const void* lx_vc_values0 = nullptr; // the fp64 array they were made from
+  int lx_vcode_blocks = 0;     // row blocks with value codes
+  int lx_vc = 1;               // use them (plan_set "lx_vcode")
   // XW: the LDS-DMA kernel on the caller's CSR arrays as they are (values,
   // 32-bit column indices), x windows staged: what a plan without lattice / LX
   // / sliced jagged form runs instead of the gather kernel (spmv_lxw.hip)
@@ -625,6 +645,14 @@ int spmv_build_lx(spmv_hip_csr_plan* pl, const int32_t* rowptr, const int32_t* c
 int spmv_lx32_bake(spmv_hip_csr_plan* pl, const double* values, bool may_alloc,
                    hipStream_t st);
 void spmv_lx32_free(spmv_hip_csr_plan* pl);
+// the 4-bit value codes and per-block dictionaries of a ring-eligible LX
+// plan: made or refreshed in place; dropped when `values` is null, the plan
+// is not ring-eligible, or a row block has more than kLxVcDictSize distinct
+// values.  may_alloc = false: only existing arrays are refreshed.  Out of
+// memory: no codes, no error.
+int spmv_lxvc_bake(spmv_hip_csr_plan* pl, const int32_t* rowptr,
+                   const double* values, bool may_alloc, hipStream_t st);
+void spmv_lxvc_free(spmv_hip_csr_plan* pl);
 // the XW records, + the plane-walk order when the matrix sits on a 3-D grid
 int spmv_build_xw_and_walk(spmv_hip_csr_plan* pl, const int32_t* rowptr,
                            const int32_t* colind);
@@ -720,6 +748,12 @@ int spmv_lxw_run_f32f64(const spmv_hip_csr_plan* pl, hipStream_t st,
                         const int32_t* rowptr, const int32_t* colind,
                         const float* values, double alpha, const double* in,
                         double beta, double* out, DotOut dot);
+// ... on the plan's 4-bit value codes (lx_vcode, lx_vdict): the ring kernel.
+// Does every row block have them, are they switched on, and would the ring
+// run?  Then spmv_lxw_run_vcode may be called.
+bool spmv_lxw_vcode_ok(const spmv_hip_csr_plan* pl);
+int spmv_lxw_run_vcode(const spmv_hip_csr_plan* pl, hipStream_t st, double alpha,
+                       const double* in, double beta, double* out, DotOut dot);
 int spmv_xw_grid(const spmv_hip_csr_plan* pl, int elem_bytes);
 int spmv_xw_run_f64(const spmv_hip_csr_plan* pl, hipStream_t st,
                     const int32_t* rowptr, const int32_t* colind,

@@ -176,6 +176,8 @@ int spmv_hip_ctx_get_option(const spmv_hip_ctx* ctx, const char* key, int64_t* v
     *value = ctx->lx_narrow_values;
   else if (!strcmp(key, "lx_ring"))
     *value = ctx->lx_ring;
+  else if (!strcmp(key, "lx_vcode"))
+    *value = ctx->lx_vcode;
   else if (!strcmp(key, "sj_min_nnz"))
     *value = ctx->sj_min_nnz;
   else
@@ -256,6 +258,11 @@ int spmv_hip_ctx_set_option(spmv_hip_ctx* ctx, const char* key, int64_t value)
     // 2 = wherever eligible
     SPMV_REQUIRE(value >= 0 && value <= 2);
     ctx->lx_ring = (int)value;
+    return SPMV_HIP_OK;
+  }
+  if (!strcmp(key, "lx_vcode")) {
+    SPMV_REQUIRE(value == 0 || value == 1);
+    ctx->lx_vcode = (int)value;
     return SPMV_HIP_OK;
   }
   if (!strcmp(key, "poisson_stencil")) {

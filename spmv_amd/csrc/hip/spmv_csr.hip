@@ -676,6 +676,10 @@ int launch_rowblock(const spmv_hip_csr_plan* pl, hipStream_t st,
   }
   if (pl->lx && pl->lxw && pl->lxw_rec && al && aligned16(in)) {
     if constexpr (sizeof(T) == 8) {
+      // every row block's values as a dictionary and 4-bit codes: the ring
+      if (values == pl->lx_vc_values0 && spmv_lxw_vcode_ok(pl))
+        return spmv_lxw_run_vcode(pl, st, alpha, in, beta, out,
+                                  DOT ? dot : DotOut());
       // the baked values are all exact in fp32: the plan's 4-byte copy
       if (pl->lx_v32 && pl->lx_val32 && values == pl->lx32_values0)
         return spmv_lxw_run_f32f64(pl, st, rowptr, colind, pl->lx_val32, alpha,

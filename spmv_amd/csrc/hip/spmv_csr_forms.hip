@@ -429,6 +429,7 @@ void spmv_free_lx(spmv_hip_csr_plan* pl)
   pl->lxw = pl->lxw_max_cnt = pl->lxw_max_pieces = 0;
   pl->lx4 = pl->lx4_blocks = pl->lx_ring_blocks = 0;
   spmv_lx32_free(pl); // (the narrowed values are the DMA kernel's)
+  spmv_lxvc_free(pl); // (and so are the value codes)
 }
 
 // The 4-bit codes of the DMA kernel (lx4_encode_kernel), after the records and
@@ -624,6 +625,201 @@ int spmv_lx32_bake(spmv_hip_csr_plan* pl, const double* values, bool may_alloc,
   spmv_lx32_free(pl);
   if (e == hipErrorOutOfMemory)
     (void)hipGetLastError();
+  pl->plan_us += (int)std::chrono::duration_cast<std::chrono::microseconds>(
+                     std::chrono::steady_clock::now() - t0)
+                     .count();
+  return e == hipSuccess || e == hipErrorOutOfMemory ? SPMV_HIP_OK
+                                                     : static_cast<int>(e);
+}
+
+// ---------------------------------------------------------------------------
+// The 4-bit value codes of the ring kernel (csr_plan.h: lx_vcode, lx_vdict):
+// a per-block dictionary of the values' bit patterns and one nibble per entry.
+// Bits are compared, never numbers: +0.0 and -0.0 are two entries, NaNs with
+// different payloads are different entries, Inf is an ordinary one.
+// ---------------------------------------------------------------------------
+namespace
+{
+
+// One workgroup per row block (lane = row).  The dictionary is found by up to
+// kLxVcDictSize + 1 rounds of "workgroup minimum of the patterns above the last
+// one taken" (unsigned order: the plan is deterministic); a round that finds
+// nothing ends the search, the 17th finding something refuses the block.  The
+// nibbles are packed and stored as lx4_encode_kernel stores its codes: whole
+// words plainly, the partial ones at both ends of the span OR-ed into the
+// zeroed array.  A refused block leaves its nibbles and its dictionary zero.
+// stat[0] counts the blocks that got codes.
+__global__ __launch_bounds__(kBlock) void lxvc_encode_kernel(
+    int32_t num_rows, const int32_t* __restrict__ rowptr,
+    const double* __restrict__ values, const int32_t* __restrict__ wrec,
+    uint32_t* __restrict__ code, double* __restrict__ dict, int num_row_blocks,
+    int32_t* __restrict__ stat)
+{
+  constexpr int CAP = kBlock * 16; // most entries of a staged block
+  __shared__ unsigned long long s_dict[kLxVcDictSize];
+  __shared__ unsigned long long s_min;
+  __shared__ int s_any;
+  __shared__ uint32_t s_pack[CAP / 8 + 2];
+  const int t = threadIdx.x;
+  const unsigned long long* bits
+      = reinterpret_cast<const unsigned long long*>(values);
+  int coded = 0;
+  for (int rb = blockIdx.x; rb < num_row_blocks; rb += gridDim.x) {
+    const int32_t* wr = wrec + (int64_t)rb * kLxwRec;
+    const int32_t a = wr[1], cnt = wr[2];
+    const int nwin = wr[0];
+    __syncthreads(); // previous block done with the shared arrays
+    if (nwin < 0 || cnt <= 0 || cnt > CAP)
+      continue; // uniform
+    const int32_t a0 = a & ~7; // first entry of the first word
+    const int nwords = (int)(((int64_t)a + cnt + 7 - a0) >> 3);
+    for (int w = t; w < nwords; w += kBlock)
+      s_pack[w] = 0;
+    if (t < kLxVcDictSize)
+      s_dict[t] = 0;
+    const int32_t r = rb * kRows + t;
+    int32_t lo = 0, hi = 0;
+    if (r < num_rows) {
+      lo = rowptr[r];
+      hi = rowptr[r + 1];
+    }
+    int n = 0;          // dictionary entries found
+    bool more = false;  // a pattern above the 16th exists
+    unsigned long long last = 0;
+    for (int k = 0; k <= kLxVcDictSize; ++k) {
+      if (t == 0) {
+        s_min = ~0ull;
+        s_any = 0;
+      }
+      __syncthreads();
+      bool have = false;
+      unsigned long long m = ~0ull;
+      for (int32_t j = lo; j < hi; ++j) {
+        const unsigned long long b = bits[j];
+        if ((k == 0 || b > last) && (!have || b < m)) {
+          m = b;
+          have = true;
+        }
+      }
+      if (have) {
+        atomicMin(&s_min, m);
+        s_any = 1;
+      }
+      __syncthreads();
+      const bool any = s_any != 0;
+      last = s_min;
+      __syncthreads(); // (read before lane 0 resets them)
+      if (!any)
+        break; // uniform
+      if (k == kLxVcDictSize) {
+        more = true;
+        break;
+      }
+      if (t == 0)
+        s_dict[k] = last;
+      n = k + 1;
+    }
+    if (more)
+      continue; // uniform
+    __syncthreads(); // the dictionary is whole
+    for (int32_t j = lo; j < hi; ++j) {
+      const unsigned long long b = bits[j];
+      uint32_t c = 0;
+      for (int k = 1; k < n; ++k)
+        c += s_dict[k] <= b ? 1u : 0u; // rank: the entries ascend
+      const int q = j - a0;
+      atomicOr(&s_pack[q >> 3], c << ((q & 7) * 4));
+    }
+    __syncthreads();
+    for (int w = t; w < nwords; w += kBlock) {
+      const bool whole = (w > 0 || a0 == a) && (int64_t)a0 + 8 * (w + 1) <= (int64_t)a + cnt;
+      uint32_t* dst = code + ((int64_t)a0 >> 3) + w;
+      if (whole)
+        *dst = s_pack[w];
+      else if (s_pack[w])
+        atomicOr(dst, s_pack[w]);
+    }
+    if (t < kLxVcDictSize)
+      reinterpret_cast<unsigned long long*>(dict)[(int64_t)rb * kLxVcDictSize + t]
+          = s_dict[t];
+    if (t == 0)
+      ++coded;
+  }
+  if (t == 0 && coded)
+    atomicAdd(&stat[0], coded);
+}
+
+} // namespace
+
+void spmv_lxvc_free(spmv_hip_csr_plan* pl)
+{
+  plan_drop(pl->lx_vcode);
+  plan_drop(pl->lx_vdict);
+  pl->lx_vc_values0 = nullptr;
+  pl->lx_vcode_blocks = 0;
+}
+
+int spmv_lxvc_bake(spmv_hip_csr_plan* pl, const int32_t* rowptr,
+                   const double* values, bool may_alloc, hipStream_t st)
+{
+  const int nrb = (pl->num_rows + kRows - 1) / kRows;
+  // only where the ring kernel could run: every row block staged, coded and
+  // fitting (the conditions of spmv_lxw_ring_ok that no values decide)
+  if (!values || !rowptr || pl->symmetric || !(pl->lx && pl->lxw && pl->lxw_rec)
+      || !pl->ctx->lx_vcode || pl->nnz == 0 || !aligned16(values) || !pl->lx_code
+      || !pl->lx_rowdesc || nrb < 1 || pl->lx_staged != nrb
+      || pl->lx4_blocks != nrb || pl->lx_ring_blocks != nrb
+      || pl->lxw_max_pieces > kLxwMaxPieces) {
+    spmv_lxvc_free(pl);
+    return SPMV_HIP_OK;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t code_bytes = (size_t)lx_code_bytes(pl->nnz);
+  const size_t dict_bytes = sizeof(double) * kLxVcDictSize * (size_t)nrb;
+  hipError_t e = hipSuccess;
+  if (!(pl->lx_vcode && pl->lx_vdict)) {
+    spmv_lxvc_free(pl);
+    e = may_alloc ? spmv_plan_malloc(&pl->lx_vcode, code_bytes)
+                  : hipErrorOutOfMemory;
+    if (e != hipSuccess)
+      pl->lx_vcode = nullptr;
+    else if ((e = spmv_plan_malloc(&pl->lx_vdict, dict_bytes)) != hipSuccess)
+      pl->lx_vdict = nullptr;
+  }
+  PlanScratch<int32_t> d_stat;
+  int32_t h_stat = 0;
+  if (e == hipSuccess)
+    e = d_stat.alloc(1);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(pl->lx_vcode, 0, code_bytes, st);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(pl->lx_vdict, 0, dict_bytes, st);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(d_stat.get(), 0, sizeof(int32_t), st);
+  if (e == hipSuccess) {
+    int grid = pl->ctx->num_cus * 8;
+    grid = grid > nrb ? nrb : grid;
+    hipLaunchKernelGGL(lxvc_encode_kernel, dim3(grid), dim3(kBlock), 0, st,
+                       pl->num_rows, rowptr, values, pl->lxw_rec,
+                       reinterpret_cast<uint32_t*>(pl->lx_vcode), pl->lx_vdict,
+                       nrb, d_stat.get());
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = plan_fetch(&h_stat, d_stat.get(), 1, st);
+  d_stat.reset();
+  if (e == hipSuccess && h_stat == nrb) {
+    pl->lx_vc_values0 = values;
+    pl->lx_vcode_blocks = h_stat;
+  } else {
+    // a block with more than 16 values, no memory, or an error: no codes (the
+    // count of a plan that keeps none is still reported)
+    spmv_lxvc_free(pl);
+    if (e == hipSuccess)
+      pl->lx_vcode_blocks = h_stat;
+    else
+      (void)hipGetLastError();
+  }
   pl->plan_us += (int)std::chrono::duration_cast<std::chrono::microseconds>(
                      std::chrono::steady_clock::now() - t0)
                      .count();

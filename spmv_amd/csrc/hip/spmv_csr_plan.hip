@@ -143,6 +143,7 @@ int spmv_hip_csr_plan_create(spmv_hip_ctx* ctx, int32_t num_rows,
     return SPMV_HIP_ENOMEM;
   pl->ctx = ctx;
   pl->lx_ring = ctx->lx_ring;
+  pl->lx_vc = ctx->lx_vcode;
   MemClock mem_clock(pl); // (a failed creation destroys pl before this is read:
                           // every such path below hands the clock a null plan)
   pl->num_rows = num_rows;
@@ -368,6 +369,13 @@ int spmv_hip_csr_plan_bake_values_f64(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan
                                 !plan->no_new_forms, st);
   if (rn != SPMV_HIP_OK)
     return rn;
+  // ... and the ring kernel's 4-bit value codes, where every row block's
+  // values have at most 16 distinct bit patterns (plan_get "lx_vcode_all")
+  const int rv = spmv_lxvc_bake(plan, plan->rowptr0,
+                                rc == SPMV_HIP_ENOTSUP ? values : nullptr,
+                                !plan->no_new_forms, st);
+  if (rv != SPMV_HIP_OK)
+    return rv;
   return rc;
 }
 
@@ -431,6 +439,7 @@ int spmv_hip_csr_plan_bake_values_f32(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan
     rc = values == nullptr ? (rj != SPMV_HIP_OK ? rj : rc) : rj;
   }
   spmv_lx32_free(plan); // (a narrowed copy of fp64 values baked before)
+  spmv_lxvc_free(plan); // (and their value codes)
   return rc;
 }
 
@@ -519,6 +528,11 @@ int spmv_hip_csr_plan_values_changed(spmv_hip_ctx* ctx, spmv_hip_csr_plan* plan,
   if (rc == SPMV_HIP_OK && plan->lx_val32 && plan->lx32_values0)
     rc = spmv_lx32_bake(plan, static_cast<const double*>(plan->lx32_values0), false,
                         st);
+  // ... and its value codes: encoded again in place -- or dropped when a row
+  // block now has more than 16 distinct values
+  if (rc == SPMV_HIP_OK && plan->lx_vcode && plan->lx_vc_values0)
+    rc = spmv_lxvc_bake(plan, plan->rowptr0,
+                        static_cast<const double*>(plan->lx_vc_values0), false, st);
   // the diagonal forms: the device checks decide the form again (a matrix
   // they no longer hold: ENOTSUP = back to the CSR-order kernels, which is a
   // correct outcome of this call)
@@ -634,6 +648,11 @@ int spmv_hip_csr_plan_set(spmv_hip_csr_plan* plan, const char* key, int value)
     SPMV_REQUIRE(value == 0 || value == 1);
     SPMV_REQUIRE(value == 0 || plan->lx_val32);
     plan->lx_v32 = value;
+  } else if (!strcmp(key, "lx_vcode")) {
+    // ... the ring variant streaming the plan's 4-bit value codes where every
+    // row block has them (0: the launch is what it is without them)
+    SPMV_REQUIRE(value == 0 || value == 1);
+    plan->lx_vc = value;
   } else if (!strcmp(key, "lx_ring")) {
     // ... in the ring variant of the DMA kernel (three LDS slots): 1 needs a
     // plan that is eligible as it stands (spmv_lxw_ring_ok); same geometry
@@ -962,6 +981,10 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
       b += lx_rowdesc_bytes(nrb);
     if (plan->lx_val32)
       b += 4 * lx32_len(nnz);
+    if (plan->lx_vcode)
+      b += lx_code_bytes(nnz);
+    if (plan->lx_vdict)
+      b += 8 * kLxVcDictSize * nrb;
     if (plan->xw_rec)
       b += 4 * nrb * kXwRec;
     if (plan->lat_tab)
@@ -1073,6 +1096,15 @@ int spmv_hip_csr_plan_get(const spmv_hip_csr_plan* plan, const char* key,
     *value = plan->lx4_lut;
   else if (!strcmp(key, "lx_v32"))
     *value = plan->lx_v32 && plan->lx_val32 ? 1 : 0;
+  else if (!strcmp(key, "lx_vcode")) // value codes present and switched on
+    *value = plan->lx_vc && plan->lx_vcode && plan->lx_vdict ? 1 : 0;
+  else if (!strcmp(key, "lx_vcode_blocks"))
+    *value = plan->lx_vcode_blocks;
+  else if (!strcmp(key, "lx_vcode_all"))
+    *value = plan->lx_vcode && plan->lx_vdict
+                     && plan->lx_vcode_blocks == (plan->num_rows + kRows - 1) / kRows
+                 ? 1
+                 : 0;
   else if (!strcmp(key, "lx_ring"))
     *value = spmv_lxw_ring_ok(plan, false) ? 1 : 0;
   else if (!strcmp(key, "lx_ring_blocks"))

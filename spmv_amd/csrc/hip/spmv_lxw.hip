@@ -185,6 +185,59 @@
 // Not tried: a fourth slot; two x pieces per wave for plans that stage at
 // most eight.
 //
+// 4-bit value codes (template parameter VC of the ring kernel; plan key /
+// context option "lx_vcode", plan arrays lx_vcode and lx_vdict): with codes
+// and descriptors the fp32 values were half of what a step streams, and for
+// the 7-point matrix they carry two numbers.  The plan (lxvc_encode_kernel,
+// spmv_csr_forms.hip; every values bake) gives a row block whose stored
+// values have at most 16 distinct BIT PATTERNS a 16-entry fp64 dictionary
+// (128 B, ascending as unsigned integers, unused entries 0) and one nibble
+// per entry in an array laid out exactly like the column codes; the
+// instantiation runs when EVERY block has them (plan_get "lx_vcode_all") and
+// the ring's other conditions hold -- the fp32 copy is not among them any
+// more: a dictionary entry has the value's own bits, so values that are not
+// exact in fp32 qualify too.  It takes precedence over the fp32 copy, which
+// stays.
+//   What a step issues now, per wave: the store and the two or three loads as
+// before, then N = VR + 1 + PWR DMA instructions with VR = 1: ONE value piece
+// -- the block's value codes in waves 0 and 1 (the address of the wave's
+// column-code piece in the other array; a fitting block's codes fill at most
+// two pieces), the block's DICTIONARY by lanes 0..7 in wave 2, a surplus piece
+// by lane 0 in wave 3 --, the code piece or the descriptors, PWR x pieces;
+// `s_waitcnt vmcnt(N)` as before, N = 5 for the 7-point matrix.  Per slot LDS
+// holds a codes slot's bytes of value codes (1 KiB for the 7-point matrix)
+// and 128 B of dictionary where 8 KiB of values were; the launch still asks
+// for the fp32 ring's LDS, so that the workgroups per CU, the grid, the
+// row-block order and the lane-to-row map stay what they are and y and the
+// fused dot's partials keep their bits.  In the row sum v[k] is one
+// ds_read_b64 of the slot's dictionary at the nibble taken from the value
+// codes exactly as the column nibble is taken from the column codes (two
+// dwords and a funnel shift per eight entries; sixteen doubles span 32
+// banks); no fp32 -> fp64 conversion remains; multiplications, additions and
+// their order are untouched.
+//   Disassembly of <DOT = 1, NT = 0, TAB = 1, VR = 1, PWR = 3, VC = 1> (hipcc
+// -O3 for gfx950): every step passes ONE vector-memory wait, `s_waitcnt
+// vmcnt(5)` (the vmcnt(0) inside the branch of a block whose own x is not
+// staged as before), then `s_waitcnt lgkmcnt(0)`, `s_barrier`; between two of
+// them 1 global_store_dwordx2, 1 global_load_dwordx2, 2 global_load_dword, 5
+// global_load_lds_dwordx4 (15 in the kernel: two blocks in the prologue).  70
+// VGPRs, no spills, no scratch, 128 B of static LDS.
+//   Measured at 512^3, one MI355X, one session against the parent (the fp32
+// ring, PWR = 3; profiles/lxvcode_ab.json): the headline, five alternating
+// runs each, parent 331.95-338.89, new 344.95-355.53 it/s, ranges apart
+// (+3.9 % between the nearest ends, +4.5 % between the medians); the new
+// sources with "lx_vcode" defaulting to 0 331.65 (the parent library's sixth
+// run of the session gave 331.63); x_sample and residual_history
+// array_equal.  What a launch streams: 0.47 GB of value codes + 0.07 GB of
+// dictionaries where 3.75 GB of fp32 values were -- 1.07 B per entry of matrix
+// stream instead of 4.5.  Kernel trace of the benchmark: 1.589 -> 1.460 ms
+// per launch (-8.1 %; the byte saving does not convert one for one, the
+// step stays bound by latency).  The plan pass: 7.5 ms beside
+// lx4_encode_kernel's 4.7 ms; plan memory +0.47 GB of codes, +67 MB of
+// dictionaries.  Not measured here: the fabric bytes (FETCH_SIZE), the
+// one-process alternation at 216^3 / 384^3 (the 128-steps gate stands as it
+// was).
+//
 // XW variant (round 5): the same kernel on the CALLER's CSR arrays as they are.
 // The 16-bit offsets are a plan-owned copy of the index stream (2 B per entry
 // of plan memory, 10 B per entry streamed); the plain row-block kernel streams
@@ -711,21 +764,39 @@ constexpr int kRingDescWave = 2;
 constexpr int kRingDumpBytes = 64;
 static_assert(lx_ring_code_bytes(kLxwRingVcap - 3) <= kRingDescWave * 1024,
               "a fitting block's codes reach the descriptor wave's piece");
-template <bool DOT, bool NT, bool TAB, int VR, int PWR>
+//   VC    the values arrive as 4-bit codes and a per-block fp64 dictionary
+//         (`vcode`, `vdict`; csr_plan.h) instead of fp32 numbers, VR = 1: a
+//         value-codes slot is a codes slot's size (`ccap`: the two streams of
+//         a block have the same layout and share their DMA addresses), the
+//         block's 128-B dictionary rides in wave kRingDescWave's value piece
+//         by eight lanes (a fitting block's value codes fill at most two
+//         pieces, like its column codes), and wave 3's value piece is surplus
+//         in every block.  `values` is not read.
+template <bool DOT, bool NT, bool TAB, int VR, int PWR, bool VC>
 __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
     int32_t num_rows, int32_t num_cols, int64_t nnz,
-    const float* __restrict__ values, const uint8_t* __restrict__ code,
+    const float* __restrict__ values, const uint8_t* __restrict__ vcode,
+    const double* __restrict__ vdict, const uint8_t* __restrict__ code,
     const uint16_t* __restrict__ desc, const int32_t* __restrict__ rec,
     double alpha, const double* __restrict__ in, double beta,
     double* __restrict__ out, DotOut dot, RowBlockOrder ord, int ccap, int xcap)
 {
   using T = double;
+  static_assert(!VC || VR == 1, "value codes: one value piece per wave");
   constexpr int NW = kBlock / 64;
-  constexpr int VCAP = VR * NW * 256; // floats per values slot
+  constexpr int VCAP = VR * NW * 256; // floats per values slot (!VC)
   constexpr int DMA = VR + 1 + PWR;   // DMA instructions per wave and block
+  constexpr int DB = kLxVcDictSize * (int)sizeof(double); // dictionary bytes
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  // the values' slots: fp32 numbers, or (VC) three slots of value codes and
+  // behind them the three dictionaries
+  const unsigned val_bytes
+      = VC ? 3u * ((unsigned)ccap + DB) : 3u * VCAP * (unsigned)sizeof(float);
   float* const s_val = reinterpret_cast<float*>(smem);
-  unsigned char* const s_code = smem + 3 * (size_t)VCAP * sizeof(float);
+  const unsigned char* const s_vcode = smem;
+  const double* const s_vdict
+      = reinterpret_cast<const double*>(smem + 3 * (size_t)ccap);
+  unsigned char* const s_code = smem + val_bytes;
   T* const s_x = reinterpret_cast<T*>(s_code + 3 * (size_t)ccap);
   // row descriptors: 512 B per slot (half a DMA piece: lanes 0..31)
   const uint16_t* const s_desc = reinterpret_cast<const uint16_t*>(
@@ -734,7 +805,8 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
   __shared__ int32_t s_dict[3 * kLxwDictSize / 2];
   const unsigned lds_val = (unsigned)(uintptr_t)(
       (__attribute__((address_space(3))) void*)s_val);
-  const unsigned lds_code = lds_val + 3u * VCAP * (unsigned)sizeof(float);
+  const unsigned lds_vdict = lds_val + 3u * (unsigned)ccap; // (VC)
+  const unsigned lds_code = lds_val + val_bytes;
   const unsigned lds_x = lds_code + 3u * (unsigned)ccap;
   const unsigned lds_desc = lds_x + 3u * (unsigned)xcap * (unsigned)sizeof(T);
   const unsigned lds_dump = lds_desc + 3u * (unsigned)(kRows * 2);
@@ -757,7 +829,7 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
   auto issue = [&](const LxwBlock& b, int32_t w, int sl) {
     const bool live = b.rb >= 0;
     const int64_t a = b.a, e = (int64_t)b.a + b.cnt;
-    {
+    if constexpr (!VC) {
       const int64_t base = a & ~(int64_t)3;
       const int64_t jclamp = (e - 1) & ~(int64_t)3;
       const int pieces = live ? (int)(((e - base) * 4 + 1023) >> 10) : 0;
@@ -783,11 +855,25 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
       int64_t j = base + (int64_t)(wave * 64 + lane) * 16;
       j = j < jclamp ? j : jclamp;
       j = real ? j : cdump;
+      const bool dsc = wave == kRingDescWave; // uniform
+      if constexpr (VC) {
+        // the value codes: the column codes' piece of the other array; wave
+        // kRingDescWave: the block's dictionary instead (no block: that of
+        // row block 0), by its lanes 0..7
+        const uint8_t* const vsrc
+            = dsc ? reinterpret_cast<const uint8_t*>(
+                        vdict + (int64_t)(live ? b.rb : 0) * kLxVcDictSize)
+                        + (lane & 7) * 16
+                  : vcode + j;
+        if (lane < (dsc ? DB / 16 : real ? 64 : 1))
+          glds16<NT>(vsrc, dsc ? lds_vdict + (unsigned)(sl * DB)
+                               : real ? lds_val + (unsigned)(sl * ccap + wave * 1024)
+                                      : lds_dump);
+      }
       // wave kRingDescWave: the block's 512 B of row descriptors instead (no
       // block: those of row block 0), by its lanes 0..31 -- the others sit the
       // instruction out, so it writes half a piece; never all lanes of a
       // wave, so the instruction is always issued and always counted
-      const bool dsc = wave == kRingDescWave; // uniform
       const uint8_t* const src
           = dsc ? reinterpret_cast<const uint8_t*>(desc)
                       + (int64_t)(live ? b.rb : 0) * (kRows * 2) + (lane & 31) * 16
@@ -900,6 +986,11 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
       const int32_t hi = j + (dsc >> kLxwDescStartBits);
       // index by the entry's position in `values`
       const float* sv = s_val + (size_t)s0 * VCAP + (cur.a & 3) - cur.a;
+      // (VC) the slot's value codes, laid out like its column codes, and its
+      // dictionary
+      const uint32_t* svc
+          = reinterpret_cast<const uint32_t*>(s_vcode + (size_t)s0 * ccap);
+      const T* sd = s_vdict + s0 * kLxVcDictSize;
       const T* sx = s_x + (size_t)s0 * xcap;
       if constexpr (DOT) {
         if (cur.own >= 0) // uniform
@@ -915,10 +1006,21 @@ __global__ __launch_bounds__(kBlock) void csr_lxw_ring_kernel(
         const uint32_t bits = __builtin_amdgcn_alignbit(c_hi, c_lo, (n & 7) * 4);
         unsigned l[8];
         T v[8], xv[8];
+        if constexpr (VC) {
+          // a value is its nibble's dictionary entry (a nibble past the row's
+          // end is another row's: any of the 16 entries, not added)
+          const uint32_t v_lo = svc[n >> 3], v_hi = svc[(n >> 3) + 1];
+          const uint32_t vbits
+              = __builtin_amdgcn_alignbit(v_hi, v_lo, (n & 7) * 4);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int32_t jj = j + k < hi ? j + k : hi - 1;
-          v[k] = (T)sv[jj];
+          for (int k = 0; k < 8; ++k)
+            v[k] = sd[(vbits >> (4 * k)) & 15u];
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const int32_t jj = j + k < hi ? j + k : hi - 1;
+            v[k] = (T)sv[jj];
+          }
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -1046,15 +1148,25 @@ LxwRingGeom lxw_ring_geom(const spmv_hip_csr_plan* pl)
   return g;
 }
 
-// Per plan, never per block: narrowed values, codes with the LDS table, every
+// Per plan, never per block: value codes for every row block or narrowed
+// values (the launch prefers the codes), codes with the LDS table, every
 // row block staged, coded and fitting, and three slots in the LDS that keeps
 // the workgroups per CU where lxw_geom puts them.
+// every row block has value codes and they are switched on
+bool lxw_vcode_on(const spmv_hip_csr_plan* pl)
+{
+  const int nrb = (pl->num_rows + kRows - 1) / kRows;
+  return pl->lx_vc && pl->lx_vcode && pl->lx_vdict && pl->lx_vc_values0
+         && pl->lx_vcode_blocks == nrb;
+}
+
 bool lxw_ring_ok(const spmv_hip_csr_plan* pl, bool forced)
 {
   const int nrb = (pl->num_rows + kRows - 1) / kRows;
+  // (the values: as codes and dictionaries, or narrowed)
   if (!(forced || pl->lx_ring) || pl->symmetric || !pl->lx || !pl->lxw
       || !pl->lxw_rec || !pl->lx4 || !pl->lx_code || pl->lx4_lut != 1
-      || !pl->lx_v32 || !pl->lx_val32 || !pl->lx_rowdesc)
+      || !((pl->lx_v32 && pl->lx_val32) || lxw_vcode_on(pl)) || !pl->lx_rowdesc)
     return false;
   if (nrb < 1 || pl->lx_staged != nrb || pl->lx4_blocks != nrb
       || pl->lx_ring_blocks != nrb || !lx_ring_fits(pl->lxw_max_cnt)
@@ -1078,12 +1190,16 @@ bool lxw_ring_ok(const spmv_hip_csr_plan* pl, bool forced)
   return forced || pl->lx_ring >= 2 || (nrb + grid - 1) / grid >= kMinSteps;
 }
 
-template <bool DOT, int PWR>
+// VC: the value-coded instantiation (`values` unused).  It asks for the LDS of
+// the fp32 one although its slots are smaller (1 KiB of value codes and a
+// 128-B dictionary where 8 KiB of values were): the workgroups per CU, and
+// with them how the grid spreads over the CUs, stay what they are.
+template <bool DOT, int PWR, bool VC>
 int lxw_ring_launch_p(const spmv_hip_csr_plan* pl, hipStream_t st,
                       const float* values, double alpha, const double* in,
                       double beta, double* out, DotOut dot)
 {
-  constexpr int VR = kLxwRingValRounds;
+  constexpr int VR = VC ? 1 : kLxwRingValRounds;
   const LxwRingGeom g = lxw_ring_geom(pl);
   const int nrb = (pl->num_rows + kRows - 1) / kRows;
   // grid and row-block order: those of csr_lxw_kernel, so that y and the fused
@@ -1097,17 +1213,18 @@ int lxw_ring_launch_p(const spmv_hip_csr_plan* pl, hipStream_t st,
   }
   auto kern
       = ord.table
-            ? (pl->nontemporal ? csr_lxw_ring_kernel<DOT, true, true, VR, PWR>
-                               : csr_lxw_ring_kernel<DOT, false, true, VR, PWR>)
-            : (pl->nontemporal ? csr_lxw_ring_kernel<DOT, true, false, VR, PWR>
-                               : csr_lxw_ring_kernel<DOT, false, false, VR, PWR>);
+            ? (pl->nontemporal ? csr_lxw_ring_kernel<DOT, true, true, VR, PWR, VC>
+                               : csr_lxw_ring_kernel<DOT, false, true, VR, PWR, VC>)
+            : (pl->nontemporal ? csr_lxw_ring_kernel<DOT, true, false, VR, PWR, VC>
+                               : csr_lxw_ring_kernel<DOT, false, false, VR, PWR, VC>);
   if (g.lds > 48 * 1024) // beyond the default dynamic-LDS limit
     SPMV_CHECK_HIP(hipFuncSetAttribute(
         reinterpret_cast<const void*>(kern),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), g.lds, st, pl->num_rows,
-                     pl->num_cols, pl->nnz, values, pl->lx_code, pl->lx_rowdesc,
-                     pl->lxw_rec, alpha, in, beta, out, dot, ord, g.ccap, g.xcap);
+                     pl->num_cols, pl->nnz, values, pl->lx_vcode, pl->lx_vdict,
+                     pl->lx_code, pl->lx_rowdesc, pl->lxw_rec, alpha, in, beta, out,
+                     dot, ord, g.ccap, g.xcap);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -1115,17 +1232,18 @@ int lxw_ring_launch_p(const spmv_hip_csr_plan* pl, hipStream_t st,
 // x pieces per wave: kLxwMaxPieces / 4 covers every plan; one fewer where the
 // plan stages at most twelve pieces (the 7-point matrix: 11), unless the plan
 // key "lx_ring_pwr" asks for all four -- one DMA instruction less per wave
-// and step, `s_waitcnt vmcnt(6)`
-template <bool DOT>
+// and step, `s_waitcnt vmcnt(6)` (value codes: vmcnt(5))
+template <bool DOT, bool VC>
 int lxw_ring_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
                     const float* values, double alpha, const double* in,
                     double beta, double* out, DotOut dot)
 {
   constexpr int NW = kBlock / 64, PWR = kLxwMaxPieces / NW;
   if (pl->lx_ring_pwr != PWR && pl->lxw_max_pieces <= (PWR - 1) * NW)
-    return lxw_ring_launch_p<DOT, PWR - 1>(pl, st, values, alpha, in, beta, out,
-                                           dot);
-  return lxw_ring_launch_p<DOT, PWR>(pl, st, values, alpha, in, beta, out, dot);
+    return lxw_ring_launch_p<DOT, PWR - 1, VC>(pl, st, values, alpha, in, beta,
+                                               out, dot);
+  return lxw_ring_launch_p<DOT, PWR, VC>(pl, st, values, alpha, in, beta, out,
+                                         dot);
 }
 
 template <typename TV, typename T, bool DOT, bool XW, int C4>
@@ -1177,7 +1295,8 @@ int lxw_launch(const spmv_hip_csr_plan* pl, hipStream_t st,
   if constexpr (!XW && std::is_same<TV, float>::value
                 && std::is_same<T, double>::value) {
     if (lxw_ring_ok(pl, false))
-      return lxw_ring_launch<DOT>(pl, st, values, alpha, in, beta, out, dot);
+      return lxw_ring_launch<DOT, false>(pl, st, values, alpha, in, beta, out,
+                                         dot);
   }
   if constexpr (!XW) {
     if (pl->lx4 && pl->lx_code)
@@ -1201,6 +1320,19 @@ int spmv_lxw_grid(const spmv_hip_csr_plan* pl, int elem_bytes)
 bool spmv_lxw_ring_ok(const spmv_hip_csr_plan* pl, bool forced)
 {
   return lxw_ring_ok(pl, forced);
+}
+
+bool spmv_lxw_vcode_ok(const spmv_hip_csr_plan* pl)
+{
+  return lxw_vcode_on(pl) && lxw_ring_ok(pl, false);
+}
+
+int spmv_lxw_run_vcode(const spmv_hip_csr_plan* pl, hipStream_t st, double alpha,
+                       const double* in, double beta, double* out, DotOut dot)
+{
+  if (dot.partials)
+    return lxw_ring_launch<true, true>(pl, st, nullptr, alpha, in, beta, out, dot);
+  return lxw_ring_launch<false, true>(pl, st, nullptr, alpha, in, beta, out, dot);
 }
 
 int spmv_xw_grid(const spmv_hip_csr_plan* pl, int elem_bytes)
