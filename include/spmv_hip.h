@@ -1327,6 +1327,70 @@ int spmv_hip_ilu0_plan_export(const spmv_hip_ilu0_plan* plan,
                               const spmv_hip_ilu0_export* before,
                               const spmv_hip_ilu0_export* after);
 
+/* ---- fp32 values in the sweep plans (additive, ABI 5) ---------------------------
+ * A sweep plan may keep the off-diagonal values of both parts -- the sliced val
+ * and the long rows' long_val -- as float: 8 bytes per stored entry (value and
+ * column) cross the fabric in a sweep, not 12.  The stored value is the fp64
+ * value rounded to nearest-even; dinv, r, z, the sums and every operation stay
+ * fp64, and the kernels compute acc = acc + (double)v32 * z[col] in the
+ * entries' order: mcgs_apply / mcgs_apply_block on such a plan have the bits of
+ * the fp64 sweeps on a plan with the widened values.  Both applications take a
+ * plan of either form; their argument rules do not change.
+ *
+ * Range.  A finite non-zero value whose rounding is +-Inf, zero or an fp32
+ * subnormal is OUT OF RANGE, so that a plan never depends on a denormal mode:
+ * |v| >= 2^128 - 2^103 or 0 < |v| < 2^-126 - 2^-150.  +-0, +-Inf and NaN
+ * convert as IEEE says and are in range.  The values are counted on the device
+ * as they are rounded.
+ *
+ * value_bits: 64 (the entry point without _ex, in every respect) or 32;
+ * anything else is SPMV_HIP_EINVAL.
+ *   mcgs_plan_create_ex / mcgs_plan_build_ex: the plan of mcgs_plan_create /
+ *     mcgs_plan_build; with 32 each fp64 value array is then rounded into a
+ *     float array by a kernel and freed, one array after the other (peak: the
+ *     fp64 plan plus 4 bytes per entry of its largest value array), and the
+ *     call waits for the count: *out_of_range != 0 is SPMV_HIP_ERANGE and no
+ *     plan (build_ex returns SPMV_HIP_ERANGE with *out_of_range == 0 for the
+ *     size limit of mcgs_plan_build).
+ *   ilu0_plan_create_ex / ilu0_plan_build_ex: the inner plan keeps floats;
+ *     ilu0_factor factors in fp64 as ever (the working copy, ilu0_get_factor
+ *     and the pivot counts do not change) and rounds l~ and u~ as it scatters
+ *     them into the inner plan, dinv~ stays fp64; every ilu0_factor rounds
+ *     again.  ilu0_counts is ilu0_pivots with a third count from the same
+ *     wait: the values of the last factorisation out of fp32's range (0 for an
+ *     fp64 plan) -- a plan with such a count must not be applied.
+ *   mcgs_plan_value_bits: 64 or 32.
+ *   mcgs_plan_bytes of an fp32 plan = that of the fp64 plan of the same input
+ *     - 4 * (sizes[3] + sizes[5] + sizes[6] + sizes[8]) of mcgs_plan_sizes: the
+ *     sliced entries (padding included) and the long entries of both parts.
+ *   mcgs_plan_export of an fp32 plan returns val / long_val WIDENED to double,
+ *     entry for entry what the kernels multiply with. */
+int spmv_hip_mcgs_plan_create_ex(spmv_hip_ctx* ctx, const spmv_hip_mcgs_host* in,
+                                 int value_bits, spmv_hip_mcgs_plan** plan,
+                                 int64_t* out_of_range);
+int spmv_hip_mcgs_plan_build_ex(spmv_hip_ctx* ctx, int32_t num_rows,
+                                int32_t num_cols, int64_t nnz,
+                                const int32_t* rowptr, const int32_t* colind,
+                                const double* values, const double* diagonal,
+                                int symmetric, const int32_t* colors,
+                                int32_t num_colors, int long_threshold,
+                                int value_bits, spmv_hip_mcgs_plan** plan,
+                                int64_t* info, int64_t* out_of_range,
+                                void* stream);
+int spmv_hip_mcgs_plan_value_bits(const spmv_hip_mcgs_plan* plan, int* bits);
+int spmv_hip_ilu0_plan_create_ex(spmv_hip_ctx* ctx, const spmv_hip_ilu0_host* in,
+                                 int value_bits, spmv_hip_ilu0_plan** plan);
+int spmv_hip_ilu0_plan_build_ex(spmv_hip_ctx* ctx, int32_t num_rows,
+                                int32_t num_cols, int64_t nnz,
+                                const int32_t* rowptr, const int32_t* colind,
+                                int symmetric, const int32_t* colors,
+                                int32_t num_colors, int long_threshold,
+                                int value_bits, spmv_hip_ilu0_plan** plan,
+                                int64_t* info, void* stream);
+int spmv_hip_ilu0_counts(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
+                         int64_t* not_usable, int64_t* negative,
+                         int64_t* out_of_range, void* stream);
+
 /* ---- Aggregation multigrid (spmv::AmgPreconditioner) ---------------------------
  * The device half of one coarsening step of a plain aggregation multigrid
  * hierarchy, fp64, every product, sum, difference and quotient a rounding of

@@ -445,6 +445,16 @@ int spmvh_lambda_max_estimate(spmvh_comm* comm, spmvh_exec* exec,
  * longest ascending path: slow on long dependency chains); colors NULL or rows
  * entries (host) that replace the colouring.  setup 0 with an order or colors
  * is an error; further errors say "not proper", "colour".
+ * spmvh_sgs_create_ex2: the same with SgsOptions::values -- values 0 fp64 (in
+ * every respect spmvh_sgs_create_ex), 1 fp32: the sweep plan keeps its
+ * off-diagonal values as float, rounded to nearest-even, with every setup,
+ * order and colors; anything else is an error ("values"), checked with the
+ * other rules of the options before a handle is looked at.  A value out of
+ * fp32's range is an error that says "fp32 range".
+ * spmvh_sgs_value_bits: 64 or 32.
+ * spmvh_fp32_range_count: the rule of that range as a plain host function --
+ * how many of the n doubles (host) are finite, non-zero and round to +-Inf,
+ * zero or an fp32 subnormal; the kernels that round count by the same rule.
  * spmvh_sgs_setup_info: rounds of the device colouring (0 otherwise) and the
  * wall time of the constructor; _setup_detail: the device setup's colouring
  * and build times and the peak bytes of its temporaries (each may be NULL).
@@ -480,6 +490,10 @@ int spmvh_sgs_build_destroy(spmvh_sgs_build* build);
 int spmvh_sgs_create(spmvh_exec* exec, spmvh_matrix* A, spmvh_sgs** M);
 int spmvh_sgs_create_ex(spmvh_exec* exec, spmvh_matrix* A, int setup, int order,
                         const int32_t* colors, spmvh_sgs** M);
+int spmvh_sgs_create_ex2(spmvh_exec* exec, spmvh_matrix* A, int setup, int order,
+                         const int32_t* colors, int values, spmvh_sgs** M);
+int spmvh_sgs_value_bits(spmvh_sgs* M, int* bits);
+int spmvh_fp32_range_count(const double* values, int64_t n, int64_t* count);
 int spmvh_sgs_setup_info(spmvh_sgs* M, int* rounds, double* setup_ms);
 int spmvh_sgs_setup_detail(spmvh_sgs* M, double* color_ms, double* build_ms,
                            int64_t* temp_bytes);
@@ -547,6 +561,10 @@ int spmvh_pcg_block(spmvh_comm* comm, spmvh_exec* exec, spmvh_matrix* A,
  * spmvh_ilu0_info: info[6] = {entries of before, of after, negative pivots,
  * plan bytes, the constructor's symbolic and numeric wall time in microseconds}.
  * spmvh_ilu0_pattern / _factor: the host copies of cg.h (outputs may be NULL).
+ * spmvh_ilu0_create_ex2: spmvh_ilu0_create_ex with `values` as
+ * spmvh_sgs_create_ex2 takes it; fp32 rounds l~ and u~ as they are scattered
+ * into the sweep plan (the factorisation, spmvh_ilu0_factor and the pivot
+ * counts stay fp64), the constructor and spmvh_ilu0_refactor say "fp32 range".
  * spmvh_ilu0_create_ex: Ilu0Preconditioner(exec, A, SgsOptions) -- the
  * arguments and their rules are spmvh_sgs_create_ex's; setup 1 colours the
  * block and builds the plan on the device (spmv_hip_ilu0_plan_build), nothing
@@ -578,6 +596,9 @@ int spmvh_ilu0_pattern(spmvh_sgs* M, int64_t* before_ptr, int32_t* before_col,
 int spmvh_ilu0_factor(spmvh_sgs* M, double* l, double* u, double* d);
 int spmvh_ilu0_create_ex(spmvh_exec* exec, spmvh_matrix* A, int setup, int order,
                          const int32_t* colors, spmvh_sgs** M);
+int spmvh_ilu0_create_ex2(spmvh_exec* exec, spmvh_matrix* A, int setup,
+                          int order, const int32_t* colors, int values,
+                          spmvh_sgs** M);
 int spmvh_ilu0_export_sizes(spmvh_sgs* M, int64_t* sizes);
 int spmvh_ilu0_export(spmvh_sgs* M, void* const* before, void* const* after);
 

@@ -24,6 +24,8 @@ struct spmv_hip_ilu0_plan {
   Ilu0PartDev before, after;
   double* wd = nullptr;       // n: d~ by position
   double* wdinv = nullptr;    // n: 1.0 / d~ by position
-  unsigned* counts = nullptr; // {not finite or zero, negative}, 16 bytes
+  // {pivots not finite or zero, pivots negative, values out of fp32's range
+  // (an inner plan that keeps floats)}, 16 bytes
+  unsigned* counts = nullptr;
   int64_t bytes = 0;          // without the inner plan's
 };

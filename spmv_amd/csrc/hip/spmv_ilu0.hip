@@ -56,6 +56,7 @@
 #include <new>
 #include <vector>
 
+#include "fp32_range.h"
 #include "ilu0_plan.h"
 #include "plan_scratch.h"
 
@@ -246,6 +247,35 @@ __global__ __launch_bounds__(kBlock) void ilu0_scatter_kernel(
   }
 }
 
+// ... into a sweep plan that keeps floats: every value rounded to nearest-even
+// as it is written; counts[2] += the values out of fp32's range (fp32_range.h),
+// one add per wavefront that met any
+__global__ __launch_bounds__(kBlock) void ilu0_scatter_narrow_kernel(
+    int64_t count, const int64_t* __restrict__ slot,
+    const double* __restrict__ w, float* __restrict__ val,
+    float* __restrict__ long_val, unsigned* counts)
+{
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  // (every lane of a wavefront makes the same number of rounds)
+  const int64_t rounds = (count + stride - 1) / stride;
+  for (int64_t k = 0; k < rounds; ++k) {
+    const int64_t e = k * stride + (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool mine = false;
+    if (e < count) {
+      const double v = w[e];
+      const int64_t s = slot[e];
+      if (s >= 0)
+        val[s] = (float)v;
+      else
+        long_val[~s] = (float)v;
+      mine = spmv_fp32_out_of_range(v);
+    }
+    const unsigned nbad = (unsigned)__popcll(__ballot(mine));
+    if ((threadIdx.x & 63) == 0 && nbad)
+      atomicAdd(counts + 2, nbad);
+  }
+}
+
 template <typename T>
 int upload(const T* host, size_t count, T** dev, int64_t* bytes)
 {
@@ -374,6 +404,27 @@ int spmv_hip_ilu0_plan_create(spmv_hip_ctx* ctx, const spmv_hip_ilu0_host* in,
   return SPMV_HIP_OK;
 }
 
+int spmv_hip_ilu0_plan_create_ex(spmv_hip_ctx* ctx, const spmv_hip_ilu0_host* in,
+                                 int value_bits, spmv_hip_ilu0_plan** plan)
+{
+  SPMV_REQUIRE(plan != nullptr);
+  *plan = nullptr;
+  SPMV_REQUIRE(value_bits == 64 || value_bits == 32);
+  spmv_hip_ilu0_plan* p = nullptr;
+  int rc = spmv_hip_ilu0_plan_create(ctx, in, &p);
+  if (rc == SPMV_HIP_OK && value_bits == 32) {
+    // the placeholders in the form the factorisation will write
+    int64_t none = 0;
+    rc = mcgs_plan_narrow(p->inner, ctx->stream, &none);
+    if (rc != SPMV_HIP_OK) {
+      spmv_hip_ilu0_plan_destroy(p);
+      return rc;
+    }
+  }
+  *plan = p;
+  return rc;
+}
+
 int spmv_hip_ilu0_plan_destroy(spmv_hip_ilu0_plan* plan)
 {
   if (!plan)
@@ -483,16 +534,21 @@ int spmv_hip_ilu0_factor(spmv_hip_ctx* ctx, spmv_hip_ilu0_plan* plan,
   }
   hipLaunchKernelGGL(ilu0_finish_kernel, dim3(rows_grid), dim3(kBlock), 0, st, n,
                      in->perm, plan->wd, plan->wdinv, in->dinv, plan->counts);
-  if (b.count > 0)
-    hipLaunchKernelGGL(ilu0_scatter_kernel,
-                       dim3(spmv_grid_for(ctx, b.count, kBlock)), dim3(kBlock), 0,
-                       st, b.count, b.slot, b.w, in->before.val,
-                       in->before.long_val);
-  if (a.count > 0)
-    hipLaunchKernelGGL(ilu0_scatter_kernel,
-                       dim3(spmv_grid_for(ctx, a.count, kBlock)), dim3(kBlock), 0,
-                       st, a.count, a.slot, a.w, in->after.val,
-                       in->after.long_val);
+  McgsPartDev* sweep[2] = {&in->before, &in->after};
+  Ilu0PartDev* part[2] = {&b, &a};
+  for (int h = 0; h < 2; ++h) {
+    if (part[h]->count == 0)
+      continue;
+    const dim3 grid(spmv_grid_for(ctx, part[h]->count, kBlock));
+    if (in->value_bits == 32)
+      hipLaunchKernelGGL(ilu0_scatter_narrow_kernel, grid, dim3(kBlock), 0, st,
+                         part[h]->count, part[h]->slot, part[h]->w,
+                         sweep[h]->val32, sweep[h]->long_val32, plan->counts);
+    else
+      hipLaunchKernelGGL(ilu0_scatter_kernel, grid, dim3(kBlock), 0, st,
+                         part[h]->count, part[h]->slot, part[h]->w, sweep[h]->val,
+                         sweep[h]->long_val);
+  }
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -506,6 +562,21 @@ int spmv_hip_ilu0_pivots(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
   SPMV_CHECK_HIP(plan_fetch(host, plan->counts, 2, spmv_stream(ctx, stream)));
   *not_usable = host[0];
   *negative = host[1];
+  return SPMV_HIP_OK;
+}
+
+int spmv_hip_ilu0_counts(spmv_hip_ctx* ctx, const spmv_hip_ilu0_plan* plan,
+                         int64_t* not_usable, int64_t* negative,
+                         int64_t* out_of_range, void* stream)
+{
+  SPMV_REQUIRE(ctx && plan && plan->ctx == ctx && not_usable && negative
+               && out_of_range);
+  SPMV_SET_DEVICE(ctx);
+  unsigned host[3] = {0, 0, 0};
+  SPMV_CHECK_HIP(plan_fetch(host, plan->counts, 3, spmv_stream(ctx, stream)));
+  *not_usable = host[0];
+  *negative = host[1];
+  *out_of_range = host[2];
   return SPMV_HIP_OK;
 }
 

@@ -36,6 +36,22 @@
 // where they are not; one instantiation with nrhs at run time serves 1, 3, 5,
 // 6 and 7.
 //
+// fp32 values (SgsOptions::values = fp32, value_bits 32).  A plan may keep val
+// and long_val of both parts as float, each the fp64 value rounded to
+// nearest-even: a sweep then streams 8 bytes per stored entry, not 12.  Both
+// kernels are templates on the stored type and compute acc = acc + (double)v32
+// * z[col] -- the widening is exact, so the result has the bits of the fp64
+// sweep on the widened values; dinv, r, z and the sums stay fp64.  A value load
+// of a slice column is 256 contiguous bytes of a wavefront, one load per k.
+// The plan is narrowed after either builder has made the fp64 plan
+// (mcgs_plan_narrow: per array allocate, round, free), the values out of
+// fp32's range (fp32_range.h) counted in the same kernel.  The fp64 arrays are
+// not kept:
+//   plan_bytes(fp32) = plan_bytes(fp64) - 4 * (E_before + E_after
+//                                              + L_before + L_after)
+// E: the sliced entries of a part, padding included (slice_ptr's last), L: its
+// long entries (long_ptr's last).
+//
 // Built with -ffp-contract=off: every product and sum is a rounding of its own.
 #include "common.h"
 #include "pcg_ws.h"
@@ -43,6 +59,7 @@
 
 #include <vector>
 
+#include "fp32_range.h"
 #include "mcgs_plan.h"
 #include "plan_scratch.h"
 
@@ -53,15 +70,18 @@ constexpr int kWaves = kBlock / 64;
 
 // One colour, one direction.  Wavefront w of the launch: slice first_slice + w
 // while w < num_slices, then long row first_long + (w - num_slices).
-template <bool FORWARD>
+// V: the stored value type, double or float (value_bits 64 / 32); a float is
+// widened before its product, exactly: the sum has the bits of the fp64 sweep
+// on the widened values.
+template <typename V, bool FORWARD>
 __global__ __launch_bounds__(kBlock) void mcgs_sweep_kernel(
     int32_t first_slice, int32_t num_slices, int32_t pos_end,
     int32_t first_long, int32_t num_long,
     const int32_t* __restrict__ slice_pos0,
     const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ len,
-    const int32_t* __restrict__ col, const double* __restrict__ val,
+    const int32_t* __restrict__ col, const V* __restrict__ val,
     const int32_t* __restrict__ long_pos, const int64_t* __restrict__ long_ptr,
-    const int32_t* __restrict__ long_col, const double* __restrict__ long_val,
+    const int32_t* __restrict__ long_col, const V* __restrict__ long_val,
     const int32_t* __restrict__ perm, const double* __restrict__ dinv,
     const double* __restrict__ r, double* z, const PcgScalars* __restrict__ sc)
 {
@@ -82,7 +102,7 @@ __global__ __launch_bounds__(kBlock) void mcgs_sweep_kernel(
 #pragma unroll 4
     for (int32_t k = 0; k < m; ++k) {
       const int64_t e = base + (int64_t)k * 64;
-      acc = acc + val[e] * z[col[e]];
+      acc = acc + (double)val[e] * z[col[e]];
     }
     const int32_t i = perm[pos];
     if constexpr (FORWARD)
@@ -99,7 +119,8 @@ __global__ __launch_bounds__(kBlock) void mcgs_sweep_kernel(
   double acc = 0.0;
   for (int64_t e = e0; e < e1; e += 64) {
     const int64_t mine = e + lane;
-    const double prod = mine < e1 ? long_val[mine] * z[long_col[mine]] : 0.0;
+    const double prod
+        = mine < e1 ? (double)long_val[mine] * z[long_col[mine]] : 0.0;
     const int cnt = e1 - e < 64 ? (int)(e1 - e) : 64;
     for (int j = 0; j < cnt; ++j) // in the entries' order, every lane the same
       acc = acc + __shfl(prod, j, 64);
@@ -176,15 +197,15 @@ __device__ __forceinline__ void block_finish(int64_t i, int nrhs, double d,
 // mcgs_sweep_kernel's.  K = 2, 4, 8: the width at compile time (VEC: 16-byte
 // accesses); K = 0: nrhs at run time, 1..8.  Every index of an accumulator is
 // a constant after unrolling: they stay in registers.
-template <int K, bool VEC, bool FORWARD>
+template <typename V, int K, bool VEC, bool FORWARD>
 __global__ __launch_bounds__(kBlock) void mcgs_sweep_block_kernel(
     int32_t first_slice, int32_t num_slices, int32_t pos_end,
     int32_t first_long, int32_t num_long,
     const int32_t* __restrict__ slice_pos0,
     const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ len,
-    const int32_t* __restrict__ col, const double* __restrict__ val,
+    const int32_t* __restrict__ col, const V* __restrict__ val,
     const int32_t* __restrict__ long_pos, const int64_t* __restrict__ long_ptr,
-    const int32_t* __restrict__ long_col, const double* __restrict__ long_val,
+    const int32_t* __restrict__ long_col, const V* __restrict__ long_val,
     const int32_t* __restrict__ perm, const double* __restrict__ dinv,
     int nrhs_rt, const double* __restrict__ r, double* z,
     const CgbState* __restrict__ st)
@@ -209,7 +230,7 @@ __global__ __launch_bounds__(kBlock) void mcgs_sweep_block_kernel(
 #pragma unroll 2
     for (int32_t k = 0; k < m; ++k) {
       const int64_t e = base + (int64_t)k * 64;
-      const double a = val[e];
+      const double a = (double)val[e];
       double zv[KM];
       block_load<VEC, KM>(z, col[e], nrhs, zv);
 #pragma unroll
@@ -230,7 +251,7 @@ __global__ __launch_bounds__(kBlock) void mcgs_sweep_block_kernel(
     const int64_t mine = e + lane;
     double prod[KM] = {};
     if (mine < e1) {
-      const double a = long_val[mine];
+      const double a = (double)long_val[mine];
       double zv[KM];
       block_load<VEC, KM>(z, long_col[mine], nrhs, zv);
 #pragma unroll
@@ -342,13 +363,52 @@ int upload_part(const spmv_hip_mcgs_host& in, const spmv_hip_mcgs_part& p,
 void free_part(McgsPartDev* d)
 {
   for (void* q : {(void*)d->slice_pos0, (void*)d->slice_ptr, (void*)d->len,
-                  (void*)d->col, (void*)d->val, (void*)d->long_pos,
-                  (void*)d->long_ptr, (void*)d->long_col, (void*)d->long_val})
+                  (void*)d->col, (void*)d->val, (void*)d->val32,
+                  (void*)d->long_pos, (void*)d->long_ptr, (void*)d->long_col,
+                  (void*)d->long_val, (void*)d->long_val32})
     if (q)
       (void)spmv_plan_free(q);
 }
 
-template <bool FORWARD>
+// the value arrays of a part in the form V
+template <typename V>
+struct PartValues;
+template <>
+struct PartValues<double> {
+  static const double* val(const McgsPartDev& p) { return p.val; }
+  static const double* long_val(const McgsPartDev& p) { return p.long_val; }
+};
+template <>
+struct PartValues<float> {
+  static const float* val(const McgsPartDev& p) { return p.val32; }
+  static const float* long_val(const McgsPartDev& p) { return p.long_val32; }
+};
+
+// out[e] = in[e] rounded to nearest-even; *bad += the values out of fp32's
+// range (fp32_range.h), one add per wavefront that met any
+__global__ __launch_bounds__(kBlock) void mcgs_narrow_kernel(
+    int64_t count, const double* __restrict__ in, float* __restrict__ out,
+    unsigned long long* __restrict__ bad)
+{
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  // (every lane of a wavefront makes the same number of rounds)
+  const int64_t rounds = (count + stride - 1) / stride;
+  for (int64_t k = 0; k < rounds; ++k) {
+    const int64_t e = k * stride + (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool mine = false;
+    if (e < count) {
+      const double v = in[e];
+      out[e] = (float)v;
+      mine = spmv_fp32_out_of_range(v);
+    }
+    const unsigned long long nbad
+        = (unsigned long long)__popcll(__ballot(mine));
+    if ((threadIdx.x & 63) == 0 && nbad)
+      atomicAdd(bad, nbad);
+  }
+}
+
+template <typename V, bool FORWARD>
 void launch_colour(const spmv_hip_mcgs_plan* plan, const McgsPartDev& p, int c,
                    const double* r, double* z, const PcgScalars* sc,
                    hipStream_t st)
@@ -359,14 +419,27 @@ void launch_colour(const spmv_hip_mcgs_plan* plan, const McgsPartDev& p, int c,
   if (waves == 0)
     return;
   const unsigned grid = (unsigned)((waves + kWaves - 1) / kWaves);
-  hipLaunchKernelGGL(mcgs_sweep_kernel<FORWARD>, dim3(grid), dim3(kBlock), 0, st,
-                     p.color_slice[c], ns, plan->color_start[c + 1],
+  hipLaunchKernelGGL((mcgs_sweep_kernel<V, FORWARD>), dim3(grid), dim3(kBlock), 0,
+                     st, p.color_slice[c], ns, plan->color_start[c + 1],
                      p.color_long[c], nl, p.slice_pos0, p.slice_ptr, p.len,
-                     p.col, p.val, p.long_pos, p.long_ptr, p.long_col,
-                     p.long_val, plan->perm, plan->dinv, r, z, sc);
+                     p.col, PartValues<V>::val(p), p.long_pos, p.long_ptr,
+                     p.long_col, PartValues<V>::long_val(p), plan->perm,
+                     plan->dinv, r, z, sc);
 }
 
-template <int K, bool VEC, bool FORWARD>
+// the 2C - 1 launches of one application
+template <typename V>
+void apply_single(const spmv_hip_mcgs_plan* plan, const double* r, double* z,
+                  const PcgScalars* sc, hipStream_t st)
+{
+  const int C = plan->num_colors;
+  for (int c = 0; c < C; ++c)
+    launch_colour<V, true>(plan, plan->before, c, r, z, sc, st);
+  for (int c = C - 2; c >= 0; --c)
+    launch_colour<V, false>(plan, plan->after, c, r, z, sc, st);
+}
+
+template <typename V, int K, bool VEC, bool FORWARD>
 void launch_colour_block(const spmv_hip_mcgs_plan* plan, const McgsPartDev& p,
                          int c, int nrhs, const double* r, double* z,
                          const CgbState* state, hipStream_t st)
@@ -377,26 +450,67 @@ void launch_colour_block(const spmv_hip_mcgs_plan* plan, const McgsPartDev& p,
   if (waves == 0)
     return;
   const unsigned grid = (unsigned)((waves + kWaves - 1) / kWaves);
-  hipLaunchKernelGGL((mcgs_sweep_block_kernel<K, VEC, FORWARD>), dim3(grid),
+  hipLaunchKernelGGL((mcgs_sweep_block_kernel<V, K, VEC, FORWARD>), dim3(grid),
                      dim3(kBlock), 0, st, p.color_slice[c], ns,
                      plan->color_start[c + 1], p.color_long[c], nl, p.slice_pos0,
-                     p.slice_ptr, p.len, p.col, p.val, p.long_pos, p.long_ptr,
-                     p.long_col, p.long_val, plan->perm, plan->dinv, nrhs, r, z,
-                     state);
+                     p.slice_ptr, p.len, p.col, PartValues<V>::val(p),
+                     p.long_pos, p.long_ptr, p.long_col,
+                     PartValues<V>::long_val(p), plan->perm, plan->dinv, nrhs, r,
+                     z, state);
 }
 
 // the 2C - 1 launches of one width
-template <int K, bool VEC>
+template <typename V, int K, bool VEC>
 void apply_block(const spmv_hip_mcgs_plan* plan, int nrhs, const double* r,
                  double* z, const CgbState* state, hipStream_t st)
 {
   const int C = plan->num_colors;
   for (int c = 0; c < C; ++c)
-    launch_colour_block<K, VEC, true>(plan, plan->before, c, nrhs, r, z, state,
-                                      st);
+    launch_colour_block<V, K, VEC, true>(plan, plan->before, c, nrhs, r, z, state,
+                                         st);
   for (int c = C - 2; c >= 0; --c)
-    launch_colour_block<K, VEC, false>(plan, plan->after, c, nrhs, r, z, state,
-                                       st);
+    launch_colour_block<V, K, VEC, false>(plan, plan->after, c, nrhs, r, z, state,
+                                          st);
+}
+
+// the width and the alignment choose the instantiation, as for every plan
+template <typename V>
+void apply_block_any(const spmv_hip_mcgs_plan* plan, int nrhs, bool vec,
+                     const double* R, double* Z, const CgbState* state,
+                     hipStream_t st)
+{
+  if (nrhs == 2 && vec)
+    apply_block<V, 2, true>(plan, nrhs, R, Z, state, st);
+  else if (nrhs == 2)
+    apply_block<V, 2, false>(plan, nrhs, R, Z, state, st);
+  else if (nrhs == 4 && vec)
+    apply_block<V, 4, true>(plan, nrhs, R, Z, state, st);
+  else if (nrhs == 4)
+    apply_block<V, 4, false>(plan, nrhs, R, Z, state, st);
+  else if (nrhs == 8 && vec)
+    apply_block<V, 8, true>(plan, nrhs, R, Z, state, st);
+  else if (nrhs == 8)
+    apply_block<V, 8, false>(plan, nrhs, R, Z, state, st);
+  else
+    apply_block<V, 0, false>(plan, nrhs, R, Z, state, st);
+}
+
+// one value array of a plan from fp64 to fp32 (mcgs_plan_narrow)
+int narrow_array(spmv_hip_ctx* ctx, int64_t count, double** wide, float** narrow,
+                 unsigned long long* bad, int64_t* bytes, hipStream_t st)
+{
+  if (count == 0 || !*wide)
+    return SPMV_HIP_OK;
+  SPMV_CHECK_HIP(spmv_plan_malloc(narrow, (size_t)count * sizeof(float)));
+  *bytes += count * (int64_t)sizeof(float);
+  hipLaunchKernelGGL(mcgs_narrow_kernel, dim3(spmv_grid_for(ctx, count, kBlock)),
+                     dim3(kBlock), 0, st, count, *wide, *narrow, bad);
+  SPMV_CHECK_HIP(hipGetLastError());
+  SPMV_CHECK_HIP(hipStreamSynchronize(st));
+  SPMV_CHECK_HIP(spmv_plan_free(*wide));
+  *wide = nullptr;
+  *bytes -= count * (int64_t)sizeof(double);
+  return SPMV_HIP_OK;
 }
 
 } // namespace
@@ -438,6 +552,31 @@ int spmv_hip_mcgs_plan_create(spmv_hip_ctx* ctx, const spmv_hip_mcgs_host* in,
   return SPMV_HIP_OK;
 }
 
+int spmv_hip_mcgs_plan_create_ex(spmv_hip_ctx* ctx, const spmv_hip_mcgs_host* in,
+                                 int value_bits, spmv_hip_mcgs_plan** plan,
+                                 int64_t* out_of_range)
+{
+  SPMV_REQUIRE(plan != nullptr);
+  *plan = nullptr;
+  SPMV_REQUIRE(out_of_range && (value_bits == 64 || value_bits == 32));
+  *out_of_range = 0;
+  spmv_hip_mcgs_plan* p = nullptr;
+  int rc = spmv_hip_mcgs_plan_create(ctx, in, &p);
+  if (rc != SPMV_HIP_OK || value_bits == 64) {
+    *plan = p;
+    return rc;
+  }
+  rc = mcgs_plan_narrow(p, ctx->stream, out_of_range);
+  if (rc == SPMV_HIP_OK && *out_of_range != 0)
+    rc = SPMV_HIP_ERANGE;
+  if (rc != SPMV_HIP_OK) {
+    spmv_hip_mcgs_plan_destroy(p);
+    return rc;
+  }
+  *plan = p;
+  return SPMV_HIP_OK;
+}
+
 int spmv_hip_mcgs_plan_destroy(spmv_hip_mcgs_plan* plan)
 {
   if (!plan)
@@ -458,6 +597,13 @@ int spmv_hip_mcgs_plan_bytes(const spmv_hip_mcgs_plan* plan, int64_t* bytes)
   return SPMV_HIP_OK;
 }
 
+int spmv_hip_mcgs_plan_value_bits(const spmv_hip_mcgs_plan* plan, int* bits)
+{
+  SPMV_REQUIRE(plan && bits);
+  *bits = plan->value_bits;
+  return SPMV_HIP_OK;
+}
+
 int spmv_hip_mcgs_apply_f64(spmv_hip_ctx* ctx, const spmv_hip_mcgs_plan* plan,
                             spmv_hip_pcg_ws* ws, const double* r, double* z,
                             void* stream)
@@ -467,11 +613,10 @@ int spmv_hip_mcgs_apply_f64(spmv_hip_ctx* ctx, const spmv_hip_mcgs_plan* plan,
   SPMV_SET_DEVICE(ctx);
   hipStream_t st = spmv_stream(ctx, stream);
   const PcgScalars* sc = ws ? ws->sc : nullptr;
-  const int C = plan->num_colors;
-  for (int c = 0; c < C; ++c)
-    launch_colour<true>(plan, plan->before, c, r, z, sc, st);
-  for (int c = C - 2; c >= 0; --c)
-    launch_colour<false>(plan, plan->after, c, r, z, sc, st);
+  if (plan->value_bits == 32)
+    apply_single<float>(plan, r, z, sc, st);
+  else
+    apply_single<double>(plan, r, z, sc, st);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
@@ -491,22 +636,45 @@ int spmv_hip_mcgs_apply_block_f64(spmv_hip_ctx* ctx,
   const bool vec
       = ((reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(Z)) & 15u)
         == 0;
-  if (nrhs == 2 && vec)
-    apply_block<2, true>(plan, nrhs, R, Z, state, st);
-  else if (nrhs == 2)
-    apply_block<2, false>(plan, nrhs, R, Z, state, st);
-  else if (nrhs == 4 && vec)
-    apply_block<4, true>(plan, nrhs, R, Z, state, st);
-  else if (nrhs == 4)
-    apply_block<4, false>(plan, nrhs, R, Z, state, st);
-  else if (nrhs == 8 && vec)
-    apply_block<8, true>(plan, nrhs, R, Z, state, st);
-  else if (nrhs == 8)
-    apply_block<8, false>(plan, nrhs, R, Z, state, st);
+  if (plan->value_bits == 32)
+    apply_block_any<float>(plan, nrhs, vec, R, Z, state, st);
   else
-    apply_block<0, false>(plan, nrhs, R, Z, state, st);
+    apply_block_any<double>(plan, nrhs, vec, R, Z, state, st);
   SPMV_CHECK_LAUNCH();
   return SPMV_HIP_OK;
 }
 
 } // extern "C"
+
+int mcgs_plan_narrow(spmv_hip_mcgs_plan* plan, hipStream_t st,
+                     int64_t* out_of_range)
+{
+  SPMV_REQUIRE(plan && out_of_range && plan->value_bits == 64);
+  SPMV_SET_DEVICE(plan->ctx);
+  *out_of_range = 0;
+  plan->value_bits = 32;
+  if (plan->n == 0)
+    return SPMV_HIP_OK;
+  PlanScratch<unsigned long long> bad;
+  SPMV_CHECK_HIP(bad.alloc(1));
+  SPMV_CHECK_HIP(hipMemsetAsync(bad.get(), 0, sizeof(unsigned long long), st));
+  const int C = plan->num_colors;
+  for (McgsPartDev* d : {&plan->before, &plan->after}) {
+    const size_t ns = (size_t)d->color_slice[(size_t)C];
+    const size_t nl = (size_t)d->color_long[(size_t)C];
+    int64_t entries = 0, long_entries = 0;
+    SPMV_CHECK_HIP(plan_fetch(&entries, d->slice_ptr + ns, 1, st));
+    SPMV_CHECK_HIP(plan_fetch(&long_entries, d->long_ptr + nl, 1, st));
+    int rc = narrow_array(plan->ctx, entries, &d->val, &d->val32, bad.get(),
+                          &plan->bytes, st);
+    if (rc == SPMV_HIP_OK)
+      rc = narrow_array(plan->ctx, long_entries, &d->long_val, &d->long_val32,
+                        bad.get(), &plan->bytes, st);
+    if (rc != SPMV_HIP_OK)
+      return rc;
+  }
+  unsigned long long host = 0;
+  SPMV_CHECK_HIP(plan_fetch(&host, bad.get(), 1, st));
+  *out_of_range = (int64_t)host;
+  return SPMV_HIP_OK;
+}

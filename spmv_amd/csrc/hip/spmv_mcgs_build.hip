@@ -866,6 +866,60 @@ int spmv_hip_mcgs_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
   return rc;
 }
 
+int spmv_hip_mcgs_plan_build_ex(spmv_hip_ctx* ctx, int32_t num_rows,
+                                int32_t num_cols, int64_t nnz,
+                                const int32_t* rowptr, const int32_t* colind,
+                                const double* values, const double* diagonal,
+                                int symmetric, const int32_t* colors,
+                                int32_t num_colors, int long_threshold,
+                                int value_bits, spmv_hip_mcgs_plan** plan,
+                                int64_t* info, int64_t* out_of_range,
+                                void* stream)
+{
+  SPMV_REQUIRE(plan != nullptr);
+  *plan = nullptr;
+  SPMV_REQUIRE(out_of_range && (value_bits == 64 || value_bits == 32));
+  *out_of_range = 0;
+  PlanDeleter guard;
+  int rc = spmv_hip_mcgs_plan_build(ctx, num_rows, num_cols, nnz, rowptr, colind,
+                                    values, diagonal, symmetric, colors,
+                                    num_colors, long_threshold, &guard.p, info,
+                                    stream);
+  if (rc == SPMV_HIP_OK && value_bits == 32) {
+    rc = mcgs_plan_narrow(guard.p, spmv_stream(ctx, stream), out_of_range);
+    if (rc == SPMV_HIP_OK && *out_of_range != 0)
+      rc = SPMV_HIP_ERANGE;
+  }
+  if (rc == SPMV_HIP_OK)
+    *plan = guard.release();
+  return rc;
+}
+
+int spmv_hip_ilu0_plan_build_ex(spmv_hip_ctx* ctx, int32_t num_rows,
+                                int32_t num_cols, int64_t nnz,
+                                const int32_t* rowptr, const int32_t* colind,
+                                int symmetric, const int32_t* colors,
+                                int32_t num_colors, int long_threshold,
+                                int value_bits, spmv_hip_ilu0_plan** plan,
+                                int64_t* info, void* stream)
+{
+  SPMV_REQUIRE(plan != nullptr);
+  *plan = nullptr;
+  SPMV_REQUIRE(value_bits == 64 || value_bits == 32);
+  Ilu0PlanDeleter guard;
+  int rc = spmv_hip_ilu0_plan_build(ctx, num_rows, num_cols, nnz, rowptr, colind,
+                                    symmetric, colors, num_colors, long_threshold,
+                                    &guard.p, info, stream);
+  if (rc == SPMV_HIP_OK && value_bits == 32) {
+    // the placeholders (+0.0) in the form the factorisation will write
+    int64_t none = 0;
+    rc = mcgs_plan_narrow(guard.p->inner, spmv_stream(ctx, stream), &none);
+  }
+  if (rc == SPMV_HIP_OK)
+    *plan = guard.release();
+  return rc;
+}
+
 int spmv_hip_ilu0_plan_build(spmv_hip_ctx* ctx, int32_t num_rows,
                              int32_t num_cols, int64_t nnz, const int32_t* rowptr,
                              const int32_t* colind, int symmetric,
@@ -953,6 +1007,22 @@ int spmv_hip_mcgs_plan_export(const spmv_hip_mcgs_plan* plan, int32_t* perm,
     return hipMemcpy(host, dev, sizeof(*host) * (size_t)count,
                      hipMemcpyDeviceToHost);
   };
+  // the values of a part, widened where the plan keeps floats
+  std::vector<float> narrow;
+  auto fetch_values = [&](double* host, const double* dev, const float* dev32,
+                          int64_t count) {
+    if (plan->value_bits == 64 || !host || count == 0)
+      return fetch(host, dev, count);
+    try {
+      narrow.resize((size_t)count);
+    } catch (...) {
+      return hipErrorOutOfMemory;
+    }
+    const hipError_t e = fetch(narrow.data(), dev32, count);
+    if (e == hipSuccess)
+      std::copy(narrow.begin(), narrow.end(), host);
+    return e;
+  };
   const int64_t n = plan->n, C = plan->num_colors, ns = sizes[2];
   MB_HIP(fetch(perm, plan->perm, n));
   MB_HIP(fetch(dinv, plan->dinv, n));
@@ -976,11 +1046,12 @@ int spmv_hip_mcgs_plan_export(const spmv_hip_mcgs_plan* plan, int32_t* perm,
     MB_HIP(fetch(o->slice_ptr, d->slice_ptr, ns + 1));
     MB_HIP(fetch(o->len, d->len, n));
     MB_HIP(fetch(o->col, d->col, entries));
-    MB_HIP(fetch(o->val, d->val, entries));
+    MB_HIP(fetch_values(o->val, d->val, d->val32, entries));
     MB_HIP(fetch(o->long_pos, d->long_pos, nl));
     MB_HIP(fetch(o->long_ptr, d->long_ptr, nl + 1));
     MB_HIP(fetch(o->long_col, d->long_col, long_entries));
-    MB_HIP(fetch(o->long_val, d->long_val, long_entries));
+    MB_HIP(fetch_values(o->long_val, d->long_val, d->long_val32,
+                        long_entries));
   }
   return SPMV_HIP_OK;
 }

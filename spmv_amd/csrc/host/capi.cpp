@@ -19,6 +19,7 @@
 #include "ilu0_build.h"
 #include "sgs_build.h"
 #include "spmv_hip.h"
+#include "../hip/fp32_range.h"
 
 using namespace spmv;
 
@@ -1452,6 +1453,61 @@ int spmvh_sgs_create_ex(spmvh_exec* exec, spmvh_matrix* A, int setup, int order,
   });
 }
 
+namespace
+{
+// the rules of SgsOptions, before any handle is looked at
+SgsOptions sgs_options_of(int setup, int order, const int32_t* colors, int values)
+{
+  require(setup == 0 || setup == 1, "setup: 0 (host) or 1 (device)");
+  require(order >= -1 && order <= 1,
+          "order: -1 (default), 0 (hashed) or 1 (natural)");
+  require(values == 0 || values == 1, "values: 0 (fp64) or 1 (fp32)");
+  // (an order given explicitly counts as given, the default included)
+  require(setup == 1 || (order == -1 && !colors),
+          "setup = host colours by itself: it takes neither colors nor an "
+          "order");
+  SgsOptions opt;
+  opt.setup = setup == 1 ? SgsSetup::device : SgsSetup::host;
+  opt.order = order == 1 ? SgsOrder::natural : SgsOrder::hashed;
+  opt.colors = colors;
+  opt.values = values == 1 ? SgsValues::fp32 : SgsValues::fp64;
+  return opt;
+}
+} // namespace
+
+int spmvh_sgs_create_ex2(spmvh_exec* exec, spmvh_matrix* A, int setup, int order,
+                         const int32_t* colors, int values, spmvh_sgs** M)
+{
+  return guarded([&] {
+    const SgsOptions opt = sgs_options_of(setup, order, colors, values);
+    require(exec && A && M, "NULL argument");
+    require(exec->hip != nullptr, "not a HipExecutor");
+    auto m = std::make_unique<spmvh_sgs>();
+    m->exec = exec->hip;
+    m->M.reset(new SgsPreconditioner(*exec->hip, *A->A, opt));
+    *M = m.release();
+  });
+}
+
+int spmvh_sgs_value_bits(spmvh_sgs* M, int* bits)
+{
+  return guarded([&] {
+    require(M && bits, "NULL argument");
+    *bits = M->M->value_bits();
+  });
+}
+
+int spmvh_fp32_range_count(const double* values, int64_t n, int64_t* count)
+{
+  return guarded([&] {
+    require(count && n >= 0 && (n == 0 || values), "NULL argument");
+    int64_t bad = 0;
+    for (int64_t i = 0; i < n; ++i)
+      bad += spmv_fp32_out_of_range(values[i]) ? 1 : 0;
+    *count = bad;
+  });
+}
+
 int spmvh_sgs_setup_info(spmvh_sgs* M, int* rounds, double* setup_ms)
 {
   return guarded([&] {
@@ -1633,6 +1689,21 @@ int spmvh_ilu0_create_ex(spmvh_exec* exec, spmvh_matrix* A, int setup, int order
     opt.setup = setup == 1 ? SgsSetup::device : SgsSetup::host;
     opt.order = order == 1 ? SgsOrder::natural : SgsOrder::hashed;
     opt.colors = colors;
+    auto m = std::make_unique<spmvh_sgs>();
+    m->exec = exec->hip;
+    m->M.reset(new Ilu0Preconditioner(*exec->hip, *A->A, opt));
+    *M = m.release();
+  });
+}
+
+int spmvh_ilu0_create_ex2(spmvh_exec* exec, spmvh_matrix* A, int setup,
+                          int order, const int32_t* colors, int values,
+                          spmvh_sgs** M)
+{
+  return guarded([&] {
+    const SgsOptions opt = sgs_options_of(setup, order, colors, values);
+    require(exec && A && M, "NULL argument");
+    require(exec->hip != nullptr, "not a HipExecutor");
     auto m = std::make_unique<spmvh_sgs>();
     m->exec = exec->hip;
     m->M.reset(new Ilu0Preconditioner(*exec->hip, *A->A, opt));

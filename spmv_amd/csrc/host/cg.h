@@ -513,12 +513,31 @@ double lambda_max_estimate(const Comm& comm, HipExecutor& exec,
 // and messages are the same on both paths.  setup = host with colors, or with
 // an order other than the default, throws std::invalid_argument: the host
 // builder colours by itself.
+//
+// values = fp32 (with every setup, order and colors) keeps the off-diagonal
+// values of the sweep plan -- the a_e above, both parts, long rows included --
+// as float, each the fp64 value rounded to nearest-even: a sweep streams 8
+// bytes per stored entry, not 12, and plan_bytes() drops by 4 bytes per stored
+// entry (padding included).  dinv, r, z, the sums and every operation stay
+// fp64: s = s + (double)a32_e * z[col_e], so sgs_apply has the bits of the fp64
+// sweeps on the widened values, and M is still a fixed SPD operator -- equal
+// values round to equal floats -- that pcg_sgs, pcg_block, gmres, minres, idrs
+// and lobpcg take under the same rules; the Krylov method converges to fp64
+// accuracy on A all the same.  A matrix whose values are exact in fp32
+// (Poisson: 6 and -1) gives the bits of the fp64 object.  A finite non-zero
+// value whose rounding is +-Inf, zero or an fp32 subnormal is refused
+// (std::runtime_error, "fp32 range"): the plan must not depend on a denormal
+// mode.  The values are counted on the device while they are rounded; the
+// constructor waits once more for the count.  values = fp64 (the default) is
+// the object as it ever was, on the code path it ever took.
 enum class SgsSetup { host, device };
 enum class SgsOrder { hashed, natural };
+enum class SgsValues { fp64, fp32 };
 struct SgsOptions {
   SgsSetup setup = SgsSetup::host;
   SgsOrder order = SgsOrder::hashed;
   const int32_t* colors = nullptr;
+  SgsValues values = SgsValues::fp64;
 };
 
 class SgsPreconditioner
@@ -545,6 +564,8 @@ public:
   // peak device memory of the device setup's temporaries (0: host setup)
   int64_t setup_temp_bytes() const { return _temp_bytes; }
   virtual int64_t plan_bytes() const; // device memory of the plan
+  // 64 or 32: the width of the sweep plan's off-diagonal values
+  int value_bits() const { return _value_bits; }
   // the plan the sweeps run on (a derived class may refuse: check_usable)
   spmv_hip_mcgs_plan* plan() const
   {
@@ -574,10 +595,11 @@ protected:
   bool _owns_plan = true;
   int _num_colors = 0;
   int _rows = 0;
+  int _value_bits = 64;
   mutable std::vector<int32_t> _colors; // (device setup: empty until asked for)
 
 private:
-  void build_on_host(const Matrix<double>& A);
+  void build_on_host(const Matrix<double>& A, SgsValues width);
   void build_on_device(const Matrix<double>& A, const SgsOptions& options);
   int _rounds = 0;
   double _setup_ms = 0, _color_ms = 0, _build_ms = 0;
@@ -644,6 +666,15 @@ private:
 // colors() and pattern() fetch the colours from the plan on their first call.
 // rounds(), color_ms(), build_ms() and setup_temp_bytes() describe the device
 // setup; symbolic_ms() is the wall time of colouring and build together.
+//
+// values = fp32: the factorisation stays fp64 -- the working copy, factor(),
+// pattern() and the pivot counts do not change --; l~ and u~ are rounded to
+// float as they are scattered into the sweep plan, dinv~ stays fp64, and
+// refactor rounds again.  The factor of a symmetric matrix stays symmetric
+// (equal values round to equal floats).  A factor entry out of fp32's range
+// throws "fp32 range" from the constructor and from refactor, counted at the
+// wait of the pivot counts; after such a refactor the object is not usable
+// (plan() throws "fp32 range") until a later refactor succeeds.
 class Ilu0Preconditioner : public SgsPreconditioner
 {
 public:
@@ -680,12 +711,14 @@ protected:
 
 private:
   void construct(const Matrix<double>& A, const SgsOptions& options);
-  void symbolic_on_host(const CSRMatrix<double>* blk, int64_t n);
+  void symbolic_on_host(const CSRMatrix<double>* blk, int64_t n,
+                        SgsValues values);
   void symbolic_on_device(const CSRMatrix<double>* blk, int64_t n,
                           const SgsOptions& options,
                           std::chrono::steady_clock::time_point t0);
   void numeric(const Matrix<double>& A);
   bool _usable = true;
+  bool _out_of_range = false; // why not: the last factor left fp32's range
 
   spmv_hip_ilu0_plan* _ilu = nullptr;
   double* _diag = nullptr; // general storage: Matrix::diagonal's output

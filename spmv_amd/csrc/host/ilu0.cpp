@@ -83,7 +83,7 @@ void Ilu0Preconditioner::construct(const Matrix<double>& A,
   _num_values = blk->non_zeros();
   try { // (the destructor does not run)
     if (options.setup == SgsSetup::host)
-      symbolic_on_host(blk, n);
+      symbolic_on_host(blk, n, options.values);
     else
       symbolic_on_device(blk, n, options, t0);
   } catch (...) {
@@ -106,7 +106,8 @@ void Ilu0Preconditioner::construct(const Matrix<double>& A,
   _numeric_ms = ms_since(t1);
 }
 
-void Ilu0Preconditioner::symbolic_on_host(const CSRMatrix<double>* blk, int64_t n)
+void Ilu0Preconditioner::symbolic_on_host(const CSRMatrix<double>* blk, int64_t n,
+                                          SgsValues values)
 {
   HipExecutor& exec = _exec;
   const int64_t nnz = blk->non_zeros();
@@ -146,8 +147,14 @@ void Ilu0Preconditioner::symbolic_on_host(const CSRMatrix<double>* blk, int64_t 
   in.num_values = nnz;
   in.before = part_of(sym.before);
   in.after = part_of(sym.after);
-  throw_on_error(spmv_hip_ilu0_plan_create(exec.context(), &in, &_ilu),
-                 "spmv_hip_ilu0_plan_create");
+  if (values == SgsValues::fp64) {
+    throw_on_error(spmv_hip_ilu0_plan_create(exec.context(), &in, &_ilu),
+                   "spmv_hip_ilu0_plan_create");
+  } else {
+    throw_on_error(spmv_hip_ilu0_plan_create_ex(exec.context(), &in, 32, &_ilu),
+                   "spmv_hip_ilu0_plan_create_ex");
+    _value_bits = 32;
+  }
   spmv_hip_mcgs_plan* inner = nullptr;
   spmv_hip_ilu0_mcgs_plan(_ilu, &inner);
   adopt(inner, sym.num_colors, std::move(sym.colors));
@@ -208,9 +215,19 @@ void Ilu0Preconditioner::symbolic_on_device(
   const double color_ms = ms_since(t0);
 
   int64_t info[SPMV_HIP_MCGS_INFO_WORDS] = {};
-  const int rc = spmv_hip_ilu0_plan_build(
-      ctx, (int32_t)n, blk->cols(), nnz, rowptr, colind, _symmetric ? 1 : 0,
-      d_colors.p, num_colors, kSgsLongThreshold, &_ilu, info, nullptr);
+  const int rc
+      = options.values == SgsValues::fp64
+            ? spmv_hip_ilu0_plan_build(ctx, (int32_t)n, blk->cols(), nnz, rowptr,
+                                       colind, _symmetric ? 1 : 0, d_colors.p,
+                                       num_colors, kSgsLongThreshold, &_ilu,
+                                       info, nullptr)
+            : spmv_hip_ilu0_plan_build_ex(ctx, (int32_t)n, blk->cols(), nnz,
+                                          rowptr, colind, _symmetric ? 1 : 0,
+                                          d_colors.p, num_colors,
+                                          kSgsLongThreshold, 32, &_ilu, info,
+                                          nullptr);
+  if (options.values == SgsValues::fp32)
+    _value_bits = 32;
   if (rc == SPMV_HIP_EINVAL && info[1] == SPMV_HIP_ILU0_DUPLICATE)
     throw std::runtime_error(
         "spmv::ilu0_symbolic - Error: duplicate column in row "
@@ -256,6 +273,11 @@ Ilu0Preconditioner::~Ilu0Preconditioner()
 
 void Ilu0Preconditioner::check_usable() const
 {
+  if (!_usable && _out_of_range)
+    throw std::runtime_error(
+        "spmv::Ilu0Preconditioner - Error: fp32 range: the last factorisation "
+        "left entries that round to Inf, zero or an fp32 subnormal; refactor "
+        "before using it");
   if (!_usable)
     throw std::runtime_error(
         "spmv::Ilu0Preconditioner - Error: the last factorisation met a pivot "
@@ -271,17 +293,31 @@ void Ilu0Preconditioner::numeric(const Matrix<double>& A)
     diagonal = _diag;
   }
   _usable = false;
+  _out_of_range = false;
   _negative = 0;
   spmv_hip_ctx* ctx = _exec.context();
   throw_on_error(spmv_hip_ilu0_factor(ctx, _ilu, blk->values(), diagonal, nullptr),
                  "spmv_hip_ilu0_factor");
-  int64_t bad = 0, negative = 0;
-  throw_on_error(spmv_hip_ilu0_pivots(ctx, _ilu, &bad, &negative, nullptr),
-                 "spmv_hip_ilu0_pivots");
+  int64_t bad = 0, negative = 0, out_of_range = 0;
+  if (_value_bits == 64)
+    throw_on_error(spmv_hip_ilu0_pivots(ctx, _ilu, &bad, &negative, nullptr),
+                   "spmv_hip_ilu0_pivots");
+  else // the same wait, one more count
+    throw_on_error(spmv_hip_ilu0_counts(ctx, _ilu, &bad, &negative, &out_of_range,
+                                        nullptr),
+                   "spmv_hip_ilu0_counts");
   if (bad != 0)
     throw std::runtime_error(
         "spmv::Ilu0Preconditioner - Error: " + std::to_string(bad) + " of "
         + std::to_string(rows()) + " pivot(s) are zero or not finite");
+  if (out_of_range != 0) {
+    _out_of_range = true;
+    throw std::runtime_error(
+        "spmv::Ilu0Preconditioner - Error: fp32 range: "
+        + std::to_string(out_of_range)
+        + " factor entries round to Inf, zero or an fp32 subnormal (values = "
+          "fp32)");
+  }
   _negative = negative;
   _usable = true;
 }

@@ -511,6 +511,14 @@ double ms_since(std::chrono::steady_clock::time_point t0)
       .count();
 }
 
+[[noreturn]] void throw_fp32_range(int64_t bad)
+{
+  throw std::runtime_error(
+      "spmv::SgsPreconditioner - Error: fp32 range: " + std::to_string(bad)
+      + " off-diagonal value(s) round to Inf, zero or an fp32 subnormal "
+        "(values = fp32)");
+}
+
 [[noreturn]] void throw_bad_diagonal(int64_t bad, int64_t n)
 {
   // jacobi_inverse's rule and message
@@ -524,7 +532,7 @@ double ms_since(std::chrono::steady_clock::time_point t0)
 SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A)
     : _exec(exec)
 {
-  build_on_host(A);
+  build_on_host(A, SgsValues::fp64);
 }
 
 SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A,
@@ -536,7 +544,7 @@ SgsPreconditioner::SgsPreconditioner(HipExecutor& exec, const Matrix<double>& A,
       throw std::invalid_argument(
           "spmv::SgsPreconditioner - Error: setup = host colours by itself: it "
           "takes neither colors nor an order");
-    build_on_host(A);
+    build_on_host(A, options.values);
     return;
   }
   try {
@@ -603,10 +611,24 @@ void SgsPreconditioner::build_on_device(const Matrix<double>& A,
   _color_ms = ms_since(t0);
 
   int64_t info[SPMV_HIP_MCGS_INFO_WORDS] = {};
-  const int rc = spmv_hip_mcgs_plan_build(
-      ctx, (int32_t)n, blk->cols(), nnz, rowptr, colind, values,
-      symmetric ? blk->diagonal() : nullptr, symmetric ? 1 : 0, d_colors.p,
-      num_colors, kSgsLongThreshold, &_plan, info, nullptr);
+  int64_t out_of_range = 0;
+  const int rc
+      = options.values == SgsValues::fp64
+            ? spmv_hip_mcgs_plan_build(
+                ctx, (int32_t)n, blk->cols(), nnz, rowptr, colind, values,
+                symmetric ? blk->diagonal() : nullptr, symmetric ? 1 : 0,
+                d_colors.p, num_colors, kSgsLongThreshold, &_plan, info, nullptr)
+            : spmv_hip_mcgs_plan_build_ex(
+                ctx, (int32_t)n, blk->cols(), nnz, rowptr, colind, values,
+                symmetric ? blk->diagonal() : nullptr, symmetric ? 1 : 0,
+                d_colors.p, num_colors, kSgsLongThreshold, 32, &_plan, info,
+                &out_of_range, nullptr);
+  // (a diagonal that is not positive is the older rule: it speaks first)
+  if (rc == SPMV_HIP_ERANGE && out_of_range != 0) {
+    if (info[0] != 0)
+      throw_bad_diagonal(info[0], n);
+    throw_fp32_range(out_of_range);
+  }
   if (rc == SPMV_HIP_EINVAL && info[1] == SPMV_HIP_MCGS_IMPROPER)
     throw std::runtime_error(
         "spmv::sgs_build - Error: the colouring is not proper (row "
@@ -623,12 +645,13 @@ void SgsPreconditioner::build_on_device(const Matrix<double>& A,
     throw_bad_diagonal(info[0], n);
   _num_colors = num_colors;
   _rows = (int)n;
+  _value_bits = options.values == SgsValues::fp32 ? 32 : 64;
   _temp_bytes = info[2];
   _setup_ms = ms_since(t0);
   _build_ms = _setup_ms - _color_ms;
 }
 
-void SgsPreconditioner::build_on_host(const Matrix<double>& A)
+void SgsPreconditioner::build_on_host(const Matrix<double>& A, SgsValues width)
 {
   const auto t0 = std::chrono::steady_clock::now();
   HipExecutor& exec = _exec;
@@ -690,8 +713,18 @@ void SgsPreconditioner::build_on_host(const Matrix<double>& A)
   in.dinv = dinv.data();
   in.before = part_of(before);
   in.after = part_of(after);
-  throw_on_error(spmv_hip_mcgs_plan_create(exec.context(), &in, &_plan),
-                 "spmv_hip_mcgs_plan_create");
+  if (width == SgsValues::fp64) {
+    throw_on_error(spmv_hip_mcgs_plan_create(exec.context(), &in, &_plan),
+                   "spmv_hip_mcgs_plan_create");
+  } else {
+    int64_t out_of_range = 0;
+    const int rc = spmv_hip_mcgs_plan_create_ex(exec.context(), &in, 32, &_plan,
+                                                &out_of_range);
+    if (rc == SPMV_HIP_ERANGE && out_of_range != 0)
+      throw_fp32_range(out_of_range);
+    throw_on_error(rc, "spmv_hip_mcgs_plan_create_ex");
+    _value_bits = 32;
+  }
   _num_colors = hp.num_colors;
   _colors = std::move(hp.colors);
   _rows = hp.n;

@@ -152,6 +152,9 @@ _PROTOS = {
     "spmvh_sgs_build_destroy": [vp],
     "spmvh_sgs_create": [vp, vp, PTR(vp)],
     "spmvh_sgs_create_ex": [vp, vp, C.c_int, C.c_int, vp, PTR(vp)],
+    "spmvh_sgs_create_ex2": [vp, vp, C.c_int, C.c_int, vp, C.c_int, PTR(vp)],
+    "spmvh_sgs_value_bits": [vp, PTR(C.c_int)],
+    "spmvh_fp32_range_count": [vp, i64, PTR(i64)],
     "spmvh_sgs_setup_info": [vp, PTR(C.c_int), PTR(f64)],
     "spmvh_sgs_setup_detail": [vp, PTR(f64), PTR(f64), PTR(i64)],
     "spmvh_sgs_export_sizes": [vp, vp],
@@ -179,6 +182,7 @@ _PROTOS = {
     "spmvh_ilu0_pattern": [vp, vp, vp, vp, vp],
     "spmvh_ilu0_factor": [vp, vp, vp, vp],
     "spmvh_ilu0_create_ex": [vp, vp, C.c_int, C.c_int, vp, PTR(vp)],
+    "spmvh_ilu0_create_ex2": [vp, vp, C.c_int, C.c_int, vp, C.c_int, PTR(vp)],
     "spmvh_ilu0_export_sizes": [vp, vp],
     "spmvh_ilu0_export": [vp, vp, vp],
     "spmvh_amg_check_options": [f64, C.c_int, i64, C.c_int, C.c_int, f64, f64],
@@ -1118,23 +1122,49 @@ class SgsPreconditioner:
     entry for entry; as many rounds as the longest ascending path of the
     pattern, slow on long dependency chains).  colors (device setup only):
     rows entries that replace the colouring, checked on the device ("not
-    proper", "colour").  setup="host" with an order or colors raises."""
+    proper", "colour").  setup="host" with an order or colors raises.
+
+    values="fp32" (with every setup, order and colors; "fp64" is the default
+    and the object as it ever was) keeps the sweep plan's off-diagonal values
+    as float, each rounded to nearest-even: a sweep streams 8 bytes per stored
+    entry, not 12, and plan_bytes() drops by 4 per stored entry.  dinv, r, z
+    and every operation stay fp64; M stays a fixed SPD operator every solver
+    takes as before.  A value that rounds to Inf, zero or an fp32 subnormal
+    raises SpmvHostError ("fp32 range"); any other string ValueError."""
 
     _SETUPS = {"host": 0, "device": 1}
     _ORDERS = {None: -1, "hashed": 0, "natural": 1}
+    _VALUES = {"fp64": 0, "fp32": 1}
+    _CREATE = "spmvh_sgs_create"
 
-    def __init__(self, exec_, A, setup="host", order=None, colors=None):
+    def __init__(self, exec_, A, setup="host", order=None, colors=None,
+                 values="fp64"):
+        if values not in self._VALUES:
+            raise ValueError(f"values {values!r}: 'fp64' or 'fp32'")
         h = vp()
-        if setup == "host" and order is None and colors is None:
-            call("spmvh_sgs_create", exec_.h, A.h, C.byref(h))
+        if (setup == "host" and order is None and colors is None
+                and values == "fp64"):
+            call(self._CREATE, exec_.h, A.h, C.byref(h))
         else:
             if setup not in self._SETUPS or order not in self._ORDERS:
                 raise ValueError(f"setup {setup!r} / order {order!r}")
             keep = (None if colors is None
                     else np.ascontiguousarray(colors, np.int32))
-            call("spmvh_sgs_create_ex", exec_.h, A.h, self._SETUPS[setup],
-                 self._ORDERS[order], _np_ptr(keep), C.byref(h))
+            if values == "fp64":
+                call(self._CREATE + "_ex", exec_.h, A.h, self._SETUPS[setup],
+                     self._ORDERS[order], _np_ptr(keep), C.byref(h))
+            else:
+                call(self._CREATE + "_ex2", exec_.h, A.h, self._SETUPS[setup],
+                     self._ORDERS[order], _np_ptr(keep), self._VALUES[values],
+                     C.byref(h))
         self.h = h
+
+    @property
+    def value_bits(self):
+        """64 or 32: the width of the sweep plan's off-diagonal values"""
+        bits = C.c_int()
+        call("spmvh_sgs_value_bits", self.h, C.byref(bits))
+        return bits.value
 
     def close(self):
         if self.h:
@@ -1210,6 +1240,16 @@ class SgsPreconditioner:
         return out
 
 
+def fp32_range_count(values):
+    """how many of the doubles are finite, non-zero and round to +-Inf, zero
+    or an fp32 subnormal: the rule by which values="fp32" refuses a value.
+    Host only."""
+    v = np.ascontiguousarray(values, np.float64)
+    count = i64()
+    call("spmvh_fp32_range_count", _np_ptr(v), v.size, C.byref(count))
+    return count.value
+
+
 def sgs_apply(exec_, M, r_ptr, z_ptr):
     """spmv::sgs_apply: z = M^-1 r on the executor's current stream; the host
     does not wait."""
@@ -1263,20 +1303,16 @@ class Ilu0Preconditioner(SgsPreconditioner):
     default) does the symbolic work on the host from the pattern read back;
     setup="device" colours the block and builds every array of the plan where
     the matrix lies (order="natural": the host-built object bit for bit).
-    setup="host" with an order or colors raises."""
+    setup="host" with an order or colors raises.
 
-    def __init__(self, exec_, A, setup="host", order=None, colors=None):
-        h = vp()
-        if setup == "host" and order is None and colors is None:
-            call("spmvh_ilu0_create", exec_.h, A.h, C.byref(h))
-        else:
-            if setup not in self._SETUPS or order not in self._ORDERS:
-                raise ValueError(f"setup {setup!r} / order {order!r}")
-            keep = (None if colors is None
-                    else np.ascontiguousarray(colors, np.int32))
-            call("spmvh_ilu0_create_ex", exec_.h, A.h, self._SETUPS[setup],
-                 self._ORDERS[order], _np_ptr(keep), C.byref(h))
-        self.h = h
+    values="fp32": the factorisation stays fp64 (factor(), pattern() and the
+    pivot counts do not change); l~ and u~ are rounded to float as they are
+    scattered into the sweep plan, dinv~ stays fp64, refactor() rounds again.
+    A factor entry out of fp32's range raises "fp32 range" from the
+    constructor and from refactor(); after such a refactor() the object raises
+    until a later one succeeds."""
+
+    _CREATE = "spmvh_ilu0_create"
 
     _ILU_KEYS = (("ptr", np.int64), ("cpos", np.int32), ("src", np.int32),
                  ("slot", np.int64))

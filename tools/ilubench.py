@@ -75,12 +75,12 @@ def run_case(case, args):
               None)
     exec_.synchronize()
     t0 = time.perf_counter()
-    M = host.Ilu0Preconditioner(exec_, A)
+    M = host.Ilu0Preconditioner(exec_, A, values=args.values)
     setup_ms = (time.perf_counter() - t0) * 1e3
     symbolic_ms, numeric_ms = M.setup_ms()
     refactor_ms = min(timed(lambda: M.refactor(A), args.repeats, args.warmup))
     t0 = time.perf_counter()
-    S = host.SgsPreconditioner(exec_, A)
+    S = host.SgsPreconditioner(exec_, A, values=args.values)
     sgs_setup_ms = (time.perf_counter() - t0) * 1e3
 
     def many(fn):
@@ -113,7 +113,7 @@ def run_case(case, args):
                          ms_to_solution=min(ms_sol),
                          final_rel_residual=float(h[-1] / h[0]),
                          converged=bool(h[-1] / h[0] < args.rtol))
-    rec = dict(case=case, rows=rows, nnz=nnz, iters=it, repeats=args.repeats,
+    rec = dict(case=case, values=args.values, rows=rows, nnz=nnz, iters=it, repeats=args.repeats,
                rtol=args.rtol, kmax=args.kmax, colors=M.num_colors(),
                negative_pivots=M.negative_pivots(), plan_bytes=M.plan_bytes(),
                sgs_plan_bytes=S.plan_bytes(), matrix_bytes=A.format_size(),
@@ -144,6 +144,8 @@ def main():
     ap.add_argument("--rtol", type=float, default=1e-10)
     ap.add_argument("--kmax", type=int, default=5000,
                     help="iteration limit of the solves to rtol")
+    ap.add_argument("--values", choices=("fp64", "fp32"), default="fp64",
+                    help="width of the sweep plans' values")
     ap.add_argument("--only", default=None, help="comma list of cases")
     ap.add_argument("--timeout", type=int, default=540, help="seconds per case")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles",
@@ -158,7 +160,8 @@ def main():
     p = None
     for case in cases:  # each GPU step under its own timeout, chained
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable,
-               os.path.abspath(__file__), "--case", case, "--n", str(args.n),
+               os.path.abspath(__file__), "--case", case, "--values", args.values,
+               "--n", str(args.n),
                "--rows", str(args.rows), "--iters", str(args.iters),
                "--repeats", str(args.repeats), "--warmup", str(args.warmup),
                "--apply-reps", str(args.apply_reps), "--rtol", str(args.rtol),

@@ -46,7 +46,7 @@ def run_case(case, args):
     A = make_matrix(case, args, comm, exec_, host, _lib)
     rows, nnz = A.rows(), A.non_zeros()
     try:
-        sgs = host.SgsPreconditioner(exec_, A)
+        sgs = host.SgsPreconditioner(exec_, A, values=args.values)
     except host.SpmvHostError as err:
         # the unstructured matrix has no positive diagonal: no SGS / ILU(0)
         # object exists for it and CG does not apply; recorded as it is
@@ -56,7 +56,7 @@ def run_case(case, args):
         comm.close()
         exec_.close()
         return
-    ilu = host.Ilu0Preconditioner(exec_, A)
+    ilu = host.Ilu0Preconditioner(exec_, A, values=args.values)
     ws1, wsb = host.SgsWorkspace(exec_), host.PcgBlockWorkspace(exec_)
     wsc = host.CgBlockWorkspace(exec_)
     for nrhs in [w for w in WIDTHS if not args.widths
@@ -70,7 +70,7 @@ def run_case(case, args):
         exec_.synchronize()
         B = exec_.copy_to_host(d_b, n).reshape(rows, nrhs)
         exec_.copy_from_host(d_s, np.ascontiguousarray(B.T))
-        rec = dict(case=case, rows=rows, nnz=nnz, nrhs=nrhs, repeats=args.repeats,
+        rec = dict(case=case, values=args.values, rows=rows, nnz=nnz, nrhs=nrhs, repeats=args.repeats,
                    colors=sgs.num_colors(), applies=args.applies)
 
         def sweeps_block():
@@ -149,6 +149,8 @@ def main():
                     help="applications of M per timed repeat")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--values", choices=("fp64", "fp32"), default="fp64",
+                    help="width of the sweep plans' values")
     ap.add_argument("--only", default=None, help="comma list of cases")
     ap.add_argument("--widths", default=None, help="comma list of nrhs")
     ap.add_argument("--timeout", type=int, default=500, help="seconds per case")
@@ -164,7 +166,8 @@ def main():
     p = None
     for case in cases:  # each GPU step under its own timeout, chained
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable,
-               os.path.abspath(__file__), "--case", case, "--n", str(args.n),
+               os.path.abspath(__file__), "--case", case, "--values", args.values,
+               "--n", str(args.n),
                "--rows", str(args.rows), "--kmax", str(args.kmax), "--applies",
                str(args.applies), "--repeats", str(args.repeats), "--warmup",
                str(args.warmup)]

@@ -77,7 +77,7 @@ def run_case(case, args):
               None)
     exec_.synchronize()
     t0 = time.perf_counter()
-    M = host.SgsPreconditioner(exec_, A)
+    M = host.SgsPreconditioner(exec_, A, values=args.values)
     setup_ms = (time.perf_counter() - t0) * 1e3
     estimate = host.lambda_max_estimate(comm, exec_, A, d_dinv, d_b, 20)
     lmax = 1.1 * estimate
@@ -97,6 +97,14 @@ def run_case(case, args):
         exec_.synchronize()
 
     apply_ms = min(timed(apply_many, args.repeats, args.warmup)) / args.apply_reps
+    fp64 = {}
+    if args.values == "fp32":  # the fp64 object next to it, in this process
+        M32, M = M, host.SgsPreconditioner(exec_, A)
+        fp64 = dict(sgs_apply_ms_fp64=min(timed(apply_many, args.repeats,
+                                                args.warmup)) / args.apply_reps,
+                    plan_bytes_fp64=M.plan_bytes())
+        M.close()
+        M = M32
     mult_ms = min(timed(mult_many, args.repeats, args.warmup)) / args.apply_reps
 
     def pcg(kmax, rtol):
@@ -132,7 +140,8 @@ def run_case(case, args):
                colors=colors, launches_per_apply=2 * colors - 1,
                plan_bytes=M.plan_bytes(), matrix_bytes=A.format_size(),
                setup_ms=setup_ms, sgs_apply_ms=apply_ms, mult_ms=mult_ms,
-               solvers=out, plan_forms=forms)
+               solvers=out, plan_forms=forms, values=args.values,
+               value_bits=M.value_bits, **fp64)
     print(json.dumps(rec), flush=True)
     ws_pcg.close(), ws_ch.close(), ws_sgs.close()
     M.close()
@@ -156,6 +165,9 @@ def main():
     ap.add_argument("--rtol", type=float, default=1e-10)
     ap.add_argument("--kmax", type=int, default=5000,
                     help="iteration limit of the solves to rtol")
+    ap.add_argument("--values", choices=("fp64", "fp32"), default="fp64",
+                    help="width of the sweep plan's values; fp32 also times "
+                         "the fp64 object's sgs_apply in the same process")
     ap.add_argument("--only", default=None, help="comma list of cases")
     ap.add_argument("--timeout", type=int, default=540, help="seconds per case")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles",
@@ -174,7 +186,7 @@ def main():
                "--rows", str(args.rows), "--iters", str(args.iters),
                "--repeats", str(args.repeats), "--warmup", str(args.warmup),
                "--apply-reps", str(args.apply_reps), "--rtol", str(args.rtol),
-               "--kmax", str(args.kmax)]
+               "--kmax", str(args.kmax), "--values", args.values]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(p.stdout)
         sys.stdout.flush()
